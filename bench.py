@@ -14,6 +14,11 @@ Multi-GPU (--gpus N via torch.distributed.run): channels shard across ranks
 per-channel block records are gathered to rank 0 with RCCL (the only exchange the
 path has).  value = samples processed by all ranks / max-over-ranks time.
 
+A plain run sets up, warms up (--warmup steps), times exactly --steps steps and prints the line; ms_per_step is the wall
+time of one timed step.  --full adds everything else the line can carry (roofline, roofline_valu, cpu_baseline, e2e,
+large_bank, frames_per_launch, paths), each measured after the timed region; without it those keys are null.
+--dump-outputs DIR writes what the last timed step delivered to its caller as DIR/<name>.npy (float32 / float64).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -77,6 +82,19 @@ def synth_dtmf_frames(n_ch, n_frames, device, seed):
         x = torch.clamp(torch.trunc(x), -32768, 32767).to(torch.int16)
         out[f0:f1] = x.view(n_ch, f1 - f0, FRAME).permute(1, 0, 2)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 or float64 only), 64 MB at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(frames_host, target_s):
@@ -388,13 +406,20 @@ def run_echo(args, engine, dev, local_rank, rank, world):
         allr = erle_dev.unsqueeze(0)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # the last step's clean frame (a seeded sample of 16 384 channels when there are more) and every channel's ERLE
+        pick = np.sort(np.random.default_rng(0xD0).choice(n_ch, min(n_ch, 16384), replace=False))
+        write_outputs(args.dump_outputs, {
+            "echo_clean": clean.cpu().numpy()[pick].astype(np.float32),
+            "echo_clean_channels": pick.astype(np.float64),
+            "echo_erle_db": allr[0].float().cpu().numpy()})
     quiet = (torch.arange(n_ch, device=dev) % 10 != 0)
     erle_single = allr[:, quiet].float()
     state_bytes = 48*4 + bp.ECHO_TAPS*4 + 4*bp.ECHO_TAPS*2 + bp.ECHO_TAPS*2
     alg_read = n_ch*(2*FRAME*2 + state_bytes)
     avg_ms = stream_ms/timed_steps
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         nc = min(4096, n_ch)
         cpu = bp.cpu_echo(tx[:60, :nc].contiguous().cpu().numpy(), rx[:60, :nc].contiguous().cpu().numpy())
     value = float(timed_steps)*n_ch*world*FRAME/dt/1e6
@@ -448,15 +473,19 @@ def main():
                     help="dtmf: BASELINE configs[1] (the headline); echo: BASELINE configs[4], one GPU's shard per rank "
                          "(131072 channels of the 128-tap echo canceller), ERLE of every channel gathered to rank 0 "
                          "once per second of signal")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline and roofline_valu, cpu_baseline, e2e, "
+                         "large_bank, frames_per_launch and paths (each can be left out again by the --no-* options below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed, as its caller receives it, to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out cpu_baseline")
     ap.add_argument("--cpu-channels", type=int, default=16384)
     ap.add_argument("--cpu-frames", type=int, default=40)
     ap.add_argument("--cpu-seconds", type=float, default=1.5, help="wall time of the all-core reference measurement")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="the timed region is repeated (whole multiples of --steps) until it lasts at least this long")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: leave out e2e and e2e_g711")
     ap.add_argument("--echo-seconds", type=int, default=10, help="--workload echo: seconds of continuous signal per line (first second untimed)")
-    ap.add_argument("--no-paths", action="store_true", help="leave out the `paths` object (BASELINE configs[2], [3], [4] at full size, ~40 s)")
+    ap.add_argument("--no-paths", action="store_true", help="--full: leave out the `paths` object (BASELINE configs[2], [3], [4] at full "
+                                                             "size, ~40 s), `large_bank` and `frames_per_launch`")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -549,25 +578,7 @@ def main():
 
     for i in range(args.warmup):
         step(i)
-    if gather is not None:
-        gather.drain()
-    torch.cuda.synchronize()
-    # A region of --steps launches of this kernel lasts a fraction of a millisecond: repeat it (whole multiples of
-    # --steps, `reps` of them) until the timed region is at least --min-timed-ms long.  Estimated on an untimed probe.
-    ev_a = torch.cuda.Event(enable_timing=True)
-    ev_b = torch.cuda.Event(enable_timing=True)
-    ev_a.record(stream)
-    for i in range(args.steps):
-        step(args.warmup + i)
-    ev_b.record(stream)
-    torch.cuda.synchronize()
-    probe_ms = max(ev_a.elapsed_time(ev_b), 1e-3)
-    reps = max(1, int(np.ceil(1.15*args.min_timed_ms/probe_ms)))      # (the probe runs cold: margin)
-    if world > 1:
-        r = torch.tensor([reps], device=dev, dtype=torch.int64)
-        dist.all_reduce(r, op=dist.ReduceOp.MAX)
-        reps = int(r.item())
-    timed_steps = args.steps*reps
+    timed_steps = args.steps
     if gather is not None:
         gather.drain()
     torch.cuda.synchronize()
@@ -598,12 +609,18 @@ def main():
     if gather is not None:
         bank.set_records_buffer(None, 0)
         bank.set_digits_buffer(None, 0)
+    if rank == 0 and args.dump_outputs:
+        # the block records of the last timed step (spangpu_bank_blocks(): what a caller of the bank reads back), before
+        # anything else runs on the bank
+        blk = bank.blocks()
+        write_outputs(args.dump_outputs, {"blocks_" + f: blk[f].astype(np.float32 if f == "energy" else np.float64)
+                                          for f in blk.dtype.names})
     # ---- roofline: the kernel's average launch duration = HIP events on the launch stream around the timed
     # region / launches in it (back-to-back launches of the one kernel; agrees with the rocprofv3 kernel average
     # in profiles/).  A second pass with an event pair around every launch gives the spread; each pair adds the
     # latency of two barrier packets, so its average reads ~2 us high and is reported as such. ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         k = min(args.steps, 200)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(k)]
         for i in range(k):
@@ -640,20 +657,20 @@ def main():
             rl_t.add_traffic(roof, "dtmf", n_ch)
 
     roof_valu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from spandsp_amd import roofline as rl
         rl.add_measured(roof, local_rank)
         roof["bound_note"] = ("graded against the HBM read roofline as north_star asks; at this bank size the launch is bound by "
                               "launch boundary + first-data latency + the VALU issue of the unfusable recurrence (roofline_valu, DESIGN 4.1)")
         roof_valu = rl.valu_roof("dtmf", roof["avg_launch_us"], channels=n_ch)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not law:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and not law:
         nc = min(args.cpu_channels, n_ch)
         host = frames[:min(args.cpu_frames, nf), :nc].contiguous().cpu().numpy()
         cpu = cpu_baseline(host, args.cpu_seconds)
     e2e = None
     e2e_g711 = None
-    if rank == 0 and world == 1 and not args.no_e2e and not law:
+    if rank == 0 and args.full and world == 1 and not args.no_e2e and not law:
         e2e = end_to_end(engine, n_ch, frames, local_rank, 60)
         # the same frames as u-law bytes (nearest code of the reference's decode table)
         tab = np.load(os.path.join(ROOT, "tests", "golden", "g711_decode.npz"))["ulaw"].astype(np.int32)
@@ -667,11 +684,11 @@ def main():
 
     large = None
     fpl = None
-    if rank == 0 and world == 1 and not args.no_paths and not law and n_ch == 65536:
+    if rank == 0 and args.full and world == 1 and not args.no_paths and not law and n_ch == 65536:
         large = large_banks(engine, dev, local_rank, frames, stream)
         fpl = frames_per_launch(engine, dev, local_rank, frames, stream)
     paths = None
-    if rank == 0 and world == 1 and not args.no_paths and not law:
+    if rank == 0 and args.full and world == 1 and not args.no_paths and not law:
         # BASELINE configs[2], [3], [4] under the same clock as the headline (tools/bench_paths.py: paths_for_bench)
         del frames
         torch.cuda.empty_cache()

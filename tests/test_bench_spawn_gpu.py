@@ -29,8 +29,7 @@ def run_bench(extra):
 
 
 def test_bench_starts_its_own_ranks_dtmf(built):
-    r = run_bench(["--steps", "50", "--warmup", "10", "--channels", "16384", "--no-cpu-baseline", "--no-e2e", "--no-paths",
-                   "--min-timed-ms", "5"])
+    r = run_bench(["--steps", "50", "--warmup", "10", "--channels", "16384", "--full", "--no-cpu-baseline", "--no-e2e", "--no-paths"])
     assert r["n_gpus"] == 1 and r["value"] > 0 and r["unit"] == "Msamples/s"
     assert r["roofline"]["frac"] > 0
 
@@ -47,5 +46,5 @@ def test_bench_with_a_bank_in_queue_mode_and_the_gather(built):
     """--queues 2 at 131 072 channels with the RCCL digit gather forced on: every collective is queued behind a
     spangpu_bank_join() (spandsp_amd/parallel.py), and the digits that arrive are checked by bench.py itself."""
     r = run_bench(["--steps", "50", "--warmup", "10", "--channels", "131072", "--queues", "2", "--distinct-frames", "30",
-                   "--no-cpu-baseline", "--no-e2e", "--no-paths", "--min-timed-ms", "5"])
+                   "--no-cpu-baseline", "--no-e2e", "--no-paths"])
     assert r["config"]["queues"] == 2 and r["value"] > 0

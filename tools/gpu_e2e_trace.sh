@@ -2,9 +2,10 @@
 cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT/gpurun_out/e2e
 rm -rf $R; mkdir -p $R
+BENCH=$PWD/bench.py
 export TMPDIR=/tmp
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $R/trace -- python $GRAFT_REPO_ROOT/bench.py --steps 40 --warmup 5 > $R/bench.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $R/trace -- python $BENCH --steps 40 --warmup 5 --full > $R/bench.log 2>&1
 cd $GRAFT_REPO_ROOT
 tail -1 $R/bench.log | cut -c1-400
 python3 - <<'PY'

@@ -9,10 +9,10 @@ export TMPDIR=/tmp
 R=$PWD/gpurun_out/r6
 mkdir -p $R
 FMA=$PWD/tools/experiments/libspangpu_fma.so
-python bench.py --no-cpu-baseline --no-e2e > $R/bench_exact.json 2> $R/bench_exact.err
-SPANGPU_LIB=$FMA python bench.py --no-cpu-baseline --no-e2e > $R/bench_fma.json 2> $R/bench_fma.err
-python bench.py --no-cpu-baseline --no-e2e > $R/bench_exact2.json 2>> $R/bench_exact.err
-SPANGPU_LIB=$FMA python bench.py --no-cpu-baseline --no-e2e > $R/bench_fma2.json 2>> $R/bench_fma.err
+python bench.py --full --no-cpu-baseline --no-e2e > $R/bench_exact.json 2> $R/bench_exact.err
+SPANGPU_LIB=$FMA python bench.py --full --no-cpu-baseline --no-e2e > $R/bench_fma.json 2> $R/bench_fma.err
+python bench.py --full --no-cpu-baseline --no-e2e > $R/bench_exact2.json 2>> $R/bench_exact.err
+SPANGPU_LIB=$FMA python bench.py --full --no-cpu-baseline --no-e2e > $R/bench_fma2.json 2>> $R/bench_fma.err
 python - <<'PY' | tee gpurun_out/r6/tone_levers.log
 import json
 def load(f):
