@@ -314,8 +314,9 @@ SPANGPU_API int spangpu_bank_cadence_set_state(spangpu_bank_t *bank, int channel
 /* Parity / diagnostics tap: per-block Goertzel energies of the last call, laid out
    [block][bin][channel] (bank created with trace=1).  Returns blocks-per-call. */
 SPANGPU_API int spangpu_bank_trace(spangpu_bank_t *bank, float *energies, size_t max_floats);
-/* Re-initialise one channel (what xxx_rx_init() on a live object does), or only
-   its filters (what dtmf_rx_fillin() does, dtmf.c:363-379) when fillin_only != 0. */
+/* Re-initialise one channel (what xxx_rx_init() on a live object does: a DTMF channel's
+   own dtmf_rx_parms() values go back to the bank's), or only its filters (what
+   dtmf_rx_fillin() does, dtmf.c:363-379) when fillin_only != 0. */
 SPANGPU_API int spangpu_bank_reset_channel(spangpu_bank_t *bank, int channel, int fillin_only);
 /* Import / export the device state of one channel as flat arrays (migration and
    differential tests).  Layout documented per kind in DESIGN.md. */

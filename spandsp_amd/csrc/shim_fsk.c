@@ -47,6 +47,7 @@ struct spangpu_line_group_s
     int n_attached;
     int n_staged;
     pthread_mutex_t lock;       /* staging, attach / detach and the tick itself (recursive: callbacks may call back in) */
+    int32_t *pristine;          /* a channel's words as the bank was created: what xxx_rx_init() leaves, default cutoff included */
 };
 
 static spangpu_line_group_t *group_new(int n_channels, int max_samples)
@@ -88,7 +89,9 @@ spangpu_line_group_t *spangpu_fsk_group_create(int device, const fsk_spec_t *spe
     g->spec.tx_level = spec->tx_level;
     g->spec.min_level = spec->min_level;
     g->spec.baud_rate = spec->baud_rate;
-    if (spangpu_fsk_create(&g->fsk, device, n_channels, &g->spec, framing_mode) != SPANGPU_OK)
+    if (spangpu_fsk_create(&g->fsk, device, n_channels, &g->spec, framing_mode) != SPANGPU_OK
+        ||  (g->pristine = (int32_t *) calloc(spangpu_fsk_state_words(g->fsk), sizeof(int32_t))) == NULL
+        ||  spangpu_fsk_get_state(g->fsk, 0, g->pristine) < 0)
     {
         spangpu_line_group_destroy(g);
         return NULL;
@@ -105,7 +108,9 @@ spangpu_line_group_t *spangpu_modem_connect_tones_group_create(int device, int t
         return NULL;
     g->is_mct = 1;
     g->tone_type = tone_type;
-    if (spangpu_mct_create(&g->mct, device, tone_type, n_channels, use_callbacks) != SPANGPU_OK)
+    if (spangpu_mct_create(&g->mct, device, tone_type, n_channels, use_callbacks) != SPANGPU_OK
+        ||  (g->pristine = (int32_t *) calloc(spangpu_mct_state_words(g->mct), sizeof(int32_t))) == NULL
+        ||  spangpu_mct_get_state(g->mct, 0, g->pristine) < 0)
     {
         spangpu_line_group_destroy(g);
         return NULL;
@@ -125,6 +130,7 @@ int spangpu_line_group_destroy(spangpu_line_group_t *g)
     free(g->handles);
     free(g->lens);
     free(g->run);
+    free(g->pristine);
     pthread_mutex_destroy(&g->lock);
     free(g);
     return 0;
@@ -313,6 +319,27 @@ static void line_detach(spangpu_line_group_t *g, int channel, int private_grp)
         spangpu_line_group_destroy(g);
 }
 
+/* Claim a slot for a new object: tested and taken under the group lock (two threads attaching the same slot: one wins).
+   On a shared bank the channel gets the words of a fresh receiver -- the slot may have served an earlier call whose object
+   was freed mid-signal, with a cutoff of its own (fsk.c:723-742 and modem_connect_tones.c:799-857 start from a memset()). */
+static int line_attach(spangpu_line_group_t *g, int channel, int private_grp, void *handle)
+{
+    int rc = 0;
+
+    pthread_mutex_lock(&g->lock);
+    if (g->handles[channel])
+        rc = -1;
+    else if (!private_grp)
+        rc = g->is_mct  ?  spangpu_mct_set_state(g->mct, channel, g->pristine)  :  spangpu_fsk_set_state(g->fsk, channel, g->pristine);
+    if (rc >= 0)
+    {
+        g->handles[channel] = handle;
+        g->n_attached++;
+    }
+    pthread_mutex_unlock(&g->lock);
+    return (rc < 0)  ?  -1  :  0;
+}
+
 /* ---- fsk_rx -------------------------------------------------------------------------------------------- */
 static fsk_rx_state_t *fsk_obj(fsk_rx_state_t *s, spangpu_line_group_t *g, int channel, int private_grp, span_put_bit_func_t put_bit,
                                void *user_data)
@@ -329,10 +356,12 @@ static fsk_rx_state_t *fsk_obj(fsk_rx_state_t *s, spangpu_line_group_t *g, int c
     s->private_grp = private_grp;
     s->put_bit = put_bit;
     s->put_bit_user_data = user_data;
-    pthread_mutex_lock(&g->lock);
-    g->handles[channel] = s;
-    g->n_attached++;
-    pthread_mutex_unlock(&g->lock);
+    if (line_attach(g, channel, private_grp, s) < 0)
+    {
+        if (!mine)
+            free(s);
+        return NULL;
+    }
     return s;
 }
 
@@ -350,7 +379,7 @@ fsk_rx_state_t *fsk_rx_init(fsk_rx_state_t *s, const fsk_spec_t *spec, int frami
 
 fsk_rx_state_t *spangpu_fsk_rx_attach(spangpu_line_group_t *g, int channel, span_put_bit_func_t put_bit, void *user_data)
 {
-    if (g == NULL  ||  g->is_mct  ||  channel < 0  ||  channel >= g->n_ch  ||  g->handles[channel])
+    if (g == NULL  ||  g->is_mct  ||  channel < 0  ||  channel >= g->n_ch)
         return NULL;
     return fsk_obj(NULL, g, channel, 0, put_bit, user_data);
 }
@@ -489,10 +518,12 @@ static modem_connect_tones_rx_state_t *mct_obj(modem_connect_tones_rx_state_t *s
     s->private_grp = private_grp;
     s->tone_callback = tone_callback;
     s->callback_data = user_data;
-    pthread_mutex_lock(&g->lock);
-    g->handles[channel] = s;
-    g->n_attached++;
-    pthread_mutex_unlock(&g->lock);
+    if (line_attach(g, channel, private_grp, s) < 0)
+    {
+        if (!mine)
+            free(s);
+        return NULL;
+    }
     return s;
 }
 
@@ -512,7 +543,7 @@ modem_connect_tones_rx_state_t *modem_connect_tones_rx_init(modem_connect_tones_
 modem_connect_tones_rx_state_t *spangpu_modem_connect_tones_rx_attach(spangpu_line_group_t *g, int channel,
                                                                       span_tone_report_func_t tone_callback, void *user_data)
 {
-    if (g == NULL  ||  !g->is_mct  ||  channel < 0  ||  channel >= g->n_ch  ||  g->handles[channel])
+    if (g == NULL  ||  !g->is_mct  ||  channel < 0  ||  channel >= g->n_ch)
         return NULL;
     return mct_obj(NULL, g, channel, 0, tone_callback, user_data);
 }

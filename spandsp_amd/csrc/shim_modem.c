@@ -32,6 +32,7 @@ struct spangpu_modem_group_s
     int n_staged;
     pthread_mutex_t lock;       /* staging, attach / detach and the tick itself (recursive: callbacks may call back in) */
     int qam_tap;                /* some object of the group has a qam report handler: the bank records the reports */
+    uint32_t *pristine;         /* a channel's words as the bank was created: what xxx_rx_init() leaves, default cutoff included */
 };
 
 typedef struct
@@ -86,6 +87,7 @@ spangpu_modem_group_t *spangpu_modem_group_create(int device, int kind, int n_ch
     g->handles = (void **) calloc(n_channels, sizeof(void *));
     g->lens = (int32_t *) calloc(n_channels, sizeof(int32_t));
     g->run = (int32_t *) calloc(n_channels, sizeof(int32_t));
+    g->pristine = (uint32_t *) calloc(MAX_WORDS, sizeof(uint32_t));
     {
         pthread_mutexattr_t at;
 
@@ -94,8 +96,9 @@ spangpu_modem_group_t *spangpu_modem_group_create(int device, int kind, int n_ch
         pthread_mutex_init(&g->lock, &at);
         pthread_mutexattr_destroy(&at);
     }
-    if (g->stage == NULL  ||  g->handles == NULL  ||  g->lens == NULL  ||  g->run == NULL
-        ||  spangpu_modem_create(&g->bank, device, kind, n_channels, bit_rate) != SPANGPU_OK)
+    if (g->stage == NULL  ||  g->handles == NULL  ||  g->lens == NULL  ||  g->run == NULL  ||  g->pristine == NULL
+        ||  spangpu_modem_create(&g->bank, device, kind, n_channels, bit_rate) != SPANGPU_OK
+        ||  spangpu_modem_get_state(g->bank, 0, g->pristine) < 0)
     {
         spangpu_modem_group_destroy(g);
         return NULL;
@@ -113,6 +116,7 @@ int spangpu_modem_group_destroy(spangpu_modem_group_t *g)
     free(g->handles);
     free(g->lens);
     free(g->run);
+    free(g->pristine);
     pthread_mutex_destroy(&g->lock);
     free(g);
     return 0;
@@ -246,6 +250,18 @@ int spangpu_modem_group_flush(spangpu_modem_group_t *g)
     return rc;
 }
 
+static void obj_logging_init(modem_obj_t *o)
+{
+    /* what span_log_init(.., SPAN_LOG_NONE, NULL) + span_log_set_protocol() leave behind (v29rx.c:1120-1121 and twins) */
+    memset(&o->logging, 0, sizeof(o->logging));
+    o->logging.samples_per_second = 8000;
+    o->logging.protocol = (o->kind == SPANGPU_V29)  ?  "V.29 RX"  :  (o->kind == SPANGPU_V27TER)  ?  "V.27ter RX"  :  "V.17 RX";
+}
+
+/* A new object on a free slot of the group.  The slot is tested and claimed under the group lock (two threads attaching
+   the same slot: one wins), and its channel gets the words of a fresh receiver -- the slot may have served an earlier
+   call, whose object was freed mid-signal with its own cutoff: the reference's xxx_rx_init() starts from a memset()
+   struct whatever the storage held (v29rx.c:1100-1131). */
 static modem_obj_t *obj_new(size_t size, int kind, spangpu_modem_group_t *g, int channel, int private_grp, int bit_rate,
                             span_put_bit_func_t put_bit, void *user_data)
 {
@@ -260,12 +276,16 @@ static modem_obj_t *obj_new(size_t size, int kind, spangpu_modem_group_t *g, int
     o->bit_rate = bit_rate;
     o->put_bit = put_bit;
     o->put_bit_user_data = user_data;
-    /* what span_log_init(.., SPAN_LOG_NONE, NULL) + span_log_set_protocol() leave behind (v29rx.c:1120-1121 and twins) */
-    memset(&o->logging, 0, sizeof(o->logging));
-    o->logging.samples_per_second = 8000;
-    o->logging.protocol = (kind == SPANGPU_V29)  ?  "V.29 RX"  :  (kind == SPANGPU_V27TER)  ?  "V.27ter RX"  :  "V.17 RX";
+    obj_logging_init(o);
     spangpu_modem_state_words(kind, &o->n_floats, NULL);
     pthread_mutex_lock(&g->lock);
+    if (g->handles[channel]
+        ||  (!private_grp  &&  spangpu_modem_set_state(g->bank, channel, g->pristine) < 0))
+    {
+        pthread_mutex_unlock(&g->lock);
+        free(o);
+        return NULL;
+    }
     g->handles[channel] = o;
     g->n_attached++;
     pthread_mutex_unlock(&g->lock);
@@ -290,7 +310,7 @@ static modem_obj_t *obj_init(size_t size, int kind, int bit_rate, span_put_bit_f
 static modem_obj_t *obj_attach(size_t size, int kind, spangpu_modem_group_t *g, int channel,
                                span_put_bit_func_t put_bit, void *user_data)
 {
-    if (g == NULL  ||  g->kind != kind  ||  channel < 0  ||  channel >= g->n_ch  ||  g->handles[channel])
+    if (g == NULL  ||  g->kind != kind  ||  channel < 0  ||  channel >= g->n_ch)
         return NULL;
     return obj_new(size, kind, g, channel, 0, g->bit_rate, put_bit, user_data);
 }
@@ -420,6 +440,30 @@ static int obj_restart(modem_obj_t *o, int bit_rate, int flag)
     return (spangpu_modem_restart_ex(g->bank, o->channel, bit_rate, flag) < 0)  ?  -1  :  0;
 }
 
+/* xxx_rx_init(s, ...) on a live private object: everything as a fresh init leaves it, which is not what a restart leaves
+   (a restart keeps the cutoff, the saved training and more).  The callbacks and handlers go; a change of rate of a
+   V.27ter / V.17 object moves it to a bank of the new rate first.  A V.29 bank keeps the words of its creation rate:
+   v29_rx_init() at another rate is those words and a restart at that rate (v29rx.c:1100-1131). */
+static int obj_reinit(modem_obj_t *o, int bit_rate)
+{
+    spangpu_modem_group_t *g;
+
+    if (o->qam_report)
+        obj_set_qam(o, NULL, NULL);
+    o->status_handler = NULL;
+    o->status_user_data = NULL;
+    obj_logging_init(o);
+    if (o->kind != SPANGPU_V29  &&  bit_rate != o->grp->bit_rate  &&  obj_restart(o, bit_rate, 0) < 0)
+        return -1;
+    g = o->grp;
+    o->bit_rate = bit_rate;
+    if (spangpu_modem_set_state(g->bank, o->channel, g->pristine) < 0)
+        return -1;
+    if (bit_rate != g->bit_rate  &&  spangpu_modem_restart_ex(g->bank, o->channel, bit_rate, 0) < 0)
+        return -1;
+    return 0;
+}
+
 static const uint32_t *obj_words(modem_obj_t *o)
 {
     if (spangpu_modem_get_state(o->grp->bank, o->channel, o->words) < 0)
@@ -458,12 +502,10 @@ T *pfx##_init(T *s, int bit_rate, span_put_bit_func_t put_bit, void *user_data) 
         /* re-initialise in place (the reference memset()s the caller's struct) */                                   \
         if (!rate_ok(KIND, bit_rate)  ||  !s->o.private_grp)                                                         \
             return NULL;                                                                                             \
+        if (obj_reinit(&s->o, bit_rate) < 0)                                                                         \
+            return NULL;                                                                                             \
         s->o.put_bit = put_bit;                                                                                      \
         s->o.put_bit_user_data = user_data;                                                                          \
-        s->o.status_handler = NULL;                                                                                  \
-        if (obj_restart(&s->o, bit_rate, 0) < 0)                                                                     \
-            return NULL;                                                                                             \
-        spangpu_modem_set_signal_cutoff(s->o.grp->bank, 0, (KIND == SPANGPU_V29)  ?  -28.5f  :  -45.5f);             \
         return s;                                                                                                    \
     }                                                                                                                \
     o = obj_init(sizeof(T), KIND, bit_rate, put_bit, user_data);                                                     \

@@ -1875,7 +1875,23 @@ int spangpu_bank_reset_channel(spangpu_bank_t *b, int channel, int fillin_only)
     w[0] = 0;
     if (!fillin_only)
         w[1] = w[2] = w[3] = 0;
-    return spangpu_bank_set_state(b, channel, f, b->nsf, w, 4);
+    rc = spangpu_bank_set_state(b, channel, f, b->nsf, w, 4);
+    if (rc < 0  ||  fillin_only  ||  b->h_chan_parms == nullptr)
+        return rc;
+    // A full reset is an init: the thresholds, twists and dial-tone filter an earlier dtmf_rx_parms() gave this channel go
+    // back to the bank's (dtmf.c:447-504 sets them afresh), as ensure_chan_parms() first laid them out.
+    const size_t n = (size_t) b->n_ch;
+    float *h = b->h_chan_parms;
+    const float on = b->tp.filter_dialtone  ?  1.0f  :  0.0f;
+    b->n_filter_on += (int) on - (int) h[3*n + channel];
+    h[channel] = b->threshold;
+    h[n + channel] = b->normal_twist;
+    h[2*n + channel] = b->reverse_twist;
+    h[3*n + channel] = on;
+    for (int i = 0;  i < 4;  i++)
+        HIP_TRY(hipMemcpyAsync(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice, joined(b)));
+    HIP_TRY(hipStreamSynchronize(joined(b)));
+    return SPANGPU_OK;
 }
 
 }   // extern "C"
