@@ -400,8 +400,9 @@ void v29_bank_kernel(const V29Launch L)
         }
         else
         {
-            int re = (int) ((zre + 5.0f)*2.0f);
-            int im = (int) ((zim + 5.0f)*2.0f);
+            // (the reference's (int): NaN and out of range -> INT32_MIN, sliced to the edge at 0 -- a runaway equaliser's point)
+            int re = v29_f2i((zre + 5.0f)*2.0f);
+            int im = v29_f2i((zim + 5.0f)*2.0f);
             re = max(0, min(19, re));
             im = max(0, min(19, im));
             nearest = t_map[re*20 + im];
