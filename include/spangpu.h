@@ -362,6 +362,19 @@ SPANGPU_API int spangpu_echo_update(spangpu_echo_t *ec, const int16_t *tx, const
    caller has to send to the line when ECHO_CAN_USE_TX_HPF is set (src/echo.c:663-669). */
 SPANGPU_API int spangpu_echo_update_tx(spangpu_echo_t *ec, const int16_t *tx, const int16_t *rx, int16_t *clean, int16_t *tx_out,
                                        int mem, int samples, long long stride, int use_hpf_tx);
+/* A tick in which every channel has a length of its own: channel c advances lens[c] samples, 0 <= lens[c] <= max_samples,
+   exactly as lens[c] calls of echo_can_update() would -- after echo_can_hpf_tx() where use_hpf_tx[c] is set (NULL: nowhere).
+   A channel whose length is 0 sits the tick out: its state, taps, history and statistics stay as they are and its clean /
+   tx_out rows are not written.  lens and use_hpf_tx are host arrays whatever `mem` says of the sample rows; rows start at
+   c*stride (stride <= 0: max_samples).  Statistics count the samples a channel ran.  The channels that take part are run by
+   one launch per distinct (length, flag) pair; a bank in step -- one non-zero length and one flag throughout -- is the
+   spangpu_echo_update_tx() call.  Returns the number of channels that took part, or a negative SPANGPU_ERR_*. */
+SPANGPU_API int spangpu_echo_update_var(spangpu_echo_t *ec, const int16_t *tx, const int16_t *rx, int16_t *clean, int16_t *tx_out,
+                                        int mem, const int32_t *lens, const uint8_t *use_hpf_tx, int max_samples, long long stride);
+/* One channel: echo_can_hpf_tx() over `samples` host samples (out may alias tx), and the state echo_can_init(taps,
+   adaption_mode) makes -- a slot that a new line takes over (its statistics start again too). */
+SPANGPU_API int spangpu_echo_hpf_tx_channel(spangpu_echo_t *ec, int channel, const int16_t *tx, int16_t *out, int samples);
+SPANGPU_API int spangpu_echo_reset_channel(spangpu_echo_t *ec, int channel, int adaption_mode);
 /* echo_can_hpf_tx() on its own, for callers that filter tx before they have the matching rx (host buffers). */
 /* Tuning / A-B testing: lanes per channel of echo banks created from now on (0 = by length, 4, 8 or 16); results are identical. */
 SPANGPU_API int spangpu_tune_echo_lanes_per_channel(int lanes);

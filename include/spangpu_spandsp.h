@@ -192,8 +192,10 @@ enum
 
 typedef struct echo_can_state_s echo_can_state_t;
 
-/* len (taps) must be 32, 64, 128 or 256.  echo_can_update() is one kernel launch per sample: source compatibility only;
-   use spangpu_echo_can_update_block() (one object, n samples) or spangpu_echo_update() (N channels) for throughput. */
+/* len (taps) must be a power of two from 32 to 1024.  An object made by echo_can_init() is a one-channel bank of its own:
+   echo_can_update() is one kernel launch per sample and spangpu_echo_can_update_block() one launch per object -- source
+   compatibility.  For throughput attach the objects to an echo group (spangpu_echo_can_attach(), below: N objects on one
+   launch per tick), or hand the rows of N channels to spangpu_echo_update() / spangpu_echo_update_var(). */
 SPANGPU_API echo_can_state_t *echo_can_init(int len, int adaption_mode);
 SPANGPU_API int echo_can_release(echo_can_state_t *ec);
 SPANGPU_API int echo_can_free(echo_can_state_t *ec);
@@ -216,6 +218,33 @@ SPANGPU_API int16_t echo_can_hpf_tx(echo_can_state_t *ec, int16_t tx)
 SPANGPU_API int spangpu_echo_can_update_block(echo_can_state_t *ec, const int16_t tx[], const int16_t rx[], int16_t clean[],
                                               int16_t tx_out[], int n, int use_hpf_tx);
 SPANGPU_API spangpu_echo_t *spangpu_echo_can_bank(echo_can_state_t *ec);
+
+/* ---- echo canceller groups: N echo_can_state_t objects on one bank, one launch per tick -------------------------------
+   spangpu_echo_can_attach() makes the object of one channel of the group: what echo_can_init(taps, adaption_mode) makes,
+   also in a slot that another object has used before.  On an attached object
+     spangpu_echo_can_update_block(ec, tx, rx, clean, tx_out, n, use_hpf_tx)
+   copies tx / rx into the group's staging rows, REMEMBERS clean and tx_out, and returns SPANGPU_OK (n <= 0: 0, nothing is
+   staged; n > max_samples: SPANGPU_ERR_BAD_ARG; a second frame before the tick ran: SPANGPU_ERR_STATE, the staged frame is
+   kept).  The tick runs inside the call that completes the set -- every attached object has staged -- or in
+   spangpu_echo_group_flush(), with the objects that have staged; the others sit it out, exactly as they were.  Frames of a
+   tick may differ in length and in use_hpf_tx.  When the call that ran the tick returns, clean[] (and tx_out[]) of every
+   object that took part are filled and its spangpu_echo_can_pending() is 0: THE CALLER KEEPS clean / tx_out VALID UNTIL
+   THEN.  An object has one submitter; the objects of a group may be staged from different threads (one mutex per group,
+   the tick runs on the thread that completes it).
+   echo_can_flush(), echo_can_adaption_mode(), echo_can_snapshot(), spangpu_echo_can_snapshot_taps() and
+   spangpu_echo_can_bank() (the group's bank) act on the object's channel alone and in call order: if the object has a frame
+   pending, the tick runs first.  echo_can_update() / echo_can_hpf_tx() on an attached object stay correct -- pending work
+   runs, then a launch over that one channel -- and stay slow.  echo_can_free() detaches: a pending frame is dropped, its
+   buffers are not written, the slot may be attached again. */
+typedef struct spangpu_echo_group_s spangpu_echo_group_t;
+SPANGPU_API spangpu_echo_group_t *spangpu_echo_group_create(int device, int n_channels, int taps, int max_samples);
+SPANGPU_API int spangpu_echo_group_destroy(spangpu_echo_group_t *g);
+/* Run the tick with what is staged.  Returns the number of channels that took part, or a negative SPANGPU_ERR_*. */
+SPANGPU_API int spangpu_echo_group_flush(spangpu_echo_group_t *g);
+SPANGPU_API long long spangpu_echo_group_ticks(const spangpu_echo_group_t *g);      /* ticks run so far */
+SPANGPU_API spangpu_echo_t *spangpu_echo_group_bank(spangpu_echo_group_t *g);
+SPANGPU_API echo_can_state_t *spangpu_echo_can_attach(spangpu_echo_group_t *g, int channel, int adaption_mode);
+SPANGPU_API int spangpu_echo_can_pending(echo_can_state_t *ec);                     /* 1 while a staged frame has not run */
 
 /* ---- channel groups: N spandsp objects on one GPU bank ----------------------------- */
 typedef struct spangpu_group_s spangpu_group_t;

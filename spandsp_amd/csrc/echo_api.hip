@@ -51,6 +51,13 @@ struct spangpu_echo_s
     int uniform_mode;       // the adaption mode every channel has, or -1 when they differ: picks the kernel compiled for that mode
     bool mode_dirty;        // a single channel's mode was written since the channels were last compared: they may all agree again
     int *d_span;            // two ints of device scratch for that comparison (made with the bank: nothing is allocated or freed in the update path)
+    // spangpu_echo_update_var(): the slot -> channel lists of a tick's launches, one after the other (made at its first call)
+    int32_t *h_chan;        // [n_ch], host
+    int32_t *d_chan;        // [n_ch], device
+    int32_t *h_off;         // first slot of every (samples, use_hpf_tx) key, [h_off_cap]
+    size_t h_off_cap;
+    int16_t *h_io;          // pinned: the compacted rows of host callers, [4][n_ch][h_io_cap] as d_io
+    size_t h_io_cap;
 };
 
 __global__ void echo_set_scalar_kernel(int32_t *scal, int lo, int hi, int idx, int value)
@@ -112,6 +119,113 @@ static void init_scalars(int32_t *s, int taps, int mode)
 }
 
 static std::atomic<int> g_echo_group{0};      // spangpu_tune_echo_lanes_per_channel(): process-wide, read once at bank creation
+
+// Room for `samples` samples per channel in the staging rows of host callers.  The rows in use stay until the larger ones
+// exist; only when the device cannot hold both are they given up first, and a failure then leaves no rows and a
+// capacity of zero -- never a pointer to freed memory.
+static int echo_io_reserve(spangpu_echo_t *e, size_t samples)
+{
+    if (samples <= e->io_cap)
+        return SPANGPU_OK;
+    int16_t *p = nullptr;
+    const size_t bytes = (size_t) 4*e->n_ch*samples*sizeof(int16_t);
+    if (hipMalloc(&p, bytes) != hipSuccess)
+    {
+        (void) hipGetLastError();
+        p = nullptr;
+        if (e->d_io)
+        {
+            (void) hipStreamSynchronize(e->stream);
+            (void) hipFree(e->d_io);
+            e->d_io = nullptr;
+            e->io_cap = 0;
+            if (hipMalloc(&p, bytes) != hipSuccess)
+                p = nullptr;
+        }
+        if (p == nullptr)
+        {
+            (void) hipGetLastError();
+            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "hipMalloc of the echo staging rows failed");
+        }
+    }
+    if (e->d_io)
+    {
+        (void) hipStreamSynchronize(e->stream);
+        (void) hipFree(e->d_io);
+    }
+    e->d_io = p;
+    e->io_cap = samples;
+    return SPANGPU_OK;
+}
+
+// One launch of the update kernel this bank runs -- its lane mapping, its length, the kernel compiled for the mode all its
+// channels have where there is one -- over the L.n_ch channels, or slots, of L.
+static void echo_launch(spangpu_echo_t *e, const EchoLaunch &L)
+{
+    const int per_wave = 64/e->group;
+    const int waves = (L.n_ch + per_wave - 1)/per_wave;
+    const int blocks = (waves + 3)/4;
+    if (e->group == 2)
+    {
+        switch (e->tpl)
+        {
+        case 16: hipLaunchKernelGGL(echo_pair_kernel<16>, dim3(blocks), dim3(256), 0, e->stream, L); break;
+        case 32: hipLaunchKernelGGL(echo_pair_kernel<32>, dim3(blocks), dim3(256), 0, e->stream, L); break;
+        default: hipLaunchKernelGGL(echo_pair_kernel<64>, dim3(blocks), dim3(256), 0, e->stream, L); break;
+        }
+    }
+    else if (e->group == 4)
+    {
+        switch (e->tpl)
+        {
+        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 4>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        case 16: hipLaunchKernelGGL((echo_bank_kernel<16, 4>), dim3(blocks), dim3(256), 0, e->stream, L); break;
+        default:
+            // the kernels compiled for one mode: the three echo_tests.c runs its lines in (adaption alone is SURVEY 8(d)-5's,
+            // and what a bank has until somebody changes it); any other mode, or lines of different modes: the general one
+            if (e->uniform_mode == kModeAdaption)
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
+            else if (e->uniform_mode == (kModeAdaption | kModeNlp))
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp>), dim3(blocks), dim3(256), 0, e->stream, L);
+            else if (e->uniform_mode == (kModeAdaption | kModeNlp | kModeCng))
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp | kModeCng>), dim3(blocks), dim3(256), 0, e->stream, L);
+            else
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4>), dim3(blocks), dim3(256), 0, e->stream, L);
+            break;
+        }
+    }
+    else if (e->group == 8)
+    {
+        switch (e->tpl)
+        {
+        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 8>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 8>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        default:
+            if (e->uniform_mode == kModeAdaption)
+                hipLaunchKernelGGL((echo_bank_kernel<16, 8, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
+            else
+                hipLaunchKernelGGL((echo_bank_kernel<16, 8>), dim3(blocks), dim3(256), 0, e->stream, L);
+            break;
+        }
+    }
+    else
+    {
+        switch (e->tpl)
+        {
+        case 2:  hipLaunchKernelGGL((echo_bank_kernel<2, 16>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 16>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        case 8:
+            if (e->uniform_mode == kModeAdaption)
+                hipLaunchKernelGGL((echo_bank_kernel<8, 16, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
+            else
+                hipLaunchKernelGGL((echo_bank_kernel<8, 16>), dim3(blocks), dim3(256), 0, e->stream, L);
+            break;
+        case 32: hipLaunchKernelGGL((echo_bank_kernel<32, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
+        case 64: hipLaunchKernelGGL((echo_bank_kernel<64, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
+        default: hipLaunchKernelGGL((echo_bank_kernel<16, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
+        }
+    }
+}
 
 extern "C" {
 
@@ -227,6 +341,10 @@ int spangpu_echo_destroy(spangpu_echo_t *e)
     if (e->stats) (void) hipFree(e->stats);
     if (e->d_erle) (void) hipFree(e->d_erle);
     if (e->d_span) (void) hipFree(e->d_span);
+    if (e->d_chan) (void) hipFree(e->d_chan);
+    if (e->h_io) (void) hipHostFree(e->h_io);
+    free(e->h_chan);
+    free(e->h_off);
     if (e->own_stream  &&  e->stream)
         (void) hipStreamDestroy(e->stream);
     free(e);
@@ -288,14 +406,8 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
     memset(&L, 0, sizeof(L));
     if (mem == SPANGPU_MEM_HOST)
     {
-        if ((size_t) samples > e->io_cap)
-        {
-            if (e->d_io) (void) hipFree(e->d_io);
-            e->d_io = nullptr;
-            e->io_cap = 0;
-            ECHO_TRY(hipMalloc(&e->d_io, (size_t) 4*e->n_ch*samples*sizeof(int16_t)));
-            e->io_cap = samples;
-        }
+        if (echo_io_reserve(e, (size_t) samples) != SPANGPU_OK)
+            return SPANGPU_ERR_NO_MEMORY;
         int16_t *dtx = e->d_io;
         int16_t *drx = e->d_io + (size_t) e->n_ch*e->io_cap;
         int16_t *dcl = e->d_io + (size_t) 2*e->n_ch*e->io_cap;
@@ -331,74 +443,12 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
     L.taps16 = e->taps16;
     L.hist = e->hist;
     L.stats = (e->stats_on == 2)  ?  e->stats  :  nullptr;
-    const int per_wave = 64/e->group;
-    const int waves = (e->n_ch + per_wave - 1)/per_wave;
-    const int blocks = (waves + 3)/4;
-    if (e->group == 2)
-    {
-        switch (e->tpl)
-        {
-        case 16: hipLaunchKernelGGL(echo_pair_kernel<16>, dim3(blocks), dim3(256), 0, e->stream, L); break;
-        case 32: hipLaunchKernelGGL(echo_pair_kernel<32>, dim3(blocks), dim3(256), 0, e->stream, L); break;
-        default: hipLaunchKernelGGL(echo_pair_kernel<64>, dim3(blocks), dim3(256), 0, e->stream, L); break;
-        }
-    }
-    else if (e->group == 4)
-    {
-        switch (e->tpl)
-        {
-        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 4>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 16: hipLaunchKernelGGL((echo_bank_kernel<16, 4>), dim3(blocks), dim3(256), 0, e->stream, L); break;
-        default:
-            // the kernels compiled for one mode: the three echo_tests.c runs its lines in (adaption alone is SURVEY 8(d)-5's,
-            // and what a bank has until somebody changes it); any other mode, or lines of different modes: the general one
-            if (e->uniform_mode == kModeAdaption)
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
-            else if (e->uniform_mode == (kModeAdaption | kModeNlp))
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp>), dim3(blocks), dim3(256), 0, e->stream, L);
-            else if (e->uniform_mode == (kModeAdaption | kModeNlp | kModeCng))
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp | kModeCng>), dim3(blocks), dim3(256), 0, e->stream, L);
-            else
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4>), dim3(blocks), dim3(256), 0, e->stream, L);
-            break;
-        }
-    }
-    else if (e->group == 8)
-    {
-        switch (e->tpl)
-        {
-        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 8>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 8>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        default:
-            if (e->uniform_mode == kModeAdaption)
-                hipLaunchKernelGGL((echo_bank_kernel<16, 8, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
-            else
-                hipLaunchKernelGGL((echo_bank_kernel<16, 8>), dim3(blocks), dim3(256), 0, e->stream, L);
-            break;
-        }
-    }
-    else
-    {
-        switch (e->tpl)
-        {
-        case 2:  hipLaunchKernelGGL((echo_bank_kernel<2, 16>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 16>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 8:
-            if (e->uniform_mode == kModeAdaption)
-                hipLaunchKernelGGL((echo_bank_kernel<8, 16, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
-            else
-                hipLaunchKernelGGL((echo_bank_kernel<8, 16>), dim3(blocks), dim3(256), 0, e->stream, L);
-            break;
-        case 32: hipLaunchKernelGGL((echo_bank_kernel<32, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
-        case 64: hipLaunchKernelGGL((echo_bank_kernel<64, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
-        default: hipLaunchKernelGGL((echo_bank_kernel<16, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
-        }
-    }
+    echo_launch(e, L);
     ECHO_TRY(hipGetLastError());
     if (e->stats_on == 1)
     {
         hipLaunchKernelGGL(echo_stats_kernel, dim3((e->n_ch + 255)/256), dim3(256), 0, e->stream,
-                           L.rx, (const int16_t *) L.clean, L.stride, samples, e->n_ch, e->stats);
+                           L.rx, (const int16_t *) L.clean, L.stride, samples, e->n_ch, e->stats, (const int32_t *) nullptr, 0);
         ECHO_TRY(hipGetLastError());
     }
     if (mem == SPANGPU_MEM_HOST)
@@ -413,6 +463,205 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
     return 0;
 }
 
+// A tick in which every channel has a length of its own (include/spangpu.h).  The channels that take part are sorted by
+// (samples, use_hpf_tx) into slot -> channel lists, one launch over each list (EchoLaunch::chan): the per-sample body of the
+// kernels never sees a length that is not its wave's.  A bank in step -- one length, one flag, nobody missing -- is the plain
+// spangpu_echo_update_tx() call, list-free.
+int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t *rx, int16_t *clean, int16_t *tx_out,
+                            int mem, const int32_t *lens, const uint8_t *use_hpf_tx, int max_samples, long long stride)
+{
+    if (e == nullptr  ||  tx == nullptr  ||  rx == nullptr  ||  clean == nullptr  ||  lens == nullptr  ||  max_samples < 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    if (mem != SPANGPU_MEM_HOST  &&  mem != SPANGPU_MEM_DEVICE)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
+    if (stride <= 0)
+        stride = max_samples;
+    const int N = e->n_ch;
+    int taking_part = 0;
+    int longest = 0;
+    bool in_step = true;
+    const int flag0 = (use_hpf_tx  &&  use_hpf_tx[0])  ?  1  :  0;
+    for (int c = 0;  c < N;  c++)
+    {
+        if (lens[c] < 0  ||  lens[c] > max_samples)
+            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0 .. max_samples");
+        if (lens[c] > 0)
+        {
+            taking_part++;
+            if (lens[c] > longest)
+                longest = lens[c];
+        }
+        if (lens[c] != lens[0]  ||  (((use_hpf_tx  &&  use_hpf_tx[c])  ?  1  :  0) != flag0))
+            in_step = false;
+    }
+    if (taking_part == 0)
+        return 0;
+    if (in_step)
+    {
+        const int rc = spangpu_echo_update_tx(e, tx, rx, clean, tx_out, mem, lens[0], stride, flag0);
+        return (rc < 0)  ?  rc  :  N;
+    }
+    if (stride < longest)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "rows overlap: stride is shorter than a channel's length");
+    ECHO_TRY(hipSetDevice(e->device));
+    // ---- the lists: a counting sort of the channels by key = 2*samples + flag, channel order kept within a key ----------
+    const size_t n_keys = (size_t) 2*(longest + 1);
+    auto key_of = [&](int c) { return 2*lens[c] + ((use_hpf_tx  &&  use_hpf_tx[c])  ?  1  :  0); };
+    if (e->h_chan == nullptr  &&  (e->h_chan = (int32_t *) malloc((size_t) N*sizeof(int32_t))) == nullptr)
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
+    if (e->d_chan == nullptr  &&  hipMalloc(&e->d_chan, (size_t) N*sizeof(int32_t)) != hipSuccess)
+    {
+        e->d_chan = nullptr;
+        (void) hipGetLastError();
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "hipMalloc of the channel lists failed");
+    }
+    if (n_keys + 1 > e->h_off_cap)
+    {
+        int32_t *p = (int32_t *) malloc((n_keys + 1)*sizeof(int32_t));
+        if (p == nullptr)
+            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
+        free(e->h_off);
+        e->h_off = p;
+        e->h_off_cap = n_keys + 1;
+    }
+    int32_t *off = e->h_off;
+    memset(off, 0, (n_keys + 1)*sizeof(int32_t));
+    for (int c = 0;  c < N;  c++)
+    {
+        if (lens[c] > 0)
+            off[key_of(c) + 1]++;
+    }
+    for (size_t k = 0;  k < n_keys;  k++)
+        off[k + 1] += off[k];           // off[k] .. off[k + 1]: the slots of key k
+    if (mem == SPANGPU_MEM_HOST)
+    {
+        if (echo_io_reserve(e, (size_t) longest) != SPANGPU_OK)
+            return SPANGPU_ERR_NO_MEMORY;
+        if ((size_t) longest > e->h_io_cap)
+        {
+            int16_t *p = nullptr;
+            if (hipHostMalloc((void **) &p, (size_t) 4*N*longest*sizeof(int16_t), hipHostMallocDefault) != hipSuccess)
+            {
+                (void) hipGetLastError();
+                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "hipHostMalloc of the compacted rows failed");
+            }
+            if (e->h_io)
+            {
+                (void) hipStreamSynchronize(e->stream);
+                (void) hipHostFree(e->h_io);
+            }
+            e->h_io = p;
+            e->h_io_cap = longest;
+        }
+    }
+    // The rows of host callers are compacted as the lists are made: slot s of the tick has row s of h_io / d_io, `cap`
+    // samples apart.  Device callers' rows are used where they are (EchoLaunch::chan_rows).
+    const size_t cap = e->h_io_cap;
+    int16_t *const htx = e->h_io;
+    int16_t *const hrx = e->h_io + (size_t) N*cap;
+    int16_t *const hcl = e->h_io + (size_t) 2*N*cap;
+    int16_t *const hto = e->h_io + (size_t) 3*N*cap;
+    {
+        // (off[] is advanced while the channels are dealt out, and put back)
+        for (int c = 0;  c < N;  c++)
+        {
+            if (lens[c] <= 0)
+                continue;
+            const int slot = off[key_of(c)]++;
+            e->h_chan[slot] = c;
+            if (mem == SPANGPU_MEM_HOST)
+            {
+                memcpy(htx + (size_t) slot*cap, tx + (size_t) c*stride, (size_t) lens[c]*sizeof(int16_t));
+                memcpy(hrx + (size_t) slot*cap, rx + (size_t) c*stride, (size_t) lens[c]*sizeof(int16_t));
+            }
+        }
+        for (size_t k = n_keys;  k > 0;  k--)
+            off[k] = off[k - 1];
+        off[0] = 0;
+    }
+    ECHO_TRY(hipMemcpyAsync(e->d_chan, e->h_chan, (size_t) taking_part*sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    int16_t *dtx = nullptr;
+    int16_t *drx = nullptr;
+    int16_t *dcl = nullptr;
+    int16_t *dto = nullptr;
+    if (mem == SPANGPU_MEM_HOST)
+    {
+        // (d_io's rows are io_cap apart, which may be more than cap: both are addressed with their own pitch)
+        dtx = e->d_io;
+        drx = e->d_io + (size_t) N*e->io_cap;
+        dcl = e->d_io + (size_t) 2*N*e->io_cap;
+        dto = e->d_io + (size_t) 3*N*e->io_cap;
+        ECHO_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), htx, cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                  taking_part, hipMemcpyHostToDevice, e->stream));
+        ECHO_TRY(hipMemcpy2DAsync(drx, e->io_cap*sizeof(int16_t), hrx, cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                  taking_part, hipMemcpyHostToDevice, e->stream));
+    }
+    if (e->mode_dirty)
+        refresh_uniform_mode(e);
+    // ---- one launch per key that has channels -----------------------------------------------------------------------------
+    for (size_t k = 2;  k < n_keys;  k++)
+    {
+        const int first = off[k];
+        const int n = off[k + 1] - first;
+        if (n <= 0)
+            continue;
+        EchoLaunch L;
+        memset(&L, 0, sizeof(L));
+        if (mem == SPANGPU_MEM_HOST)
+        {
+            L.tx = dtx + (size_t) first*e->io_cap;
+            L.rx = drx + (size_t) first*e->io_cap;
+            L.clean = dcl + (size_t) first*e->io_cap;
+            L.tx_out = tx_out  ?  (dto + (size_t) first*e->io_cap)  :  nullptr;
+            L.stride = (long long) e->io_cap;
+            L.chan_rows = 0;
+        }
+        else
+        {
+            L.tx = tx;
+            L.rx = rx;
+            L.clean = clean;
+            L.tx_out = tx_out;
+            L.stride = stride;
+            L.chan_rows = 1;
+        }
+        L.chan = e->d_chan + first;
+        L.samples = (int) (k >> 1);
+        L.n_ch = n;
+        L.use_hpf_tx = (int) (k & 1);
+        L.scal = e->scal;
+        L.taps32 = e->taps32;
+        L.taps16 = e->taps16;
+        L.hist = e->hist;
+        L.stats = (e->stats_on == 2)  ?  e->stats  :  nullptr;
+        echo_launch(e, L);
+        ECHO_TRY(hipGetLastError());
+        if (e->stats_on == 1)
+        {
+            hipLaunchKernelGGL(echo_stats_kernel, dim3((n + 255)/256), dim3(256), 0, e->stream,
+                               L.rx, (const int16_t *) L.clean, L.stride, L.samples, n, e->stats, L.chan, L.chan_rows);
+            ECHO_TRY(hipGetLastError());
+        }
+    }
+    if (mem == SPANGPU_MEM_HOST)
+    {
+        ECHO_TRY(hipMemcpy2DAsync(hcl, cap*sizeof(int16_t), dcl, e->io_cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                  taking_part, hipMemcpyDeviceToHost, e->stream));
+        if (tx_out)
+            ECHO_TRY(hipMemcpy2DAsync(hto, cap*sizeof(int16_t), dto, e->io_cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                      taking_part, hipMemcpyDeviceToHost, e->stream));
+        ECHO_TRY(hipStreamSynchronize(e->stream));
+        for (int slot = 0;  slot < taking_part;  slot++)
+        {
+            const int c = e->h_chan[slot];
+            memcpy(clean + (size_t) c*stride, hcl + (size_t) slot*cap, (size_t) lens[c]*sizeof(int16_t));
+            if (tx_out)
+                memcpy(tx_out + (size_t) c*stride, hto + (size_t) slot*cap, (size_t) lens[c]*sizeof(int16_t));
+        }
+    }
+    return taking_part;
+}
+
 // echo_can_hpf_tx() for every channel, separately from the update (the spandsp calling sequence: tx' = hpf_tx(tx), send
 // tx' to the line, later clean = update(tx', rx)).  Host buffers only; out may alias tx.
 int spangpu_echo_hpf_tx(spangpu_echo_t *e, const int16_t *tx, int16_t *out, int samples, long long stride)
@@ -424,14 +673,8 @@ int spangpu_echo_hpf_tx(spangpu_echo_t *e, const int16_t *tx, int16_t *out, int 
     if (stride <= 0)
         stride = samples;
     ECHO_TRY(hipSetDevice(e->device));
-    if ((size_t) samples > e->io_cap)
-    {
-        if (e->d_io) (void) hipFree(e->d_io);
-        e->d_io = nullptr;
-        e->io_cap = 0;
-        ECHO_TRY(hipMalloc(&e->d_io, (size_t) 4*e->n_ch*samples*sizeof(int16_t)));
-        e->io_cap = samples;
-    }
+    if (echo_io_reserve(e, (size_t) samples) != SPANGPU_OK)
+        return SPANGPU_ERR_NO_MEMORY;
     int16_t *dtx = e->d_io;
     int16_t *dout = e->d_io + (size_t) 3*e->n_ch*e->io_cap;
     ECHO_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), tx, stride*sizeof(int16_t), samples*sizeof(int16_t),
@@ -769,6 +1012,53 @@ int spangpu_echo_flush(spangpu_echo_t *e, int channel)
     ECHO_TRY(hipMemset(e->taps32 + (size_t) channel*T, 0, T*sizeof(int32_t)));
     ECHO_TRY(hipMemset(e->taps16 + (size_t) channel*4*T, 0, 4*T*sizeof(int16_t)));
     ECHO_TRY(hipMemset(e->hist + (size_t) channel*T, 0, T*sizeof(int16_t)));
+    return SPANGPU_OK;
+}
+
+// echo_can_hpf_tx() for one channel of the bank (host buffers; out may alias tx): an object attached to an echo group
+int spangpu_echo_hpf_tx_channel(spangpu_echo_t *e, int channel, const int16_t *tx, int16_t *out, int samples)
+{
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch  ||  tx == nullptr  ||  out == nullptr  ||  samples < 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    if (samples == 0)
+        return 0;
+    ECHO_TRY(hipSetDevice(e->device));
+    if (echo_io_reserve(e, (size_t) samples) != SPANGPU_OK)
+        return SPANGPU_ERR_NO_MEMORY;
+    int16_t *dtx = e->d_io;
+    int16_t *dout = e->d_io + (size_t) 3*e->n_ch*e->io_cap;
+    ECHO_TRY(hipMemcpyAsync(dtx, tx, samples*sizeof(int16_t), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(echo_hpf_tx_kernel, dim3(1), dim3(64), 0, e->stream, dtx, dout, (long long) e->io_cap,
+                       samples, 1, e->scal + (size_t) channel*kEchoScalars);
+    ECHO_TRY(hipGetLastError());
+    ECHO_TRY(hipMemcpyAsync(out, dout, samples*sizeof(int16_t), hipMemcpyDeviceToHost, e->stream));
+    ECHO_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// One channel back to what echo_can_init(taps, adaption_mode) makes (echo.c:254-301): a slot of an echo group that a new
+// call takes over
+int spangpu_echo_reset_channel(spangpu_echo_t *e, int channel, int adaption_mode)
+{
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    ECHO_TRY(hipSetDevice(e->device));
+    ECHO_TRY(hipStreamSynchronize(e->stream));
+    const int T = e->taps;
+    int32_t s[kEchoScalars];
+    init_scalars(s, T, adaption_mode);
+    e->mode_dirty = true;
+    if (adaption_mode != e->uniform_mode  &&  e->n_ch > 1)
+        e->uniform_mode = -1;
+    else
+        e->uniform_mode = adaption_mode;
+    ECHO_TRY(hipMemcpyAsync(e->scal + (size_t) channel*kEchoScalars, s, sizeof(s), hipMemcpyHostToDevice, e->stream));
+    ECHO_TRY(hipMemsetAsync(e->taps32 + (size_t) channel*T, 0, T*sizeof(int32_t), e->stream));
+    ECHO_TRY(hipMemsetAsync(e->taps16 + (size_t) channel*4*T, 0, 4*T*sizeof(int16_t), e->stream));
+    ECHO_TRY(hipMemsetAsync(e->hist + (size_t) channel*T, 0, T*sizeof(int16_t), e->stream));
+    if (e->stats)
+        ECHO_TRY(hipMemsetAsync(e->stats + channel, 0, sizeof(EchoStats), e->stream));
+    ECHO_TRY(hipStreamSynchronize(e->stream));
     return SPANGPU_OK;
 }
 

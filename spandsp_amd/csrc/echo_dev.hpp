@@ -89,6 +89,12 @@ struct EchoLaunch
     int16_t *taps16;            // [n_ch][4][T]
     int16_t *hist;              // [n_ch][T], window order: hist[i] = history[(i + curr_pos) mod T]
     EchoStats *stats;           // [n_ch] or nullptr: the update kernel itself adds the frame's energy sums (no second pass)
+    // A launch over a subset of the bank (spangpu_echo_update_var()).  chan == nullptr: slot s of the launch is channel s, as
+    // ever.  Otherwise n_ch counts the launch's SLOTS, and slot s works on bank channel chan[s] -- scalars, taps, history and
+    // statistics -- on I/O row s of compact buffers, or, with chan_rows set, on row chan[s] of buffers that hold every
+    // channel of the bank (a caller's device buffers, used where they are).  No channel may appear twice in a list.
+    const int32_t *chan;
+    int chan_rows;
 };
 
 __device__ __forceinline__ int echo_hpf(int32_t &c0, int32_t &c1, int amp)
@@ -386,7 +392,9 @@ void echo_bank_kernel(const EchoLaunch L)
     const int j = lane%G;
     const int ch_raw = ((blockIdx.x*4 + wv)*kChPerWave) + g;
     const bool live = ch_raw < L.n_ch;
-    const int ch = live  ?  ch_raw  :  (L.n_ch - 1);
+    const int slot = live  ?  ch_raw  :  (L.n_ch - 1);
+    const int ch = L.chan  ?  L.chan[slot]  :  slot;       // the channel whose state this is ...
+    const int row = L.chan_rows  ?  ch  :  slot;           // ... and the row its samples are in (EchoLaunch)
     const bool leader = live  &&  (j == 0);
 
     int32_t *sc = L.scal + (size_t) ch*kEchoScalars;
@@ -563,10 +571,10 @@ void echo_bank_kernel(const EchoLaunch L)
         // Rows that allow it (16-byte aligned: every frame a caller's 160-sample rows lie in) move 16 bytes -- eight samples -- at
         // a time, in and out; a sample per lane and instruction, as this was, is a two-byte access a lane, which the memory side
         // serves as 32-byte partial accesses (profiles/r5_hbm_calibration.json).  Ragged ends and unaligned rows: a sample at a time.
-        const int16_t *const txrow = L.tx + (size_t) ch*L.stride + base;
-        const int16_t *const rxrow = L.rx + (size_t) ch*L.stride + base;
-        int16_t *const cleanrow = L.clean + (size_t) ch*L.stride + base;
-        int16_t *const txoutrow = L.tx_out  ?  (L.tx_out + (size_t) ch*L.stride + base)  :  nullptr;
+        const int16_t *const txrow = L.tx + (size_t) row*L.stride + base;
+        const int16_t *const rxrow = L.rx + (size_t) row*L.stride + base;
+        int16_t *const cleanrow = L.clean + (size_t) row*L.stride + base;
+        int16_t *const txoutrow = L.tx_out  ?  (L.tx_out + (size_t) row*L.stride + base)  :  nullptr;
         const bool vec = ((L.stride & 7) == 0)
                          &&  ((((uintptr_t) L.tx | (uintptr_t) L.rx | (uintptr_t) L.clean | (uintptr_t) L.tx_out) & 15) == 0);
         const int nvec = vec  ?  (n & ~7)  :  0;
@@ -1272,7 +1280,8 @@ void echo_hpf_tx_kernel(const int16_t *tx, int16_t *out, long long stride, int s
 // int16 little-endian stream) of everything the canceller has put out, for bit-exactness checks against the CPU path.
 // The frame was written a moment ago by echo_bank_kernel and is read from L2; the CRC table sits in LDS.
 __global__ __launch_bounds__(256)
-void echo_stats_kernel(const int16_t *rx, const int16_t *clean, long long stride, int samples, int n_ch, EchoStats *st)
+void echo_stats_kernel(const int16_t *rx, const int16_t *clean, long long stride, int samples, int n_ch, EchoStats *st,
+                       const int32_t *chan, int chan_rows)
 {
     __shared__ uint32_t table[256];
     {
@@ -1282,13 +1291,15 @@ void echo_stats_kernel(const int16_t *rx, const int16_t *clean, long long stride
         table[threadIdx.x] = c;
     }
     __syncthreads();
-    const int ch = blockIdx.x*256 + threadIdx.x;
-    if (ch >= n_ch)
+    const int slot = blockIdx.x*256 + threadIdx.x;
+    if (slot >= n_ch)
         return;
+    const int ch = chan  ?  chan[slot]  :  slot;           // as in the update kernel (EchoLaunch)
+    const int row = chan_rows  ?  ch  :  slot;
     EchoStats s = st[ch];
     uint32_t crc = ~s.crc;
-    const int16_t *r = rx + (size_t) ch*stride;
-    const int16_t *c = clean + (size_t) ch*stride;
+    const int16_t *r = rx + (size_t) row*stride;
+    const int16_t *c = clean + (size_t) row*stride;
     auto one = [&](int a, int b)
     {
         s.sum_rx2 += (unsigned long long) (a*a);

@@ -127,7 +127,9 @@ void echo_pair_kernel(const EchoLaunch L)
     const int j = lane & 1;
     const int ch_raw = ((blockIdx.x*4 + wv)*kChPerWave) + g;
     const bool live = ch_raw < L.n_ch;
-    const int ch = live  ?  ch_raw  :  (L.n_ch - 1);
+    const int slot = live  ?  ch_raw  :  (L.n_ch - 1);
+    const int ch = L.chan  ?  L.chan[slot]  :  slot;       // the channel whose state this is ...
+    const int row = L.chan_rows  ?  ch  :  slot;           // ... and the row its samples are in (EchoLaunch)
     const bool leader = live  &&  (j == 0);
     short *bounce = &bounce_all[wv][g][0];
     float *acfbuf = &acf_all[wv][g][0];
@@ -324,8 +326,8 @@ void echo_pair_kernel(const EchoLaunch L)
         unsigned long long st_part = 0;                     // this lane's share of the pass's received energy (L.stats)
         for (int i = j;  i < n;  i += G)
         {
-            const int a = (uint16_t) L.tx[(size_t) ch*L.stride + base + i];
-            const int b = (uint16_t) L.rx[(size_t) ch*L.stride + base + i];
+            const int a = (uint16_t) L.tx[(size_t) row*L.stride + base + i];
+            const int b = (uint16_t) L.rx[(size_t) row*L.stride + base + i];
             io[wv][g][i] = a | (b << 16);
             st_part += (unsigned long long) ((int) (short) b*(int) (short) b);
         }
@@ -635,10 +637,10 @@ void echo_pair_kernel(const EchoLaunch L)
             for (int i = j;  i < n;  i += G)
             {
                 const int word = io[wv][g][i];
-                L.clean[(size_t) ch*L.stride + base + i] = (int16_t) (word & 0xFFFF);
+                L.clean[(size_t) row*L.stride + base + i] = (int16_t) (word & 0xFFFF);
                 cl_part += (unsigned long long) ((int) (short) (word & 0xFFFF)*(int) (short) (word & 0xFFFF));
                 if (L.tx_out)
-                    L.tx_out[(size_t) ch*L.stride + base + i] = (int16_t) (word >> 16);
+                    L.tx_out[(size_t) row*L.stride + base + i] = (int16_t) (word >> 16);
             }
         }
         if (L.stats)

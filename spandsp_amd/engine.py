@@ -292,6 +292,27 @@ def lib():
             "spangpu_echo_flush": (ci, [vp, ci]),
             "spangpu_echo_get_state": (ci, [vp, ci, vp, vp, vp, vp]),
             "spangpu_echo_set_state": (ci, [vp, ci, vp, vp, vp, vp]),
+            "spangpu_echo_update_tx": (ci, [vp, vp, vp, vp, vp, ci, ci, ll, ci]),
+            "spangpu_echo_update_var": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, ll]),
+            "spangpu_echo_hpf_tx_channel": (ci, [vp, ci, vp, vp, ci]),
+            "spangpu_echo_reset_channel": (ci, [vp, ci, ci]),
+            # include/spangpu_spandsp.h: echo canceller objects and their groups
+            "spangpu_echo_group_create": (vp, [ci, ci, ci, ci]),
+            "spangpu_echo_group_destroy": (ci, [vp]),
+            "spangpu_echo_group_flush": (ci, [vp]),
+            "spangpu_echo_group_ticks": (ll, [vp]),
+            "spangpu_echo_group_bank": (vp, [vp]),
+            "spangpu_echo_can_attach": (vp, [vp, ci, ci]),
+            "spangpu_echo_can_pending": (ci, [vp]),
+            "spangpu_echo_can_update_block": (ci, [vp, vp, vp, vp, vp, ci, ci]),
+            "spangpu_echo_can_snapshot_taps": (ci, [vp, vp, ci]),
+            "spangpu_echo_can_bank": (vp, [vp]),
+            "echo_can_free": (ci, [vp]),
+            "echo_can_flush": (None, [vp]),
+            "echo_can_adaption_mode": (None, [vp, ci]),
+            "echo_can_snapshot": (None, [vp]),
+            "echo_can_update": (C.c_int16, [vp, C.c_int16, C.c_int16]),
+            "echo_can_hpf_tx": (C.c_int16, [vp, C.c_int16]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -1105,6 +1126,37 @@ class EchoBank:
     def update_device(self, tx_ptr, rx_ptr, clean_ptr, samples, stride, use_hpf_tx=False):
         _check(lib().spangpu_echo_update(self.h, tx_ptr, rx_ptr, clean_ptr, MEM_DEVICE, samples, stride, int(use_hpf_tx)))
 
+    def update_var_host(self, tx, rx, lens, use_hpf_tx=None, clean=None, tx_out=None):
+        """A tick in which channel c advances lens[c] samples of its rows (0: it sits the tick out).  tx, rx: [n][max_samples];
+        use_hpf_tx: per-channel flags or None.  Returns (clean, channels that took part); rows of channels that sat out, and
+        samples past a channel's length, are as they were in the `clean` / `tx_out` arrays handed in (fresh ones: zero)."""
+        tx = np.ascontiguousarray(tx, np.int16)
+        rx = np.ascontiguousarray(rx, np.int16)
+        assert tx.shape == rx.shape and tx.shape[0] == self.n
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert lens.shape == (self.n,)
+        flags = None if use_hpf_tx is None else np.ascontiguousarray(use_hpf_tx, np.uint8)
+        if clean is None:
+            clean = np.zeros_like(tx)
+        assert clean.shape == tx.shape and clean.dtype == np.int16 and clean.flags.c_contiguous
+        if tx_out is not None:
+            assert tx_out.shape == tx.shape and tx_out.dtype == np.int16 and tx_out.flags.c_contiguous
+        n = _check(lib().spangpu_echo_update_var(self.h, tx.ctypes.data, rx.ctypes.data, clean.ctypes.data,
+                                                 None if tx_out is None else tx_out.ctypes.data, MEM_HOST, lens.ctypes.data,
+                                                 None if flags is None else flags.ctypes.data, tx.shape[1], tx.shape[1]))
+        return clean, n
+
+    def update_var_device(self, tx_ptr, rx_ptr, clean_ptr, tx_out_ptr, lens, use_hpf_tx, max_samples, stride):
+        """As update_var_host() on rows that are in HBM (lens and use_hpf_tx stay host arrays); asynchronous on the bank's stream."""
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert lens.shape == (self.n,)
+        flags = None if use_hpf_tx is None else np.ascontiguousarray(use_hpf_tx, np.uint8)
+        return _check(lib().spangpu_echo_update_var(self.h, tx_ptr, rx_ptr, clean_ptr, tx_out_ptr, MEM_DEVICE, lens.ctypes.data,
+                                                    None if flags is None else flags.ctypes.data, max_samples, stride))
+
+    def reset_channel(self, channel, adaption_mode):
+        _check(lib().spangpu_echo_reset_channel(self.h, channel, adaption_mode))
+
     def adaption_mode(self, mode, channel=-1):
         _check(lib().spangpu_echo_adaption_mode(self.h, channel, mode))
 
@@ -1144,6 +1196,96 @@ class EchoBank:
         d["taps16"] = t16.reshape(4, self.taps)
         d["history"] = h
         return d
+
+
+class _GroupBank(EchoBank):
+    """The bank of an echo group, seen through EchoBank's methods; the group owns it."""
+
+    def __init__(self, handle, n_channels, taps):
+        self.n = n_channels
+        self.taps = taps
+        self.h = C.c_void_p(handle)
+
+    def close(self):
+        self.h = C.c_void_p()
+
+
+class EchoCan:
+    """An echo_can_state_t attached to an EchoGroup (include/spangpu_spandsp.h): the spandsp-named calls on one channel."""
+
+    def __init__(self, group, channel, adaption_mode):
+        self.group = group
+        self.channel = channel
+        self.p = lib().spangpu_echo_can_attach(group.h, channel, adaption_mode)
+        if not self.p:
+            raise SpanGpuError(-5, "spangpu_echo_can_attach(channel %d) failed" % channel)
+
+    def update_block(self, tx, rx, clean, tx_out=None, use_hpf_tx=False):
+        """Stage a frame; clean (and tx_out) are int16 arrays the caller keeps until the tick has run.  Returns the C result."""
+        tx = np.ascontiguousarray(tx, np.int16)
+        rx = np.ascontiguousarray(rx, np.int16)
+        assert len(tx) == len(rx) and clean.dtype == np.int16 and len(clean) >= len(tx)
+        return lib().spangpu_echo_can_update_block(self.p, tx.ctypes.data, rx.ctypes.data, clean.ctypes.data,
+                                                   None if tx_out is None else tx_out.ctypes.data, len(tx), int(use_hpf_tx))
+
+    def pending(self):
+        return lib().spangpu_echo_can_pending(self.p)
+
+    def update(self, tx, rx):
+        return int(lib().echo_can_update(self.p, int(tx), int(rx)))
+
+    def hpf_tx(self, tx):
+        return int(lib().echo_can_hpf_tx(self.p, int(tx)))
+
+    def flush(self):
+        lib().echo_can_flush(self.p)
+
+    def adaption_mode(self, mode):
+        lib().echo_can_adaption_mode(self.p, mode)
+
+    def snapshot_taps(self):
+        lib().echo_can_snapshot(self.p)
+        out = np.zeros(self.group.taps, np.int16)
+        n = lib().spangpu_echo_can_snapshot_taps(self.p, out.ctypes.data, len(out))
+        return out[:n]
+
+    def bank_handle(self):
+        return lib().spangpu_echo_can_bank(self.p)
+
+    def free(self):
+        if self.p:
+            lib().echo_can_free(self.p)
+            self.p = None
+
+
+class EchoGroup:
+    """N echo_can_state_t objects on one bank and one launch per tick (spangpu_echo_group_*)."""
+
+    def __init__(self, n_channels, taps, max_samples, device=0):
+        self.n = n_channels
+        self.taps = taps
+        self.max_samples = max_samples
+        self.h = lib().spangpu_echo_group_create(device, n_channels, taps, max_samples)
+        if not self.h:
+            code = -1 if device_count() <= 0 else -2
+            raise SpanGpuError(code, lib().spangpu_last_error().decode("latin1"))
+        self.bank = _GroupBank(lib().spangpu_echo_group_bank(self.h), n_channels, taps)
+
+    def attach(self, channel, adaption_mode):
+        return EchoCan(self, channel, adaption_mode)
+
+    def flush(self):
+        return _check(lib().spangpu_echo_group_flush(self.h))
+
+    def ticks(self):
+        return int(lib().spangpu_echo_group_ticks(self.h))
+
+    def close(self):
+        """(after the attached objects have been freed)"""
+        if self.h:
+            self.bank.close()
+            lib().spangpu_echo_group_destroy(self.h)
+            self.h = None
 
 
 V29 = 6

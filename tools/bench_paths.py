@@ -500,6 +500,96 @@ def echo_spot_check(tx64, rx64, clean64):
             "bit_exact": bool(ok)}
 
 
+def bench_echo_group(args, dev, stream):
+    """Echo canceller ticks with per-channel lengths (spangpu_echo_update_var(), device rows) and the echo group path, on the
+    lines of the `echo` workload: (plain) spangpu_echo_update() as `--workload echo` times it, (a) every length 160 -- the
+    same launch by the in-step condition --, (b) a random tenth of the channels sitting each tick out, (c) the lengths split
+    50 / 50 between 80 and 160, (d) tests/c_callers/echo_group.c staging that many objects from 1 and from 16 threads.  Each
+    of (plain) .. (c): a bank of its own, one second of warm-up, then `repeats` timed stretches of `steps` ticks between HIP
+    events; the median and the spread of the stretches are reported.  Nothing here is a pass / fail number."""
+    import re
+    import subprocess
+    import tempfile
+    from spandsp_amd import engine
+    n_ch = args.channels or 131072
+    steps = 40                          # (a tick of 131 072 lines is 84 MB of tx and rx on the device: 250 ticks are resident)
+    repeats = 5
+    warm = 50
+    nf = warm + steps*repeats
+    tx, rx = synth_echo(n_ch, nf, dev, seed=0xEC40)
+    clean = torch.empty(n_ch, FRAME, dtype=torch.int16, device=dev)
+    fb = n_ch*FRAME*2
+    rng = np.random.default_rng(0xEC41)
+    full = np.full(n_ch, FRAME, np.int32)
+
+    def lens_of(kind, k):
+        if kind == "b":
+            v = full.copy()
+            v[rng.random(n_ch) < 0.1] = 0
+            return v
+        if kind == "c":
+            return np.where(rng.random(n_ch) < 0.5, FRAME//2, FRAME).astype(np.int32)
+        return full
+
+    def run(kind):
+        if args.echo_lanes:
+            engine.lib().spangpu_tune_echo_lanes_per_channel(args.echo_lanes)
+        bank = engine.EchoBank(n_ch, ECHO_TAPS, ECHO_MODE)
+        engine.lib().spangpu_tune_echo_lanes_per_channel(0)
+        bank.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        lens = [None if kind == "plain" else lens_of(kind, k) for k in range(nf)]
+
+        def step(k):
+            p = (ctypes.c_void_p(tx.data_ptr() + k*fb), ctypes.c_void_p(rx.data_ptr() + k*fb), ctypes.c_void_p(clean.data_ptr()))
+            if kind == "plain":
+                bank.update_device(p[0], p[1], p[2], FRAME, FRAME)
+            else:
+                bank.update_var_device(p[0], p[1], p[2], None, lens[k], None, FRAME, FRAME)
+        for k in range(warm):
+            step(k)
+        torch.cuda.synchronize()
+        ms = []
+        for r in range(repeats):
+            ev0 = torch.cuda.Event(enable_timing=True)
+            ev1 = torch.cuda.Event(enable_timing=True)
+            ev0.record(stream)
+            for k in range(warm + r*steps, warm + (r + 1)*steps):
+                step(k)
+            ev1.record(stream)
+            torch.cuda.synchronize()
+            ms.append(ev0.elapsed_time(ev1)/steps)
+        lanes = engine.lib().spangpu_echo_lanes_per_channel(bank.h)
+        bank.close()
+        ms.sort()
+        return {"ms_per_tick": round(ms[len(ms)//2], 4), "min": round(ms[0], 4), "max": round(ms[-1], 4), "stretches": repeats,
+                "ticks_per_stretch": steps, "lanes_per_channel": lanes}
+
+    out = {"workload": "echo_group", "channels": n_ch, "taps": ECHO_TAPS, "samples": FRAME, "mode": ECHO_MODE,
+           "timing": "HIP events on the bank's stream around each stretch, host calls included; median (min, max) of the stretches",
+           "plain_update": run("plain"), "a_var_all_160": run("a"), "b_var_tenth_sitting_out": run("b"),
+           "c_var_half_80_half_160": run("c")}
+    del tx, rx, clean
+    torch.cuda.synchronize()
+    if not getattr(args, "no_e2e", False):
+        # (d) the group path end to end, by the C caller of the test suite: its own white-noise lines, staging + tick per tick
+        tmp = tempfile.mkdtemp()
+        exe = os.path.join(tmp, "echo_group")
+        subprocess.run(["gcc", "-O2", "-std=c99", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c_callers", "echo_group.c"),
+                        "-o", exe, "-L" + os.path.join(ROOT, "spandsp_amd"), "-lspangpu", "-lm", "-lpthread",
+                        "-Wl,-rpath," + os.path.join(ROOT, "spandsp_amd")], check=True)
+        p = subprocess.run([exe, str(n_ch), "16", "20"], capture_output=True, text=True)
+        d = {"returncode": p.returncode, "output": (p.stdout + p.stderr).strip().splitlines()[-3:]}
+        m = re.search(r"ms per tick: ([0-9.]+) from 16 threads, ([0-9.]+) from one", p.stdout)
+        if m:
+            d["ms_per_tick_16_threads"] = float(m.group(1))
+            d["ms_per_tick_1_thread"] = float(m.group(2))
+        d["includes"] = ("per tick: %d spangpu_echo_can_update_block() calls (copy into pageable staging rows under the group's one mutex), then the "
+                         "synchronous tick on the thread that completed the set: H2D of tx and rx, the update kernel, D2H of clean, and the copy "
+                         "to each caller's buffer -- the tone groups' threading model, measured, not optimised" % n_ch)
+        out["d_group_end_to_end"] = d
+    return out
+
+
 def bench_echo(args, dev, stream):
     """BASELINE configs[4], one GPU's shard, on SURVEY 8(d)-5's workload: `seconds` of continuous signal on G.168 lines
     (synth_echo); the first second warms up (and is checked against the oracle on 64 lines), the rest is timed; the ERLE of
@@ -1424,7 +1514,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
     ap.add_argument("--warmup", type=int, default=0)
@@ -1458,6 +1548,9 @@ def main():
     engine.tune_fsk_waves(args.fsk_waves)
     if args.workload == "echo":
         emit(bench_echo(args, dev, stream), "echo", args.channels or None)
+        return
+    if args.workload == "echo_group":
+        print(json.dumps(bench_echo_group(args, dev, stream)))
         return
     if args.workload == "mixed":
         emit(bench_mixed(args, dev, stream), "mixed", args.channels or None)
