@@ -639,6 +639,91 @@ SPANGPU_API int spangpu_mct_state_words(const spangpu_mct_t *mct);
 SPANGPU_API int spangpu_mct_get_state(spangpu_mct_t *mct, int channel, int32_t *words);
 SPANGPU_API int spangpu_mct_set_state(spangpu_mct_t *mct, int channel, const int32_t *words);
 
+/* ---- FSK and connect tone transmitter banks ---------------
+ * The senders beside the two receiver banks above: N fsk_tx() modulators, or N modem_connect_tones_tx() generators of
+ * one tone type, state in HBM, one launch per call.  Integer arithmetic throughout (dds_mod() over the 257 entry quarter
+ * sine, src/dds_int.c:340-387): every sample equals the reference's.
+ *   spangpu_fsktx_create()          fsk_tx_init(NULL, spec, get_bit, user)          src/fsk.c:237-255
+ *   spangpu_fsktx_tx()              fsk_tx(s, amp, len) x N                         src/fsk.c:162-198
+ *   spangpu_fsktx_restart()         fsk_tx_restart(s, spec)                         src/fsk.c:221-235
+ *   spangpu_fsktx_power()           fsk_tx_power(s, power)                          src/fsk.c:201-204
+ *   spangpu_fsktx_events()          the channels whose get_bit answered SIG_STATUS_END_OF_DATA in the last call: the
+ *                                   caller owes each the two status calls of      src/fsk.c:179-189
+ *   spangpu_async_frame_bits(), spangpu_fsktx_set_framing() / _put_bytes()
+ *                                   async_tx_init() / async_tx_get_bit() / async_tx_presend_bits()   src/async.c:277-380
+ *   spangpu_mcttx_create()          modem_connect_tones_tx_init(NULL, tone_type)    src/modem_connect_tones.c:302-403
+ *   spangpu_mcttx_tx()              modem_connect_tones_tx(s, amp, len) x N         src/modem_connect_tones.c:114-299
+ * The spec of an FSK sender is per channel (a sender has no correlation window): _restart() may give a channel another.
+ * Where a bit comes from is the bank's: SPANGPU_FSKTX_LFSR is the x^15 + x^14 + 1 register of spangpu_modemtx_*, seeded
+ * per channel; SPANGPU_FSKTX_QUEUE is a per-channel ring of queue_bits bits in HBM.  An empty ring at a bit boundary sends
+ * a mark and consumes nothing (a get_bit that answers 1; async_tx_get_bit() idles the same way), or, after
+ * spangpu_fsktx_end_of_data(), answers SIG_STATUS_END_OF_DATA: the channel stops at that sample, is shut down, and every
+ * later call yields 0 samples for it until it is restarted.
+ * As with the other sender banks, samples past a channel's returned length are zero-filled.  FAX CNG and the calling tone
+ * step over one sample when their cadence starts again inside a call (the reference's loop increments past it: the sample
+ * is neither written nor counted, so the output depends on where the calls end); the bank does the same and writes 0 there.
+ */
+#define SPANGPU_FSKTX_LFSR          0
+#define SPANGPU_FSKTX_QUEUE         1
+
+/* async.h:149-158 */
+#define SPANGPU_ASYNC_PARITY_NONE   0
+#define SPANGPU_ASYNC_PARITY_EVEN   1
+#define SPANGPU_ASYNC_PARITY_ODD    2
+#define SPANGPU_ASYNC_PARITY_MARK   3
+#define SPANGPU_ASYNC_PARITY_SPACE  4
+
+typedef struct spangpu_fsktx_s spangpu_fsktx_t;
+typedef struct spangpu_mcttx_s spangpu_mcttx_t;
+
+/* seeds: [n_channels] LFSR states (NULL: one per channel of the library's choosing), queue_bits: the capacity of a ring */
+SPANGPU_API int spangpu_fsktx_create(spangpu_fsktx_t **tx, int device, int n_channels, const spangpu_fsk_spec_t *spec, int bit_source,
+                                     const uint32_t *seeds, int queue_bits);
+SPANGPU_API void spangpu_fsktx_destroy(spangpu_fsktx_t *tx);
+SPANGPU_API int spangpu_fsktx_channels(const spangpu_fsktx_t *tx);
+SPANGPU_API int spangpu_fsktx_set_stream(spangpu_fsktx_t *tx, void *hip_stream);
+SPANGPU_API int spangpu_fsktx_sync(spangpu_fsktx_t *tx);
+/* One call of every channel: pcm[channel*stride + i], i < samples; lens[channel] (may be NULL) = what fsk_tx() would have
+   returned.  pcm and lens live where mem_kind says. */
+SPANGPU_API int spangpu_fsktx_tx(spangpu_fsktx_t *tx, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens);
+SPANGPU_API int spangpu_fsktx_power(spangpu_fsktx_t *tx, int channel, float power_dbm0);
+SPANGPU_API int spangpu_fsktx_restart(spangpu_fsktx_t *tx, int channel, const spangpu_fsk_spec_t *spec);
+/* Channel first + i gets lens[i] bits, packed LSB first from bits[i*stride] (host arrays); accepted[i] (may be NULL) = how
+   many of them its ring had room for. */
+SPANGPU_API int spangpu_fsktx_put_bits(spangpu_fsktx_t *tx, int first, int n, const uint8_t *bits, int stride, const int32_t *lens,
+                                       int32_t *accepted);
+SPANGPU_API int spangpu_fsktx_queued(spangpu_fsktx_t *tx, int channel);
+SPANGPU_API int spangpu_fsktx_end_of_data(spangpu_fsktx_t *tx, int channel, int on);
+/* the channels that shut down in the last spangpu_fsktx_tx(); returns how many.  Valid until the next call on this bank. */
+SPANGPU_API int spangpu_fsktx_events(spangpu_fsktx_t *tx, const int32_t **channels);
+/* async_tx_init(s, data_bits, parity, stop_bits, ...) for a channel (-1: every channel; 8N1 until set), and characters for
+   channels first .. first + n - 1: lens[i] bytes from bytes[i*stride], behind presend_bits marks.  Characters are queued
+   whole; accepted[i] (may be NULL) = how many of channel first + i's were. */
+SPANGPU_API int spangpu_fsktx_set_framing(spangpu_fsktx_t *tx, int channel, int data_bits, int parity, int stop_bits);
+SPANGPU_API int spangpu_fsktx_put_bytes(spangpu_fsktx_t *tx, int first, int n, const uint8_t *bytes, int stride, const int32_t *lens,
+                                        int presend_bits, int32_t *accepted);
+/* Test / checkpoint access to one channel's state (layout: fsktx_dev.hpp) */
+SPANGPU_API int spangpu_fsktx_state_words(void);
+SPANGPU_API int spangpu_fsktx_get_state(spangpu_fsktx_t *tx, int channel, int32_t *words);
+/* Host code, no device needed.  The bits async_tx_get_bit() makes of these bytes (start bit, data LSB first, parity, stop
+   bits), one 0/1 per entry; returns how many there are and writes at most max.  And the number of get_bit calls a
+   fsk_tx() call of `samples` makes from this baud_frac. */
+SPANGPU_API int spangpu_async_frame_bits(int data_bits, int parity, int stop_bits, const uint8_t *bytes, int n, uint8_t *bits_out, int max);
+SPANGPU_API long long spangpu_fsktx_bits_due(int baud_rate, int baud_frac, int samples);
+
+/* tone_type: SPANGPU_MCT_FAX_CNG, _ANS, _ANS_PR, _ANSAM, _ANSAM_PR, _BELL_ANS or _CALLING_TONE; the others have no sender
+   (modem_connect_tones_tx_init() returns NULL for them) */
+SPANGPU_API int spangpu_mcttx_create(spangpu_mcttx_t **tx, int device, int tone_type, int n_channels);
+SPANGPU_API void spangpu_mcttx_destroy(spangpu_mcttx_t *tx);
+SPANGPU_API int spangpu_mcttx_channels(const spangpu_mcttx_t *tx);
+SPANGPU_API int spangpu_mcttx_set_stream(spangpu_mcttx_t *tx, void *hip_stream);
+SPANGPU_API int spangpu_mcttx_sync(spangpu_mcttx_t *tx);
+/* modem_connect_tones_tx_init() again on one channel */
+SPANGPU_API int spangpu_mcttx_restart(spangpu_mcttx_t *tx, int channel);
+SPANGPU_API int spangpu_mcttx_tx(spangpu_mcttx_t *tx, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens);
+SPANGPU_API int spangpu_mcttx_state_words(void);
+SPANGPU_API int spangpu_mcttx_get_state(spangpu_mcttx_t *tx, int channel, int32_t *words);
+
 /* ---- signalling tone banks (sig_tone.c) -----------------
  * N in-band signalling tone receivers, or senders, of one tone type: 2280 Hz (AC15 and relatives), 2600 Hz, or
  * 2400 Hz / 2600 Hz (SS5).  A receiver detects the tone(s) -- notch filters as guard filters, a sharp detector that

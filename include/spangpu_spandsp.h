@@ -109,7 +109,10 @@ enum
     SIG_STATUS_CARRIER_UP = -2,
     SIG_STATUS_TRAINING_IN_PROGRESS = -3,
     SIG_STATUS_TRAINING_SUCCEEDED = -4,
-    SIG_STATUS_TRAINING_FAILED = -5
+    SIG_STATUS_TRAINING_FAILED = -5,
+    SIG_STATUS_END_OF_DATA = -7,
+    SIG_STATUS_SHUTDOWN_COMPLETE = -10,
+    SIG_STATUS_LINK_IDLE = -17
 };
 
 typedef struct v29_rx_state_s v29_rx_state_t;
@@ -493,6 +496,83 @@ SPANGPU_API int modem_connect_tones_rx_get(modem_connect_tones_rx_state_t *s);
 SPANGPU_API int modem_connect_tones_rx_release(modem_connect_tones_rx_state_t *s);
 SPANGPU_API int modem_connect_tones_rx_free(modem_connect_tones_rx_state_t *s);
 SPANGPU_API const char *modem_connect_tone_to_str(int tone);
+
+/* ---- FSK sender, modem connect tone generator, async character framer (csrc/shim_fsktx.c) -----------------
+ * Reference declarations being replaced:
+ *   fsk_tx_init/_restart/_power/_set_get_bit/_set_modem_status_handler/_release/_free, fsk_tx
+ *                                          src/spandsp/fsk.h:160-193   src/fsk.c:162-269
+ *   modem_connect_tones_tx_init/_release/_free, modem_connect_tones_tx
+ *                                          src/spandsp/modem_connect_tones.h:115-138   src/modem_connect_tones.c:114-417
+ *   async_tx_init/_get_bit/_presend_bits/_release/_free (host code)
+ *                                          src/spandsp/async.h:212-241   src/async.c:277-393
+ * A sender object is a one-channel bank (spangpu.h, "FSK and connect tone transmitter banks").  fsk_tx(s, amp, len)
+ * works out how many bits the call needs, calls get_bit exactly that many times in order -- stopping at
+ * SIG_STATUS_END_OF_DATA, after which it makes the two status calls and returns the short count, as fsk.c:179-189 --
+ * and launches.  amp past the returned count is left as the caller had it.  Without a GPU the two _init() return NULL.
+ */
+typedef int (*span_get_bit_func_t)(void *user_data);
+typedef int (*span_get_byte_func_t)(void *user_data);
+
+typedef struct fsk_tx_state_s fsk_tx_state_t;
+typedef struct modem_connect_tones_tx_state_s modem_connect_tones_tx_state_t;
+typedef struct async_tx_state_s async_tx_state_t;
+
+struct fsk_tx_state_s
+{
+    spangpu_fsktx_t *bank;
+    span_get_bit_func_t get_bit;
+    void *get_bit_user_data;
+    span_modem_status_func_t status_handler;
+    void *status_user_data;
+    int baud_rate;
+    int baud_frac;
+    int shutdown;
+    int16_t *row;
+    int row_cap;
+    int caller_storage;
+};
+struct modem_connect_tones_tx_state_s
+{
+    spangpu_mcttx_t *bank;
+    int tone_type;
+    int16_t *row;
+    int row_cap;
+    int caller_storage;
+};
+struct async_tx_state_s
+{
+    int data_bits;
+    int parity;
+    int stop_bits;
+    int total_bits;
+    span_get_byte_func_t get_byte;
+    void *user_data;
+    uint16_t frame_in_progress;
+    int bitpos;
+    int presend_bits;
+    int caller_storage;
+};
+
+SPANGPU_API fsk_tx_state_t *fsk_tx_init(fsk_tx_state_t *s, const fsk_spec_t *spec, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API int fsk_tx_restart(fsk_tx_state_t *s, const fsk_spec_t *spec);
+SPANGPU_API int fsk_tx_release(fsk_tx_state_t *s);
+SPANGPU_API int fsk_tx_free(fsk_tx_state_t *s);
+SPANGPU_API void fsk_tx_power(fsk_tx_state_t *s, float power);
+SPANGPU_API void fsk_tx_set_get_bit(fsk_tx_state_t *s, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API void fsk_tx_set_modem_status_handler(fsk_tx_state_t *s, span_modem_status_func_t handler, void *user_data);
+SPANGPU_API int fsk_tx(fsk_tx_state_t *s, int16_t amp[], int len);
+
+SPANGPU_API modem_connect_tones_tx_state_t *modem_connect_tones_tx_init(modem_connect_tones_tx_state_t *s, int tone_type);
+SPANGPU_API int modem_connect_tones_tx_release(modem_connect_tones_tx_state_t *s);
+SPANGPU_API int modem_connect_tones_tx_free(modem_connect_tones_tx_state_t *s);
+SPANGPU_API int modem_connect_tones_tx(modem_connect_tones_tx_state_t *s, int16_t amp[], int len);
+
+SPANGPU_API int async_tx_get_bit(void *user_data);
+SPANGPU_API void async_tx_presend_bits(async_tx_state_t *s, int bits);
+SPANGPU_API async_tx_state_t *async_tx_init(async_tx_state_t *s, int data_bits, int parity, int stop_bits, bool use_v14,
+                                            span_get_byte_func_t get_byte, void *user_data);
+SPANGPU_API int async_tx_release(async_tx_state_t *s);
+SPANGPU_API int async_tx_free(async_tx_state_t *s);
 
 /* ---- in-band signalling tones (csrc/shim_sigtone.c) ------------------------------------------------------
  * Reference declarations being replaced:

@@ -1,0 +1,586 @@
+// fsktx_dev.hpp -- device side of the FSK and modem connect tone transmitter banks (the last
+// two signal sources): N fsk_tx() / modem_connect_tones_tx() generators, state in HBM, one launch per call.
+//
+// What is restated (reference paths relative to the reference tree):
+//   fsk_tx()                       src/fsk.c:162-198       fsk_tx_restart()   src/fsk.c:221-235
+//   modem_connect_tones_tx()       src/modem_connect_tones.c:114-299          _tx_init()   :302-403
+//   dds_lookup() / dds_mod()       src/dds_int.c:340-355, 380-387   (257 entry quarter sine, phase >> 22)
+//
+// Both generators are integer only, and their DDS phase accumulators are uint32 and wrap, so every sample is a closed
+// form of its index: phase(i) = phase0 + (number of samples before i)*rate (+ 2^31 per phase hop).  The kernels have the
+// two-phase shape of tx_bank_kernel (txgen_dev.hpp):
+//   phase 1 (one lane per channel): walk the channel's bit boundaries / cadence and leave RUNS -- stretches of samples
+//            with one phase rate -- in LDS, consuming bits as it goes; no per-sample work;
+//   phase 2 (all 64 lanes over the wave's channels): a lane renders 8 adjacent samples (16 bytes) from the run(s) they
+//            fall in, so the stores of a channel's row are full and contiguous.
+// A channel with more runs than fit takes another round.  State is structure-of-arrays int32 words [words][n_channels].
+//
+// Samples a channel does not produce (after shutdown, after a finite tone's end, the sample the reference skips when a
+// cadence wraps inside a call) are written as 0; the per-channel length is what the reference would have returned.
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace spg
+{
+
+// dds_lookup(), dds_int.c:340-355
+__device__ __forceinline__ int ftx_dds_lookup(const int16_t *quarter, uint32_t phase)
+{
+    phase >>= 22;
+    uint32_t step = phase & 255u;
+    if (phase & 256u)
+        step = 256u - step;
+    int amp = quarter[step];
+    if (phase & 512u)
+        amp = -amp;
+    return amp;
+}
+
+// dds_mod() without the accumulator update, dds_int.c:380-387
+__device__ __forceinline__ int ftx_dds_mod(const int16_t *quarter, uint32_t phase, int scale)
+{
+    return (int) (int16_t) ((ftx_dds_lookup(quarter, phase)*scale) >> 15);
+}
+
+// Eight samples of one row: one 16-byte store when the chunk is whole and the row allows it.
+__device__ __forceinline__ void ftx_store8(int16_t *at, const int v[8], int first, int last, bool vec)
+{
+    if (vec  &&  first == 0  &&  last == 8)
+    {
+        uint4 w;
+        w.x = ((uint32_t) v[0] & 0xFFFFu) | ((uint32_t) v[1] << 16);
+        w.y = ((uint32_t) v[2] & 0xFFFFu) | ((uint32_t) v[3] << 16);
+        w.z = ((uint32_t) v[4] & 0xFFFFu) | ((uint32_t) v[5] << 16);
+        w.w = ((uint32_t) v[6] & 0xFFFFu) | ((uint32_t) v[7] << 16);
+        *reinterpret_cast<uint4 *>(at) = w;
+        return;
+    }
+#pragma unroll
+    for (int j = 0;  j < 8;  j++)
+    {
+        if (j >= first  &&  j < last)
+            at[j] = (int16_t) v[j];
+    }
+}
+
+// ---- fsk_tx() ---------------------------------------------------------------------------------------------------------
+
+enum
+{
+    FT_BAUD_RATE = 0,       // baud x 100
+    FT_RATE0 = 1,           // phase_rates[0] (space), [1] (mark)
+    FT_RATE1 = 2,
+    FT_SCALING = 3,
+    FT_CUR_RATE = 4,        // current_phase_rate
+    FT_PHASE = 5,           // phase_acc
+    FT_BAUD_FRAC = 6,
+    FT_SHUTDOWN = 7,
+    FT_LFSR = 8,            // bit source SPANGPU_FSKTX_LFSR: the x^15 + x^14 + 1 register
+    FT_QRD = 9,             // bit source SPANGPU_FSKTX_QUEUE: read position and fill of the channel's ring, in bits
+    FT_QCOUNT = 10,
+    FT_EOD = 11,            // an empty ring answers SIG_STATUS_END_OF_DATA instead of a mark
+    FT_EVENT = 12,          // the channel shut down in the last call
+    kFskTxWords = 13
+};
+
+enum { FTX_SRC_LFSR = 0, FTX_SRC_QUEUE = 1 };
+
+constexpr int kFtxBaudUnit = 8000*100;      // SAMPLE_RATE*100
+constexpr int kFtxWaves = 4;                // waves per workgroup; they share one copy of the quarter sine
+constexpr int kFtxCpw = 16;                 // channels per wave
+constexpr int kFtxRuns = 32;                // runs of a channel per round: 1200 baud x 160 samples has 25
+constexpr int kFtxRunStride = kFtxRuns + 1; // odd: the 16 owner lanes write 16 different LDS banks
+
+struct FskTxLaunch
+{
+    int32_t *st;
+    const int16_t *quarter;     // [257] in HBM
+    uint32_t *queue;            // [qring/32][n_ch] packed bits, LSB first, or null
+    int16_t *pcm;               // [n_ch][stride]
+    int32_t *lens;              // [n_ch] or null
+    long long stride;
+    int n_ch;
+    int samples;
+    int source;
+    int qring;                  // ring size in bits, a multiple of 32
+    int vec;                    // rows are 16-byte aligned
+};
+
+__global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLaunch L)
+{
+    __shared__ int16_t quarter[258];
+    __shared__ int32_t all_start[kFtxWaves][kFtxCpw][kFtxRunStride];
+    __shared__ int32_t all_phase[kFtxWaves][kFtxCpw][kFtxRunStride];
+    __shared__ int32_t all_rate[kFtxWaves][kFtxCpw][kFtxRunStride];
+    __shared__ __attribute__((aligned(16))) int32_t all_hdr[kFtxWaves][kFtxCpw][8];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    int32_t (*r_start)[kFtxRunStride] = all_start[wave];
+    int32_t (*r_phase)[kFtxRunStride] = all_phase[wave];
+    int32_t (*r_rate)[kFtxRunStride] = all_rate[wave];
+    int32_t (*r_hdr)[8] = all_hdr[wave];
+    const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
+    const int ch = ch0 + lane;
+    const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+
+    for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
+        quarter[i] = L.quarter[i];
+
+    const size_t n = (size_t) L.n_ch;
+    int32_t *st = L.st + (owner  ?  ch  :  0);
+    const int samples = L.samples;
+    int baud_rate = 1;
+    int rate0 = 0;
+    int rate1 = 0;
+    int scaling = 0;
+    int cur_rate = 0;
+    uint32_t phase = 0u;
+    int baud_frac = 0;
+    bool shutdown = true;
+    uint32_t lfsr = 0u;
+    int qrd = 0;
+    int qcount = 0;
+    bool eod = false;
+    if (owner)
+    {
+        baud_rate = st[FT_BAUD_RATE*n];
+        rate0 = st[FT_RATE0*n];
+        rate1 = st[FT_RATE1*n];
+        scaling = st[FT_SCALING*n];
+        cur_rate = st[FT_CUR_RATE*n];
+        phase = (uint32_t) st[FT_PHASE*n];
+        baud_frac = st[FT_BAUD_FRAC*n];
+        shutdown = st[FT_SHUTDOWN*n] != 0;
+        if (L.source == FTX_SRC_LFSR)
+        {
+            lfsr = (uint32_t) st[FT_LFSR*n];
+        }
+        else
+        {
+            qrd = st[FT_QRD*n];
+            qcount = st[FT_QCOUNT*n];
+            eod = st[FT_EOD*n] != 0;
+        }
+    }
+    const bool was_shutdown = shutdown;
+    int done = owner  ?  0  :  samples;
+    int len = samples;          // what fsk_tx() returns
+    int zero_from = 0x7FFFFFFF;
+    if (owner  &&  shutdown)
+    {
+        len = 0;
+        zero_from = 0;
+    }
+    __syncthreads();
+
+    for (;;)
+    {
+        // ---- phase 1: the next runs of my channel ----
+        const int lo = done;
+        int nr = 0;
+        if (owner  &&  done < samples)
+        {
+            if (shutdown)
+            {
+                done = samples;
+            }
+            else
+            {
+                r_start[lane][0] = done;
+                r_phase[lane][0] = (int32_t) phase;
+                r_rate[lane][0] = cur_rate;
+                nr = 1;
+                while (nr < kFtxRuns)
+                {
+                    // the first sample k >= 0 ahead with baud_frac + (k + 1)*baud_rate >= 800000 (fsk.c:176); advancing
+                    // run by run keeps every product inside 32 bits whatever the length of the call
+                    const int kb = (kFtxBaudUnit - baud_frac + baud_rate - 1)/baud_rate - 1;
+                    if (kb >= samples - done)
+                    {
+                        const int m = samples - done;
+                        phase += (uint32_t) m*(uint32_t) cur_rate;
+                        baud_frac += m*baud_rate;
+                        done = samples;
+                        break;
+                    }
+                    phase += (uint32_t) kb*(uint32_t) cur_rate;
+                    done += kb;
+                    baud_frac += (kb + 1)*baud_rate - kFtxBaudUnit;
+                    int bit;
+                    if (L.source == FTX_SRC_LFSR)
+                    {
+                        bit = (int) (((lfsr >> 14) ^ (lfsr >> 13)) & 1u);
+                        lfsr = ((lfsr << 1) | (uint32_t) bit) & 0x7FFFu;
+                    }
+                    else if (qcount > 0)
+                    {
+                        bit = (int) ((L.queue[(size_t) (qrd >> 5)*n + ch] >> (qrd & 31)) & 1u);
+                        qrd = (qrd + 1 == L.qring)  ?  0  :  (qrd + 1);
+                        qcount--;
+                    }
+                    else if (eod)
+                    {
+                        // SIG_STATUS_END_OF_DATA, fsk.c:179-189: this sample is not made
+                        shutdown = true;
+                        len = done;
+                        zero_from = done;
+                        done = samples;
+                        break;
+                    }
+                    else
+                    {
+                        bit = 1;        // an idle mark, and nothing is consumed
+                    }
+                    cur_rate = bit  ?  rate1  :  rate0;
+                    r_start[lane][nr] = done;
+                    r_phase[lane][nr] = (int32_t) phase;
+                    r_rate[lane][nr] = cur_rate;
+                    nr++;
+                    phase += (uint32_t) cur_rate;
+                    done++;
+                    if (done >= samples)
+                        break;
+                }
+            }
+        }
+        if (lane < kFtxCpw)
+        {
+            r_hdr[lane][0] = lo;
+            r_hdr[lane][1] = done;
+            r_hdr[lane][2] = nr;
+            r_hdr[lane][3] = zero_from;
+            r_hdr[lane][4] = scaling;
+        }
+        __syncthreads();
+
+        // ---- phase 2: the samples of those runs, 8 per lane ----
+        {
+            const int nchan = (L.n_ch - ch0 < kFtxCpw)  ?  (L.n_ch - ch0)  :  kFtxCpw;
+            const int cpr = (samples + 7) >> 3;
+            const int total = nchan*cpr;
+            for (int idx = lane;  idx < total;  idx += 64)
+            {
+                const int c = idx/cpr;
+                const int i0 = (idx - c*cpr)*8;
+                const int4 hdr = *reinterpret_cast<const int4 *>(&r_hdr[c][0]);     // lo, hi, runs, zero_from
+                const int a = (i0 > hdr.x)  ?  i0  :  hdr.x;
+                const int b = (i0 + 8 < hdr.y)  ?  (i0 + 8)  :  hdr.y;
+                if (a >= b)
+                    continue;
+                const int scale = r_hdr[c][4];
+                const int32_t *S = r_start[c];
+                int r = 0;
+#pragma unroll
+                for (int step = kFtxRuns/2;  step > 0;  step >>= 1)
+                    r += (r + step < hdr.z  &&  S[r + step] <= a)  ?  step  :  0;
+                int rate = 0;
+                uint32_t ph = 0u;
+                int next = 0x7FFFFFFF;
+                if (hdr.z > 0)
+                {
+                    rate = r_rate[c][r];
+                    ph = (uint32_t) r_phase[c][r] + (uint32_t) (a - S[r])*(uint32_t) rate;
+                    next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
+                }
+                int v[8];
+#pragma unroll
+                for (int j = 0;  j < 8;  j++)
+                {
+                    const int i = i0 + j;
+                    v[j] = 0;
+                    if (i >= a  &&  i < b)
+                    {
+                        while (i >= next)
+                        {
+                            r++;
+                            rate = r_rate[c][r];
+                            ph = (uint32_t) r_phase[c][r];
+                            next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
+                        }
+                        if (i < hdr.w  &&  hdr.z > 0)
+                            v[j] = ftx_dds_mod(quarter, ph, scale);
+                        ph += (uint32_t) rate;
+                    }
+                }
+                ftx_store8(L.pcm + (size_t) (ch0 + c)*L.stride + i0, v, a - i0, b - i0, L.vec != 0);
+            }
+        }
+        if (!__syncthreads_or(done < samples))
+            break;
+    }
+
+    if (owner)
+    {
+        if (!was_shutdown)
+        {
+            st[FT_CUR_RATE*n] = cur_rate;
+            st[FT_PHASE*n] = (int32_t) phase;
+            st[FT_BAUD_FRAC*n] = baud_frac;
+            st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
+            if (L.source == FTX_SRC_LFSR)
+            {
+                st[FT_LFSR*n] = (int32_t) lfsr;
+            }
+            else
+            {
+                st[FT_QRD*n] = qrd;
+                st[FT_QCOUNT*n] = qcount;
+            }
+        }
+        st[FT_EVENT*n] = (shutdown  &&  !was_shutdown)  ?  1  :  0;
+        if (L.lens)
+            L.lens[ch] = len;
+    }
+}
+
+// spangpu_fsktx_put_bits() on channels [lo, hi): the bits of channel c are packed LSB first at bits[(c - lo)*bstride ...],
+// lens[c - lo] of them; accepted[c - lo] = how many had room.
+__global__ void fsktx_put_kernel(int32_t *st, uint32_t *queue, int n_ch, int qring, int qcap, int lo, int hi, const uint8_t *bits,
+                                 int bstride, const int32_t *lens, int32_t *accepted)
+{
+    const int ch = lo + blockIdx.x*blockDim.x + threadIdx.x;
+    if (ch >= hi)
+        return;
+    const size_t n = (size_t) n_ch;
+    const uint8_t *src = bits + (size_t) (ch - lo)*bstride;
+    const int rd = st[FT_QRD*n + ch];
+    const int count = st[FT_QCOUNT*n + ch];
+    int mine = lens[ch - lo];
+    mine = (mine > qcap - count)  ?  (qcap - count)  :  mine;
+    mine = (mine < 0)  ?  0  :  mine;
+    int at = rd + count;
+    at -= (at >= qring)  ?  qring  :  0;
+    for (int i = 0;  i < mine;  i++)
+    {
+        const uint32_t bit = (src[i >> 3] >> (i & 7)) & 1u;
+        uint32_t *w = queue + (size_t) (at >> 5)*n + ch;
+        *w = (*w & ~(1u << (at & 31))) | (bit << (at & 31));
+        at = (at + 1 == qring)  ?  0  :  (at + 1);
+    }
+    st[FT_QCOUNT*n + ch] = count + mine;
+    accepted[ch - lo] = mine;
+}
+
+// ---- modem_connect_tones_tx() -----------------------------------------------------------------------------------------
+
+enum
+{
+    MTX_TIMER = 0,          // duration_timer
+    MTX_HOP = 1,            // hop_timer
+    MTX_TONE_PHASE = 2,
+    MTX_MOD_PHASE = 3,
+    kMctTxWords = 4
+};
+
+constexpr int kMtxRuns = 4;         // tone bursts of a channel per round
+constexpr int kMtxHop = 3600;       // milliseconds_to_samples(450)
+
+struct MctTxLaunch
+{
+    int32_t *st;
+    const int16_t *quarter;
+    int16_t *pcm;
+    int32_t *lens;
+    long long stride;
+    int n_ch;
+    int samples;
+    int vec;
+    // the tone type, as modem_connect_tones_tx_init() sets it up
+    int cadenced;           // FAX CNG and the calling tone: tone and silence for ever; the others end
+    int hops;               // the /PR types
+    int am;                 // the ANSam types
+    int tone_rate;
+    int mod_rate;
+    int level;
+    int mod_level;
+    int tone_len;           // finite: samples of tone at the end of the timer; cadenced: samples of silence per cycle
+    int period;             // cadenced: samples per cycle
+};
+
+__global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLaunch L)
+{
+    __shared__ int16_t quarter[258];
+    __shared__ __attribute__((aligned(16))) int32_t all_runs[kFtxWaves][kFtxCpw][kMtxRuns][4];  // start, end, phase
+    __shared__ __attribute__((aligned(16))) int32_t all_hdr[kFtxWaves][kFtxCpw][8];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    int32_t (*runs)[kMtxRuns][4] = all_runs[wave];
+    int32_t (*r_hdr)[8] = all_hdr[wave];
+    const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
+    const int ch = ch0 + lane;
+    const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+
+    for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
+        quarter[i] = L.quarter[i];
+
+    const size_t n = (size_t) L.n_ch;
+    int32_t *st = L.st + (owner  ?  ch  :  0);
+    const int samples = L.samples;
+    int timer = 0;
+    int hop = 0;
+    uint32_t tone_phase = 0u;
+    uint32_t mod_phase = 0u;
+    if (owner)
+    {
+        timer = st[MTX_TIMER*n];
+        hop = st[MTX_HOP*n];
+        tone_phase = (uint32_t) st[MTX_TONE_PHASE*n];
+        mod_phase = (uint32_t) st[MTX_MOD_PHASE*n];
+    }
+    int done = owner  ?  0  :  samples;
+    int len = samples;
+    __syncthreads();
+
+    for (;;)
+    {
+        // ---- phase 1 ----
+        const int lo = done;
+        int nr = 0;
+        int hop0 = 0x7FFFFFFF;
+        const uint32_t mod0 = mod_phase;
+        if (owner  &&  done < samples)
+        {
+            if (!L.cadenced)
+            {
+                // modem_connect_tones.c:155-172 and its four likes: the call is clipped to what is left of the tone
+                len = (timer < samples)  ?  timer  :  samples;
+                int lead = 0;
+                if (timer > L.tone_len)
+                    lead = (timer - L.tone_len > len)  ?  len  :  (timer - L.tone_len);
+                const int m = len - lead;
+                runs[lane][0][0] = lead;
+                runs[lane][0][1] = len;
+                runs[lane][0][2] = (int32_t) tone_phase;
+                nr = 1;
+                uint32_t nh = 0u;
+                if (L.hops)
+                {
+                    // --hop_timer <= 0 before tone sample k (from 0): k + 1 >= hop, then every 3600 samples
+                    hop0 = hop;
+                    if (m >= hop)
+                    {
+                        nh = 1u + (uint32_t) (m - hop)/(uint32_t) kMtxHop;
+                        hop = kMtxHop - (m - hop)%kMtxHop;
+                    }
+                    else
+                    {
+                        hop -= m;
+                    }
+                }
+                tone_phase += (uint32_t) m*(uint32_t) L.tone_rate + (nh << 31);
+                mod_phase += (uint32_t) m*(uint32_t) L.mod_rate;
+                timer -= len;
+                done = samples;
+            }
+            else
+            {
+                // modem_connect_tones.c:125-154 / :264-293
+                while (done < samples  &&  nr < kMtxRuns)
+                {
+                    if (timer > L.tone_len)
+                    {
+                        int m = timer - L.tone_len;
+                        m = (m > samples - done)  ?  (samples - done)  :  m;
+                        runs[lane][nr][0] = done;
+                        runs[lane][nr][1] = done + m;
+                        runs[lane][nr][2] = (int32_t) tone_phase;
+                        nr++;
+                        tone_phase += (uint32_t) m*(uint32_t) L.tone_rate;
+                        timer -= m;
+                        done += m;
+                    }
+                    if (timer > 0)
+                    {
+                        int m = timer;
+                        m = (m > samples - done)  ?  (samples - done)  :  m;
+                        timer -= m;
+                        done += m;
+                    }
+                    if (timer == 0)
+                    {
+                        // the cycle starts again; inside a call the reference's loop increment steps over one sample,
+                        // which is neither written nor counted
+                        timer = L.period;
+                        if (done < samples)
+                            done++;
+                    }
+                }
+            }
+        }
+        if (lane < kFtxCpw)
+        {
+            r_hdr[lane][0] = lo;
+            r_hdr[lane][1] = done;
+            r_hdr[lane][2] = nr;
+            r_hdr[lane][3] = hop0;
+            r_hdr[lane][4] = (int32_t) mod0;
+        }
+        __syncthreads();
+
+        // ---- phase 2 ----
+        {
+            const int nchan = (L.n_ch - ch0 < kFtxCpw)  ?  (L.n_ch - ch0)  :  kFtxCpw;
+            const int cpr = (samples + 7) >> 3;
+            const int total = nchan*cpr;
+            for (int idx = lane;  idx < total;  idx += 64)
+            {
+                const int c = idx/cpr;
+                const int i0 = (idx - c*cpr)*8;
+                const int4 hdr = *reinterpret_cast<const int4 *>(&r_hdr[c][0]);     // lo, hi, runs, hop timer
+                const int a = (i0 > hdr.x)  ?  i0  :  hdr.x;
+                const int b = (i0 + 8 < hdr.y)  ?  (i0 + 8)  :  hdr.y;
+                if (a >= b)
+                    continue;
+                const uint32_t mod0c = (uint32_t) r_hdr[c][4];
+                int4 run = make_int4(0, 0, 0, 0);
+                int r = -1;
+                int v[8];
+#pragma unroll
+                for (int j = 0;  j < 8;  j++)
+                {
+                    const int i = i0 + j;
+                    v[j] = 0;
+                    if (i >= a  &&  i < b)
+                    {
+                        while (i >= run.y  &&  r + 1 < hdr.z)
+                        {
+                            r++;
+                            run = *reinterpret_cast<const int4 *>(&runs[c][r][0]);
+                        }
+                        if (i >= run.x  &&  i < run.y)
+                        {
+                            const uint32_t k = (uint32_t) (i - run.x);
+                            uint32_t ph = (uint32_t) run.z + k*(uint32_t) L.tone_rate;
+                            if ((int) (k + 1u) >= hdr.w)
+                                ph += (1u + (k + 1u - (uint32_t) hdr.w)/(uint32_t) kMtxHop) << 31;
+                            int scale = L.level;
+                            if (L.am)
+                                scale = (int) (int16_t) (L.level + ftx_dds_mod(quarter, mod0c + k*(uint32_t) L.mod_rate, L.mod_level));
+                            v[j] = ftx_dds_mod(quarter, ph, scale);
+                        }
+                    }
+                }
+                ftx_store8(L.pcm + (size_t) (ch0 + c)*L.stride + i0, v, a - i0, b - i0, L.vec != 0);
+            }
+        }
+        if (!__syncthreads_or(done < samples))
+            break;
+    }
+
+    if (owner)
+    {
+        st[MTX_TIMER*n] = timer;
+        st[MTX_HOP*n] = hop;
+        st[MTX_TONE_PHASE*n] = (int32_t) tone_phase;
+        st[MTX_MOD_PHASE*n] = (int32_t) mod_phase;
+        if (L.lens)
+            L.lens[ch] = len;
+    }
+}
+
+}   // namespace spg

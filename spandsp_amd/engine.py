@@ -112,6 +112,33 @@ def lib():
             "spangpu_modemtx_state_words": (ci, []),
             "spangpu_modemtx_get_state": (ci, [vp, ci, vp]),
             "spangpu_modemtx_table": (ci, [ci, vp, ci]),
+            "spangpu_fsktx_create": (ci, [C.POINTER(vp), ci, ci, vp, ci, vp, ci]),
+            "spangpu_fsktx_destroy": (None, [vp]),
+            "spangpu_fsktx_channels": (ci, [vp]),
+            "spangpu_fsktx_set_stream": (ci, [vp, vp]),
+            "spangpu_fsktx_sync": (ci, [vp]),
+            "spangpu_fsktx_tx": (ci, [vp, ci, vp, ll, ci, vp]),
+            "spangpu_fsktx_power": (ci, [vp, ci, cf]),
+            "spangpu_fsktx_restart": (ci, [vp, ci, vp]),
+            "spangpu_fsktx_put_bits": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+            "spangpu_fsktx_queued": (ci, [vp, ci]),
+            "spangpu_fsktx_end_of_data": (ci, [vp, ci, ci]),
+            "spangpu_fsktx_events": (ci, [vp, C.POINTER(vp)]),
+            "spangpu_fsktx_set_framing": (ci, [vp, ci, ci, ci, ci]),
+            "spangpu_fsktx_put_bytes": (ci, [vp, ci, ci, vp, ci, vp, ci, vp]),
+            "spangpu_fsktx_state_words": (ci, []),
+            "spangpu_fsktx_get_state": (ci, [vp, ci, vp]),
+            "spangpu_async_frame_bits": (ci, [ci, ci, ci, vp, ci, vp, ci]),
+            "spangpu_fsktx_bits_due": (ll, [ci, ci, ci]),
+            "spangpu_mcttx_create": (ci, [C.POINTER(vp), ci, ci, ci]),
+            "spangpu_mcttx_destroy": (None, [vp]),
+            "spangpu_mcttx_channels": (ci, [vp]),
+            "spangpu_mcttx_set_stream": (ci, [vp, vp]),
+            "spangpu_mcttx_sync": (ci, [vp]),
+            "spangpu_mcttx_restart": (ci, [vp, ci]),
+            "spangpu_mcttx_tx": (ci, [vp, ci, vp, ll, ci, vp]),
+            "spangpu_mcttx_state_words": (ci, []),
+            "spangpu_mcttx_get_state": (ci, [vp, ci, vp]),
             "spangpu_awgn_create": (ci, [C.POINTER(vp), ci, ci, vp, vp]),
             "spangpu_awgn_destroy": (None, [vp]),
             "spangpu_awgn_channels": (ci, [vp]),
@@ -1672,6 +1699,146 @@ class MctBank:
         w = np.zeros(self.words, np.int32)
         _check(lib().spangpu_mct_get_state(self.h, channel, w.ctypes.data))
         return w
+
+
+# ---- FSK and connect tone transmitter banks (include/spangpu.h) ---------------------------
+FSKTX_LFSR, FSKTX_QUEUE = 0, 1
+ASYNC_PARITY_NONE, ASYNC_PARITY_EVEN, ASYNC_PARITY_ODD, ASYNC_PARITY_MARK, ASYNC_PARITY_SPACE = range(5)
+
+
+def async_frame_bits(data_bits, parity, stop_bits, data):
+    """The 0/1 bits async_tx_get_bit() makes of these bytes (host code, no device)."""
+    src = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    out = np.zeros(max(1, 12*len(src)), np.uint8)
+    n = _check(lib().spangpu_async_frame_bits(data_bits, parity, stop_bits, src.ctypes.data if len(src) else None, len(src),
+                                              out.ctypes.data, len(out)))
+    return out[:n]
+
+
+def fsktx_bits_due(baud_rate, baud_frac, samples):
+    """How many get_bit calls a fsk_tx() call of `samples` makes (host code, no device)."""
+    return _check(lib().spangpu_fsktx_bits_due(baud_rate, baud_frac, samples))
+
+
+class _SenderBank:
+    """What FskTxBank and MctTxBank share: one call of every channel into host or device rows."""
+    _prefix = None
+
+    def _f(self, name):
+        return getattr(lib(), "spangpu_%s_%s" % (self._prefix, name))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        _check(self._f("set_stream")(self.h, hip_stream))
+
+    def sync(self):
+        _check(self._f("sync")(self.h))
+
+    def tx_host(self, samples):
+        pcm = np.zeros((self.n, max(1, samples)), np.int16)
+        lens = np.zeros(self.n, np.int32)
+        _check(self._f("tx")(self.h, MEM_HOST, pcm.ctypes.data, pcm.shape[1], samples, lens.ctypes.data))
+        return pcm[:, :samples], lens
+
+    def tx_device(self, pcm_ptr, stride, samples, lens_ptr=None):
+        _check(self._f("tx")(self.h, MEM_DEVICE, pcm_ptr, stride, samples, lens_ptr))
+
+    def get_state(self, channel):
+        w = np.zeros(self._f("state_words")(), np.int32)
+        _check(self._f("get_state")(self.h, channel, w.ctypes.data))
+        return w
+
+
+class FskTxBank(_SenderBank):
+    """N FSK modulators (fsk_tx), state in HBM.  Bits come from a per-channel LFSR or a per-channel bit queue."""
+    _prefix = "fsktx"
+
+    def __init__(self, spec, n_channels, bit_source=FSKTX_LFSR, seeds=None, queue_bits=4096, device=0):
+        self.spec = fsk_preset(spec) if isinstance(spec, int) else spec
+        self.n = n_channels
+        self.h = C.c_void_p()
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint32)
+        assert sd is None or len(sd) == n_channels
+        _check(lib().spangpu_fsktx_create(C.byref(self.h), device, n_channels, C.byref(self.spec), bit_source,
+                                          None if sd is None else sd.ctypes.data, queue_bits))
+
+    def power(self, channel, power_dbm0):
+        _check(lib().spangpu_fsktx_power(self.h, channel, power_dbm0))
+
+    def restart(self, channel, spec):
+        sp = fsk_preset(spec) if isinstance(spec, int) else spec
+        _check(lib().spangpu_fsktx_restart(self.h, channel, C.byref(sp)))
+
+    def put_bits(self, bit_lists, first=0):
+        """One sequence of 0/1 per channel from `first` on; returns how many bits each ring accepted."""
+        n = len(bit_lists)
+        stride = max(1, (max(len(b) for b in bit_lists) + 7)//8)
+        buf = np.zeros((n, stride), np.uint8)
+        lens = np.zeros(n, np.int32)
+        for i, b in enumerate(bit_lists):
+            b = np.asarray(b, np.uint8)
+            lens[i] = len(b)
+            if len(b):
+                buf[i, :(len(b) + 7)//8] = np.packbits(b, bitorder="little")
+        acc = np.zeros(n, np.int32)
+        _check(lib().spangpu_fsktx_put_bits(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, acc.ctypes.data))
+        return acc
+
+    def queued(self, channel):
+        return _check(lib().spangpu_fsktx_queued(self.h, channel))
+
+    def end_of_data(self, channel, on=True):
+        _check(lib().spangpu_fsktx_end_of_data(self.h, channel, int(on)))
+
+    def events(self):
+        """The channels that shut down in the last call."""
+        p = C.c_void_p()
+        k = _check(lib().spangpu_fsktx_events(self.h, C.byref(p)))
+        if k == 0:
+            return np.zeros(0, np.int32)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (k,)).copy()
+
+    def set_framing(self, data_bits, parity, stop_bits, channel=-1):
+        _check(lib().spangpu_fsktx_set_framing(self.h, channel, data_bits, parity, stop_bits))
+
+    def put_bytes(self, texts, first=0, presend_bits=0):
+        """One byte string per channel from `first` on, framed as set_framing() says; returns the bytes accepted."""
+        bs = [bytes(t) for t in texts]
+        n = len(bs)
+        stride = max(1, max(len(b) for b in bs))
+        buf = np.zeros((n, stride), np.uint8)
+        lens = np.zeros(n, np.int32)
+        for i, b in enumerate(bs):
+            buf[i, :len(b)] = np.frombuffer(b, np.uint8)
+            lens[i] = len(b)
+        acc = np.zeros(n, np.int32)
+        _check(lib().spangpu_fsktx_put_bytes(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, presend_bits,
+                                             acc.ctypes.data))
+        return acc
+
+
+class MctTxBank(_SenderBank):
+    """N modem connect tone generators of one tone type (modem_connect_tones_tx), state in HBM."""
+    _prefix = "mcttx"
+
+    def __init__(self, tone_type, n_channels, device=0):
+        self.tone_type = tone_type
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_mcttx_create(C.byref(self.h), device, tone_type, n_channels))
+
+    def restart(self, channel):
+        _check(lib().spangpu_mcttx_restart(self.h, channel))
 
 
 # ---- signalling tone banks (include/spangpu.h "signalling tone banks") ---------------------

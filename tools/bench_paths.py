@@ -1309,6 +1309,68 @@ def bench_dtmf_tx(args, dev, stream):
         "cpu_baseline": cpu}
 
 
+def bench_sender(args, dev, stream, which):
+    """SURVEY 8(f)-1, the last two sources: the FSK transmitter bank (V.21 channel 2, bits from the per-channel LFSR) or the
+    connect tone transmitter bank (ANSam/PR, the busiest type: 15 Hz AM and phase hops) writing 160-sample frames into HBM."""
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    if which == "fsk_tx":
+        rng = np.random.default_rng(7)
+        bank = engine.FskTxBank(engine.FSK_V21CH2, n_ch, engine.FSKTX_LFSR, rng.integers(1, 0x7FFF, n_ch).astype(np.uint32))
+        kernel, words, what = "fsktx_bank_kernel", 13, "fsk_tx bank, V.21 ch 2, LFSR bit source"
+    else:
+        bank = engine.MctTxBank(engine.MCT_ANSAM_PR, n_ch)
+        kernel, words, what = "mcttx_bank_kernel", 4, "modem_connect_tones_tx bank, ANSam/PR"
+    bank.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    out = torch.zeros(4, n_ch, FRAME, dtype=torch.int16, device=dev)
+    d_lens = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+
+    def step(i):
+        bank.tx_device(ctypes.c_void_p(out[i % 4].data_ptr()), FRAME, FRAME, ctypes.c_void_p(d_lens.data_ptr()))
+    for i in range(args.warmup):
+        step(i)
+    torch.cuda.synchronize()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        evs[i][0].record(stream)
+        step(args.warmup + i)
+        evs[i][1].record(stream)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    per = [a.elapsed_time(b) for a, b in evs]
+    avg_ms = sum(per)/len(per)
+    assert int(d_lens.min()) == FRAME or which == "mct_tx"     # (a finite tone ends after 260 frames)
+    rms = float(out.float().pow(2).mean().sqrt())
+    cpu = None
+    if not args.no_cpu_baseline:
+        from oracle import ref
+        n = 0
+        t1 = time.perf_counter()
+        while time.perf_counter() - t1 < 1.0:
+            n += len(ref.fsk_tx(1, 400000, seed=5 + n) if which == "fsk_tx" else ref.modem_connect_tones_tx(engine.MCT_ANSAM_PR, 41600))
+        dtc = time.perf_counter() - t1
+        cpu = {"value": n/dtc/1e6, "unit": "Msamples/s", "cores": 1,
+               "sample": "oracle/_ref %s through ctypes for %.1f s on one core" % ("fsk_tx()" if which == "fsk_tx" else "modem_connect_tones_tx()", dtc)}
+    # 320 B written per channel-frame, the state words read and written (the FSK sender writes back 5 of its 13, and its length)
+    alg_write = n_ch*(FRAME*2 + (6 if which == "fsk_tx" else 5)*4)
+    alg_read = n_ch*words*4
+    value = args.steps*n_ch*FRAME/dt/1e6
+    return {
+        "metric": "Msamples/s of batched %s (signal source bank)" % ("fsk_tx" if which == "fsk_tx" else "modem_connect_tones_tx"),
+        "value": value, "unit": "Msamples/s",
+        "realtime_channels": value*1e6/8000.0, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt*1e3/args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "i16",
+        "data": "synthetic",
+        "config": {"workload": "%s, %d channels x %d-sample frames" % (what, n_ch, FRAME), "channels_per_gpu": n_ch,
+                   "rms_of_last_frames": rms},
+        "roofline": {"bound": "hbm", "kernel": kernel, "achieved": (alg_write + alg_read)/(avg_ms*1e-3)/1e9,
+                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": (alg_write + alg_read)/(avg_ms*1e-3)/1e9/HBM_PEAK_GBPS,
+                     "traffic": None, "alg_write_bytes_per_launch": alg_write, "alg_read_bytes_per_launch": alg_read,
+                     "avg_launch_us": avg_ms*1e3, "min_launch_us": min(per)*1e3},
+        "cpu_baseline": cpu}
+
+
 def modem_spot_check(kind, bit_rate, frames64, events64, cutoffs=None):
     """The oracle's receiver (oracle/v29_oracle.c ..., pinned to the reference) over the same first frames of 64 channels:
     the put_bit stream of every frame equal?  frames64: int16 [frames, 64, FRAME]; events64[frame][channel]: int8 arrays."""
@@ -1514,7 +1576,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
     ap.add_argument("--warmup", type=int, default=0)
@@ -1578,6 +1640,9 @@ def main():
     if args.workload == "fsk":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         emit(bench_fsk(args, dev, stream), "fsk", args.channels or None)
+        return
+    if args.workload in ("fsk_tx", "mct_tx"):
+        emit(bench_sender(args, dev, stream, args.workload), args.workload, args.channels or None)
         return
     if args.workload == "dtmf_tx":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
