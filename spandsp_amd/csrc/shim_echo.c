@@ -6,35 +6,26 @@
  * group's bank: its frames are staged, and the frames of all the group's objects run in one tick -- one launch per frame
  * length in the tick (spangpu_echo_update_var()).  No arithmetic of the canceller happens here.
  */
-#include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include "spangpu_spandsp.h"
+#include "shim_group.h"
 
-/* The threading model is the tone groups' (shim_tone.c): one mutex per group covers staging, attach / detach, the tick and
-   every call on the bank; frames are copied in outside it (a channel has one submitter); the tick is synchronous and runs on
-   the thread that completes the set. */
+/* The staging protocol and its threading model are every group's: shim_group.h.  This family's delivery makes no callbacks
+   -- it copies the results to the buffers the callers named -- so nothing re-enters a tick here. */
 struct spangpu_echo_group_s
 {
+    grp_core_t core;
     spangpu_echo_t *bank;
-    int n_ch;
     int taps;
-    int max_samples;
     int16_t *stage_tx;          /* [n_ch][max_samples] */
     int16_t *stage_rx;
     int16_t *out_clean;         /* the tick's results, before they go to the buffers the callers named */
     int16_t *out_tx;
-    echo_can_state_t **handles; /* per channel: the attached object or NULL */
-    int32_t *lens;              /* per channel: samples staged for the tick being collected (0 = none) */
-    uint8_t *hpf;               /* ... its use_hpf_tx */
+    uint8_t *hpf;               /* per channel: the staged frame's use_hpf_tx */
     int16_t **clean_dst;        /* ... and where its results are to go */
     int16_t **tx_dst;
-    int n_attached;
-    int n_staged;
     int n_tx_dst;               /* staged frames that asked for tx_out */
     long long ticks;
-    pthread_mutex_t lock;
+    int rc;                     /* what the last tick's spangpu_echo_update_var() returned */
 };
 
 struct echo_can_state_s
@@ -46,42 +37,38 @@ struct echo_can_state_s
     int channel;
 };
 
-/* Run the tick with the channels that have staged a frame; the others sit it out.  Returns the number of channels that
-   took part.  The tick is over whatever came of it: a failure must not make every later frame a "second frame". */
-static int echo_group_tick_locked(spangpu_echo_group_t *g)
+/* The tick's launch.  A tick that fails counts as a tick too. */
+static int echo_group_run(grp_core_t *core)
 {
-    int rc;
-    int c;
+    spangpu_echo_group_t *g = (spangpu_echo_group_t *) core;
 
-    if (g->n_staged == 0)
-        return 0;
-    rc = spangpu_echo_update_var(g->bank, g->stage_tx, g->stage_rx, g->out_clean, (g->n_tx_dst)  ?  g->out_tx  :  NULL,
-                                 SPANGPU_MEM_HOST, g->lens, g->hpf, g->max_samples, g->max_samples);
-    for (c = 0;  c < g->n_ch;  c++)
-    {
-        if (g->lens[c] == 0)
-            continue;
-        if (rc >= 0)
-        {
-            memcpy(g->clean_dst[c], g->out_clean + (size_t) c*g->max_samples, sizeof(int16_t)*g->lens[c]);
-            if (g->tx_dst[c])
-                memcpy(g->tx_dst[c], g->out_tx + (size_t) c*g->max_samples, sizeof(int16_t)*g->lens[c]);
-        }
-        g->lens[c] = 0;
-        g->clean_dst[c] = NULL;
-        g->tx_dst[c] = NULL;
-    }
-    g->n_staged = 0;
+    g->rc = spangpu_echo_update_var(g->bank, g->stage_tx, g->stage_rx, g->out_clean, (g->n_tx_dst)  ?  g->out_tx  :  NULL,
+                                    SPANGPU_MEM_HOST, core->lens, g->hpf, core->max_samples, core->max_samples);
     g->n_tx_dst = 0;
     g->ticks++;
-    return rc;
+    return g->rc;
+}
+
+static void echo_group_deliver(grp_core_t *core)
+{
+    spangpu_echo_group_t *g = (spangpu_echo_group_t *) core;
+    int c;
+
+    for (c = 0;  c < core->n_ch;  c++)
+    {
+        if (core->run[c] == 0)
+            continue;
+        memcpy(g->clean_dst[c], g->out_clean + (size_t) c*core->max_samples, sizeof(int16_t)*core->run[c]);
+        if (g->tx_dst[c])
+            memcpy(g->tx_dst[c], g->out_tx + (size_t) c*core->max_samples, sizeof(int16_t)*core->run[c]);
+    }
 }
 
 /* The object's channel is about to be read or changed: its staged frame, if it has one, runs first. */
 static void echo_group_settle_locked(spangpu_echo_group_t *g, int channel)
 {
-    if (g->lens[channel])
-        echo_group_tick_locked(g);
+    if (g->core.lens[channel])
+        grp_flush_locked(&g->core);
 }
 
 spangpu_echo_group_t *spangpu_echo_group_create(int device, int n_channels, int taps, int max_samples)
@@ -98,22 +85,18 @@ spangpu_echo_group_t *spangpu_echo_group_create(int device, int n_channels, int 
         free(g);
         return NULL;
     }
-    g->n_ch = n_channels;
     g->taps = taps;
-    g->max_samples = max_samples;
     n = (size_t) n_channels*max_samples;
     g->stage_tx = (int16_t *) calloc(n, sizeof(int16_t));
     g->stage_rx = (int16_t *) calloc(n, sizeof(int16_t));
     g->out_clean = (int16_t *) calloc(n, sizeof(int16_t));
     g->out_tx = (int16_t *) calloc(n, sizeof(int16_t));
-    g->handles = (echo_can_state_t **) calloc(n_channels, sizeof(echo_can_state_t *));
-    g->lens = (int32_t *) calloc(n_channels, sizeof(int32_t));
     g->hpf = (uint8_t *) calloc(n_channels, sizeof(uint8_t));
     g->clean_dst = (int16_t **) calloc(n_channels, sizeof(int16_t *));
     g->tx_dst = (int16_t **) calloc(n_channels, sizeof(int16_t *));
-    pthread_mutex_init(&g->lock, NULL);
-    if (g->stage_tx == NULL  ||  g->stage_rx == NULL  ||  g->out_clean == NULL  ||  g->out_tx == NULL  ||  g->handles == NULL
-        ||  g->lens == NULL  ||  g->hpf == NULL  ||  g->clean_dst == NULL  ||  g->tx_dst == NULL)
+    if (grp_init(&g->core, n_channels, max_samples, echo_group_run, echo_group_deliver) < 0
+        ||  g->stage_tx == NULL  ||  g->stage_rx == NULL  ||  g->out_clean == NULL  ||  g->out_tx == NULL
+        ||  g->hpf == NULL  ||  g->clean_dst == NULL  ||  g->tx_dst == NULL)
     {
         spangpu_echo_group_destroy(g);
         return NULL;
@@ -131,25 +114,27 @@ int spangpu_echo_group_destroy(spangpu_echo_group_t *g)
     free(g->stage_rx);
     free(g->out_clean);
     free(g->out_tx);
-    free(g->handles);
-    free(g->lens);
     free(g->hpf);
     free(g->clean_dst);
     free(g->tx_dst);
-    pthread_mutex_destroy(&g->lock);
+    grp_free(&g->core);
     free(g);
     return SPANGPU_OK;
 }
 
+/* Returns what the tick's spangpu_echo_update_var() returned (0 when nothing was staged), not the number of frames as the
+   other families' flush does. */
 int spangpu_echo_group_flush(spangpu_echo_group_t *g)
 {
     int rc;
 
     if (g == NULL)
         return SPANGPU_ERR_BAD_ARG;
-    pthread_mutex_lock(&g->lock);
-    rc = echo_group_tick_locked(g);
-    pthread_mutex_unlock(&g->lock);
+    pthread_mutex_lock(&g->core.lock);
+    g->rc = 0;
+    grp_flush_locked(&g->core);
+    rc = g->rc;
+    pthread_mutex_unlock(&g->core.lock);
     return rc;
 }
 
@@ -160,9 +145,9 @@ long long spangpu_echo_group_ticks(const spangpu_echo_group_t *g)
 
     if (g == NULL)
         return 0;
-    pthread_mutex_lock(&m->lock);
+    pthread_mutex_lock(&m->core.lock);
     n = m->ticks;
-    pthread_mutex_unlock(&m->lock);
+    pthread_mutex_unlock(&m->core.lock);
     return n;
 }
 
@@ -171,11 +156,17 @@ spangpu_echo_t *spangpu_echo_group_bank(spangpu_echo_group_t *g)
     return (g)  ?  g->bank  :  NULL;
 }
 
+/* A claimed slot is a new canceller in the mode asked for; if the reset fails the attach is refused. */
+static int echo_group_fresh(grp_core_t *core, int channel, void *adaption_mode)
+{
+    return (spangpu_echo_reset_channel(((spangpu_echo_group_t *) core)->bank, channel, *(int *) adaption_mode) == SPANGPU_OK)  ?  0  :  -1;
+}
+
 echo_can_state_t *spangpu_echo_can_attach(spangpu_echo_group_t *g, int channel, int adaption_mode)
 {
     echo_can_state_t *ec;
 
-    if (g == NULL  ||  channel < 0  ||  channel >= g->n_ch)
+    if (g == NULL  ||  channel < 0  ||  channel >= g->core.n_ch)
         return NULL;
     if ((ec = (echo_can_state_t *) calloc(1, sizeof(*ec))) == NULL)
         return NULL;
@@ -188,17 +179,12 @@ echo_can_state_t *spangpu_echo_can_attach(spangpu_echo_group_t *g, int channel, 
     ec->taps = g->taps;
     ec->grp = g;
     ec->channel = channel;
-    pthread_mutex_lock(&g->lock);
-    if (g->handles[channel]  ||  spangpu_echo_reset_channel(g->bank, channel, adaption_mode) != SPANGPU_OK)
+    if (grp_claim(&g->core, channel, ec, echo_group_fresh, &adaption_mode) < 0)
     {
-        pthread_mutex_unlock(&g->lock);
         free(ec->snapshot);
         free(ec);
         return NULL;
     }
-    g->handles[channel] = ec;
-    g->n_attached++;
-    pthread_mutex_unlock(&g->lock);
     return ec;
 }
 
@@ -208,41 +194,31 @@ int spangpu_echo_can_pending(echo_can_state_t *ec)
 
     if (ec == NULL  ||  ec->grp == NULL)
         return 0;
-    pthread_mutex_lock(&ec->grp->lock);
-    rc = (ec->grp->lens[ec->channel] != 0);
-    pthread_mutex_unlock(&ec->grp->lock);
+    pthread_mutex_lock(&ec->grp->core.lock);
+    rc = (ec->grp->core.lens[ec->channel] != 0);
+    pthread_mutex_unlock(&ec->grp->core.lock);
     return rc;
 }
 
+/* The slot is released only if this object holds it (a tone group asks whether anybody does, the modem and line groups
+   do not ask). */
 static void echo_group_detach(echo_can_state_t *ec)
 {
     spangpu_echo_group_t *g = ec->grp;
     int c = ec->channel;
 
-    pthread_mutex_lock(&g->lock);
-    if (g->handles[c] == ec)
+    pthread_mutex_lock(&g->core.lock);
+    if (g->core.handles[c] == ec)
     {
-        g->handles[c] = NULL;
-        g->n_attached--;
-        if (g->lens[c])
-        {
-            /* a pending frame is dropped: nothing runs, nothing is written */
-            if (g->tx_dst[c])
-                g->n_tx_dst--;
-            g->lens[c] = 0;
-            g->clean_dst[c] = NULL;
-            g->tx_dst[c] = NULL;
-            g->n_staged--;
-        }
-        /* the channels that remain may all have been waiting for this one */
-        if (g->n_staged > 0  &&  g->n_staged >= g->n_attached)
-            echo_group_tick_locked(g);
+        if (g->core.lens[c]  &&  g->tx_dst[c])
+            g->n_tx_dst--;
+        grp_release(&g->core, c);
     }
-    pthread_mutex_unlock(&g->lock);
+    pthread_mutex_unlock(&g->core.lock);
 }
 
 /* Stage one object's frame (any thread); the tick runs when every attached object has staged, or in
-   spangpu_echo_group_flush().  The frame is copied outside the lock: a channel has one submitter, as a spandsp object has. */
+   spangpu_echo_group_flush().  Returns SPANGPU_OK or an error code of include/spangpu.h (the other families' xxx_rx() say -1). */
 static int echo_group_stage(echo_can_state_t *ec, const int16_t tx[], const int16_t rx[], int16_t clean[], int16_t tx_out[],
                             int n, int use_hpf_tx)
 {
@@ -250,34 +226,22 @@ static int echo_group_stage(echo_can_state_t *ec, const int16_t tx[], const int1
     int c = ec->channel;
     int rc;
 
-    if (n > g->max_samples  ||  tx == NULL  ||  rx == NULL  ||  clean == NULL)
+    if (n > g->core.max_samples  ||  tx == NULL  ||  rx == NULL  ||  clean == NULL)
         return SPANGPU_ERR_BAD_ARG;
-    pthread_mutex_lock(&g->lock);
-    if (g->lens[c])
-    {
-        pthread_mutex_unlock(&g->lock);
+    if (grp_stage_begin(&g->core, c) < 0)
         return SPANGPU_ERR_STATE;       /* second frame before the tick ran */
-    }
-    pthread_mutex_unlock(&g->lock);
-    memcpy(g->stage_tx + (size_t) c*g->max_samples, tx, sizeof(int16_t)*n);
-    memcpy(g->stage_rx + (size_t) c*g->max_samples, rx, sizeof(int16_t)*n);
-    pthread_mutex_lock(&g->lock);
-    g->lens[c] = n;
+    memcpy(g->stage_tx + (size_t) c*g->core.max_samples, tx, sizeof(int16_t)*n);
+    memcpy(g->stage_rx + (size_t) c*g->core.max_samples, rx, sizeof(int16_t)*n);
+    /* what goes with the frame is set under the lock that counts it: the tick reads every channel's flag */
+    pthread_mutex_lock(&g->core.lock);
     g->hpf[c] = (use_hpf_tx)  ?  1  :  0;
     g->clean_dst[c] = clean;
     g->tx_dst[c] = tx_out;
     if (tx_out)
         g->n_tx_dst++;
-    g->n_staged++;
-    rc = SPANGPU_OK;
-    if (g->n_staged >= g->n_attached)
-    {
-        rc = echo_group_tick_locked(g);
-        if (rc > 0)
-            rc = SPANGPU_OK;
-    }
-    pthread_mutex_unlock(&g->lock);
-    return rc;
+    rc = grp_stage_commit(&g->core, c, n);
+    pthread_mutex_unlock(&g->core.lock);
+    return (rc > 0)  ?  SPANGPU_OK  :  rc;
 }
 
 echo_can_state_t *echo_can_init(int len, int adaption_mode)
@@ -324,7 +288,7 @@ static void echo_enter(echo_can_state_t *ec)
 {
     if (ec->grp)
     {
-        pthread_mutex_lock(&ec->grp->lock);
+        pthread_mutex_lock(&ec->grp->core.lock);
         echo_group_settle_locked(ec->grp, ec->channel);
     }
 }
@@ -332,7 +296,7 @@ static void echo_enter(echo_can_state_t *ec)
 static void echo_leave(echo_can_state_t *ec)
 {
     if (ec->grp)
-        pthread_mutex_unlock(&ec->grp->lock);
+        pthread_mutex_unlock(&ec->grp->core.lock);
 }
 
 void echo_can_flush(echo_can_state_t *ec)
@@ -384,20 +348,21 @@ int16_t echo_can_update(echo_can_state_t *ec, int16_t tx, int16_t rx)
 
     if (g)
     {
-        /* whatever the group has staged runs first, then this one sample as a tick of one channel */
-        size_t at = (size_t) ec->channel*g->max_samples;
+        /* whatever the group has staged runs first, then this one sample as a tick of one channel: outside the staging
+           protocol (nobody else's frame can be in `lens` while the lock is held), and not counted as a tick of the group */
+        size_t at = (size_t) ec->channel*g->core.max_samples;
 
-        pthread_mutex_lock(&g->lock);
-        echo_group_tick_locked(g);
+        pthread_mutex_lock(&g->core.lock);
+        grp_flush_locked(&g->core);
         g->stage_tx[at] = tx;
         g->stage_rx[at] = rx;
-        g->lens[ec->channel] = 1;
+        g->core.lens[ec->channel] = 1;
         g->hpf[ec->channel] = 0;
-        if (spangpu_echo_update_var(g->bank, g->stage_tx, g->stage_rx, g->out_clean, NULL, SPANGPU_MEM_HOST, g->lens, g->hpf,
-                                    g->max_samples, g->max_samples) == 1)
+        if (spangpu_echo_update_var(g->bank, g->stage_tx, g->stage_rx, g->out_clean, NULL, SPANGPU_MEM_HOST, g->core.lens, g->hpf,
+                                    g->core.max_samples, g->core.max_samples) == 1)
             clean = g->out_clean[at];
-        g->lens[ec->channel] = 0;
-        pthread_mutex_unlock(&g->lock);
+        g->core.lens[ec->channel] = 0;
+        pthread_mutex_unlock(&g->core.lock);
         return clean;
     }
     spangpu_echo_update(ec->bank, &tx, &rx, &clean, SPANGPU_MEM_HOST, 1, 1, 0);
@@ -410,10 +375,11 @@ int16_t echo_can_hpf_tx(echo_can_state_t *ec, int16_t tx)
 
     if (ec->grp)
     {
-        pthread_mutex_lock(&ec->grp->lock);
-        echo_group_tick_locked(ec->grp);
+        /* (as echo_can_update(): the group's staged frames first, then one sample of one channel under the group's lock) */
+        pthread_mutex_lock(&ec->grp->core.lock);
+        grp_flush_locked(&ec->grp->core);
         spangpu_echo_hpf_tx_channel(ec->bank, ec->channel, &tx, &out, 1);
-        pthread_mutex_unlock(&ec->grp->lock);
+        pthread_mutex_unlock(&ec->grp->core.lock);
         return out;
     }
     spangpu_echo_hpf_tx(ec->bank, &tx, &out, 1, 1);

@@ -7,11 +7,9 @@
  * Without a GPU every init returns NULL: there is no CPU implementation.
  */
 #include <math.h>
-#include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "spangpu_spandsp.h"
+#include "shim_group.h"
 
 /* preset_fsk_specs[], src/fsk.c:60-155 */
 const fsk_spec_t preset_fsk_specs[] =
@@ -32,45 +30,29 @@ const fsk_spec_t preset_fsk_specs[] =
 /* ---- one staging group for both receiver kinds ---------------------------------------------------------- */
 struct spangpu_line_group_s
 {
+    grp_core_t core;            /* the staging protocol: shim_group.h */
     int is_mct;
     spangpu_fsk_t *fsk;
     spangpu_mct_t *mct;
     spangpu_fsk_spec_t spec;
     int tone_type;
-    int n_ch;
-    int max_samples;
     int16_t *stage;
-    void **handles;
-    int32_t *lens;              /* per channel: samples staged for the tick being collected (0 = none) */
-    int32_t *run;               /* ... and of the tick whose callbacks are being delivered */
-    int delivering;             /* a tick's callbacks are being made: staging from inside them waits for the next flush */
-    int n_attached;
-    int n_staged;
-    pthread_mutex_t lock;       /* staging, attach / detach and the tick itself (recursive: callbacks may call back in) */
     int32_t *pristine;          /* a channel's words as the bank was created: what xxx_rx_init() leaves, default cutoff included */
+    /* the results of the tick being delivered (views into the bank's buffers) */
+    const int16_t *fsk_events;
+    const int32_t *mct_events;
+    const int32_t *counts;
+    int cap;
 };
 
-static spangpu_line_group_t *group_new(int n_channels, int max_samples)
+static spangpu_line_group_t *group_new(int n_channels, int max_samples, int (*run_tick)(grp_core_t *), void (*deliver)(grp_core_t *))
 {
     spangpu_line_group_t *g;
 
     if (n_channels <= 0  ||  max_samples <= 0  ||  (g = (spangpu_line_group_t *) calloc(1, sizeof(*g))) == NULL)
         return NULL;
-    g->n_ch = n_channels;
-    g->max_samples = max_samples;
     g->stage = (int16_t *) calloc((size_t) n_channels*max_samples, sizeof(int16_t));
-    g->handles = (void **) calloc(n_channels, sizeof(void *));
-    g->lens = (int32_t *) calloc(n_channels, sizeof(int32_t));
-    g->run = (int32_t *) calloc(n_channels, sizeof(int32_t));
-    {
-        pthread_mutexattr_t at;
-
-        pthread_mutexattr_init(&at);
-        pthread_mutexattr_settype(&at, PTHREAD_MUTEX_RECURSIVE);
-        pthread_mutex_init(&g->lock, &at);
-        pthread_mutexattr_destroy(&at);
-    }
-    if (g->stage == NULL  ||  g->handles == NULL  ||  g->lens == NULL  ||  g->run == NULL)
+    if (grp_init(&g->core, n_channels, max_samples, run_tick, deliver) < 0  ||  g->stage == NULL)
     {
         spangpu_line_group_destroy(g);
         return NULL;
@@ -78,11 +60,81 @@ static spangpu_line_group_t *group_new(int n_channels, int max_samples)
     return g;
 }
 
+/* The tick of an FSK group: the launch and a view of each channel's put_bit / status stream ... */
+static int fsk_run(grp_core_t *core)
+{
+    spangpu_line_group_t *g = (spangpu_line_group_t *) core;
+    const int rc = spangpu_fsk_rx_var(g->fsk, g->stage, SPANGPU_MEM_HOST, core->lens, core->max_samples, core->max_samples);
+
+    return g->cap = (rc < 0)  ?  rc  :  spangpu_fsk_events(g->fsk, &g->fsk_events, &g->counts);
+}
+
+/* ... replayed */
+static void fsk_deliver(grp_core_t *core)
+{
+    spangpu_line_group_t *g = (spangpu_line_group_t *) core;
+    const int cap = g->cap;
+    int c;
+    int i;
+    int n;
+
+    for (c = 0;  c < core->n_ch;  c++)
+    {
+        fsk_rx_state_t *s = (fsk_rx_state_t *) core->handles[c];
+
+        n = (g->counts[c] < cap)  ?  g->counts[c]  :  cap;
+        if (s  &&  core->run[c] > 0)
+        {
+            for (i = 0;  i < n;  i++)
+            {
+                const int v = g->fsk_events[(size_t) c*cap + i];
+
+                /* report_status_change(), fsk.c:343-349: the status handler if there is one, else put_bit */
+                if (v < 0  &&  s->status_handler)
+                    s->status_handler(s->status_user_data, v);
+                else if (s->put_bit)
+                    s->put_bit(s->put_bit_user_data, v);
+            }
+        }
+    }
+}
+
+/* The same pair for a connect-tone group: (tone, level) reports */
+static int mct_run(grp_core_t *core)
+{
+    spangpu_line_group_t *g = (spangpu_line_group_t *) core;
+    const int rc = spangpu_mct_rx_var(g->mct, g->stage, SPANGPU_MEM_HOST, core->lens, core->max_samples, core->max_samples);
+
+    return g->cap = (rc < 0)  ?  rc  :  spangpu_mct_events(g->mct, &g->mct_events, &g->counts);
+}
+
+static void mct_deliver(grp_core_t *core)
+{
+    spangpu_line_group_t *g = (spangpu_line_group_t *) core;
+    const int cap = g->cap;
+    int c;
+    int i;
+    int n;
+
+    for (c = 0;  c < core->n_ch;  c++)
+    {
+        modem_connect_tones_rx_state_t *s = (modem_connect_tones_rx_state_t *) core->handles[c];
+
+        n = (g->counts[c] < cap)  ?  g->counts[c]  :  cap;
+        if (s  &&  s->tone_callback  &&  core->run[c] > 0)
+        {
+            /* report_tone_state(), modem_connect_tones.c:420-423 */
+            for (i = 0;  i < n;  i++)
+                s->tone_callback(s->callback_data, g->mct_events[((size_t) c*cap + i)*2], g->mct_events[((size_t) c*cap + i)*2 + 1], 0);
+        }
+    }
+}
+
 spangpu_line_group_t *spangpu_fsk_group_create(int device, const fsk_spec_t *spec, int framing_mode, int n_channels, int max_samples)
 {
     spangpu_line_group_t *g;
 
-    if (spec == NULL  ||  (g = group_new(n_channels, max_samples)) == NULL)
+    if (spec == NULL  ||  (g = group_new(n_channels, max_samples, fsk_run, fsk_deliver)) == NULL)
         return NULL;
     g->spec.freq_zero = spec->freq_zero;
     g->spec.freq_one = spec->freq_one;
@@ -104,7 +156,7 @@ spangpu_line_group_t *spangpu_modem_connect_tones_group_create(int device, int t
 {
     spangpu_line_group_t *g;
 
-    if ((g = group_new(n_channels, max_samples)) == NULL)
+    if ((g = group_new(n_channels, max_samples, mct_run, mct_deliver)) == NULL)
         return NULL;
     g->is_mct = 1;
     g->tone_type = tone_type;
@@ -127,217 +179,77 @@ int spangpu_line_group_destroy(spangpu_line_group_t *g)
     if (g->mct)
         spangpu_mct_destroy(g->mct);
     free(g->stage);
-    free(g->handles);
-    free(g->lens);
-    free(g->run);
     free(g->pristine);
-    pthread_mutex_destroy(&g->lock);
+    grp_free(&g->core);
     free(g);
     return 0;
 }
 
-/* The tick is over, whatever came of it: its frames leave the staging area before anything is delivered -- a failure must
-   not make every later call a "second frame" or run the same frames again, and a callback that stages a new frame finds
-   a clean slate (that frame waits for the next tick).  Returns how many frames the tick had. */
-static int tick_taken(spangpu_line_group_t *g)
-{
-    const int took = g->n_staged;
-
-    memcpy(g->run, g->lens, sizeof(int32_t)*g->n_ch);
-    memset(g->lens, 0, sizeof(int32_t)*g->n_ch);
-    g->n_staged = 0;
-    return took;
-}
-
-/* Run the tick with the receivers that have staged a frame; the others sit it out, untouched (as the reference's are when
-   their xxx_rx() is not called), and may stage for the next one.  Returns how many took part. */
-static int line_flush_locked_tick(spangpu_line_group_t *g)
-{
-    int cap;
-    int c;
-    int i;
-    int n;
-    int rc;
-
-    int took;
-
-    if (g->n_staged == 0)
-        return 0;
-    if (g->is_mct)
-    {
-        const int32_t *events;
-        const int32_t *counts;
-
-        rc = spangpu_mct_rx_var(g->mct, g->stage, SPANGPU_MEM_HOST, g->lens, g->max_samples, g->max_samples);
-        cap = (rc < 0)  ?  rc  :  spangpu_mct_events(g->mct, &events, &counts);
-        took = tick_taken(g);
-        if (cap < 0)
-            return cap;
-        g->delivering = 1;
-        for (c = 0;  c < g->n_ch;  c++)
-        {
-            modem_connect_tones_rx_state_t *s = (modem_connect_tones_rx_state_t *) g->handles[c];
-
-            n = (counts[c] < cap)  ?  counts[c]  :  cap;
-            if (s  &&  s->tone_callback  &&  g->run[c] > 0)
-            {
-                /* report_tone_state(), modem_connect_tones.c:420-423 */
-                for (i = 0;  i < n;  i++)
-                    s->tone_callback(s->callback_data, events[((size_t) c*cap + i)*2], events[((size_t) c*cap + i)*2 + 1], 0);
-            }
-        }
-    }
-    else
-    {
-        const int16_t *events;
-        const int32_t *counts;
-
-        rc = spangpu_fsk_rx_var(g->fsk, g->stage, SPANGPU_MEM_HOST, g->lens, g->max_samples, g->max_samples);
-        cap = (rc < 0)  ?  rc  :  spangpu_fsk_events(g->fsk, &events, &counts);
-        took = tick_taken(g);
-        if (cap < 0)
-            return cap;
-        g->delivering = 1;
-        for (c = 0;  c < g->n_ch;  c++)
-        {
-            fsk_rx_state_t *s = (fsk_rx_state_t *) g->handles[c];
-
-            n = (counts[c] < cap)  ?  counts[c]  :  cap;
-            if (s  &&  g->run[c] > 0)
-            {
-                for (i = 0;  i < n;  i++)
-                {
-                    const int v = events[(size_t) c*cap + i];
-
-                    /* report_status_change(), fsk.c:343-349: the status handler if there is one, else put_bit */
-                    if (v < 0  &&  s->status_handler)
-                        s->status_handler(s->status_user_data, v);
-                    else if (s->put_bit)
-                        s->put_bit(s->put_bit_user_data, v);
-                }
-            }
-        }
-    }
-    g->delivering = 0;
-    return took;
-}
-
-/* The tick(s) that are due.  Callbacks may stage frames (a put_bit handler that answers by feeding its receiver, say): while
-   a tick's callbacks run, a flush from inside them does nothing (`delivering`); when they are over, the tick those frames
-   complete -- every attached channel has staged again -- runs at once instead of waiting for somebody to ask, so that no
-   later xxx_rx() is refused as a second frame of a tick that nobody would ever have run. */
-static int line_flush_locked(spangpu_line_group_t *g)
-{
-    int total = 0;
-    int rc;
-
-    if (g->delivering)
-        return 0;
-    for (;;)
-    {
-        if ((rc = line_flush_locked_tick(g)) < 0)
-            return rc;
-        total += rc;
-        if (g->n_staged == 0  ||  g->n_staged < g->n_attached)
-            break;
-    }
-    return total;
-}
-
 int spangpu_line_group_flush(spangpu_line_group_t *g)
 {
-    int rc;
-
-    if (g == NULL)
-        return SPANGPU_ERR_BAD_ARG;
-    pthread_mutex_lock(&g->lock);
-    rc = line_flush_locked(g);
-    pthread_mutex_unlock(&g->lock);
-    return rc;
+    return (g)  ?  grp_flush(&g->core)  :  SPANGPU_ERR_BAD_ARG;
 }
 
-/* One object's frame: a private bank runs it now (in slices); a shared one stages it (any thread; one submitter per
-   receiver) and the tick runs when every attached receiver has staged, or when its owner calls
-   spangpu_line_group_flush() at the deadline.  A frame longer than the group was made for, or a second frame for a
-   receiver before the tick has run, is refused with -1: nothing is dropped silently. */
+/* A shared bank stages one frame per receiver and tick (any thread; one submitter per receiver); the tick runs when every
+   attached receiver has staged, or when its owner calls spangpu_line_group_flush() at the deadline.  A frame longer than
+   the group was made for, or a second frame for a receiver before the tick has run, is refused with -1 (a tone group tells
+   the two apart): nothing is dropped silently. */
+static int line_stage(grp_core_t *core, int channel, const int16_t amp[], int len)
+{
+    spangpu_line_group_t *g = (spangpu_line_group_t *) core;
+
+    if (len > core->max_samples  ||  grp_stage_begin(core, channel) < 0)
+        return -1;
+    memcpy(g->stage + (size_t) channel*core->max_samples, amp, len*sizeof(int16_t));
+    return (grp_stage_commit(core, channel, len) < 0)  ?  -1  :  0;
+}
+
+/* A piece of a private object's buffer: a tick that fails is not reported, and the pieces after it still run (a tone
+   object stops at the first and returns -1). */
+static int line_stage_private(grp_core_t *core, int channel, const int16_t amp[], int len)
+{
+    (void) line_stage(core, channel, amp, len);
+    return 0;
+}
+
+/* One object's frame: a shared bank stages it, a private one runs it now (in slices). */
 static int line_rx(spangpu_line_group_t *g, int channel, int private_grp, const int16_t amp[], int len)
 {
-    int n;
-    int rc;
-
     if (len <= 0)
         return 0;                           /* as the reference: nothing to do (fsk.c:330 loops over len) */
-    if (private_grp)
-    {
-        if (g->delivering)
-            return -1;                      /* called from inside its own callback: refused, not dropped (the staging row is in use) */
-        while (len > 0)
-        {
-            n = (len > g->max_samples)  ?  g->max_samples  :  len;
-            memcpy(g->stage, amp, n*sizeof(int16_t));
-            g->lens[0] = n;
-            g->n_staged = 1;
-            spangpu_line_group_flush(g);
-            amp += n;
-            len -= n;
-        }
-        return 0;
-    }
-    if (len > g->max_samples)
+    if (!private_grp)
+        return line_stage(&g->core, channel, amp, len);
+    /* Called from inside its own callback: refused, not dropped (a tone object's frame is accepted, and runs when the
+       delivery is over). */
+    if (grp_in_callback(&g->core))
         return -1;
-    pthread_mutex_lock(&g->lock);
-    if (g->lens[channel])
-    {
-        pthread_mutex_unlock(&g->lock);
-        return -1;
-    }
-    pthread_mutex_unlock(&g->lock);
-    memcpy(g->stage + (size_t) channel*g->max_samples, amp, len*sizeof(int16_t));
-    pthread_mutex_lock(&g->lock);
-    g->lens[channel] = len;
-    g->n_staged++;
-    rc = (g->n_staged >= g->n_attached)  ?  line_flush_locked(g)  :  0;
-    pthread_mutex_unlock(&g->lock);
-    return (rc < 0)  ?  -1  :  0;
+    return grp_feed_private(&g->core, amp, len, line_stage_private);
 }
 
+/* The slot is released whether or not it is held (a tone group looks first); a private object detaches, then destroys its
+   group (a tone object only destroys it). */
 static void line_detach(spangpu_line_group_t *g, int channel, int private_grp)
 {
-    pthread_mutex_lock(&g->lock);
-    g->handles[channel] = NULL;
-    g->n_attached--;
-    if (g->lens[channel])
-    {
-        /* its frame of the tick in progress goes with it */
-        g->lens[channel] = 0;
-        g->n_staged--;
-    }
-    if (!private_grp  &&  g->n_staged > 0  &&  g->n_staged >= g->n_attached)
-        line_flush_locked(g);               /* it was the one the others were waiting for */
-    pthread_mutex_unlock(&g->lock);
+    grp_release(&g->core, channel);
     if (private_grp)
         spangpu_line_group_destroy(g);
 }
 
-/* Claim a slot for a new object: tested and taken under the group lock (two threads attaching the same slot: one wins).
-   On a shared bank the channel gets the words of a fresh receiver -- the slot may have served an earlier call whose object
-   was freed mid-signal, with a cutoff of its own (fsk.c:723-742 and modem_connect_tones.c:799-857 start from a memset()). */
+/* The channel of a slot being claimed on a shared bank gets the words of a fresh receiver -- the slot may have served an
+   earlier call whose object was freed mid-signal, with a cutoff of its own (fsk.c:723-742 and modem_connect_tones.c:799-857
+   start from a memset()).  If that fails the attach is refused (a tone group does not look). */
+static int line_fresh(grp_core_t *core, int channel, void *arg)
+{
+    spangpu_line_group_t *g = (spangpu_line_group_t *) core;
+
+    (void) arg;
+    return g->is_mct  ?  spangpu_mct_set_state(g->mct, channel, g->pristine)  :  spangpu_fsk_set_state(g->fsk, channel, g->pristine);
+}
+
+/* A private object's bank is new, and is left as it was made. */
 static int line_attach(spangpu_line_group_t *g, int channel, int private_grp, void *handle)
 {
-    int rc = 0;
-
-    pthread_mutex_lock(&g->lock);
-    if (g->handles[channel])
-        rc = -1;
-    else if (!private_grp)
-        rc = g->is_mct  ?  spangpu_mct_set_state(g->mct, channel, g->pristine)  :  spangpu_fsk_set_state(g->fsk, channel, g->pristine);
-    if (rc >= 0)
-    {
-        g->handles[channel] = handle;
-        g->n_attached++;
-    }
-    pthread_mutex_unlock(&g->lock);
-    return (rc < 0)  ?  -1  :  0;
+    return grp_claim(&g->core, channel, handle, (private_grp)  ?  NULL  :  line_fresh, NULL);
 }
 
 /* ---- fsk_rx -------------------------------------------------------------------------------------------- */
@@ -379,7 +291,7 @@ fsk_rx_state_t *fsk_rx_init(fsk_rx_state_t *s, const fsk_spec_t *spec, int frami
 
 fsk_rx_state_t *spangpu_fsk_rx_attach(spangpu_line_group_t *g, int channel, span_put_bit_func_t put_bit, void *user_data)
 {
-    if (g == NULL  ||  g->is_mct  ||  channel < 0  ||  channel >= g->n_ch)
+    if (g == NULL  ||  g->is_mct  ||  channel < 0  ||  channel >= g->core.n_ch)
         return NULL;
     return fsk_obj(NULL, g, channel, 0, put_bit, user_data);
 }
@@ -413,11 +325,7 @@ int fsk_rx_restart(fsk_rx_state_t *s, const fsk_spec_t *spec, int framing_mode)
         line_detach(s->grp, s->channel, 1);
         s->grp = g;
         s->channel = 0;
-        pthread_mutex_lock(&g->lock);
-        g->handles[0] = s;
-        g->n_attached++;
-        pthread_mutex_unlock(&g->lock);
-        return 0;
+        return line_attach(g, 0, 1, s);
     }
     return (spangpu_fsk_restart(s->grp->fsk, s->channel, framing_mode) < 0)  ?  -1  :  0;
 }
@@ -543,7 +451,7 @@ modem_connect_tones_rx_state_t *modem_connect_tones_rx_init(modem_connect_tones_
 modem_connect_tones_rx_state_t *spangpu_modem_connect_tones_rx_attach(spangpu_line_group_t *g, int channel,
                                                                       span_tone_report_func_t tone_callback, void *user_data)
 {
-    if (g == NULL  ||  !g->is_mct  ||  channel < 0  ||  channel >= g->n_ch)
+    if (g == NULL  ||  !g->is_mct  ||  channel < 0  ||  channel >= g->core.n_ch)
         return NULL;
     return mct_obj(NULL, g, channel, 0, tone_callback, user_data);
 }

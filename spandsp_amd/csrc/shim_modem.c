@@ -8,31 +8,28 @@
  * Without a GPU every init returns NULL: there is no CPU implementation.
  */
 #include <math.h>
-#include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "spangpu_spandsp.h"
+#include "shim_group.h"
 
 #define MAX_WORDS   1024
 
 struct spangpu_modem_group_s
 {
+    grp_core_t core;            /* the staging protocol: shim_group.h */
     spangpu_modem_t *bank;
     int kind;
     int bit_rate;
-    int n_ch;
-    int max_samples;
     int16_t *stage;
-    void **handles;
-    int32_t *lens;              /* per channel: samples staged for the tick being collected (0 = none) */
-    int32_t *run;               /* ... and of the tick whose callbacks are being delivered */
-    int delivering;             /* a tick's callbacks are being made: staging from inside them waits for the next flush */
-    int n_attached;
-    int n_staged;
-    pthread_mutex_t lock;       /* staging, attach / detach and the tick itself (recursive: callbacks may call back in) */
     int qam_tap;                /* some object of the group has a qam report handler: the bank records the reports */
     uint32_t *pristine;         /* a channel's words as the bank was created: what xxx_rx_init() leaves, default cutoff included */
+    /* the results of the tick being delivered (views into the bank's buffers) */
+    const int8_t *events;
+    const int32_t *counts;
+    int cap;
+    const uint32_t *qam;
+    const int32_t *qcounts;
+    int qcap;
 };
 
 typedef struct
@@ -71,6 +68,9 @@ static int rate_ok(int kind, int bit_rate)
     return 0;
 }
 
+static int group_run(grp_core_t *core);
+static void group_deliver(grp_core_t *core);
+
 spangpu_modem_group_t *spangpu_modem_group_create(int device, int kind, int n_channels, int bit_rate, int max_samples)
 {
     spangpu_modem_group_t *g;
@@ -81,22 +81,9 @@ spangpu_modem_group_t *spangpu_modem_group_create(int device, int kind, int n_ch
         return NULL;
     g->kind = kind;
     g->bit_rate = bit_rate;
-    g->n_ch = n_channels;
-    g->max_samples = max_samples;
     g->stage = (int16_t *) calloc((size_t) n_channels*max_samples, sizeof(int16_t));
-    g->handles = (void **) calloc(n_channels, sizeof(void *));
-    g->lens = (int32_t *) calloc(n_channels, sizeof(int32_t));
-    g->run = (int32_t *) calloc(n_channels, sizeof(int32_t));
     g->pristine = (uint32_t *) calloc(MAX_WORDS, sizeof(uint32_t));
-    {
-        pthread_mutexattr_t at;
-
-        pthread_mutexattr_init(&at);
-        pthread_mutexattr_settype(&at, PTHREAD_MUTEX_RECURSIVE);
-        pthread_mutex_init(&g->lock, &at);
-        pthread_mutexattr_destroy(&at);
-    }
-    if (g->stage == NULL  ||  g->handles == NULL  ||  g->lens == NULL  ||  g->run == NULL  ||  g->pristine == NULL
+    if (grp_init(&g->core, n_channels, max_samples, group_run, group_deliver) < 0  ||  g->stage == NULL  ||  g->pristine == NULL
         ||  spangpu_modem_create(&g->bank, device, kind, n_channels, bit_rate) != SPANGPU_OK
         ||  spangpu_modem_get_state(g->bank, 0, g->pristine) < 0)
     {
@@ -113,11 +100,8 @@ int spangpu_modem_group_destroy(spangpu_modem_group_t *g)
     if (g->bank)
         spangpu_modem_destroy(g->bank);
     free(g->stage);
-    free(g->handles);
-    free(g->lens);
-    free(g->run);
     free(g->pristine);
-    pthread_mutex_destroy(&g->lock);
+    grp_free(&g->core);
     free(g);
     return 0;
 }
@@ -171,83 +155,44 @@ static void deliver(modem_obj_t *o, const int8_t *ev, int n, const uint32_t *qam
     }
 }
 
-/* Run the tick with the receivers that have staged a frame; the others sit it out, untouched (as the reference's are
-   when their xxx_rx() is not called), and may stage for the next one.  Returns how many took part. */
-static int group_flush_locked_tick(spangpu_modem_group_t *g)
+/* The tick's launch, and views of what it left */
+static int group_run(grp_core_t *core)
 {
-    const int8_t *events;
-    const int32_t *counts;
-    const uint32_t *qam = NULL;
-    const int32_t *qcounts = NULL;
-    int cap;
-    int qcap = 0;
-    int c;
+    spangpu_modem_group_t *g = (spangpu_modem_group_t *) core;
     int rc;
 
-    if (g->n_staged == 0)
-        return 0;
-    rc = spangpu_modem_rx_var(g->bank, g->stage, SPANGPU_MEM_HOST, g->lens, g->max_samples, g->max_samples);
+    g->qam = NULL;
+    g->qcounts = NULL;
+    g->qcap = 0;
+    rc = spangpu_modem_rx_var(g->bank, g->stage, SPANGPU_MEM_HOST, core->lens, core->max_samples, core->max_samples);
     /* the put_bit stream comes up packed (a header word and the data bits per channel, status reports as a sparse list) and is
        spread out on the host: spangpu_modem_events_packed() */
-    cap = (rc < 0)  ?  rc  :  spangpu_modem_events_packed(g->bank, &events, &counts);
-    if (cap >= 0  &&  g->qam_tap)
-        qcap = spangpu_modem_qam_reports(g->bank, &qam, &qcounts);
-    /* The tick is over whatever happened: its frames are taken off the staging area before anything is delivered, so
-       that a failure cannot make every later xxx_rx() a "second frame" (or run the same frames again), and so that a
-       callback which stages a new frame sees a clean slate (that frame waits for the next tick). */
-    rc = g->n_staged;
-    memcpy(g->run, g->lens, sizeof(int32_t)*g->n_ch);
-    memset(g->lens, 0, sizeof(int32_t)*g->n_ch);
-    g->n_staged = 0;
-    if (cap < 0)
-        return cap;
-    if (qcap < 0)
-        return qcap;
-    g->delivering = 1;
-    for (c = 0;  c < g->n_ch;  c++)
-    {
-        if (g->handles[c]  &&  g->run[c] > 0)
-        {
-            deliver((modem_obj_t *) g->handles[c], events + (size_t) c*cap, (counts[c] < cap)  ?  counts[c]  :  cap,
-                    qam  ?  qam + (size_t) c*qcap*7  :  NULL, qam  ?  ((qcounts[c] < qcap)  ?  qcounts[c]  :  qcap)  :  0);
-        }
-    }
-    g->delivering = 0;
-    return rc;
+    g->cap = (rc < 0)  ?  rc  :  spangpu_modem_events_packed(g->bank, &g->events, &g->counts);
+    if (g->cap >= 0  &&  g->qam_tap)
+        g->qcap = spangpu_modem_qam_reports(g->bank, &g->qam, &g->qcounts);
+    return (g->cap < 0)  ?  g->cap  :  (g->qcap < 0)  ?  g->qcap  :  0;
 }
 
-/* The tick(s) that are due.  Callbacks may stage frames (a put_bit handler that answers by feeding its receiver, say): while
-   a tick's callbacks run, a flush from inside them does nothing (`delivering`); when they are over, the tick those frames
-   complete -- every attached channel has staged again -- runs at once instead of waiting for somebody to ask, so that no
-   later xxx_rx() is refused as a second frame of a tick that nobody would ever have run. */
-static int group_flush_locked(spangpu_modem_group_t *g)
+static void group_deliver(grp_core_t *core)
 {
-    int total = 0;
-    int rc;
+    spangpu_modem_group_t *g = (spangpu_modem_group_t *) core;
+    const int cap = g->cap;
+    const int qcap = g->qcap;
+    int c;
 
-    if (g->delivering)
-        return 0;
-    for (;;)
+    for (c = 0;  c < core->n_ch;  c++)
     {
-        if ((rc = group_flush_locked_tick(g)) < 0)
-            return rc;
-        total += rc;
-        if (g->n_staged == 0  ||  g->n_staged < g->n_attached)
-            break;
+        if (core->handles[c]  &&  core->run[c] > 0)
+        {
+            deliver((modem_obj_t *) core->handles[c], g->events + (size_t) c*cap, (g->counts[c] < cap)  ?  g->counts[c]  :  cap,
+                    g->qam  ?  g->qam + (size_t) c*qcap*7  :  NULL, g->qam  ?  ((g->qcounts[c] < qcap)  ?  g->qcounts[c]  :  qcap)  :  0);
+        }
     }
-    return total;
 }
 
 int spangpu_modem_group_flush(spangpu_modem_group_t *g)
 {
-    int rc;
-
-    if (g == NULL)
-        return SPANGPU_ERR_BAD_ARG;
-    pthread_mutex_lock(&g->lock);
-    rc = group_flush_locked(g);
-    pthread_mutex_unlock(&g->lock);
-    return rc;
+    return (g)  ?  grp_flush(&g->core)  :  SPANGPU_ERR_BAD_ARG;
 }
 
 static void obj_logging_init(modem_obj_t *o)
@@ -258,10 +203,18 @@ static void obj_logging_init(modem_obj_t *o)
     o->logging.protocol = (o->kind == SPANGPU_V29)  ?  "V.29 RX"  :  (o->kind == SPANGPU_V27TER)  ?  "V.27ter RX"  :  "V.17 RX";
 }
 
-/* A new object on a free slot of the group.  The slot is tested and claimed under the group lock (two threads attaching
-   the same slot: one wins), and its channel gets the words of a fresh receiver -- the slot may have served an earlier
-   call, whose object was freed mid-signal with its own cutoff: the reference's xxx_rx_init() starts from a memset()
-   struct whatever the storage held (v29rx.c:1100-1131). */
+/* The channel of a slot being claimed on a shared bank gets the words of a fresh receiver -- the slot may have served an
+   earlier call, whose object was freed mid-signal with its own cutoff: the reference's xxx_rx_init() starts from a memset()
+   struct whatever the storage held (v29rx.c:1100-1131).  If that fails the attach is refused (a tone group does not look). */
+static int group_fresh(grp_core_t *core, int channel, void *arg)
+{
+    spangpu_modem_group_t *g = (spangpu_modem_group_t *) core;
+
+    (void) arg;
+    return spangpu_modem_set_state(g->bank, channel, g->pristine);
+}
+
+/* A new object on a free slot of the group; a private object's bank is new, and is left as it was made. */
 static modem_obj_t *obj_new(size_t size, int kind, spangpu_modem_group_t *g, int channel, int private_grp, int bit_rate,
                             span_put_bit_func_t put_bit, void *user_data)
 {
@@ -278,17 +231,11 @@ static modem_obj_t *obj_new(size_t size, int kind, spangpu_modem_group_t *g, int
     o->put_bit_user_data = user_data;
     obj_logging_init(o);
     spangpu_modem_state_words(kind, &o->n_floats, NULL);
-    pthread_mutex_lock(&g->lock);
-    if (g->handles[channel]
-        ||  (!private_grp  &&  spangpu_modem_set_state(g->bank, channel, g->pristine) < 0))
+    if (grp_claim(&g->core, channel, o, (private_grp)  ?  NULL  :  group_fresh, NULL) < 0)
     {
-        pthread_mutex_unlock(&g->lock);
         free(o);
         return NULL;
     }
-    g->handles[channel] = o;
-    g->n_attached++;
-    pthread_mutex_unlock(&g->lock);
     return o;
 }
 
@@ -310,7 +257,7 @@ static modem_obj_t *obj_init(size_t size, int kind, int bit_rate, span_put_bit_f
 static modem_obj_t *obj_attach(size_t size, int kind, spangpu_modem_group_t *g, int channel,
                                span_put_bit_func_t put_bit, void *user_data)
 {
-    if (g == NULL  ||  g->kind != kind  ||  channel < 0  ||  channel >= g->n_ch)
+    if (g == NULL  ||  g->kind != kind  ||  channel < 0  ||  channel >= g->core.n_ch)
         return NULL;
     return obj_new(size, kind, g, channel, 0, g->bit_rate, put_bit, user_data);
 }
@@ -325,9 +272,9 @@ static void obj_set_qam(modem_obj_t *o, qam_report_handler_t handler, void *user
 
     o->qam_report = handler;
     o->qam_user_data = user_data;
-    for (c = 0;  c < g->n_ch;  c++)
+    for (c = 0;  c < g->core.n_ch;  c++)
     {
-        if (g->handles[c]  &&  ((modem_obj_t *) g->handles[c])->qam_report)
+        if (g->core.handles[c]  &&  ((modem_obj_t *) g->core.handles[c])->qam_report)
             any = 1;
     }
     if (any != g->qam_tap)
@@ -337,52 +284,45 @@ static void obj_set_qam(modem_obj_t *o, qam_report_handler_t handler, void *user
     }
 }
 
+/* A shared bank advances in ticks: a frame per receiver that has one (any thread may stage; one submitter per receiver, as
+   for a spandsp object).  The tick runs when every attached receiver has staged, or when its owner calls
+   spangpu_modem_group_flush() at the deadline.  Nothing is dropped silently: a frame longer than the group was made for, or
+   a second frame for a receiver before the tick has run, is refused with -1 (a tone group tells the two apart). */
+static int group_stage(grp_core_t *core, int channel, const int16_t amp[], int len)
+{
+    spangpu_modem_group_t *g = (spangpu_modem_group_t *) core;
+
+    if (len > core->max_samples  ||  grp_stage_begin(core, channel) < 0)
+        return -1;
+    memcpy(g->stage + (size_t) channel*core->max_samples, amp, len*sizeof(int16_t));
+    return (grp_stage_commit(core, channel, len) < 0)  ?  -1  :  0;
+}
+
+/* A piece of a private object's buffer: a tick that fails is not reported, and the pieces after it still run (a tone
+   object stops at the first and returns -1). */
+static int group_stage_private(grp_core_t *core, int channel, const int16_t amp[], int len)
+{
+    (void) group_stage(core, channel, amp, len);
+    return 0;
+}
+
 static int obj_rx(modem_obj_t *o, const int16_t amp[], int len)
 {
-    spangpu_modem_group_t *g = o->grp;
-    int n;
-    int rc;
+    grp_core_t *core = &o->grp->core;
 
     if (len <= 0)
         return 0;                           /* as the reference: nothing to do (v29rx.c:867-965 loops over len) */
-    if (o->private_grp)
-    {
-        if (g->delivering)
-            return -1;                      /* called from inside its own callback: refused, not dropped (the staging row is in use) */
-        while (len > 0)
-        {
-            n = (len > g->max_samples)  ?  g->max_samples  :  len;
-            memcpy(g->stage, amp, n*sizeof(int16_t));
-            g->lens[0] = n;
-            g->n_staged = 1;
-            spangpu_modem_group_flush(g);
-            amp += n;
-            len -= n;
-        }
-        return 0;
-    }
-    /* A shared bank advances in ticks: a frame per receiver that has one (any thread may stage; one submitter per
-       receiver, as for a spandsp object).  The tick runs when every attached receiver has staged, or when its owner calls
-       spangpu_modem_group_flush() at the deadline.  Nothing is dropped silently: a frame longer than the group was made
-       for, or a second frame for a receiver before the tick has run, is refused with -1. */
-    if (len > g->max_samples)
+    if (!o->private_grp)
+        return group_stage(core, o->channel, amp, len);
+    /* Called from inside its own callback: refused, not dropped (a tone object's frame is accepted, and runs when the
+       delivery is over). */
+    if (grp_in_callback(core))
         return -1;
-    pthread_mutex_lock(&g->lock);
-    if (g->lens[o->channel])
-    {
-        pthread_mutex_unlock(&g->lock);
-        return -1;
-    }
-    pthread_mutex_unlock(&g->lock);
-    memcpy(g->stage + (size_t) o->channel*g->max_samples, amp, len*sizeof(int16_t));
-    pthread_mutex_lock(&g->lock);
-    g->lens[o->channel] = len;
-    g->n_staged++;
-    rc = (g->n_staged >= g->n_attached)  ?  group_flush_locked(g)  :  0;
-    pthread_mutex_unlock(&g->lock);
-    return (rc < 0)  ?  -1  :  0;
+    return grp_feed_private(core, amp, len, group_stage_private);
 }
 
+/* The slot is released whether or not it is held (a tone group looks first); a private object detaches, then destroys its
+   group (a tone object only destroys it). */
 static int obj_free(modem_obj_t *o)
 {
     if (o == NULL)
@@ -391,22 +331,9 @@ static int obj_free(modem_obj_t *o)
         obj_set_qam(o, NULL, NULL);
     if (o->grp)
     {
-        spangpu_modem_group_t *g = o->grp;
-
-        pthread_mutex_lock(&g->lock);
-        g->handles[o->channel] = NULL;
-        g->n_attached--;
-        if (g->lens[o->channel])
-        {
-            /* its frame of the tick in progress goes with it */
-            g->lens[o->channel] = 0;
-            g->n_staged--;
-        }
-        if (!o->private_grp  &&  g->n_staged > 0  &&  g->n_staged >= g->n_attached)
-            group_flush_locked(g);          /* it was the one the others were waiting for */
-        pthread_mutex_unlock(&g->lock);
+        grp_release(&o->grp->core, o->channel);
         if (o->private_grp)
-            spangpu_modem_group_destroy(g);
+            spangpu_modem_group_destroy(o->grp);
     }
     free(o);
     return 0;
@@ -427,12 +354,10 @@ static int obj_restart(modem_obj_t *o, int bit_rate, int flag)
         if (!o->private_grp)
             return -1;                      /* a shared bank runs one rate */
         words = spangpu_modem_get_state(g->bank, 0, o->words);
-        if (words < 0  ||  (ng = spangpu_modem_group_create(0, o->kind, 1, bit_rate, g->max_samples)) == NULL)
+        if (words < 0  ||  (ng = spangpu_modem_group_create(0, o->kind, 1, bit_rate, g->core.max_samples)) == NULL)
             return -1;
         spangpu_modem_set_state(ng->bank, 0, o->words);
-        ng->handles[0] = o;
-        ng->n_attached = 1;
-        g->handles[0] = NULL;
+        grp_claim(&ng->core, 0, o, NULL, NULL);
         spangpu_modem_group_destroy(g);
         o->grp = g = ng;
     }

@@ -11,12 +11,10 @@
  */
 #include <limits.h>
 #include <math.h>
-#include <pthread.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include "spangpu_spandsp.h"
 #include "spangpu_refstate.h"
+#include "shim_group.h"
 
 #define SUPER_TONE_BINS     128             /* src/spandsp/private/super_tone_rx.h:29 */
 
@@ -25,20 +23,13 @@
 /* ------------------------------------------------------------------------------------ */
 struct spangpu_group_s
 {
+    grp_core_t core;            /* the staging protocol: shim_group.h */
     spangpu_bank_t *bank;
     int kind;
-    int n_ch;
-    int max_samples;
     int16_t *stage;             /* [n_ch][max_samples] */
-    void **handles;             /* per channel: the attached state object or NULL */
-    int32_t *lens;              /* per channel: samples staged for the tick being collected (0 = none) */
-    int32_t *run;               /* ... and of the tick whose callbacks are being delivered */
-    int delivering;             /* a tick's callbacks are being made: staging from inside them waits for the next flush */
-    int n_attached;
-    int n_staged;
-    pthread_mutex_t lock;       /* staging, attach / detach and the tick itself (recursive: callbacks may call back in) */
-    spangpu_block_t *blocks;
+    spangpu_block_t *blocks;    /* the records of the tick being delivered */
     int blocks_cap;
+    int n_blocks;
     spangpu_tone_params_t params;
 };
 
@@ -163,79 +154,14 @@ struct goertzel_state_s
 static void replay(spangpu_group_t *g, int channel, const spangpu_block_t *b, int n);
 static void end_of_call(spangpu_group_t *g, int channel);
 
-spangpu_group_t *spangpu_group_create(int device, int kind, int n_channels, int max_samples,
-                                      const spangpu_tone_params_t *params)
+/* The tick's launch, and its block records brought to the host */
+static int group_run(grp_core_t *core)
 {
-    spangpu_group_t *g;
-
-    if (n_channels <= 0  ||  max_samples <= 0)
-        return NULL;
-    if ((g = (spangpu_group_t *) calloc(1, sizeof(*g))) == NULL)
-        return NULL;
-    g->kind = kind;
-    g->n_ch = n_channels;
-    g->max_samples = max_samples;
-    if (params)
-        g->params = *params;
-    if (spangpu_bank_create(&g->bank, device, kind, n_channels, &g->params, sizeof(g->params)) != SPANGPU_OK)
-    {
-        free(g);
-        return NULL;
-    }
-    g->stage = (int16_t *) calloc((size_t) n_channels*max_samples, sizeof(int16_t));
-    g->handles = (void **) calloc(n_channels, sizeof(void *));
-    g->lens = (int32_t *) calloc(n_channels, sizeof(int32_t));
-    g->run = (int32_t *) calloc(n_channels, sizeof(int32_t));
-    {
-        pthread_mutexattr_t at;
-
-        pthread_mutexattr_init(&at);
-        pthread_mutexattr_settype(&at, PTHREAD_MUTEX_RECURSIVE);
-        pthread_mutex_init(&g->lock, &at);
-        pthread_mutexattr_destroy(&at);
-    }
-    if (g->stage == NULL  ||  g->handles == NULL  ||  g->lens == NULL  ||  g->run == NULL)
-    {
-        spangpu_group_destroy(g);
-        return NULL;
-    }
-    return g;
-}
-
-int spangpu_group_destroy(spangpu_group_t *g)
-{
-    if (g == NULL)
-        return SPANGPU_OK;
-    spangpu_bank_destroy(g->bank);
-    free(g->stage);
-    free(g->handles);
-    free(g->lens);
-    free(g->run);
-    free(g->blocks);
-    pthread_mutex_destroy(&g->lock);
-    free(g);
-    return SPANGPU_OK;
-}
-
-spangpu_bank_t *spangpu_group_bank(spangpu_group_t *g)
-{
-    return (g)  ?  g->bank  :  NULL;
-}
-
-/* Run the tick with the channels that have staged a frame.  The others sit it out -- their detectors are exactly as they
-   were, as the reference's are for a channel whose xxx_rx() was not called -- and may stage for the next one.  Returns
-   the number of channels that took part. */
-static int group_flush_locked_tick(spangpu_group_t *g)
-{
+    spangpu_group_t *g = (spangpu_group_t *) core;
     int rc;
     int n;
-    int i;
-    int start;
-    int ch;
 
-    if (g->n_staged == 0)
-        return 0;
-    rc = spangpu_bank_rx_var(g->bank, g->stage, SPANGPU_MEM_HOST, g->lens, g->max_samples, g->max_samples);
+    rc = spangpu_bank_rx_var(g->bank, g->stage, SPANGPU_MEM_HOST, core->lens, core->max_samples, core->max_samples);
     n = (rc < 0)  ?  rc  :  spangpu_bank_blocks(g->bank, NULL, 0);
     if (n > g->blocks_cap)
     {
@@ -249,131 +175,134 @@ static int group_flush_locked_tick(spangpu_group_t *g)
     }
     if (n > 0)
         n = spangpu_bank_blocks(g->bank, g->blocks, g->blocks_cap);
-    /* The tick is over, whatever came of it: its frames leave the staging area before anything is delivered -- a failure
-       must not make every later call a "second frame" or run the same frames again, and a callback that stages a new
-       frame finds a clean slate (that frame waits for the next tick). */
-    rc = g->n_staged;
-    memcpy(g->run, g->lens, sizeof(int32_t)*g->n_ch);
-    memset(g->lens, 0, sizeof(int32_t)*g->n_ch);
-    g->n_staged = 0;
-    if (n < 0)
-        return n;
-    /* Records arrive in (channel, block) order: replay channel by channel. */
-    g->delivering = 1;
-    start = 0;
-    for (ch = 0;  ch < g->n_ch;  ch++)
+    g->n_blocks = n;
+    return n;
+}
+
+/* Records arrive in (channel, block) order: replay channel by channel. */
+static void group_deliver(grp_core_t *core)
+{
+    spangpu_group_t *g = (spangpu_group_t *) core;
+    int start = 0;
+    int i;
+    int ch;
+
+    for (ch = 0;  ch < core->n_ch;  ch++)
     {
         i = start;
-        while (i < n  &&  g->blocks[i].channel == ch)
+        while (i < g->n_blocks  &&  g->blocks[i].channel == ch)
             i++;
-        if (g->handles[ch]  &&  g->run[ch] > 0)
+        if (core->handles[ch]  &&  core->run[ch] > 0)
         {
             replay(g, ch, &g->blocks[start], i - start);
             end_of_call(g, ch);
         }
         start = i;
     }
-    g->delivering = 0;
-    return rc;
 }
 
-/* The tick(s) that are due.  Callbacks may stage frames (a put_bit handler that answers by feeding its receiver, say): while
-   a tick's callbacks run, a flush from inside them does nothing (`delivering`); when they are over, the tick those frames
-   complete -- every attached channel has staged again -- runs at once instead of waiting for somebody to ask, so that no
-   later xxx_rx() is refused as a second frame of a tick that nobody would ever have run. */
-static int group_flush_locked(spangpu_group_t *g)
+spangpu_group_t *spangpu_group_create(int device, int kind, int n_channels, int max_samples,
+                                      const spangpu_tone_params_t *params)
 {
-    int total = 0;
-    int rc;
+    spangpu_group_t *g;
 
-    if (g->delivering)
-        return 0;
-    for (;;)
+    if (n_channels <= 0  ||  max_samples <= 0)
+        return NULL;
+    if ((g = (spangpu_group_t *) calloc(1, sizeof(*g))) == NULL)
+        return NULL;
+    g->kind = kind;
+    if (params)
+        g->params = *params;
+    if (spangpu_bank_create(&g->bank, device, kind, n_channels, &g->params, sizeof(g->params)) != SPANGPU_OK)
     {
-        if ((rc = group_flush_locked_tick(g)) < 0)
-            return rc;
-        total += rc;
-        if (g->n_staged == 0  ||  g->n_staged < g->n_attached)
-            break;
+        free(g);
+        return NULL;
     }
-    return total;
+    g->stage = (int16_t *) calloc((size_t) n_channels*max_samples, sizeof(int16_t));
+    if (grp_init(&g->core, n_channels, max_samples, group_run, group_deliver) < 0  ||  g->stage == NULL)
+    {
+        spangpu_group_destroy(g);
+        return NULL;
+    }
+    return g;
+}
+
+int spangpu_group_destroy(spangpu_group_t *g)
+{
+    if (g == NULL)
+        return SPANGPU_OK;
+    spangpu_bank_destroy(g->bank);
+    free(g->stage);
+    free(g->blocks);
+    grp_free(&g->core);
+    free(g);
+    return SPANGPU_OK;
+}
+
+spangpu_bank_t *spangpu_group_bank(spangpu_group_t *g)
+{
+    return (g)  ?  g->bank  :  NULL;
 }
 
 int spangpu_group_flush(spangpu_group_t *g)
 {
-    int rc;
-
-    if (g == NULL)
-        return SPANGPU_ERR_BAD_ARG;
-    pthread_mutex_lock(&g->lock);
-    rc = group_flush_locked(g);
-    pthread_mutex_unlock(&g->lock);
-    return rc;
+    return (g)  ?  grp_flush(&g->core)  :  SPANGPU_ERR_BAD_ARG;
 }
 
 /* Stage one channel's frame (any thread); the tick runs when every attached channel has staged, or when the owner of
-   the tick calls spangpu_group_flush() at its deadline.  The frame is copied outside the lock: a channel has one
-   submitter, as a spandsp object has. */
-static int group_stage(spangpu_group_t *g, int channel, const int16_t amp[], int samples)
+   the tick calls spangpu_group_flush() at its deadline.  This family tells a frame that is too long from a second frame
+   (the xxx_rx() calls make -1 of both), and a private object fed from inside its own callback comes through here like any
+   other: the frame is accepted and runs as the next tick when delivery ends. */
+static int group_stage(grp_core_t *core, int channel, const int16_t amp[], int samples)
 {
-    int rc;
+    spangpu_group_t *g = (spangpu_group_t *) core;
 
     if (samples <= 0)
         return 0;
-    if (samples > g->max_samples)
+    if (samples > core->max_samples)
         return SPANGPU_ERR_BAD_ARG;
-    pthread_mutex_lock(&g->lock);
-    if (g->lens[channel])
-    {
-        pthread_mutex_unlock(&g->lock);
+    if (grp_stage_begin(core, channel) < 0)
         return SPANGPU_ERR_STATE;       /* second frame before the tick ran */
-    }
-    pthread_mutex_unlock(&g->lock);
-    memcpy(g->stage + (size_t) channel*g->max_samples, amp, sizeof(int16_t)*samples);
-    pthread_mutex_lock(&g->lock);
-    g->lens[channel] = samples;
-    g->n_staged++;
-    rc = (g->n_staged >= g->n_attached)  ?  group_flush_locked(g)  :  0;
-    pthread_mutex_unlock(&g->lock);
-    return rc;
+    memcpy(g->stage + (size_t) channel*core->max_samples, amp, sizeof(int16_t)*samples);
+    return grp_stage_commit(core, channel, samples);
+}
+
+/* A claimed slot starts from a reset channel (reset under the lock that hands the slot over); what the reset returns is not
+   looked at (the modem and line groups refuse the attach when theirs fails). */
+static int group_fresh(grp_core_t *core, int channel, void *arg)
+{
+    (void) arg;
+    spangpu_bank_reset_channel(((spangpu_group_t *) core)->bank, channel, 0);
+    return 0;
 }
 
 static int group_attach(spangpu_group_t *g, int channel, void *handle)
 {
-    if (g == NULL  ||  channel < 0  ||  channel >= g->n_ch)
+    if (g == NULL  ||  channel < 0  ||  channel >= g->core.n_ch)
         return -1;
-    pthread_mutex_lock(&g->lock);
-    if (g->handles[channel])
-    {
-        pthread_mutex_unlock(&g->lock);
-        return -1;
-    }
-    g->handles[channel] = handle;
-    g->n_attached++;
-    spangpu_bank_reset_channel(g->bank, channel, 0);
-    pthread_mutex_unlock(&g->lock);
-    return 0;
+    return grp_claim(&g->core, channel, handle, group_fresh, NULL);
 }
 
+/* A private object's group of one: a new bank, nothing to make fresh */
+static spangpu_group_t *group_private(void *handle, int kind, int max_samples, const spangpu_tone_params_t *params)
+{
+    spangpu_group_t *g;
+
+    if ((g = spangpu_group_create(0, kind, 1, max_samples, params)) != NULL)
+        grp_claim(&g->core, 0, handle, NULL, NULL);
+    return g;
+}
+
+/* This family releases a slot only if it is held (the modem and line groups release unconditionally), and a private object
+   destroys its group without detaching (theirs detach first). */
 static void group_detach(spangpu_group_t *g, int channel)
 {
     if (g == NULL)
         return;
-    pthread_mutex_lock(&g->lock);
-    if (g->handles[channel])
-    {
-        g->handles[channel] = NULL;
-        g->n_attached--;
-        if (g->lens[channel])
-        {
-            g->lens[channel] = 0;
-            g->n_staged--;
-        }
-        /* the channels that remain may all have been waiting for this one */
-        if (g->n_staged > 0  &&  g->n_staged >= g->n_attached)
-            group_flush_locked(g);
-    }
-    pthread_mutex_unlock(&g->lock);
+    pthread_mutex_lock(&g->core.lock);
+    if (g->core.handles[channel])
+        grp_release(&g->core, channel);
+    pthread_mutex_unlock(&g->core.lock);
 }
 
 /* ------------------------------------------------------------------------------------ */
@@ -450,20 +379,18 @@ static int dtmf_private_rebuild(dtmf_rx_state_t *s, int max_samples)
 
     if (s->grp)
     {
-        if (!s->dirty  &&  max_samples <= s->grp->max_samples)
+        if (!s->dirty  &&  max_samples <= s->grp->core.max_samples)
             return 0;
         nf = spangpu_bank_get_state(s->grp->bank, 0, f, 64, w, 4);
         have_state = (nf > 0);
-        if (max_samples < s->grp->max_samples)
-            max_samples = s->grp->max_samples;
+        if (max_samples < s->grp->core.max_samples)
+            max_samples = s->grp->core.max_samples;
         spangpu_group_destroy(s->grp);
         s->grp = NULL;
     }
     s->params.report_mode = (s->realtime_callback)  ?  SPANGPU_REPORT_REALTIME  :  SPANGPU_REPORT_DIGITS;
-    if ((s->grp = spangpu_group_create(0, SPANGPU_DTMF, 1, (max_samples < 160)  ?  160  :  max_samples, &s->params)) == NULL)
+    if ((s->grp = group_private(s, SPANGPU_DTMF, (max_samples < 160)  ?  160  :  max_samples, &s->params)) == NULL)
         return -1;
-    s->grp->handles[0] = s;
-    s->grp->n_attached = 1;
     if (have_state)
         spangpu_bank_set_state(s->grp->bank, 0, f, nf, w, 4);
     s->dirty = 0;
@@ -604,9 +531,10 @@ void dtmf_rx_parms(dtmf_rx_state_t *s, int filter_dialtone, float twist, float r
         p.reverse_twist_db = reverse_twist;
         p.threshold_dbm0 = threshold;
         p.set_mask = SPANGPU_TP_TWIST | SPANGPU_TP_REVERSE_TWIST | SPANGPU_TP_THRESHOLD;    /* the bank applies dtmf.c:436-444's tests */
-        pthread_mutex_lock(&s->grp->lock);
+        /* (the group's lock taken outside shim_group.h: it covers every call on the bank, and this one is not a tick) */
+        pthread_mutex_lock(&s->grp->core.lock);
         spangpu_bank_set_channel_params(s->grp->bank, s->channel, &p, sizeof(p));
-        pthread_mutex_unlock(&s->grp->lock);
+        pthread_mutex_unlock(&s->grp->core.lock);
         return;
     }
     if (filter_dialtone >= 0)
@@ -638,25 +566,22 @@ void dtmf_rx_parms(dtmf_rx_state_t *s, int filter_dialtone, float twist, float r
     dtmf_private_rebuild(s, 160);
 }
 
+/* One object's frame: a shared group stages it; a private object runs it now, in pieces no longer than the staging row.
+   Whatever went wrong is -1 to the caller. */
+static int stage_any(spangpu_group_t *g, int private_grp, int channel, const int16_t amp[], int samples)
+{
+    if (g == NULL)
+        return -1;
+    if (!private_grp)
+        return (group_stage(&g->core, channel, amp, samples) < 0)  ?  -1  :  0;
+    return (grp_feed_private(&g->core, amp, samples, group_stage) < 0)  ?  -1  :  0;
+}
+
 int dtmf_rx(dtmf_rx_state_t *s, const int16_t amp[], int samples)
 {
-    int pos;
-    int n;
-
-    if (s == NULL  ||  s->grp == NULL)
+    if (s == NULL)
         return -1;
-    if (!s->private_grp)
-        return (group_stage(s->grp, s->channel, amp, samples) < 0)  ?  -1  :  0;
-    /* private object: run the frame now, in pieces no longer than the staging row */
-    for (pos = 0;  pos < samples;  pos += n)
-    {
-        n = samples - pos;
-        if (n > s->grp->max_samples)
-            n = s->grp->max_samples;
-        if (group_stage(s->grp, 0, amp + pos, n) < 0)
-            return -1;
-    }
-    return 0;
+    return stage_any(s->grp, s->private_grp, s->channel, amp, samples);
 }
 
 int dtmf_rx_fillin(dtmf_rx_state_t *s, int samples)
@@ -739,13 +664,11 @@ bell_mf_rx_state_t *bell_mf_rx_init(bell_mf_rx_state_t *s, digits_rx_callback_t 
         if ((s = (bell_mf_rx_state_t *) calloc(1, sizeof(*s))) == NULL)
             return NULL;
         s->private_grp = 1;
-        if ((s->grp = spangpu_group_create(0, SPANGPU_BELL_MF, 1, 160, NULL)) == NULL)
+        if ((s->grp = group_private(s, SPANGPU_BELL_MF, 160, NULL)) == NULL)
         {
             free(s);
             return NULL;
         }
-        s->grp->handles[0] = s;
-        s->grp->n_attached = 1;
     }
     else
     {
@@ -797,26 +720,6 @@ int bell_mf_rx_free(bell_mf_rx_state_t *s)
     return 0;
 }
 
-static int stage_any(spangpu_group_t *g, int private_grp, int channel, const int16_t amp[], int samples)
-{
-    int pos;
-    int n;
-
-    if (g == NULL)
-        return -1;
-    if (!private_grp)
-        return (group_stage(g, channel, amp, samples) < 0)  ?  -1  :  0;
-    for (pos = 0;  pos < samples;  pos += n)
-    {
-        n = samples - pos;
-        if (n > g->max_samples)
-            n = g->max_samples;
-        if (group_stage(g, 0, amp + pos, n) < 0)
-            return -1;
-    }
-    return 0;
-}
-
 int bell_mf_rx(bell_mf_rx_state_t *s, const int16_t amp[], int samples)
 {
     return stage_any(s->grp, s->private_grp, s->channel, amp, samples);
@@ -865,13 +768,11 @@ r2_mf_rx_state_t *r2_mf_rx_init(r2_mf_rx_state_t *s, bool fwd, span_tone_report_
         s->private_grp = 1;
         memset(&p, 0, sizeof(p));
         p.r2_fwd = fwd;
-        if ((s->grp = spangpu_group_create(0, SPANGPU_R2_MF, 1, 160, &p)) == NULL)
+        if ((s->grp = group_private(s, SPANGPU_R2_MF, 160, &p)) == NULL)
         {
             free(s);
             return NULL;
         }
-        s->grp->handles[0] = s;
-        s->grp->n_attached = 1;
     }
     else
     {
@@ -1221,13 +1122,11 @@ super_tone_rx_state_t *super_tone_rx_init(super_tone_rx_state_t *s, super_tone_r
             return NULL;
         s->private_grp = 1;
         st_params(desc, &p);
-        if ((s->grp = spangpu_group_create(0, SPANGPU_SUPER_TONE, 1, 160, &p)) == NULL)
+        if ((s->grp = group_private(s, SPANGPU_SUPER_TONE, 160, &p)) == NULL)
         {
             free(s);
             return NULL;
         }
-        s->grp->handles[0] = s;
-        s->grp->n_attached = 1;
     }
     else
     {
@@ -1571,7 +1470,7 @@ float goertzel_result(goertzel_state_t *s)
 /* ------------------------------------------------------------------------------------ */
 static void replay(spangpu_group_t *g, int channel, const spangpu_block_t *b, int n)
 {
-    void *h = g->handles[channel];
+    void *h = g->core.handles[channel];
 
     switch (g->kind)
     {
@@ -1592,7 +1491,7 @@ static void replay(spangpu_group_t *g, int channel, const spangpu_block_t *b, in
 
 static void end_of_call(spangpu_group_t *g, int channel)
 {
-    void *h = g->handles[channel];
+    void *h = g->core.handles[channel];
 
     switch (g->kind)
     {
