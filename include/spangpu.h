@@ -805,14 +805,37 @@ SPANGPU_API int spangpu_sigtone_tx_get_state(spangpu_sigtone_tx_t *bank, int cha
  *   spangpu_modemtx_power()                  v29_tx_power() / v27ter_tx_power()     src/v29tx.c:322-338, src/v27ter_tx.c:352-364
  *   spangpu_modemtx_restart()                v29_tx_restart() / v27ter_tx_restart() src/v29tx.c:365-404, src/v27ter_tx.c:384-409
  *   spangpu_modemtx_restart_ex()             v17_tx_restart(s, rate, tep, short_train)  src/v17tx.c:397-450 (and _power: :371-383)
- * The data bits of channel c come from a 15 bit LFSR (x^15 + x^14 + 1) seeded with seeds[c] (NULL: a seed per
- * channel is derived from its index); a get_bit() callback, and with it the end-of-data shutdown sequence, is
- * not replayed.
+ *   spangpu_modemtx_put_bits() / _end_of_data() / _events()   the caller's get_bit and status handler, see below
+ * Where a data bit comes from is the bank's (spangpu_modemtx_create_ex(); spangpu_modemtx_create() is the LFSR form):
+ *   SPANGPU_MODEMTX_LFSR    a 15 bit LFSR (x^15 + x^14 + 1) per channel, seeded with seeds[c] (NULL: a seed per channel is
+ *                           derived from its index): noise-like data for the receiver banks.
+ *   SPANGPU_MODEMTX_QUEUE   the caller's data: a ring of queue_bits bits per channel in HBM, filled by
+ *                           spangpu_modemtx_put_bits().  A bit is taken exactly where the reference calls the caller's get_bit
+ *                           (never while training).  An empty ring answers 1 and consumes nothing (a get_bit that answers 1,
+ *                           as spangpu_fsktx_*); once spangpu_modemtx_end_of_data() is set it answers
+ *                           SIG_STATUS_END_OF_DATA instead: that bit and every later one is 1, the rest of the baud is still
+ *                           sent, and the shutdown symbols follow -- 32 bauds of scrambled ones (src/v29tx.c:180-199,
+ *                           src/v27ter_tx.c:215-235); V.17: ones, then 48 bauds of silence (src/v17tx.c:273-289).  The call in
+ *                           which the shutdown ends is whole; every later call yields 0 samples for the channel (its row is
+ *                           zero-filled, as the other sender banks do) until it is restarted.  _restart() / _restart_ex()
+ *                           empty the channel's ring and clear its end-of-data flag.
+ * spangpu_modemtx_events() lists what the status handler of each channel would have been called with in the last call:
+ * SPANGPU_MODEMTX_END_OF_DATA and SPANGPU_MODEMTX_SHUTDOWN_COMPLETE, the values of SIG_STATUS_END_OF_DATA and
+ * SIG_STATUS_SHUTDOWN_COMPLETE (src/spandsp/async.h).  V.17 never reports the second: v17tx.c:275-288 returns its silence
+ * before the test it would be reported from.
  */
+#define SPANGPU_MODEMTX_LFSR                0
+#define SPANGPU_MODEMTX_QUEUE               1
+#define SPANGPU_MODEMTX_END_OF_DATA         (-7)
+#define SPANGPU_MODEMTX_SHUTDOWN_COMPLETE   (-10)
+
 typedef struct spangpu_modemtx_s spangpu_modemtx_t;
 
 SPANGPU_API int spangpu_modemtx_create(spangpu_modemtx_t **tx, int device, int modem, int n_channels, int bit_rate, int tep,
                                        const uint32_t *seeds);
+/* seeds: used by SPANGPU_MODEMTX_LFSR; queue_bits: the capacity of a ring, SPANGPU_MODEMTX_QUEUE */
+SPANGPU_API int spangpu_modemtx_create_ex(spangpu_modemtx_t **tx, int device, int modem, int n_channels, int bit_rate, int tep,
+                                          int bit_source, const uint32_t *seeds, int queue_bits);
 SPANGPU_API void spangpu_modemtx_destroy(spangpu_modemtx_t *tx);
 SPANGPU_API int spangpu_modemtx_channels(const spangpu_modemtx_t *tx);
 SPANGPU_API int spangpu_modemtx_set_stream(spangpu_modemtx_t *tx, void *hip_stream);
@@ -827,6 +850,36 @@ SPANGPU_API int spangpu_modemtx_restart(spangpu_modemtx_t *tx, int channel, int 
 SPANGPU_API int spangpu_modemtx_restart_ex(spangpu_modemtx_t *tx, int channel, int bit_rate, int tep, int short_train);
 /* pcm[channel*stride + i], i < samples, where mem says; returns samples */
 SPANGPU_API int spangpu_modemtx_tx(spangpu_modemtx_t *tx, int mem, int16_t *pcm, long long stride, int samples);
+/* the same, and lens[channel] (where mem says; may be NULL) = what xxx_tx() would have returned: samples, or 0 after shutdown */
+SPANGPU_API int spangpu_modemtx_tx_lens(spangpu_modemtx_t *tx, int mem, int16_t *pcm, long long stride, int samples, int32_t *lens);
+/* For a caller that makes one xxx_tx() call of several launches: the next `samples` of the call the last launch began.  The
+   test for the end of the shutdown, which the reference makes at the start of a call only, is not made again. */
+SPANGPU_API int spangpu_modemtx_tx_continue(spangpu_modemtx_t *tx, int mem, int16_t *pcm, long long stride, int samples, int32_t *lens);
+/* SPANGPU_MODEMTX_QUEUE banks.  Channel first + i gets lens[i] bits, packed LSB first from bits[i*stride] (host arrays);
+   accepted[i] (may be NULL) = how many of them its ring had room for. */
+SPANGPU_API int spangpu_modemtx_put_bits(spangpu_modemtx_t *tx, int first, int n, const uint8_t *bits, int stride, const int32_t *lens,
+                                         int32_t *accepted);
+SPANGPU_API int spangpu_modemtx_queued(spangpu_modemtx_t *tx, int channel);
+SPANGPU_API int spangpu_modemtx_end_of_data(spangpu_modemtx_t *tx, int channel, int on);
+/* The status calls of the last spangpu_modemtx_tx(): channels[i] got kinds[i] (SPANGPU_MODEMTX_END_OF_DATA or
+   _SHUTDOWN_COMPLETE), by channel and, for a channel with both, in that order, which is the reference's.  Returns how many.
+   Valid until the next call on this bank. */
+SPANGPU_API int spangpu_modemtx_events(spangpu_modemtx_t *tx, const int32_t **channels, const int32_t **kinds);
+/* Host code, no device needed: where a sender is in its training / data / shutdown sequence, stepped call by call.
+   spangpu_modemtx_cursor_advance() returns how many get_bit calls a xxx_tx() call of `samples` makes from this state -- the one
+   that answers SIG_STATUS_END_OF_DATA included -- and moves the cursor past the call.  bits_before_end < 0: the data does not
+   end in this call.  Otherwise the get_bit call after that many bits answers SIG_STATUS_END_OF_DATA, and no more are made. */
+typedef struct
+{
+    int modem;              /* SPANGPU_V29, SPANGPU_V27TER or SPANGPU_V17 */
+    int bit_rate;
+    int short_train;        /* V.17 */
+    int baud_phase;
+    int training_step;
+    int in_training;
+} spangpu_modemtx_cursor_t;
+SPANGPU_API int spangpu_modemtx_cursor_init(spangpu_modemtx_cursor_t *cur, int modem, int bit_rate, int tep, int short_train);
+SPANGPU_API long long spangpu_modemtx_cursor_advance(spangpu_modemtx_cursor_t *cur, int samples, long long bits_before_end);
 SPANGPU_API int spangpu_modemtx_state_words(void);
 SPANGPU_API int spangpu_modemtx_get_state(spangpu_modemtx_t *tx, int channel, int32_t *words);
 /* The pulse shaper tables as built by this library (host code): which = 0 V.29, 1 V.27ter 4800 bps, 2 V.27ter 2400 bps */

@@ -574,6 +574,79 @@ SPANGPU_API async_tx_state_t *async_tx_init(async_tx_state_t *s, int data_bits, 
 SPANGPU_API int async_tx_release(async_tx_state_t *s);
 SPANGPU_API int async_tx_free(async_tx_state_t *s);
 
+/* ---- V.29, V.27ter and V.17 senders (csrc/shim_modemtx.c) --------------------------------------------------
+ * Reference declarations being replaced:
+ *   v29_tx_init/_restart/_release/_free/_power/_set_get_bit/_set_modem_status_handler/_get_logging_state, v29_tx
+ *                                          src/spandsp/v29tx.h:110-170      src/v29tx.c:226-445
+ *   v27ter_tx_* (same set)                 src/spandsp/v27ter_tx.h:80-139   src/v27ter_tx.c:257-447
+ *   v17_tx_* (same set)                    src/spandsp/v17tx.h:97-158       src/v17tx.c:315-515
+ * A sender object is a one-channel bank with the bit queue as its source (spangpu.h, "modem transmitter banks"): plumbing
+ * for a caller that moves over one call at a time.  The path for scale is the bank: N channels per launch.
+ * xxx_tx(s, amp, len) steps a cursor (spangpu_modemtx_cursor_advance()) to learn how many bits the call needs, calls get_bit
+ * exactly that many times, in order, stops at SIG_STATUS_END_OF_DATA -- the status handler hears of it straight after that
+ * get_bit, as in the reference -- queues the bits and launches.  SIG_STATUS_SHUTDOWN_COMPLETE comes in the call whose samples
+ * end the shutdown (never from v17_tx, as in the reference), and later calls return 0.  Without a GPU the _init() return NULL.
+ */
+typedef struct
+{
+    spangpu_modemtx_t *bank;
+    spangpu_modemtx_cursor_t cursor;
+    span_get_bit_func_t get_bit;
+    void *get_bit_user_data;
+    span_modem_status_func_t status_handler;
+    void *status_user_data;
+    logging_state_t logging;
+    int16_t *row;
+    int row_cap;
+    int caller_storage;
+} spangpu_modemtx_object_t;
+
+typedef struct v29_tx_state_s v29_tx_state_t;
+typedef struct v27ter_tx_state_s v27ter_tx_state_t;
+typedef struct v17_tx_state_s v17_tx_state_t;
+struct v29_tx_state_s
+{
+    spangpu_modemtx_object_t o;
+};
+struct v27ter_tx_state_s
+{
+    spangpu_modemtx_object_t o;
+};
+struct v17_tx_state_s
+{
+    spangpu_modemtx_object_t o;
+};
+
+SPANGPU_API v29_tx_state_t *v29_tx_init(v29_tx_state_t *s, int bit_rate, bool tep, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API int v29_tx_restart(v29_tx_state_t *s, int bit_rate, bool tep);
+SPANGPU_API int v29_tx_release(v29_tx_state_t *s);
+SPANGPU_API int v29_tx_free(v29_tx_state_t *s);
+SPANGPU_API void v29_tx_power(v29_tx_state_t *s, float power);
+SPANGPU_API void v29_tx_set_get_bit(v29_tx_state_t *s, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API void v29_tx_set_modem_status_handler(v29_tx_state_t *s, span_modem_status_func_t handler, void *user_data);
+SPANGPU_API logging_state_t *v29_tx_get_logging_state(v29_tx_state_t *s);
+SPANGPU_API int v29_tx(v29_tx_state_t *s, int16_t amp[], int len);
+
+SPANGPU_API v27ter_tx_state_t *v27ter_tx_init(v27ter_tx_state_t *s, int bit_rate, bool tep, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API int v27ter_tx_restart(v27ter_tx_state_t *s, int bit_rate, bool tep);
+SPANGPU_API int v27ter_tx_release(v27ter_tx_state_t *s);
+SPANGPU_API int v27ter_tx_free(v27ter_tx_state_t *s);
+SPANGPU_API void v27ter_tx_power(v27ter_tx_state_t *s, float power);
+SPANGPU_API void v27ter_tx_set_get_bit(v27ter_tx_state_t *s, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API void v27ter_tx_set_modem_status_handler(v27ter_tx_state_t *s, span_modem_status_func_t handler, void *user_data);
+SPANGPU_API logging_state_t *v27ter_tx_get_logging_state(v27ter_tx_state_t *s);
+SPANGPU_API int v27ter_tx(v27ter_tx_state_t *s, int16_t amp[], int len);
+
+SPANGPU_API v17_tx_state_t *v17_tx_init(v17_tx_state_t *s, int bit_rate, bool tep, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API int v17_tx_restart(v17_tx_state_t *s, int bit_rate, bool tep, bool short_train);
+SPANGPU_API int v17_tx_release(v17_tx_state_t *s);
+SPANGPU_API int v17_tx_free(v17_tx_state_t *s);
+SPANGPU_API void v17_tx_power(v17_tx_state_t *s, float power);
+SPANGPU_API void v17_tx_set_get_bit(v17_tx_state_t *s, span_get_bit_func_t get_bit, void *user_data);
+SPANGPU_API void v17_tx_set_modem_status_handler(v17_tx_state_t *s, span_modem_status_func_t handler, void *user_data);
+SPANGPU_API logging_state_t *v17_tx_get_logging_state(v17_tx_state_t *s);
+SPANGPU_API int v17_tx(v17_tx_state_t *s, int16_t amp[], int len);
+
 /* ---- in-band signalling tones (csrc/shim_sigtone.c) ------------------------------------------------------
  * Reference declarations being replaced:
  *   sig_tone_rx_init/_rx/_set_mode/_release/_free, sig_tone_tx_init/_tx/_set_mode/_release/_free

@@ -1,6 +1,7 @@
 // modemtx_api.hip -- C ABI of the modem transmitter banks (include/spangpu.h, "modem transmitter banks"): batched
-// v29_tx() / v27ter_tx() as device-side signal sources.  Device code: modemtx_dev.hpp.  No CPU implementation exists behind
-// these entry points.
+// v29_tx() / v27ter_tx() / v17_tx() as device-side signal sources, carrying an LFSR's bits or the caller's (a bit ring per
+// channel, with the end-of-data shutdown).  Device code: modemtx_dev.hpp.  No CPU implementation of the modulators exists
+// behind these entry points; the cursor at the end is plain host code.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -42,6 +43,17 @@ struct spangpu_modemtx_s
     float *shaper;
     int16_t *d_pcm;
     size_t pcm_cap;
+    int source;             // kTxSrcLfsr or kTxSrcQueue
+    int qcap;               // bits a channel's ring takes
+    int qring;              // ring size in bits: qcap rounded up to whole words
+    uint32_t *queue;
+    int32_t *qst;           // [kVqWords][n_ch]
+    int32_t *d_lens;        // [n_ch]: the returned lengths of a host caller
+    int32_t *h_row;         // [5][n_ch] host scratch: the events as channels [2n], kinds [2n], and the flags read back [n]
+    uint8_t *d_bits;        // staging of spangpu_modemtx_put_bits()
+    int32_t *d_blens;
+    int32_t *d_acc;
+    size_t bits_cap;
 };
 
 static void put_f(int32_t *w, int idx, float v)
@@ -169,12 +181,47 @@ static int rw_words(spangpu_modemtx_s *t, int ch, int32_t *w, bool write)
     return SPANGPU_OK;
 }
 
+// words [first, first + count) of one channel's ring bookkeeping
+static int rw_qwords(spangpu_modemtx_s *t, int ch, int first, int count, int32_t *w, bool write)
+{
+    VT_TRY(hipSetDevice(t->device));
+    int32_t *at = t->qst + (size_t) first*t->n_ch + ch;
+    if (write)
+        VT_TRY(hipMemcpy2DAsync(at, (size_t) t->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), count,
+                                hipMemcpyHostToDevice, t->stream));
+    else
+        VT_TRY(hipMemcpy2DAsync(w, sizeof(int32_t), at, (size_t) t->n_ch*sizeof(int32_t), sizeof(int32_t), count,
+                                hipMemcpyDeviceToHost, t->stream));
+    VT_TRY(hipStreamSynchronize(t->stream));
+    return SPANGPU_OK;
+}
+
+template <int SRC>
+static void launch_bank(spangpu_modemtx_s *t, const V29TxLaunch &L)
+{
+    if (t->kind == kTxV29)
+        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV29, SRC>), dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+    else if (t->kind == kTxV17)
+        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV17, SRC>), dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+    else
+        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV27ter, SRC>), dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+}
+
 extern "C" {
 
 int spangpu_modemtx_create(spangpu_modemtx_t **out, int device, int modem, int n_channels, int bit_rate, int tep, const uint32_t *seeds)
 {
+    return spangpu_modemtx_create_ex(out, device, modem, n_channels, bit_rate, tep, SPANGPU_MODEMTX_LFSR, seeds, 0);
+}
+
+int spangpu_modemtx_create_ex(spangpu_modemtx_t **out, int device, int modem, int n_channels, int bit_rate, int tep, int bit_source,
+                              const uint32_t *seeds, int queue_bits)
+{
     if (out == NULL  ||  n_channels <= 0  ||  (modem != SPANGPU_V29  &&  modem != SPANGPU_V27TER  &&  modem != SPANGPU_V17))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (modem SPANGPU_V29, SPANGPU_V27TER or SPANGPU_V17)");
+    if ((bit_source != SPANGPU_MODEMTX_LFSR  &&  bit_source != SPANGPU_MODEMTX_QUEUE)
+        ||  (bit_source == SPANGPU_MODEMTX_QUEUE  &&  (queue_bits <= 0  ||  queue_bits > (1 << 24))))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bit source, queue_bits 1 .. 2^24)");
     const int kind = (modem == SPANGPU_V29)  ?  kTxV29  :  ((modem == SPANGPU_V27TER)  ?  kTxV27ter  :  kTxV17);
     int32_t probe[kV29TxWords];
     memset(probe, 0, sizeof(probe));
@@ -193,6 +240,7 @@ int spangpu_modemtx_create(spangpu_modemtx_t **out, int device, int modem, int n
     t->device = device;
     t->kind = kind;
     t->n_ch = n_channels;
+    t->source = (bit_source == SPANGPU_MODEMTX_LFSR)  ?  kTxSrcLfsr  :  kTxSrcQueue;
     if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess)
     {
         free(t);
@@ -207,6 +255,23 @@ int spangpu_modemtx_create(spangpu_modemtx_t **out, int device, int modem, int n
     {
         spangpu_modemtx_destroy(t);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the V.29 transmitter bank failed");
+    }
+    if (t->source == kTxSrcQueue)
+    {
+        t->qcap = queue_bits;
+        t->qring = (queue_bits + 31) & ~31;
+        const size_t ring_bytes = (size_t) (t->qring/32)*n_channels*sizeof(uint32_t);
+        const size_t q_bytes = (size_t) kVqWords*n_channels*sizeof(int32_t);
+        t->h_row = (int32_t *) malloc((size_t) 5*n_channels*sizeof(int32_t));
+        if (t->h_row == NULL
+            ||  hipMalloc(&t->queue, ring_bytes) != hipSuccess  ||  hipMemset(t->queue, 0, ring_bytes) != hipSuccess
+            ||  hipMalloc(&t->qst, q_bytes) != hipSuccess  ||  hipMemset(t->qst, 0, q_bytes) != hipSuccess
+            ||  hipMalloc(&t->d_blens, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
+            ||  hipMalloc(&t->d_acc, (size_t) n_channels*sizeof(int32_t)) != hipSuccess)
+        {
+            spangpu_modemtx_destroy(t);
+            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the bit rings failed");
+        }
     }
     float sine[2048];
     float shaper[225];
@@ -290,6 +355,13 @@ void spangpu_modemtx_destroy(spangpu_modemtx_t *t)
     (void) hipFree(t->shaper);
     (void) hipFree(t->constel);
     (void) hipFree(t->d_pcm);
+    (void) hipFree(t->queue);
+    (void) hipFree(t->qst);
+    (void) hipFree(t->d_lens);
+    (void) hipFree(t->d_bits);
+    (void) hipFree(t->d_blens);
+    (void) hipFree(t->d_acc);
+    free(t->h_row);
     if (t->own_stream  &&  t->stream)
         (void) hipStreamDestroy(t->stream);
     free(t);
@@ -389,7 +461,11 @@ int spangpu_modemtx_restart_ex(spangpu_modemtx_t *t, int channel, int bit_rate, 
         return rc;
     if (restart_words(w, t->kind, bit_rate, tep, short_train) != 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bit rate not valid for this modem");
-    return rw_words(t, channel, w, true);
+    if ((rc = rw_words(t, channel, w, true)) != SPANGPU_OK  ||  t->source != kTxSrcQueue)
+        return rc;
+    // a fresh sender has nothing queued and has not been told of the end of its data (as fsk_tx_restart() of the FSK objects)
+    int32_t q[VQ_EOD + 1] = {0, 0, 0};
+    return rw_qwords(t, channel, VQ_RD, VQ_EOD + 1, q, true);
 }
 
 int spangpu_modemtx_get_state(spangpu_modemtx_t *t, int channel, int32_t *words)
@@ -399,15 +475,44 @@ int spangpu_modemtx_get_state(spangpu_modemtx_t *t, int channel, int32_t *words)
     return rw_words(t, channel, words, false);
 }
 
+static int tx_call(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens, int more);
+
 int spangpu_modemtx_tx(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples)
+{
+    return spangpu_modemtx_tx_lens(t, mem_kind, pcm, stride, samples, NULL);
+}
+
+int spangpu_modemtx_tx_lens(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens)
+{
+    return tx_call(t, mem_kind, pcm, stride, samples, lens, 0);
+}
+
+int spangpu_modemtx_tx_continue(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens)
+{
+    return tx_call(t, mem_kind, pcm, stride, samples, lens, 1);
+}
+
+static int tx_call(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens, int more)
 {
     if (t == NULL  ||  pcm == NULL  ||  samples < 0  ||  stride < samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    if (samples == 0)
-        return 0;
     VT_TRY(hipSetDevice(t->device));
+    if (samples == 0)
+    {
+        // xxx_tx(s, amp, 0) returns 0 and touches nothing; no channel has an event
+        if (t->source == kTxSrcQueue)
+            VT_TRY(hipMemsetAsync(t->qst + (size_t) VQ_EVENT*t->n_ch, 0, (size_t) t->n_ch*sizeof(int32_t), t->stream));
+        if (lens  &&  mem_kind == SPANGPU_MEM_HOST)
+            memset(lens, 0, (size_t) t->n_ch*sizeof(int32_t));
+        else if (lens)
+            VT_TRY(hipMemsetAsync(lens, 0, (size_t) t->n_ch*sizeof(int32_t), t->stream));
+        return 0;
+    }
+    if (lens  &&  mem_kind == SPANGPU_MEM_HOST  &&  t->source == kTxSrcQueue  &&  t->d_lens == NULL
+        &&  hipMalloc(&t->d_lens, (size_t) t->n_ch*sizeof(int32_t)) != hipSuccess)
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "length staging");
     V29TxLaunch L;
     memset(&L, 0, sizeof(L));
     L.st = t->st;
@@ -438,20 +543,224 @@ int spangpu_modemtx_tx(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long lo
         L.stride = stride;
     }
     L.vec = ((L.stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(L.pcm) & 15) == 0)  ?  1  :  0;
-    if (t->kind == kTxV29)
-        hipLaunchKernelGGL(modemtx_bank_kernel<kTxV29>, dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
-    else if (t->kind == kTxV17)
-        hipLaunchKernelGGL(modemtx_bank_kernel<kTxV17>, dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+    if (t->source == kTxSrcQueue)
+    {
+        L.qring = t->qring;
+        L.more = more;
+        L.queue = t->queue;
+        L.qst = t->qst;
+        L.lens = (lens == NULL)  ?  NULL  :  ((mem_kind == SPANGPU_MEM_HOST)  ?  t->d_lens  :  lens);
+        launch_bank<kTxSrcQueue>(t, L);
+    }
     else
-        hipLaunchKernelGGL(modemtx_bank_kernel<kTxV27ter>, dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+    {
+        launch_bank<kTxSrcLfsr>(t, L);
+        // an LFSR never runs out of bits: no channel of such a bank shuts down
+        if (lens  &&  mem_kind == SPANGPU_MEM_DEVICE)
+            VT_TRY(hipMemsetD32Async((hipDeviceptr_t) lens, samples, (size_t) t->n_ch, t->stream));
+    }
     VT_TRY(hipGetLastError());
     if (mem_kind == SPANGPU_MEM_HOST)
     {
         VT_TRY(hipMemcpy2DAsync(pcm, (size_t) stride*sizeof(int16_t), t->d_pcm, t->pcm_cap*sizeof(int16_t),
                                 (size_t) samples*sizeof(int16_t), t->n_ch, hipMemcpyDeviceToHost, t->stream));
+        if (lens  &&  t->source == kTxSrcQueue)
+            VT_TRY(hipMemcpyAsync(lens, t->d_lens, (size_t) t->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
         VT_TRY(hipStreamSynchronize(t->stream));
+        for (int c = 0;  lens  &&  t->source == kTxSrcLfsr  &&  c < t->n_ch;  c++)
+            lens[c] = samples;
     }
     return samples;
+}
+
+int spangpu_modemtx_put_bits(spangpu_modemtx_t *t, int first, int n, const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted)
+{
+    if (t == NULL  ||  t->source != kTxSrcQueue  ||  first < 0  ||  n <= 0  ||  first + n > t->n_ch  ||  bits == NULL  ||  lens == NULL
+        ||  stride <= 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    for (int i = 0;  i < n;  i++)
+    {
+        if (lens[i] < 0  ||  (lens[i] + 7)/8 > stride)
+            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's bits do not fit its row");
+    }
+    VT_TRY(hipSetDevice(t->device));
+    const size_t bytes = (size_t) n*stride;
+    if (bytes > t->bits_cap)
+    {
+        VT_TRY(hipStreamSynchronize(t->stream));
+        (void) hipFree(t->d_bits);
+        t->d_bits = NULL;
+        t->bits_cap = 0;
+        if (hipMalloc(&t->d_bits, bytes) != hipSuccess)
+            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "bit staging");
+        t->bits_cap = bytes;
+    }
+    VT_TRY(hipMemcpyAsync(t->d_bits, bits, bytes, hipMemcpyHostToDevice, t->stream));
+    VT_TRY(hipMemcpyAsync(t->d_blens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
+    hipLaunchKernelGGL(modemtx_put_kernel, dim3((n + 63)/64), dim3(64), 0, t->stream, t->qst, t->queue, t->n_ch, t->qring, t->qcap,
+                       first, first + n, t->d_bits, stride, t->d_blens, t->d_acc);
+    VT_TRY(hipGetLastError());
+    if (accepted)
+        VT_TRY(hipMemcpyAsync(accepted, t->d_acc, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    // the caller's arrays are pageable: they must not change under the copies
+    VT_TRY(hipStreamSynchronize(t->stream));
+    return SPANGPU_OK;
+}
+
+int spangpu_modemtx_queued(spangpu_modemtx_t *t, int channel)
+{
+    if (t == NULL  ||  channel < 0  ||  channel >= t->n_ch  ||  t->source != kTxSrcQueue)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    int32_t w = 0;
+    const int rc = rw_qwords(t, channel, VQ_COUNT, 1, &w, false);
+    return (rc != SPANGPU_OK)  ?  rc  :  w;
+}
+
+int spangpu_modemtx_end_of_data(spangpu_modemtx_t *t, int channel, int on)
+{
+    if (t == NULL  ||  channel < 0  ||  channel >= t->n_ch  ||  t->source != kTxSrcQueue)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    int32_t w = on  ?  1  :  0;
+    return rw_qwords(t, channel, VQ_EOD, 1, &w, true);
+}
+
+int spangpu_modemtx_events(spangpu_modemtx_t *t, const int32_t **channels, const int32_t **kinds)
+{
+    if (t == NULL)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
+    if (channels)
+        *channels = NULL;
+    if (kinds)
+        *kinds = NULL;
+    if (t->source != kTxSrcQueue)
+        return 0;
+    const int n = t->n_ch;
+    int32_t *chans = t->h_row;                      // a channel has at most two events in a call
+    int32_t *kind = t->h_row + (size_t) 2*n;
+    int32_t *flags = t->h_row + (size_t) 4*n;
+    VT_TRY(hipSetDevice(t->device));
+    VT_TRY(hipMemcpyAsync(flags, t->qst + (size_t) VQ_EVENT*n, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+    VT_TRY(hipStreamSynchronize(t->stream));
+    int count = 0;
+    for (int c = 0;  c < n;  c++)
+    {
+        // the reference's order: the end of the data, then (in a long call) the end of the shutdown it starts
+        if (flags[c] & kVqEndOfData)
+        {
+            chans[count] = c;
+            kind[count++] = SPANGPU_MODEMTX_END_OF_DATA;
+        }
+        if (flags[c] & kVqShutdownComplete)
+        {
+            chans[count] = c;
+            kind[count++] = SPANGPU_MODEMTX_SHUTDOWN_COMPLETE;
+        }
+    }
+    if (channels)
+        *channels = chans;
+    if (kinds)
+        *kinds = kind;
+    return count;
+}
+
+// ---- host code: the cursor.  The bookkeeping of getbaud() without the signal: which bauds ask the caller for bits ----
+
+int spangpu_modemtx_cursor_init(spangpu_modemtx_cursor_t *cur, int modem, int bit_rate, int tep, int short_train)
+{
+    if (cur == NULL  ||  (modem != SPANGPU_V29  &&  modem != SPANGPU_V27TER  &&  modem != SPANGPU_V17))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (modem SPANGPU_V29, SPANGPU_V27TER or SPANGPU_V17)");
+    const int kind = (modem == SPANGPU_V29)  ?  kTxV29  :  ((modem == SPANGPU_V27TER)  ?  kTxV27ter  :  kTxV17);
+    int32_t w[kV29TxWords];
+    memset(w, 0, sizeof(w));
+    if (restart_words(w, kind, bit_rate, tep, short_train) != 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bit rate not valid for this modem");
+    cur->modem = modem;
+    cur->bit_rate = bit_rate;
+    cur->short_train = (kind == kTxV17  &&  short_train)  ?  1  :  0;
+    cur->baud_phase = w[VT_BAUD_PHASE];
+    cur->training_step = w[VT_TRAINING_STEP];
+    cur->in_training = w[VT_IN_TRAINING];
+    return SPANGPU_OK;
+}
+
+long long spangpu_modemtx_cursor_advance(spangpu_modemtx_cursor_t *cur, int samples, long long bits_before_end)
+{
+    if (cur == NULL  ||  samples < 0  ||  (cur->modem != SPANGPU_V29  &&  cur->modem != SPANGPU_V27TER  &&  cur->modem != SPANGPU_V17))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    const int modem = cur->modem;
+    const int rate = cur->bit_rate;
+    int step = 3;
+    int period = 10;            // V.29, V.17: 2400 baud
+    int bits_per_baud;
+    int shutdown_end;
+    if (modem == SPANGPU_V29)
+    {
+        bits_per_baud = (rate == 9600)  ?  4  :  ((rate == 7200)  ?  3  :  2);
+        shutdown_end = kVtShutdownEnd;
+    }
+    else if (modem == SPANGPU_V27TER)
+    {
+        step = (rate == 4800)  ?  1  :  3;              // 1600 baud, 1200 baud
+        period = (rate == 4800)  ?  5  :  20;
+        bits_per_baud = (rate == 4800)  ?  3  :  2;
+        shutdown_end = kV27ShutdownEnd;
+    }
+    else
+    {
+        bits_per_baud = rate/2400;
+        shutdown_end = kV17ShutdownEnd;
+    }
+    // the test at the start of xxx_tx(), v29tx.c:241
+    if (cur->training_step >= shutdown_end)
+        return 0;
+    long long calls = 0;
+    for (int i = 0;  i < samples;  i++)
+    {
+        if ((cur->baud_phase += step) < period)
+            continue;
+        cur->baud_phase -= period;
+        // getbaud()
+        if (cur->in_training)
+        {
+            if (modem == SPANGPU_V17)
+            {
+                if (cur->training_step <= kV17End)
+                {
+                    if (cur->training_step < kV17Seg4)
+                    {
+                        // training_get(), v17tx.c:143-175
+                        cur->training_step++;
+                        if (cur->training_step > kV17Seg2  &&  cur->training_step <= kV17Seg3  &&  cur->short_train
+                            &&  cur->training_step == kV17ShortSeg4)
+                            cur->training_step = kV17Seg4;
+                        continue;
+                    }
+                    if (++cur->training_step > kV17End)
+                        cur->in_training = 0;
+                }
+                else
+                {
+                    cur->training_step++;
+                }
+            }
+            else
+            {
+                const int last_seg = (modem == SPANGPU_V29)  ?  kVtSeg4  :  kV27Seg5;
+                const int end = (modem == SPANGPU_V29)  ?  kVtEnd  :  kV27End;
+                if (++cur->training_step <= last_seg)
+                    continue;
+                if (cur->training_step == end + 1)
+                    cur->in_training = 0;
+            }
+        }
+        for (int b = 0;  b < bits_per_baud  &&  !cur->in_training;  b++)
+        {
+            calls++;
+            if (bits_before_end >= 0  &&  calls > bits_before_end)
+                cur->in_training = 1;       // SIG_STATUS_END_OF_DATA: fake_get_bit() for the rest, and the shutdown
+        }
+    }
+    return calls;
 }
 
 // The pulse shaper tables this library builds (for tests).  which: 0 V.29 [10][9], 1 V.27ter 4800 bps [5][9],

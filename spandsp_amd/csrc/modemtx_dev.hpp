@@ -13,8 +13,18 @@
 //   dds_complexf()             src/dds_float.c:2184-2191
 //   lfastrintf()               a truncating cast on x86-64 (spandsp/fast_convert.h:184-197)
 //
-// Data bits come from a per-channel 15 bit LFSR (x^15 + x^14 + 1, the source the test harness of the oracle feeds
-// the reference with); a caller's get_bit() callback, and with it the end-of-data shutdown, is not replayed.
+// Data bits come from one of two sources, a template argument of the kernel:
+//   kTxSrcLfsr    a per-channel 15 bit LFSR (x^15 + x^14 + 1, the source the test harness of the oracle feeds the reference
+//                 with);
+//   kTxSrcQueue   a per-channel ring of bits in HBM, the caller's data: queue[qring/32][n_ch], packed LSB first and word-
+//                 interleaved across channels as fsktx_dev.hpp's, so that a wave's ring reads coalesce; a ring word is loaded
+//                 once per 32 bits.  A bit is taken where the reference calls current_get_bit with the caller's function in it
+//                 (never while training).  An empty ring answers 1 and consumes nothing -- or, once the channel's end-of-data
+//                 flag is set, SIG_STATUS_END_OF_DATA (v29tx.c:108-118, v27ter_tx.c:132-142, v17tx.c:296-306): that bit and
+//                 every later one is fake_get_bit() = 1, in_training goes back on, and the shutdown symbols follow
+//                 (v29tx.c:180-199, v27ter_tx.c:215-235: 32 bauds of scrambled ones; v17tx.c:273-289: ones up to
+//                 V17_TRAINING_SHUTDOWN_A, then silence).  Ring position, fill, the flag and the events of the last call are
+//                 words of their own (VQ_*) beside the 32 state words.
 //
 // The nine-symbol pulse shaping buffer is kept oldest-first in registers (a shift per baud); the ring position
 // of the reference only decides where its dot product splits into two partial sums, and that split is
@@ -48,6 +58,22 @@ enum
     VT_PRBS = 31,
     kV29TxWords = 32
 };
+
+// bit source kTxSrcQueue: [kVqWords][n_ch] beside the state words
+enum
+{
+    VQ_RD = 0,              // read position and fill of the channel's ring, in bits
+    VQ_COUNT = 1,
+    VQ_EOD = 2,             // an empty ring answers SIG_STATUS_END_OF_DATA instead of a 1
+    VQ_EVENT = 3,           // what the last call met: kVqEndOfData | kVqShutdownComplete
+    kVqWords = 4
+};
+
+constexpr int kVqEndOfData = 1;
+constexpr int kVqShutdownComplete = 2;
+
+constexpr int kTxSrcLfsr = 0;
+constexpr int kTxSrcQueue = 1;
 
 constexpr int kVtSeg1 = 480;
 constexpr int kVtSeg2 = kVtSeg1 + 48;
@@ -89,6 +115,12 @@ struct V29TxLaunch
     int n_ch;
     int samples;
     int vec;
+    // bit source kTxSrcQueue only
+    int qring;                  // ring size in bits, a multiple of 32
+    uint32_t *queue;            // [qring/32][n_ch]
+    int32_t *qst;               // [kVqWords][n_ch]
+    int32_t *lens;              // [n_ch] or null: what xxx_tx() returns, `samples` or 0
+    int more;                   // this launch goes on with the xxx_tx() call of the last one: no test for the end of the shutdown
 };
 
 // v29tx_constellation_maps.h: index = amplitude bit << 3 | phase octant
@@ -115,7 +147,7 @@ __device__ __forceinline__ void v27tx_point(int oct, float &re, float &im)
     im = r*cy;
 }
 
-template <int KIND>
+template <int KIND, int SRC = kTxSrcLfsr>
 __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
 {
     __shared__ float sine[2048];
@@ -166,14 +198,58 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
         aim[i] = __int_as_float(st[(size_t) (VT_RRC_IM + at)*n]);
     }
 
+    // bit source kTxSrcQueue
+    int qrd = 0;
+    int qcount = 0;
+    bool eod = false;
+    int events = 0;
+    uint32_t qword = 0u;
+    bool qstale = true;         // the ring word qrd is in has not been loaded in this call
+    if (SRC == kTxSrcQueue)
+    {
+        qrd = L.qst[VQ_RD*n + ch];
+        qcount = L.qst[VQ_COUNT*n + ch];
+        eod = L.qst[VQ_EOD*n + ch] != 0;
+    }
+    // the caller's get_bit(): asked only while not training
+    auto queue_bit = [&]() -> int
+    {
+        if (qcount > 0)
+        {
+            if (qstale  ||  (qrd & 31) == 0)
+            {
+                qword = L.queue[(size_t) (qrd >> 5)*n + ch];
+                qstale = false;
+            }
+            const int bit = (int) ((qword >> (qrd & 31)) & 1u);
+            qrd = (qrd + 1 == L.qring)  ?  0  :  (qrd + 1);
+            qcount--;
+            return bit;
+        }
+        if (eod)
+        {
+            // SIG_STATUS_END_OF_DATA: fake_get_bit() from here on, and the shutdown symbols
+            in_training = 1;
+            events |= kVqEndOfData;
+        }
+        return 1;
+    };
+
     auto scrambled_bit = [&]() -> int
     {
         // get_scrambled_bit(), v29tx.c:103-123 / v27ter_tx.c:127-146; while training the source is fake_get_bit() = 1
         int bit = 1;
         if (!in_training)
         {
-            bit = (int) (((prbs >> 14) ^ (prbs >> 13)) & 1u);
-            prbs = ((prbs << 1) | (uint32_t) bit) & 0x7FFFu;
+            if (SRC == kTxSrcLfsr)
+            {
+                bit = (int) (((prbs >> 14) ^ (prbs >> 13)) & 1u);
+                prbs = ((prbs << 1) | (uint32_t) bit) & 0x7FFFu;
+            }
+            else
+            {
+                bit = queue_bit();
+            }
         }
         if (KIND == kTxV29)
         {
@@ -211,7 +287,8 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     const int pts_at = (bit_rate == 14400)  ?  0  :  ((bit_rate == 12000)  ?  128  :  ((bit_rate == 9600)  ?  192  :  ((bit_rate == 7200)  ?  224  :  240)));
 
     int16_t *row = L.pcm + (size_t) ch*L.stride;
-    const bool silent = (training_step >= ((KIND == kTxV29)  ?  kVtShutdownEnd  :  ((KIND == kTxV27ter)  ?  kV27ShutdownEnd  :  kV17ShutdownEnd)));
+    const bool silent = (training_step >= ((KIND == kTxV29)  ?  kVtShutdownEnd  :  ((KIND == kTxV27ter)  ?  kV27ShutdownEnd  :  kV17ShutdownEnd)))
+                        &&  !(SRC == kTxSrcQueue  &&  L.more);
     for (int base = 0;  base < L.samples;  base += 8)
     {
         uint32_t pk[4] = {0u, 0u, 0u, 0u};
@@ -285,6 +362,10 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                             {
                                 in_training = 0;
                             }
+                            else if (SRC == kTxSrcQueue  &&  training_step == kVtShutdownEnd)
+                            {
+                                events |= kVqShutdownComplete;      // v29tx.c:192-197
+                            }
                         }
                         if (!have)
                         {
@@ -354,6 +435,14 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                                     in_training = 0;
                             }
                         }
+                        else if (SRC == kTxSrcQueue  &&  in_training)
+                        {
+                            // the shutdown, v17tx.c:273-289: ones up to V17_TRAINING_SHUTDOWN_A, then silence.  The reference
+                            // returns the silence before its test for V17_TRAINING_SHUTDOWN_END, so it never reports
+                            // SIG_STATUS_SHUTDOWN_COMPLETE, and nor does this
+                            training_step++;
+                            have = (training_step > kV17End + 32);
+                        }
                         if (!have)
                         {
                             const int nbits = (bit_rate == 14400)  ?  6  :  ((bit_rate == 12000)  ?  5  :  ((bit_rate == 9600)  ?  4  :  ((bit_rate == 7200)  ?  3  :  2)));
@@ -363,8 +452,15 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                                 int bit = 1;
                                 if (!in_training)
                                 {
-                                    bit = (int) (((prbs >> 14) ^ (prbs >> 13)) & 1u);
-                                    prbs = ((prbs << 1) | (uint32_t) bit) & 0x7FFFu;
+                                    if (SRC == kTxSrcLfsr)
+                                    {
+                                        bit = (int) (((prbs >> 14) ^ (prbs >> 13)) & 1u);
+                                        prbs = ((prbs << 1) | (uint32_t) bit) & 0x7FFFu;
+                                    }
+                                    else
+                                    {
+                                        bit = queue_bit();
+                                    }
                                 }
                                 q |= scramble17(bit) << i;
                             }
@@ -428,6 +524,10 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                             else if (training_step == kV27End + 1)
                             {
                                 in_training = 0;
+                            }
+                            else if (SRC == kTxSrcQueue  &&  training_step == kV27ShutdownEnd)
+                            {
+                                events |= kVqShutdownComplete;      // v27ter_tx.c:228-233
                             }
                         }
                         if (!have)
@@ -519,7 +619,47 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     st[VT_CARRIER_PHASE*n] = (int32_t) carrier_phase;
     st[VT_BAUD_PHASE*n] = baud_phase;
     st[VT_CONSTELLATION*n] = constellation;
-    st[VT_PRBS*n] = (int32_t) prbs;
+    if (SRC == kTxSrcLfsr)
+    {
+        st[VT_PRBS*n] = (int32_t) prbs;
+    }
+    else
+    {
+        L.qst[VQ_RD*n + ch] = qrd;
+        L.qst[VQ_COUNT*n + ch] = qcount;
+        L.qst[VQ_EVENT*n + ch] = events;
+        // the test for the end of the shutdown is made at the start of a call (v29tx.c:241): the call it ends in is whole
+        if (L.lens)
+            L.lens[ch] = silent  ?  0  :  L.samples;
+    }
+}
+
+// spangpu_modemtx_put_bits() on channels [lo, hi): the bits of channel c are packed LSB first at bits[(c - lo)*bstride ...],
+// lens[c - lo] of them; accepted[c - lo] = how many had room.
+__global__ void modemtx_put_kernel(int32_t *qst, uint32_t *queue, int n_ch, int qring, int qcap, int lo, int hi, const uint8_t *bits,
+                                   int bstride, const int32_t *lens, int32_t *accepted)
+{
+    const int ch = lo + blockIdx.x*blockDim.x + threadIdx.x;
+    if (ch >= hi)
+        return;
+    const size_t n = (size_t) n_ch;
+    const uint8_t *src = bits + (size_t) (ch - lo)*bstride;
+    const int rd = qst[VQ_RD*n + ch];
+    const int count = qst[VQ_COUNT*n + ch];
+    int mine = lens[ch - lo];
+    mine = (mine > qcap - count)  ?  (qcap - count)  :  mine;
+    mine = (mine < 0)  ?  0  :  mine;
+    int at = rd + count;
+    at -= (at >= qring)  ?  qring  :  0;
+    for (int i = 0;  i < mine;  i++)
+    {
+        const uint32_t bit = (src[i >> 3] >> (i & 7)) & 1u;
+        uint32_t *w = queue + (size_t) (at >> 5)*n + ch;
+        *w = (*w & ~(1u << (at & 31))) | (bit << (at & 31));
+        at = (at + 1 == qring)  ?  0  :  (at + 1);
+    }
+    qst[VQ_COUNT*n + ch] = count + mine;
+    accepted[ch - lo] = mine;
 }
 
 }   // namespace spg

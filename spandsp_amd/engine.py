@@ -112,6 +112,15 @@ def lib():
             "spangpu_modemtx_state_words": (ci, []),
             "spangpu_modemtx_get_state": (ci, [vp, ci, vp]),
             "spangpu_modemtx_table": (ci, [ci, vp, ci]),
+            "spangpu_modemtx_create_ex": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, ci, vp, ci]),
+            "spangpu_modemtx_tx_lens": (ci, [vp, ci, vp, ll, ci, vp]),
+            "spangpu_modemtx_tx_continue": (ci, [vp, ci, vp, ll, ci, vp]),
+            "spangpu_modemtx_put_bits": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+            "spangpu_modemtx_queued": (ci, [vp, ci]),
+            "spangpu_modemtx_end_of_data": (ci, [vp, ci, ci]),
+            "spangpu_modemtx_events": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_modemtx_cursor_init": (ci, [vp, ci, ci, ci, ci]),
+            "spangpu_modemtx_cursor_advance": (ll, [vp, ci, ll]),
             "spangpu_fsktx_create": (ci, [C.POINTER(vp), ci, ci, vp, ci, vp, ci]),
             "spangpu_fsktx_destroy": (None, [vp]),
             "spangpu_fsktx_channels": (ci, [vp]),
@@ -1996,10 +2005,29 @@ def v29_tx_table():
     return modem_tx_table(0)
 
 
-class ModemTxBank:
-    """N V.29 / V.27ter modulators (v29_tx, v27ter_tx), state in HBM; data bits from a per-channel LFSR."""
+MODEMTX_LFSR, MODEMTX_QUEUE = 0, 1
+MODEMTX_END_OF_DATA, MODEMTX_SHUTDOWN_COMPLETE = -7, -10
 
-    def __init__(self, modem, n_channels, bit_rate, tep=False, seeds=None, device=0):
+
+class ModemTxCursor(C.Structure):
+    """spangpu_modemtx_cursor_t: where a sender is in training / data / shutdown, stepped call by call (host code, no device)."""
+    _fields_ = [("modem", C.c_int), ("bit_rate", C.c_int), ("short_train", C.c_int), ("baud_phase", C.c_int),
+                ("training_step", C.c_int), ("in_training", C.c_int)]
+
+    def __init__(self, modem, bit_rate, tep=False, short_train=False):
+        super().__init__()
+        _check(lib().spangpu_modemtx_cursor_init(C.byref(self), modem, bit_rate, int(tep), int(short_train)))
+
+    def advance(self, samples, bits_before_end=-1):
+        """How many get_bit calls a xxx_tx() call of `samples` makes from here (the one answering END_OF_DATA included)."""
+        return _check(lib().spangpu_modemtx_cursor_advance(C.byref(self), samples, bits_before_end))
+
+
+class ModemTxBank:
+    """N V.29 / V.27ter / V.17 modulators (v29_tx, v27ter_tx, v17_tx), state in HBM; data bits from a per-channel LFSR or a
+    per-channel bit queue (the caller's data, with the end-of-data shutdown)."""
+
+    def __init__(self, modem, n_channels, bit_rate, tep=False, seeds=None, device=0, bit_source=MODEMTX_LFSR, queue_bits=4096):
         self.n = n_channels
         self.h = C.c_void_p()
         sp = None
@@ -2007,7 +2035,42 @@ class ModemTxBank:
             seeds = np.ascontiguousarray(seeds, np.uint32)
             assert len(seeds) == n_channels
             sp = seeds.ctypes.data
-        _check(lib().spangpu_modemtx_create(C.byref(self.h), device, modem, n_channels, bit_rate, int(tep), sp))
+        if bit_source == MODEMTX_LFSR:
+            _check(lib().spangpu_modemtx_create(C.byref(self.h), device, modem, n_channels, bit_rate, int(tep), sp))
+        else:
+            _check(lib().spangpu_modemtx_create_ex(C.byref(self.h), device, modem, n_channels, bit_rate, int(tep), bit_source, sp,
+                                                   queue_bits))
+
+    def put_bits(self, bit_lists, first=0):
+        """One sequence of 0/1 per channel from `first` on; returns how many bits each ring accepted."""
+        n = len(bit_lists)
+        stride = max(1, (max(len(b) for b in bit_lists) + 7)//8)
+        buf = np.zeros((n, stride), np.uint8)
+        lens = np.zeros(n, np.int32)
+        for i, b in enumerate(bit_lists):
+            b = np.asarray(b, np.uint8)
+            lens[i] = len(b)
+            if len(b):
+                buf[i, :(len(b) + 7)//8] = np.packbits(b, bitorder="little")
+        acc = np.zeros(n, np.int32)
+        _check(lib().spangpu_modemtx_put_bits(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, acc.ctypes.data))
+        return acc
+
+    def queued(self, channel):
+        return _check(lib().spangpu_modemtx_queued(self.h, channel))
+
+    def end_of_data(self, channel, on=True):
+        _check(lib().spangpu_modemtx_end_of_data(self.h, channel, int(on)))
+
+    def events(self):
+        """[(channel, kind)] of the last call: MODEMTX_END_OF_DATA / MODEMTX_SHUTDOWN_COMPLETE, in the reference's order."""
+        pc, pk = C.c_void_p(), C.c_void_p()
+        k = _check(lib().spangpu_modemtx_events(self.h, C.byref(pc), C.byref(pk)))
+        if k == 0:
+            return []
+        ch = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_int32)), (k,))
+        kind = np.ctypeslib.as_array(C.cast(pk, C.POINTER(C.c_int32)), (k,))
+        return [(int(a), int(b)) for a, b in zip(ch, kind)]
 
     def close(self):
         if self.h:
@@ -2039,13 +2102,22 @@ class ModemTxBank:
     def restart(self, channel, bit_rate, tep, short_train=False):
         _check(lib().spangpu_modemtx_restart_ex(self.h, channel, bit_rate, int(tep), int(short_train)))
 
-    def tx_host(self, samples):
+    def tx_host(self, samples, lens=False):
         pcm = np.zeros((self.n, samples), np.int16)
-        _check(lib().spangpu_modemtx_tx(self.h, MEM_HOST, pcm.ctypes.data, samples, samples))
-        return pcm
+        if not lens:
+            _check(lib().spangpu_modemtx_tx(self.h, MEM_HOST, pcm.ctypes.data, samples, samples))
+            return pcm
+        got = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_modemtx_tx_lens(self.h, MEM_HOST, pcm.ctypes.data, samples, samples, got.ctypes.data))
+        return pcm, got
 
-    def tx_device(self, pcm_ptr, stride, samples):
-        _check(lib().spangpu_modemtx_tx(self.h, MEM_DEVICE, pcm_ptr, stride, samples))
+    tx = tx_host
+
+    def tx_device(self, pcm_ptr, stride, samples, lens_ptr=None):
+        if lens_ptr is None:
+            _check(lib().spangpu_modemtx_tx(self.h, MEM_DEVICE, pcm_ptr, stride, samples))
+        else:
+            _check(lib().spangpu_modemtx_tx_lens(self.h, MEM_DEVICE, pcm_ptr, stride, samples, lens_ptr))
 
     def get_state(self, channel):
         w = np.zeros(lib().spangpu_modemtx_state_words(), np.uint32)
@@ -2054,18 +2126,88 @@ class ModemTxBank:
 
 
 class V29TxBank(ModemTxBank):
-    def __init__(self, n_channels, bit_rate=9600, tep=False, seeds=None, device=0):
-        super().__init__(V29, n_channels, bit_rate, tep, seeds, device)
+    def __init__(self, n_channels, bit_rate=9600, tep=False, seeds=None, device=0, **kw):
+        super().__init__(V29, n_channels, bit_rate, tep, seeds, device, **kw)
 
 
 class V27terTxBank(ModemTxBank):
-    def __init__(self, n_channels, bit_rate=4800, tep=False, seeds=None, device=0):
-        super().__init__(V27TER, n_channels, bit_rate, tep, seeds, device)
+    def __init__(self, n_channels, bit_rate=4800, tep=False, seeds=None, device=0, **kw):
+        super().__init__(V27TER, n_channels, bit_rate, tep, seeds, device, **kw)
 
 
 class V17TxBank(ModemTxBank):
-    def __init__(self, n_channels, bit_rate=14400, tep=False, seeds=None, device=0):
-        super().__init__(V17, n_channels, bit_rate, tep, seeds, device)
+    def __init__(self, n_channels, bit_rate=14400, tep=False, seeds=None, device=0, **kw):
+        super().__init__(V17, n_channels, bit_rate, tep, seeds, device, **kw)
+
+
+_GET_BIT = C.CFUNCTYPE(C.c_int, C.c_void_p)
+_MODEM_STATUS = C.CFUNCTYPE(None, C.c_void_p, C.c_int)
+_modem_tx_declared = []
+
+
+class ModemTxObject:
+    """v29_tx / v27ter_tx / v17_tx by their spandsp names (include/spangpu_spandsp.h): a thin wrapper for the tests.  get_bit()
+    and status(code) are Python callables."""
+
+    def __init__(self, name, bit_rate, tep, get_bit, status=None):
+        L = lib()
+        vp, ci = C.c_void_p, C.c_int
+        if name not in _modem_tx_declared:
+            for fn, res, args in [("_init", vp, [vp, ci, C.c_bool, vp, vp]), ("_free", ci, [vp]), ("_release", ci, [vp]),
+                                  ("_power", None, [vp, C.c_float]), ("_set_get_bit", None, [vp, vp, vp]),
+                                  ("_set_modem_status_handler", None, [vp, vp, vp]), ("_get_logging_state", vp, [vp]),
+                                  ("", ci, [vp, vp, ci]),
+                                  ("_restart", ci, [vp, ci, C.c_bool] + ([C.c_bool] if name == "v17_tx" else []))]:
+                f = getattr(L, name + fn)
+                f.restype = res
+                f.argtypes = args
+            _modem_tx_declared.append(name)
+        self.name = name
+        self.cb = _GET_BIT(lambda _: get_bit())
+        self.p = getattr(L, name + "_init")(None, bit_rate, tep, C.cast(self.cb, vp), None)
+        if not self.p:
+            raise RuntimeError("%s_init() returned NULL: %s" % (name, lib().spangpu_last_error().decode("latin1")))
+        self.scb = None
+        if status is not None:
+            self.set_status(status)
+
+    def _f(self, fn):
+        return getattr(lib(), self.name + fn)
+
+    def set_get_bit(self, get_bit):
+        keep = self.cb
+        self.cb = _GET_BIT(lambda _: get_bit())
+        self._f("_set_get_bit")(self.p, C.cast(self.cb, C.c_void_p), None)
+        del keep
+
+    def set_status(self, status):
+        self.scb = _MODEM_STATUS(lambda _, code: status(code))
+        self._f("_set_modem_status_handler")(self.p, C.cast(self.scb, C.c_void_p), None)
+
+    def power(self, dbm0):
+        self._f("_power")(self.p, dbm0)
+
+    def restart(self, bit_rate, tep, short_train=False):
+        if self.name == "v17_tx":
+            return self._f("_restart")(self.p, bit_rate, tep, short_train)
+        return self._f("_restart")(self.p, bit_rate, tep)
+
+    def tx(self, n):
+        """(row of n samples, zero where none was written; returned length)"""
+        row = np.zeros(max(1, n), np.int16)
+        got = self._f("")(self.p, row.ctypes.data, n)
+        return row[:n], got
+
+    def close(self):
+        if self.p:
+            self._f("_free")(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class AwgnBank:
