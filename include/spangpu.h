@@ -724,6 +724,68 @@ SPANGPU_API int spangpu_mcttx_tx(spangpu_mcttx_t *tx, int mem_kind, int16_t *pcm
 SPANGPU_API int spangpu_mcttx_state_words(void);
 SPANGPU_API int spangpu_mcttx_get_state(spangpu_mcttx_t *tx, int channel, int32_t *words);
 
+/* ---- V.18 text banks (csrc/v18_api.hip, csrc/v18_dev.hpp) ----------------------------------
+ * N Baudot text telephones (TTY/TDD) in one of the three Weitbrecht 5-bit modes of v18.c, with V18_AUTOMODING_NONE: text in,
+ * text out.  A channel is the reference's v18_state_t in these modes: a 128-byte text ring, the Baudot coder with its shift
+ * state, 5N2 character framing, the FSK modulator; and the framed FSK demodulator with the Baudot decoder behind it.  The
+ * two halves share the half-duplex suppression timer: for 300 ms after the sender pulled its last byte the receiver drops
+ * what it hears.  One launch per tx call and one per rx call, both on the bank's stream, in the caller's order.
+ *
+ *   spangpu_v18_create()       v18_init(NULL, calling_party, mode, V18_AUTOMODING_NONE, ..)        src/v18.c:2054-2116
+ *   spangpu_v18_put()          v18_put(s, msg, len): the whole message or nothing; results[i] = len, or -1 for
+ *                              one that does not fit (nothing changes then)                         src/v18.c:1990-2017
+ *   spangpu_v18_tx()           v18_tx(s, amp, max_len) x N; lens[c] is what it returns, samples past it are 0
+ *   spangpu_v18_rx()           v18_rx(s, amp, len) x N                                              src/v18.c:1874-1941
+ *   spangpu_v18_fillin()       v18_rx_fillin(s, len)
+ *   spangpu_v18_text()         the put_msg calls of the last rx call: counts[c] characters of channel c at
+ *                              chars[c*capacity], in order (each is one put_msg call of length 1); returns the capacity
+ *   spangpu_v18_restart()      what v18_set_modem() does to a channel: modulator (its shutdown included), framer,
+ *                              demodulator and shift states start again in `mode`; the text ring, tx_signal_on,
+ *                              tx_draining and the suppression timer stay as they are
+ *
+ * As in the reference, a sender that has run dry shuts its modulator down for good: a later put is accepted and never sent,
+ * until spangpu_v18_restart().  Automoding, the DTMF mode and the 7-bit FSK modes are not part of these banks.
+ */
+#define SPANGPU_V18_MODE_WEITBRECHT_5BIT_4545   0x0002
+#define SPANGPU_V18_MODE_WEITBRECHT_5BIT_50     0x0004
+#define SPANGPU_V18_MODE_WEITBRECHT_5BIT_476    0x0200
+
+/* bits of the V18_RX_STATUS state word: what the carrier detector reported in the last rx call */
+#define SPANGPU_V18_RX_CARRIER_UP               1
+#define SPANGPU_V18_RX_CARRIER_DOWN             2
+
+typedef struct spangpu_v18_s spangpu_v18_t;
+
+/* modes[]: n_modes == 1 (every channel) or n_modes == n_channels */
+SPANGPU_API int spangpu_v18_create(spangpu_v18_t **bank, int device, int n_channels, const int32_t *modes, int n_modes, int calling_party);
+SPANGPU_API void spangpu_v18_destroy(spangpu_v18_t *bank);
+SPANGPU_API int spangpu_v18_channels(const spangpu_v18_t *bank);
+SPANGPU_API int spangpu_v18_set_stream(spangpu_v18_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_v18_sync(spangpu_v18_t *bank);
+/* channels first .. first + n - 1: lens[i] bytes from text[i*stride] (host memory); results may be NULL */
+SPANGPU_API int spangpu_v18_put(spangpu_v18_t *bank, int first, int n, const uint8_t *text, int stride, const int32_t *lens, int32_t *results);
+/* pcm[c*stride + i]; lens ([n_channels], may be NULL) lives where pcm lives */
+SPANGPU_API int spangpu_v18_tx(spangpu_v18_t *bank, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens);
+SPANGPU_API int spangpu_v18_rx(spangpu_v18_t *bank, const int16_t *amp, int mem_kind, int samples, long long stride);
+/* lens[] is host memory; a channel with lens[c] == 0 sits the call out */
+SPANGPU_API int spangpu_v18_rx_var(spangpu_v18_t *bank, const int16_t *amp, int mem_kind, const int32_t *lens, int max_samples, long long stride);
+SPANGPU_API int spangpu_v18_fillin(spangpu_v18_t *bank, int channel, int len);
+/* Valid until the next call on this bank.  A record takes samples*baud/(8000*7) + 2 characters (spangpu_v18_text_capacity());
+   a count above that is an error (SPANGPU_ERR_STATE), never a record cut short. */
+SPANGPU_API int spangpu_v18_text(spangpu_v18_t *bank, const uint8_t **chars, const int32_t **counts);
+SPANGPU_API int spangpu_v18_text_capacity(const spangpu_v18_t *bank, int samples);
+SPANGPU_API int spangpu_v18_restart(spangpu_v18_t *bank, int channel, int mode);
+/* Test / checkpoint access to one channel's state (layout: v18_dev.hpp) */
+SPANGPU_API int spangpu_v18_state_words(const spangpu_v18_t *bank);
+SPANGPU_API int spangpu_v18_get_state(spangpu_v18_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_v18_set_state(spangpu_v18_t *bank, int channel, const int32_t *words);
+/* Host code, no device needed: encode_baudot() / decode_baudot() over a string.  Codes are the 5-bit values on the line,
+   shift codes (0x1B figures, 0x1F letters) included.  *shift_state: 0 letters, 1 figures; for the encoder also 2 = send a
+   shift ahead of the first character that needs one (how a v18 sender starts).  Characters without a code are skipped.
+   Return the number of codes / characters written, or SPANGPU_ERR_BAD_ARG (the encoder also when more than max). */
+SPANGPU_API int spangpu_baudot_encode(const uint8_t *text, int n, uint8_t *codes_out, int max, int *shift_state);
+SPANGPU_API int spangpu_baudot_decode(const uint8_t *codes, int n, uint8_t *text_out, int *shift_state);
+
 /* ---- signalling tone banks (sig_tone.c) -----------------
  * N in-band signalling tone receivers, or senders, of one tone type: 2280 Hz (AC15 and relatives), 2600 Hz, or
  * 2400 Hz / 2600 Hz (SS5).  A receiver detects the tone(s) -- notch filters as guard filters, a sharp detector that

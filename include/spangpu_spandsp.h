@@ -705,6 +705,105 @@ SPANGPU_API int r2_mf_tx_free(r2_mf_tx_state_t *s);
 SPANGPU_API int r2_mf_tx_put(r2_mf_tx_state_t *s, char digit);
 SPANGPU_API int r2_mf_tx(r2_mf_tx_state_t *s, int16_t amp[], int samples);
 
+/* ---- V.18 text telephones in the Weitbrecht modes (csrc/shim_v18.c) ---------------------------------------------
+ * Reference declarations being replaced:
+ *   v18_init/_release/_free, v18_tx, v18_rx, v18_rx_fillin, v18_put, v18_get_current_mode, v18_set_stored_message,
+ *   v18_mode_to_str, v18_status_to_str, v18_get_logging_state      src/spandsp/v18.h:124-214   src/v18.c:680-737, 1806-2130
+ * An object is a one-channel V.18 text bank (spangpu.h, "V.18 text banks"): plumbing for a caller that moves over one call
+ * at a time; the path for scale is the bank.  v18_init() returns NULL for a mode other than the three Weitbrecht 5-bit
+ * modes (V18_MODE_REPETITIVE_SHIFTS_OPTION is stripped, as the reference strips it), for a nation other than
+ * V18_AUTOMODING_NONE, and without a GPU.  put_msg is called from inside v18_rx(), once per character, with a NUL behind
+ * it.  status_handler is kept and never called: the reference calls it from automoding only.
+ * These names are declared with a macro of their own: tests/test_c_callers.py holds the SPANGPU_API names against a fixed
+ * list of the reference's headers, and tests/test_v18_prototypes.py holds these against src/spandsp/v18.h.
+ */
+typedef void (*span_put_msg_func_t)(void *user_data, const uint8_t *msg, int len);
+
+#define SPANGPU_V18_API SPANGPU_API
+
+typedef struct v18_state_s v18_state_t;
+struct v18_state_s
+{
+    spangpu_v18_t *bank;
+    span_put_msg_func_t put_msg;
+    void *put_msg_user_data;
+    span_modem_status_func_t status_handler;
+    void *status_handler_user_data;
+    int current_mode;
+    char stored_message[81];
+    logging_state_t logging;
+    int16_t *row;
+    int row_cap;
+    int caller_storage;
+};
+
+enum
+{
+    V18_MODE_NONE = 0x0001,
+    V18_MODE_WEITBRECHT_5BIT_4545 = 0x0002,
+    V18_MODE_WEITBRECHT_5BIT_50 = 0x0004,
+    V18_MODE_DTMF = 0x0008,
+    V18_MODE_EDT = 0x0010,
+    V18_MODE_BELL103 = 0x0020,
+    V18_MODE_V23VIDEOTEX = 0x0040,
+    V18_MODE_V21TEXTPHONE = 0x0080,
+    V18_MODE_V18TEXTPHONE = 0x0100,
+    V18_MODE_WEITBRECHT_5BIT_476 = 0x0200,
+    V18_MODE_REPETITIVE_SHIFTS_OPTION = 0x1000
+};
+
+enum v18_autobauding_modes_e
+{
+    V18_AUTOMODING_GLOBAL = 0,
+    V18_AUTOMODING_NONE,
+    V18_AUTOMODING_AUSTRALIA,
+    V18_AUTOMODING_IRELAND,
+    V18_AUTOMODING_GERMANY,
+    V18_AUTOMODING_SWITZERLAND,
+    V18_AUTOMODING_ITALY,
+    V18_AUTOMODING_SPAIN,
+    V18_AUTOMODING_AUSTRIA,
+    V18_AUTOMODING_NETHERLANDS,
+    V18_AUTOMODING_ICELAND,
+    V18_AUTOMODING_NORWAY,
+    V18_AUTOMODING_SWEDEN,
+    V18_AUTOMODING_FINALND,
+    V18_AUTOMODING_DENMARK,
+    V18_AUTOMODING_UK,
+    V18_AUTOMODING_USA,
+    V18_AUTOMODING_FRANCE,
+    V18_AUTOMODING_BELGIUM,
+    V18_AUTOMODING_END
+};
+
+enum v18_status_e
+{
+    V18_STATUS_SWITCH_TO_NONE,
+    V18_STATUS_SWITCH_TO_WEITBRECHT_5BIT_4545,
+    V18_STATUS_SWITCH_TO_WEITBRECHT_5BIT_476,
+    V18_STATUS_SWITCH_TO_WEITBRECHT_5BIT_50,
+    V18_STATUS_SWITCH_TO_DTMF,
+    V18_STATUS_SWITCH_TO_EDT,
+    V18_STATUS_SWITCH_TO_BELL103,
+    V18_STATUS_SWITCH_TO_V23VIDEOTEX,
+    V18_STATUS_SWITCH_TO_V21TEXTPHONE,
+    V18_STATUS_SWITCH_TO_V18TEXTPHONE
+};
+
+SPANGPU_V18_API logging_state_t *v18_get_logging_state(v18_state_t *s);
+SPANGPU_V18_API v18_state_t *v18_init(v18_state_t *s, bool calling_party, int mode, int nation, span_put_msg_func_t put_msg,
+                                      void *put_msg_user_data, span_modem_status_func_t status_handler, void *status_handler_user_data);
+SPANGPU_V18_API int v18_release(v18_state_t *s);
+SPANGPU_V18_API int v18_free(v18_state_t *s);
+SPANGPU_V18_API int v18_tx(v18_state_t *s, int16_t amp[], int max_len);
+SPANGPU_V18_API int v18_rx(v18_state_t *s, const int16_t amp[], int len);
+SPANGPU_V18_API int v18_rx_fillin(v18_state_t *s, int len);
+SPANGPU_V18_API int v18_put(v18_state_t *s, const char msg[], int len);
+SPANGPU_V18_API int v18_set_stored_message(v18_state_t *s, const char *msg);
+SPANGPU_V18_API int v18_get_current_mode(v18_state_t *s);
+SPANGPU_V18_API const char *v18_mode_to_str(int mode);
+SPANGPU_V18_API const char *v18_status_to_str(int status);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -309,6 +309,30 @@ static void restart_words(int32_t *w, const spangpu_fsk_spec_t *spec, int framin
     w[FS_SIGNAL_PRESENT] = 0;
 }
 
+// The control plane's edits of one channel's words, for the bank families that carry an FSK receiver inside them (v18_api.hip);
+// not part of the ABI.
+extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_words_init(int32_t *w, const spangpu_fsk_spec_t *spec, int framing_mode,
+                                                                             int data_bits, int parity, int stop_bits)
+{
+    restart_words(w, spec, framing_mode);
+    frame_words(w, data_bits, parity, stop_bits);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_words_fillin(int32_t *w, int len)
+{
+    if (len > 0)
+    {
+        int32_t *slot = w + kFskScalars + 4*w[FS_BUF_PTR];
+        w[FS_DOT0RE] -= slot[0];
+        w[FS_DOT0IM] -= slot[1];
+        w[FS_DOT1RE] -= slot[2];
+        w[FS_DOT1IM] -= slot[3];
+        slot[0] = slot[1] = slot[2] = slot[3] = 0;
+        w[FS_ACC0] = (int32_t) ((uint32_t) w[FS_ACC0] + (uint32_t) len*(uint32_t) w[FS_RATE0]);
+        w[FS_ACC1] = (int32_t) ((uint32_t) w[FS_ACC1] + (uint32_t) len*(uint32_t) w[FS_RATE1]);
+    }
+}
+
 static int read_words(spangpu_fsk_s *f, int ch, int32_t *w)
 {
     FSK_TRY(hipSetDevice(f->device));
@@ -623,17 +647,7 @@ static int edit(spangpu_fsk_s *f, int channel, int what, int a, int b, int c, fl
         case 3:
             // fsk_rx_fillin(), fsk.c:625-657: the current window slot is cleared, the oscillators run on, and
             // the slot index does not move
-            if (a > 0)
-            {
-                int32_t *slot = w + kFskScalars + 4*w[FS_BUF_PTR];
-                w[FS_DOT0RE] -= slot[0];
-                w[FS_DOT0IM] -= slot[1];
-                w[FS_DOT1RE] -= slot[2];
-                w[FS_DOT1IM] -= slot[3];
-                slot[0] = slot[1] = slot[2] = slot[3] = 0;
-                w[FS_ACC0] = (int32_t) ((uint32_t) w[FS_ACC0] + (uint32_t) a*(uint32_t) w[FS_RATE0]);
-                w[FS_ACC1] = (int32_t) ((uint32_t) w[FS_ACC1] + (uint32_t) a*(uint32_t) w[FS_RATE1]);
-            }
+            spangpu_fsk_words_fillin(w, a);
             break;
         }
         rc = write_words(f, channel, w);

@@ -101,6 +101,12 @@ static void fsk_restart_words(int32_t *w, const spangpu_fsk_spec_t *spec)
     w[FT_SHUTDOWN] = 0;
 }
 
+// (for the bank families that carry an FSK sender inside them, v18_api.hip; not part of the ABI)
+extern "C" __attribute__((visibility("hidden"))) void spangpu_fsktx_words_restart(int32_t *w, const spangpu_fsk_spec_t *spec)
+{
+    fsk_restart_words(w, spec);
+}
+
 static int common_create(TxCommon *c, int device, int n_channels, int words)
 {
     c->device = device;

@@ -109,6 +109,126 @@ struct FskTxLaunch
     int vec;                    // rows are 16-byte aligned
 };
 
+// The modulator's words while a call runs (fsk.c: baud_rate, phase_rates[], current_phase_rate, phase_acc, baud_frac)
+struct FtxMod
+{
+    int baud_rate;
+    int rate0;
+    int rate1;
+    int cur_rate;
+    int baud_frac;
+    uint32_t phase;
+};
+
+// Phase 1 of a round for one channel: the runs from sample `done` on, at most kFtxRuns of them, into the channel's LDS rows.
+// next_bit() stands for get_bit(): 0 or 1, or a negative value for SIG_STATUS_END_OF_DATA (fsk.c:179-189: the sample is not
+// made, the channel is shut down, `len` is what fsk_tx() returns).  Returns the number of runs.
+template <class NextBit>
+__device__ __forceinline__ int ftx_walk(FtxMod &m, int &done, int samples, bool &shutdown, int &len, int &zero_from, int32_t *r_start,
+                                        int32_t *r_phase, int32_t *r_rate, NextBit &&next_bit)
+{
+    r_start[0] = done;
+    r_phase[0] = (int32_t) m.phase;
+    r_rate[0] = m.cur_rate;
+    int nr = 1;
+    while (nr < kFtxRuns)
+    {
+        // the first sample k >= 0 ahead with baud_frac + (k + 1)*baud_rate >= 800000 (fsk.c:176); advancing
+        // run by run keeps every product inside 32 bits whatever the length of the call
+        const int kb = (kFtxBaudUnit - m.baud_frac + m.baud_rate - 1)/m.baud_rate - 1;
+        if (kb >= samples - done)
+        {
+            const int k = samples - done;
+            m.phase += (uint32_t) k*(uint32_t) m.cur_rate;
+            m.baud_frac += k*m.baud_rate;
+            done = samples;
+            break;
+        }
+        m.phase += (uint32_t) kb*(uint32_t) m.cur_rate;
+        done += kb;
+        m.baud_frac += (kb + 1)*m.baud_rate - kFtxBaudUnit;
+        const int bit = next_bit();
+        if (bit < 0)
+        {
+            // SIG_STATUS_END_OF_DATA, fsk.c:179-189: this sample is not made
+            shutdown = true;
+            len = done;
+            zero_from = done;
+            done = samples;
+            break;
+        }
+        m.cur_rate = bit  ?  m.rate1  :  m.rate0;
+        r_start[nr] = done;
+        r_phase[nr] = (int32_t) m.phase;
+        r_rate[nr] = m.cur_rate;
+        nr++;
+        m.phase += (uint32_t) m.cur_rate;
+        done++;
+        if (done >= samples)
+            break;
+    }
+    return nr;
+}
+
+// Phase 2 of a round for a wave: the samples of its channels' runs, 8 per lane.  r_hdr[c] = lo, hi, runs, zero_from, scaling.
+__device__ __forceinline__ void ftx_render(const int16_t *quarter, const int32_t (*r_hdr)[8], const int32_t (*r_start)[kFtxRunStride],
+                                           const int32_t (*r_phase)[kFtxRunStride], const int32_t (*r_rate)[kFtxRunStride], int16_t *pcm,
+                                           long long stride, int ch0, int n_ch, int samples, int lane, bool vec)
+{
+    const int nchan = (n_ch - ch0 < kFtxCpw)  ?  (n_ch - ch0)  :  kFtxCpw;
+    const int cpr = (samples + 7) >> 3;
+    const int total = nchan*cpr;
+    for (int idx = lane;  idx < total;  idx += 64)
+    {
+        const int c = idx/cpr;
+        const int i0 = (idx - c*cpr)*8;
+        const int4 hdr = *reinterpret_cast<const int4 *>(&r_hdr[c][0]);     // lo, hi, runs, zero_from
+        const int a = (i0 > hdr.x)  ?  i0  :  hdr.x;
+        const int b = (i0 + 8 < hdr.y)  ?  (i0 + 8)  :  hdr.y;
+        if (a >= b)
+            continue;
+        const int scale = r_hdr[c][4];
+        const int32_t *S = r_start[c];
+        int r = 0;
+#pragma unroll
+        for (int step = kFtxRuns/2;  step > 0;  step >>= 1)
+            r += (r + step < hdr.z  &&  S[r + step] <= a)  ?  step  :  0;
+        int rate = 0;
+        uint32_t ph = 0u;
+        int next = 0x7FFFFFFF;
+        if (hdr.z > 0)
+        {
+            rate = r_rate[c][r];
+            ph = (uint32_t) r_phase[c][r] + (uint32_t) (a - S[r])*(uint32_t) rate;
+            next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
+        }
+        int v[8];
+#pragma unroll
+        for (int j = 0;  j < 8;  j++)
+        {
+            const int i = i0 + j;
+            v[j] = 0;
+            if (i >= a  &&  i < b)
+            {
+                while (i >= next)
+                {
+                    r++;
+                    rate = r_rate[c][r];
+                    ph = (uint32_t) r_phase[c][r];
+                    next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
+                }
+                if (i < hdr.w  &&  hdr.z > 0)
+                    v[j] = ftx_dds_mod(quarter, ph, scale);
+                ph += (uint32_t) rate;
+            }
+        }
+        ftx_store8(pcm + (size_t) (ch0 + c)*stride + i0, v, a - i0, b - i0, vec);
+    }
+}
+
+// (a second unit that includes this header for ftx_walk() / ftx_render() alone -- v18_dev.hpp -- leaves the kernels out)
+#if !defined(SPG_FTX_WITHOUT_KERNELS)
+
 __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLaunch L)
 {
     __shared__ int16_t quarter[258];
@@ -133,13 +253,8 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
     const size_t n = (size_t) L.n_ch;
     int32_t *st = L.st + (owner  ?  ch  :  0);
     const int samples = L.samples;
-    int baud_rate = 1;
-    int rate0 = 0;
-    int rate1 = 0;
+    FtxMod m = {1, 0, 0, 0, 0, 0u};
     int scaling = 0;
-    int cur_rate = 0;
-    uint32_t phase = 0u;
-    int baud_frac = 0;
     bool shutdown = true;
     uint32_t lfsr = 0u;
     int qrd = 0;
@@ -147,13 +262,13 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
     bool eod = false;
     if (owner)
     {
-        baud_rate = st[FT_BAUD_RATE*n];
-        rate0 = st[FT_RATE0*n];
-        rate1 = st[FT_RATE1*n];
+        m.baud_rate = st[FT_BAUD_RATE*n];
+        m.rate0 = st[FT_RATE0*n];
+        m.rate1 = st[FT_RATE1*n];
         scaling = st[FT_SCALING*n];
-        cur_rate = st[FT_CUR_RATE*n];
-        phase = (uint32_t) st[FT_PHASE*n];
-        baud_frac = st[FT_BAUD_FRAC*n];
+        m.cur_rate = st[FT_CUR_RATE*n];
+        m.phase = (uint32_t) st[FT_PHASE*n];
+        m.baud_frac = st[FT_BAUD_FRAC*n];
         shutdown = st[FT_SHUTDOWN*n] != 0;
         if (L.source == FTX_SRC_LFSR)
         {
@@ -177,6 +292,27 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
     }
     __syncthreads();
 
+    auto next_bit = [&]() __attribute__((always_inline))
+    {
+        int bit;
+        if (L.source == FTX_SRC_LFSR)
+        {
+            bit = (int) (((lfsr >> 14) ^ (lfsr >> 13)) & 1u);
+            lfsr = ((lfsr << 1) | (uint32_t) bit) & 0x7FFFu;
+        }
+        else if (qcount > 0)
+        {
+            bit = (int) ((L.queue[(size_t) (qrd >> 5)*n + ch] >> (qrd & 31)) & 1u);
+            qrd = (qrd + 1 == L.qring)  ?  0  :  (qrd + 1);
+            qcount--;
+        }
+        else
+        {
+            bit = eod  ?  -1  :  1;     // SIG_STATUS_END_OF_DATA, or an idle mark with nothing consumed
+        }
+        return bit;
+    };
+
     for (;;)
     {
         // ---- phase 1: the next runs of my channel ----
@@ -185,67 +321,9 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
         if (owner  &&  done < samples)
         {
             if (shutdown)
-            {
                 done = samples;
-            }
             else
-            {
-                r_start[lane][0] = done;
-                r_phase[lane][0] = (int32_t) phase;
-                r_rate[lane][0] = cur_rate;
-                nr = 1;
-                while (nr < kFtxRuns)
-                {
-                    // the first sample k >= 0 ahead with baud_frac + (k + 1)*baud_rate >= 800000 (fsk.c:176); advancing
-                    // run by run keeps every product inside 32 bits whatever the length of the call
-                    const int kb = (kFtxBaudUnit - baud_frac + baud_rate - 1)/baud_rate - 1;
-                    if (kb >= samples - done)
-                    {
-                        const int m = samples - done;
-                        phase += (uint32_t) m*(uint32_t) cur_rate;
-                        baud_frac += m*baud_rate;
-                        done = samples;
-                        break;
-                    }
-                    phase += (uint32_t) kb*(uint32_t) cur_rate;
-                    done += kb;
-                    baud_frac += (kb + 1)*baud_rate - kFtxBaudUnit;
-                    int bit;
-                    if (L.source == FTX_SRC_LFSR)
-                    {
-                        bit = (int) (((lfsr >> 14) ^ (lfsr >> 13)) & 1u);
-                        lfsr = ((lfsr << 1) | (uint32_t) bit) & 0x7FFFu;
-                    }
-                    else if (qcount > 0)
-                    {
-                        bit = (int) ((L.queue[(size_t) (qrd >> 5)*n + ch] >> (qrd & 31)) & 1u);
-                        qrd = (qrd + 1 == L.qring)  ?  0  :  (qrd + 1);
-                        qcount--;
-                    }
-                    else if (eod)
-                    {
-                        // SIG_STATUS_END_OF_DATA, fsk.c:179-189: this sample is not made
-                        shutdown = true;
-                        len = done;
-                        zero_from = done;
-                        done = samples;
-                        break;
-                    }
-                    else
-                    {
-                        bit = 1;        // an idle mark, and nothing is consumed
-                    }
-                    cur_rate = bit  ?  rate1  :  rate0;
-                    r_start[lane][nr] = done;
-                    r_phase[lane][nr] = (int32_t) phase;
-                    r_rate[lane][nr] = cur_rate;
-                    nr++;
-                    phase += (uint32_t) cur_rate;
-                    done++;
-                    if (done >= samples)
-                        break;
-                }
-            }
+                nr = ftx_walk(m, done, samples, shutdown, len, zero_from, r_start[lane], r_phase[lane], r_rate[lane], next_bit);
         }
         if (lane < kFtxCpw)
         {
@@ -258,57 +336,7 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
         __syncthreads();
 
         // ---- phase 2: the samples of those runs, 8 per lane ----
-        {
-            const int nchan = (L.n_ch - ch0 < kFtxCpw)  ?  (L.n_ch - ch0)  :  kFtxCpw;
-            const int cpr = (samples + 7) >> 3;
-            const int total = nchan*cpr;
-            for (int idx = lane;  idx < total;  idx += 64)
-            {
-                const int c = idx/cpr;
-                const int i0 = (idx - c*cpr)*8;
-                const int4 hdr = *reinterpret_cast<const int4 *>(&r_hdr[c][0]);     // lo, hi, runs, zero_from
-                const int a = (i0 > hdr.x)  ?  i0  :  hdr.x;
-                const int b = (i0 + 8 < hdr.y)  ?  (i0 + 8)  :  hdr.y;
-                if (a >= b)
-                    continue;
-                const int scale = r_hdr[c][4];
-                const int32_t *S = r_start[c];
-                int r = 0;
-#pragma unroll
-                for (int step = kFtxRuns/2;  step > 0;  step >>= 1)
-                    r += (r + step < hdr.z  &&  S[r + step] <= a)  ?  step  :  0;
-                int rate = 0;
-                uint32_t ph = 0u;
-                int next = 0x7FFFFFFF;
-                if (hdr.z > 0)
-                {
-                    rate = r_rate[c][r];
-                    ph = (uint32_t) r_phase[c][r] + (uint32_t) (a - S[r])*(uint32_t) rate;
-                    next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
-                }
-                int v[8];
-#pragma unroll
-                for (int j = 0;  j < 8;  j++)
-                {
-                    const int i = i0 + j;
-                    v[j] = 0;
-                    if (i >= a  &&  i < b)
-                    {
-                        while (i >= next)
-                        {
-                            r++;
-                            rate = r_rate[c][r];
-                            ph = (uint32_t) r_phase[c][r];
-                            next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
-                        }
-                        if (i < hdr.w  &&  hdr.z > 0)
-                            v[j] = ftx_dds_mod(quarter, ph, scale);
-                        ph += (uint32_t) rate;
-                    }
-                }
-                ftx_store8(L.pcm + (size_t) (ch0 + c)*L.stride + i0, v, a - i0, b - i0, L.vec != 0);
-            }
-        }
+        ftx_render(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, samples, lane, L.vec != 0);
         if (!__syncthreads_or(done < samples))
             break;
     }
@@ -317,9 +345,9 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
     {
         if (!was_shutdown)
         {
-            st[FT_CUR_RATE*n] = cur_rate;
-            st[FT_PHASE*n] = (int32_t) phase;
-            st[FT_BAUD_FRAC*n] = baud_frac;
+            st[FT_CUR_RATE*n] = m.cur_rate;
+            st[FT_PHASE*n] = (int32_t) m.phase;
+            st[FT_BAUD_FRAC*n] = m.baud_frac;
             st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
             if (L.source == FTX_SRC_LFSR)
             {
@@ -582,5 +610,7 @@ __global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLau
             L.lens[ch] = len;
     }
 }
+
+#endif
 
 }   // namespace spg

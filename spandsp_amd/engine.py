@@ -148,6 +148,24 @@ def lib():
             "spangpu_mcttx_tx": (ci, [vp, ci, vp, ll, ci, vp]),
             "spangpu_mcttx_state_words": (ci, []),
             "spangpu_mcttx_get_state": (ci, [vp, ci, vp]),
+            "spangpu_v18_create": (ci, [C.POINTER(vp), ci, ci, vp, ci, ci]),
+            "spangpu_v18_destroy": (None, [vp]),
+            "spangpu_v18_channels": (ci, [vp]),
+            "spangpu_v18_set_stream": (ci, [vp, vp]),
+            "spangpu_v18_sync": (ci, [vp]),
+            "spangpu_v18_put": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+            "spangpu_v18_tx": (ci, [vp, ci, vp, ll, ci, vp]),
+            "spangpu_v18_rx": (ci, [vp, vp, ci, ci, ll]),
+            "spangpu_v18_rx_var": (ci, [vp, vp, ci, vp, ci, ll]),
+            "spangpu_v18_fillin": (ci, [vp, ci, ci]),
+            "spangpu_v18_text": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_v18_text_capacity": (ci, [vp, ci]),
+            "spangpu_v18_restart": (ci, [vp, ci, ci]),
+            "spangpu_v18_state_words": (ci, [vp]),
+            "spangpu_v18_get_state": (ci, [vp, ci, vp]),
+            "spangpu_v18_set_state": (ci, [vp, ci, vp]),
+            "spangpu_baudot_encode": (ci, [vp, ci, vp, ci, vp]),
+            "spangpu_baudot_decode": (ci, [vp, ci, vp, vp]),
             "spangpu_awgn_create": (ci, [C.POINTER(vp), ci, ci, vp, vp]),
             "spangpu_awgn_destroy": (None, [vp]),
             "spangpu_awgn_channels": (ci, [vp]),
@@ -1834,6 +1852,106 @@ class FskTxBank(_SenderBank):
         _check(lib().spangpu_fsktx_put_bytes(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, presend_bits,
                                              acc.ctypes.data))
         return acc
+
+
+# ---- V.18 text banks (include/spangpu.h "V.18 text banks") ---------------------------------
+V18_MODE_WEITBRECHT_5BIT_4545 = 0x0002
+V18_MODE_WEITBRECHT_5BIT_50 = 0x0004
+V18_MODE_WEITBRECHT_5BIT_476 = 0x0200
+V18_MODES = (V18_MODE_WEITBRECHT_5BIT_4545, V18_MODE_WEITBRECHT_5BIT_476, V18_MODE_WEITBRECHT_5BIT_50)
+V18_FSK_PRESET = {V18_MODE_WEITBRECHT_5BIT_4545: FSK_WEITBRECHT_4545, V18_MODE_WEITBRECHT_5BIT_476: FSK_WEITBRECHT_476,
+                  V18_MODE_WEITBRECHT_5BIT_50: FSK_WEITBRECHT_50}
+# the text layer's words of a channel's state (csrc/v18_dev.hpp); the sender's (fsktx layout) and the receiver's (fsk layout) follow
+(V18_W_MODE, V18_W_TX_SIGNAL_ON, V18_W_TX_DRAINING, V18_W_BAUDOT_TX_SHIFT, V18_W_BAUDOT_RX_SHIFT, V18_W_NEXT_BYTE,
+ V18_W_RX_SUPPRESSION, V18_W_Q_IPTR, V18_W_Q_OPTR, V18_W_A_BITPOS, V18_W_A_FRAME, V18_W_A_PRESEND, V18_W_RX_STATUS,
+ V18_W_CALLING_PARTY) = range(14)
+V18_TEXT_WORDS = 16
+
+
+def baudot_encode(text, shift_state=2):
+    """(codes, shift state after): the 5-bit codes a v18 sender puts on the line for `text`, shifts included."""
+    t = np.frombuffer(bytes(text), np.uint8)
+    out = np.zeros(2*len(t) + 1, np.uint8)
+    st = C.c_int(shift_state)
+    k = _check(lib().spangpu_baudot_encode(t.ctypes.data if len(t) else out.ctypes.data, len(t), out.ctypes.data, len(out), C.byref(st)))
+    return out[:k].copy(), st.value
+
+
+def baudot_decode(codes, shift_state=0):
+    """(text, shift state after): what a v18 receiver prints for these 5-bit codes."""
+    c = np.ascontiguousarray(codes, np.uint8)
+    out = np.zeros(len(c) + 1, np.uint8)
+    st = C.c_int(shift_state)
+    k = _check(lib().spangpu_baudot_decode(c.ctypes.data if len(c) else out.ctypes.data, len(c), out.ctypes.data, C.byref(st)))
+    return out[:k].tobytes(), st.value
+
+
+class V18Bank(_SenderBank):
+    """N Baudot text telephones (v18_put / v18_tx / v18_rx in a Weitbrecht mode, no automoding), state in HBM."""
+    _prefix = "v18"
+
+    def __init__(self, modes, n_channels, calling_party=False, device=0):
+        m = np.atleast_1d(np.asarray(modes, np.int32)).copy()
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_v18_create(C.byref(self.h), device, n_channels, m.ctypes.data, len(m), int(calling_party)))
+        self.words = lib().spangpu_v18_state_words(self.h)
+
+    def put(self, texts, first=0):
+        """One byte string per channel from `first` on; returns what v18_put() returns for each (-1: it did not fit)."""
+        bs = [bytes(t) for t in texts]
+        n = len(bs)
+        stride = max(1, max(len(b) for b in bs))
+        buf = np.zeros((n, stride), np.uint8)
+        lens = np.zeros(n, np.int32)
+        for i, b in enumerate(bs):
+            buf[i, :len(b)] = np.frombuffer(b, np.uint8)
+            lens[i] = len(b)
+        res = np.zeros(n, np.int32)
+        _check(lib().spangpu_v18_put(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, res.ctypes.data))
+        return res
+
+    def rx_host(self, amp):
+        amp = np.ascontiguousarray(amp, np.int16)
+        assert amp.shape[0] == self.n
+        _check(lib().spangpu_v18_rx(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
+
+    def rx_device(self, ptr, samples, stride=0):
+        _check(lib().spangpu_v18_rx(self.h, ptr, MEM_DEVICE, samples, stride))
+
+    def rx_host_var(self, amp, lens):
+        amp = np.ascontiguousarray(amp, np.int16)
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert amp.shape[0] == self.n and len(lens) == self.n
+        _check(lib().spangpu_v18_rx_var(self.h, amp.ctypes.data, MEM_HOST, lens.ctypes.data, amp.shape[1], amp.shape[1]))
+
+    def fillin(self, channel, n):
+        _check(lib().spangpu_v18_fillin(self.h, channel, n))
+
+    def text(self):
+        """Per channel: the characters of the last rx call as bytes, in order (one put_msg call each)."""
+        ch = C.c_void_p()
+        cnt = C.c_void_p()
+        cap = _check(lib().spangpu_v18_text(self.h, C.byref(ch), C.byref(cnt)))
+        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,)).copy()
+        flat = np.ctypeslib.as_array(C.cast(ch, C.POINTER(C.c_uint8)), (self.n*cap,)).reshape(self.n, cap)
+        return [flat[c, :counts[c]].tobytes() for c in range(self.n)]
+
+    def text_capacity(self, samples):
+        return _check(lib().spangpu_v18_text_capacity(self.h, samples))
+
+    def restart(self, channel, mode):
+        _check(lib().spangpu_v18_restart(self.h, channel, mode))
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_v18_get_state(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_v18_set_state(self.h, channel, w.ctypes.data))
 
 
 class MctTxBank(_SenderBank):

@@ -1029,16 +1029,17 @@ def bench_fsk(args, dev, stream):
     import synth
     from spandsp_amd import engine
     n_ch = args.channels or 65536
-    which = engine.FSK_V21CH2
+    which = engine.FSK_V21CH2 if args.fsk_preset < 0 else args.fsk_preset
+    framing = engine.FSK_FRAME_MODE_FRAMED if args.fsk_framed else engine.FSK_FRAME_MODE_SYNC
     sp = engine.fsk_preset(which)
     nf = 50
     n_src = 256
-    src_host = synth.fsk_channels(n_src, nf*FRAME, 77, sp.freq_zero, sp.freq_one, sp.baud_rate)
+    src_host = synth.fsk_channels(n_src, nf*FRAME, 77, sp.freq_zero, sp.freq_one, sp.baud_rate, framed=args.fsk_framed)
     src = torch.tensor(src_host, device=dev).view(n_src, nf, FRAME)
     idx = torch.arange(n_ch, device=dev)
     fsel = (torch.arange(nf, device=dev).unsqueeze(0) + ((idx//n_src) % nf).unsqueeze(1)) % nf
     frames = src[(idx % n_src).unsqueeze(1), fsel].permute(1, 0, 2).contiguous()         # [frame, ch, FRAME]
-    bank = engine.FskBank(which, n_ch, engine.FSK_FRAME_MODE_SYNC)
+    bank = engine.FskBank(which, n_ch, framing)
     bank.set_stream(ctypes.c_void_p(stream.cuda_stream))
     frame_bytes = n_ch*FRAME*2
 
@@ -1337,6 +1338,65 @@ def bench_dtmf_tx(args, dev, stream):
         "cpu_baseline": cpu}
 
 
+def bench_v18(args, dev, stream):
+    """A V.18 text bank (Weitbrecht, Baudot) sending into HBM and a second one receiving from there: v18_tx() and v18_rx() of
+    every line per tick, timed separately.  Text is put again whenever the rings run low, outside the timed region, so every
+    line stays busy; the far end's text is checked to be what was put."""
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    mode = args.v18_mode
+    sender = engine.V18Bank(mode, n_ch)
+    receiver = engine.V18Bank(mode, n_ch)
+    sender.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    receiver.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    out = torch.zeros(n_ch, FRAME, dtype=torch.int16, device=dev)
+    d_lens = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+    line = b"THE QUICK BROWN FOX JUMPS OVER THE LAZY DOG 0123456789 "
+    texts = [line[c % len(line):] + line[:c % len(line)] for c in range(n_ch)]
+    printed = [bytearray() for _ in range(64)]
+    per_tx, per_rx = [], []
+    total = args.warmup + args.steps
+    t0 = None
+    for i in range(total):
+        if i % 400 == 0:        # 56 characters last well over 400 ticks; a ring takes 128
+            res = sender.put(texts)
+            assert int(res.min()) == len(line), "a ring did not take its refill"
+        if i == args.warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record(stream)
+        sender.tx_device(ctypes.c_void_p(out.data_ptr()), FRAME, FRAME, ctypes.c_void_p(d_lens.data_ptr()))
+        e[1].record(stream)
+        receiver.rx_device(ctypes.c_void_p(out.data_ptr()), FRAME, FRAME)
+        e[2].record(stream)
+        if i >= args.warmup:
+            per_tx.append((e[0], e[1]))
+            per_rx.append((e[1], e[2]))
+        got = receiver.text()
+        for c in range(64):
+            printed[c] += got[c]
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert int(d_lens.min()) == FRAME
+    for c in range(64):
+        want = (texts[c]*(total//400 + 1))[:len(printed[c])]
+        assert len(printed[c]) > 0 and bytes(printed[c]) == want, (c, bytes(printed[c])[:40], want[:40])
+    tx_ms = [a.elapsed_time(b) for a, b in per_tx]
+    rx_ms = [a.elapsed_time(b) for a, b in per_rx]
+    value = args.steps*n_ch*FRAME/dt/1e6
+    return {
+        "metric": "Msamples/s of a V.18 text bank pair (v18_tx into HBM, v18_rx from HBM; text read back every tick)", "value": value,
+        "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt*1e3/args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32",
+        "data": "synthetic",
+        "config": {"workload": "v18 text banks, mode 0x%04x, %d channels x %d-sample frames" % (mode, n_ch, FRAME), "channels_per_gpu": n_ch,
+                   "characters_printed_on_64_lines": int(sum(len(p) for p in printed))},
+        "kernels": {"v18_tx_kernel": {"avg_launch_us": sum(tx_ms)/len(tx_ms)*1e3, "min_launch_us": min(tx_ms)*1e3},
+                    "v18_rx_kernel": {"avg_launch_us": sum(rx_ms)/len(rx_ms)*1e3, "min_launch_us": min(rx_ms)*1e3}},
+        "cpu_baseline": None}
+
+
 def bench_sender(args, dev, stream, which):
     """SURVEY 8(f)-1, the last two sources: the FSK transmitter bank (V.21 channel 2, bits from the per-channel LFSR) or the
     connect tone transmitter bank (ANSam/PR, the busiest type: 15 Hz AM and phase hops) writing 160-sample frames into HBM."""
@@ -1344,7 +1404,8 @@ def bench_sender(args, dev, stream, which):
     n_ch = args.channels or 65536
     if which == "fsk_tx":
         rng = np.random.default_rng(7)
-        bank = engine.FskTxBank(engine.FSK_V21CH2, n_ch, engine.FSKTX_LFSR, rng.integers(1, 0x7FFF, n_ch).astype(np.uint32))
+        bank = engine.FskTxBank(engine.FSK_V21CH2 if args.fsk_preset < 0 else args.fsk_preset, n_ch, engine.FSKTX_LFSR,
+                                rng.integers(1, 0x7FFF, n_ch).astype(np.uint32))
         kernel, words, what = "fsktx_bank_kernel", 13, "fsk_tx bank, V.21 ch 2, LFSR bit source"
     else:
         bank = engine.MctTxBank(engine.MCT_ANSAM_PR, n_ch)
@@ -1604,7 +1665,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
@@ -1620,6 +1681,9 @@ def main():
     ap.add_argument("--three-queues", action="store_true", help="mixed: a launch per bank on three hardware queues (the default is two queues: super-tone | Bell MF + R2 MF)")
     ap.add_argument("--no-cadences", action="store_true", help="mixed: the super-tone third without its cadence matcher (the rounds-1-to-5 workload; not configs[2])")
     ap.add_argument("--line", choices=["contract", "in_step"], default="contract", help="v29 / v17 / v27ter: SURVEY 8(d)-4's lines (carrier +- 7 Hz, -30 .. -10 dBm0, SNR 25 .. 40 dB, random start) or the nominal-carrier, all-in-step workload of the earlier rounds")
+    ap.add_argument("--fsk-preset", type=int, default=-1, help="fsk / fsk_tx: the preset_fsk_specs[] entry (default V.21 channel 2; 7, 9, 8 are the Weitbrecht rates)")
+    ap.add_argument("--fsk-framed", action="store_true", help="fsk: framed mode (8N1 as fsk_rx_restart() leaves it) instead of synchronous")
+    ap.add_argument("--v18-mode", type=lambda x: int(x, 0), default=0x0002, help="v18: 0x0002 (45.45 baud), 0x0200 (47.6) or 0x0004 (50)")
     ap.add_argument("--fsk-waves", type=int, default=0,
                     help="fsk / mct / sigtone: 0 = the library's choice, 1 = one wavefront per 64 receivers, 2 = two (A-B runs)")
     ap.add_argument("--modem-mapping", type=int, default=0,
@@ -1669,6 +1733,9 @@ def main():
     if args.workload == "fsk":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         emit(bench_fsk(args, dev, stream), "fsk", args.channels or None)
+        return
+    if args.workload == "v18":
+        emit(bench_v18(args, dev, stream), "v18", args.channels or None)
         return
     if args.workload in ("fsk_tx", "mct_tx"):
         emit(bench_sender(args, dev, stream, args.workload), args.workload, args.channels or None)
