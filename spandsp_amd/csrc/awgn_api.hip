@@ -10,33 +10,15 @@
 
 #include "../../include/spangpu.h"
 #include "awgn_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define AWGN_TRY(expr)                                                                      \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
-
 struct spangpu_awgn_s
 {
-    int device;
-    int n_ch;
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;
-    int16_t *d_amp;
-    size_t amp_cap;
+    BankCore c;
+    int16_t *d_amp;         // staging for a host caller: whole rows at the caller's stride
+    size_t amp_cap;         // samples
 };
 
 static void put_double(int32_t w[], double v)
@@ -76,45 +58,31 @@ int spangpu_awgn_create(spangpu_awgn_t **out, int device, int n_channels, const 
     if (out == NULL  ||  n_channels <= 0  ||  seeds == NULL  ||  levels_dbm0 == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     *out = NULL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    AWGN_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_awgn_s *b = (spangpu_awgn_s *) calloc(1, sizeof(*b));
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    b->device = device;
-    b->n_ch = n_channels;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
-    {
-        free(b);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
-    }
-    b->own_stream = true;
-    const size_t words = (size_t) kAwgnWords*n_channels;
-    int32_t *host = (int32_t *) malloc(words*sizeof(int32_t));
-    if (host == NULL
-        ||  hipMalloc(&b->st, words*sizeof(int32_t)) != hipSuccess)
-    {
-        free(host);
-        spangpu_awgn_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the noise source bank failed");
-    }
+    int32_t *host = (int32_t *) malloc((size_t) kAwgnWords*n_channels*sizeof(int32_t));
+    if (host == NULL)
+        rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the noise source bank failed");
+    else
+        rc = core_create(&b->c, device, n_channels, kAwgnWords);
     int32_t one[kAwgnWords];
-    for (int c = 0;  c < n_channels;  c++)
+    for (int c = 0;  rc == SPANGPU_OK  &&  c < n_channels;  c++)
     {
         seed_words(one, seeds[c], levels_dbm0[c]);
         for (int k = 0;  k < kAwgnWords;  k++)
             host[(size_t) k*n_channels + c] = one[k];
     }
-    hipError_t e = hipMemcpy(b->st, host, words*sizeof(int32_t), hipMemcpyHostToDevice);
+    if (rc == SPANGPU_OK)
+        rc = core_upload(&b->c, host);
     free(host);
-    if (e != hipSuccess)
+    if (rc != SPANGPU_OK)
     {
         spangpu_awgn_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+        return rc;
     }
     *out = b;
     return SPANGPU_OK;
@@ -124,86 +92,58 @@ void spangpu_awgn_destroy(spangpu_awgn_t *b)
 {
     if (b == NULL)
         return;
-    (void) hipSetDevice(b->device);
-    if (b->stream)
-        (void) hipStreamSynchronize(b->stream);
-    (void) hipFree(b->st);
+    core_destroy(&b->c);
     (void) hipFree(b->d_amp);
-    if (b->own_stream  &&  b->stream)
-        (void) hipStreamDestroy(b->stream);
     free(b);
 }
 
-int spangpu_awgn_channels(const spangpu_awgn_t *b) { return b  ?  b->n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_awgn_channels(const spangpu_awgn_t *b) { return b  ?  b->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 int spangpu_awgn_state_words(const spangpu_awgn_t *b) { return b  ?  kAwgnWords  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_awgn_set_stream(spangpu_awgn_t *b, void *stream)
 {
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    AWGN_TRY(hipSetDevice(b->device));
-    AWGN_TRY(hipStreamSynchronize(b->stream));
-    if (b->own_stream)
-        (void) hipStreamDestroy(b->stream);
-    b->stream = (hipStream_t) stream;
-    b->own_stream = false;
-    return SPANGPU_OK;
+    return core_set_stream(&b->c, stream);
 }
 
 int spangpu_awgn_sync(spangpu_awgn_t *b)
 {
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    AWGN_TRY(hipSetDevice(b->device));
-    AWGN_TRY(hipStreamSynchronize(b->stream));
-    return SPANGPU_OK;
+    return core_sync(&b->c);
 }
 
 int spangpu_awgn_reinit(spangpu_awgn_t *b, int channel, int seed, float level_dbm0)
 {
-    if (b == NULL  ||  channel < 0  ||  channel >= b->n_ch)
+    if (b == NULL  ||  !channel_ok(&b->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    AWGN_TRY(hipSetDevice(b->device));
-    AWGN_TRY(hipStreamSynchronize(b->stream));
     int32_t one[kAwgnWords];
     seed_words(one, seed, level_dbm0);
-    AWGN_TRY(hipMemcpy2D(b->st + channel, (size_t) b->n_ch*sizeof(int32_t), one, sizeof(int32_t), sizeof(int32_t),
-                         kAwgnWords, hipMemcpyHostToDevice));
-    return SPANGPU_OK;
+    return core_rw_words(&b->c, channel, 0, kAwgnWords, one, true);
 }
 
 int spangpu_awgn_tx(spangpu_awgn_t *b, int mem_kind, int16_t *amp, long long stride, int samples, int mix)
 {
-    if (b == NULL  ||  amp == NULL  ||  samples <= 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    if (stride <= 0)
-        stride = samples;
-    if (stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < samples");
-    AWGN_TRY(hipSetDevice(b->device));
+    int rc = rx_args_ok(b, mem_kind, amp, samples, &stride);
+    if (rc != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipSetDevice(b->c.device));
     AwgnLaunch L;
     memset(&L, 0, sizeof(L));
-    L.st = b->st;
-    L.n_ch = b->n_ch;
+    L.st = b->c.st;
+    L.n_ch = b->c.n_ch;
     L.samples = samples;
     L.mix = mix  ?  1  :  0;
-    const size_t bytes = (size_t) b->n_ch*(size_t) stride*sizeof(int16_t);
+    // (not a PcmStage: the noise is mixed into whole rows at the caller's own stride, and the kernel has no vector path)
+    const size_t count = (size_t) b->c.n_ch*(size_t) stride;
+    const size_t bytes = count*sizeof(int16_t);
     if (mem_kind == SPANGPU_MEM_HOST)
     {
-        if (bytes > b->amp_cap)
-        {
-            AWGN_TRY(hipStreamSynchronize(b->stream));
-            (void) hipFree(b->d_amp);
-            b->d_amp = NULL;
-            b->amp_cap = 0;
-            if (hipMalloc(&b->d_amp, bytes) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "sample staging buffer");
-            b->amp_cap = bytes;
-        }
+        if ((rc = grow(&b->d_amp, &b->amp_cap, count, 1, b->c.stream)) != SPANGPU_OK)
+            return rc;
         if (mix)
-            AWGN_TRY(hipMemcpyAsync(b->d_amp, amp, bytes, hipMemcpyHostToDevice, b->stream));
+            SPG_TRY(hipMemcpyAsync(b->d_amp, amp, bytes, hipMemcpyHostToDevice, b->c.stream));
         L.amp = b->d_amp;
     }
     else
@@ -211,26 +151,22 @@ int spangpu_awgn_tx(spangpu_awgn_t *b, int mem_kind, int16_t *amp, long long str
         L.amp = amp;
     }
     L.stride = stride;
-    hipLaunchKernelGGL(awgn_bank_kernel, dim3((b->n_ch + 63)/64), dim3(64), (97*64 + 2*kLogTab)*sizeof(double), b->stream, L);
-    AWGN_TRY(hipGetLastError());
+    hipLaunchKernelGGL(awgn_bank_kernel, dim3((b->c.n_ch + 63)/64), dim3(64), (97*64 + 2*kLogTab)*sizeof(double), b->c.stream, L);
+    SPG_TRY(hipGetLastError());
     if (mem_kind == SPANGPU_MEM_HOST)
     {
         // the caller's buffer is only borrowed for this call
-        AWGN_TRY(hipMemcpyAsync(amp, b->d_amp, bytes, hipMemcpyDeviceToHost, b->stream));
-        AWGN_TRY(hipStreamSynchronize(b->stream));
+        SPG_TRY(hipMemcpyAsync(amp, b->d_amp, bytes, hipMemcpyDeviceToHost, b->c.stream));
+        SPG_TRY(hipStreamSynchronize(b->c.stream));
     }
     return samples;
 }
 
 int spangpu_awgn_get_state(spangpu_awgn_t *b, int channel, int32_t *words)
 {
-    if (b == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= b->n_ch)
+    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    AWGN_TRY(hipSetDevice(b->device));
-    AWGN_TRY(hipStreamSynchronize(b->stream));
-    AWGN_TRY(hipMemcpy2D(words, sizeof(int32_t), b->st + channel, (size_t) b->n_ch*sizeof(int32_t), sizeof(int32_t),
-                         kAwgnWords, hipMemcpyDeviceToHost));
-    return SPANGPU_OK;
+    return core_rw_words(&b->c, channel, 0, kAwgnWords, words, false);
 }
 
 }   // extern "C"

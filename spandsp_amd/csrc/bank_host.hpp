@@ -1,0 +1,174 @@
+// bank_host.hpp -- the host plumbing the sender and side-receiver banks share (txgen, modemtx, fsktx, v18, fsk, mct, sigtone
+// and awgn _api.hip): the HIP-call macro, the device check, a bank's stream and state words, the staging of a host caller's
+// frames, grow-only device scratch, the quarter sine of dds_int.c and the put side of a bit ring.  Plain structs and free
+// functions; a bank struct embeds BankCore (and PcmStage where it stages frames) and keeps only what is its own.  Nothing
+// here is exported.
+//
+// The one behaviour this sharing makes uniform: every sender's tx refuses more than kMaxSamples samples a call (tx_args_ok);
+// before, the tone and modem senders did not.  Everything else a family does differently is a parameter or stays at its call
+// site.
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/spangpu.h"
+
+extern "C" int spangpu_set_error(int code, const char *msg);
+
+#define SPG_TRY(expr)                                                                       \
+    do                                                                                      \
+    {                                                                                       \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess)                                                               \
+        {                                                                                   \
+            char m_[256];                                                                   \
+            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
+            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
+        }                                                                                   \
+    }                                                                                       \
+    while (0)
+
+namespace spg __attribute__((visibility("hidden")))
+{
+
+constexpr int kMaxSamples = 1 << 24;        // per call: the chunk index of a wave's 16 rows stays inside 32 bits
+
+// hipGetDeviceCount, the range check, hipSetDevice: SPANGPU_ERR_NO_DEVICE where there is no GPU, never a CPU path
+int device_ok(int device);
+
+// ---- a bank's stream and its state words st[words][n_ch] -------------------------------------------------------------
+
+struct BankCore
+{
+    int device;
+    int n_ch;
+    int words;
+    hipStream_t stream;
+    bool own_stream;
+    int32_t *st;
+};
+
+int core_create(BankCore *c, int device, int n_channels, int words);        // the stream and the (unwritten) state
+int core_upload(BankCore *c, const int32_t *host);                          // all of st, as the caller prepared it
+int core_fill(BankCore *c, const int32_t *one, int lead = -1);             // one[0 .. lead) in every channel, zero after (-1: all)
+int core_set_stream(BankCore *c, void *stream);
+int core_sync(BankCore *c);
+void core_destroy(BankCore *c);                                             // syncs first; the stream goes only if the bank made it
+// words [first, first + count) of one channel, of st or of another [..][n_ch] array of the bank's
+int core_rw_at(BankCore *c, int32_t *base, int ch, int first, int count, int32_t *w, bool write);
+
+static inline int core_rw_words(BankCore *c, int ch, int first, int count, int32_t *w, bool write)
+{
+    return core_rw_at(c, c->st, ch, first, count, w, write);
+}
+
+static inline bool channel_ok(const BankCore *c, int ch)
+{
+    return ch >= 0  &&  ch < c->n_ch;
+}
+
+static inline bool range_ok(const BankCore *c, int first, int n)
+{
+    return first >= 0  &&  n > 0  &&  first <= c->n_ch - n;
+}
+
+// ---- frames of a host caller -----------------------------------------------------------------------------------------
+
+struct PcmStage
+{
+    int16_t *d_pcm;         // [n_ch][pcm_cap]
+    size_t pcm_cap;         // samples per channel, a multiple of 8
+    int32_t *d_lens;        // [n_ch]: the lengths a sender returns to a host caller (stage_lens())
+};
+
+int stage_lens(BankCore *c, PcmStage *s);
+
+static inline void stage_free(PcmStage *s)
+{
+    (void) hipFree(s->d_pcm);
+    (void) hipFree(s->d_lens);
+}
+
+static inline int mem_kind_ok(int mem_kind)
+{
+    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
+    return SPANGPU_OK;
+}
+
+// A sender's arguments: 0 <= samples <= kMaxSamples, stride >= samples.
+static inline int tx_args_ok(const void *bank, int mem_kind, const int16_t *pcm, long long stride, int samples)
+{
+    if (bank == NULL  ||  pcm == NULL  ||  samples < 0  ||  samples > kMaxSamples  ||  stride < samples)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    return mem_kind_ok(mem_kind);
+}
+
+// A receiver's: samples > 0, and stride <= 0 stands for "rows are `samples` long".
+static inline int rx_args_ok(const void *bank, int mem_kind, const int16_t *amp, int samples, long long *stride)
+{
+    if (bank == NULL  ||  amp == NULL  ||  samples <= 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    if (mem_kind_ok(mem_kind) != SPANGPU_OK)
+        return SPANGPU_ERR_BAD_ARG;
+    if (*stride <= 0)
+        *stride = samples;
+    if (*stride < samples)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < samples");
+    return SPANGPU_OK;
+}
+
+// Senders.  Where the kernel writes: the caller's rows, or the staging copy of them; then the way back.  vec may be NULL.
+int stage_out_target(BankCore *c, PcmStage *s, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens,
+                     int16_t **k_pcm, long long *k_stride, int32_t **k_lens, int *vec);
+int stage_out_back(BankCore *c, PcmStage *s, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens);
+// Receivers.  What the kernel reads: a host caller's rows are copied in, and with `sync` the copy is waited for (the buffer
+// is only borrowed for the call).
+int stage_in(BankCore *c, PcmStage *s, int mem_kind, const int16_t *amp, long long stride, int samples, bool sync,
+             const int16_t **k_pcm, long long *k_stride, int *vec);
+
+// ---- grow-only device scratch: need*per elements once need > *cap; the stream is synchronised before the old block goes --
+
+template <typename T, typename C>
+static inline int grow(T **ptr, C *cap, C need, size_t per, hipStream_t stream)
+{
+    if (need <= *cap)
+        return SPANGPU_OK;
+    SPG_TRY(hipStreamSynchronize(stream));
+    (void) hipFree(*ptr);
+    *ptr = NULL;
+    *cap = 0;
+    if (hipMalloc(ptr, (size_t) need*per*sizeof(T)) != hipSuccess)
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "device scratch");
+    *cap = need;
+    return SPANGPU_OK;
+}
+
+// dds_int.c: one quadrant of a sine, 257 entries, in device memory (hipFree() it)
+int quarter_sine_upload(int16_t **quarter);
+
+// ---- the put side of a bit ring per channel (spangpu_fsktx_put_bits(), spangpu_modemtx_put_bits()) ----------------------
+
+struct BitPut
+{
+    uint8_t *d_bits;
+    size_t bits_cap;
+    int32_t *d_blens;       // [n_ch]
+    int32_t *d_acc;         // [n_ch]
+};
+
+// rd_row / count_row: the [n_ch] rows of the bank's words that hold each ring's read index and fill
+int bitring_put(BankCore *c, BitPut *p, int32_t *rd_row, int32_t *count_row, uint32_t *queue, int qring, int qcap, int first, int n,
+                const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted);
+
+static inline void bitput_free(BitPut *p)
+{
+    (void) hipFree(p->d_bits);
+    (void) hipFree(p->d_blens);
+    (void) hipFree(p->d_acc);
+}
+
+}   // namespace spg

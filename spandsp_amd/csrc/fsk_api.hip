@@ -11,23 +11,9 @@
 
 #include "../../include/spangpu.h"
 #include "fsk_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
-
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define FSK_TRY(expr)                                                                       \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
 
 namespace spg
 {
@@ -213,17 +199,11 @@ struct spangpu_fsk_s
     const int32_t *next_lens;   // per-channel lengths of the call being prepared (device), or NULL
     int32_t *d_lens;            // [n_ch], device
     int32_t *h_lens;            // [n_ch], pinned
-    int device;
-    int n_ch;
+    BankCore c;
+    PcmStage pcm;               // staging for host-resident frames
     int span;
-    int words;                  // per channel
     spangpu_fsk_spec_t spec;
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;
     int16_t *quarter;
-    int16_t *d_pcm;             // staging for host-resident frames
-    size_t pcm_cap;
     int16_t *events;
     int32_t *ev_count;
     int ev_cap;
@@ -333,24 +313,6 @@ extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_words_fillin(i
     }
 }
 
-static int read_words(spangpu_fsk_s *f, int ch, int32_t *w)
-{
-    FSK_TRY(hipSetDevice(f->device));
-    FSK_TRY(hipMemcpy2DAsync(w, sizeof(int32_t), f->st + ch, (size_t) f->n_ch*sizeof(int32_t), sizeof(int32_t), f->words,
-                             hipMemcpyDeviceToHost, f->stream));
-    FSK_TRY(hipStreamSynchronize(f->stream));
-    return SPANGPU_OK;
-}
-
-static int write_words(spangpu_fsk_s *f, int ch, const int32_t *w)
-{
-    FSK_TRY(hipSetDevice(f->device));
-    FSK_TRY(hipMemcpy2DAsync(f->st + ch, (size_t) f->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), f->words,
-                             hipMemcpyHostToDevice, f->stream));
-    FSK_TRY(hipStreamSynchronize(f->stream));
-    return SPANGPU_OK;
-}
-
 extern "C" {
 
 int spangpu_fsk_preset(int which, spangpu_fsk_spec_t *spec)
@@ -366,64 +328,37 @@ int spangpu_fsk_create(spangpu_fsk_t **out, int device, int n_channels, const sp
     if (out == NULL  ||  spec == NULL  ||  n_channels <= 0  ||  spec->baud_rate <= 0  ||  framing_mode < 0  ||  framing_mode > 2)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     *out = NULL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    FSK_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_fsk_s *f = (spangpu_fsk_s *) calloc(1, sizeof(*f));
     if (f == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    f->device = device;
-    f->n_ch = n_channels;
     f->spec = *spec;
     f->span = span_of(spec);
-    f->words = kFskScalars + 4*f->span;
-    if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess)
+    const int words = kFskScalars + 4*f->span;
+    if ((rc = core_create(&f->c, device, n_channels, words)) != SPANGPU_OK  ||  (rc = quarter_sine_upload(&f->quarter)) != SPANGPU_OK)
     {
-        free(f);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
+        spangpu_fsk_destroy(f);
+        return rc;
     }
-    f->own_stream = true;
-    const size_t words = (size_t) f->words*n_channels;
-    if (hipMalloc(&f->st, words*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&f->quarter, 257*sizeof(int16_t)) != hipSuccess
-        ||  hipMalloc(&f->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
-        ||  (f->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL)
+    int32_t *one = (int32_t *) calloc(words, sizeof(int32_t));
+    if (hipMalloc(&f->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
+        ||  (f->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL
+        ||  one == NULL)
     {
+        free(one);
         spangpu_fsk_destroy(f);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the FSK bank failed");
     }
-    // dds_int.c: one quadrant of a sine, 257 entries
-    int16_t quarter[257];
-    for (int i = 0;  i <= 256;  i++)
-        quarter[i] = (int16_t) lrint(32767.0*sin(i*3.14159265358979323846/512.0));
-    // fsk_rx_init() = memset + fsk_rx_restart(), fsk.c:723-742
-    int32_t *one = (int32_t *) calloc(f->words, sizeof(int32_t));
-    int32_t *host = (int32_t *) calloc(words, sizeof(int32_t));
-    if (one == NULL  ||  host == NULL)
-    {
-        free(one);
-        free(host);
-        spangpu_fsk_destroy(f);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    }
+    // fsk_rx_init() = memset + fsk_rx_restart(), fsk.c:723-742; the correlation window stays zero
     restart_words(one, spec, framing_mode);
-    for (int w = 0;  w < kFskScalars;  w++)
-    {
-        for (int c = 0;  c < n_channels;  c++)
-            host[(size_t) w*n_channels + c] = one[w];
-    }
-    hipError_t e = hipMemcpy(f->st, host, words*sizeof(int32_t), hipMemcpyHostToDevice);
+    rc = core_fill(&f->c, one, kFskScalars);
     free(one);
-    free(host);
-    if (e == hipSuccess)
-        e = hipMemcpy(f->quarter, quarter, sizeof(quarter), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
+    if (rc != SPANGPU_OK)
     {
         spangpu_fsk_destroy(f);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+        return rc;
     }
     *out = f;
     return SPANGPU_OK;
@@ -433,114 +368,64 @@ void spangpu_fsk_destroy(spangpu_fsk_t *f)
 {
     if (f == NULL)
         return;
-    (void) hipSetDevice(f->device);
-    if (f->stream)
-        (void) hipStreamSynchronize(f->stream);
-    (void) hipFree(f->st);
+    core_destroy(&f->c);
+    stage_free(&f->pcm);
     (void) hipFree(f->quarter);
-    (void) hipFree(f->d_pcm);
     (void) hipFree(f->d_lens);
     if (f->h_lens) (void) hipHostFree(f->h_lens);
     (void) hipFree(f->events);
     (void) hipFree(f->ev_count);
     free(f->h_events);
     free(f->h_count);
-    if (f->own_stream  &&  f->stream)
-        (void) hipStreamDestroy(f->stream);
     free(f);
 }
 
-int spangpu_fsk_channels(const spangpu_fsk_t *f) { return f  ?  f->n_ch  :  SPANGPU_ERR_BAD_ARG; }
-int spangpu_fsk_state_words(const spangpu_fsk_t *f) { return f  ?  f->words  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_fsk_channels(const spangpu_fsk_t *f) { return f  ?  f->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_fsk_state_words(const spangpu_fsk_t *f) { return f  ?  f->c.words  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_fsk_set_stream(spangpu_fsk_t *f, void *stream)
 {
     if (f == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    FSK_TRY(hipSetDevice(f->device));
-    FSK_TRY(hipStreamSynchronize(f->stream));
-    if (f->own_stream)
-        (void) hipStreamDestroy(f->stream);
-    f->stream = (hipStream_t) stream;
-    f->own_stream = false;
-    return SPANGPU_OK;
+    return core_set_stream(&f->c, stream);
 }
 
 int spangpu_fsk_sync(spangpu_fsk_t *f)
 {
     if (f == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    FSK_TRY(hipSetDevice(f->device));
-    FSK_TRY(hipStreamSynchronize(f->stream));
-    return SPANGPU_OK;
+    return core_sync(&f->c);
 }
 
 int spangpu_fsk_rx(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, int samples, long long stride)
 {
-    if (f == NULL  ||  amp == NULL  ||  samples <= 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    if (stride <= 0)
-        stride = samples;
-    if (stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < samples");
-    FSK_TRY(hipSetDevice(f->device));
+    int rc = rx_args_ok(f, mem_kind, amp, samples, &stride);
+    if (rc != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipSetDevice(f->c.device));
     // at most one event per sample (a status change and a bit can share one sample: + 2)
-    const int cap = samples + 2;
-    if (cap > f->ev_cap)
-    {
-        FSK_TRY(hipStreamSynchronize(f->stream));
-        (void) hipFree(f->events);
-        f->events = NULL;
-        f->ev_cap = 0;
-        if (hipMalloc(&f->events, (size_t) f->n_ch*cap*sizeof(int16_t)) != hipSuccess)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "event buffer");
-        f->ev_cap = cap;
-    }
+    if ((rc = grow(&f->events, &f->ev_cap, samples + 2, (size_t) f->c.n_ch, f->c.stream)) != SPANGPU_OK)
+        return rc;
     FskLaunch L;
     memset(&L, 0, sizeof(L));
-    L.st = f->st;
+    L.st = f->c.st;
     L.quarter = f->quarter;
     L.events = f->events;
     L.ev_count = f->ev_count;
-    L.n_ch = f->n_ch;
+    L.n_ch = f->c.n_ch;
     L.samples = samples;
     L.lens = f->next_lens;
     L.span = f->span;
     L.ev_cap = f->ev_cap;
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > f->pcm_cap)
-        {
-            FSK_TRY(hipStreamSynchronize(f->stream));
-            (void) hipFree(f->d_pcm);
-            f->d_pcm = NULL;
-            f->pcm_cap = 0;
-            if (hipMalloc(&f->d_pcm, need*f->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            f->pcm_cap = need;
-        }
-        FSK_TRY(hipMemcpy2DAsync(f->d_pcm, f->pcm_cap*sizeof(int16_t), amp, (size_t) stride*sizeof(int16_t),
-                                 (size_t) samples*sizeof(int16_t), f->n_ch, hipMemcpyHostToDevice, f->stream));
-        // the caller's buffer is only borrowed for the call
-        FSK_TRY(hipStreamSynchronize(f->stream));
-        L.pcm = f->d_pcm;
-        L.stride = (long long) f->pcm_cap;
-    }
-    else
-    {
-        L.pcm = amp;
-        L.stride = stride;
-    }
-    L.vec = ((L.stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(L.pcm) & 15) == 0)  ?  1  :  0;
+    // the caller's buffer is only borrowed for the call: the copy in is waited for
+    if ((rc = stage_in(&f->c, &f->pcm, mem_kind, amp, stride, samples, true, &L.pcm, &L.stride, &L.vec)) != SPANGPU_OK)
+        return rc;
     const size_t lds = (size_t) (4*f->span*64)*sizeof(int32_t);
     if (g_fsk_waves != 1)
-        hipLaunchKernelGGL(fsk_pair_kernel, dim3((f->n_ch + 63)/64), dim3(128), lds + 2*kFskMsgWords*64*sizeof(int32_t), f->stream, L);
+        hipLaunchKernelGGL(fsk_pair_kernel, dim3((f->c.n_ch + 63)/64), dim3(128), lds + 2*kFskMsgWords*64*sizeof(int32_t), f->c.stream, L);
     else
-        hipLaunchKernelGGL(fsk_bank_kernel, dim3((f->n_ch + 63)/64), dim3(64), lds, f->stream, L);
-    FSK_TRY(hipGetLastError());
+        hipLaunchKernelGGL(fsk_bank_kernel, dim3((f->c.n_ch + 63)/64), dim3(64), lds, f->c.stream, L);
+    SPG_TRY(hipGetLastError());
     f->last_cap = f->ev_cap;
     return SPANGPU_OK;
 }
@@ -553,7 +438,7 @@ int spangpu_fsk_rx_var(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, const
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int longest = 0;
     bool all = true;
-    for (int c = 0;  c < f->n_ch;  c++)
+    for (int c = 0;  c < f->c.n_ch;  c++)
     {
         if (lens[c] < 0  ||  lens[c] > max_samples)
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
@@ -562,21 +447,21 @@ int spangpu_fsk_rx_var(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, const
     }
     if (longest == 0)
         return SPANGPU_OK;
-    for (int c = 0;  c < f->n_ch;  c++)
+    for (int c = 0;  c < f->c.n_ch;  c++)
         all &= (lens[c] == longest);
     if (stride <= 0)
         stride = max_samples;
     if (all)
         return spangpu_fsk_rx(f, amp, mem_kind, longest, stride);
-    FSK_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipSetDevice(f->c.device));
     if (f->d_lens == NULL)
     {
-        FSK_TRY(hipMalloc(&f->d_lens, (size_t) f->n_ch*sizeof(int32_t)));
-        FSK_TRY(hipHostMalloc(&f->h_lens, (size_t) f->n_ch*sizeof(int32_t)));
+        SPG_TRY(hipMalloc(&f->d_lens, (size_t) f->c.n_ch*sizeof(int32_t)));
+        SPG_TRY(hipHostMalloc(&f->h_lens, (size_t) f->c.n_ch*sizeof(int32_t)));
     }
-    FSK_TRY(hipStreamSynchronize(f->stream));
-    memcpy(f->h_lens, lens, (size_t) f->n_ch*sizeof(int32_t));
-    FSK_TRY(hipMemcpyAsync(f->d_lens, f->h_lens, (size_t) f->n_ch*sizeof(int32_t), hipMemcpyHostToDevice, f->stream));
+    SPG_TRY(hipStreamSynchronize(f->c.stream));
+    memcpy(f->h_lens, lens, (size_t) f->c.n_ch*sizeof(int32_t));
+    SPG_TRY(hipMemcpyAsync(f->d_lens, f->h_lens, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, f->c.stream));
     f->next_lens = f->d_lens;
     const int rc = spangpu_fsk_rx(f, amp, mem_kind, longest, stride);
     f->next_lens = NULL;
@@ -589,8 +474,8 @@ int spangpu_fsk_events(spangpu_fsk_t *f, const int16_t **events, const int32_t *
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (f->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_fsk_rx() yet");
-    FSK_TRY(hipSetDevice(f->device));
-    const size_t bytes = (size_t) f->n_ch*f->last_cap*sizeof(int16_t);
+    SPG_TRY(hipSetDevice(f->c.device));
+    const size_t bytes = (size_t) f->c.n_ch*f->last_cap*sizeof(int16_t);
     if (bytes > f->h_events_cap)
     {
         free(f->h_events);
@@ -599,9 +484,9 @@ int spangpu_fsk_events(spangpu_fsk_t *f, const int16_t **events, const int32_t *
             return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host event buffer");
         f->h_events_cap = bytes;
     }
-    FSK_TRY(hipMemcpyAsync(f->h_events, f->events, bytes, hipMemcpyDeviceToHost, f->stream));
-    FSK_TRY(hipMemcpyAsync(f->h_count, f->ev_count, (size_t) f->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-    FSK_TRY(hipStreamSynchronize(f->stream));
+    SPG_TRY(hipMemcpyAsync(f->h_events, f->events, bytes, hipMemcpyDeviceToHost, f->c.stream));
+    SPG_TRY(hipMemcpyAsync(f->h_count, f->ev_count, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, f->c.stream));
+    SPG_TRY(hipStreamSynchronize(f->c.stream));
     *events = f->h_events;
     *counts = f->h_count;
     return f->last_cap;
@@ -609,28 +494,28 @@ int spangpu_fsk_events(spangpu_fsk_t *f, const int16_t **events, const int32_t *
 
 int spangpu_fsk_get_state(spangpu_fsk_t *f, int channel, int32_t *words)
 {
-    if (f == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= f->n_ch)
+    if (f == NULL  ||  words == NULL  ||  !channel_ok(&f->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return read_words(f, channel, words);
+    return core_rw_words(&f->c, channel, 0, f->c.words, words, false);
 }
 
 int spangpu_fsk_set_state(spangpu_fsk_t *f, int channel, const int32_t *words)
 {
-    if (f == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= f->n_ch)
+    if (f == NULL  ||  words == NULL  ||  !channel_ok(&f->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (words[FS_SPAN] != f->span)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "the correlation span of a channel is fixed by its bank's baud rate");
-    return write_words(f, channel, words);
+    return core_rw_words(&f->c, channel, 0, f->c.words, const_cast<int32_t *>(words), true);
 }
 
 static int edit(spangpu_fsk_s *f, int channel, int what, int a, int b, int c, float x)
 {
-    if (f == NULL  ||  channel < 0  ||  channel >= f->n_ch)
+    if (f == NULL  ||  !channel_ok(&f->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    int32_t *w = (int32_t *) malloc((size_t) f->words*sizeof(int32_t));
+    int32_t *w = (int32_t *) malloc((size_t) f->c.words*sizeof(int32_t));
     if (w == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
-    int rc = read_words(f, channel, w);
+    int rc = core_rw_words(&f->c, channel, 0, f->c.words, w, false);
     if (rc == SPANGPU_OK)
     {
         switch (what)
@@ -650,7 +535,7 @@ static int edit(spangpu_fsk_s *f, int channel, int what, int a, int b, int c, fl
             spangpu_fsk_words_fillin(w, a);
             break;
         }
-        rc = write_words(f, channel, w);
+        rc = core_rw_words(&f->c, channel, 0, f->c.words, w, true);
     }
     free(w);
     return rc;

@@ -12,60 +12,29 @@
 #include "../../include/spangpu.h"
 #include "modem_tables.h"
 #include "fsktx_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define FT_TRY(expr)                                                                        \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
-
-constexpr int kMaxSamples = 1 << 24;        // per call: the chunk index of a wave's 16 rows stays inside 32 bits
-
-// What the two banks share: the stream, the state words, the quarter sine and the staging of a host caller's frame.
-struct TxCommon
-{
-    int device;
-    int n_ch;
-    int words;
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;
-    int16_t *quarter;
-    int16_t *d_pcm;
-    size_t pcm_cap;
-    int32_t *d_lens;
-};
-
 struct spangpu_fsktx_s
 {
-    TxCommon c;
+    BankCore c;
+    PcmStage pcm;
+    int16_t *quarter;
     int source;
     int qcap;               // bits a channel's ring takes
     int qring;              // ring size in bits: qcap rounded up to whole words
     uint32_t *queue;
     int32_t *h_row;         // [n_ch] host scratch: a row of state words, the list of events
     uint8_t *frame_par;     // [n_ch][3]: data bits, parity, stop bits of spangpu_fsktx_put_bytes()
-    uint8_t *d_bits;
-    int32_t *d_blens;
-    int32_t *d_acc;
-    size_t bits_cap;
-    int put_cap;
+    BitPut put;
 };
 
 struct spangpu_mcttx_s
 {
-    TxCommon c;
+    BankCore c;
+    PcmStage pcm;
+    int16_t *quarter;
     int tone_type;
     MctTxLaunch proto;      // the tone type's constants
     int32_t init[kMctTxWords];
@@ -107,153 +76,13 @@ extern "C" __attribute__((visibility("hidden"))) void spangpu_fsktx_words_restar
     fsk_restart_words(w, spec);
 }
 
-static int common_create(TxCommon *c, int device, int n_channels, int words)
+// the state, the quarter sine and the lengths of a host caller: the same in both banks
+static int sender_create(BankCore *c, PcmStage *pcm, int16_t **quarter, int device, int n_channels, int words)
 {
-    c->device = device;
-    c->n_ch = n_channels;
-    c->words = words;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
-    c->own_stream = true;
-    if (hipMalloc(&c->st, (size_t) words*n_channels*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&c->quarter, 257*sizeof(int16_t)) != hipSuccess
-        ||  hipMalloc(&c->d_lens, (size_t) n_channels*sizeof(int32_t)) != hipSuccess)
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the transmitter bank failed");
-    // dds_int.c: one quadrant of a sine, 257 entries
-    int16_t quarter[257];
-    for (int i = 0;  i <= 256;  i++)
-        quarter[i] = (int16_t) lrint(32767.0*sin(i*3.14159265358979323846/512.0));
-    if (hipMemcpy(c->quarter, quarter, sizeof(quarter), hipMemcpyHostToDevice) != hipSuccess)
-        return spangpu_set_error(SPANGPU_ERR_HIP, "table upload failed");
-    return SPANGPU_OK;
-}
-
-static void common_destroy(TxCommon *c)
-{
-    (void) hipSetDevice(c->device);
-    if (c->stream)
-        (void) hipStreamSynchronize(c->stream);
-    (void) hipFree(c->st);
-    (void) hipFree(c->quarter);
-    (void) hipFree(c->d_pcm);
-    (void) hipFree(c->d_lens);
-    if (c->own_stream  &&  c->stream)
-        (void) hipStreamDestroy(c->stream);
-}
-
-// every channel starts from the same words
-static int common_fill(TxCommon *c, const int32_t *one)
-{
-    const size_t n = (size_t) c->n_ch;
-    int32_t *host = (int32_t *) malloc((size_t) c->words*n*sizeof(int32_t));
-    if (host == NULL)
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
-    for (int k = 0;  k < c->words;  k++)
-    {
-        for (size_t ch = 0;  ch < n;  ch++)
-            host[(size_t) k*n + ch] = one[k];
-    }
-    const hipError_t e = hipMemcpy(c->st, host, (size_t) c->words*n*sizeof(int32_t), hipMemcpyHostToDevice);
-    free(host);
-    if (e != hipSuccess)
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
-    return SPANGPU_OK;
-}
-
-static int common_set_stream(TxCommon *c, void *stream)
-{
-    FT_TRY(hipSetDevice(c->device));
-    FT_TRY(hipStreamSynchronize(c->stream));
-    if (c->own_stream)
-        (void) hipStreamDestroy(c->stream);
-    c->stream = (hipStream_t) stream;
-    c->own_stream = false;
-    return SPANGPU_OK;
-}
-
-static int common_sync(TxCommon *c)
-{
-    FT_TRY(hipSetDevice(c->device));
-    FT_TRY(hipStreamSynchronize(c->stream));
-    return SPANGPU_OK;
-}
-
-// words [first, first + count) of one channel
-static int rw_words(TxCommon *c, int ch, int first, int count, int32_t *w, bool write)
-{
-    FT_TRY(hipSetDevice(c->device));
-    int32_t *at = c->st + (size_t) first*c->n_ch + ch;
-    if (write)
-        FT_TRY(hipMemcpy2DAsync(at, (size_t) c->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), count,
-                                hipMemcpyHostToDevice, c->stream));
-    else
-        FT_TRY(hipMemcpy2DAsync(w, sizeof(int32_t), at, (size_t) c->n_ch*sizeof(int32_t), sizeof(int32_t), count,
-                                hipMemcpyDeviceToHost, c->stream));
-    FT_TRY(hipStreamSynchronize(c->stream));
-    return SPANGPU_OK;
-}
-
-// Where the kernel writes: the caller's rows, or a staging copy of them for a host caller.
-static int frame_target(TxCommon *c, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens, int16_t **k_pcm,
-                        long long *k_stride, int32_t **k_lens, int *vec)
-{
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > c->pcm_cap)
-        {
-            FT_TRY(hipStreamSynchronize(c->stream));
-            (void) hipFree(c->d_pcm);
-            c->d_pcm = NULL;
-            c->pcm_cap = 0;
-            if (hipMalloc(&c->d_pcm, need*c->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            c->pcm_cap = need;
-        }
-        *k_pcm = c->d_pcm;
-        *k_stride = (long long) c->pcm_cap;
-        *k_lens = c->d_lens;
-    }
-    else
-    {
-        *k_pcm = pcm;
-        *k_stride = stride;
-        *k_lens = lens;
-    }
-    *vec = ((*k_stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(*k_pcm) & 15) == 0)  ?  1  :  0;
-    return SPANGPU_OK;
-}
-
-static int frame_back(TxCommon *c, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens)
-{
-    if (mem_kind != SPANGPU_MEM_HOST)
-        return SPANGPU_OK;
-    FT_TRY(hipMemcpy2DAsync(pcm, (size_t) stride*sizeof(int16_t), c->d_pcm, c->pcm_cap*sizeof(int16_t),
-                            (size_t) samples*sizeof(int16_t), c->n_ch, hipMemcpyDeviceToHost, c->stream));
-    if (lens)
-        FT_TRY(hipMemcpyAsync(lens, c->d_lens, (size_t) c->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FT_TRY(hipStreamSynchronize(c->stream));
-    return SPANGPU_OK;
-}
-
-static int tx_args_ok(const void *t, int mem_kind, const int16_t *pcm, long long stride, int samples)
-{
-    if (t == NULL  ||  pcm == NULL  ||  samples < 0  ||  samples > kMaxSamples  ||  stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    return SPANGPU_OK;
-}
-
-static int device_ok(int device)
-{
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    FT_TRY(hipSetDevice(device));
-    return SPANGPU_OK;
+    int rc;
+    if ((rc = core_create(c, device, n_channels, words)) != SPANGPU_OK  ||  (rc = quarter_sine_upload(quarter)) != SPANGPU_OK)
+        return rc;
+    return stage_lens(c, pcm);
 }
 
 static int framing_ok(int data_bits, int parity, int stop_bits)
@@ -298,11 +127,11 @@ void spangpu_fsktx_destroy(spangpu_fsktx_t *t)
 {
     if (t == NULL)
         return;
-    common_destroy(&t->c);
+    core_destroy(&t->c);
+    stage_free(&t->pcm);
+    bitput_free(&t->put);
+    (void) hipFree(t->quarter);
     (void) hipFree(t->queue);
-    (void) hipFree(t->d_bits);
-    (void) hipFree(t->d_blens);
-    (void) hipFree(t->d_acc);
     free(t->h_row);
     free(t->frame_par);
     free(t);
@@ -323,7 +152,7 @@ int spangpu_fsktx_create(spangpu_fsktx_t **out, int device, int n_channels, cons
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
     t->source = (bit_source == SPANGPU_FSKTX_LFSR)  ?  FTX_SRC_LFSR  :  FTX_SRC_QUEUE;
-    if ((rc = common_create(&t->c, device, n_channels, kFskTxWords)) != SPANGPU_OK)
+    if ((rc = sender_create(&t->c, &t->pcm, &t->quarter, device, n_channels, kFskTxWords)) != SPANGPU_OK)
     {
         spangpu_fsktx_destroy(t);
         return rc;
@@ -356,7 +185,7 @@ int spangpu_fsktx_create(spangpu_fsktx_t **out, int device, int n_channels, cons
     int32_t one[kFskTxWords];
     memset(one, 0, sizeof(one));
     fsk_restart_words(one, spec);
-    if ((rc = common_fill(&t->c, one)) != SPANGPU_OK)
+    if ((rc = core_fill(&t->c, one)) != SPANGPU_OK)
     {
         spangpu_fsktx_destroy(t);
         return rc;
@@ -382,98 +211,64 @@ int spangpu_fsktx_set_stream(spangpu_fsktx_t *t, void *stream)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    return common_set_stream(&t->c, stream);
+    return core_set_stream(&t->c, stream);
 }
 
 int spangpu_fsktx_sync(spangpu_fsktx_t *t)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    return common_sync(&t->c);
+    return core_sync(&t->c);
 }
 
 int spangpu_fsktx_get_state(spangpu_fsktx_t *t, int channel, int32_t *words)
 {
-    if (t == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= t->c.n_ch)
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return rw_words(&t->c, channel, 0, kFskTxWords, words, false);
+    return core_rw_words(&t->c, channel, 0, kFskTxWords, words, false);
 }
 
 // fsk_tx_power(), fsk.c:201-204
 int spangpu_fsktx_power(spangpu_fsktx_t *t, int channel, float power_dbm0)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->c.n_ch)
+    if (t == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int32_t w = scaling_dbm0(power_dbm0);
-    return rw_words(&t->c, channel, FT_SCALING, 1, &w, true);
+    return core_rw_words(&t->c, channel, FT_SCALING, 1, &w, true);
 }
 
 int spangpu_fsktx_restart(spangpu_fsktx_t *t, int channel, const spangpu_fsk_spec_t *spec)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->c.n_ch  ||  !spec_ok(spec))
+    if (t == NULL  ||  !channel_ok(&t->c, channel)  ||  !spec_ok(spec))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int32_t w[FT_SHUTDOWN + 1];
     fsk_restart_words(w, spec);
-    return rw_words(&t->c, channel, 0, FT_SHUTDOWN + 1, w, true);
+    return core_rw_words(&t->c, channel, 0, FT_SHUTDOWN + 1, w, true);
 }
 
 int spangpu_fsktx_end_of_data(spangpu_fsktx_t *t, int channel, int on)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->c.n_ch  ||  t->source != FTX_SRC_QUEUE)
+    if (t == NULL  ||  !channel_ok(&t->c, channel)  ||  t->source != FTX_SRC_QUEUE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
     int32_t w = on  ?  1  :  0;
-    return rw_words(&t->c, channel, FT_EOD, 1, &w, true);
+    return core_rw_words(&t->c, channel, FT_EOD, 1, &w, true);
 }
 
 int spangpu_fsktx_queued(spangpu_fsktx_t *t, int channel)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->c.n_ch  ||  t->source != FTX_SRC_QUEUE)
+    if (t == NULL  ||  !channel_ok(&t->c, channel)  ||  t->source != FTX_SRC_QUEUE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
     int32_t w = 0;
-    const int rc = rw_words(&t->c, channel, FT_QCOUNT, 1, &w, false);
+    const int rc = core_rw_words(&t->c, channel, FT_QCOUNT, 1, &w, false);
     return (rc != SPANGPU_OK)  ?  rc  :  w;
 }
 
 int spangpu_fsktx_put_bits(spangpu_fsktx_t *t, int first, int n, const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted)
 {
-    if (t == NULL  ||  t->source != FTX_SRC_QUEUE  ||  first < 0  ||  n <= 0  ||  first + n > t->c.n_ch  ||  bits == NULL
-        ||  lens == NULL  ||  stride <= 0)
+    if (t == NULL  ||  t->source != FTX_SRC_QUEUE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
-    for (int i = 0;  i < n;  i++)
-    {
-        if (lens[i] < 0  ||  (lens[i] + 7)/8 > stride)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's bits do not fit its row");
-    }
-    FT_TRY(hipSetDevice(t->c.device));
-    const size_t bytes = (size_t) n*stride;
-    if (bytes > t->bits_cap  ||  n > t->put_cap)
-    {
-        FT_TRY(hipStreamSynchronize(t->c.stream));
-        (void) hipFree(t->d_bits);
-        (void) hipFree(t->d_blens);
-        (void) hipFree(t->d_acc);
-        t->d_bits = NULL;
-        t->d_blens = NULL;
-        t->d_acc = NULL;
-        t->bits_cap = 0;
-        t->put_cap = 0;
-        const size_t want = (bytes > t->bits_cap)  ?  bytes  :  t->bits_cap;
-        if (hipMalloc(&t->d_bits, want) != hipSuccess  ||  hipMalloc(&t->d_blens, (size_t) t->c.n_ch*sizeof(int32_t)) != hipSuccess
-            ||  hipMalloc(&t->d_acc, (size_t) t->c.n_ch*sizeof(int32_t)) != hipSuccess)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "bit staging");
-        t->bits_cap = want;
-        t->put_cap = t->c.n_ch;
-    }
-    FT_TRY(hipMemcpyAsync(t->d_bits, bits, bytes, hipMemcpyHostToDevice, t->c.stream));
-    FT_TRY(hipMemcpyAsync(t->d_blens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, t->c.stream));
-    hipLaunchKernelGGL(fsktx_put_kernel, dim3((n + 63)/64), dim3(64), 0, t->c.stream, t->c.st, t->queue, t->c.n_ch, t->qring, t->qcap,
-                       first, first + n, t->d_bits, stride, t->d_blens, t->d_acc);
-    FT_TRY(hipGetLastError());
-    if (accepted)
-        FT_TRY(hipMemcpyAsync(accepted, t->d_acc, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, t->c.stream));
-    // the caller's arrays are pageable: they must not change under the copies
-    FT_TRY(hipStreamSynchronize(t->c.stream));
-    return SPANGPU_OK;
+    return bitring_put(&t->c, &t->put, t->c.st + (size_t) FT_QRD*t->c.n_ch, t->c.st + (size_t) FT_QCOUNT*t->c.n_ch, t->queue, t->qring,
+                       t->qcap, first, n, bits, stride, lens, accepted);
 }
 
 int spangpu_fsktx_set_framing(spangpu_fsktx_t *t, int channel, int data_bits, int parity, int stop_bits)
@@ -503,10 +298,10 @@ int spangpu_fsktx_put_bytes(spangpu_fsktx_t *t, int first, int n, const uint8_t 
         most = (lens[i] > most)  ?  lens[i]  :  most;
     }
     // how much room each ring has: whole characters only
-    FT_TRY(hipSetDevice(t->c.device));
-    FT_TRY(hipMemcpyAsync(t->h_row, t->c.st + (size_t) FT_QCOUNT*t->c.n_ch + first, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost,
+    SPG_TRY(hipSetDevice(t->c.device));
+    SPG_TRY(hipMemcpyAsync(t->h_row, t->c.st + (size_t) FT_QCOUNT*t->c.n_ch + first, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost,
                           t->c.stream));
-    FT_TRY(hipStreamSynchronize(t->c.stream));
+    SPG_TRY(hipStreamSynchronize(t->c.stream));
     const int row = (presend_bits + most*12 + 7)/8 + 1;
     uint8_t *packed = (uint8_t *) calloc((size_t) n, (size_t) row);
     int32_t *blens = (int32_t *) malloc((size_t) n*sizeof(int32_t));
@@ -554,17 +349,18 @@ int spangpu_fsktx_tx(spangpu_fsktx_t *t, int mem_kind, int16_t *pcm, long long s
         return rc;
     if (samples == 0)
     {
+        // (an empty call zeroes a host caller's lens; the tone sender leaves them)
         if (lens  &&  mem_kind == SPANGPU_MEM_HOST)
             memset(lens, 0, (size_t) t->c.n_ch*sizeof(int32_t));
         return SPANGPU_OK;
     }
-    FT_TRY(hipSetDevice(t->c.device));
+    SPG_TRY(hipSetDevice(t->c.device));
     FskTxLaunch L;
     memset(&L, 0, sizeof(L));
-    if ((rc = frame_target(&t->c, mem_kind, pcm, stride, samples, lens, &L.pcm, &L.stride, &L.lens, &L.vec)) != SPANGPU_OK)
+    if ((rc = stage_out_target(&t->c, &t->pcm, mem_kind, pcm, stride, samples, lens, &L.pcm, &L.stride, &L.lens, &L.vec)) != SPANGPU_OK)
         return rc;
     L.st = t->c.st;
-    L.quarter = t->c.quarter;
+    L.quarter = t->quarter;
     L.queue = t->queue;
     L.n_ch = t->c.n_ch;
     L.samples = samples;
@@ -573,18 +369,18 @@ int spangpu_fsktx_tx(spangpu_fsktx_t *t, int mem_kind, int16_t *pcm, long long s
     // 16 channels per wave, four waves per workgroup, as the other sender banks (txgen_api.hip)
     hipLaunchKernelGGL(fsktx_bank_kernel, dim3((t->c.n_ch + kFtxCpw*kFtxWaves - 1)/(kFtxCpw*kFtxWaves)), dim3(64*kFtxWaves), 0,
                        t->c.stream, L);
-    FT_TRY(hipGetLastError());
-    return frame_back(&t->c, mem_kind, pcm, stride, samples, lens);
+    SPG_TRY(hipGetLastError());
+    return stage_out_back(&t->c, &t->pcm, mem_kind, pcm, stride, samples, lens);
 }
 
 int spangpu_fsktx_events(spangpu_fsktx_t *t, const int32_t **channels)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    FT_TRY(hipSetDevice(t->c.device));
-    FT_TRY(hipMemcpyAsync(t->h_row, t->c.st + (size_t) FT_EVENT*t->c.n_ch, (size_t) t->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost,
+    SPG_TRY(hipSetDevice(t->c.device));
+    SPG_TRY(hipMemcpyAsync(t->h_row, t->c.st + (size_t) FT_EVENT*t->c.n_ch, (size_t) t->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost,
                           t->c.stream));
-    FT_TRY(hipStreamSynchronize(t->c.stream));
+    SPG_TRY(hipStreamSynchronize(t->c.stream));
     int count = 0;
     for (int c = 0;  c < t->c.n_ch;  c++)
     {
@@ -602,7 +398,9 @@ void spangpu_mcttx_destroy(spangpu_mcttx_t *t)
 {
     if (t == NULL)
         return;
-    common_destroy(&t->c);
+    core_destroy(&t->c);
+    stage_free(&t->pcm);
+    (void) hipFree(t->quarter);
     free(t);
 }
 
@@ -680,7 +478,8 @@ int spangpu_mcttx_create(spangpu_mcttx_t **out, int device, int tone_type, int n
     t->tone_type = tone_type;
     t->proto = P;
     memcpy(t->init, init, sizeof(init));
-    if ((rc = common_create(&t->c, device, n_channels, kMctTxWords)) != SPANGPU_OK  ||  (rc = common_fill(&t->c, init)) != SPANGPU_OK)
+    if ((rc = sender_create(&t->c, &t->pcm, &t->quarter, device, n_channels, kMctTxWords)) != SPANGPU_OK
+        ||  (rc = core_fill(&t->c, init)) != SPANGPU_OK)
     {
         spangpu_mcttx_destroy(t);
         return rc;
@@ -696,28 +495,28 @@ int spangpu_mcttx_set_stream(spangpu_mcttx_t *t, void *stream)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    return common_set_stream(&t->c, stream);
+    return core_set_stream(&t->c, stream);
 }
 
 int spangpu_mcttx_sync(spangpu_mcttx_t *t)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    return common_sync(&t->c);
+    return core_sync(&t->c);
 }
 
 int spangpu_mcttx_get_state(spangpu_mcttx_t *t, int channel, int32_t *words)
 {
-    if (t == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= t->c.n_ch)
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return rw_words(&t->c, channel, 0, kMctTxWords, words, false);
+    return core_rw_words(&t->c, channel, 0, kMctTxWords, words, false);
 }
 
 int spangpu_mcttx_restart(spangpu_mcttx_t *t, int channel)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->c.n_ch)
+    if (t == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return rw_words(&t->c, channel, 0, kMctTxWords, t->init, true);
+    return core_rw_words(&t->c, channel, 0, kMctTxWords, t->init, true);
 }
 
 int spangpu_mcttx_tx(spangpu_mcttx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens)
@@ -727,22 +526,23 @@ int spangpu_mcttx_tx(spangpu_mcttx_t *t, int mem_kind, int16_t *pcm, long long s
         return rc;
     if (samples == 0)
     {
+        // (an empty call zeroes a host caller's lens; the tone sender leaves them)
         if (lens  &&  mem_kind == SPANGPU_MEM_HOST)
             memset(lens, 0, (size_t) t->c.n_ch*sizeof(int32_t));
         return SPANGPU_OK;
     }
-    FT_TRY(hipSetDevice(t->c.device));
+    SPG_TRY(hipSetDevice(t->c.device));
     MctTxLaunch L = t->proto;
-    if ((rc = frame_target(&t->c, mem_kind, pcm, stride, samples, lens, &L.pcm, &L.stride, &L.lens, &L.vec)) != SPANGPU_OK)
+    if ((rc = stage_out_target(&t->c, &t->pcm, mem_kind, pcm, stride, samples, lens, &L.pcm, &L.stride, &L.lens, &L.vec)) != SPANGPU_OK)
         return rc;
     L.st = t->c.st;
-    L.quarter = t->c.quarter;
+    L.quarter = t->quarter;
     L.n_ch = t->c.n_ch;
     L.samples = samples;
     hipLaunchKernelGGL(mcttx_bank_kernel, dim3((t->c.n_ch + kFtxCpw*kFtxWaves - 1)/(kFtxCpw*kFtxWaves)), dim3(64*kFtxWaves), 0,
                        t->c.stream, L);
-    FT_TRY(hipGetLastError());
-    return frame_back(&t->c, mem_kind, pcm, stride, samples, lens);
+    SPG_TRY(hipGetLastError());
+    return stage_out_back(&t->c, &t->pcm, mem_kind, pcm, stride, samples, lens);
 }
 
 // ---- host helpers: async_tx framing and the bit clock, no device needed ---------------------------------------------------

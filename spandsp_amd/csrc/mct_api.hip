@@ -10,40 +10,20 @@
 
 #include "../../include/spangpu.h"
 #include "mct_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
-
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define MCT_TRY(expr)                                                                       \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
 
 struct spangpu_mct_s
 {
     const int32_t *next_lens;   // per-channel lengths of the call being prepared (device), or NULL
     int32_t *d_lens;            // [n_ch], device
     int32_t *h_lens;            // [n_ch], pinned
-    int device;
-    int n_ch;
+    BankCore c;
+    PcmStage pcm;
     int tone_type;              // after modem_connect_tones_rx_init()'s folding of the ANS variants
     int latch;
-    int words;
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;
     int16_t *quarter;
-    int16_t *d_pcm;
-    size_t pcm_cap;
     int32_t *events;
     int32_t *ev_count;
     int ev_cap;
@@ -89,9 +69,9 @@ static void launch(const spangpu_mct_s *m, const MctLaunch &L)
     const bool fsk = (TYPE == MCT_FAX_PREAMBLE  ||  TYPE == MCT_FAX_CED_OR_PREAMBLE);
     const size_t lds = fsk  ?  (size_t) (4*kMctV21Span*64)*sizeof(int32_t)  :  0;
     if (TYPE == MCT_FAX_CED_OR_PREAMBLE  &&  spangpu_fsk_waves_choice() != 1)
-        hipLaunchKernelGGL(mct_ced_pair_kernel, dim3((m->n_ch + 63)/64), dim3(128), lds + 3*64*sizeof(int32_t), m->stream, L);
+        hipLaunchKernelGGL(mct_ced_pair_kernel, dim3((m->c.n_ch + 63)/64), dim3(128), lds + 3*64*sizeof(int32_t), m->c.stream, L);
     else
-        hipLaunchKernelGGL(mct_bank_kernel<TYPE>, dim3((m->n_ch + 63)/64), dim3(64), lds, m->stream, L);
+        hipLaunchKernelGGL(mct_bank_kernel<TYPE>, dim3((m->c.n_ch + 63)/64), dim3(64), lds, m->c.stream, L);
 }
 
 extern "C" {
@@ -107,47 +87,29 @@ int spangpu_mct_create(spangpu_mct_t **out, int device, int tone_type, int n_cha
         type = MCT_ANS;
     if (type < MCT_FAX_CNG  ||  type > MCT_CALLING_TONE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "not a modem connect tone type");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    MCT_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_mct_s *m = (spangpu_mct_s *) calloc(1, sizeof(*m));
     if (m == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    m->device = device;
-    m->n_ch = n_channels;
     m->tone_type = type;
     m->latch = use_callback  ?  0  :  1;
     const bool fsk = (type == MCT_FAX_PREAMBLE  ||  type == MCT_FAX_CED_OR_PREAMBLE);
-    m->words = kMctWords + (fsk  ?  (kFskScalars + 4*kMctV21Span)  :  0);
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess)
-    {
-        free(m);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
-    }
-    m->own_stream = true;
-    const size_t words = (size_t) m->words*n_channels;
-    if (hipMalloc(&m->st, words*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&m->quarter, 257*sizeof(int16_t)) != hipSuccess
-        ||  hipMalloc(&m->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
-        ||  (m->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL)
+    const int words = kMctWords + (fsk  ?  (kFskScalars + 4*kMctV21Span)  :  0);
+    if ((rc = core_create(&m->c, device, n_channels, words)) != SPANGPU_OK  ||  (rc = quarter_sine_upload(&m->quarter)) != SPANGPU_OK)
     {
         spangpu_mct_destroy(m);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the connect tone bank failed");
+        return rc;
     }
-    int16_t quarter[257];
-    for (int i = 0;  i <= 256;  i++)
-        quarter[i] = (int16_t) lrint(32767.0*sin(i*3.14159265358979323846/512.0));
-    int32_t *one = (int32_t *) calloc(m->words, sizeof(int32_t));
-    int32_t *host = (int32_t *) calloc(words, sizeof(int32_t));
-    if (one == NULL  ||  host == NULL)
+    int32_t *one = (int32_t *) calloc(words, sizeof(int32_t));
+    if (hipMalloc(&m->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
+        ||  (m->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL
+        ||  one == NULL)
     {
         free(one);
-        free(host);
         spangpu_mct_destroy(m);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the connect tone bank failed");
     }
     one[MC_TONE_TYPE] = type;
     if (fsk)
@@ -165,20 +127,13 @@ int spangpu_mct_create(spangpu_mct_t **out, int device, int tone_type, int n_cha
         w[FS_SHIFT] = 5;
         w[FS_FRAME_POS] = -2;
     }
-    for (int k = 0;  k < kMctWords + (fsk  ?  kFskScalars  :  0);  k++)
-    {
-        for (int c = 0;  c < n_channels;  c++)
-            host[(size_t) k*n_channels + c] = one[k];
-    }
-    hipError_t e = hipMemcpy(m->st, host, words*sizeof(int32_t), hipMemcpyHostToDevice);
+    // (the preamble hunter's correlation window stays zero)
+    rc = core_fill(&m->c, one, kMctWords + (fsk  ?  kFskScalars  :  0));
     free(one);
-    free(host);
-    if (e == hipSuccess)
-        e = hipMemcpy(m->quarter, quarter, sizeof(quarter), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
+    if (rc != SPANGPU_OK)
     {
         spangpu_mct_destroy(m);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+        return rc;
     }
     *out = m;
     return SPANGPU_OK;
@@ -188,108 +143,59 @@ void spangpu_mct_destroy(spangpu_mct_t *m)
 {
     if (m == NULL)
         return;
-    (void) hipSetDevice(m->device);
-    if (m->stream)
-        (void) hipStreamSynchronize(m->stream);
-    (void) hipFree(m->st);
+    core_destroy(&m->c);
+    stage_free(&m->pcm);
     (void) hipFree(m->quarter);
-    (void) hipFree(m->d_pcm);
     (void) hipFree(m->d_lens);
     if (m->h_lens) (void) hipHostFree(m->h_lens);
     (void) hipFree(m->events);
     (void) hipFree(m->ev_count);
     free(m->h_events);
     free(m->h_count);
-    if (m->own_stream  &&  m->stream)
-        (void) hipStreamDestroy(m->stream);
     free(m);
 }
 
-int spangpu_mct_channels(const spangpu_mct_t *m) { return m  ?  m->n_ch  :  SPANGPU_ERR_BAD_ARG; }
-int spangpu_mct_state_words(const spangpu_mct_t *m) { return m  ?  m->words  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_mct_channels(const spangpu_mct_t *m) { return m  ?  m->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_mct_state_words(const spangpu_mct_t *m) { return m  ?  m->c.words  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_mct_set_stream(spangpu_mct_t *m, void *stream)
 {
     if (m == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    MCT_TRY(hipSetDevice(m->device));
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    if (m->own_stream)
-        (void) hipStreamDestroy(m->stream);
-    m->stream = (hipStream_t) stream;
-    m->own_stream = false;
-    return SPANGPU_OK;
+    return core_set_stream(&m->c, stream);
 }
 
 int spangpu_mct_sync(spangpu_mct_t *m)
 {
     if (m == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    MCT_TRY(hipSetDevice(m->device));
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    return SPANGPU_OK;
+    return core_sync(&m->c);
 }
 
 int spangpu_mct_rx(spangpu_mct_t *m, const int16_t *amp, int mem_kind, int samples, long long stride)
 {
-    if (m == NULL  ||  amp == NULL  ||  samples <= 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    if (stride <= 0)
-        stride = samples;
-    if (stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < samples");
-    MCT_TRY(hipSetDevice(m->device));
+    int rc = rx_args_ok(m, mem_kind, amp, samples, &stride);
+    if (rc != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipSetDevice(m->c.device));
     // a tone needs >= 415 ms to be declared and can only be withdrawn once declared: two reports per ~3300
     // samples at the very most; the preamble hunter needs 40 bits (1067 samples) per declaration
-    const int cap = 8 + samples/256;
-    if (cap > m->ev_cap)
-    {
-        MCT_TRY(hipStreamSynchronize(m->stream));
-        (void) hipFree(m->events);
-        m->events = NULL;
-        m->ev_cap = 0;
-        if (hipMalloc(&m->events, (size_t) m->n_ch*cap*2*sizeof(int32_t)) != hipSuccess)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "event buffer");
-        m->ev_cap = cap;
-    }
+    if ((rc = grow(&m->events, &m->ev_cap, 8 + samples/256, (size_t) m->c.n_ch*2, m->c.stream)) != SPANGPU_OK)
+        return rc;
     MctLaunch L;
     memset(&L, 0, sizeof(L));
-    L.st = m->st;
+    L.st = m->c.st;
     L.quarter = m->quarter;
     L.events = m->events;
     L.ev_count = m->ev_count;
-    L.n_ch = m->n_ch;
+    L.n_ch = m->c.n_ch;
     L.samples = samples;
     L.lens = m->next_lens;
     L.ev_cap = m->ev_cap;
     L.latch = m->latch;
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > m->pcm_cap)
-        {
-            MCT_TRY(hipStreamSynchronize(m->stream));
-            (void) hipFree(m->d_pcm);
-            m->d_pcm = NULL;
-            m->pcm_cap = 0;
-            if (hipMalloc(&m->d_pcm, need*m->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            m->pcm_cap = need;
-        }
-        MCT_TRY(hipMemcpy2DAsync(m->d_pcm, m->pcm_cap*sizeof(int16_t), amp, (size_t) stride*sizeof(int16_t),
-                                 (size_t) samples*sizeof(int16_t), m->n_ch, hipMemcpyHostToDevice, m->stream));
-        MCT_TRY(hipStreamSynchronize(m->stream));       // the caller's buffer is only borrowed for the call
-        L.pcm = m->d_pcm;
-        L.stride = (long long) m->pcm_cap;
-    }
-    else
-    {
-        L.pcm = amp;
-        L.stride = stride;
-    }
-    L.vec = ((L.stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(L.pcm) & 15) == 0)  ?  1  :  0;
+    // the caller's buffer is only borrowed for the call: the copy in is waited for
+    if ((rc = stage_in(&m->c, &m->pcm, mem_kind, amp, stride, samples, true, &L.pcm, &L.stride, &L.vec)) != SPANGPU_OK)
+        return rc;
     switch (m->tone_type)
     {
     case MCT_FAX_CNG:               launch<MCT_FAX_CNG>(m, L); break;
@@ -299,7 +205,7 @@ int spangpu_mct_rx(spangpu_mct_t *m, const int16_t *amp, int mem_kind, int sampl
     case MCT_BELL_ANS:              launch<MCT_BELL_ANS>(m, L); break;
     default:                        launch<MCT_CALLING_TONE>(m, L); break;
     }
-    MCT_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     m->last_cap = m->ev_cap;
     return SPANGPU_OK;
 }
@@ -312,7 +218,7 @@ int spangpu_mct_rx_var(spangpu_mct_t *m, const int16_t *amp, int mem_kind, const
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int longest = 0;
     bool all = true;
-    for (int c = 0;  c < m->n_ch;  c++)
+    for (int c = 0;  c < m->c.n_ch;  c++)
     {
         if (lens[c] < 0  ||  lens[c] > max_samples)
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
@@ -321,21 +227,21 @@ int spangpu_mct_rx_var(spangpu_mct_t *m, const int16_t *amp, int mem_kind, const
     }
     if (longest == 0)
         return SPANGPU_OK;
-    for (int c = 0;  c < m->n_ch;  c++)
+    for (int c = 0;  c < m->c.n_ch;  c++)
         all &= (lens[c] == longest);
     if (stride <= 0)
         stride = max_samples;
     if (all)
         return spangpu_mct_rx(m, amp, mem_kind, longest, stride);
-    MCT_TRY(hipSetDevice(m->device));
+    SPG_TRY(hipSetDevice(m->c.device));
     if (m->d_lens == NULL)
     {
-        MCT_TRY(hipMalloc(&m->d_lens, (size_t) m->n_ch*sizeof(int32_t)));
-        MCT_TRY(hipHostMalloc(&m->h_lens, (size_t) m->n_ch*sizeof(int32_t)));
+        SPG_TRY(hipMalloc(&m->d_lens, (size_t) m->c.n_ch*sizeof(int32_t)));
+        SPG_TRY(hipHostMalloc(&m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t)));
     }
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    memcpy(m->h_lens, lens, (size_t) m->n_ch*sizeof(int32_t));
-    MCT_TRY(hipMemcpyAsync(m->d_lens, m->h_lens, (size_t) m->n_ch*sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
+    memcpy(m->h_lens, lens, (size_t) m->c.n_ch*sizeof(int32_t));
+    SPG_TRY(hipMemcpyAsync(m->d_lens, m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, m->c.stream));
     m->next_lens = m->d_lens;
     const int rc = spangpu_mct_rx(m, amp, mem_kind, longest, stride);
     m->next_lens = NULL;
@@ -348,8 +254,8 @@ int spangpu_mct_events(spangpu_mct_t *m, const int32_t **events, const int32_t *
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_mct_rx() yet");
-    MCT_TRY(hipSetDevice(m->device));
-    const size_t bytes = (size_t) m->n_ch*m->last_cap*2*sizeof(int32_t);
+    SPG_TRY(hipSetDevice(m->c.device));
+    const size_t bytes = (size_t) m->c.n_ch*m->last_cap*2*sizeof(int32_t);
     if (bytes > m->h_events_cap)
     {
         free(m->h_events);
@@ -358,10 +264,10 @@ int spangpu_mct_events(spangpu_mct_t *m, const int32_t **events, const int32_t *
             return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host event buffer");
         m->h_events_cap = bytes;
     }
-    MCT_TRY(hipMemcpyAsync(m->h_events, m->events, bytes, hipMemcpyDeviceToHost, m->stream));
-    MCT_TRY(hipMemcpyAsync(m->h_count, m->ev_count, (size_t) m->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    for (int c = 0;  c < m->n_ch;  c++)
+    SPG_TRY(hipMemcpyAsync(m->h_events, m->events, bytes, hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipMemcpyAsync(m->h_count, m->ev_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
+    for (int c = 0;  c < m->c.n_ch;  c++)
     {
         int32_t *e = m->h_events + (size_t) c*m->last_cap*2;
         const int cnt = (m->h_count[c] < m->last_cap)  ?  m->h_count[c]  :  m->last_cap;
@@ -375,41 +281,32 @@ int spangpu_mct_events(spangpu_mct_t *m, const int32_t **events, const int32_t *
 
 int spangpu_mct_get(spangpu_mct_t *m, int channel)
 {
-    if (m == NULL  ||  channel < 0  ||  channel >= m->n_ch)
+    if (m == NULL  ||  !channel_ok(&m->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     // modem_connect_tones_rx_get(), modem_connect_tones.c:793-797: read and clear the latch
-    MCT_TRY(hipSetDevice(m->device));
+    SPG_TRY(hipSetDevice(m->c.device));
     int32_t hit = 0;
     const int32_t zero = 0;
-    int32_t *at = m->st + (size_t) MC_HIT*m->n_ch + channel;
-    MCT_TRY(hipMemcpyAsync(&hit, at, sizeof(hit), hipMemcpyDeviceToHost, m->stream));
-    MCT_TRY(hipMemcpyAsync(at, &zero, sizeof(zero), hipMemcpyHostToDevice, m->stream));
-    MCT_TRY(hipStreamSynchronize(m->stream));
+    int32_t *at = m->c.st + (size_t) MC_HIT*m->c.n_ch + channel;
+    SPG_TRY(hipMemcpyAsync(&hit, at, sizeof(hit), hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipMemcpyAsync(at, &zero, sizeof(zero), hipMemcpyHostToDevice, m->c.stream));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
     return hit;
 }
 
 int spangpu_mct_get_state(spangpu_mct_t *m, int channel, int32_t *words)
 {
-    if (m == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= m->n_ch)
+    if (m == NULL  ||  words == NULL  ||  !channel_ok(&m->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    MCT_TRY(hipSetDevice(m->device));
-    MCT_TRY(hipMemcpy2DAsync(words, sizeof(int32_t), m->st + channel, (size_t) m->n_ch*sizeof(int32_t), sizeof(int32_t), m->words,
-                             hipMemcpyDeviceToHost, m->stream));
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    return SPANGPU_OK;
+    return core_rw_words(&m->c, channel, 0, m->c.words, words, false);
 }
 
 // The reverse of spangpu_mct_get_state(): a channel's words as a caller holds them.
 int spangpu_mct_set_state(spangpu_mct_t *m, int channel, const int32_t *words)
 {
-    if (m == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= m->n_ch)
+    if (m == NULL  ||  words == NULL  ||  !channel_ok(&m->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    MCT_TRY(hipSetDevice(m->device));
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    MCT_TRY(hipMemcpy2DAsync(m->st + channel, (size_t) m->n_ch*sizeof(int32_t), words, sizeof(int32_t), sizeof(int32_t), m->words,
-                             hipMemcpyHostToDevice, m->stream));
-    MCT_TRY(hipStreamSynchronize(m->stream));
-    return SPANGPU_OK;
+    return core_rw_words(&m->c, channel, 0, m->c.words, const_cast<int32_t *>(words), true);
 }
 
 }   // extern "C"

@@ -12,48 +12,25 @@
 #include "../../include/spangpu.h"
 #include "modem_tables.h"
 #include "modemtx_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define VT_TRY(expr)                                                                        \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
-
 struct spangpu_modemtx_s
 {
-    int device;
+    BankCore c;             // st[kV29TxWords][n_ch]
+    PcmStage pcm;           // d_lens: only once a host caller of a queue-sourced bank asks for lengths
     int kind;               // kTxV29, kTxV27ter or kTxV17
     float *constel;         // V.17: the constellations of every rate + the ABCD training points
-    int n_ch;
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;
     float *sine;
     float *shaper;
-    int16_t *d_pcm;
-    size_t pcm_cap;
     int source;             // kTxSrcLfsr or kTxSrcQueue
     int qcap;               // bits a channel's ring takes
     int qring;              // ring size in bits: qcap rounded up to whole words
     uint32_t *queue;
     int32_t *qst;           // [kVqWords][n_ch]
-    int32_t *d_lens;        // [n_ch]: the returned lengths of a host caller
     int32_t *h_row;         // [5][n_ch] host scratch: the events as channels [2n], kinds [2n], and the flags read back [n]
-    uint8_t *d_bits;        // staging of spangpu_modemtx_put_bits()
-    int32_t *d_blens;
-    int32_t *d_acc;
-    size_t bits_cap;
+    BitPut put;             // staging of spangpu_modemtx_put_bits()
 };
 
 static void put_f(int32_t *w, int idx, float v)
@@ -168,43 +145,15 @@ static int restart_words(int32_t *w, int kind, int bit_rate, int tep, int short_
     return 0;
 }
 
-static int rw_words(spangpu_modemtx_s *t, int ch, int32_t *w, bool write)
-{
-    VT_TRY(hipSetDevice(t->device));
-    if (write)
-        VT_TRY(hipMemcpy2DAsync(t->st + ch, (size_t) t->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), kV29TxWords,
-                                hipMemcpyHostToDevice, t->stream));
-    else
-        VT_TRY(hipMemcpy2DAsync(w, sizeof(int32_t), t->st + ch, (size_t) t->n_ch*sizeof(int32_t), sizeof(int32_t), kV29TxWords,
-                                hipMemcpyDeviceToHost, t->stream));
-    VT_TRY(hipStreamSynchronize(t->stream));
-    return SPANGPU_OK;
-}
-
-// words [first, first + count) of one channel's ring bookkeeping
-static int rw_qwords(spangpu_modemtx_s *t, int ch, int first, int count, int32_t *w, bool write)
-{
-    VT_TRY(hipSetDevice(t->device));
-    int32_t *at = t->qst + (size_t) first*t->n_ch + ch;
-    if (write)
-        VT_TRY(hipMemcpy2DAsync(at, (size_t) t->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), count,
-                                hipMemcpyHostToDevice, t->stream));
-    else
-        VT_TRY(hipMemcpy2DAsync(w, sizeof(int32_t), at, (size_t) t->n_ch*sizeof(int32_t), sizeof(int32_t), count,
-                                hipMemcpyDeviceToHost, t->stream));
-    VT_TRY(hipStreamSynchronize(t->stream));
-    return SPANGPU_OK;
-}
-
 template <int SRC>
 static void launch_bank(spangpu_modemtx_s *t, const V29TxLaunch &L)
 {
     if (t->kind == kTxV29)
-        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV29, SRC>), dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV29, SRC>), dim3((t->c.n_ch + 63)/64), dim3(64), 0, t->c.stream, L);
     else if (t->kind == kTxV17)
-        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV17, SRC>), dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV17, SRC>), dim3((t->c.n_ch + 63)/64), dim3(64), 0, t->c.stream, L);
     else
-        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV27ter, SRC>), dim3((t->n_ch + 63)/64), dim3(64), 0, t->stream, L);
+        hipLaunchKernelGGL((modemtx_bank_kernel<kTxV27ter, SRC>), dim3((t->c.n_ch + 63)/64), dim3(64), 0, t->c.stream, L);
 }
 
 extern "C" {
@@ -228,28 +177,20 @@ int spangpu_modemtx_create_ex(spangpu_modemtx_t **out, int device, int modem, in
     if (restart_words(probe, kind, bit_rate, tep) != 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bit rate not valid for this modem (V.29: 9600/7200/4800, V.27ter: 4800/2400, V.17: 14400/12000/9600/7200/4800)");
     *out = NULL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    VT_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_modemtx_s *t = (spangpu_modemtx_s *) calloc(1, sizeof(*t));
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    t->device = device;
     t->kind = kind;
-    t->n_ch = n_channels;
     t->source = (bit_source == SPANGPU_MODEMTX_LFSR)  ?  kTxSrcLfsr  :  kTxSrcQueue;
-    if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess)
+    if ((rc = core_create(&t->c, device, n_channels, kV29TxWords)) != SPANGPU_OK)
     {
-        free(t);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
+        spangpu_modemtx_destroy(t);
+        return rc;
     }
-    t->own_stream = true;
-    const size_t words = (size_t) kV29TxWords*n_channels;
-    if (hipMalloc(&t->st, words*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&t->sine, 2048*sizeof(float)) != hipSuccess
+    if (hipMalloc(&t->sine, 2048*sizeof(float)) != hipSuccess
         ||  hipMalloc(&t->shaper, 225*sizeof(float)) != hipSuccess
         ||  hipMalloc(&t->constel, 496*sizeof(float)) != hipSuccess)
     {
@@ -265,9 +206,7 @@ int spangpu_modemtx_create_ex(spangpu_modemtx_t **out, int device, int modem, in
         t->h_row = (int32_t *) malloc((size_t) 5*n_channels*sizeof(int32_t));
         if (t->h_row == NULL
             ||  hipMalloc(&t->queue, ring_bytes) != hipSuccess  ||  hipMemset(t->queue, 0, ring_bytes) != hipSuccess
-            ||  hipMalloc(&t->qst, q_bytes) != hipSuccess  ||  hipMemset(t->qst, 0, q_bytes) != hipSuccess
-            ||  hipMalloc(&t->d_blens, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
-            ||  hipMalloc(&t->d_acc, (size_t) n_channels*sizeof(int32_t)) != hipSuccess)
+            ||  hipMalloc(&t->qst, q_bytes) != hipSuccess  ||  hipMemset(t->qst, 0, q_bytes) != hipSuccess)
         {
             spangpu_modemtx_destroy(t);
             return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the bit rings failed");
@@ -313,31 +252,32 @@ int spangpu_modemtx_create_ex(spangpu_modemtx_t **out, int device, int modem, in
     }
     power_words(one, kind, -14.0f);
     restart_words(one, kind, bit_rate, tep);
-    int32_t *host = (int32_t *) malloc(words*sizeof(int32_t));
-    if (host == NULL)
+    // every channel starts from the same words, but for the seed of its LFSR
+    int32_t *seed_row = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t));
+    if (seed_row == NULL)
     {
         spangpu_modemtx_destroy(t);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
     }
-    for (int k = 0;  k < kV29TxWords;  k++)
-    {
-        for (int c = 0;  c < n_channels;  c++)
-            host[(size_t) k*n_channels + c] = one[k];
-    }
     for (int c = 0;  c < n_channels;  c++)
-        host[(size_t) VT_PRBS*n_channels + c] = (int32_t) ((seeds  ?  seeds[c]  :  (uint32_t) (c*2654435761u + 1u)) & 0x7FFFu);
-    hipError_t e = hipMemcpy(t->st, host, words*sizeof(int32_t), hipMemcpyHostToDevice);
-    free(host);
+        seed_row[c] = (int32_t) ((seeds  ?  seeds[c]  :  (uint32_t) (c*2654435761u + 1u)) & 0x7FFFu);
+    rc = core_fill(&t->c, one);
+    hipError_t e = hipSuccess;
+    if (rc == SPANGPU_OK)
+        e = hipMemcpy(t->c.st + (size_t) VT_PRBS*n_channels, seed_row, (size_t) n_channels*sizeof(int32_t), hipMemcpyHostToDevice);
+    free(seed_row);
     if (e == hipSuccess)
         e = hipMemcpy(t->sine, sine, sizeof(sine), hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = hipMemcpy(t->shaper, shaper, sizeof(shaper), hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = hipMemcpy(t->constel, constel, sizeof(constel), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
+    if (rc == SPANGPU_OK  &&  e != hipSuccess)
+        rc = spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+    if (rc != SPANGPU_OK)
     {
         spangpu_modemtx_destroy(t);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+        return rc;
     }
     *out = t;
     return SPANGPU_OK;
@@ -347,61 +287,45 @@ void spangpu_modemtx_destroy(spangpu_modemtx_t *t)
 {
     if (t == NULL)
         return;
-    (void) hipSetDevice(t->device);
-    if (t->stream)
-        (void) hipStreamSynchronize(t->stream);
-    (void) hipFree(t->st);
+    core_destroy(&t->c);
+    stage_free(&t->pcm);
+    bitput_free(&t->put);
     (void) hipFree(t->sine);
     (void) hipFree(t->shaper);
     (void) hipFree(t->constel);
-    (void) hipFree(t->d_pcm);
     (void) hipFree(t->queue);
     (void) hipFree(t->qst);
-    (void) hipFree(t->d_lens);
-    (void) hipFree(t->d_bits);
-    (void) hipFree(t->d_blens);
-    (void) hipFree(t->d_acc);
     free(t->h_row);
-    if (t->own_stream  &&  t->stream)
-        (void) hipStreamDestroy(t->stream);
     free(t);
 }
 
-int spangpu_modemtx_channels(const spangpu_modemtx_t *t) { return t  ?  t->n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_modemtx_channels(const spangpu_modemtx_t *t) { return t  ?  t->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 int spangpu_modemtx_state_words(void) { return kV29TxWords; }
 
 int spangpu_modemtx_set_stream(spangpu_modemtx_t *t, void *stream)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    VT_TRY(hipSetDevice(t->device));
-    VT_TRY(hipStreamSynchronize(t->stream));
-    if (t->own_stream)
-        (void) hipStreamDestroy(t->stream);
-    t->stream = (hipStream_t) stream;
-    t->own_stream = false;
-    return SPANGPU_OK;
+    return core_set_stream(&t->c, stream);
 }
 
 int spangpu_modemtx_sync(spangpu_modemtx_t *t)
 {
     if (t == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    VT_TRY(hipSetDevice(t->device));
-    VT_TRY(hipStreamSynchronize(t->stream));
-    return SPANGPU_OK;
+    return core_sync(&t->c);
 }
 
 int spangpu_modemtx_power(spangpu_modemtx_t *t, int channel, float power_dbm0)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->n_ch)
+    if (t == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int32_t w[kV29TxWords];
-    int rc = rw_words(t, channel, w, false);
+    int rc = core_rw_words(&t->c, channel, 0, kV29TxWords, w, false);
     if (rc != SPANGPU_OK)
         return rc;
     power_words(w, t->kind, power_dbm0);
-    return rw_words(t, channel, w, true);
+    return core_rw_words(&t->c, channel, 0, kV29TxWords, w, true);
 }
 
 // Every channel's level and carrier frequency in one pass over the state words: a population of lines for the receiver
@@ -414,19 +338,19 @@ int spangpu_modemtx_line(spangpu_modemtx_t *t, const float *power_dbm0, const fl
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
     if (power_dbm0 == NULL  &&  carrier_hz == NULL)
         return SPANGPU_OK;
-    for (int c = 0;  carrier_hz  &&  c < t->n_ch;  c++)
+    for (int c = 0;  carrier_hz  &&  c < t->c.n_ch;  c++)
     {
         if (!(carrier_hz[c] > 0.0f  &&  carrier_hz[c] < 4000.0f))
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "carrier frequency out of range");
     }
-    VT_TRY(hipSetDevice(t->device));
-    VT_TRY(hipStreamSynchronize(t->stream));
-    const size_t n = (size_t) t->n_ch;
+    SPG_TRY(hipSetDevice(t->c.device));
+    SPG_TRY(hipStreamSynchronize(t->c.stream));
+    const size_t n = (size_t) t->c.n_ch;
     int32_t *host = (int32_t *) malloc((size_t) kV29TxWords*n*sizeof(int32_t));
     if (host == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
-    hipError_t e = hipMemcpy(host, t->st, (size_t) kV29TxWords*n*sizeof(int32_t), hipMemcpyDeviceToHost);
-    for (int c = 0;  e == hipSuccess  &&  c < t->n_ch;  c++)
+    hipError_t e = hipMemcpy(host, t->c.st, (size_t) kV29TxWords*n*sizeof(int32_t), hipMemcpyDeviceToHost);
+    for (int c = 0;  e == hipSuccess  &&  c < t->c.n_ch;  c++)
     {
         int32_t w[kV29TxWords];
         for (int k = 0;  k < kV29TxWords;  k++)
@@ -439,7 +363,7 @@ int spangpu_modemtx_line(spangpu_modemtx_t *t, const float *power_dbm0, const fl
             host[(size_t) k*n + c] = w[k];
     }
     if (e == hipSuccess)
-        e = hipMemcpy(t->st, host, (size_t) kV29TxWords*n*sizeof(int32_t), hipMemcpyHostToDevice);
+        e = hipMemcpy(t->c.st, host, (size_t) kV29TxWords*n*sizeof(int32_t), hipMemcpyHostToDevice);
     free(host);
     if (e != hipSuccess)
         return spangpu_set_error(SPANGPU_ERR_HIP, "state transfer failed");
@@ -453,26 +377,26 @@ int spangpu_modemtx_restart(spangpu_modemtx_t *t, int channel, int bit_rate, int
 
 int spangpu_modemtx_restart_ex(spangpu_modemtx_t *t, int channel, int bit_rate, int tep, int short_train)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->n_ch)
+    if (t == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int32_t w[kV29TxWords];
-    int rc = rw_words(t, channel, w, false);
+    int rc = core_rw_words(&t->c, channel, 0, kV29TxWords, w, false);
     if (rc != SPANGPU_OK)
         return rc;
     if (restart_words(w, t->kind, bit_rate, tep, short_train) != 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bit rate not valid for this modem");
-    if ((rc = rw_words(t, channel, w, true)) != SPANGPU_OK  ||  t->source != kTxSrcQueue)
+    if ((rc = core_rw_words(&t->c, channel, 0, kV29TxWords, w, true)) != SPANGPU_OK  ||  t->source != kTxSrcQueue)
         return rc;
     // a fresh sender has nothing queued and has not been told of the end of its data (as fsk_tx_restart() of the FSK objects)
     int32_t q[VQ_EOD + 1] = {0, 0, 0};
-    return rw_qwords(t, channel, VQ_RD, VQ_EOD + 1, q, true);
+    return core_rw_at(&t->c, t->qst, channel, VQ_RD, VQ_EOD + 1, q, true);
 }
 
 int spangpu_modemtx_get_state(spangpu_modemtx_t *t, int channel, int32_t *words)
 {
-    if (t == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= t->n_ch)
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return rw_words(t, channel, words, false);
+    return core_rw_words(&t->c, channel, 0, kV29TxWords, words, false);
 }
 
 static int tx_call(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens, int more);
@@ -494,134 +418,87 @@ int spangpu_modemtx_tx_continue(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm
 
 static int tx_call(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens, int more)
 {
-    if (t == NULL  ||  pcm == NULL  ||  samples < 0  ||  stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    VT_TRY(hipSetDevice(t->device));
+    int rc = tx_args_ok(t, mem_kind, pcm, stride, samples);
+    if (rc != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipSetDevice(t->c.device));
+    const bool host = (mem_kind == SPANGPU_MEM_HOST);
+    const bool queue = (t->source == kTxSrcQueue);
     if (samples == 0)
     {
         // xxx_tx(s, amp, 0) returns 0 and touches nothing; no channel has an event
-        if (t->source == kTxSrcQueue)
-            VT_TRY(hipMemsetAsync(t->qst + (size_t) VQ_EVENT*t->n_ch, 0, (size_t) t->n_ch*sizeof(int32_t), t->stream));
-        if (lens  &&  mem_kind == SPANGPU_MEM_HOST)
-            memset(lens, 0, (size_t) t->n_ch*sizeof(int32_t));
+        // (an empty call zeroes the lens of a device caller too and clears the event flags; the other senders do neither)
+        if (queue)
+            SPG_TRY(hipMemsetAsync(t->qst + (size_t) VQ_EVENT*t->c.n_ch, 0, (size_t) t->c.n_ch*sizeof(int32_t), t->c.stream));
+        if (lens  &&  host)
+            memset(lens, 0, (size_t) t->c.n_ch*sizeof(int32_t));
         else if (lens)
-            VT_TRY(hipMemsetAsync(lens, 0, (size_t) t->n_ch*sizeof(int32_t), t->stream));
+            SPG_TRY(hipMemsetAsync(lens, 0, (size_t) t->c.n_ch*sizeof(int32_t), t->c.stream));
         return 0;
     }
-    if (lens  &&  mem_kind == SPANGPU_MEM_HOST  &&  t->source == kTxSrcQueue  &&  t->d_lens == NULL
-        &&  hipMalloc(&t->d_lens, (size_t) t->n_ch*sizeof(int32_t)) != hipSuccess)
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "length staging");
+    // the kernel reports lengths only where they can differ: a queue-sourced bank whose caller asks for them
+    int32_t *want = queue  ?  lens  :  NULL;
+    if (want  &&  host  &&  (rc = stage_lens(&t->c, &t->pcm)) != SPANGPU_OK)
+        return rc;
     V29TxLaunch L;
     memset(&L, 0, sizeof(L));
-    L.st = t->st;
+    L.st = t->c.st;
     L.sine = t->sine;
     L.shaper = t->shaper;
     L.constel = t->constel;
-    L.n_ch = t->n_ch;
+    L.n_ch = t->c.n_ch;
     L.samples = samples;
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > t->pcm_cap)
-        {
-            VT_TRY(hipStreamSynchronize(t->stream));
-            (void) hipFree(t->d_pcm);
-            t->d_pcm = NULL;
-            t->pcm_cap = 0;
-            if (hipMalloc(&t->d_pcm, need*t->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            t->pcm_cap = need;
-        }
-        L.pcm = t->d_pcm;
-        L.stride = (long long) t->pcm_cap;
-    }
-    else
-    {
-        L.pcm = pcm;
-        L.stride = stride;
-    }
-    L.vec = ((L.stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(L.pcm) & 15) == 0)  ?  1  :  0;
-    if (t->source == kTxSrcQueue)
+    if ((rc = stage_out_target(&t->c, &t->pcm, mem_kind, pcm, stride, samples, want, &L.pcm, &L.stride, &L.lens, &L.vec)) != SPANGPU_OK)
+        return rc;
+    if (queue)
     {
         L.qring = t->qring;
         L.more = more;
         L.queue = t->queue;
         L.qst = t->qst;
-        L.lens = (lens == NULL)  ?  NULL  :  ((mem_kind == SPANGPU_MEM_HOST)  ?  t->d_lens  :  lens);
+        L.lens = want  ?  L.lens  :  NULL;
         launch_bank<kTxSrcQueue>(t, L);
     }
     else
     {
+        L.lens = NULL;
         launch_bank<kTxSrcLfsr>(t, L);
         // an LFSR never runs out of bits: no channel of such a bank shuts down
-        if (lens  &&  mem_kind == SPANGPU_MEM_DEVICE)
-            VT_TRY(hipMemsetD32Async((hipDeviceptr_t) lens, samples, (size_t) t->n_ch, t->stream));
+        if (lens  &&  !host)
+            SPG_TRY(hipMemsetD32Async((hipDeviceptr_t) lens, samples, (size_t) t->c.n_ch, t->c.stream));
     }
-    VT_TRY(hipGetLastError());
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        VT_TRY(hipMemcpy2DAsync(pcm, (size_t) stride*sizeof(int16_t), t->d_pcm, t->pcm_cap*sizeof(int16_t),
-                                (size_t) samples*sizeof(int16_t), t->n_ch, hipMemcpyDeviceToHost, t->stream));
-        if (lens  &&  t->source == kTxSrcQueue)
-            VT_TRY(hipMemcpyAsync(lens, t->d_lens, (size_t) t->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-        VT_TRY(hipStreamSynchronize(t->stream));
-        for (int c = 0;  lens  &&  t->source == kTxSrcLfsr  &&  c < t->n_ch;  c++)
-            lens[c] = samples;
-    }
+    SPG_TRY(hipGetLastError());
+    if ((rc = stage_out_back(&t->c, &t->pcm, mem_kind, pcm, stride, samples, want)) != SPANGPU_OK)
+        return rc;
+    for (int c = 0;  lens  &&  host  &&  !queue  &&  c < t->c.n_ch;  c++)
+        lens[c] = samples;
+    // (the modem senders return the length of the call, as xxx_tx() does; every other sender returns SPANGPU_OK)
     return samples;
 }
 
 int spangpu_modemtx_put_bits(spangpu_modemtx_t *t, int first, int n, const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted)
 {
-    if (t == NULL  ||  t->source != kTxSrcQueue  ||  first < 0  ||  n <= 0  ||  first + n > t->n_ch  ||  bits == NULL  ||  lens == NULL
-        ||  stride <= 0)
+    if (t == NULL  ||  t->source != kTxSrcQueue)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
-    for (int i = 0;  i < n;  i++)
-    {
-        if (lens[i] < 0  ||  (lens[i] + 7)/8 > stride)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's bits do not fit its row");
-    }
-    VT_TRY(hipSetDevice(t->device));
-    const size_t bytes = (size_t) n*stride;
-    if (bytes > t->bits_cap)
-    {
-        VT_TRY(hipStreamSynchronize(t->stream));
-        (void) hipFree(t->d_bits);
-        t->d_bits = NULL;
-        t->bits_cap = 0;
-        if (hipMalloc(&t->d_bits, bytes) != hipSuccess)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "bit staging");
-        t->bits_cap = bytes;
-    }
-    VT_TRY(hipMemcpyAsync(t->d_bits, bits, bytes, hipMemcpyHostToDevice, t->stream));
-    VT_TRY(hipMemcpyAsync(t->d_blens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, t->stream));
-    hipLaunchKernelGGL(modemtx_put_kernel, dim3((n + 63)/64), dim3(64), 0, t->stream, t->qst, t->queue, t->n_ch, t->qring, t->qcap,
-                       first, first + n, t->d_bits, stride, t->d_blens, t->d_acc);
-    VT_TRY(hipGetLastError());
-    if (accepted)
-        VT_TRY(hipMemcpyAsync(accepted, t->d_acc, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-    // the caller's arrays are pageable: they must not change under the copies
-    VT_TRY(hipStreamSynchronize(t->stream));
-    return SPANGPU_OK;
+    return bitring_put(&t->c, &t->put, t->qst + (size_t) VQ_RD*t->c.n_ch, t->qst + (size_t) VQ_COUNT*t->c.n_ch, t->queue, t->qring,
+                       t->qcap, first, n, bits, stride, lens, accepted);
 }
 
 int spangpu_modemtx_queued(spangpu_modemtx_t *t, int channel)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->n_ch  ||  t->source != kTxSrcQueue)
+    if (t == NULL  ||  !channel_ok(&t->c, channel)  ||  t->source != kTxSrcQueue)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
     int32_t w = 0;
-    const int rc = rw_qwords(t, channel, VQ_COUNT, 1, &w, false);
+    const int rc = core_rw_at(&t->c, t->qst, channel, VQ_COUNT, 1, &w, false);
     return (rc != SPANGPU_OK)  ?  rc  :  w;
 }
 
 int spangpu_modemtx_end_of_data(spangpu_modemtx_t *t, int channel, int on)
 {
-    if (t == NULL  ||  channel < 0  ||  channel >= t->n_ch  ||  t->source != kTxSrcQueue)
+    if (t == NULL  ||  !channel_ok(&t->c, channel)  ||  t->source != kTxSrcQueue)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
     int32_t w = on  ?  1  :  0;
-    return rw_qwords(t, channel, VQ_EOD, 1, &w, true);
+    return core_rw_at(&t->c, t->qst, channel, VQ_EOD, 1, &w, true);
 }
 
 int spangpu_modemtx_events(spangpu_modemtx_t *t, const int32_t **channels, const int32_t **kinds)
@@ -634,13 +511,13 @@ int spangpu_modemtx_events(spangpu_modemtx_t *t, const int32_t **channels, const
         *kinds = NULL;
     if (t->source != kTxSrcQueue)
         return 0;
-    const int n = t->n_ch;
+    const int n = t->c.n_ch;
     int32_t *chans = t->h_row;                      // a channel has at most two events in a call
     int32_t *kind = t->h_row + (size_t) 2*n;
     int32_t *flags = t->h_row + (size_t) 4*n;
-    VT_TRY(hipSetDevice(t->device));
-    VT_TRY(hipMemcpyAsync(flags, t->qst + (size_t) VQ_EVENT*n, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
-    VT_TRY(hipStreamSynchronize(t->stream));
+    SPG_TRY(hipSetDevice(t->c.device));
+    SPG_TRY(hipMemcpyAsync(flags, t->qst + (size_t) VQ_EVENT*n, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, t->c.stream));
+    SPG_TRY(hipStreamSynchronize(t->c.stream));
     int count = 0;
     for (int c = 0;  c < n;  c++)
     {

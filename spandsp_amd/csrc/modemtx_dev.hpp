@@ -634,32 +634,4 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     }
 }
 
-// spangpu_modemtx_put_bits() on channels [lo, hi): the bits of channel c are packed LSB first at bits[(c - lo)*bstride ...],
-// lens[c - lo] of them; accepted[c - lo] = how many had room.
-__global__ void modemtx_put_kernel(int32_t *qst, uint32_t *queue, int n_ch, int qring, int qcap, int lo, int hi, const uint8_t *bits,
-                                   int bstride, const int32_t *lens, int32_t *accepted)
-{
-    const int ch = lo + blockIdx.x*blockDim.x + threadIdx.x;
-    if (ch >= hi)
-        return;
-    const size_t n = (size_t) n_ch;
-    const uint8_t *src = bits + (size_t) (ch - lo)*bstride;
-    const int rd = qst[VQ_RD*n + ch];
-    const int count = qst[VQ_COUNT*n + ch];
-    int mine = lens[ch - lo];
-    mine = (mine > qcap - count)  ?  (qcap - count)  :  mine;
-    mine = (mine < 0)  ?  0  :  mine;
-    int at = rd + count;
-    at -= (at >= qring)  ?  qring  :  0;
-    for (int i = 0;  i < mine;  i++)
-    {
-        const uint32_t bit = (src[i >> 3] >> (i & 7)) & 1u;
-        uint32_t *w = queue + (size_t) (at >> 5)*n + ch;
-        *w = (*w & ~(1u << (at & 31))) | (bit << (at & 31));
-        at = (at + 1 == qring)  ?  0  :  (at + 1);
-    }
-    qst[VQ_COUNT*n + ch] = count + mine;
-    accepted[ch - lo] = mine;
-}
-
 }   // namespace spg

@@ -10,36 +10,16 @@
 #include "../../include/spangpu.h"
 #include "modem_tables.h"
 #include "txgen_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define TX_TRY(expr)                                                                        \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
-
 struct spangpu_txbank_s
 {
-    int device;
+    BankCore c;             // st[kTxWords][n_ch]
+    PcmStage pcm;
     int kind;
-    int n_ch;
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;            // [kTxWords][n_ch]
     float *sine;            // [2048]
-    int16_t *d_pcm;         // staging for host-resident output
-    size_t pcm_cap;         // samples per channel
-    int32_t *d_lens;        // [n_ch]
     uint8_t *d_digits;      // staging for put
     size_t digits_cap;
     int32_t *d_put_lens;    // [n_ch]
@@ -125,28 +105,19 @@ int spangpu_txbank_create(spangpu_txbank_t **out, int device, int kind, int n_ch
     if (out == NULL  ||  n_channels <= 0  ||  kind < SPANGPU_TX_TONE_GEN  ||  kind > SPANGPU_TX_R2_MF_BACK)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     *out = NULL;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    TX_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_txbank_s *b = (spangpu_txbank_s *) calloc(1, sizeof(*b));
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    b->device = device;
     b->kind = kind;
-    b->n_ch = n_channels;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+    if ((rc = core_create(&b->c, device, n_channels, kTxWords)) != SPANGPU_OK  ||  (rc = stage_lens(&b->c, &b->pcm)) != SPANGPU_OK)
     {
-        free(b);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
+        spangpu_txbank_destroy(b);
+        return rc;
     }
-    b->own_stream = true;
-    const size_t words = (size_t) kTxWords*n_channels;
-    if (hipMalloc(&b->st, words*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&b->sine, 2048*sizeof(float)) != hipSuccess
-        ||  hipMalloc(&b->d_lens, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
+    if (hipMalloc(&b->sine, 2048*sizeof(float)) != hipSuccess
         ||  hipMalloc(&b->d_put_lens, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
         ||  hipMalloc(&b->d_put_res, (size_t) n_channels*sizeof(int32_t)) != hipSuccess)
     {
@@ -158,34 +129,23 @@ int spangpu_txbank_create(spangpu_txbank_t **out, int device, int kind, int n_ch
     build_digit_table(&b->dig, kind);
     // Initial state: xxx_tx_init() leaves every generator idle (dtmf.c:640-660, bell_r2_mf.c:358-381,
     // bell_r2_mf.c:430-487) -- all words zero except section = -1 and the DTMF defaults.
-    int32_t *host = (int32_t *) calloc(words, sizeof(int32_t));
-    if (host == NULL)
+    int32_t one[kTxWords];
+    memset(one, 0, sizeof(one));
+    one[TX_SECTION] = -1;
+    if (kind == TXK_DTMF)
+    {
+        const float lvl = spg_dds_scaling_dbm0f(-10.0f);
+        memcpy(&one[TX_LOW], &lvl, 4);
+        memcpy(&one[TX_HIGH], &lvl, 4);
+        one[TX_ON] = 50*8000/1000;
+        one[TX_OFF] = 55*8000/1000;
+    }
+    if ((rc = core_fill(&b->c, one)) == SPANGPU_OK  &&  hipMemcpy(b->sine, sine, sizeof(sine), hipMemcpyHostToDevice) != hipSuccess)
+        rc = spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+    if (rc != SPANGPU_OK)
     {
         spangpu_txbank_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    }
-    const float lvl = spg_dds_scaling_dbm0f(-10.0f);
-    int32_t lvl_bits;
-    memcpy(&lvl_bits, &lvl, 4);
-    for (int c = 0;  c < n_channels;  c++)
-    {
-        host[(size_t) TX_SECTION*n_channels + c] = -1;
-        if (kind == TXK_DTMF)
-        {
-            host[(size_t) TX_LOW*n_channels + c] = lvl_bits;
-            host[(size_t) TX_HIGH*n_channels + c] = lvl_bits;
-            host[(size_t) TX_ON*n_channels + c] = 50*8000/1000;
-            host[(size_t) TX_OFF*n_channels + c] = 55*8000/1000;
-        }
-    }
-    hipError_t e = hipMemcpy(b->st, host, words*sizeof(int32_t), hipMemcpyHostToDevice);
-    free(host);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->sine, sine, sizeof(sine), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-    {
-        spangpu_txbank_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+        return rc;
     }
     *out = b;
     return SPANGPU_OK;
@@ -195,49 +155,35 @@ void spangpu_txbank_destroy(spangpu_txbank_t *b)
 {
     if (b == NULL)
         return;
-    (void) hipSetDevice(b->device);
-    if (b->stream)
-        (void) hipStreamSynchronize(b->stream);
-    (void) hipFree(b->st);
+    core_destroy(&b->c);
+    stage_free(&b->pcm);
     (void) hipFree(b->sine);
-    (void) hipFree(b->d_pcm);
-    (void) hipFree(b->d_lens);
     (void) hipFree(b->d_digits);
     (void) hipFree(b->d_put_lens);
     (void) hipFree(b->d_put_res);
-    if (b->own_stream  &&  b->stream)
-        (void) hipStreamDestroy(b->stream);
     free(b);
 }
 
-int spangpu_txbank_channels(const spangpu_txbank_t *b) { return b  ?  b->n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_txbank_channels(const spangpu_txbank_t *b) { return b  ?  b->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 int spangpu_txbank_state_words(void) { return kTxWords; }
 
 int spangpu_txbank_set_stream(spangpu_txbank_t *b, void *stream)
 {
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    TX_TRY(hipSetDevice(b->device));
-    TX_TRY(hipStreamSynchronize(b->stream));
-    if (b->own_stream)
-        (void) hipStreamDestroy(b->stream);
-    b->stream = (hipStream_t) stream;
-    b->own_stream = false;
-    return SPANGPU_OK;
+    return core_set_stream(&b->c, stream);
 }
 
 int spangpu_txbank_sync(spangpu_txbank_t *b)
 {
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    TX_TRY(hipSetDevice(b->device));
-    TX_TRY(hipStreamSynchronize(b->stream));
-    return SPANGPU_OK;
+    return core_sync(&b->c);
 }
 
 static int check_range(const spangpu_txbank_s *b, int first, int n)
 {
-    if (b == NULL  ||  first < 0  ||  n <= 0  ||  first > b->n_ch - n)
+    if (b == NULL  ||  !range_ok(&b->c, first, n))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "channel range outside the bank");
     return SPANGPU_OK;
 }
@@ -256,11 +202,11 @@ int spangpu_txbank_tone(spangpu_txbank_t *b, int first, int n, const spangpu_ton
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a repeating cadence needs a first section of at least 1 ms");
     td.r2digit = -1;
     td.load = 1;
-    TX_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     int blocks;
     const int threads = launch_cfg(n, &blocks);
-    hipLaunchKernelGGL(tx_load_descriptor_kernel, dim3(blocks), dim3(threads), 0, b->stream, b->st, b->n_ch, first, first + n, td);
-    TX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tx_load_descriptor_kernel, dim3(blocks), dim3(threads), 0, b->c.stream, b->c.st, b->c.n_ch, first, first + n, td);
+    SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
 
@@ -277,12 +223,12 @@ int spangpu_txbank_set_level(spangpu_txbank_t *b, int first, int n, int level, i
     int32_t lo_bits, hi_bits;
     memcpy(&lo_bits, &lo, 4);
     memcpy(&hi_bits, &hi, 4);
-    TX_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     int blocks;
     const int threads = launch_cfg(n, &blocks);
-    hipLaunchKernelGGL(tx_set_words_kernel, dim3(blocks), dim3(threads), 0, b->stream, b->st, b->n_ch, first, first + n,
+    hipLaunchKernelGGL(tx_set_words_kernel, dim3(blocks), dim3(threads), 0, b->c.stream, b->c.st, b->c.n_ch, first, first + n,
                        (int) TX_LOW, lo_bits, (int) TX_HIGH, hi_bits);
-    TX_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
 
@@ -296,12 +242,12 @@ int spangpu_txbank_set_timing(spangpu_txbank_t *b, int first, int n, int on_time
     // dtmf_tx_set_timing(), dtmf.c:628-633
     const int on = ((on_time >= 0)  ?  on_time  :  50)*8000/1000;
     const int off = ((off_time >= 0)  ?  off_time  :  55)*8000/1000;
-    TX_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     int blocks;
     const int threads = launch_cfg(n, &blocks);
-    hipLaunchKernelGGL(tx_set_words_kernel, dim3(blocks), dim3(threads), 0, b->stream, b->st, b->n_ch, first, first + n,
+    hipLaunchKernelGGL(tx_set_words_kernel, dim3(blocks), dim3(threads), 0, b->c.stream, b->c.st, b->c.n_ch, first, first + n,
                        (int) TX_ON, on, (int) TX_OFF, off);
-    TX_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
 
@@ -326,11 +272,11 @@ static int put_r2(spangpu_txbank_s *b, int first, int n, char digit)
         td.load = 0;
         td.r2digit = 0;
     }
-    TX_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     int blocks;
     const int threads = launch_cfg(n, &blocks);
-    hipLaunchKernelGGL(tx_load_descriptor_kernel, dim3(blocks), dim3(threads), 0, b->stream, b->st, b->n_ch, first, first + n, td);
-    TX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tx_load_descriptor_kernel, dim3(blocks), dim3(threads), 0, b->c.stream, b->c.st, b->c.n_ch, first, first + n, td);
+    SPG_TRY(hipGetLastError());
     return 0;
 }
 
@@ -338,27 +284,20 @@ static int put_common(spangpu_txbank_s *b, int first, int n, const char *digits,
                       int *results)
 {
     const size_t bytes = lens  ?  (size_t) n*dstride  :  (size_t) len;
-    TX_TRY(hipSetDevice(b->device));
-    if (bytes > b->digits_cap)
-    {
-        TX_TRY(hipStreamSynchronize(b->stream));
-        (void) hipFree(b->d_digits);
-        b->d_digits = NULL;
-        b->digits_cap = 0;
-        if (hipMalloc(&b->d_digits, bytes) != hipSuccess)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "digit staging");
-        b->digits_cap = bytes;
-    }
+    SPG_TRY(hipSetDevice(b->c.device));
+    const int rc = grow(&b->d_digits, &b->digits_cap, bytes, 1, b->c.stream);
+    if (rc != SPANGPU_OK)
+        return rc;
     if (bytes)
-        TX_TRY(hipMemcpyAsync(b->d_digits, digits, bytes, hipMemcpyHostToDevice, b->stream));
+        SPG_TRY(hipMemcpyAsync(b->d_digits, digits, bytes, hipMemcpyHostToDevice, b->c.stream));
     if (lens)
-        TX_TRY(hipMemcpyAsync(b->d_put_lens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+        SPG_TRY(hipMemcpyAsync(b->d_put_lens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, b->c.stream));
     int blocks;
     const int threads = launch_cfg(n, &blocks);
-    hipLaunchKernelGGL(tx_put_kernel, dim3(blocks), dim3(threads), 0, b->stream, b->st, b->n_ch, first, first + n,
+    hipLaunchKernelGGL(tx_put_kernel, dim3(blocks), dim3(threads), 0, b->c.stream, b->c.st, b->c.n_ch, first, first + n,
                        (const uint8_t *) b->d_digits, lens  ?  dstride  :  0, lens  ?  (const int32_t *) b->d_put_lens  :  NULL,
                        len, b->d_put_res);
-    TX_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     int *res = results;
     int *tmp = NULL;
     if (res == NULL)
@@ -367,9 +306,9 @@ static int put_common(spangpu_txbank_s *b, int first, int n, const char *digits,
             return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
         res = tmp;
     }
-    hipError_t e = hipMemcpyAsync(res, b->d_put_res, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, b->stream);
+    hipError_t e = hipMemcpyAsync(res, b->d_put_res, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream);
     if (e == hipSuccess)
-        e = hipStreamSynchronize(b->stream);       // also: the caller's digit buffers are only borrowed
+        e = hipStreamSynchronize(b->c.stream);       // also: the caller's digit buffers are only borrowed
     int worst = 0;
     if (e == hipSuccess)
     {
@@ -419,69 +358,36 @@ int spangpu_txbank_put_each(spangpu_txbank_t *b, int first, int n, const char *d
 
 int spangpu_txbank_tx(spangpu_txbank_t *b, int mem_kind, int16_t *pcm, long long stride, int samples, int *lens)
 {
-    if (b == NULL  ||  pcm == NULL  ||  samples < 0  ||  stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
+    int rc = tx_args_ok(b, mem_kind, pcm, stride, samples);
+    if (rc != SPANGPU_OK)
+        return rc;
+    // (an empty call leaves a host caller's lens as they are; the FSK, connect tone and V.18 senders zero them)
     if (samples == 0)
         return SPANGPU_OK;
-    TX_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     TxLaunch L;
     memset(&L, 0, sizeof(L));
-    L.st = b->st;
+    L.st = b->c.st;
     L.sine = b->sine;
-    L.n_ch = b->n_ch;
+    L.n_ch = b->c.n_ch;
     L.samples = samples;
     L.kind = b->kind;
     L.dig = b->dig;
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > b->pcm_cap)
-        {
-            TX_TRY(hipStreamSynchronize(b->stream));
-            (void) hipFree(b->d_pcm);
-            b->d_pcm = NULL;
-            b->pcm_cap = 0;
-            if (hipMalloc(&b->d_pcm, need*b->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            b->pcm_cap = need;
-        }
-        L.pcm = b->d_pcm;
-        L.stride = (long long) b->pcm_cap;
-        L.lens = b->d_lens;
-    }
-    else
-    {
-        L.pcm = pcm;
-        L.stride = stride;
-        L.lens = lens;
-    }
+    if ((rc = stage_out_target(&b->c, &b->pcm, mem_kind, pcm, stride, samples, lens, &L.pcm, &L.stride, &L.lens, NULL)) != SPANGPU_OK)
+        return rc;
     // 16 channels per wave, four waves per workgroup: even a small bank puts several waves on every SIMD,
     // and the 8 KB sine table copy is shared by 64 channels
-    hipLaunchKernelGGL(tx_bank_kernel<kTxChannelsPerWave>, dim3((b->n_ch + kTxChannelsPerWave*kTxWaves - 1)/(kTxChannelsPerWave*kTxWaves)),
-                       dim3(64*kTxWaves), 0, b->stream, L);
-    TX_TRY(hipGetLastError());
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        TX_TRY(hipMemcpy2DAsync(pcm, (size_t) stride*sizeof(int16_t), b->d_pcm, b->pcm_cap*sizeof(int16_t),
-                                (size_t) samples*sizeof(int16_t), b->n_ch, hipMemcpyDeviceToHost, b->stream));
-        if (lens)
-            TX_TRY(hipMemcpyAsync(lens, b->d_lens, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-        TX_TRY(hipStreamSynchronize(b->stream));
-    }
-    return SPANGPU_OK;
+    hipLaunchKernelGGL(tx_bank_kernel<kTxChannelsPerWave>, dim3((b->c.n_ch + kTxChannelsPerWave*kTxWaves - 1)/(kTxChannelsPerWave*kTxWaves)),
+                       dim3(64*kTxWaves), 0, b->c.stream, L);
+    SPG_TRY(hipGetLastError());
+    return stage_out_back(&b->c, &b->pcm, mem_kind, pcm, stride, samples, lens);
 }
 
 int spangpu_txbank_get_state(spangpu_txbank_t *b, int channel, int32_t *words)
 {
-    if (b == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= b->n_ch)
+    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    TX_TRY(hipSetDevice(b->device));
-    TX_TRY(hipMemcpy2DAsync(words, sizeof(int32_t), b->st + channel, (size_t) b->n_ch*sizeof(int32_t), sizeof(int32_t),
-                            kTxWords, hipMemcpyDeviceToHost, b->stream));
-    TX_TRY(hipStreamSynchronize(b->stream));
-    return SPANGPU_OK;
+    return core_rw_words(&b->c, channel, 0, kTxWords, words, false);
 }
 
 }   // extern "C"

@@ -12,45 +12,23 @@
 
 #include "../../include/spangpu.h"
 #include "v18_dev.hpp"
+#include "bank_host.hpp"
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
 extern "C" void spangpu_fsk_words_init(int32_t *w, const spangpu_fsk_spec_t *spec, int framing_mode, int data_bits, int parity, int stop_bits);
 extern "C" void spangpu_fsk_words_fillin(int32_t *w, int len);
 extern "C" void spangpu_fsktx_words_restart(int32_t *w, const spangpu_fsk_spec_t *spec);
 
-#define V18_TRY(expr)                                                                       \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
-
-constexpr int kMaxSamples = 1 << 24;
-
 struct spangpu_v18_s
 {
-    int device;
-    int n_ch;
+    BankCore c;
+    PcmStage pcm;               // frames of a host caller, either way; d_lens: the sender's lengths
     int span;
-    int words;
     int max_baud;               // x 100, over the bank's channels: sizes the text records
-    hipStream_t stream;
-    bool own_stream;
-    int32_t *st;
     int16_t *quarter;
     uint8_t *ring;
     uint8_t *tables;
-    int16_t *d_pcm;             // staging for host-resident frames
-    size_t pcm_cap;
-    int32_t *d_lens;            // [n_ch]: the sender's lengths for a host caller
     int32_t *d_rxlens;          // [n_ch]: per-channel lengths of an rx_var call
     int32_t *h_rxlens;          // pinned
     uint8_t *chars;
@@ -150,34 +128,17 @@ static void modem_words(int32_t *w, int words, int mode)
     spangpu_fsk_words_init(w + kV18Words + kFskTxWords, &spec, SPANGPU_FSK_FRAME_MODE_FRAMED, 5, SPANGPU_ASYNC_PARITY_NONE, 2);
 }
 
-static int rw_words(spangpu_v18_s *b, int ch, int32_t *w, bool write)
-{
-    V18_TRY(hipSetDevice(b->device));
-    if (write)
-        V18_TRY(hipMemcpy2DAsync(b->st + ch, (size_t) b->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), b->words,
-                                 hipMemcpyHostToDevice, b->stream));
-    else
-        V18_TRY(hipMemcpy2DAsync(w, sizeof(int32_t), b->st + ch, (size_t) b->n_ch*sizeof(int32_t), sizeof(int32_t), b->words,
-                                 hipMemcpyDeviceToHost, b->stream));
-    V18_TRY(hipStreamSynchronize(b->stream));
-    return SPANGPU_OK;
-}
-
 extern "C" {
 
 void spangpu_v18_destroy(spangpu_v18_t *b)
 {
     if (b == NULL)
         return;
-    (void) hipSetDevice(b->device);
-    if (b->stream)
-        (void) hipStreamSynchronize(b->stream);
-    (void) hipFree(b->st);
+    core_destroy(&b->c);
+    stage_free(&b->pcm);
     (void) hipFree(b->quarter);
     (void) hipFree(b->ring);
     (void) hipFree(b->tables);
-    (void) hipFree(b->d_pcm);
-    (void) hipFree(b->d_lens);
     (void) hipFree(b->d_rxlens);
     if (b->h_rxlens)
         (void) hipHostFree(b->h_rxlens);
@@ -188,8 +149,6 @@ void spangpu_v18_destroy(spangpu_v18_t *b)
     (void) hipFree(b->d_res);
     free(b->h_chars);
     free(b->h_counts);
-    if (b->own_stream  &&  b->stream)
-        (void) hipStreamDestroy(b->stream);
     free(b);
 }
 
@@ -203,36 +162,28 @@ int spangpu_v18_create(spangpu_v18_t **out, int device, int n_channels, const in
         if (preset_of(modes[i]) < 0)
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a V.18 text bank runs the three Weitbrecht 5-bit modes only");
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess  ||  count <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= count)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    V18_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_v18_s *b = (spangpu_v18_s *) calloc(1, sizeof(*b));
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    b->device = device;
-    b->n_ch = n_channels;
     b->span = kFskMaxWindow;        // 800000/baud is above the window's limit at all three rates
-    b->words = kV18Words + kFskTxWords + kFskScalars + 4*b->span;
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+    const int n_words = kV18Words + kFskTxWords + kFskScalars + 4*b->span;
+    if ((rc = core_create(&b->c, device, n_channels, n_words)) != SPANGPU_OK  ||  (rc = quarter_sine_upload(&b->quarter)) != SPANGPU_OK
+        ||  (rc = stage_lens(&b->c, &b->pcm)) != SPANGPU_OK)
     {
-        free(b);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
+        spangpu_v18_destroy(b);
+        return rc;
     }
-    b->own_stream = true;
     const size_t n = (size_t) n_channels;
-    const size_t words = (size_t) b->words*n;
-    int32_t *one = (int32_t *) calloc(b->words, sizeof(int32_t));
+    const size_t words = (size_t) n_words*n;
+    int32_t *one = (int32_t *) calloc(n_words, sizeof(int32_t));
     int32_t *host = (int32_t *) calloc(words, sizeof(int32_t));
     b->h_counts = (int32_t *) malloc(n*sizeof(int32_t));
     if (one == NULL  ||  host == NULL  ||  b->h_counts == NULL
-        ||  hipMalloc(&b->st, words*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&b->quarter, 257*sizeof(int16_t)) != hipSuccess
         ||  hipMalloc(&b->ring, n*kV18Ring) != hipSuccess
         ||  hipMalloc(&b->tables, 192) != hipSuccess
-        ||  hipMalloc(&b->d_lens, n*sizeof(int32_t)) != hipSuccess
         ||  hipMalloc(&b->counts, n*sizeof(int32_t)) != hipSuccess)
     {
         free(one);
@@ -240,10 +191,6 @@ int spangpu_v18_create(spangpu_v18_t **out, int device, int n_channels, const in
         spangpu_v18_destroy(b);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the V.18 bank failed");
     }
-    // dds_int.c: one quadrant of a sine, 257 entries
-    int16_t quarter[257];
-    for (int i = 0;  i <= 256;  i++)
-        quarter[i] = (int16_t) lrint(32767.0*sin(i*3.14159265358979323846/512.0));
     // v18_init(), v18.c:2054-2115: memset, v18_set_modem(), an empty ring
     int last_mode = 0;
     for (int c = 0;  c < n_channels;  c++)
@@ -251,8 +198,8 @@ int spangpu_v18_create(spangpu_v18_t **out, int device, int n_channels, const in
         const int mode = modes[(n_modes == 1)  ?  0  :  c];
         if (mode != last_mode)
         {
-            memset(one, 0, (size_t) b->words*sizeof(int32_t));
-            modem_words(one, b->words, mode);
+            memset(one, 0, (size_t) b->c.words*sizeof(int32_t));
+            modem_words(one, b->c.words, mode);
             one[V18_CALLING_PARTY] = calling_party  ?  1  :  0;
             last_mode = mode;
             spangpu_fsk_spec_t spec;
@@ -263,140 +210,94 @@ int spangpu_v18_create(spangpu_v18_t **out, int device, int n_channels, const in
         for (int w = 0;  w < kV18Words + kFskTxWords + kFskScalars;  w++)
             host[(size_t) w*n + c] = one[w];
     }
-    hipError_t e = hipMemcpy(b->st, host, words*sizeof(int32_t), hipMemcpyHostToDevice);
+    // (the modes differ by channel: the words go up as they were prepared, not from one prototype)
+    rc = core_upload(&b->c, host);
     free(one);
     free(host);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->quarter, quarter, sizeof(quarter), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(b->tables, tables(), 192, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemset(b->ring, 0, n*kV18Ring);
-    if (e != hipSuccess)
+    if (rc == SPANGPU_OK
+        &&  (hipMemcpy(b->tables, tables(), 192, hipMemcpyHostToDevice) != hipSuccess  ||  hipMemset(b->ring, 0, n*kV18Ring) != hipSuccess))
+        rc = spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+    if (rc != SPANGPU_OK)
     {
         spangpu_v18_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
+        return rc;
     }
     *out = b;
     return SPANGPU_OK;
 }
 
-int spangpu_v18_channels(const spangpu_v18_t *b) { return b  ?  b->n_ch  :  SPANGPU_ERR_BAD_ARG; }
-int spangpu_v18_state_words(const spangpu_v18_t *b) { return b  ?  b->words  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_v18_channels(const spangpu_v18_t *b) { return b  ?  b->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_v18_state_words(const spangpu_v18_t *b) { return b  ?  b->c.words  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_v18_set_stream(spangpu_v18_t *b, void *stream)
 {
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    V18_TRY(hipSetDevice(b->device));
-    V18_TRY(hipStreamSynchronize(b->stream));
-    if (b->own_stream)
-        (void) hipStreamDestroy(b->stream);
-    b->stream = (hipStream_t) stream;
-    b->own_stream = false;
-    return SPANGPU_OK;
+    return core_set_stream(&b->c, stream);
 }
 
 int spangpu_v18_sync(spangpu_v18_t *b)
 {
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    V18_TRY(hipSetDevice(b->device));
-    V18_TRY(hipStreamSynchronize(b->stream));
-    return SPANGPU_OK;
+    return core_sync(&b->c);
 }
 
 int spangpu_v18_put(spangpu_v18_t *b, int first, int n, const uint8_t *text, int stride, const int32_t *lens, int32_t *results)
 {
-    if (b == NULL  ||  first < 0  ||  n <= 0  ||  first + n > b->n_ch  ||  text == NULL  ||  lens == NULL  ||  stride <= 0)
+    if (b == NULL  ||  !range_ok(&b->c, first, n)  ||  text == NULL  ||  lens == NULL  ||  stride <= 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     for (int i = 0;  i < n;  i++)
     {
         if (lens[i] < 0  ||  lens[i] > stride)
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's text does not fit its row");
     }
-    V18_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     const size_t bytes = (size_t) n*stride;
-    if (bytes > b->text_cap  ||  b->d_tlens == NULL)
-    {
-        V18_TRY(hipStreamSynchronize(b->stream));
-        (void) hipFree(b->d_text);
-        b->d_text = NULL;
-        b->text_cap = 0;
-        if (hipMalloc(&b->d_text, bytes) != hipSuccess
-            ||  (b->d_tlens == NULL  &&  hipMalloc(&b->d_tlens, (size_t) b->n_ch*sizeof(int32_t)) != hipSuccess)
-            ||  (b->d_res == NULL  &&  hipMalloc(&b->d_res, (size_t) b->n_ch*sizeof(int32_t)) != hipSuccess))
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "text staging");
-        b->text_cap = bytes;
-    }
-    V18_TRY(hipMemcpyAsync(b->d_text, text, bytes, hipMemcpyHostToDevice, b->stream));
-    V18_TRY(hipMemcpyAsync(b->d_tlens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
-    hipLaunchKernelGGL(v18_put_kernel, dim3((n + 63)/64), dim3(64), 0, b->stream, b->st, b->ring, b->n_ch, first, first + n, b->d_text, stride,
+    const int rc = grow(&b->d_text, &b->text_cap, bytes, 1, b->c.stream);
+    if (rc != SPANGPU_OK)
+        return rc;
+    if ((b->d_tlens == NULL  &&  hipMalloc(&b->d_tlens, (size_t) b->c.n_ch*sizeof(int32_t)) != hipSuccess)
+        ||  (b->d_res == NULL  &&  hipMalloc(&b->d_res, (size_t) b->c.n_ch*sizeof(int32_t)) != hipSuccess))
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "text staging");
+    SPG_TRY(hipMemcpyAsync(b->d_text, text, bytes, hipMemcpyHostToDevice, b->c.stream));
+    SPG_TRY(hipMemcpyAsync(b->d_tlens, lens, (size_t) n*sizeof(int32_t), hipMemcpyHostToDevice, b->c.stream));
+    hipLaunchKernelGGL(v18_put_kernel, dim3((n + 63)/64), dim3(64), 0, b->c.stream, b->c.st, b->ring, b->c.n_ch, first, first + n, b->d_text, stride,
                        b->d_tlens, b->d_res);
-    V18_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (results)
-        V18_TRY(hipMemcpyAsync(results, b->d_res, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+        SPG_TRY(hipMemcpyAsync(results, b->d_res, (size_t) n*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
     // the caller's arrays are pageable: they must not change under the copies
-    V18_TRY(hipStreamSynchronize(b->stream));
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
     return SPANGPU_OK;
 }
 
 int spangpu_v18_tx(spangpu_v18_t *b, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens)
 {
-    if (b == NULL  ||  pcm == NULL  ||  samples < 0  ||  samples > kMaxSamples  ||  stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
+    int rc = tx_args_ok(b, mem_kind, pcm, stride, samples);
+    if (rc != SPANGPU_OK)
+        return rc;
     if (samples == 0)
     {
+        // (an empty call zeroes a host caller's lens; the tone sender leaves them)
         if (lens  &&  mem_kind == SPANGPU_MEM_HOST)
-            memset(lens, 0, (size_t) b->n_ch*sizeof(int32_t));
+            memset(lens, 0, (size_t) b->c.n_ch*sizeof(int32_t));
         return SPANGPU_OK;
     }
-    V18_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     V18TxLaunch L;
     memset(&L, 0, sizeof(L));
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > b->pcm_cap)
-        {
-            V18_TRY(hipStreamSynchronize(b->stream));
-            (void) hipFree(b->d_pcm);
-            b->d_pcm = NULL;
-            b->pcm_cap = 0;
-            if (hipMalloc(&b->d_pcm, need*b->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            b->pcm_cap = need;
-        }
-        L.pcm = b->d_pcm;
-        L.stride = (long long) b->pcm_cap;
-        L.lens = b->d_lens;
-    }
-    else
-    {
-        L.pcm = pcm;
-        L.stride = stride;
-        L.lens = lens;
-    }
-    L.vec = ((L.stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(L.pcm) & 15) == 0)  ?  1  :  0;
-    L.st = b->st;
+    if ((rc = stage_out_target(&b->c, &b->pcm, mem_kind, pcm, stride, samples, lens, &L.pcm, &L.stride, &L.lens, &L.vec)) != SPANGPU_OK)
+        return rc;
+    L.st = b->c.st;
     L.quarter = b->quarter;
     L.ring = b->ring;
     L.tables = b->tables;
-    L.n_ch = b->n_ch;
+    L.n_ch = b->c.n_ch;
     L.samples = samples;
-    hipLaunchKernelGGL(v18_tx_kernel, dim3((b->n_ch + kFtxCpw*kFtxWaves - 1)/(kFtxCpw*kFtxWaves)), dim3(64*kFtxWaves), 0, b->stream, L);
-    V18_TRY(hipGetLastError());
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        V18_TRY(hipMemcpy2DAsync(pcm, (size_t) stride*sizeof(int16_t), b->d_pcm, b->pcm_cap*sizeof(int16_t),
-                                 (size_t) samples*sizeof(int16_t), b->n_ch, hipMemcpyDeviceToHost, b->stream));
-        if (lens)
-            V18_TRY(hipMemcpyAsync(lens, b->d_lens, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-        V18_TRY(hipStreamSynchronize(b->stream));
-    }
-    return SPANGPU_OK;
+    hipLaunchKernelGGL(v18_tx_kernel, dim3((b->c.n_ch + kFtxCpw*kFtxWaves - 1)/(kFtxCpw*kFtxWaves)), dim3(64*kFtxWaves), 0, b->c.stream, L);
+    SPG_TRY(hipGetLastError());
+    return stage_out_back(&b->c, &b->pcm, mem_kind, pcm, stride, samples, lens);
 }
 
 int spangpu_v18_text_capacity(const spangpu_v18_t *b, int samples)
@@ -410,75 +311,42 @@ int spangpu_v18_text_capacity(const spangpu_v18_t *b, int samples)
 
 static int rx_launch(spangpu_v18_s *b, const int16_t *amp, int mem_kind, int samples, long long stride, const int32_t *d_lens)
 {
-    V18_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     const int cap = spangpu_v18_text_capacity(b, samples);
-    if (cap > b->cap)
-    {
-        V18_TRY(hipStreamSynchronize(b->stream));
-        (void) hipFree(b->chars);
-        b->chars = NULL;
-        b->cap = 0;
-        if (hipMalloc(&b->chars, (size_t) b->n_ch*cap) != hipSuccess)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "text records");
-        b->cap = cap;
-    }
+    int rc = grow(&b->chars, &b->cap, cap, (size_t) b->c.n_ch, b->c.stream);
+    if (rc != SPANGPU_OK)
+        return rc;
     V18RxLaunch V;
     memset(&V, 0, sizeof(V));
     FskLaunch &L = V.f;
-    L.st = b->st + (size_t) (kV18Words + kFskTxWords)*b->n_ch;
+    L.st = b->c.st + (size_t) (kV18Words + kFskTxWords)*b->c.n_ch;
     L.quarter = b->quarter;
-    L.n_ch = b->n_ch;
+    L.n_ch = b->c.n_ch;
     L.samples = samples;
     L.lens = d_lens;
     L.span = b->span;
-    if (mem_kind == SPANGPU_MEM_HOST)
-    {
-        const size_t need = (size_t) ((samples + 7) & ~7);
-        if (need > b->pcm_cap)
-        {
-            V18_TRY(hipStreamSynchronize(b->stream));
-            (void) hipFree(b->d_pcm);
-            b->d_pcm = NULL;
-            b->pcm_cap = 0;
-            if (hipMalloc(&b->d_pcm, need*b->n_ch*sizeof(int16_t)) != hipSuccess)
-                return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pcm staging");
-            b->pcm_cap = need;
-        }
-        V18_TRY(hipMemcpy2DAsync(b->d_pcm, b->pcm_cap*sizeof(int16_t), amp, (size_t) stride*sizeof(int16_t),
-                                 (size_t) samples*sizeof(int16_t), b->n_ch, hipMemcpyHostToDevice, b->stream));
-        // the caller's buffer is only borrowed for the call
-        V18_TRY(hipStreamSynchronize(b->stream));
-        L.pcm = b->d_pcm;
-        L.stride = (long long) b->pcm_cap;
-    }
-    else
-    {
-        L.pcm = amp;
-        L.stride = stride;
-    }
-    L.vec = ((L.stride & 7) == 0  &&  (reinterpret_cast<uintptr_t>(L.pcm) & 15) == 0)  ?  1  :  0;
-    V.sv = b->st;
+    // the caller's buffer is only borrowed for the call: the copy in is waited for
+    if ((rc = stage_in(&b->c, &b->pcm, mem_kind, amp, stride, samples, true, &L.pcm, &L.stride, &L.vec)) != SPANGPU_OK)
+        return rc;
+    V.sv = b->c.st;
     V.tables = b->tables;
     V.chars = b->chars;
     V.counts = b->counts;
     V.cap = cap;
     const size_t lds = (size_t) (4*b->span*64 + 2*kFskMsgWords*64)*sizeof(int32_t);
-    hipLaunchKernelGGL(v18_rx_kernel, dim3((b->n_ch + 63)/64), dim3(128), lds, b->stream, V);
-    V18_TRY(hipGetLastError());
+    hipLaunchKernelGGL(v18_rx_kernel, dim3((b->c.n_ch + 63)/64), dim3(128), lds, b->c.stream, V);
+    SPG_TRY(hipGetLastError());
     b->last_cap = cap;
     return SPANGPU_OK;
 }
 
 int spangpu_v18_rx(spangpu_v18_t *b, const int16_t *amp, int mem_kind, int samples, long long stride)
 {
-    if (b == NULL  ||  amp == NULL  ||  samples <= 0  ||  samples > kMaxSamples)
+    if (samples > kMaxSamples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    if (stride <= 0)
-        stride = samples;
-    if (stride < samples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < samples");
+    const int rc = rx_args_ok(b, mem_kind, amp, samples, &stride);
+    if (rc != SPANGPU_OK)
+        return rc;
     return rx_launch(b, amp, mem_kind, samples, stride, NULL);
 }
 
@@ -490,7 +358,7 @@ int spangpu_v18_rx_var(spangpu_v18_t *b, const int16_t *amp, int mem_kind, const
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    for (int c = 0;  c < b->n_ch;  c++)
+    for (int c = 0;  c < b->c.n_ch;  c++)
     {
         if (lens[c] < 0  ||  lens[c] > max_samples)
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
@@ -499,15 +367,15 @@ int spangpu_v18_rx_var(spangpu_v18_t *b, const int16_t *amp, int mem_kind, const
         stride = max_samples;
     if (stride < max_samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < max_samples");
-    V18_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->c.device));
     if (b->d_rxlens == NULL)
     {
-        V18_TRY(hipMalloc(&b->d_rxlens, (size_t) b->n_ch*sizeof(int32_t)));
-        V18_TRY(hipHostMalloc(&b->h_rxlens, (size_t) b->n_ch*sizeof(int32_t)));
+        SPG_TRY(hipMalloc(&b->d_rxlens, (size_t) b->c.n_ch*sizeof(int32_t)));
+        SPG_TRY(hipHostMalloc(&b->h_rxlens, (size_t) b->c.n_ch*sizeof(int32_t)));
     }
-    V18_TRY(hipStreamSynchronize(b->stream));
-    memcpy(b->h_rxlens, lens, (size_t) b->n_ch*sizeof(int32_t));
-    V18_TRY(hipMemcpyAsync(b->d_rxlens, b->h_rxlens, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
+    memcpy(b->h_rxlens, lens, (size_t) b->c.n_ch*sizeof(int32_t));
+    SPG_TRY(hipMemcpyAsync(b->d_rxlens, b->h_rxlens, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, b->c.stream));
     return rx_launch(b, amp, mem_kind, max_samples, stride, b->d_rxlens);
 }
 
@@ -517,8 +385,8 @@ int spangpu_v18_text(spangpu_v18_t *b, const uint8_t **chars, const int32_t **co
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_v18_rx() yet");
-    V18_TRY(hipSetDevice(b->device));
-    const size_t bytes = (size_t) b->n_ch*b->last_cap;
+    SPG_TRY(hipSetDevice(b->c.device));
+    const size_t bytes = (size_t) b->c.n_ch*b->last_cap;
     if (bytes > b->h_chars_cap)
     {
         free(b->h_chars);
@@ -527,11 +395,11 @@ int spangpu_v18_text(spangpu_v18_t *b, const uint8_t **chars, const int32_t **co
             return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host text records");
         b->h_chars_cap = bytes;
     }
-    V18_TRY(hipMemcpyAsync(b->h_chars, b->chars, bytes, hipMemcpyDeviceToHost, b->stream));
-    V18_TRY(hipMemcpyAsync(b->h_counts, b->counts, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    V18_TRY(hipStreamSynchronize(b->stream));
+    SPG_TRY(hipMemcpyAsync(b->h_chars, b->chars, bytes, hipMemcpyDeviceToHost, b->c.stream));
+    SPG_TRY(hipMemcpyAsync(b->h_counts, b->counts, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
     // the record is sized from the frame format; a count above it would mean the sizing is wrong, and is not cut short quietly
-    for (int c = 0;  c < b->n_ch;  c++)
+    for (int c = 0;  c < b->c.n_ch;  c++)
     {
         if (b->h_counts[c] > b->last_cap)
             return spangpu_set_error(SPANGPU_ERR_STATE, "a channel decoded more characters than a call of this length can carry");
@@ -543,34 +411,34 @@ int spangpu_v18_text(spangpu_v18_t *b, const uint8_t **chars, const int32_t **co
 
 int spangpu_v18_get_state(spangpu_v18_t *b, int channel, int32_t *words)
 {
-    if (b == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= b->n_ch)
+    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return rw_words(b, channel, words, false);
+    return core_rw_words(&b->c, channel, 0, b->c.words, words, false);
 }
 
 int spangpu_v18_set_state(spangpu_v18_t *b, int channel, const int32_t *words)
 {
-    if (b == NULL  ||  words == NULL  ||  channel < 0  ||  channel >= b->n_ch)
+    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->c, channel))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (preset_of(words[V18_MODE]) < 0  ||  words[kV18Words + kFskTxWords + FS_SPAN] != b->span
         ||  words[V18_Q_IPTR] < 0  ||  words[V18_Q_IPTR] >= kV18Ring  ||  words[V18_Q_OPTR] < 0  ||  words[V18_Q_OPTR] >= kV18Ring
         ||  words[kV18Words + kFskTxWords + FS_BUF_PTR] < 0  ||  words[kV18Words + kFskTxWords + FS_BUF_PTR] >= b->span
         ||  words[kV18Words + FT_BAUD_RATE] <= 0  ||  words[kV18Words + FT_BAUD_RATE] > kFtxBaudUnit)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "not the words of a channel of this bank");
-    return rw_words(b, channel, const_cast<int32_t *>(words), true);
+    return core_rw_words(&b->c, channel, 0, b->c.words, const_cast<int32_t *>(words), true);
 }
 
 static int edit(spangpu_v18_s *b, int channel, int what, int a)
 {
-    int32_t *w = (int32_t *) malloc((size_t) b->words*sizeof(int32_t));
+    int32_t *w = (int32_t *) malloc((size_t) b->c.words*sizeof(int32_t));
     if (w == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
-    int rc = rw_words(b, channel, w, false);
+    int rc = core_rw_words(&b->c, channel, 0, b->c.words, w, false);
     if (rc == SPANGPU_OK)
     {
         if (what == 0)
         {
-            modem_words(w, b->words, a);
+            modem_words(w, b->c.words, a);
         }
         else
         {
@@ -579,7 +447,7 @@ static int edit(spangpu_v18_s *b, int channel, int what, int a)
                 w[V18_RX_SUPPRESSION] = (w[V18_RX_SUPPRESSION] > a)  ?  (w[V18_RX_SUPPRESSION] - a)  :  0;
             spangpu_fsk_words_fillin(w + kV18Words + kFskTxWords, a);
         }
-        rc = rw_words(b, channel, w, true);
+        rc = core_rw_words(&b->c, channel, 0, b->c.words, w, true);
     }
     free(w);
     return rc;
@@ -587,7 +455,7 @@ static int edit(spangpu_v18_s *b, int channel, int what, int a)
 
 int spangpu_v18_restart(spangpu_v18_t *b, int channel, int mode)
 {
-    if (b == NULL  ||  channel < 0  ||  channel >= b->n_ch  ||  preset_of(mode) < 0)
+    if (b == NULL  ||  !channel_ok(&b->c, channel)  ||  preset_of(mode) < 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (one of the three Weitbrecht 5-bit modes)");
     spangpu_fsk_spec_t spec;
     spangpu_fsk_preset(preset_of(mode), &spec);
@@ -597,7 +465,7 @@ int spangpu_v18_restart(spangpu_v18_t *b, int channel, int mode)
 
 int spangpu_v18_fillin(spangpu_v18_t *b, int channel, int len)
 {
-    if (b == NULL  ||  channel < 0  ||  channel >= b->n_ch  ||  len < 0)
+    if (b == NULL  ||  !channel_ok(&b->c, channel)  ||  len < 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     return edit(b, channel, 1, len);
 }
