@@ -1,4 +1,4 @@
-// bank_host.hip -- the host plumbing the sender and side-receiver banks share; see bank_host.hpp.  Host code, apart from
+// bank_host.hip -- the host plumbing the banks share; see bank_host.hpp.  Host code, apart from
 // the put kernel of the bit rings.
 
 #include <math.h>
@@ -56,7 +56,7 @@ int core_fill(BankCore *c, const int32_t *one, int lead)
     return rc;
 }
 
-int core_set_stream(BankCore *c, void *stream)
+int core_set_stream(BankCore *c, void *stream, bool fresh_if_null)
 {
     SPG_TRY(hipSetDevice(c->device));
     SPG_TRY(hipStreamSynchronize(c->stream));
@@ -64,6 +64,11 @@ int core_set_stream(BankCore *c, void *stream)
         (void) hipStreamDestroy(c->stream);
     c->stream = (hipStream_t) stream;
     c->own_stream = false;
+    if (stream == NULL  &&  fresh_if_null)
+    {
+        SPG_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        c->own_stream = true;
+    }
     return SPANGPU_OK;
 }
 

@@ -1,12 +1,20 @@
-// bank_host.hpp -- the host plumbing the sender and side-receiver banks share (txgen, modemtx, fsktx, v18, fsk, mct, sigtone
-// and awgn _api.hip): the HIP-call macro, the device check, a bank's stream and state words, the staging of a host caller's
-// frames, grow-only device scratch, the quarter sine of dds_int.c and the put side of a bit ring.  Plain structs and free
-// functions; a bank struct embeds BankCore (and PcmStage where it stages frames) and keeps only what is its own.  Nothing
-// here is exported.
+// bank_host.hpp -- the host plumbing the banks share: the HIP-call macro (every C ABI unit), the device check, a bank's stream
+// and state words, the staging of a host caller's frames, grow-only device scratch, the quarter sine of dds_int.c and the put
+// side of a bit ring.  Plain structs and free functions; a bank struct embeds BankCore (and PcmStage where it stages frames)
+// and keeps only what is its own.  Nothing here is exported.
 //
-// The one behaviour this sharing makes uniform: every sender's tx refuses more than kMaxSamples samples a call (tx_args_ok);
-// before, the tone and modem senders did not.  Everything else a family does differently is a parameter or stays at its call
-// site.
+// Who uses what.  The sender and side-receiver banks (txgen, modemtx, fsktx, v18, fsk, mct, sigtone, awgn _api.hip) and the
+// modem receiver bank (modem_api.hip) embed BankCore and PcmStage; the echo canceller bank (echo_api.hip) embeds BankCore for
+// its device, channel count and stream alone (its four-row staging is its own).  The sets of banks over several devices
+// (shard_api.hip) sit on shard_core.hpp, which holds banks of these kinds.  The tone bank (spangpu_api.hip), the feeds and the
+// primitives take SPG_TRY only: two joined streams and slot rings are another shape.
+//
+// The behaviours this sharing makes uniform:
+//  - every sender's tx refuses more than kMaxSamples samples a call (tx_args_ok); before, the tone and modem senders did not;
+//  - set_stream and sync of the modem receiver and echo canceller banks make the bank's device current first, as the core's
+//    always did; before, those two acted on whatever device the calling thread had current;
+//  - spangpu_modem_rx() refuses a row stride shorter than the call (rx_args_ok), like the other receivers.
+// Everything else a family does differently is a parameter or stays at its call site.
 
 #pragma once
 
@@ -54,7 +62,10 @@ struct BankCore
 int core_create(BankCore *c, int device, int n_channels, int words);        // the stream and the (unwritten) state
 int core_upload(BankCore *c, const int32_t *host);                          // all of st, as the caller prepared it
 int core_fill(BankCore *c, const int32_t *one, int lead = -1);             // one[0 .. lead) in every channel, zero after (-1: all)
-int core_set_stream(BankCore *c, void *stream);
+// Hands the bank to the caller's stream, after the work on the old one.  A NULL stream is stored as it is (the eight sender and
+// side-receiver banks: the caller asked for the null stream) unless fresh_if_null, where the bank makes itself a new stream
+// of its own (the modem receiver and echo canceller banks: their documented way back from a borrowed stream).
+int core_set_stream(BankCore *c, void *stream, bool fresh_if_null = false);
 int core_sync(BankCore *c);
 void core_destroy(BankCore *c);                                             // syncs first; the stream goes only if the bank made it
 // words [first, first + count) of one channel, of st or of another [..][n_ch] array of the bank's
@@ -144,6 +155,26 @@ static inline int grow(T **ptr, C *cap, C need, size_t per, hipStream_t stream)
     if (hipMalloc(ptr, (size_t) need*per*sizeof(T)) != hipSuccess)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "device scratch");
     *cap = need;
+    return SPANGPU_OK;
+}
+
+// the same for a device block and the pinned host block its contents are handed out of: one capacity, both or neither
+template <typename T, typename C>
+static inline int grow_pair(T **dev, T **pinned, C *cap, C need, size_t per, hipStream_t stream)
+{
+    if (need <= *cap)
+        return SPANGPU_OK;
+    const int rc = grow(dev, cap, need, per, stream);
+    if (rc != SPANGPU_OK)
+        return rc;
+    if (*pinned)
+        (void) hipHostFree(*pinned);
+    *pinned = NULL;
+    if (hipHostMalloc(pinned, (size_t) need*per*sizeof(T)) != hipSuccess)
+    {
+        *cap = 0;
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "pinned scratch");
+    }
     return SPANGPU_OK;
 }
 

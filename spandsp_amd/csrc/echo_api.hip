@@ -10,35 +10,18 @@
 
 #include "../../include/spangpu.h"
 #include "../../include/spangpu_refstate.h"
+#include "bank_host.hpp"
 #include "echo_dev.hpp"
 #include "echo_pair.hpp"
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define ECHO_TRY(expr)                                                                      \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
-
 struct spangpu_echo_s
 {
-    int device;
-    int n_ch;
+    BankCore c;             // device, channels, stream; st is unused (no words: the control words below are channel-major)
     int taps;
     int tpl;
     int group;              // lanes per channel: 16, 8 or 4
-    hipStream_t stream;
-    bool own_stream;
     int32_t *scal;
     int32_t *taps32;
     int16_t *taps16;
@@ -88,11 +71,11 @@ static void refresh_uniform_mode(spangpu_echo_t *e)
     if (e->uniform_mode >= 0  ||  e->d_span == nullptr)
         return;
     int h[2] = {0x7FFFFFFF, (int) 0x80000000};
-    if (hipMemcpyAsync(e->d_span, h, sizeof(h), hipMemcpyHostToDevice, e->stream) == hipSuccess)
+    if (hipMemcpyAsync(e->d_span, h, sizeof(h), hipMemcpyHostToDevice, e->c.stream) == hipSuccess)
     {
-        hipLaunchKernelGGL(echo_mode_span_kernel, dim3((e->n_ch + 255)/256), dim3(256), 0, e->stream, (const int32_t *) e->scal, e->n_ch, e->d_span);
-        if (hipMemcpyAsync(h, e->d_span, sizeof(h), hipMemcpyDeviceToHost, e->stream) == hipSuccess
-            &&  hipStreamSynchronize(e->stream) == hipSuccess  &&  h[0] == h[1])
+        hipLaunchKernelGGL(echo_mode_span_kernel, dim3((e->c.n_ch + 255)/256), dim3(256), 0, e->c.stream, (const int32_t *) e->scal, e->c.n_ch, e->d_span);
+        if (hipMemcpyAsync(h, e->d_span, sizeof(h), hipMemcpyDeviceToHost, e->c.stream) == hipSuccess
+            &&  hipStreamSynchronize(e->c.stream) == hipSuccess  &&  h[0] == h[1])
             e->uniform_mode = h[0];
         else if (h[0] > h[1])
             e->mode_dirty = true;       // the comparison did not run (a HIP error): the general kernel stays, and the next update looks again
@@ -128,14 +111,14 @@ static int echo_io_reserve(spangpu_echo_t *e, size_t samples)
     if (samples <= e->io_cap)
         return SPANGPU_OK;
     int16_t *p = nullptr;
-    const size_t bytes = (size_t) 4*e->n_ch*samples*sizeof(int16_t);
+    const size_t bytes = (size_t) 4*e->c.n_ch*samples*sizeof(int16_t);
     if (hipMalloc(&p, bytes) != hipSuccess)
     {
         (void) hipGetLastError();
         p = nullptr;
         if (e->d_io)
         {
-            (void) hipStreamSynchronize(e->stream);
+            (void) hipStreamSynchronize(e->c.stream);
             (void) hipFree(e->d_io);
             e->d_io = nullptr;
             e->io_cap = 0;
@@ -150,7 +133,7 @@ static int echo_io_reserve(spangpu_echo_t *e, size_t samples)
     }
     if (e->d_io)
     {
-        (void) hipStreamSynchronize(e->stream);
+        (void) hipStreamSynchronize(e->c.stream);
         (void) hipFree(e->d_io);
     }
     e->d_io = p;
@@ -169,28 +152,28 @@ static void echo_launch(spangpu_echo_t *e, const EchoLaunch &L)
     {
         switch (e->tpl)
         {
-        case 16: hipLaunchKernelGGL(echo_pair_kernel<16>, dim3(blocks), dim3(256), 0, e->stream, L); break;
-        case 32: hipLaunchKernelGGL(echo_pair_kernel<32>, dim3(blocks), dim3(256), 0, e->stream, L); break;
-        default: hipLaunchKernelGGL(echo_pair_kernel<64>, dim3(blocks), dim3(256), 0, e->stream, L); break;
+        case 16: hipLaunchKernelGGL(echo_pair_kernel<16>, dim3(blocks), dim3(256), 0, e->c.stream, L); break;
+        case 32: hipLaunchKernelGGL(echo_pair_kernel<32>, dim3(blocks), dim3(256), 0, e->c.stream, L); break;
+        default: hipLaunchKernelGGL(echo_pair_kernel<64>, dim3(blocks), dim3(256), 0, e->c.stream, L); break;
         }
     }
     else if (e->group == 4)
     {
         switch (e->tpl)
         {
-        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 4>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 16: hipLaunchKernelGGL((echo_bank_kernel<16, 4>), dim3(blocks), dim3(256), 0, e->stream, L); break;
+        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 4>), dim3(blocks), dim3(256), 0, e->c.stream, L);  break;
+        case 16: hipLaunchKernelGGL((echo_bank_kernel<16, 4>), dim3(blocks), dim3(256), 0, e->c.stream, L); break;
         default:
             // the kernels compiled for one mode: the three echo_tests.c runs its lines in (adaption alone is SURVEY 8(d)-5's,
             // and what a bank has until somebody changes it); any other mode, or lines of different modes: the general one
             if (e->uniform_mode == kModeAdaption)
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             else if (e->uniform_mode == (kModeAdaption | kModeNlp))
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             else if (e->uniform_mode == (kModeAdaption | kModeNlp | kModeCng))
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp | kModeCng>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4, kModeAdaption | kModeNlp | kModeCng>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             else
-                hipLaunchKernelGGL((echo_bank_kernel<32, 4>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<32, 4>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             break;
         }
     }
@@ -198,13 +181,13 @@ static void echo_launch(spangpu_echo_t *e, const EchoLaunch &L)
     {
         switch (e->tpl)
         {
-        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 8>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 8>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 8>), dim3(blocks), dim3(256), 0, e->c.stream, L);  break;
+        case 8:  hipLaunchKernelGGL((echo_bank_kernel<8, 8>), dim3(blocks), dim3(256), 0, e->c.stream, L);  break;
         default:
             if (e->uniform_mode == kModeAdaption)
-                hipLaunchKernelGGL((echo_bank_kernel<16, 8, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<16, 8, kModeAdaption>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             else
-                hipLaunchKernelGGL((echo_bank_kernel<16, 8>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<16, 8>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             break;
         }
     }
@@ -212,17 +195,17 @@ static void echo_launch(spangpu_echo_t *e, const EchoLaunch &L)
     {
         switch (e->tpl)
         {
-        case 2:  hipLaunchKernelGGL((echo_bank_kernel<2, 16>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
-        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 16>), dim3(blocks), dim3(256), 0, e->stream, L);  break;
+        case 2:  hipLaunchKernelGGL((echo_bank_kernel<2, 16>), dim3(blocks), dim3(256), 0, e->c.stream, L);  break;
+        case 4:  hipLaunchKernelGGL((echo_bank_kernel<4, 16>), dim3(blocks), dim3(256), 0, e->c.stream, L);  break;
         case 8:
             if (e->uniform_mode == kModeAdaption)
-                hipLaunchKernelGGL((echo_bank_kernel<8, 16, kModeAdaption>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<8, 16, kModeAdaption>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             else
-                hipLaunchKernelGGL((echo_bank_kernel<8, 16>), dim3(blocks), dim3(256), 0, e->stream, L);
+                hipLaunchKernelGGL((echo_bank_kernel<8, 16>), dim3(blocks), dim3(256), 0, e->c.stream, L);
             break;
-        case 32: hipLaunchKernelGGL((echo_bank_kernel<32, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
-        case 64: hipLaunchKernelGGL((echo_bank_kernel<64, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
-        default: hipLaunchKernelGGL((echo_bank_kernel<16, 16>), dim3(blocks), dim3(256), 0, e->stream, L); break;
+        case 32: hipLaunchKernelGGL((echo_bank_kernel<32, 16>), dim3(blocks), dim3(256), 0, e->c.stream, L); break;
+        case 64: hipLaunchKernelGGL((echo_bank_kernel<64, 16>), dim3(blocks), dim3(256), 0, e->c.stream, L); break;
+        default: hipLaunchKernelGGL((echo_bank_kernel<16, 16>), dim3(blocks), dim3(256), 0, e->c.stream, L); break;
         }
     }
 }
@@ -245,16 +228,12 @@ int spangpu_echo_create(spangpu_echo_t **out, int device, int n_channels, int ta
     *out = nullptr;
     if (taps != 32  &&  taps != 64  &&  taps != 128  &&  taps != 256  &&  taps != 512  &&  taps != 1024)
         return spangpu_set_error(SPANGPU_ERR_UNSUPPORTED, "echo canceller length must be 32, 64, 128, 256, 512 or 1024 taps");
-    if (spangpu_device_count() <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= spangpu_device_count())
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    ECHO_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_echo_t *e = (spangpu_echo_t *) calloc(1, sizeof(*e));
     if (e == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    e->device = device;
-    e->n_ch = n_channels;
     e->taps = taps;
     // Lanes per channel.  The scalar control of echo_can_update() is replicated in a channel's lanes, so the fewer lanes a
     // channel has the more channels share each control instruction; a small bank wants the opposite -- more,
@@ -286,12 +265,11 @@ int spangpu_echo_create(spangpu_echo_t **out, int device, int n_channels, int ta
     if (e->group == 8  &&  (taps/8 < 2  ||  taps/8 > 16))
         e->group = 16;
     e->tpl = taps/e->group;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
+    if ((rc = core_create(&e->c, device, n_channels, 0)) != SPANGPU_OK)
     {
-        free(e);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
+        spangpu_echo_destroy(e);
+        return rc;
     }
-    e->own_stream = true;
     const size_t n = (size_t) n_channels;
     if (hipMalloc(&e->scal, n*kEchoScalars*sizeof(int32_t)) != hipSuccess
         ||  hipMalloc(&e->taps32, n*taps*sizeof(int32_t)) != hipSuccess
@@ -302,9 +280,9 @@ int spangpu_echo_create(spangpu_echo_t **out, int device, int n_channels, int ta
         spangpu_echo_destroy(e);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "hipMalloc of echo state failed");
     }
-    (void) hipMemsetAsync(e->taps32, 0, n*taps*sizeof(int32_t), e->stream);
-    (void) hipMemsetAsync(e->taps16, 0, n*4*taps*sizeof(int16_t), e->stream);
-    (void) hipMemsetAsync(e->hist, 0, n*taps*sizeof(int16_t), e->stream);
+    (void) hipMemsetAsync(e->taps32, 0, n*taps*sizeof(int32_t), e->c.stream);
+    (void) hipMemsetAsync(e->taps16, 0, n*4*taps*sizeof(int16_t), e->c.stream);
+    (void) hipMemsetAsync(e->hist, 0, n*taps*sizeof(int16_t), e->c.stream);
     int32_t *h = (int32_t *) malloc(n*kEchoScalars*sizeof(int32_t));
     if (h == nullptr)
     {
@@ -314,10 +292,10 @@ int spangpu_echo_create(spangpu_echo_t **out, int device, int n_channels, int ta
     for (size_t c = 0;  c < n;  c++)
         init_scalars(h + c*kEchoScalars, taps, adaption_mode);
     e->uniform_mode = adaption_mode;
-    hipError_t rc = hipMemcpyAsync(e->scal, h, n*kEchoScalars*sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    (void) hipStreamSynchronize(e->stream);
+    const hipError_t up = hipMemcpyAsync(e->scal, h, n*kEchoScalars*sizeof(int32_t), hipMemcpyHostToDevice, e->c.stream);
+    (void) hipStreamSynchronize(e->c.stream);
     free(h);
-    if (rc != hipSuccess)
+    if (up != hipSuccess)
     {
         spangpu_echo_destroy(e);
         return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
@@ -330,9 +308,7 @@ int spangpu_echo_destroy(spangpu_echo_t *e)
 {
     if (e == nullptr)
         return SPANGPU_OK;
-    (void) hipSetDevice(e->device);
-    if (e->stream)
-        (void) hipStreamSynchronize(e->stream);
+    core_destroy(&e->c);
     if (e->scal) (void) hipFree(e->scal);
     if (e->taps32) (void) hipFree(e->taps32);
     if (e->taps16) (void) hipFree(e->taps16);
@@ -345,45 +321,29 @@ int spangpu_echo_destroy(spangpu_echo_t *e)
     if (e->h_io) (void) hipHostFree(e->h_io);
     free(e->h_chan);
     free(e->h_off);
-    if (e->own_stream  &&  e->stream)
-        (void) hipStreamDestroy(e->stream);
     free(e);
     return SPANGPU_OK;
 }
 
-int spangpu_echo_channels(const spangpu_echo_t *e) { return e  ?  e->n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_echo_channels(const spangpu_echo_t *e) { return e  ?  e->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 int spangpu_echo_taps(const spangpu_echo_t *e) { return e  ?  e->taps  :  SPANGPU_ERR_BAD_ARG; }
 int spangpu_echo_lanes_per_channel(const spangpu_echo_t *e) { return e  ?  e->group  :  SPANGPU_ERR_BAD_ARG; }
 
-void *spangpu_echo_get_stream(spangpu_echo_t *e) { return e  ?  (void *) e->stream  :  nullptr; }
-int spangpu_echo_device(const spangpu_echo_t *e) { return e  ?  e->device  :  SPANGPU_ERR_BAD_ARG; }
+void *spangpu_echo_get_stream(spangpu_echo_t *e) { return e  ?  (void *) e->c.stream  :  nullptr; }
+int spangpu_echo_device(const spangpu_echo_t *e) { return e  ?  e->c.device  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_echo_set_stream(spangpu_echo_t *e, void *hip_stream)
 {
     if (e == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    (void) hipStreamSynchronize(e->stream);
-    if (e->own_stream)
-        (void) hipStreamDestroy(e->stream);
-    if (hip_stream)
-    {
-        e->stream = (hipStream_t) hip_stream;
-        e->own_stream = false;
-    }
-    else
-    {
-        ECHO_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-        e->own_stream = true;
-    }
-    return SPANGPU_OK;
+    return core_set_stream(&e->c, hip_stream, true);       // NULL: a fresh stream of the bank's own
 }
 
 int spangpu_echo_sync(spangpu_echo_t *e)
 {
     if (e == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    ECHO_TRY(hipStreamSynchronize(e->stream));
-    return SPANGPU_OK;
+    return core_sync(&e->c);
 }
 
 int spangpu_echo_update(spangpu_echo_t *e, const int16_t *tx, const int16_t *rx, int16_t *clean,
@@ -401,7 +361,7 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
         return 0;
     if (stride <= 0)
         stride = samples;
-    ECHO_TRY(hipSetDevice(e->device));
+    SPG_TRY(hipSetDevice(e->c.device));
     EchoLaunch L;
     memset(&L, 0, sizeof(L));
     if (mem == SPANGPU_MEM_HOST)
@@ -409,16 +369,16 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
         if (echo_io_reserve(e, (size_t) samples) != SPANGPU_OK)
             return SPANGPU_ERR_NO_MEMORY;
         int16_t *dtx = e->d_io;
-        int16_t *drx = e->d_io + (size_t) e->n_ch*e->io_cap;
-        int16_t *dcl = e->d_io + (size_t) 2*e->n_ch*e->io_cap;
-        ECHO_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), tx, stride*sizeof(int16_t), samples*sizeof(int16_t),
-                                  e->n_ch, hipMemcpyHostToDevice, e->stream));
-        ECHO_TRY(hipMemcpy2DAsync(drx, e->io_cap*sizeof(int16_t), rx, stride*sizeof(int16_t), samples*sizeof(int16_t),
-                                  e->n_ch, hipMemcpyHostToDevice, e->stream));
+        int16_t *drx = e->d_io + (size_t) e->c.n_ch*e->io_cap;
+        int16_t *dcl = e->d_io + (size_t) 2*e->c.n_ch*e->io_cap;
+        SPG_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), tx, stride*sizeof(int16_t), samples*sizeof(int16_t),
+                                  e->c.n_ch, hipMemcpyHostToDevice, e->c.stream));
+        SPG_TRY(hipMemcpy2DAsync(drx, e->io_cap*sizeof(int16_t), rx, stride*sizeof(int16_t), samples*sizeof(int16_t),
+                                  e->c.n_ch, hipMemcpyHostToDevice, e->c.stream));
         L.tx = dtx;
         L.rx = drx;
         L.clean = dcl;
-        L.tx_out = tx_out  ?  (e->d_io + (size_t) 3*e->n_ch*e->io_cap)  :  nullptr;
+        L.tx_out = tx_out  ?  (e->d_io + (size_t) 3*e->c.n_ch*e->io_cap)  :  nullptr;
         L.stride = (long long) e->io_cap;
     }
     else if (mem == SPANGPU_MEM_DEVICE)
@@ -436,7 +396,7 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
     if (e->mode_dirty)
         refresh_uniform_mode(e);
     L.samples = samples;
-    L.n_ch = e->n_ch;
+    L.n_ch = e->c.n_ch;
     L.use_hpf_tx = use_hpf_tx;
     L.scal = e->scal;
     L.taps32 = e->taps32;
@@ -444,21 +404,21 @@ int spangpu_echo_update_tx(spangpu_echo_t *e, const int16_t *tx, const int16_t *
     L.hist = e->hist;
     L.stats = (e->stats_on == 2)  ?  e->stats  :  nullptr;
     echo_launch(e, L);
-    ECHO_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (e->stats_on == 1)
     {
-        hipLaunchKernelGGL(echo_stats_kernel, dim3((e->n_ch + 255)/256), dim3(256), 0, e->stream,
-                           L.rx, (const int16_t *) L.clean, L.stride, samples, e->n_ch, e->stats, (const int32_t *) nullptr, 0);
-        ECHO_TRY(hipGetLastError());
+        hipLaunchKernelGGL(echo_stats_kernel, dim3((e->c.n_ch + 255)/256), dim3(256), 0, e->c.stream,
+                           L.rx, (const int16_t *) L.clean, L.stride, samples, e->c.n_ch, e->stats, (const int32_t *) nullptr, 0);
+        SPG_TRY(hipGetLastError());
     }
     if (mem == SPANGPU_MEM_HOST)
     {
-        ECHO_TRY(hipMemcpy2DAsync(clean, stride*sizeof(int16_t), L.clean, e->io_cap*sizeof(int16_t), samples*sizeof(int16_t),
-                                  e->n_ch, hipMemcpyDeviceToHost, e->stream));
+        SPG_TRY(hipMemcpy2DAsync(clean, stride*sizeof(int16_t), L.clean, e->io_cap*sizeof(int16_t), samples*sizeof(int16_t),
+                                  e->c.n_ch, hipMemcpyDeviceToHost, e->c.stream));
         if (tx_out)
-            ECHO_TRY(hipMemcpy2DAsync(tx_out, stride*sizeof(int16_t), L.tx_out, e->io_cap*sizeof(int16_t), samples*sizeof(int16_t),
-                                      e->n_ch, hipMemcpyDeviceToHost, e->stream));
-        ECHO_TRY(hipStreamSynchronize(e->stream));
+            SPG_TRY(hipMemcpy2DAsync(tx_out, stride*sizeof(int16_t), L.tx_out, e->io_cap*sizeof(int16_t), samples*sizeof(int16_t),
+                                      e->c.n_ch, hipMemcpyDeviceToHost, e->c.stream));
+        SPG_TRY(hipStreamSynchronize(e->c.stream));
     }
     return 0;
 }
@@ -476,7 +436,7 @@ int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t 
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
     if (stride <= 0)
         stride = max_samples;
-    const int N = e->n_ch;
+    const int N = e->c.n_ch;
     int taking_part = 0;
     int longest = 0;
     bool in_step = true;
@@ -503,7 +463,7 @@ int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t 
     }
     if (stride < longest)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "rows overlap: stride is shorter than a channel's length");
-    ECHO_TRY(hipSetDevice(e->device));
+    SPG_TRY(hipSetDevice(e->c.device));
     // ---- the lists: a counting sort of the channels by key = 2*samples + flag, channel order kept within a key ----------
     const size_t n_keys = (size_t) 2*(longest + 1);
     auto key_of = [&](int c) { return 2*lens[c] + ((use_hpf_tx  &&  use_hpf_tx[c])  ?  1  :  0); };
@@ -547,7 +507,7 @@ int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t 
             }
             if (e->h_io)
             {
-                (void) hipStreamSynchronize(e->stream);
+                (void) hipStreamSynchronize(e->c.stream);
                 (void) hipHostFree(e->h_io);
             }
             e->h_io = p;
@@ -579,7 +539,7 @@ int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t 
             off[k] = off[k - 1];
         off[0] = 0;
     }
-    ECHO_TRY(hipMemcpyAsync(e->d_chan, e->h_chan, (size_t) taking_part*sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    SPG_TRY(hipMemcpyAsync(e->d_chan, e->h_chan, (size_t) taking_part*sizeof(int32_t), hipMemcpyHostToDevice, e->c.stream));
     int16_t *dtx = nullptr;
     int16_t *drx = nullptr;
     int16_t *dcl = nullptr;
@@ -591,10 +551,10 @@ int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t 
         drx = e->d_io + (size_t) N*e->io_cap;
         dcl = e->d_io + (size_t) 2*N*e->io_cap;
         dto = e->d_io + (size_t) 3*N*e->io_cap;
-        ECHO_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), htx, cap*sizeof(int16_t), longest*sizeof(int16_t),
-                                  taking_part, hipMemcpyHostToDevice, e->stream));
-        ECHO_TRY(hipMemcpy2DAsync(drx, e->io_cap*sizeof(int16_t), hrx, cap*sizeof(int16_t), longest*sizeof(int16_t),
-                                  taking_part, hipMemcpyHostToDevice, e->stream));
+        SPG_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), htx, cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                  taking_part, hipMemcpyHostToDevice, e->c.stream));
+        SPG_TRY(hipMemcpy2DAsync(drx, e->io_cap*sizeof(int16_t), hrx, cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                  taking_part, hipMemcpyHostToDevice, e->c.stream));
     }
     if (e->mode_dirty)
         refresh_uniform_mode(e);
@@ -635,22 +595,22 @@ int spangpu_echo_update_var(spangpu_echo_t *e, const int16_t *tx, const int16_t 
         L.hist = e->hist;
         L.stats = (e->stats_on == 2)  ?  e->stats  :  nullptr;
         echo_launch(e, L);
-        ECHO_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
         if (e->stats_on == 1)
         {
-            hipLaunchKernelGGL(echo_stats_kernel, dim3((n + 255)/256), dim3(256), 0, e->stream,
+            hipLaunchKernelGGL(echo_stats_kernel, dim3((n + 255)/256), dim3(256), 0, e->c.stream,
                                L.rx, (const int16_t *) L.clean, L.stride, L.samples, n, e->stats, L.chan, L.chan_rows);
-            ECHO_TRY(hipGetLastError());
+            SPG_TRY(hipGetLastError());
         }
     }
     if (mem == SPANGPU_MEM_HOST)
     {
-        ECHO_TRY(hipMemcpy2DAsync(hcl, cap*sizeof(int16_t), dcl, e->io_cap*sizeof(int16_t), longest*sizeof(int16_t),
-                                  taking_part, hipMemcpyDeviceToHost, e->stream));
+        SPG_TRY(hipMemcpy2DAsync(hcl, cap*sizeof(int16_t), dcl, e->io_cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                  taking_part, hipMemcpyDeviceToHost, e->c.stream));
         if (tx_out)
-            ECHO_TRY(hipMemcpy2DAsync(hto, cap*sizeof(int16_t), dto, e->io_cap*sizeof(int16_t), longest*sizeof(int16_t),
-                                      taking_part, hipMemcpyDeviceToHost, e->stream));
-        ECHO_TRY(hipStreamSynchronize(e->stream));
+            SPG_TRY(hipMemcpy2DAsync(hto, cap*sizeof(int16_t), dto, e->io_cap*sizeof(int16_t), longest*sizeof(int16_t),
+                                      taking_part, hipMemcpyDeviceToHost, e->c.stream));
+        SPG_TRY(hipStreamSynchronize(e->c.stream));
         for (int slot = 0;  slot < taking_part;  slot++)
         {
             const int c = e->h_chan[slot];
@@ -672,19 +632,19 @@ int spangpu_echo_hpf_tx(spangpu_echo_t *e, const int16_t *tx, int16_t *out, int 
         return 0;
     if (stride <= 0)
         stride = samples;
-    ECHO_TRY(hipSetDevice(e->device));
+    SPG_TRY(hipSetDevice(e->c.device));
     if (echo_io_reserve(e, (size_t) samples) != SPANGPU_OK)
         return SPANGPU_ERR_NO_MEMORY;
     int16_t *dtx = e->d_io;
-    int16_t *dout = e->d_io + (size_t) 3*e->n_ch*e->io_cap;
-    ECHO_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), tx, stride*sizeof(int16_t), samples*sizeof(int16_t),
-                              e->n_ch, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(echo_hpf_tx_kernel, dim3((e->n_ch + 63)/64), dim3(64), 0, e->stream, dtx, dout, (long long) e->io_cap,
-                       samples, e->n_ch, e->scal);
-    ECHO_TRY(hipGetLastError());
-    ECHO_TRY(hipMemcpy2DAsync(out, stride*sizeof(int16_t), dout, e->io_cap*sizeof(int16_t), samples*sizeof(int16_t),
-                              e->n_ch, hipMemcpyDeviceToHost, e->stream));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    int16_t *dout = e->d_io + (size_t) 3*e->c.n_ch*e->io_cap;
+    SPG_TRY(hipMemcpy2DAsync(dtx, e->io_cap*sizeof(int16_t), tx, stride*sizeof(int16_t), samples*sizeof(int16_t),
+                              e->c.n_ch, hipMemcpyHostToDevice, e->c.stream));
+    hipLaunchKernelGGL(echo_hpf_tx_kernel, dim3((e->c.n_ch + 63)/64), dim3(64), 0, e->c.stream, dtx, dout, (long long) e->io_cap,
+                       samples, e->c.n_ch, e->scal);
+    SPG_TRY(hipGetLastError());
+    SPG_TRY(hipMemcpy2DAsync(out, stride*sizeof(int16_t), dout, e->io_cap*sizeof(int16_t), samples*sizeof(int16_t),
+                              e->c.n_ch, hipMemcpyDeviceToHost, e->c.stream));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     return 0;
 }
 
@@ -693,23 +653,23 @@ int spangpu_echo_hpf_tx(spangpu_echo_t *e, const int16_t *tx, int16_t *out, int 
 // history in its physical (circular) order.
 int spangpu_echo_get_state(spangpu_echo_t *e, int channel, int32_t *scal, int32_t *taps32, int16_t *taps16, int16_t *history)
 {
-    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch)
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    ECHO_TRY(hipSetDevice(e->device));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipSetDevice(e->c.device));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     const int T = e->taps;
     int32_t s[kEchoScalars];
-    ECHO_TRY(hipMemcpy(s, e->scal + (size_t) channel*kEchoScalars, sizeof(s), hipMemcpyDeviceToHost));
+    SPG_TRY(hipMemcpy(s, e->scal + (size_t) channel*kEchoScalars, sizeof(s), hipMemcpyDeviceToHost));
     if (scal)
         memcpy(scal, s, sizeof(s));
     if (taps32)
-        ECHO_TRY(hipMemcpy(taps32, e->taps32 + (size_t) channel*T, T*sizeof(int32_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(taps32, e->taps32 + (size_t) channel*T, T*sizeof(int32_t), hipMemcpyDeviceToHost));
     if (taps16)
-        ECHO_TRY(hipMemcpy(taps16, e->taps16 + (size_t) channel*4*T, 4*T*sizeof(int16_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(taps16, e->taps16 + (size_t) channel*4*T, 4*T*sizeof(int16_t), hipMemcpyDeviceToHost));
     if (history)
     {
         int16_t w[1024];
-        ECHO_TRY(hipMemcpy(w, e->hist + (size_t) channel*T, T*sizeof(int16_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(w, e->hist + (size_t) channel*T, T*sizeof(int16_t), hipMemcpyDeviceToHost));
         // window order -> physical order: w[i] = history[(i + curr_pos + 1) mod T]
         for (int i = 0;  i < T;  i++)
             history[(i + s[ES_CURR_POS] + 1)%T] = w[i];
@@ -719,30 +679,30 @@ int spangpu_echo_get_state(spangpu_echo_t *e, int channel, int32_t *scal, int32_
 
 int spangpu_echo_set_state(spangpu_echo_t *e, int channel, const int32_t *scal, const int32_t *taps32, const int16_t *taps16, const int16_t *history)
 {
-    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch  ||  scal == nullptr)
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch  ||  scal == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    ECHO_TRY(hipSetDevice(e->device));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipSetDevice(e->c.device));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     const int T = e->taps;
     // (the kernels derive every sample's position from this word with & (T - 1): echo_dev.hpp)
     if (scal[ES_CURR_POS] < 0  ||  scal[ES_CURR_POS] >= T)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "curr_pos outside 0 .. taps - 1");
     e->mode_dirty = true;
-    if (scal[ES_ADAPTION_MODE] != e->uniform_mode  &&  e->n_ch > 1)
+    if (scal[ES_ADAPTION_MODE] != e->uniform_mode  &&  e->c.n_ch > 1)
         e->uniform_mode = -1;
     else
         e->uniform_mode = scal[ES_ADAPTION_MODE];
-    ECHO_TRY(hipMemcpy(e->scal + (size_t) channel*kEchoScalars, scal, kEchoScalars*sizeof(int32_t), hipMemcpyHostToDevice));
+    SPG_TRY(hipMemcpy(e->scal + (size_t) channel*kEchoScalars, scal, kEchoScalars*sizeof(int32_t), hipMemcpyHostToDevice));
     if (taps32)
-        ECHO_TRY(hipMemcpy(e->taps32 + (size_t) channel*T, taps32, T*sizeof(int32_t), hipMemcpyHostToDevice));
+        SPG_TRY(hipMemcpy(e->taps32 + (size_t) channel*T, taps32, T*sizeof(int32_t), hipMemcpyHostToDevice));
     if (taps16)
-        ECHO_TRY(hipMemcpy(e->taps16 + (size_t) channel*4*T, taps16, 4*T*sizeof(int16_t), hipMemcpyHostToDevice));
+        SPG_TRY(hipMemcpy(e->taps16 + (size_t) channel*4*T, taps16, 4*T*sizeof(int16_t), hipMemcpyHostToDevice));
     if (history)
     {
         int16_t w[1024];
         for (int i = 0;  i < T;  i++)
             w[i] = history[(i + scal[ES_CURR_POS] + 1)%T];
-        ECHO_TRY(hipMemcpy(e->hist + (size_t) channel*T, w, T*sizeof(int16_t), hipMemcpyHostToDevice));
+        SPG_TRY(hipMemcpy(e->hist + (size_t) channel*T, w, T*sizeof(int16_t), hipMemcpyHostToDevice));
     }
     return SPANGPU_OK;
 }
@@ -796,7 +756,7 @@ static void echo_words_from_ref(const spangpu_ref_echo_can_t *ec, int32_t *s)
 
 int spangpu_echo_import_state(spangpu_echo_t *e, int channel, const spangpu_ref_echo_can_t *ec)
 {
-    if (e == nullptr  ||  ec == nullptr  ||  channel < 0  ||  channel >= e->n_ch)
+    if (e == nullptr  ||  ec == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (ec->taps != e->taps  ||  ec->fir_taps32 == nullptr  ||  ec->fir_state.history == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "the canceller is of another length than the bank, or has no arrays");
@@ -820,7 +780,7 @@ int spangpu_echo_import_state(spangpu_echo_t *e, int channel, const spangpu_ref_
 
 int spangpu_echo_export_state(spangpu_echo_t *e, int channel, spangpu_ref_echo_can_t *ec)
 {
-    if (e == nullptr  ||  ec == nullptr  ||  channel < 0  ||  channel >= e->n_ch)
+    if (e == nullptr  ||  ec == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (ec->taps != e->taps  ||  ec->fir_taps32 == nullptr  ||  ec->fir_state.history == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "the canceller is of another length than the bank, or has no arrays");
@@ -887,11 +847,11 @@ int spangpu_echo_stats(spangpu_echo_t *e, int enable)
 {
     if (e == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    ECHO_TRY(hipSetDevice(e->device));
+    SPG_TRY(hipSetDevice(e->c.device));
     if (enable  &&  e->stats == nullptr)
     {
-        ECHO_TRY(hipMalloc(&e->stats, (size_t) e->n_ch*sizeof(EchoStats)));
-        ECHO_TRY(hipMemsetAsync(e->stats, 0, (size_t) e->n_ch*sizeof(EchoStats), e->stream));
+        SPG_TRY(hipMalloc(&e->stats, (size_t) e->c.n_ch*sizeof(EchoStats)));
+        SPG_TRY(hipMemsetAsync(e->stats, 0, (size_t) e->c.n_ch*sizeof(EchoStats), e->c.stream));
     }
     e->stats_on = (enable == 2)  ?  2  :  (enable != 0)  ?  1  :  0;
     return SPANGPU_OK;
@@ -916,9 +876,9 @@ int spangpu_echo_stats_reset(spangpu_echo_t *e, int what)
 {
     if (e == nullptr  ||  e->stats == nullptr)
         return spangpu_set_error(SPANGPU_ERR_STATE, "statistics are not enabled on this bank");
-    ECHO_TRY(hipSetDevice(e->device));
-    hipLaunchKernelGGL(echo_stats_reset_kernel, dim3((e->n_ch + 255)/256), dim3(256), 0, e->stream, e->stats, e->n_ch, what);
-    ECHO_TRY(hipGetLastError());
+    SPG_TRY(hipSetDevice(e->c.device));
+    hipLaunchKernelGGL(echo_stats_reset_kernel, dim3((e->c.n_ch + 255)/256), dim3(256), 0, e->c.stream, e->stats, e->c.n_ch, what);
+    SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
 
@@ -926,12 +886,12 @@ int spangpu_echo_stats_get(spangpu_echo_t *e, int first, int n, spangpu_echo_sta
 {
     if (e == nullptr  ||  e->stats == nullptr)
         return spangpu_set_error(SPANGPU_ERR_STATE, "statistics are not enabled on this bank");
-    if (out == nullptr  ||  first < 0  ||  n < 0  ||  first + n > e->n_ch)
+    if (out == nullptr  ||  first < 0  ||  n < 0  ||  first + n > e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     static_assert(sizeof(spangpu_echo_stats_t) == sizeof(EchoStats), "ABI struct and device struct are the same record");
-    ECHO_TRY(hipSetDevice(e->device));
-    ECHO_TRY(hipMemcpyAsync(out, e->stats + first, (size_t) n*sizeof(EchoStats), hipMemcpyDeviceToHost, e->stream));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipSetDevice(e->c.device));
+    SPG_TRY(hipMemcpyAsync(out, e->stats + first, (size_t) n*sizeof(EchoStats), hipMemcpyDeviceToHost, e->c.stream));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     return SPANGPU_OK;
 }
 
@@ -941,54 +901,54 @@ int spangpu_echo_erle(spangpu_echo_t *e, float *erle_db, int mem)
         return spangpu_set_error(SPANGPU_ERR_STATE, "statistics are not enabled on this bank");
     if (erle_db == nullptr  ||  (mem != SPANGPU_MEM_HOST  &&  mem != SPANGPU_MEM_DEVICE))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    ECHO_TRY(hipSetDevice(e->device));
+    SPG_TRY(hipSetDevice(e->c.device));
     float *dst = erle_db;
     if (mem == SPANGPU_MEM_HOST)
     {
         if (e->d_erle == nullptr)
-            ECHO_TRY(hipMalloc(&e->d_erle, (size_t) e->n_ch*sizeof(float)));
+            SPG_TRY(hipMalloc(&e->d_erle, (size_t) e->c.n_ch*sizeof(float)));
         dst = e->d_erle;
     }
-    hipLaunchKernelGGL(echo_erle_kernel, dim3((e->n_ch + 255)/256), dim3(256), 0, e->stream, (const EchoStats *) e->stats, dst, e->n_ch);
-    ECHO_TRY(hipGetLastError());
+    hipLaunchKernelGGL(echo_erle_kernel, dim3((e->c.n_ch + 255)/256), dim3(256), 0, e->c.stream, (const EchoStats *) e->stats, dst, e->c.n_ch);
+    SPG_TRY(hipGetLastError());
     if (mem == SPANGPU_MEM_HOST)
     {
-        ECHO_TRY(hipMemcpyAsync(erle_db, dst, (size_t) e->n_ch*sizeof(float), hipMemcpyDeviceToHost, e->stream));
-        ECHO_TRY(hipStreamSynchronize(e->stream));
+        SPG_TRY(hipMemcpyAsync(erle_db, dst, (size_t) e->c.n_ch*sizeof(float), hipMemcpyDeviceToHost, e->c.stream));
+        SPG_TRY(hipStreamSynchronize(e->c.stream));
     }
     return SPANGPU_OK;
 }
 
 int spangpu_echo_adaption_mode(spangpu_echo_t *e, int channel, int adaption_mode)
 {
-    if (e == nullptr  ||  channel >= e->n_ch)
+    if (e == nullptr  ||  channel >= e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    ECHO_TRY(hipSetDevice(e->device));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipSetDevice(e->c.device));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     const int lo = (channel < 0)  ?  0  :  channel;
-    const int hi = (channel < 0)  ?  e->n_ch  :  (channel + 1);
-    if (hi - lo == e->n_ch)
+    const int hi = (channel < 0)  ?  e->c.n_ch  :  (channel + 1);
+    if (hi - lo == e->c.n_ch)
         e->uniform_mode = adaption_mode;
     else if (adaption_mode != e->uniform_mode)
         e->uniform_mode = -1;
-    e->mode_dirty = (hi - lo != e->n_ch);
-    hipLaunchKernelGGL(echo_set_scalar_kernel, dim3((hi - lo + 255)/256), dim3(256), 0, e->stream,
+    e->mode_dirty = (hi - lo != e->c.n_ch);
+    hipLaunchKernelGGL(echo_set_scalar_kernel, dim3((hi - lo + 255)/256), dim3(256), 0, e->c.stream,
                        e->scal, lo, hi, (int) ES_ADAPTION_MODE, adaption_mode);
-    ECHO_TRY(hipGetLastError());
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipGetLastError());
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     return SPANGPU_OK;
 }
 
 // echo_can_flush(), echo.c:331-372
 int spangpu_echo_flush(spangpu_echo_t *e, int channel)
 {
-    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch)
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    ECHO_TRY(hipSetDevice(e->device));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipSetDevice(e->c.device));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     const int T = e->taps;
     int32_t s[kEchoScalars];
-    ECHO_TRY(hipMemcpy(s, e->scal + (size_t) channel*kEchoScalars, sizeof(s), hipMemcpyDeviceToHost));
+    SPG_TRY(hipMemcpy(s, e->scal + (size_t) channel*kEchoScalars, sizeof(s), hipMemcpyDeviceToHost));
     s[ES_TX_POWER0] = s[ES_TX_POWER1] = s[ES_TX_POWER2] = s[ES_TX_POWER3] = 0;
     s[ES_RX_POWER0] = s[ES_RX_POWER1] = s[ES_RX_POWER2] = 0;
     s[ES_CLEAN_RX_POWER] = 0;
@@ -1008,31 +968,31 @@ int spangpu_echo_flush(spangpu_echo_t *e, int channel)
         s[ES_LAST_ACF + i] = 0;
     s[ES_NARROWBAND_COUNT] = 0;
     s[ES_NARROWBAND_SCORE] = 0;
-    ECHO_TRY(hipMemcpy(e->scal + (size_t) channel*kEchoScalars, s, sizeof(s), hipMemcpyHostToDevice));
-    ECHO_TRY(hipMemset(e->taps32 + (size_t) channel*T, 0, T*sizeof(int32_t)));
-    ECHO_TRY(hipMemset(e->taps16 + (size_t) channel*4*T, 0, 4*T*sizeof(int16_t)));
-    ECHO_TRY(hipMemset(e->hist + (size_t) channel*T, 0, T*sizeof(int16_t)));
+    SPG_TRY(hipMemcpy(e->scal + (size_t) channel*kEchoScalars, s, sizeof(s), hipMemcpyHostToDevice));
+    SPG_TRY(hipMemset(e->taps32 + (size_t) channel*T, 0, T*sizeof(int32_t)));
+    SPG_TRY(hipMemset(e->taps16 + (size_t) channel*4*T, 0, 4*T*sizeof(int16_t)));
+    SPG_TRY(hipMemset(e->hist + (size_t) channel*T, 0, T*sizeof(int16_t)));
     return SPANGPU_OK;
 }
 
 // echo_can_hpf_tx() for one channel of the bank (host buffers; out may alias tx): an object attached to an echo group
 int spangpu_echo_hpf_tx_channel(spangpu_echo_t *e, int channel, const int16_t *tx, int16_t *out, int samples)
 {
-    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch  ||  tx == nullptr  ||  out == nullptr  ||  samples < 0)
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch  ||  tx == nullptr  ||  out == nullptr  ||  samples < 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (samples == 0)
         return 0;
-    ECHO_TRY(hipSetDevice(e->device));
+    SPG_TRY(hipSetDevice(e->c.device));
     if (echo_io_reserve(e, (size_t) samples) != SPANGPU_OK)
         return SPANGPU_ERR_NO_MEMORY;
     int16_t *dtx = e->d_io;
-    int16_t *dout = e->d_io + (size_t) 3*e->n_ch*e->io_cap;
-    ECHO_TRY(hipMemcpyAsync(dtx, tx, samples*sizeof(int16_t), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(echo_hpf_tx_kernel, dim3(1), dim3(64), 0, e->stream, dtx, dout, (long long) e->io_cap,
+    int16_t *dout = e->d_io + (size_t) 3*e->c.n_ch*e->io_cap;
+    SPG_TRY(hipMemcpyAsync(dtx, tx, samples*sizeof(int16_t), hipMemcpyHostToDevice, e->c.stream));
+    hipLaunchKernelGGL(echo_hpf_tx_kernel, dim3(1), dim3(64), 0, e->c.stream, dtx, dout, (long long) e->io_cap,
                        samples, 1, e->scal + (size_t) channel*kEchoScalars);
-    ECHO_TRY(hipGetLastError());
-    ECHO_TRY(hipMemcpyAsync(out, dout, samples*sizeof(int16_t), hipMemcpyDeviceToHost, e->stream));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipGetLastError());
+    SPG_TRY(hipMemcpyAsync(out, dout, samples*sizeof(int16_t), hipMemcpyDeviceToHost, e->c.stream));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     return 0;
 }
 
@@ -1040,25 +1000,25 @@ int spangpu_echo_hpf_tx_channel(spangpu_echo_t *e, int channel, const int16_t *t
 // call takes over
 int spangpu_echo_reset_channel(spangpu_echo_t *e, int channel, int adaption_mode)
 {
-    if (e == nullptr  ||  channel < 0  ||  channel >= e->n_ch)
+    if (e == nullptr  ||  channel < 0  ||  channel >= e->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    ECHO_TRY(hipSetDevice(e->device));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+    SPG_TRY(hipSetDevice(e->c.device));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     const int T = e->taps;
     int32_t s[kEchoScalars];
     init_scalars(s, T, adaption_mode);
     e->mode_dirty = true;
-    if (adaption_mode != e->uniform_mode  &&  e->n_ch > 1)
+    if (adaption_mode != e->uniform_mode  &&  e->c.n_ch > 1)
         e->uniform_mode = -1;
     else
         e->uniform_mode = adaption_mode;
-    ECHO_TRY(hipMemcpyAsync(e->scal + (size_t) channel*kEchoScalars, s, sizeof(s), hipMemcpyHostToDevice, e->stream));
-    ECHO_TRY(hipMemsetAsync(e->taps32 + (size_t) channel*T, 0, T*sizeof(int32_t), e->stream));
-    ECHO_TRY(hipMemsetAsync(e->taps16 + (size_t) channel*4*T, 0, 4*T*sizeof(int16_t), e->stream));
-    ECHO_TRY(hipMemsetAsync(e->hist + (size_t) channel*T, 0, T*sizeof(int16_t), e->stream));
+    SPG_TRY(hipMemcpyAsync(e->scal + (size_t) channel*kEchoScalars, s, sizeof(s), hipMemcpyHostToDevice, e->c.stream));
+    SPG_TRY(hipMemsetAsync(e->taps32 + (size_t) channel*T, 0, T*sizeof(int32_t), e->c.stream));
+    SPG_TRY(hipMemsetAsync(e->taps16 + (size_t) channel*4*T, 0, 4*T*sizeof(int16_t), e->c.stream));
+    SPG_TRY(hipMemsetAsync(e->hist + (size_t) channel*T, 0, T*sizeof(int16_t), e->c.stream));
     if (e->stats)
-        ECHO_TRY(hipMemsetAsync(e->stats + channel, 0, sizeof(EchoStats), e->stream));
-    ECHO_TRY(hipStreamSynchronize(e->stream));
+        SPG_TRY(hipMemsetAsync(e->stats + channel, 0, sizeof(EchoStats), e->c.stream));
+    SPG_TRY(hipStreamSynchronize(e->c.stream));
     return SPANGPU_OK;
 }
 

@@ -16,10 +16,7 @@
 #include <string.h>
 
 #include "../../include/spangpu.h"
-
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define FEED_TRY(x) do { if ((x) != hipSuccess) return spangpu_set_error(SPANGPU_ERR_HIP, #x " failed"); } while (0)
+#include "bank_host.hpp"
 
 enum { kFeedMaxDepth = 8 };
 
@@ -157,12 +154,12 @@ int spangpu_feed_commit(spangpu_feed_t *f, int samples)
     const int slot = (int) (f->n_commit % f->depth);
     if (f->busy[slot])
         return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    FEED_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipSetDevice(f->device));
     hipStream_t bs = (hipStream_t) spangpu_bank_get_stream(f->bank);
     // (the slot's device buffers are free: its last tick was collected, i.e. its kernel and copies are done)
-    FEED_TRY(hipMemcpyAsync(f->d_frame[slot], f->h_stage[slot], f->frame_bytes, hipMemcpyHostToDevice, f->copy_stream));
-    FEED_TRY(hipEventRecord(f->ev_h2d[slot], f->copy_stream));
-    FEED_TRY(hipStreamWaitEvent(bs, f->ev_h2d[slot], 0));
+    SPG_TRY(hipMemcpyAsync(f->d_frame[slot], f->h_stage[slot], f->frame_bytes, hipMemcpyHostToDevice, f->copy_stream));
+    SPG_TRY(hipEventRecord(f->ev_h2d[slot], f->copy_stream));
+    SPG_TRY(hipStreamWaitEvent(bs, f->ev_h2d[slot], 0));
     int rc;
     if (f->law)
         rc = spangpu_bank_rx_g711(f->bank, (const uint8_t *) f->d_frame[slot], SPANGPU_MEM_DEVICE, f->law, samples, f->stride);
@@ -172,8 +169,8 @@ int spangpu_feed_commit(spangpu_feed_t *f, int samples)
         return rc;
     if ((rc = spangpu_bank_digit_events(f->bank, f->d_list[slot], f->cap)) < 0)
         return rc;
-    FEED_TRY(hipMemcpyAsync(f->h_list[slot], f->d_list[slot], (size_t) (1 + f->quick)*sizeof(uint32_t), hipMemcpyDeviceToHost, bs));
-    FEED_TRY(hipEventRecord(f->ev_done[slot], bs));
+    SPG_TRY(hipMemcpyAsync(f->h_list[slot], f->d_list[slot], (size_t) (1 + f->quick)*sizeof(uint32_t), hipMemcpyDeviceToHost, bs));
+    SPG_TRY(hipEventRecord(f->ev_done[slot], bs));
     f->busy[slot] = true;
     f->n_commit++;
     return SPANGPU_OK;
@@ -190,8 +187,8 @@ int spangpu_feed_collect(spangpu_feed_t *f, const uint32_t **entries)
     if (f->n_collect >= f->n_commit)
         return 0;
     const int slot = (int) (f->n_collect % f->depth);
-    FEED_TRY(hipSetDevice(f->device));
-    FEED_TRY(hipEventSynchronize(f->ev_done[slot]));
+    SPG_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipEventSynchronize(f->ev_done[slot]));
     f->busy[slot] = false;
     f->n_collect++;
     const uint32_t n = f->h_list[slot][0];
@@ -200,7 +197,7 @@ int spangpu_feed_collect(spangpu_feed_t *f, const uint32_t **entries)
     if (n > (uint32_t) f->quick)
     {
         // more digits than travel with every tick (an eighth of the channels delivering one in the same 20 ms): the rest now
-        FEED_TRY(hipMemcpy(f->h_list[slot] + 1 + f->quick, f->d_list[slot] + 1 + f->quick, (size_t) (n - (uint32_t) f->quick)*sizeof(uint32_t),
+        SPG_TRY(hipMemcpy(f->h_list[slot] + 1 + f->quick, f->d_list[slot] + 1 + f->quick, (size_t) (n - (uint32_t) f->quick)*sizeof(uint32_t),
                            hipMemcpyDeviceToHost));
     }
     *entries = f->h_list[slot] + 1;
@@ -462,10 +459,10 @@ static int xfeed_copy_out(spangpu_xfeed_t *f, int slot)
     {
         const size_t n16 = (f->out_bytes + 15)/16;
         hipLaunchKernelGGL(copy_out_kernel, dim3(256), dim3(256), 0, f->out_stream, (feed_u32x4 *) f->h_out_dev[slot], (const feed_u32x4 *) f->d_out[slot], n16);
-        FEED_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
         return SPANGPU_OK;
     }
-    FEED_TRY(hipMemcpyAsync(f->h_out[slot], f->d_out[slot], f->out_bytes, hipMemcpyDeviceToHost, f->out_stream));
+    SPG_TRY(hipMemcpyAsync(f->h_out[slot], f->d_out[slot], f->out_bytes, hipMemcpyDeviceToHost, f->out_stream));
     return SPANGPU_OK;
 }
 
@@ -578,24 +575,24 @@ int spangpu_echo_feed_commit(spangpu_echo_feed_t *feed, int samples)
     const int slot = (int) (f->n_commit % f->depth);
     if (f->busy[slot])
         return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    FEED_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipSetDevice(f->device));
     hipStream_t bs = (hipStream_t) spangpu_echo_get_stream(f->echo);
-    FEED_TRY(hipMemcpyAsync(f->d_in[slot], f->h_in[slot], f->in_bytes, hipMemcpyHostToDevice, f->in_stream));
-    FEED_TRY(hipEventRecord(f->ev_in[slot], f->in_stream));
-    FEED_TRY(hipStreamWaitEvent(bs, f->ev_in[slot], 0));
+    SPG_TRY(hipMemcpyAsync(f->d_in[slot], f->h_in[slot], f->in_bytes, hipMemcpyHostToDevice, f->in_stream));
+    SPG_TRY(hipEventRecord(f->ev_in[slot], f->in_stream));
+    SPG_TRY(hipStreamWaitEvent(bs, f->ev_in[slot], 0));
     const size_t rows = (size_t) f->stride*f->n_ch;
     int rc;
     if (f->law)
     {
         const long long n16 = (long long) (2*rows/16);
         hipLaunchKernelGGL(g711_to_linear_kernel, dim3((unsigned) ((n16 + 255)/256)), dim3(256), 0, bs, (const uint8_t *) f->d_in[slot], f->d_pcm_in, n16, f->law);
-        FEED_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
         rc = spangpu_echo_update(f->echo, f->d_pcm_in, f->d_pcm_in + rows, f->d_pcm_out, SPANGPU_MEM_DEVICE, samples, f->stride, f->use_hpf_tx);
         if (rc < 0)
             return rc;
         const long long m16 = (long long) (rows/16);
         hipLaunchKernelGGL(linear_to_g711_kernel, dim3((unsigned) ((m16 + 255)/256)), dim3(256), 0, bs, (const int16_t *) f->d_pcm_out, (uint8_t *) f->d_out[slot], m16, f->law);
-        FEED_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
     }
     else
     {
@@ -604,11 +601,11 @@ int spangpu_echo_feed_commit(spangpu_echo_feed_t *feed, int samples)
         if (rc < 0)
             return rc;
     }
-    FEED_TRY(hipEventRecord(f->ev_k[slot], bs));
-    FEED_TRY(hipStreamWaitEvent(f->out_stream, f->ev_k[slot], 0));
+    SPG_TRY(hipEventRecord(f->ev_k[slot], bs));
+    SPG_TRY(hipStreamWaitEvent(f->out_stream, f->ev_k[slot], 0));
     if ((rc = xfeed_copy_out(f, slot)) < 0)
         return rc;
-    FEED_TRY(hipEventRecord(f->ev_done[slot], f->out_stream));
+    SPG_TRY(hipEventRecord(f->ev_done[slot], f->out_stream));
     f->busy[slot] = true;
     f->samples_of[slot] = samples;
     f->n_commit++;
@@ -626,8 +623,8 @@ int spangpu_echo_feed_collect(spangpu_echo_feed_t *feed, const void **clean)
     if (f->n_collect >= f->n_commit)
         return 0;
     const int slot = (int) (f->n_collect % f->depth);
-    FEED_TRY(hipSetDevice(f->device));
-    FEED_TRY(hipEventSynchronize(f->ev_done[slot]));
+    SPG_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipEventSynchronize(f->ev_done[slot]));
     f->busy[slot] = false;
     f->n_collect++;
     *clean = f->h_out[slot];
@@ -750,11 +747,11 @@ int spangpu_modem_feed_commit(spangpu_modem_feed_t *feed, int samples)
     const int slot = (int) (f->n_commit % f->depth);
     if (f->busy[slot])
         return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    FEED_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipSetDevice(f->device));
     hipStream_t bs = (hipStream_t) spangpu_modem_get_stream(f->modem);
-    FEED_TRY(hipMemcpyAsync(f->d_in[slot], f->h_in[slot], f->in_bytes, hipMemcpyHostToDevice, f->in_stream));
-    FEED_TRY(hipEventRecord(f->ev_in[slot], f->in_stream));
-    FEED_TRY(hipStreamWaitEvent(bs, f->ev_in[slot], 0));
+    SPG_TRY(hipMemcpyAsync(f->d_in[slot], f->h_in[slot], f->in_bytes, hipMemcpyHostToDevice, f->in_stream));
+    SPG_TRY(hipEventRecord(f->ev_in[slot], f->in_stream));
+    SPG_TRY(hipStreamWaitEvent(bs, f->ev_in[slot], 0));
     int rc = spangpu_modem_rx(f->modem, (const int16_t *) f->d_in[slot], SPANGPU_MEM_DEVICE, samples, f->stride);
     if (rc < 0)
         return rc;
@@ -762,11 +759,11 @@ int spangpu_modem_feed_commit(spangpu_modem_feed_t *feed, int samples)
     uint32_t *status = packed + (size_t) f->n_ch*f->wpc;
     if ((rc = spangpu_modem_pack_events(f->modem, packed, f->wpc, status, f->status_cap)) < 0)
         return rc;
-    FEED_TRY(hipEventRecord(f->ev_k[slot], bs));
-    FEED_TRY(hipStreamWaitEvent(f->out_stream, f->ev_k[slot], 0));
+    SPG_TRY(hipEventRecord(f->ev_k[slot], bs));
+    SPG_TRY(hipStreamWaitEvent(f->out_stream, f->ev_k[slot], 0));
     if ((rc = xfeed_copy_out(f, slot)) < 0)
         return rc;
-    FEED_TRY(hipEventRecord(f->ev_done[slot], f->out_stream));
+    SPG_TRY(hipEventRecord(f->ev_done[slot], f->out_stream));
     f->busy[slot] = true;
     f->samples_of[slot] = samples;
     f->n_commit++;
@@ -786,8 +783,8 @@ int spangpu_modem_feed_collect(spangpu_modem_feed_t *feed, const uint32_t **pack
     if (f->n_collect >= f->n_commit)
         return 0;
     const int slot = (int) (f->n_collect % f->depth);
-    FEED_TRY(hipSetDevice(f->device));
-    FEED_TRY(hipEventSynchronize(f->ev_done[slot]));
+    SPG_TRY(hipSetDevice(f->device));
+    SPG_TRY(hipEventSynchronize(f->ev_done[slot]));
     f->busy[slot] = false;
     f->n_collect++;
     *packed = (const uint32_t *) f->h_out[slot];

@@ -8,8 +8,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/spangpu.h"
+#include "bank_host.hpp"
 #include "modem_tables.h"
 #include "v29_dev.hpp"
 #include "v29_quad.hpp"
@@ -28,40 +30,18 @@ void launch_v27ter_quad(const V27Launch &L, hipStream_t stream);
 
 using namespace spg;
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
 static std::atomic<int> g_modem_mapping{0};     // spangpu_tune_modem_mapping(): a process-wide knob another thread may turn while a bank launches
-
-#define V29_TRY(expr)                                                                       \
-    do                                                                                      \
-    {                                                                                       \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-        {                                                                                   \
-            char m_[256];                                                                   \
-            snprintf(m_, sizeof(m_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-            return spangpu_set_error(SPANGPU_ERR_HIP, m_);                                  \
-        }                                                                                   \
-    }                                                                                       \
-    while (0)
 
 struct spangpu_modem_s
 {
-    const int32_t *next_lens;   // per-channel lengths of the call being prepared (device), or nullptr
-    int32_t *d_lens;            // [n_ch], device
+    const int32_t *next_lens;   // per-channel lengths of the call being prepared (device: pcm.d_lens), or nullptr
     int32_t *h_lens;            // [n_ch], pinned
+    BankCore c;                 // st = [state words of the kind][n_ch]; uint32_t towards the kernels
+    PcmStage pcm;               // staging for host-resident frames, and the device copy of a call's lengths
     int kind;
-    int n_words;
     int n_floats;
-    int device;
-    int n_ch;
     int bit_rate;
-    hipStream_t stream;
-    bool own_stream;
-    uint32_t *state;            // [kV29Words][n_ch]
     void *tab;
-    int16_t *d_amp;
-    size_t amp_cap;
     int8_t *events;
     int32_t *ev_count;
     int ev_cap;
@@ -205,6 +185,100 @@ static int initial_words(int kind, uint32_t *w, int bit_rate)
 
 static constexpr int kMaxWords = 1024;
 
+// ---- the launch of a call: one launch record and one choice of kernel for the three receivers ------------------------------
+
+template <typename L>
+static L make_launch(const spangpu_modem_t *m, const int16_t *amp, long long stride, int samples)
+{
+    L l;
+    memset(&l, 0, sizeof(l));
+    l.amp = amp;
+    l.stride = stride;
+    l.samples = samples;
+    l.lens = m->next_lens;
+    l.n_ch = m->c.n_ch;
+    if constexpr (!std::is_same<L, V29Launch>::value)
+        l.bit_rate = m->bit_rate;                   // V.17 and V.27ter banks run one rate; a V.29 channel carries its own
+    l.state = (uint32_t *) m->c.st;
+    l.events = m->events;
+    l.ev_count = m->ev_count;
+    l.ev_cap = m->ev_cap;
+    l.tab = (decltype(l.tab)) m->tab;
+    l.qam = m->qam;
+    l.qam_count = m->qam_count;
+    l.qam_cap = m->qam_cap;
+    return l;
+}
+
+// What is a receiver's own: its kernels, how many full waves share a workgroup's tables, and the unit of its quad kernel.
+struct V29Rx
+{
+    typedef V29Launch Launch;
+    // full waves: four to a workgroup, sharing the tables, the RRC delay line as packed int16 pairs -- 150 KB of
+    // LDS per workgroup, one workgroup per CU, a wave on every SIMD (v29_dev.hpp)
+    static constexpr int kFullWaves = 4;
+    static void qam(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL((v29_bank_kernel<16, true>), g, dim3(64), 0, s, l); }
+    static void full(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL((v29_bank_kernel<64, false, 4, 16, true>), g, dim3(256), 0, s, l); }
+    static void quad(const Launch &l, hipStream_t s) { launch_v29_quad(l, s); }          // modem_v29q.hip (a scheduler of its own)
+    static void k32(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL(v29_bank_kernel<32>, g, dim3(64), 0, s, l); }
+    static void k16(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL(v29_bank_kernel<16>, g, dim3(64), 0, s, l); }
+};
+
+struct V17Rx
+{
+    typedef V17Launch Launch;
+    static constexpr int kFullWaves = 3;
+    static void qam(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL((v17_bank_kernel<16, true>), g, dim3(64), 0, s, l); }
+    static void full(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL((v17_bank_kernel<64, false, 3, 16, true>), g, dim3(192), 0, s, l); }
+    static void quad(const Launch &l, hipStream_t s) { launch_v17_quad(l, s); }          // modem_v17q.hip (a scheduler of its own)
+    static void k32(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL(v17_bank_kernel<32>, g, dim3(64), 0, s, l); }
+    static void k16(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL(v17_bank_kernel<16>, g, dim3(64), 0, s, l); }
+};
+
+struct V27Rx
+{
+    typedef V27Launch Launch;
+    static constexpr int kFullWaves = 4;
+    static void qam(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL((v27ter_bank_kernel<16, true>), g, dim3(64), 0, s, l); }
+    static void full(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL((v27ter_bank_kernel<64, false, 4, 16, true>), g, dim3(256), 0, s, l); }
+    static void quad(const Launch &l, hipStream_t s) { launch_v27ter_quad(l, s); }       // modem_v27q.hip (a scheduler of its own)
+    static void k32(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL(v27ter_bank_kernel<32>, g, dim3(64), 0, s, l); }
+    static void k16(dim3 g, hipStream_t s, const Launch &l) { hipLaunchKernelGGL(v27ter_bank_kernel<16>, g, dim3(64), 0, s, l); }
+};
+
+template <typename R>
+static void launch_rx(const spangpu_modem_t *m, const int16_t *amp, long long stride, int samples)
+{
+    const typename R::Launch L = make_launch<typename R::Launch>(m, amp, stride, samples);
+    const int n_ch = m->c.n_ch;
+    // enough workgroups to put a wave on every SIMD (256 CUs x 4) before filling the waves
+    const int cpw = (n_ch >= 64*1024)  ?  64  :  (n_ch >= 32*1024)  ?  32  :  16;
+    // lanes per channel: 1 = the one-channel-per-lane kernels, 4 = a quad per channel with 16 channels per wave (8 is taken as
+    // 4: the variant with 8 channels per wave, two waves per SIMD, was measured -- slower -- and removed);
+    // spangpu_tune_modem_mapping() overrides
+    // (measured, 16 384-channel rounds of the quad kernels against the one-lane kernels, V.29 / V.17 / V.27ter: 32 768 channels
+    // 0.32 / 0.40 / 0.24 ms against 0.75 / 0.86 / 0.26; 49 152 channels 0.47 / 0.59 / 0.34 against 0.75 / 0.84 / 0.48; from
+    // 65 536 channels the full-wave one-lane kernels win: 0.45 / 0.92 / 0.29 ms against four rounds of 0.156 / 0.215 / 0.111)
+    const int mapping = g_modem_mapping.load(std::memory_order_relaxed);        // read once per launch
+    const int quad = (mapping != 0)  ?  mapping  :  (n_ch < 64*1024)  ?  4  :  1;
+    const bool forced_quad = (mapping == 4  ||  mapping == 8);       // an explicit four lanes per channel holds at every bank size (A-B runs)
+    const dim3 grid((n_ch + cpw - 1)/cpw);
+    if (m->qam_tap)
+        R::qam(dim3((n_ch + 15)/16), m->c.stream, L);
+    else if (cpw == 64  &&  !forced_quad)
+        R::full(dim3(((n_ch + 63)/64 + R::kFullWaves - 1)/R::kFullWaves), m->c.stream, L);
+    else if (quad == 4  ||  quad == 8)
+    {
+        // banks that cannot fill the chip's 1 024 SIMDs with full waves of one channel per lane: four lanes per
+        // channel, 16 channels per wave, four waves per workgroup sharing the tables (v29_quad.hpp)
+        R::quad(L, m->c.stream);
+    }
+    else if (cpw == 32)
+        R::k32(grid, m->c.stream, L);
+    else
+        R::k16(grid, m->c.stream, L);
+}
+
 extern "C" {
 
 int spangpu_modem_state_words(int kind, int *n_floats, int *n_ints)
@@ -258,38 +332,29 @@ int spangpu_modem_create(spangpu_modem_t **out, int device, int kind, int n_chan
         return n_words;
     if (initial_words(kind, w, bit_rate) < 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bit rate not valid for this modem (V.29: 9600/7200/4800, V.27ter: 4800/2400, V.17: 14400/12000/9600/7200/4800)");
-    if (spangpu_device_count() <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    if (device < 0  ||  device >= spangpu_device_count())
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "device out of range");
-    V29_TRY(hipSetDevice(device));
+    int rc = device_ok(device);
+    if (rc != SPANGPU_OK)
+        return rc;
     spangpu_modem_t *m = (spangpu_modem_t *) calloc(1, sizeof(*m));
     if (m == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
     m->kind = kind;
-    m->n_words = n_words;
     spangpu_modem_state_words(kind, &m->n_floats, nullptr);
-    m->device = device;
-    m->n_ch = n_channels;
     m->bit_rate = bit_rate;
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess)
+    if ((rc = core_create(&m->c, device, n_channels, n_words)) != SPANGPU_OK)
     {
-        free(m);
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipStreamCreate failed");
+        spangpu_modem_destroy(m);
+        return rc;
     }
-    m->own_stream = true;
     const size_t n = (size_t) n_channels;
     const size_t tab_bytes = (kind == SPANGPU_V29)  ?  sizeof(V29Tables)  :  (kind == SPANGPU_V17)  ?  sizeof(V17Tables)  :  sizeof(V27Tables);
     void *ht = calloc(1, tab_bytes);
-    uint32_t *hs = (uint32_t *) malloc(n*n_words*sizeof(uint32_t));
-    if (ht == nullptr  ||  hs == nullptr
-        ||  hipMalloc(&m->state, n*n_words*sizeof(uint32_t)) != hipSuccess
+    if (ht == nullptr
         ||  hipMalloc(&m->tab, tab_bytes) != hipSuccess
         ||  hipMalloc(&m->ev_count, n*sizeof(int32_t)) != hipSuccess
         ||  hipHostMalloc(&m->h_count, n*sizeof(int32_t)) != hipSuccess)
     {
         free(ht);
-        free(hs);
         spangpu_modem_destroy(m);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of V.29 bank failed");
     }
@@ -322,7 +387,6 @@ int spangpu_modem_create(spangpu_modem_t **out, int device, int kind, int n_chan
             free(re);
             free(maps);
             free(ht);
-            free(hs);
             spangpu_modem_destroy(m);
             return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "table scratch");
         }
@@ -369,16 +433,9 @@ int spangpu_modem_create(spangpu_modem_t **out, int device, int kind, int n_chan
         spg_make_sine_table(t->sine);
         spg_make_sqrt_table(t->sqrt_tab);
     }
-    for (int k = 0;  k < n_words;  k++)
-    {
-        for (size_t c = 0;  c < n;  c++)
-            hs[(size_t) k*n + c] = w[k];
-    }
-    hipError_t rc1 = hipMemcpy(m->tab, ht, tab_bytes, hipMemcpyHostToDevice);
-    hipError_t rc2 = hipMemcpy(m->state, hs, n*n_words*sizeof(uint32_t), hipMemcpyHostToDevice);
+    const hipError_t e = hipMemcpy(m->tab, ht, tab_bytes, hipMemcpyHostToDevice);
     free(ht);
-    free(hs);
-    if (rc1 != hipSuccess  ||  rc2 != hipSuccess)
+    if (e != hipSuccess  ||  core_fill(&m->c, (const int32_t *) w) != SPANGPU_OK)
     {
         spangpu_modem_destroy(m);
         return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
@@ -391,13 +448,9 @@ int spangpu_modem_destroy(spangpu_modem_t *m)
 {
     if (m == nullptr)
         return SPANGPU_OK;
-    (void) hipSetDevice(m->device);
-    if (m->stream)
-        (void) hipStreamSynchronize(m->stream);
-    if (m->state) (void) hipFree(m->state);
+    core_destroy(&m->c);
+    stage_free(&m->pcm);
     if (m->tab) (void) hipFree(m->tab);
-    if (m->d_amp) (void) hipFree(m->d_amp);
-    if (m->d_lens) (void) hipFree(m->d_lens);
     if (m->h_lens) (void) hipHostFree(m->h_lens);
     if (m->events) (void) hipFree(m->events);
     if (m->ev_count) (void) hipFree(m->ev_count);
@@ -409,228 +462,69 @@ int spangpu_modem_destroy(spangpu_modem_t *m)
     if (m->h_qam_count) (void) hipHostFree(m->h_qam_count);
     if (m->d_packed) (void) hipFree(m->d_packed);
     if (m->h_packed) (void) hipHostFree(m->h_packed);
-    if (m->own_stream  &&  m->stream)
-        (void) hipStreamDestroy(m->stream);
     free(m);
     return SPANGPU_OK;
 }
 
-int spangpu_modem_channels(const spangpu_modem_t *m) { return m  ?  m->n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_modem_channels(const spangpu_modem_t *m) { return m  ?  m->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_modem_set_stream(spangpu_modem_t *m, void *hip_stream)
 {
     if (m == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    (void) hipStreamSynchronize(m->stream);
-    if (m->own_stream)
-        (void) hipStreamDestroy(m->stream);
-    if (hip_stream)
-    {
-        m->stream = (hipStream_t) hip_stream;
-        m->own_stream = false;
-    }
-    else
-    {
-        V29_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-        m->own_stream = true;
-    }
-    return SPANGPU_OK;
+    return core_set_stream(&m->c, hip_stream, true);       // NULL: a fresh stream of the bank's own
 }
 
 int spangpu_modem_sync(spangpu_modem_t *m)
 {
     if (m == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    V29_TRY(hipStreamSynchronize(m->stream));
-    return SPANGPU_OK;
+    return core_sync(&m->c);
 }
 
 int spangpu_modem_rx(spangpu_modem_t *m, const int16_t *amp, int mem, int samples, long long stride)
 {
-    if (m == nullptr  ||  amp == nullptr  ||  samples < 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (samples == 0)
+    if (m != nullptr  &&  amp != nullptr  &&  samples == 0)
         return 0;
-    if (stride <= 0)
-        stride = samples;
-    V29_TRY(hipSetDevice(m->device));
+    int rc = rx_args_ok(m, mem, amp, samples, &stride);
+    if (rc != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipSetDevice(m->c.device));
     // at most 4 (V.17: 6) bits per baud and nominally a baud every 8000/2400 samples; symbol timing recovery can run the
     // baud clock fast by up to 5/160 of a baud per baud, so 1/16 more bauds than nominal are provided for, plus room
     // for every status report a call can make.  spangpu_modem_events() refuses to hand out a stream that did not fit.
     const int bauds = (samples*3 + 9)/10;
     const int cap = ((bauds + bauds/16 + 2)*((m->kind == SPANGPU_V17)  ?  6  :  4) + 16 + 15) & ~15;
-    if (cap > m->ev_cap)
-    {
-        if (m->events) (void) hipFree(m->events);
-        if (m->h_events) (void) hipHostFree(m->h_events);
-        m->events = nullptr;
-        m->h_events = nullptr;
-        m->ev_cap = 0;
-        V29_TRY(hipMalloc(&m->events, (size_t) m->n_ch*cap));
-        V29_TRY(hipHostMalloc(&m->h_events, (size_t) m->n_ch*cap));
-        m->ev_cap = cap;
-    }
+    if ((rc = grow_pair(&m->events, &m->h_events, &m->ev_cap, cap, (size_t) m->c.n_ch, m->c.stream)) != SPANGPU_OK)
+        return rc;
     if (m->qam_tap)
     {
         // one report per baud (at most 2400 per second) and, V.27ter, one per timing hop (at most one per baud)
         const int qcap = 2*((samples*3 + 9)/10 + 2);
-        if (qcap > m->qam_cap)
-        {
-            if (m->qam) (void) hipFree(m->qam);
-            if (m->h_qam) (void) hipHostFree(m->h_qam);
-            m->qam = nullptr;
-            m->h_qam = nullptr;
-            m->qam_cap = 0;
-            V29_TRY(hipMalloc(&m->qam, (size_t) m->n_ch*qcap*7*sizeof(uint32_t)));
-            V29_TRY(hipHostMalloc(&m->h_qam, (size_t) m->n_ch*qcap*7*sizeof(uint32_t)));
-            m->qam_cap = qcap;
-        }
+        if ((rc = grow_pair(&m->qam, &m->h_qam, &m->qam_cap, qcap, (size_t) m->c.n_ch*7, m->c.stream)) != SPANGPU_OK)
+            return rc;
         if (m->qam_count == nullptr)
         {
-            V29_TRY(hipMalloc(&m->qam_count, (size_t) m->n_ch*sizeof(int32_t)));
-            V29_TRY(hipHostMalloc(&m->h_qam_count, (size_t) m->n_ch*sizeof(int32_t)));
+            SPG_TRY(hipMalloc(&m->qam_count, (size_t) m->c.n_ch*sizeof(int32_t)));
+            SPG_TRY(hipHostMalloc(&m->h_qam_count, (size_t) m->c.n_ch*sizeof(int32_t)));
         }
     }
-    const int16_t *d_amp = amp;
-    long long d_stride = stride;
-    if (mem == SPANGPU_MEM_HOST)
+    // amp[] of a host caller is only borrowed for the duration of the call: the copy in is waited for
+    const int16_t *d_amp;
+    long long d_stride;
+    if ((rc = stage_in(&m->c, &m->pcm, mem, amp, stride, samples, true, &d_amp, &d_stride, nullptr)) != SPANGPU_OK)
+        return rc;
+    switch (m->kind)
     {
-        if ((size_t) samples > m->amp_cap)
-        {
-            if (m->d_amp) (void) hipFree(m->d_amp);
-            m->d_amp = nullptr;
-            m->amp_cap = 0;
-            V29_TRY(hipMalloc(&m->d_amp, (size_t) m->n_ch*samples*sizeof(int16_t)));
-            m->amp_cap = samples;
-        }
-        V29_TRY(hipMemcpy2DAsync(m->d_amp, m->amp_cap*sizeof(int16_t), amp, stride*sizeof(int16_t),
-                                 samples*sizeof(int16_t), m->n_ch, hipMemcpyHostToDevice, m->stream));
-        V29_TRY(hipStreamSynchronize(m->stream));         // amp[] is only borrowed for the duration of the call
-        d_amp = m->d_amp;
-        d_stride = (long long) m->amp_cap;
+    case SPANGPU_V29: launch_rx<V29Rx>(m, d_amp, d_stride, samples); break;
+    case SPANGPU_V17: launch_rx<V17Rx>(m, d_amp, d_stride, samples); break;
+    default: launch_rx<V27Rx>(m, d_amp, d_stride, samples); break;
     }
-    else if (mem != SPANGPU_MEM_DEVICE)
-    {
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    }
-    // enough workgroups to put a wave on every SIMD (256 CUs x 4) before filling the waves
-    const int cpw = (m->n_ch >= 64*1024)  ?  64  :  (m->n_ch >= 32*1024)  ?  32  :  16;
-    // lanes per channel: 1 = the one-channel-per-lane kernels, 4 = a quad per channel with 16 channels per wave (8 is taken as
-    // 4: the variant with 8 channels per wave, two waves per SIMD, was measured -- slower -- and removed);
-    // spangpu_tune_modem_mapping() overrides
-    // (measured, 16 384-channel rounds of the quad kernels against the one-lane kernels, V.29 / V.17 / V.27ter: 32 768 channels
-    // 0.32 / 0.40 / 0.24 ms against 0.75 / 0.86 / 0.26; 49 152 channels 0.47 / 0.59 / 0.34 against 0.75 / 0.84 / 0.48; from
-    // 65 536 channels the full-wave one-lane kernels win: 0.45 / 0.92 / 0.29 ms against four rounds of 0.156 / 0.215 / 0.111)
-    const int mapping = g_modem_mapping.load(std::memory_order_relaxed);        // read once per launch
-    const int quad = (mapping != 0)  ?  mapping  :  (m->n_ch < 64*1024)  ?  4  :  1;
-    const bool forced_quad = (mapping == 4  ||  mapping == 8);       // an explicit four lanes per channel holds at every bank size (A-B runs)
-    const dim3 grid((m->n_ch + cpw - 1)/cpw);
-    if (m->kind == SPANGPU_V29)
-    {
-        V29Launch L;
-        memset(&L, 0, sizeof(L));
-        L.amp = d_amp;
-        L.stride = d_stride;
-        L.samples = samples;
-        L.lens = m->next_lens;
-        L.n_ch = m->n_ch;
-        L.state = m->state;
-        L.events = m->events;
-        L.ev_count = m->ev_count;
-        L.ev_cap = m->ev_cap;
-        L.tab = (const V29Tables *) m->tab;
-        L.qam = m->qam;
-        L.qam_count = m->qam_count;
-        L.qam_cap = m->qam_cap;
-        if (m->qam_tap)
-            hipLaunchKernelGGL((v29_bank_kernel<16, true>), dim3((m->n_ch + 15)/16), dim3(64), 0, m->stream, L);
-        else if (cpw == 64  &&  !forced_quad)
-        {
-            // full waves: four to a workgroup, sharing the tables, the RRC delay line as packed int16 pairs -- 150 KB of
-            // LDS per workgroup, one workgroup per CU, a wave on every SIMD (v29_dev.hpp)
-            const int waves = (m->n_ch + 63)/64;
-            hipLaunchKernelGGL((v29_bank_kernel<64, false, 4, 16, true>), dim3((waves + 3)/4), dim3(256), 0, m->stream, L);
-        }
-        else if (quad == 4  ||  quad == 8)
-        {
-            // banks that cannot fill the chip's 1 024 SIMDs with full waves of one channel per lane: four lanes per
-            // channel, 16 channels per wave, four waves per workgroup sharing the tables (v29_quad.hpp)
-            launch_v29_quad(L, m->stream);                          // modem_v29q.hip (a scheduler of its own)
-        }
-        else if (cpw == 32)
-            hipLaunchKernelGGL(v29_bank_kernel<32>, grid, dim3(64), 0, m->stream, L);
-        else
-            hipLaunchKernelGGL(v29_bank_kernel<16>, grid, dim3(64), 0, m->stream, L);
-    }
-    else if (m->kind == SPANGPU_V17)
-    {
-        V17Launch L;
-        memset(&L, 0, sizeof(L));
-        L.amp = d_amp;
-        L.stride = d_stride;
-        L.samples = samples;
-        L.lens = m->next_lens;
-        L.n_ch = m->n_ch;
-        L.bit_rate = m->bit_rate;
-        L.state = m->state;
-        L.events = m->events;
-        L.ev_count = m->ev_count;
-        L.ev_cap = m->ev_cap;
-        L.tab = (const V17Tables *) m->tab;
-        L.qam = m->qam;
-        L.qam_count = m->qam_count;
-        L.qam_cap = m->qam_cap;
-        if (m->qam_tap)
-            hipLaunchKernelGGL((v17_bank_kernel<16, true>), dim3((m->n_ch + 15)/16), dim3(64), 0, m->stream, L);
-        else if (cpw == 64  &&  !forced_quad)
-        {
-            const int waves = (m->n_ch + 63)/64;
-            hipLaunchKernelGGL((v17_bank_kernel<64, false, 3, 16, true>), dim3((waves + 2)/3), dim3(192), 0, m->stream, L);
-        }
-        else if (quad == 4  ||  quad == 8)
-            launch_v17_quad(L, m->stream);                          // modem_v17q.hip (a scheduler of its own)
-        else if (cpw == 32)
-            hipLaunchKernelGGL(v17_bank_kernel<32>, grid, dim3(64), 0, m->stream, L);
-        else
-            hipLaunchKernelGGL(v17_bank_kernel<16>, grid, dim3(64), 0, m->stream, L);
-    }
-    else
-    {
-        V27Launch L;
-        memset(&L, 0, sizeof(L));
-        L.amp = d_amp;
-        L.stride = d_stride;
-        L.samples = samples;
-        L.lens = m->next_lens;
-        L.n_ch = m->n_ch;
-        L.bit_rate = m->bit_rate;
-        L.state = m->state;
-        L.events = m->events;
-        L.ev_count = m->ev_count;
-        L.ev_cap = m->ev_cap;
-        L.tab = (const V27Tables *) m->tab;
-        L.qam = m->qam;
-        L.qam_count = m->qam_count;
-        L.qam_cap = m->qam_cap;
-        if (m->qam_tap)
-            hipLaunchKernelGGL((v27ter_bank_kernel<16, true>), dim3((m->n_ch + 15)/16), dim3(64), 0, m->stream, L);
-        else if (cpw == 64  &&  !forced_quad)
-        {
-            const int waves = (m->n_ch + 63)/64;
-            hipLaunchKernelGGL((v27ter_bank_kernel<64, false, 4, 16, true>), dim3((waves + 3)/4), dim3(256), 0, m->stream, L);
-        }
-        else if (quad == 4  ||  quad == 8)
-            launch_v27ter_quad(L, m->stream);                       // modem_v27q.hip (a scheduler of its own)
-        else if (cpw == 32)
-            hipLaunchKernelGGL(v27ter_bank_kernel<32>, grid, dim3(64), 0, m->stream, L);
-        else
-            hipLaunchKernelGGL(v27ter_bank_kernel<16>, grid, dim3(64), 0, m->stream, L);
-    }
-    V29_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     m->last_cap = m->ev_cap;
     m->last_qam_cap = m->qam_tap  ?  m->qam_cap  :  0;
     if (mem == SPANGPU_MEM_HOST)
-        V29_TRY(hipStreamSynchronize(m->stream));
+        SPG_TRY(hipStreamSynchronize(m->c.stream));
     return 0;
 }
 
@@ -642,7 +536,7 @@ int spangpu_modem_rx_var(spangpu_modem_t *m, const int16_t *amp, int mem, const 
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int longest = 0;
     bool all = true;
-    for (int c = 0;  c < m->n_ch;  c++)
+    for (int c = 0;  c < m->c.n_ch;  c++)
     {
         if (lens[c] < 0  ||  lens[c] > max_samples)
             return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
@@ -651,23 +545,23 @@ int spangpu_modem_rx_var(spangpu_modem_t *m, const int16_t *amp, int mem, const 
     }
     if (longest == 0)
         return 0;
-    for (int c = 0;  c < m->n_ch;  c++)
+    for (int c = 0;  c < m->c.n_ch;  c++)
         all &= (lens[c] == longest);
     if (stride <= 0)
         stride = max_samples;
     if (all)
         return spangpu_modem_rx(m, amp, mem, longest, stride);
-    V29_TRY(hipSetDevice(m->device));
-    if (m->d_lens == nullptr)
-    {
-        V29_TRY(hipMalloc(&m->d_lens, (size_t) m->n_ch*sizeof(int32_t)));
-        V29_TRY(hipHostMalloc(&m->h_lens, (size_t) m->n_ch*sizeof(int32_t)));
-    }
-    V29_TRY(hipStreamSynchronize(m->stream));
-    memcpy(m->h_lens, lens, (size_t) m->n_ch*sizeof(int32_t));
-    V29_TRY(hipMemcpyAsync(m->d_lens, m->h_lens, (size_t) m->n_ch*sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
-    m->next_lens = m->d_lens;
-    const int rc = spangpu_modem_rx(m, amp, mem, longest, stride);
+    SPG_TRY(hipSetDevice(m->c.device));
+    int rc = stage_lens(&m->c, &m->pcm);
+    if (rc != SPANGPU_OK)
+        return rc;
+    if (m->h_lens == nullptr)
+        SPG_TRY(hipHostMalloc(&m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t)));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
+    memcpy(m->h_lens, lens, (size_t) m->c.n_ch*sizeof(int32_t));
+    SPG_TRY(hipMemcpyAsync(m->pcm.d_lens, m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, m->c.stream));
+    m->next_lens = m->pcm.d_lens;
+    rc = spangpu_modem_rx(m, amp, mem, longest, stride);
     m->next_lens = nullptr;
     return rc;
 }
@@ -691,10 +585,10 @@ int spangpu_modem_qam_reports(spangpu_modem_t *m, const uint32_t **records, cons
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_qam_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() with the tap on yet");
-    V29_TRY(hipSetDevice(m->device));
-    V29_TRY(hipMemcpyAsync(m->h_qam, m->qam, (size_t) m->n_ch*m->last_qam_cap*7*sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    V29_TRY(hipMemcpyAsync(m->h_qam_count, m->qam_count, (size_t) m->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    V29_TRY(hipStreamSynchronize(m->stream));
+    SPG_TRY(hipSetDevice(m->c.device));
+    SPG_TRY(hipMemcpyAsync(m->h_qam, m->qam, (size_t) m->c.n_ch*m->last_qam_cap*7*sizeof(uint32_t), hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipMemcpyAsync(m->h_qam_count, m->qam_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
     *records = m->h_qam;
     *counts = m->h_qam_count;
     return m->last_qam_cap;
@@ -709,11 +603,11 @@ int spangpu_modem_events(spangpu_modem_t *m, const int8_t **events, const int32_
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() yet");
-    V29_TRY(hipSetDevice(m->device));
-    V29_TRY(hipMemcpyAsync(m->h_events, m->events, (size_t) m->n_ch*m->last_cap, hipMemcpyDeviceToHost, m->stream));
-    V29_TRY(hipMemcpyAsync(m->h_count, m->ev_count, (size_t) m->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-    V29_TRY(hipStreamSynchronize(m->stream));
-    for (int c = 0;  c < m->n_ch;  c++)
+    SPG_TRY(hipSetDevice(m->c.device));
+    SPG_TRY(hipMemcpyAsync(m->h_events, m->events, (size_t) m->c.n_ch*m->last_cap, hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipMemcpyAsync(m->h_count, m->ev_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
+    for (int c = 0;  c < m->c.n_ch;  c++)
     {
         if (m->h_count[c] > m->last_cap)
             return spangpu_set_error(SPANGPU_ERR_STATE, "modem event buffer overflow: a channel produced more events than the call's frame length allows");
@@ -733,14 +627,14 @@ int spangpu_modem_copy_events(spangpu_modem_t *m, void *dev_dst, size_t dst_byte
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() yet");
-    const size_t need = (size_t) m->n_ch*(sizeof(int32_t) + (size_t) per_channel);
+    const size_t need = (size_t) m->c.n_ch*(sizeof(int32_t) + (size_t) per_channel);
     if (dst_bytes < need)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "destination too small");
-    V29_TRY(hipSetDevice(m->device));
-    V29_TRY(hipMemcpyAsync(dev_dst, m->ev_count, (size_t) m->n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, m->stream));
+    SPG_TRY(hipSetDevice(m->c.device));
+    SPG_TRY(hipMemcpyAsync(dev_dst, m->ev_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, m->c.stream));
     const int w = (per_channel < m->last_cap)  ?  per_channel  :  m->last_cap;
-    V29_TRY(hipMemcpy2DAsync((char *) dev_dst + (size_t) m->n_ch*sizeof(int32_t), (size_t) per_channel, m->events, (size_t) m->last_cap,
-                             (size_t) w, (size_t) m->n_ch, hipMemcpyDeviceToDevice, m->stream));
+    SPG_TRY(hipMemcpy2DAsync((char *) dev_dst + (size_t) m->c.n_ch*sizeof(int32_t), (size_t) per_channel, m->events, (size_t) m->last_cap,
+                             (size_t) w, (size_t) m->c.n_ch, hipMemcpyDeviceToDevice, m->c.stream));
     return SPANGPU_OK;
 }
 
@@ -829,11 +723,11 @@ int spangpu_modem_pack_events(spangpu_modem_t *m, uint32_t *packed_device, int w
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() yet");
-    V29_TRY(hipSetDevice(m->device));
-    V29_TRY(hipMemsetAsync(status_device, 0, sizeof(uint32_t), m->stream));
-    hipLaunchKernelGGL(modem_pack_kernel, dim3((m->n_ch + 255)/256), dim3(256), 0, m->stream, (const int8_t *) m->events,
-                       (const int32_t *) m->ev_count, m->n_ch, m->last_cap, packed_device, words_per_channel, status_device, status_cap);
-    V29_TRY(hipGetLastError());
+    SPG_TRY(hipSetDevice(m->c.device));
+    SPG_TRY(hipMemsetAsync(status_device, 0, sizeof(uint32_t), m->c.stream));
+    hipLaunchKernelGGL(modem_pack_kernel, dim3((m->c.n_ch + 255)/256), dim3(256), 0, m->c.stream, (const int8_t *) m->events,
+                       (const int32_t *) m->ev_count, m->c.n_ch, m->last_cap, packed_device, words_per_channel, status_device, status_cap);
+    SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
 
@@ -910,9 +804,9 @@ int spangpu_modem_events_packed(spangpu_modem_t *m, const int8_t **events, const
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() yet");
-    V29_TRY(hipSetDevice(m->device));
+    SPG_TRY(hipSetDevice(m->c.device));
     const int wpc = 1 + (m->last_cap + 31)/32;              // (no call delivers more data bits than its event buffer has room for)
-    const int scap = (m->n_ch > 1024)  ?  m->n_ch  :  1024;
+    const int scap = (m->c.n_ch > 1024)  ?  m->c.n_ch  :  1024;
     if (wpc > m->packed_wpc  ||  scap > m->packed_status_cap)
     {
         if (m->d_packed) (void) hipFree(m->d_packed);
@@ -920,23 +814,23 @@ int spangpu_modem_events_packed(spangpu_modem_t *m, const int8_t **events, const
         m->d_packed = nullptr;
         m->h_packed = nullptr;
         m->packed_wpc = 0;
-        const size_t words = (size_t) m->n_ch*wpc + 1 + 2*(size_t) scap;
-        V29_TRY(hipMalloc(&m->d_packed, words*sizeof(uint32_t)));
-        V29_TRY(hipHostMalloc(&m->h_packed, words*sizeof(uint32_t)));
+        const size_t words = (size_t) m->c.n_ch*wpc + 1 + 2*(size_t) scap;
+        SPG_TRY(hipMalloc(&m->d_packed, words*sizeof(uint32_t)));
+        SPG_TRY(hipHostMalloc(&m->h_packed, words*sizeof(uint32_t)));
         m->packed_wpc = wpc;
         m->packed_status_cap = scap;
     }
-    uint32_t *d_status = m->d_packed + (size_t) m->n_ch*m->packed_wpc;
+    uint32_t *d_status = m->d_packed + (size_t) m->c.n_ch*m->packed_wpc;
     int rc = spangpu_modem_pack_events(m, m->d_packed, m->packed_wpc, d_status, m->packed_status_cap);
     if (rc < 0)
         return rc;
-    const size_t words = (size_t) m->n_ch*m->packed_wpc + 1 + 2*(size_t) m->packed_status_cap;
-    V29_TRY(hipMemcpyAsync(m->h_packed, m->d_packed, words*sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
-    V29_TRY(hipStreamSynchronize(m->stream));
-    const uint32_t *h_status = m->h_packed + (size_t) m->n_ch*m->packed_wpc;
+    const size_t words = (size_t) m->c.n_ch*m->packed_wpc + 1 + 2*(size_t) m->packed_status_cap;
+    SPG_TRY(hipMemcpyAsync(m->h_packed, m->d_packed, words*sizeof(uint32_t), hipMemcpyDeviceToHost, m->c.stream));
+    SPG_TRY(hipStreamSynchronize(m->c.stream));
+    const uint32_t *h_status = m->h_packed + (size_t) m->c.n_ch*m->packed_wpc;
     if (h_status[0] > (uint32_t) m->packed_status_cap)
         return spangpu_modem_events(m, events, counts);     // (more status reports in one call than channels: the plain way)
-    rc = spangpu_modem_unpack_events(m->h_packed, m->packed_wpc, h_status, m->packed_status_cap, m->n_ch, m->h_events, m->last_cap, m->h_count);
+    rc = spangpu_modem_unpack_events(m->h_packed, m->packed_wpc, h_status, m->packed_status_cap, m->c.n_ch, m->h_events, m->last_cap, m->h_count);
     if (rc < 0)
         return spangpu_modem_events(m, events, counts);     // (a row too short -- an event buffer overflow shows there: same error path)
     *events = m->h_events;
@@ -946,7 +840,7 @@ int spangpu_modem_events_packed(spangpu_modem_t *m, const int8_t **events, const
 
 void *spangpu_modem_get_stream(spangpu_modem_t *m)
 {
-    return m  ?  (void *) m->stream  :  nullptr;
+    return m  ?  (void *) m->c.stream  :  nullptr;
 }
 
 int spangpu_modem_bit_rate(const spangpu_modem_t *m)
@@ -956,7 +850,7 @@ int spangpu_modem_bit_rate(const spangpu_modem_t *m)
 
 int spangpu_modem_device(const spangpu_modem_t *m)
 {
-    return m  ?  m->device  :  SPANGPU_ERR_BAD_ARG;
+    return m  ?  m->c.device  :  SPANGPU_ERR_BAD_ARG;
 }
 
 }   // extern "C"
@@ -1138,20 +1032,16 @@ static int v17_restart_words(uint32_t *w, int bit_rate, int short_train)
     return 0;
 }
 
+// one channel's words, after the work queued on the bank's stream
 static int fetch_words(spangpu_modem_t *m, int channel, uint32_t *w)
 {
-    V29_TRY(hipSetDevice(m->device));
-    V29_TRY(hipStreamSynchronize(m->stream));
-    V29_TRY(hipMemcpy2D(w, sizeof(uint32_t), m->state + channel, (size_t) m->n_ch*sizeof(uint32_t),
-                        sizeof(uint32_t), m->n_words, hipMemcpyDeviceToHost));
-    return SPANGPU_OK;
+    const int rc = core_sync(&m->c);
+    return (rc != SPANGPU_OK)  ?  rc  :  core_rw_words(&m->c, channel, 0, m->c.words, (int32_t *) w, false);
 }
 
 static int store_words(spangpu_modem_t *m, int channel, const uint32_t *w)
 {
-    V29_TRY(hipMemcpy2D(m->state + channel, (size_t) m->n_ch*sizeof(uint32_t), w, sizeof(uint32_t),
-                        sizeof(uint32_t), m->n_words, hipMemcpyHostToDevice));
-    return SPANGPU_OK;
+    return core_rw_words(&m->c, channel, 0, m->c.words, (int32_t *) w, true);
 }
 
 extern "C" {
@@ -1160,19 +1050,18 @@ extern "C" {
 // (order: "State word map" in v29_dev.hpp / v27ter_dev.hpp / v17_dev.hpp).
 int spangpu_modem_get_state(spangpu_modem_t *m, int channel, uint32_t *words)
 {
-    if (m == nullptr  ||  channel < 0  ||  channel >= m->n_ch  ||  words == nullptr)
+    if (m == nullptr  ||  channel < 0  ||  channel >= m->c.n_ch  ||  words == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     const int rc = fetch_words(m, channel, words);
-    return (rc < 0)  ?  rc  :  m->n_words;
+    return (rc < 0)  ?  rc  :  m->c.words;
 }
 
 int spangpu_modem_set_state(spangpu_modem_t *m, int channel, const uint32_t *words)
 {
-    if (m == nullptr  ||  channel < 0  ||  channel >= m->n_ch  ||  words == nullptr)
+    if (m == nullptr  ||  channel < 0  ||  channel >= m->c.n_ch  ||  words == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    V29_TRY(hipSetDevice(m->device));
-    V29_TRY(hipStreamSynchronize(m->stream));
-    return store_words(m, channel, words);
+    const int rc = core_sync(&m->c);
+    return (rc != SPANGPU_OK)  ?  rc  :  store_words(m, channel, words);
 }
 
 // v29_rx_restart(s, bit_rate, old_train) / v27ter_rx_restart(s, bit_rate, old_train) / v17_rx_restart(s, bit_rate,
@@ -1181,7 +1070,7 @@ int spangpu_modem_set_state(spangpu_modem_t *m, int channel, const uint32_t *wor
 // reference.
 int spangpu_modem_restart_ex(spangpu_modem_t *m, int channel, int bit_rate, int train_flag)
 {
-    if (m == nullptr  ||  channel < 0  ||  channel >= m->n_ch)
+    if (m == nullptr  ||  channel < 0  ||  channel >= m->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     uint32_t w[kMaxWords];
     int rc = fetch_words(m, channel, w);
@@ -1209,7 +1098,7 @@ int spangpu_modem_restart_ex(spangpu_modem_t *m, int channel, int bit_rate, int 
 // xxx_rx_restart(s, current rate, false)
 int spangpu_modem_restart(spangpu_modem_t *m, int channel)
 {
-    if (m == nullptr  ||  channel < 0  ||  channel >= m->n_ch)
+    if (m == nullptr  ||  channel < 0  ||  channel >= m->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     int rate = m->bit_rate;
     if (m->kind == SPANGPU_V29)
@@ -1227,7 +1116,7 @@ int spangpu_modem_restart(spangpu_modem_t *m, int channel)
 // v17rx.c:1320-1358)
 int spangpu_modem_fillin(spangpu_modem_t *m, int channel, int len)
 {
-    if (m == nullptr  ||  channel < 0  ||  channel >= m->n_ch  ||  len < 0)
+    if (m == nullptr  ||  channel < 0  ||  channel >= m->c.n_ch  ||  len < 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     uint32_t w[kMaxWords];
     const int rc = fetch_words(m, channel, w);
@@ -1266,17 +1155,17 @@ int spangpu_modem_fillin(spangpu_modem_t *m, int channel, int len)
 // xxx_rx_set_signal_cutoff(s, cutoff) (v29rx.c:163-169)
 int spangpu_modem_set_signal_cutoff(spangpu_modem_t *m, int channel, float cutoff_dbm0)
 {
-    if (m == nullptr  ||  channel < -1  ||  channel >= m->n_ch)
+    if (m == nullptr  ||  channel < -1  ||  channel >= m->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     const int i_on = (m->kind == SPANGPU_V29)  ?  VI_ON_POWER  :  (m->kind == SPANGPU_V17)  ?  XI_ON_POWER  :  WI_ON_POWER;
     if (channel == -1)
     {
         // every channel of the bank (what fax_modems.c:416 does for each of its receivers): the two words are rows of the state
-        V29_TRY(hipSetDevice(m->device));
-        V29_TRY(hipStreamSynchronize(m->stream));
-        uint32_t *row = m->state + (size_t) (m->n_floats + i_on)*m->n_ch;
-        V29_TRY(hipMemsetD32((hipDeviceptr_t) row, (int32_t) (level_dbm0(cutoff_dbm0 + 2.5f)*0.4f), (size_t) m->n_ch));
-        V29_TRY(hipMemsetD32((hipDeviceptr_t) (row + m->n_ch), (int32_t) (level_dbm0(cutoff_dbm0 - 2.5f)*0.4f), (size_t) m->n_ch));
+        SPG_TRY(hipSetDevice(m->c.device));
+        SPG_TRY(hipStreamSynchronize(m->c.stream));
+        uint32_t *row = (uint32_t *) m->c.st + (size_t) (m->n_floats + i_on)*m->c.n_ch;
+        SPG_TRY(hipMemsetD32((hipDeviceptr_t) row, (int32_t) (level_dbm0(cutoff_dbm0 + 2.5f)*0.4f), (size_t) m->c.n_ch));
+        SPG_TRY(hipMemsetD32((hipDeviceptr_t) (row + m->c.n_ch), (int32_t) (level_dbm0(cutoff_dbm0 - 2.5f)*0.4f), (size_t) m->c.n_ch));
         return SPANGPU_OK;
     }
     uint32_t w[kMaxWords];
@@ -1296,19 +1185,19 @@ int spangpu_modem_set_signal_cutoffs(spangpu_modem_t *m, const float *cutoff_dbm
     if (m == nullptr  ||  cutoff_dbm0 == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     const int i_on = (m->kind == SPANGPU_V29)  ?  VI_ON_POWER  :  (m->kind == SPANGPU_V17)  ?  XI_ON_POWER  :  WI_ON_POWER;
-    int32_t *rows = (int32_t *) malloc((size_t) 2*m->n_ch*sizeof(int32_t));
+    int32_t *rows = (int32_t *) malloc((size_t) 2*m->c.n_ch*sizeof(int32_t));
     if (rows == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "malloc");
-    for (int c = 0;  c < m->n_ch;  c++)
+    for (int c = 0;  c < m->c.n_ch;  c++)
     {
         rows[c] = (int32_t) (level_dbm0(cutoff_dbm0[c] + 2.5f)*0.4f);
-        rows[m->n_ch + c] = (int32_t) (level_dbm0(cutoff_dbm0[c] - 2.5f)*0.4f);
+        rows[m->c.n_ch + c] = (int32_t) (level_dbm0(cutoff_dbm0[c] - 2.5f)*0.4f);
     }
-    hipError_t e = hipSetDevice(m->device);
+    hipError_t e = hipSetDevice(m->c.device);
     if (e == hipSuccess)
-        e = hipStreamSynchronize(m->stream);
+        e = hipStreamSynchronize(m->c.stream);
     if (e == hipSuccess)
-        e = hipMemcpy(m->state + (size_t) (m->n_floats + i_on)*m->n_ch, rows, (size_t) 2*m->n_ch*sizeof(int32_t), hipMemcpyHostToDevice);
+        e = hipMemcpy((uint32_t *) m->c.st + (size_t) (m->n_floats + i_on)*m->c.n_ch, rows, (size_t) 2*m->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice);
     free(rows);
     if (e != hipSuccess)
         return spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");

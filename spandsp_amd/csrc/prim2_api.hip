@@ -14,12 +14,9 @@
 #include <mutex>
 
 #include "../../include/spangpu.h"
+#include "bank_host.hpp"
 #include "modem_tables.h"
 #include "v29_common.hpp"
-
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define P2_TRY(x) do { if ((x) != hipSuccess) return spangpu_set_error(SPANGPU_ERR_HIP, #x " failed"); } while (0)
 
 namespace {
 
@@ -148,7 +145,7 @@ int to_device(const T *src, size_t count, int mem, T **dev, bool *owned)
         *dev = (T *) src;
         return SPANGPU_OK;
     }
-    P2_TRY(hipMalloc((void **) dev, count*sizeof(T) + 16));
+    SPG_TRY(hipMalloc((void **) dev, count*sizeof(T) + 16));
     if (hipMemcpy(*dev, src, count*sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
     {
         (void) hipFree(*dev);
@@ -181,17 +178,17 @@ int ready(int device, int items, int n, const void *a, const void *b, const void
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (spangpu_device_count() <= 0)
         return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    P2_TRY(hipSetDevice(device));
+    SPG_TRY(hipSetDevice(device));
     return SPANGPU_OK;
 }
 
 int finish(int mem, void *host, const void *dev, size_t bytes)
 {
-    P2_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        P2_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
     else
-        P2_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -215,10 +212,10 @@ int tables(int device, const float **sine, const uint16_t **sq)
         q[193] = 0;
         float *ds = nullptr;
         uint16_t *dq = nullptr;
-        P2_TRY(hipMalloc((void **) &ds, sizeof(s)));
-        P2_TRY(hipMalloc((void **) &dq, sizeof(q)));
-        P2_TRY(hipMemcpy(ds, s, sizeof(s), hipMemcpyHostToDevice));
-        P2_TRY(hipMemcpy(dq, q, sizeof(q), hipMemcpyHostToDevice));
+        SPG_TRY(hipMalloc((void **) &ds, sizeof(s)));
+        SPG_TRY(hipMalloc((void **) &dq, sizeof(q)));
+        SPG_TRY(hipMemcpy(ds, s, sizeof(s), hipMemcpyHostToDevice));
+        SPG_TRY(hipMemcpy(dq, q, sizeof(q), hipMemcpyHostToDevice));
         g_sine[device] = ds;
         g_sqrt[device] = dq;
     }
@@ -273,15 +270,15 @@ int spangpu_periodogram_prepare_batch(int device, const float *amp, long long a_
     if ((rc = to_device((const float *) diff, 2*half*items, mem, &dd, &o)) < 0) return rc;
     h.keep(dd, o);
     hipLaunchKernelGGL(periodogram_prepare_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) da, a_stride, (float2 *) ds, (float2 *) dd, items, len);
-    P2_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
     {
-        P2_TRY(hipMemcpy(sum, ds, 2*half*items*sizeof(float), hipMemcpyDeviceToHost));
-        P2_TRY(hipMemcpy(diff, dd, 2*half*items*sizeof(float), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(sum, ds, 2*half*items*sizeof(float), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(diff, dd, 2*half*items*sizeof(float), hipMemcpyDeviceToHost));
     }
     else
     {
-        P2_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     }
     return (int) half;
 }
@@ -377,9 +374,9 @@ int spangpu_dds_complexf_batch(int device, uint32_t *phase_acc, const int32_t *p
     if ((rc = to_device((const float *) out, 2*(size_t) items*n, mem, &dout, &o)) < 0) return rc;
     h.keep(dout, o);
     hipLaunchKernelGGL(dds_complexf_kernel, dim3((items + 63)/64), dim3(64), 0, 0, sine, da, (const int32_t *) dr, (float2 *) dout, items, n);
-    P2_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        P2_TRY(hipMemcpy(phase_acc, da, (size_t) items*sizeof(uint32_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(phase_acc, da, (size_t) items*sizeof(uint32_t), hipMemcpyDeviceToHost));
     return finish(mem, out, dout, 2*(size_t) items*n*sizeof(float));
 }
 

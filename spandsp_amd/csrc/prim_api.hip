@@ -16,10 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/spangpu.h"
-
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define PR_TRY(x) do { if ((x) != hipSuccess) return spangpu_set_error(SPANGPU_ERR_HIP, #x " failed"); } while (0)
+#include "bank_host.hpp"
 
 namespace {
 
@@ -194,7 +191,7 @@ int stage_in(const T *src, size_t count, int mem, T **dev, bool *owned)
         *dev = (T *) src;
         return SPANGPU_OK;
     }
-    PR_TRY(hipMalloc((void **) dev, count*sizeof(T) + 16));
+    SPG_TRY(hipMalloc((void **) dev, count*sizeof(T) + 16));
     if (hipMemcpy(*dev, src, count*sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
     {
         (void) hipFree(*dev);           // (the caller's Staged has not been told of it yet)
@@ -227,7 +224,7 @@ int check(int device, int items, int n, const void *a, const void *b, const void
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (spangpu_device_count() <= 0)
         return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    PR_TRY(hipSetDevice(device));
+    SPG_TRY(hipSetDevice(device));
     return SPANGPU_OK;
 }
 
@@ -269,11 +266,11 @@ int spangpu_vec_circular_dot_prodf_batch(int device, const float *x, long long x
     if ((rc = stage_in(z, (size_t) items, mem, &dz, &o)) < 0) return rc;
     st.keep(dz, o);
     hipLaunchKernelGGL(vec_circ_dot_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dx, x_stride, dy, y_stride, dp, dz, items, n);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        PR_TRY(hipMemcpy(z, dz, (size_t) items*sizeof(float), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(z, dz, (size_t) items*sizeof(float), hipMemcpyDeviceToHost));
     else
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -300,11 +297,11 @@ int spangpu_vec_circular_lmsf_batch(int device, const float *x, long long x_stri
     if ((rc = stage_in(error, (size_t) items, mem, &de, &o)) < 0) return rc;
     st.keep(de, o);
     hipLaunchKernelGGL(vec_circ_lms_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dx, x_stride, dy, y_stride, dp, de, items, n);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        PR_TRY(hipMemcpy(y, dy, (size_t) y_stride*items*sizeof(float), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(y, dy, (size_t) y_stride*items*sizeof(float), hipMemcpyDeviceToHost));
     else
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -331,11 +328,11 @@ int spangpu_cvec_circular_dot_prodf_batch(int device, const float *x, long long 
     st.keep(dz, o);
     hipLaunchKernelGGL(cvec_circ_dot_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) dx, x_stride, (const float2 *) dy, y_stride, dp,
                        (float2 *) dz, items, n);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        PR_TRY(hipMemcpy(z, dz, 2*(size_t) items*sizeof(float), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(z, dz, 2*(size_t) items*sizeof(float), hipMemcpyDeviceToHost));
     else
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -363,11 +360,11 @@ int spangpu_cvec_circular_lmsf_batch(int device, const float *x, long long x_str
     st.keep(de, o);
     hipLaunchKernelGGL(cvec_circ_lms_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) dx, x_stride, (float2 *) dy, y_stride, dp,
                        (const float2 *) de, items, n);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        PR_TRY(hipMemcpy(y, dy, 2*(size_t) y_stride*items*sizeof(float), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(y, dy, 2*(size_t) y_stride*items*sizeof(float), hipMemcpyDeviceToHost));
     else
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -388,11 +385,11 @@ int spangpu_power_meter_update_batch(int device, const int16_t *amp, long long s
     if ((rc = stage_in(shift, (size_t) items, mem, &ds, &o)) < 0) return rc;
     st.keep(ds, o);
     hipLaunchKernelGGL(power_meter_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const int16_t *) da, stride, dr, (const int32_t *) ds, items, n);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        PR_TRY(hipMemcpy(reading, dr, (size_t) items*sizeof(int32_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(reading, dr, (size_t) items*sizeof(int32_t), hipMemcpyDeviceToHost));
     else
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -416,11 +413,11 @@ int spangpu_godard_ted_rx_batch(int device, uint32_t *state, const uint32_t *des
     if ((rc = stage_in(samples, (size_t) stride*(items - 1) + n, mem, &dx, &o)) < 0) return rc;
     st.keep(dx, o);
     hipLaunchKernelGGL(godard_rx_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dst, (const uint32_t *) dd, desc_stride, (const float *) dx, stride, items, n);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
-        PR_TRY(hipMemcpy(state, dst, (size_t) items*8*sizeof(uint32_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(state, dst, (size_t) items*8*sizeof(uint32_t), hipMemcpyDeviceToHost));
     else
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     return SPANGPU_OK;
 }
 
@@ -443,15 +440,15 @@ int spangpu_godard_ted_per_baud_batch(int device, uint32_t *state, const uint32_
     if ((rc = stage_in((const int32_t *) correction, (size_t) items, mem, &dc, &o)) < 0) return rc;
     st.keep(dc, o);
     hipLaunchKernelGGL(godard_baud_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dst, (const uint32_t *) dd, desc_stride, dc, items);
-    PR_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     if (mem != SPANGPU_MEM_DEVICE)
     {
-        PR_TRY(hipMemcpy(state, dst, (size_t) items*8*sizeof(uint32_t), hipMemcpyDeviceToHost));
-        PR_TRY(hipMemcpy(correction, dc, (size_t) items*sizeof(int32_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(state, dst, (size_t) items*8*sizeof(uint32_t), hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(correction, dc, (size_t) items*sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     else
     {
-        PR_TRY(hipDeviceSynchronize());
+        SPG_TRY(hipDeviceSynchronize());
     }
     return SPANGPU_OK;
 }

@@ -1,4 +1,7 @@
-// shard_api.hip -- one logical tone bank over several devices, behind the C ABI (include/spangpu.h: spangpu_shard_*).
+// shard_api.hip -- one logical bank over several devices, behind the C ABI (include/spangpu.h): tone banks (spangpu_shard_*),
+// echo cancellers (spangpu_echo_shard_*) and modem receivers (spangpu_modem_shard_*).  The three sit on one shard core
+// (shard_core.hpp: the struct and what needs no GPU; below: create, destroy, sync, post, wait) and keep only what is theirs.
+// No kernel lives in this unit.
 //
 // channels are independent, so a bank of N channels shards as contiguous channel ranges, n/G per device; every
 // device owns its channels' state for their lifetime; inputs are delivered per device; nothing is exchanged between compute
@@ -14,15 +17,12 @@
 #include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include "../../include/spangpu.h"
+#include "bank_host.hpp"
+#include "shard_core.hpp"
 
-extern "C" int spangpu_set_error(int code, const char *msg);
-
-#define SH_TRY(x) do { if ((x) != hipSuccess) return spangpu_set_error(SPANGPU_ERR_HIP, #x " failed"); } while (0)
-
-enum { kMaxShards = 64 };
+using namespace spg;
 
 // How shard i's results reach the collecting device: SPANGPU_LINK_SAME (it is the collecting device), SPANGPU_LINK_PEER (peer
 // access is on: hipMemcpyPeerAsync goes device to device over xGMI) or SPANGPU_LINK_STAGED (the devices cannot reach each
@@ -54,38 +54,149 @@ static hipError_t gather_copy(void *dst, int dst_device, const void *src, int sr
     return hipMemcpyPeerAsync(dst, dst_device, src, src_device, bytes, st);
 }
 
-static int shard_info(int n, const int *device, const int *first, const int *link, int collect_device, int i, spangpu_shard_info_t *info)
+// ---- the shard core's calls that touch a device ---------------------------------------------------------------------------
+
+template <typename B, int (*Sync)(B *), int (*Destroy)(B *), void *(*GetStream)(B *)>
+static const ShardOps kOps = {[](void *b) { return Sync((B *) b); }, [](void *b) { return Destroy((B *) b); },
+                              [](void *b) { return GetStream((B *) b); }};
+
+static void shard_destroy(ShardCore *c)
 {
-    if (i < 0  ||  i >= n  ||  info == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad shard");
-    info->device = device[i];
-    info->first_channel = first[i];
-    info->n_channels = first[i + 1] - first[i];
-    info->collect_device = collect_device;
-    info->link = link[i];
-    info->forced_peer_copy = g_force_peer.load();
+    for (int i = 0;  i < c->n;  i++)
+    {
+        (void) hipSetDevice(c->device[i]);
+        if (c->bank[i])
+        {
+            (void) c->ops->sync(c->bank[i]);
+            (void) c->ops->destroy(c->bank[i]);
+        }
+        if (c->out[i]) (void) hipFree(c->out[i]);
+        for (int k = 0;  k < 2;  k++)
+        {
+            if (c->done[k][i]) (void) hipEventDestroy(c->done[k][i]);
+        }
+    }
+    (void) hipSetDevice(c->collect_device);
+    for (int k = 0;  k < 2;  k++)
+    {
+        if (c->gathered[k]) (void) hipFree(c->gathered[k]);
+    }
+    if (c->h_gathered) (void) hipHostFree(c->h_gathered);
+}
+
+// Deals the channels, then per shard: its device, its bank (make_bank(i, device, channels, &bank): what it made is kept even
+// where it fails, for the destroy that follows), its result buffer of out_per_channel bytes a channel, its two events, its
+// link; then the two collecting slots, and the pinned copy of one where the family reorders on the host.  A failure leaves
+// the core as far as it got: the caller's destroy unwinds it.
+template <typename F>
+static int shard_create(ShardCore *c, const ShardOps *ops, const int *devices, int n_devices, int n_channels, size_t out_per_channel,
+                        bool pinned, const char *gathered_what, F make_bank)
+{
+    c->ops = ops;
+    if (shard_deal(c, devices, n_devices, n_channels) != SPANGPU_OK)
+    {
+        c->n = 0;
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "channels do not deal out over the shards");
+    }
+    int rc = SPANGPU_OK;
+    for (int i = 0;  i < n_devices  &&  rc == SPANGPU_OK;  i++)
+    {
+        const int mine = shard_channels(c, i);
+        if (hipSetDevice(devices[i]) != hipSuccess)
+            rc = spangpu_set_error(SPANGPU_ERR_HIP, "hipSetDevice failed");
+        else if ((rc = make_bank(i, devices[i], mine, &c->bank[i])) == SPANGPU_OK)
+        {
+            if (hipMalloc(&c->out[i], out_per_channel*mine) != hipSuccess
+                ||  hipEventCreateWithFlags(&c->done[0][i], hipEventDisableTiming) != hipSuccess
+                ||  hipEventCreateWithFlags(&c->done[1][i], hipEventDisableTiming) != hipSuccess)
+                rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of device memory");
+        }
+        if (rc == SPANGPU_OK)
+            c->link[i] = link_to(devices[i], c->collect_device);
+    }
+    if (rc == SPANGPU_OK)
+    {
+        if (hipSetDevice(c->collect_device) != hipSuccess
+            ||  hipMalloc(&c->gathered[0], out_per_channel*n_channels) != hipSuccess
+            ||  hipMalloc(&c->gathered[1], out_per_channel*n_channels) != hipSuccess
+            ||  (pinned  &&  hipHostMalloc(&c->h_gathered, out_per_channel*n_channels) != hipSuccess))
+            rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, gathered_what);
+    }
+    return rc;
+}
+
+static int shard_sync(ShardCore *c)
+{
+    if (c == nullptr)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard");
+    for (int i = 0;  i < c->n;  i++)
+    {
+        SPG_TRY(hipSetDevice(c->device[i]));
+        const int rc = c->ops->sync(c->bank[i]);
+        if (rc < 0)
+            return rc;
+    }
     return SPANGPU_OK;
 }
 
+// Behind what shard i's bank has queued on its stream: `bytes` of its result buffer go to byte `offset` of collecting slot
+// `slot`, and the slot's event of the shard is recorded.  (The shard's device is current.)
+static int shard_post(ShardCore *c, int i, int slot, size_t offset, size_t bytes)
+{
+    hipStream_t st = (hipStream_t) c->ops->get_stream(c->bank[i]);
+    SPG_TRY(gather_copy((uint8_t *) c->gathered[slot] + offset, c->collect_device, c->out[i], c->device[i], bytes, st));
+    SPG_TRY(hipEventRecord(c->done[slot][i], st));
+    return SPANGPU_OK;
+}
+
+static int shard_last_slot(const ShardCore *c)
+{
+    return (int) ((c->steps - 1u) & 1u);
+}
+
+// `hip_stream` (a stream of the collecting device; NULL: the calling host thread) waits until every shard's bytes of the last
+// step have arrived.
+static int shard_wait(ShardCore *c, void *hip_stream)
+{
+    const int slot = shard_last_slot(c);
+    for (int i = 0;  i < c->n;  i++)
+    {
+        if (hip_stream)
+        {
+            SPG_TRY(hipSetDevice(c->collect_device));
+            SPG_TRY(hipStreamWaitEvent((hipStream_t) hip_stream, c->done[slot][i], 0));
+        }
+        else
+        {
+            SPG_TRY(hipSetDevice(c->device[i]));
+            SPG_TRY(hipEventSynchronize(c->done[slot][i]));
+        }
+    }
+    return SPANGPU_OK;
+}
+
+// the last step's slot in the pinned host copy
+static int shard_fetch(ShardCore *c, size_t bytes)
+{
+    SPG_TRY(hipSetDevice(c->collect_device));
+    SPG_TRY(hipMemcpy(c->h_gathered, c->gathered[shard_last_slot(c)], bytes, hipMemcpyDeviceToHost));
+    return SPANGPU_OK;
+}
+
+template <typename S>
+static ShardCore *core_of(S *s)
+{
+    return s  ?  (ShardCore *) &s->c  :  nullptr;
+}
+
+// ---- tone banks: the digit byte of every block and channel -----------------------------------------------------------------
 struct spangpu_shard_s
 {
-    int link[kMaxShards];               // SPANGPU_LINK_*: how shard i's bytes reach the collecting device
-    int n;                              // shards
-    int n_ch;                           // channels of the whole bank
+    ShardCore c;                        // out[i] = digits [max_blocks][channels of the shard]; a slot is shard-major, shard i's
+                                        // [max_blocks][n_i] at max_blocks*first[i]
     int kind;
-    int collect_device;                 // where the gathered bytes go: the first shard's device
-    int device[kMaxShards];
-    int first[kMaxShards + 1];          // first channel of shard i; first[n] = n_ch
-    spangpu_bank_t *bank[kMaxShards];
-    uint8_t *digits[kMaxShards];        // [max_blocks][channels of the shard], on the shard's device
-    hipEvent_t done[2][kMaxShards];     // the shard's bytes of a step have arrived on the collecting device (per slot)
-    uint8_t *gathered[2];               // on collect_device: shard-major, shard i's [max_blocks][n_i] at max_blocks*first[i].  Two
-                                        // slots used in turn: a step's bytes stay whole while the next step is queued and runs
-                                        // (a reader that takes a step's bytes before the step after next is queued never sees a mix)
-    uint8_t *h_gathered;                // pinned host copy (spangpu_shard_digits_host)
     int max_blocks;
     int last_blocks;
-    unsigned steps;                     // spangpu_shard_rx() calls so far; the last one wrote slot (steps - 1) & 1
 };
 
 extern "C" {
@@ -94,33 +205,12 @@ int spangpu_shard_destroy(spangpu_shard_t *s)
 {
     if (s == nullptr)
         return SPANGPU_OK;
-    for (int i = 0;  i < s->n;  i++)
-    {
-        (void) hipSetDevice(s->device[i]);
-        if (s->bank[i])
-        {
-            (void) spangpu_bank_sync(s->bank[i]);
-            (void) spangpu_bank_destroy(s->bank[i]);
-        }
-        if (s->digits[i]) (void) hipFree(s->digits[i]);
-        for (int k = 0;  k < 2;  k++)
-        {
-            if (s->done[k][i]) (void) hipEventDestroy(s->done[k][i]);
-        }
-    }
-    (void) hipSetDevice(s->collect_device);
-    for (int k = 0;  k < 2;  k++)
-    {
-        if (s->gathered[k]) (void) hipFree(s->gathered[k]);
-    }
-    if (s->h_gathered) (void) hipHostFree(s->h_gathered);
+    shard_destroy(&s->c);
     free(s);
     return SPANGPU_OK;
 }
 
-// devices[i] is the HIP device of shard i (a device may appear more than once: two shards on one GPU, each with its own
-// stream -- how a one-GPU box exercises this path).  Channels are dealt in contiguous ranges, as evenly as they go, in
-// multiples of 64 (a wavefront's worth) except for the last shard.  max_samples sizes the digit buffers.
+// max_samples sizes the digit buffers.  (The dealing of the channels over devices[]: shard_deal(), shard_core.hpp.)
 int spangpu_shard_create(spangpu_shard_t **out, const int *devices, int n_devices, int kind, int n_channels, int max_samples,
                          const void *params, size_t params_size)
 {
@@ -132,56 +222,15 @@ int spangpu_shard_create(spangpu_shard_t **out, const int *devices, int n_device
     spangpu_shard_t *s = (spangpu_shard_t *) calloc(1, sizeof(*s));
     if (s == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory");
-    s->n = n_devices;
-    s->n_ch = n_channels;
     s->kind = kind;
-    s->collect_device = devices[0];
     // shortest block of the kinds above: DTMF 102 samples
     s->max_blocks = max_samples/102 + 2;
-    const int per = ((n_channels + n_devices - 1)/n_devices + 63)/64*64;
-    int at = 0;
-    for (int i = 0;  i < n_devices;  i++)
-    {
-        s->device[i] = devices[i];
-        s->first[i] = at;
-        int left = n_channels - at;
-        int mine = (i == n_devices - 1)  ?  left  :  ((per < left - (n_devices - 1 - i))  ?  per  :  (left - (n_devices - 1 - i)));
-        if (mine < 1)
-            mine = 1;
-        at += mine;
-    }
-    s->first[n_devices] = n_channels;
-    if (at != n_channels)
-    {
-        free(s);
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "channels do not deal out over the shards");
-    }
-    int rc = SPANGPU_OK;
-    for (int i = 0;  i < n_devices  &&  rc == SPANGPU_OK;  i++)
-    {
-        const int mine = s->first[i + 1] - s->first[i];
-        if (hipSetDevice(devices[i]) != hipSuccess)
-            rc = spangpu_set_error(SPANGPU_ERR_HIP, "hipSetDevice failed");
-        else if ((rc = spangpu_bank_create(&s->bank[i], devices[i], kind, mine, params, params_size)) == SPANGPU_OK)
-        {
-            if (hipMalloc((void **) &s->digits[i], (size_t) s->max_blocks*mine) != hipSuccess
-                ||  hipEventCreateWithFlags(&s->done[0][i], hipEventDisableTiming) != hipSuccess
-                ||  hipEventCreateWithFlags(&s->done[1][i], hipEventDisableTiming) != hipSuccess)
-                rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of device memory");
-            else
-                rc = spangpu_bank_set_digits_buffer(s->bank[i], s->digits[i], (size_t) s->max_blocks*mine);
-        }
-        if (rc == SPANGPU_OK)
-            s->link[i] = link_to(devices[i], s->collect_device);
-    }
-    if (rc == SPANGPU_OK)
-    {
-        if (hipSetDevice(s->collect_device) != hipSuccess
-            ||  hipMalloc((void **) &s->gathered[0], (size_t) s->max_blocks*n_channels) != hipSuccess
-            ||  hipMalloc((void **) &s->gathered[1], (size_t) s->max_blocks*n_channels) != hipSuccess
-            ||  hipHostMalloc((void **) &s->h_gathered, (size_t) s->max_blocks*n_channels) != hipSuccess)
-            rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory for the gathered digits");
-    }
+    int rc = shard_create(&s->c, &kOps<spangpu_bank_t, spangpu_bank_sync, spangpu_bank_destroy, spangpu_bank_get_stream>, devices, n_devices,
+                          n_channels, (size_t) s->max_blocks, true, "out of memory for the gathered digits",
+                          [&](int, int device, int mine, void **bank)
+                          { return spangpu_bank_create((spangpu_bank_t **) bank, device, kind, mine, params, params_size); });
+    for (int i = 0;  i < s->c.n  &&  rc == SPANGPU_OK;  i++)
+        rc = spangpu_bank_set_digits_buffer((spangpu_bank_t *) s->c.bank[i], (uint8_t *) s->c.out[i], (size_t) s->max_blocks*shard_channels(&s->c, i));
     if (rc != SPANGPU_OK)
     {
         spangpu_shard_destroy(s);
@@ -191,26 +240,19 @@ int spangpu_shard_create(spangpu_shard_t **out, const int *devices, int n_device
     return SPANGPU_OK;
 }
 
-int spangpu_shard_count(const spangpu_shard_t *s) { return s  ?  s->n  :  SPANGPU_ERR_BAD_ARG; }
-int spangpu_shard_channels(const spangpu_shard_t *s) { return s  ?  s->n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_shard_count(const spangpu_shard_t *s) { return s  ?  s->c.n  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_shard_channels(const spangpu_shard_t *s) { return s  ?  s->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 
 // Shard i: its device, its first channel and how many it has; its bank (for everything a bank can do: parameters, state,
 // records, a stream of the caller's choice ...).
 int spangpu_shard_range(const spangpu_shard_t *s, int i, int *device, int *first_channel, int *n_channels)
 {
-    if (s == nullptr  ||  i < 0  ||  i >= s->n)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad shard");
-    if (device) *device = s->device[i];
-    if (first_channel) *first_channel = s->first[i];
-    if (n_channels) *n_channels = s->first[i + 1] - s->first[i];
-    return SPANGPU_OK;
+    return shard_range(core_of(s), i, device, first_channel, n_channels);
 }
 
 int spangpu_shard_info(const spangpu_shard_t *s, int i, spangpu_shard_info_t *info)
 {
-    if (s == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard set");
-    return shard_info(s->n, s->device, s->first, s->link, s->collect_device, i, info);
+    return shard_info(core_of(s), i, g_force_peer.load(), info);
 }
 
 int spangpu_tune_force_peer_copy(int on)
@@ -220,7 +262,7 @@ int spangpu_tune_force_peer_copy(int on)
 
 spangpu_bank_t *spangpu_shard_bank(spangpu_shard_t *s, int i)
 {
-    return (s  &&  i >= 0  &&  i < s->n)  ?  s->bank[i]  :  nullptr;
+    return (spangpu_bank_t *) shard_bank(core_of(s), i);
 }
 
 // One step of the whole bank: amp[i] = shard i's frame on ITS device (channel-major rows of `stride` samples, its own
@@ -234,20 +276,15 @@ int spangpu_shard_rx(spangpu_shard_t *s, const int16_t *const *amp, int samples,
     const int maxb = (samples + block - 1)/block;
     if (maxb > s->max_blocks)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "more samples than the shard was made for");
-    const int slot = (int) (s->steps & 1u);
-    for (int i = 0;  i < s->n;  i++)
+    const int slot = (int) (s->c.steps & 1u);
+    for (int i = 0;  i < s->c.n;  i++)
     {
-        const int mine = s->first[i + 1] - s->first[i];
-        SH_TRY(hipSetDevice(s->device[i]));
-        const int rc = spangpu_bank_rx(s->bank[i], amp[i], SPANGPU_MEM_DEVICE, SPANGPU_LAYOUT_CHANNEL_MAJOR, samples, stride);
-        if (rc < 0)
+        SPG_TRY(hipSetDevice(s->c.device[i]));
+        int rc = spangpu_bank_rx((spangpu_bank_t *) s->c.bank[i], amp[i], SPANGPU_MEM_DEVICE, SPANGPU_LAYOUT_CHANNEL_MAJOR, samples, stride);
+        if (rc < 0  ||  (rc = shard_post(&s->c, i, slot, (size_t) s->max_blocks*s->c.first[i], (size_t) maxb*shard_channels(&s->c, i))) < 0)
             return rc;
-        hipStream_t st = (hipStream_t) spangpu_bank_get_stream(s->bank[i]);
-        uint8_t *dst = s->gathered[slot] + (size_t) s->max_blocks*s->first[i];
-        SH_TRY(gather_copy(dst, s->collect_device, s->digits[i], s->device[i], (size_t) maxb*mine, st));
-        SH_TRY(hipEventRecord(s->done[slot][i], st));
     }
-    s->steps++;
+    s->c.steps++;
     s->last_blocks = maxb;
     return maxb;
 }
@@ -259,24 +296,13 @@ int spangpu_shard_digits_device(spangpu_shard_t *s, void *hip_stream, const uint
 {
     if (s == nullptr  ||  digits == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (s->steps == 0)
+    if (s->c.steps == 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no step has been queued yet");
-    const int slot = (int) ((s->steps - 1u) & 1u);
-    for (int i = 0;  i < s->n;  i++)
-    {
-        if (hip_stream)
-        {
-            SH_TRY(hipSetDevice(s->collect_device));
-            SH_TRY(hipStreamWaitEvent((hipStream_t) hip_stream, s->done[slot][i], 0));
-        }
-        else
-        {
-            SH_TRY(hipSetDevice(s->device[i]));
-            SH_TRY(hipEventSynchronize(s->done[slot][i]));
-        }
-    }
-    *digits = s->gathered[slot];
-    if (collect_device) *collect_device = s->collect_device;
+    const int rc = shard_wait(&s->c, hip_stream);
+    if (rc < 0)
+        return rc;
+    *digits = (const uint8_t *) s->c.gathered[shard_last_slot(&s->c)];
+    if (collect_device) *collect_device = s->c.collect_device;
     if (max_blocks) *max_blocks = s->max_blocks;
     return s->last_blocks;
 }
@@ -291,34 +317,21 @@ int spangpu_shard_digits_host(spangpu_shard_t *s, uint8_t *out, size_t out_bytes
     const int nb = spangpu_shard_digits_device(s, nullptr, &dev, nullptr, nullptr);
     if (nb < 0)
         return nb;
-    if (out_bytes < (size_t) nb*s->n_ch)
+    if (out_bytes < (size_t) nb*s->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "destination too small");
-    SH_TRY(hipSetDevice(s->collect_device));
-    SH_TRY(hipMemcpy(s->h_gathered, dev, (size_t) s->max_blocks*s->n_ch, hipMemcpyDeviceToHost));
-    for (int i = 0;  i < s->n;  i++)
-    {
-        const int mine = s->first[i + 1] - s->first[i];
-        const uint8_t *src = s->h_gathered + (size_t) s->max_blocks*s->first[i];
-        for (int b = 0;  b < nb;  b++)
-            memcpy(out + (size_t) b*s->n_ch + s->first[i], src + (size_t) b*mine, (size_t) mine);
-    }
+    const int rc = shard_fetch(&s->c, (size_t) s->max_blocks*s->c.n_ch);
+    if (rc < 0)
+        return rc;
+    shard_rows_to_channels(&s->c, (const uint8_t *) s->c.h_gathered, s->max_blocks, nb, out);
     return nb;
 }
 
 int spangpu_shard_sync(spangpu_shard_t *s)
 {
-    if (s == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard");
-    for (int i = 0;  i < s->n;  i++)
-    {
-        SH_TRY(hipSetDevice(s->device[i]));
-        const int rc = spangpu_bank_sync(s->bank[i]);
-        if (rc < 0)
-            return rc;
-    }
-    return SPANGPU_OK;
+    return shard_sync(core_of(s));
 }
 
+}   // extern "C"
 
 // ---- BASELINE configs[4]'s own object: the echo cancellers of N lines over several devices --------------------------------
 // Channels in contiguous ranges (multiples of 64), every device owning its lines' taps, history and control words for their
@@ -329,61 +342,17 @@ int spangpu_shard_sync(spangpu_shard_t *s)
 // ERLE is tests/echo_tests.c:577-594's level measurement, 10 log10(sum rx^2 / sum clean^2).)
 struct spangpu_echo_shard_s
 {
-    int link[kMaxShards];               // SPANGPU_LINK_*
-    int n;
-    int n_ch;
-    int collect_device;
-    int device[kMaxShards];
-    int first[kMaxShards + 1];
-    spangpu_echo_t *bank[kMaxShards];
-    float *erle[kMaxShards];            // [channels of the shard] on the shard's device
-    hipEvent_t done[2][kMaxShards];
-    float *gathered[2];                 // [n_ch] on collect_device, the whole bank's channel order
-    unsigned reports;
+    ShardCore c;                        // out[i] = float erle[channels of the shard]; a slot is float [n_ch], the whole bank's
+                                        // channel order; steps counts the reports
 };
 
-// (the dealing of spangpu_shard_create(): contiguous ranges, multiples of 64 but for the last)
-static int deal_channels(int n_channels, int n_devices, int *first)
-{
-    const int per = ((n_channels + n_devices - 1)/n_devices + 63)/64*64;
-    int at = 0;
-    for (int i = 0;  i < n_devices;  i++)
-    {
-        first[i] = at;
-        const int left = n_channels - at;
-        int mine = (i == n_devices - 1)  ?  left  :  ((per < left - (n_devices - 1 - i))  ?  per  :  (left - (n_devices - 1 - i)));
-        if (mine < 1)
-            mine = 1;
-        at += mine;
-    }
-    first[n_devices] = n_channels;
-    return (at == n_channels)  ?  SPANGPU_OK  :  SPANGPU_ERR_BAD_ARG;
-}
-
+extern "C" {
 
 int spangpu_echo_shard_destroy(spangpu_echo_shard_t *s)
 {
     if (s == nullptr)
         return SPANGPU_OK;
-    for (int i = 0;  i < s->n;  i++)
-    {
-        (void) hipSetDevice(s->device[i]);
-        if (s->bank[i])
-        {
-            (void) spangpu_echo_sync(s->bank[i]);
-            (void) spangpu_echo_destroy(s->bank[i]);
-        }
-        if (s->erle[i]) (void) hipFree(s->erle[i]);
-        for (int k = 0;  k < 2;  k++)
-        {
-            if (s->done[k][i]) (void) hipEventDestroy(s->done[k][i]);
-        }
-    }
-    (void) hipSetDevice(s->collect_device);
-    for (int k = 0;  k < 2;  k++)
-    {
-        if (s->gathered[k]) (void) hipFree(s->gathered[k]);
-    }
+    shard_destroy(&s->c);
     free(s);
     return SPANGPU_OK;
 }
@@ -396,40 +365,14 @@ int spangpu_echo_shard_create(spangpu_echo_shard_t **out, const int *devices, in
     spangpu_echo_shard_t *s = (spangpu_echo_shard_t *) calloc(1, sizeof(*s));
     if (s == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory");
-    s->n = n_devices;
-    s->n_ch = n_channels;
-    s->collect_device = devices[0];
-    if (deal_channels(n_channels, n_devices, s->first) != SPANGPU_OK)
-    {
-        free(s);
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "channels do not deal out over the shards");
-    }
-    int rc = SPANGPU_OK;
-    for (int i = 0;  i < n_devices  &&  rc == SPANGPU_OK;  i++)
-    {
-        const int mine = s->first[i + 1] - s->first[i];
-        s->device[i] = devices[i];
-        if (hipSetDevice(devices[i]) != hipSuccess)
-            rc = spangpu_set_error(SPANGPU_ERR_HIP, "hipSetDevice failed");
-        else if ((rc = spangpu_echo_create(&s->bank[i], devices[i], mine, taps, adaption_mode)) == SPANGPU_OK)
-        {
-            if (hipMalloc((void **) &s->erle[i], (size_t) mine*sizeof(float)) != hipSuccess
-                ||  hipEventCreateWithFlags(&s->done[0][i], hipEventDisableTiming) != hipSuccess
-                ||  hipEventCreateWithFlags(&s->done[1][i], hipEventDisableTiming) != hipSuccess)
-                rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of device memory");
-            else
-                rc = spangpu_echo_stats(s->bank[i], 2);         // the update kernel itself keeps the energy sums
-        }
-        if (rc == SPANGPU_OK)
-            s->link[i] = link_to(devices[i], s->collect_device);
-    }
-    if (rc == SPANGPU_OK)
-    {
-        if (hipSetDevice(s->collect_device) != hipSuccess
-            ||  hipMalloc((void **) &s->gathered[0], (size_t) n_channels*sizeof(float)) != hipSuccess
-            ||  hipMalloc((void **) &s->gathered[1], (size_t) n_channels*sizeof(float)) != hipSuccess)
-            rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory for the gathered ERLE");
-    }
+    const int rc = shard_create(&s->c, &kOps<spangpu_echo_t, spangpu_echo_sync, spangpu_echo_destroy, spangpu_echo_get_stream>, devices, n_devices,
+                                n_channels, sizeof(float), false, "out of memory for the gathered ERLE",
+                                [&](int, int device, int mine, void **bank)
+                                {
+                                    const int r = spangpu_echo_create((spangpu_echo_t **) bank, device, mine, taps, adaption_mode);
+                                    // the update kernel itself keeps the energy sums
+                                    return (r != SPANGPU_OK)  ?  r  :  spangpu_echo_stats((spangpu_echo_t *) *bank, 2);
+                                });
     if (rc != SPANGPU_OK)
     {
         spangpu_echo_shard_destroy(s);
@@ -439,28 +382,21 @@ int spangpu_echo_shard_create(spangpu_echo_shard_t **out, const int *devices, in
     return SPANGPU_OK;
 }
 
-int spangpu_echo_shard_count(const spangpu_echo_shard_t *s) { return s  ?  s->n  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_echo_shard_count(const spangpu_echo_shard_t *s) { return s  ?  s->c.n  :  SPANGPU_ERR_BAD_ARG; }
 
 int spangpu_echo_shard_range(const spangpu_echo_shard_t *s, int i, int *device, int *first_channel, int *n_channels)
 {
-    if (s == nullptr  ||  i < 0  ||  i >= s->n)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad shard");
-    if (device) *device = s->device[i];
-    if (first_channel) *first_channel = s->first[i];
-    if (n_channels) *n_channels = s->first[i + 1] - s->first[i];
-    return SPANGPU_OK;
+    return shard_range(core_of(s), i, device, first_channel, n_channels);
 }
 
 int spangpu_echo_shard_info(const spangpu_echo_shard_t *s, int i, spangpu_shard_info_t *info)
 {
-    if (s == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard set");
-    return shard_info(s->n, s->device, s->first, s->link, s->collect_device, i, info);
+    return shard_info(core_of(s), i, g_force_peer.load(), info);
 }
 
 spangpu_echo_t *spangpu_echo_shard_bank(spangpu_echo_shard_t *s, int i)
 {
-    return (s  &&  i >= 0  &&  i < s->n)  ?  s->bank[i]  :  nullptr;
+    return (spangpu_echo_t *) shard_bank(core_of(s), i);
 }
 
 // One step: tx[i], rx[i], clean[i] = shard i's rows on ITS device (its own lines only), `samples` per line.  Queues one
@@ -470,10 +406,10 @@ int spangpu_echo_shard_update(spangpu_echo_shard_t *s, const int16_t *const *tx,
 {
     if (s == nullptr  ||  tx == nullptr  ||  rx == nullptr  ||  clean == nullptr  ||  samples <= 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    for (int i = 0;  i < s->n;  i++)
+    for (int i = 0;  i < s->c.n;  i++)
     {
-        SH_TRY(hipSetDevice(s->device[i]));
-        const int rc = spangpu_echo_update(s->bank[i], tx[i], rx[i], clean[i], SPANGPU_MEM_DEVICE, samples, stride, 0);
+        SPG_TRY(hipSetDevice(s->c.device[i]));
+        const int rc = spangpu_echo_update((spangpu_echo_t *) s->c.bank[i], tx[i], rx[i], clean[i], SPANGPU_MEM_DEVICE, samples, stride, 0);
         if (rc < 0)
             return rc;
     }
@@ -486,22 +422,18 @@ int spangpu_echo_shard_report(spangpu_echo_shard_t *s, int reset)
 {
     if (s == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard");
-    const int slot = (int) (s->reports & 1u);
-    for (int i = 0;  i < s->n;  i++)
+    const int slot = (int) (s->c.steps & 1u);
+    for (int i = 0;  i < s->c.n;  i++)
     {
-        const int mine = s->first[i + 1] - s->first[i];
-        SH_TRY(hipSetDevice(s->device[i]));
-        int rc = spangpu_echo_erle(s->bank[i], s->erle[i], SPANGPU_MEM_DEVICE);
-        if (rc < 0)
+        spangpu_echo_t *bank = (spangpu_echo_t *) s->c.bank[i];
+        SPG_TRY(hipSetDevice(s->c.device[i]));
+        int rc = spangpu_echo_erle(bank, (float *) s->c.out[i], SPANGPU_MEM_DEVICE);
+        if (rc < 0  ||  (rc = shard_post(&s->c, i, slot, (size_t) s->c.first[i]*sizeof(float), (size_t) shard_channels(&s->c, i)*sizeof(float))) < 0)
             return rc;
-        hipStream_t st = (hipStream_t) spangpu_echo_get_stream(s->bank[i]);
-        float *dst = s->gathered[slot] + s->first[i];
-        SH_TRY(gather_copy(dst, s->collect_device, s->erle[i], s->device[i], (size_t) mine*sizeof(float), st));
-        SH_TRY(hipEventRecord(s->done[slot][i], st));
-        if (reset  &&  (rc = spangpu_echo_stats_reset(s->bank[i], SPANGPU_ECHO_STATS_SUMS)) < 0)
+        if (reset  &&  (rc = spangpu_echo_stats_reset(bank, SPANGPU_ECHO_STATS_SUMS)) < 0)
             return rc;
     }
-    s->reports++;
+    s->c.steps++;
     return SPANGPU_OK;
 }
 
@@ -510,53 +442,35 @@ int spangpu_echo_shard_erle_device(spangpu_echo_shard_t *s, void *hip_stream, co
 {
     if (s == nullptr  ||  erle_db == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (s->reports == 0)
+    if (s->c.steps == 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no report has been queued yet");
-    const int slot = (int) ((s->reports - 1u) & 1u);
-    for (int i = 0;  i < s->n;  i++)
-    {
-        if (hip_stream)
-        {
-            SH_TRY(hipSetDevice(s->collect_device));
-            SH_TRY(hipStreamWaitEvent((hipStream_t) hip_stream, s->done[slot][i], 0));
-        }
-        else
-        {
-            SH_TRY(hipSetDevice(s->device[i]));
-            SH_TRY(hipEventSynchronize(s->done[slot][i]));
-        }
-    }
-    *erle_db = s->gathered[slot];
-    if (collect_device) *collect_device = s->collect_device;
-    return s->n_ch;
+    const int rc = shard_wait(&s->c, hip_stream);
+    if (rc < 0)
+        return rc;
+    *erle_db = (const float *) s->c.gathered[shard_last_slot(&s->c)];
+    if (collect_device) *collect_device = s->c.collect_device;
+    return s->c.n_ch;
 }
 
 int spangpu_echo_shard_erle_host(spangpu_echo_shard_t *s, float *out, size_t out_floats)
 {
     const float *dev;
-    if (s == nullptr  ||  out == nullptr  ||  out_floats < (size_t) s->n_ch)
+    if (s == nullptr  ||  out == nullptr  ||  out_floats < (size_t) s->c.n_ch)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     const int n = spangpu_echo_shard_erle_device(s, nullptr, &dev, nullptr);
     if (n < 0)
         return n;
-    SH_TRY(hipSetDevice(s->collect_device));
-    SH_TRY(hipMemcpy(out, dev, (size_t) n*sizeof(float), hipMemcpyDeviceToHost));
+    SPG_TRY(hipSetDevice(s->c.collect_device));
+    SPG_TRY(hipMemcpy(out, dev, (size_t) n*sizeof(float), hipMemcpyDeviceToHost));
     return n;
 }
 
 int spangpu_echo_shard_sync(spangpu_echo_shard_t *s)
 {
-    if (s == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard");
-    for (int i = 0;  i < s->n;  i++)
-    {
-        SH_TRY(hipSetDevice(s->device[i]));
-        const int rc = spangpu_echo_sync(s->bank[i]);
-        if (rc < 0)
-            return rc;
-    }
-    return SPANGPU_OK;
+    return shard_sync(core_of(s));
 }
+
+}   // extern "C"
 
 // ---- modem receivers over several devices: the put_bit streams of a step gathered to one device ---------------------------
 // What travels per shard and step is what spangpu_modem_copy_events() lays out: int32 counts[n_i], then int8 events[n_i][per]
@@ -564,45 +478,17 @@ int spangpu_echo_shard_sync(spangpu_echo_shard_t *s)
 // (4 + per)*first_channel(i) of the collecting buffer.
 struct spangpu_modem_shard_s
 {
-    int link[kMaxShards];               // SPANGPU_LINK_*
-    int n;
-    int n_ch;
+    ShardCore c;                        // out[i] = the shard's block
     int per;
-    int collect_device;
-    int device[kMaxShards];
-    int first[kMaxShards + 1];
-    spangpu_modem_t *bank[kMaxShards];
-    uint8_t *ev[kMaxShards];
-    hipEvent_t done[2][kMaxShards];
-    uint8_t *gathered[2];
-    uint8_t *h_gathered;
-    unsigned steps;
 };
+
+extern "C" {
 
 int spangpu_modem_shard_destroy(spangpu_modem_shard_t *s)
 {
     if (s == nullptr)
         return SPANGPU_OK;
-    for (int i = 0;  i < s->n;  i++)
-    {
-        (void) hipSetDevice(s->device[i]);
-        if (s->bank[i])
-        {
-            (void) spangpu_modem_sync(s->bank[i]);
-            (void) spangpu_modem_destroy(s->bank[i]);
-        }
-        if (s->ev[i]) (void) hipFree(s->ev[i]);
-        for (int k = 0;  k < 2;  k++)
-        {
-            if (s->done[k][i]) (void) hipEventDestroy(s->done[k][i]);
-        }
-    }
-    (void) hipSetDevice(s->collect_device);
-    for (int k = 0;  k < 2;  k++)
-    {
-        if (s->gathered[k]) (void) hipFree(s->gathered[k]);
-    }
-    if (s->h_gathered) (void) hipHostFree(s->h_gathered);
+    shard_destroy(&s->c);
     free(s);
     return SPANGPU_OK;
 }
@@ -617,41 +503,11 @@ int spangpu_modem_shard_create(spangpu_modem_shard_t **out, const int *devices, 
     spangpu_modem_shard_t *s = (spangpu_modem_shard_t *) calloc(1, sizeof(*s));
     if (s == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory");
-    s->n = n_devices;
-    s->n_ch = n_channels;
     s->per = events_per_channel;
-    s->collect_device = devices[0];
-    if (deal_channels(n_channels, n_devices, s->first) != SPANGPU_OK)
-    {
-        free(s);
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "channels do not deal out over the shards");
-    }
-    const size_t per_ch = 4u + (size_t) events_per_channel;
-    int rc = SPANGPU_OK;
-    for (int i = 0;  i < n_devices  &&  rc == SPANGPU_OK;  i++)
-    {
-        const int mine = s->first[i + 1] - s->first[i];
-        s->device[i] = devices[i];
-        if (hipSetDevice(devices[i]) != hipSuccess)
-            rc = spangpu_set_error(SPANGPU_ERR_HIP, "hipSetDevice failed");
-        else if ((rc = spangpu_modem_create(&s->bank[i], devices[i], kind, mine, bit_rate)) == SPANGPU_OK)
-        {
-            if (hipMalloc((void **) &s->ev[i], per_ch*mine) != hipSuccess
-                ||  hipEventCreateWithFlags(&s->done[0][i], hipEventDisableTiming) != hipSuccess
-                ||  hipEventCreateWithFlags(&s->done[1][i], hipEventDisableTiming) != hipSuccess)
-                rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of device memory");
-        }
-        if (rc == SPANGPU_OK)
-            s->link[i] = link_to(devices[i], s->collect_device);
-    }
-    if (rc == SPANGPU_OK)
-    {
-        if (hipSetDevice(s->collect_device) != hipSuccess
-            ||  hipMalloc((void **) &s->gathered[0], per_ch*n_channels) != hipSuccess
-            ||  hipMalloc((void **) &s->gathered[1], per_ch*n_channels) != hipSuccess
-            ||  hipHostMalloc((void **) &s->h_gathered, per_ch*n_channels) != hipSuccess)
-            rc = spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory for the gathered events");
-    }
+    const int rc = shard_create(&s->c, &kOps<spangpu_modem_t, spangpu_modem_sync, spangpu_modem_destroy, spangpu_modem_get_stream>, devices,
+                                n_devices, n_channels, 4u + (size_t) events_per_channel, true, "out of memory for the gathered events",
+                                [&](int, int device, int mine, void **bank)
+                                { return spangpu_modem_create((spangpu_modem_t **) bank, device, kind, mine, bit_rate); });
     if (rc != SPANGPU_OK)
     {
         spangpu_modem_shard_destroy(s);
@@ -663,24 +519,17 @@ int spangpu_modem_shard_create(spangpu_modem_shard_t **out, const int *devices, 
 
 int spangpu_modem_shard_range(const spangpu_modem_shard_t *s, int i, int *device, int *first_channel, int *n_channels)
 {
-    if (s == nullptr  ||  i < 0  ||  i >= s->n)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad shard");
-    if (device) *device = s->device[i];
-    if (first_channel) *first_channel = s->first[i];
-    if (n_channels) *n_channels = s->first[i + 1] - s->first[i];
-    return SPANGPU_OK;
+    return shard_range(core_of(s), i, device, first_channel, n_channels);
 }
 
 int spangpu_modem_shard_info(const spangpu_modem_shard_t *s, int i, spangpu_shard_info_t *info)
 {
-    if (s == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard set");
-    return shard_info(s->n, s->device, s->first, s->link, s->collect_device, i, info);
+    return shard_info(core_of(s), i, g_force_peer.load(), info);
 }
 
 spangpu_modem_t *spangpu_modem_shard_bank(spangpu_modem_shard_t *s, int i)
 {
-    return (s  &&  i >= 0  &&  i < s->n)  ?  s->bank[i]  :  nullptr;
+    return (spangpu_modem_t *) shard_bank(core_of(s), i);
 }
 
 // One step: amp[i] = shard i's rows on its device; queues per shard the receiver launch, the copy of its event block and
@@ -689,23 +538,19 @@ int spangpu_modem_shard_rx(spangpu_modem_shard_t *s, const int16_t *const *amp, 
 {
     if (s == nullptr  ||  amp == nullptr  ||  samples <= 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int slot = (int) (s->steps & 1u);
+    const int slot = (int) (s->c.steps & 1u);
     const size_t per_ch = 4u + (size_t) s->per;
-    for (int i = 0;  i < s->n;  i++)
+    for (int i = 0;  i < s->c.n;  i++)
     {
-        const int mine = s->first[i + 1] - s->first[i];
-        SH_TRY(hipSetDevice(s->device[i]));
-        int rc = spangpu_modem_rx(s->bank[i], amp[i], SPANGPU_MEM_DEVICE, samples, stride);
-        if (rc < 0)
+        spangpu_modem_t *bank = (spangpu_modem_t *) s->c.bank[i];
+        const size_t bytes = per_ch*shard_channels(&s->c, i);
+        SPG_TRY(hipSetDevice(s->c.device[i]));
+        int rc = spangpu_modem_rx(bank, amp[i], SPANGPU_MEM_DEVICE, samples, stride);
+        if (rc < 0  ||  (rc = spangpu_modem_copy_events(bank, s->c.out[i], bytes, s->per)) < 0
+            ||  (rc = shard_post(&s->c, i, slot, per_ch*s->c.first[i], bytes)) < 0)
             return rc;
-        if ((rc = spangpu_modem_copy_events(s->bank[i], s->ev[i], per_ch*mine, s->per)) < 0)
-            return rc;
-        hipStream_t st = (hipStream_t) spangpu_modem_get_stream(s->bank[i]);
-        uint8_t *dst = s->gathered[slot] + per_ch*s->first[i];
-        SH_TRY(gather_copy(dst, s->collect_device, s->ev[i], s->device[i], per_ch*mine, st));
-        SH_TRY(hipEventRecord(s->done[slot][i], st));
     }
-    s->steps++;
+    s->c.steps++;
     return SPANGPU_OK;
 }
 
@@ -715,39 +560,18 @@ int spangpu_modem_shard_events_host(spangpu_modem_shard_t *s, int32_t *counts, i
 {
     if (s == nullptr  ||  counts == nullptr  ||  events == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (s->steps == 0)
+    if (s->c.steps == 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no step has been queued yet");
-    const int slot = (int) ((s->steps - 1u) & 1u);
-    const size_t per_ch = 4u + (size_t) s->per;
-    for (int i = 0;  i < s->n;  i++)
-    {
-        SH_TRY(hipSetDevice(s->device[i]));
-        SH_TRY(hipEventSynchronize(s->done[slot][i]));
-    }
-    SH_TRY(hipSetDevice(s->collect_device));
-    SH_TRY(hipMemcpy(s->h_gathered, s->gathered[slot], per_ch*s->n_ch, hipMemcpyDeviceToHost));
-    for (int i = 0;  i < s->n;  i++)
-    {
-        const int mine = s->first[i + 1] - s->first[i];
-        const uint8_t *blk = s->h_gathered + per_ch*s->first[i];
-        memcpy(counts + s->first[i], blk, (size_t) mine*4u);
-        memcpy(events + (size_t) s->first[i]*s->per, blk + (size_t) mine*4u, (size_t) mine*s->per);
-    }
-    return s->n_ch;
+    int rc = shard_wait(&s->c, nullptr);
+    if (rc < 0  ||  (rc = shard_fetch(&s->c, (4u + (size_t) s->per)*s->c.n_ch)) < 0)
+        return rc;
+    shard_blocks_to_channels(&s->c, (const uint8_t *) s->c.h_gathered, 4u, (size_t) s->per, (uint8_t *) counts, (uint8_t *) events);
+    return s->c.n_ch;
 }
 
 int spangpu_modem_shard_sync(spangpu_modem_shard_t *s)
 {
-    if (s == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null shard");
-    for (int i = 0;  i < s->n;  i++)
-    {
-        SH_TRY(hipSetDevice(s->device[i]));
-        const int rc = spangpu_modem_sync(s->bank[i]);
-        if (rc < 0)
-            return rc;
-    }
-    return SPANGPU_OK;
+    return shard_sync(core_of(s));
 }
 
 }   // extern "C"

@@ -17,6 +17,7 @@
 
 #include "../../include/spangpu.h"
 #include "../../include/spangpu_refstate.h"
+#include "bank_host.hpp"
 #include "tone_dev.hpp"
 #include "tone_fast.hpp"
 
@@ -33,14 +34,6 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                   \
-    do                                                                                  \
-    {                                                                                   \
-        hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(SPANGPU_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    }                                                                                   \
-    while (0)
 
 struct spangpu_bank_s
 {
@@ -484,7 +477,7 @@ int spangpu_probe_stream_read(int device, size_t bytes, int reps, double *gb_per
 {
     if (gb_per_s == nullptr  ||  bytes < (1u << 20)  ||  reps <= 0)
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(device));
+    SPG_TRY(hipSetDevice(device));
     uint4 *buf = nullptr;
     uint32_t *sink = nullptr;
     hipEvent_t e0 = nullptr;
@@ -566,30 +559,30 @@ static int ensure_outputs(spangpu_bank_t *b, int maxb)
         const int caught = cadence_catch_up(b);
         if (caught != SPANGPU_OK)
             return caught;
-        HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipStreamSynchronize(joined(b)));
     }
     free_outputs(b);
     const size_t n = (size_t) maxb*b->n_ch;
-    HIP_TRY(hipMalloc(&b->rec, n*sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc(&b->h_rec, n*sizeof(uint32_t)));
+    SPG_TRY(hipMalloc(&b->rec, n*sizeof(uint32_t)));
+    SPG_TRY(hipHostMalloc(&b->h_rec, n*sizeof(uint32_t)));
     const bool want_energy = (b->kind == SPANGPU_DTMF  &&  b->tp.report_mode == SPANGPU_REPORT_REALTIME)
                              ||  b->kind == SPANGPU_SUPER_TONE;
     if (want_energy)
     {
-        HIP_TRY(hipMalloc(&b->rec_energy, n*sizeof(float)));
-        HIP_TRY(hipHostMalloc(&b->h_energy, n*sizeof(float)));
-        HIP_TRY(hipMemsetAsync(b->rec_energy, 0, n*sizeof(float), joined(b)));
+        SPG_TRY(hipMalloc(&b->rec_energy, n*sizeof(float)));
+        SPG_TRY(hipHostMalloc(&b->h_energy, n*sizeof(float)));
+        SPG_TRY(hipMemsetAsync(b->rec_energy, 0, n*sizeof(float), joined(b)));
     }
     if (b->kind == SPANGPU_DTMF  &&  b->tp.report_mode == SPANGPU_REPORT_REALTIME)
     {
-        HIP_TRY(hipMalloc(&b->rec_dur, n*sizeof(int32_t)));
-        HIP_TRY(hipHostMalloc(&b->h_dur, n*sizeof(int32_t)));
-        HIP_TRY(hipMemsetAsync(b->rec_dur, 0, n*sizeof(int32_t), joined(b)));
+        SPG_TRY(hipMalloc(&b->rec_dur, n*sizeof(int32_t)));
+        SPG_TRY(hipHostMalloc(&b->h_dur, n*sizeof(int32_t)));
+        SPG_TRY(hipMemsetAsync(b->rec_dur, 0, n*sizeof(int32_t), joined(b)));
     }
     if (b->tp.trace  ||  b->kind == SPANGPU_GOERTZEL)
     {
-        HIP_TRY(hipMalloc(&b->trace, n*(b->nb + 1)*sizeof(float)));
-        HIP_TRY(hipMemsetAsync(b->trace, 0, n*(b->nb + 1)*sizeof(float), joined(b)));
+        SPG_TRY(hipMalloc(&b->trace, n*(b->nb + 1)*sizeof(float)));
+        SPG_TRY(hipMemsetAsync(b->trace, 0, n*(b->nb + 1)*sizeof(float), joined(b)));
     }
     b->maxb_cap = maxb;
     return SPANGPU_OK;
@@ -605,7 +598,7 @@ int spangpu_bank_create(spangpu_bank_t **bank, int device, int kind, int n_chann
         return fail(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
     if (device < 0  ||  device >= spangpu_device_count())
         return fail(SPANGPU_ERR_BAD_ARG, "device %d out of range", device);
-    HIP_TRY(hipSetDevice(device));
+    SPG_TRY(hipSetDevice(device));
 
     spangpu_bank_t *b = (spangpu_bank_t *) calloc(1, sizeof(*b));
     if (b == nullptr)
@@ -755,7 +748,7 @@ int spangpu_bank_set_stream(spangpu_bank_t *b, void *hip_stream)
     }
     else
     {
-        HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        SPG_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
         b->own_stream = true;
     }
     return SPANGPU_OK;
@@ -808,7 +801,7 @@ int spangpu_banks_own_queues(spangpu_bank_t *const *banks, int n_banks)
         if (banks[k] == nullptr  ||  banks[k]->device != banks[0]->device)
             return fail(SPANGPU_ERR_BAD_ARG, "null bank, or banks on different devices");
     }
-    HIP_TRY(hipSetDevice(banks[0]->device));
+    SPG_TRY(hipSetDevice(banks[0]->device));
     constexpr int kCandidates = 12;
     hipStream_t cand[kCandidates];
     int n_cand = 0;
@@ -836,7 +829,7 @@ int spangpu_banks_own_queues(spangpu_bank_t *const *banks, int n_banks)
     while (n_chosen < n_banks)
     {
         hipStream_t st = nullptr;
-        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        SPG_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         chosen[n_chosen++] = st;
     }
     for (int i = 0;  i < n_cand;  i++)
@@ -844,7 +837,7 @@ int spangpu_banks_own_queues(spangpu_bank_t *const *banks, int n_banks)
     for (int k = 0;  k < n_banks;  k++)
     {
         spangpu_bank_t *b = banks[k];
-        HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipStreamSynchronize(joined(b)));
         if (b->own_stream)
             (void) hipStreamDestroy(b->stream);
         b->stream = chosen[k];
@@ -870,7 +863,7 @@ int spangpu_bank_set_queues(spangpu_bank_t *b, int queues)
 {
     if (b == nullptr  ||  queues < 0  ||  queues > 2)
         return fail(SPANGPU_ERR_BAD_ARG, "queues must be 0 (the library's choice), 1 or 2");
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     // The library's own choice is two queues only for a bank on its OWN stream: there every frame reaches the bank through this
     // library (the host copy, or a device frame that is complete when the call is made), and the second queue's ordering is the
     // library's business.  On a caller's stream (spangpu_bank_set_stream) frames may be produced by the caller's kernels on
@@ -882,9 +875,9 @@ int spangpu_bank_set_queues(spangpu_bank_t *b, int queues)
     (void) joined(b);
     if (queues == 2  &&  b->stream2 == nullptr)
     {
-        HIP_TRY(hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&b->ev_q, hipEventDisableTiming));
+        SPG_TRY(hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking));
+        SPG_TRY(hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
+        SPG_TRY(hipEventCreateWithFlags(&b->ev_q, hipEventDisableTiming));
     }
     b->queues = queues;
     return queues;
@@ -994,8 +987,8 @@ static int launch_bank(spangpu_bank_t *b, const int16_t *d_amp, long long d_stri
     {
         // something else went onto the bank's stream since the last split launch (a state edit, a launch of the other kernel
         // family, work of the caller's behind spangpu_bank_get_stream() / _join()): the second half runs behind it
-        HIP_TRY(hipEventRecord(b->ev_in, b->stream));
-        HIP_TRY(hipStreamWaitEvent(b->stream2, b->ev_in, 0));
+        SPG_TRY(hipEventRecord(b->ev_in, b->stream));
+        SPG_TRY(hipStreamWaitEvent(b->stream2, b->ev_in, 0));
         b->main_touched = false;
     }
     for (int half = 0;  half < (split  ?  2  :  1);  half++)
@@ -1008,7 +1001,7 @@ static int launch_bank(spangpu_bank_t *b, const int16_t *d_amp, long long d_stri
         st = half  ?  b->stream2  :  b->stream;
     }
     if (b->timing)
-        HIP_TRY(hipEventRecord(b->ev0, st));
+        SPG_TRY(hipEventRecord(b->ev0, st));
     g_cadence_fused = false;
     switch (b->kind)
     {
@@ -1051,7 +1044,7 @@ static int launch_bank(spangpu_bank_t *b, const int16_t *d_amp, long long d_stri
     default:
         return fail(SPANGPU_ERR_UNSUPPORTED, "kind %d", b->kind);
     }
-    HIP_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     }
     if (split)
         b->s2_busy = true;
@@ -1062,7 +1055,7 @@ static int launch_bank(spangpu_bank_t *b, const int16_t *d_amp, long long d_stri
     }
     if (b->timing)
     {
-        HIP_TRY(hipEventRecord(b->ev1, joined(b)));
+        SPG_TRY(hipEventRecord(b->ev1, joined(b)));
         b->ev_valid = true;
     }
     return SPANGPU_OK;
@@ -1076,7 +1069,7 @@ int spangpu_bank_rx(spangpu_bank_t *b, const int16_t *amp, int mem, int layout, 
         return fail(SPANGPU_ERR_BAD_ARG, "bad layout");
     if (samples == 0)
         return 0;
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     if (stride <= 0)
         stride = (layout == SPANGPU_LAYOUT_CHANNEL_MAJOR)  ?  samples  :  b->n_ch;
 
@@ -1098,12 +1091,12 @@ int spangpu_bank_rx(spangpu_bank_t *b, const int16_t *amp, int mem, int layout, 
                 if (b->d_amp) (void) hipFree(b->d_amp);
                 b->d_amp = nullptr;
                 b->d_amp_cap = 0;
-                HIP_TRY(hipMalloc(&b->d_amp, need*sizeof(int16_t)));
+                SPG_TRY(hipMalloc(&b->d_amp, need*sizeof(int16_t)));
                 b->d_amp_cap = need;
             }
-            HIP_TRY(hipMemcpy2DAsync(b->d_amp, padded*sizeof(int16_t), amp, stride*sizeof(int16_t),
+            SPG_TRY(hipMemcpy2DAsync(b->d_amp, padded*sizeof(int16_t), amp, stride*sizeof(int16_t),
                                      samples*sizeof(int16_t), b->n_ch, hipMemcpyHostToDevice, joined(b)));
-            HIP_TRY(hipStreamSynchronize(joined(b)));       // amp[] is only borrowed for the duration of the call
+            SPG_TRY(hipStreamSynchronize(joined(b)));       // amp[] is only borrowed for the duration of the call
             d_stride = padded;
         }
         else
@@ -1114,12 +1107,12 @@ int spangpu_bank_rx(spangpu_bank_t *b, const int16_t *amp, int mem, int layout, 
                 if (b->d_amp) (void) hipFree(b->d_amp);
                 b->d_amp = nullptr;
                 b->d_amp_cap = 0;
-                HIP_TRY(hipMalloc(&b->d_amp, need*sizeof(int16_t)));
+                SPG_TRY(hipMalloc(&b->d_amp, need*sizeof(int16_t)));
                 b->d_amp_cap = need;
             }
-            HIP_TRY(hipMemcpy2DAsync(b->d_amp, b->n_ch*sizeof(int16_t), amp, stride*sizeof(int16_t),
+            SPG_TRY(hipMemcpy2DAsync(b->d_amp, b->n_ch*sizeof(int16_t), amp, stride*sizeof(int16_t),
                                      b->n_ch*sizeof(int16_t), samples, hipMemcpyHostToDevice, joined(b)));
-            HIP_TRY(hipStreamSynchronize(joined(b)));
+            SPG_TRY(hipStreamSynchronize(joined(b)));
             d_stride = b->n_ch;
         }
         d_amp = b->d_amp;
@@ -1168,15 +1161,15 @@ int spangpu_bank_rx_var(spangpu_bank_t *b, const int16_t *amp, int mem, const in
     }
     if (all)
         return spangpu_bank_rx(b, amp, mem, SPANGPU_LAYOUT_CHANNEL_MAJOR, longest, stride);
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     if (b->d_lens == nullptr)
     {
-        HIP_TRY(hipMalloc(&b->d_lens, (size_t) b->n_ch*sizeof(int32_t)));
-        HIP_TRY(hipHostMalloc(&b->h_lens, (size_t) b->n_ch*sizeof(int32_t), hipHostMallocDefault));
+        SPG_TRY(hipMalloc(&b->d_lens, (size_t) b->n_ch*sizeof(int32_t)));
+        SPG_TRY(hipHostMalloc(&b->h_lens, (size_t) b->n_ch*sizeof(int32_t), hipHostMallocDefault));
     }
-    HIP_TRY(hipStreamSynchronize(joined(b)));               // the previous call's copy out of h_lens is done
+    SPG_TRY(hipStreamSynchronize(joined(b)));               // the previous call's copy out of h_lens is done
     memcpy(b->h_lens, lens, (size_t) b->n_ch*sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(b->d_lens, b->h_lens, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyHostToDevice, joined(b)));
+    SPG_TRY(hipMemcpyAsync(b->d_lens, b->h_lens, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyHostToDevice, joined(b)));
     b->next_lens = b->d_lens;
     b->next_ragged = ragged;
     const int rc = spangpu_bank_rx(b, amp, mem, SPANGPU_LAYOUT_CHANNEL_MAJOR, longest, stride);
@@ -1208,7 +1201,7 @@ static int ensure_chan_parms(spangpu_bank_t *b)
         b->h_chan_parms = nullptr;
         return fail(SPANGPU_ERR_NO_MEMORY, "hipMalloc of per-channel parameters failed");
     }
-    HIP_TRY(hipMemcpy(d, b->h_chan_parms, 4*n*sizeof(float), hipMemcpyHostToDevice));
+    SPG_TRY(hipMemcpy(d, b->h_chan_parms, 4*n*sizeof(float), hipMemcpyHostToDevice));
     b->chan_parms = d;
     return SPANGPU_OK;
 }
@@ -1227,8 +1220,8 @@ int spangpu_bank_set_channel_params(spangpu_bank_t *b, int channel, const spangp
     spangpu_tone_params_t tp;
     memset(&tp, 0, sizeof(tp));
     memcpy(&tp, params, (params_size < sizeof(tp))  ?  params_size  :  sizeof(tp));
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     const size_t n = (size_t) b->n_ch;
     const int rc0 = ensure_chan_parms(b);
     if (rc0 != SPANGPU_OK)
@@ -1253,11 +1246,11 @@ int spangpu_bank_set_channel_params(spangpu_bank_t *b, int channel, const spangp
         b->n_filter_on += (int) on - (int) h[3*n + channel];
         h[3*n + channel] = on;
         for (int i = 0;  i < 4;  i++)
-            HIP_TRY(hipMemsetAsync(b->sf + (size_t) (17 + i)*n + channel, 0, sizeof(float), joined(b)));
+            SPG_TRY(hipMemsetAsync(b->sf + (size_t) (17 + i)*n + channel, 0, sizeof(float), joined(b)));
     }
     for (int i = 0;  i < 4;  i++)
-        HIP_TRY(hipMemcpyAsync(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice, joined(b)));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipMemcpyAsync(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice, joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     return SPANGPU_OK;
 }
 
@@ -1272,7 +1265,7 @@ int spangpu_bank_rx_g711(spangpu_bank_t *b, const uint8_t *codes, int mem, int l
         return fail(SPANGPU_ERR_BAD_ARG, "law must be SPANGPU_G711_ALAW or SPANGPU_G711_ULAW");
     if (samples == 0)
         return 0;
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     if (stride <= 0)
         stride = samples;
     const int maxb = (samples + b->block_len - 1)/b->block_len;
@@ -1290,11 +1283,11 @@ int spangpu_bank_rx_g711(spangpu_bank_t *b, const uint8_t *codes, int mem, int l
             if (b->d_amp) (void) hipFree(b->d_amp);
             b->d_amp = nullptr;
             b->d_amp_cap = 0;
-            HIP_TRY(hipMalloc(&b->d_amp, need*sizeof(int16_t)));
+            SPG_TRY(hipMalloc(&b->d_amp, need*sizeof(int16_t)));
             b->d_amp_cap = need;
         }
-        HIP_TRY(hipMemcpy2DAsync(b->d_amp, padded, codes, stride, samples, b->n_ch, hipMemcpyHostToDevice, joined(b)));
-        HIP_TRY(hipStreamSynchronize(joined(b)));           // codes[] is only borrowed for the duration of the call
+        SPG_TRY(hipMemcpy2DAsync(b->d_amp, padded, codes, stride, samples, b->n_ch, hipMemcpyHostToDevice, joined(b)));
+        SPG_TRY(hipStreamSynchronize(joined(b)));           // codes[] is only borrowed for the duration of the call
         d_codes = (const uint8_t *) b->d_amp;
         d_stride = padded;
     }
@@ -1378,7 +1371,7 @@ int spangpu_banks_rx(spangpu_bank_t *const *banks, const int16_t *const *amps, i
     }
     for (int k = 0;  k < n_banks;  k++)
         (void) joined(banks[k]);
-    HIP_TRY(hipSetDevice(banks[0]->device));
+    SPG_TRY(hipSetDevice(banks[0]->device));
     bool all_fast = true;
     for (int k = 0;  k < n_banks;  k++)
     {
@@ -1463,7 +1456,7 @@ int spangpu_banks_rx(spangpu_bank_t *const *banks, const int16_t *const *amps, i
         hipLaunchKernelGGL(tone_multi_kernel<2>, dim3(first), dim3(kWave*kWavesPerBlock), 0, banks[0]->stream, M);
     else
         hipLaunchKernelGGL(tone_multi_kernel<1>, dim3(first), dim3(kWave*kWavesPerBlock), 0, banks[0]->stream, M);
-    HIP_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     return 0;
 }
 
@@ -1471,7 +1464,7 @@ int spangpu_bank_force_block(spangpu_bank_t *b)
 {
     if (b == nullptr)
         return fail(SPANGPU_ERR_BAD_ARG, "null bank");
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     int rc = ensure_outputs(b, 1);
     if (rc != SPANGPU_OK)
         return rc;
@@ -1488,7 +1481,7 @@ int spangpu_bank_sync(spangpu_bank_t *b)
 {
     if (b == nullptr)
         return fail(SPANGPU_ERR_BAD_ARG, "null bank");
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     return SPANGPU_OK;
 }
 
@@ -1510,14 +1503,14 @@ int spangpu_bank_blocks(spangpu_bank_t *b, spangpu_block_t *out, int max)
         return fail(SPANGPU_ERR_BAD_ARG, "null bank");
     if (b->last_maxb <= 0)
         return 0;
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     const size_t n = (size_t) b->last_maxb*b->n_ch;
-    HIP_TRY(hipMemcpyAsync(b->h_rec, b->cur_rec  ?  b->cur_rec  :  b->rec, n*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
+    SPG_TRY(hipMemcpyAsync(b->h_rec, b->cur_rec  ?  b->cur_rec  :  b->rec, n*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
     if (b->rec_energy)
-        HIP_TRY(hipMemcpyAsync(b->h_energy, b->rec_energy, n*sizeof(float), hipMemcpyDeviceToHost, joined(b)));
+        SPG_TRY(hipMemcpyAsync(b->h_energy, b->rec_energy, n*sizeof(float), hipMemcpyDeviceToHost, joined(b)));
     if (b->rec_dur)
-        HIP_TRY(hipMemcpyAsync(b->h_dur, b->rec_dur, n*sizeof(int32_t), hipMemcpyDeviceToHost, joined(b)));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipMemcpyAsync(b->h_dur, b->rec_dur, n*sizeof(int32_t), hipMemcpyDeviceToHost, joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     int count = 0;
     const bool bias = (b->kind == SPANGPU_SUPER_TONE);
     for (int ch = 0;  ch < b->n_ch;  ch++)
@@ -1568,8 +1561,8 @@ long long spangpu_bank_copy_records(spangpu_bank_t *b, void *dst_device, size_t 
         return fail(SPANGPU_ERR_BAD_ARG, "record buffer too small: need %zu bytes", bytes);
     if (bytes == 0)
         return 0;
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpyAsync(dst_device, b->cur_rec  ?  b->cur_rec  :  b->rec, bytes, hipMemcpyDeviceToDevice, joined(b)));
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipMemcpyAsync(dst_device, b->cur_rec  ?  b->cur_rec  :  b->rec, bytes, hipMemcpyDeviceToDevice, joined(b)));
     return (long long) bytes;
 }
 
@@ -1603,13 +1596,13 @@ int spangpu_bank_digit_events(spangpu_bank_t *b, uint32_t *dst_device, int cap_e
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->n_ch > (1 << 20)  ||  b->last_maxb > 16)
         return fail(SPANGPU_ERR_UNSUPPORTED, "digit events pack the channel in 20 bits and the block in 4");
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemsetAsync(dst_device, 0, sizeof(uint32_t), joined(b)));
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipMemsetAsync(dst_device, 0, sizeof(uint32_t), joined(b)));
     if (b->last_maxb > 0)
     {
         hipLaunchKernelGGL(digit_events_kernel, dim3((b->n_ch + 255)/256), dim3(256), 0, joined(b),
                            (const uint32_t *) (b->cur_rec  ?  b->cur_rec  :  b->rec), b->n_ch, b->last_maxb, dst_device, cap_entries);
-        HIP_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
     }
     return SPANGPU_OK;
 }
@@ -1623,9 +1616,9 @@ int spangpu_bank_trace(spangpu_bank_t *b, float *energies, size_t max_floats)
     const size_t n = (size_t) b->last_maxb*(b->nb + 1)*b->n_ch;
     if (n > max_floats)
         return fail(SPANGPU_ERR_BAD_ARG, "trace buffer too small: need %zu floats", n);
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
-    HIP_TRY(hipMemcpy(energies, b->trace, n*sizeof(float), hipMemcpyDeviceToHost));
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipMemcpy(energies, b->trace, n*sizeof(float), hipMemcpyDeviceToHost));
     return b->last_maxb;
 }
 
@@ -1640,12 +1633,12 @@ int spangpu_bank_get_state(spangpu_bank_t *b, int channel, float *fstate, int ma
 {
     if (b == nullptr  ||  channel < 0  ||  channel >= b->n_ch  ||  max_f < b->nsf  ||  max_i < 4)
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
-    HIP_TRY(hipMemcpy2D(fstate, sizeof(float), b->sf + channel, (size_t) b->n_ch*sizeof(float),
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipMemcpy2D(fstate, sizeof(float), b->sf + channel, (size_t) b->n_ch*sizeof(float),
                         sizeof(float), b->nsf, hipMemcpyDeviceToHost));
     int32_t w[2];
-    HIP_TRY(hipMemcpy2D(w, sizeof(int32_t), b->si + channel, (size_t) b->n_ch*sizeof(int32_t),
+    SPG_TRY(hipMemcpy2D(w, sizeof(int32_t), b->si + channel, (size_t) b->n_ch*sizeof(int32_t),
                         sizeof(int32_t), 2, hipMemcpyDeviceToHost));
     istate[0] = w[0] & 0xFFFF;
     istate[1] = (w[0] >> 16) & 0xFF;
@@ -1658,14 +1651,14 @@ int spangpu_bank_set_state(spangpu_bank_t *b, int channel, const float *fstate, 
 {
     if (b == nullptr  ||  channel < 0  ||  channel >= b->n_ch  ||  n_f != b->nsf  ||  n_i != 4)
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
-    HIP_TRY(hipMemcpy2D(b->sf + channel, (size_t) b->n_ch*sizeof(float), fstate, sizeof(float),
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipMemcpy2D(b->sf + channel, (size_t) b->n_ch*sizeof(float), fstate, sizeof(float),
                         sizeof(float), b->nsf, hipMemcpyHostToDevice));
     int32_t w[2];
     w[0] = (istate[0] & 0xFFFF) | ((istate[1] & 0xFF) << 16) | ((int32_t) ((uint32_t) (istate[2] & 0xFF) << 24));
     w[1] = istate[3];
-    HIP_TRY(hipMemcpy2D(b->si + channel, (size_t) b->n_ch*sizeof(int32_t), w, sizeof(int32_t),
+    SPG_TRY(hipMemcpy2D(b->si + channel, (size_t) b->n_ch*sizeof(int32_t), w, sizeof(int32_t),
                         sizeof(int32_t), 2, hipMemcpyHostToDevice));
     return SPANGPU_OK;
 }
@@ -1712,7 +1705,7 @@ int spangpu_dtmf_import_state(spangpu_bank_t *b, int channel, const spangpu_ref_
     h[2*n + channel] = s->reverse_twist;
     h[3*n + channel] = on;
     for (int i = 0;  i < 4;  i++)
-        HIP_TRY(hipMemcpy(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice));
+        SPG_TRY(hipMemcpy(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice));
     return SPANGPU_OK;
 }
 
@@ -1889,8 +1882,8 @@ int spangpu_bank_reset_channel(spangpu_bank_t *b, int channel, int fillin_only)
     h[2*n + channel] = b->reverse_twist;
     h[3*n + channel] = on;
     for (int i = 0;  i < 4;  i++)
-        HIP_TRY(hipMemcpyAsync(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice, joined(b)));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipMemcpyAsync(b->chan_parms + (size_t) i*n + channel, &h[(size_t) i*n + channel], sizeof(float), hipMemcpyHostToDevice, joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     return SPANGPU_OK;
 }
 
@@ -1917,7 +1910,7 @@ static int cadence_event_room(spangpu_bank_t *b, int slots)
     Cadence *c = b->cad;
     if (slots <= c->slots_cap)
         return SPANGPU_OK;
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     if (c->d_ev) (void) hipFree(c->d_ev);
     if (c->h_ev) (void) hipHostFree(c->h_ev);
     if (c->d_list) (void) hipFree(c->d_list);
@@ -1927,11 +1920,11 @@ static int cadence_event_room(spangpu_bank_t *b, int slots)
     c->d_list = nullptr;
     c->h_list = nullptr;
     c->slots_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_ev, (size_t) slots*b->n_ch*2*sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc(&c->h_ev, (size_t) slots*b->n_ch*2*sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->d_list, ((size_t) slots*b->n_ch*3 + 2)*sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc(&c->h_list, ((size_t) slots*b->n_ch*3 + 2)*sizeof(uint32_t)));
-    HIP_TRY(hipMemset(c->d_list, 0, 2*sizeof(uint32_t)));
+    SPG_TRY(hipMalloc(&c->d_ev, (size_t) slots*b->n_ch*2*sizeof(uint32_t)));
+    SPG_TRY(hipHostMalloc(&c->h_ev, (size_t) slots*b->n_ch*2*sizeof(uint32_t)));
+    SPG_TRY(hipMalloc(&c->d_list, ((size_t) slots*b->n_ch*3 + 2)*sizeof(uint32_t)));
+    SPG_TRY(hipHostMalloc(&c->h_list, ((size_t) slots*b->n_ch*3 + 2)*sizeof(uint32_t)));
+    SPG_TRY(hipMemset(c->d_list, 0, 2*sizeof(uint32_t)));
     c->which = 0;
     c->slots_cap = slots;
     return SPANGPU_OK;
@@ -1947,8 +1940,8 @@ int spangpu_bank_set_cadences(spangpu_bank_t *b, const int32_t *tone_elems, int 
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->kind != SPANGPU_SUPER_TONE)
         return fail(SPANGPU_ERR_UNSUPPORTED, "cadences belong to a super-tone bank");
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     std::vector<int32_t> first(n_tones + 1, 0);
     for (int t = 0;  t < n_tones;  t++)
     {
@@ -2003,7 +1996,7 @@ int spangpu_bank_set_cadences(spangpu_bank_t *b, const int32_t *tone_elems, int 
             if (n_elem) (void) hipFree(n_elem);
             return fail(SPANGPU_ERR_NO_MEMORY, "out of device memory for the cadence tables");
         }
-        HIP_TRY(hipStreamSynchronize(joined(b)));        // no launch still reads the old ones
+        SPG_TRY(hipStreamSynchronize(joined(b)));        // no launch still reads the old ones
         if (c->d_first) (void) hipFree(c->d_first);
         if (c->d_elem) (void) hipFree(c->d_elem);
         c->d_first = n_first;
@@ -2014,15 +2007,15 @@ int spangpu_bank_set_cadences(spangpu_bank_t *b, const int32_t *tone_elems, int 
         // the tone numbers of the old set mean nothing in the new one: nobody is following a tone (the run histories stay)
         // (-2, not -1: "none, and look at every cadence at the next block" -- the channel may be in the middle of a run that
         // one of the new cadences ends with, see cadence_dev.hpp)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t) (c->d_state + (size_t) 2*b->n_ch), (int) 0xFFFFFFFEu, (size_t) b->n_ch, joined(b)));
-        HIP_TRY(hipMemsetAsync(c->d_state + (size_t) 3*b->n_ch, 0, (size_t) b->n_ch*sizeof(int32_t), joined(b)));
+        SPG_TRY(hipMemsetD32Async((hipDeviceptr_t) (c->d_state + (size_t) 2*b->n_ch), (int) 0xFFFFFFFEu, (size_t) b->n_ch, joined(b)));
+        SPG_TRY(hipMemsetAsync(c->d_state + (size_t) 3*b->n_ch, 0, (size_t) b->n_ch*sizeof(int32_t), joined(b)));
     }
     c->n_tones = n_tones;
     c->n_elems = n_elems;
     for (int t = 0;  t < n_tones  &&  t < kCadLdsTones;  t++)
         c->tone_len[t] = first[t + 1] - first[t];
     c->segments = want_segments  ?  1  :  0;
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     return SPANGPU_OK;
 }
 
@@ -2035,7 +2028,7 @@ int spangpu_bank_cadence_run(spangpu_bank_t *b)
         return fail(SPANGPU_ERR_STATE, "no cadences were given to this bank (spangpu_bank_set_cadences)");
     if (c->done_serial == b->launch_serial)
         return c->last_slots;
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     const int slots = kCadSlotsPerBlock*b->last_maxb;
     if (c->fused)
     {
@@ -2056,11 +2049,11 @@ int spangpu_bank_cadence_run(spangpu_bank_t *b)
         cadence_args(b, c, A, c->which);
         hipLaunchKernelGGL(cadence_kernel, dim3((b->n_ch + 255)/256), dim3(256), 0, joined(b),
                            (const uint32_t *) (b->cur_rec  ?  b->cur_rec  :  b->rec), b->n_ch, b->last_maxb, A);
-        HIP_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
     }
     else
     {
-        HIP_TRY(hipMemsetAsync(c->d_count, 0, (size_t) b->n_ch*sizeof(int32_t), joined(b)));
+        SPG_TRY(hipMemsetAsync(c->d_count, 0, (size_t) b->n_ch*sizeof(int32_t), joined(b)));
     }
     c->done_serial = b->launch_serial;
     c->last_slots = slots;
@@ -2073,10 +2066,10 @@ int spangpu_bank_cadence_events(spangpu_bank_t *b, const uint32_t **events, cons
     if (slots < 0)
         return slots;
     Cadence *c = b->cad;
-    HIP_TRY(hipMemcpyAsync(c->h_count, c->d_count, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, joined(b)));
+    SPG_TRY(hipMemcpyAsync(c->h_count, c->d_count, (size_t) b->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, joined(b)));
     if (slots > 0)
-        HIP_TRY(hipMemcpyAsync(c->h_ev, c->d_ev, (size_t) slots*b->n_ch*2*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipMemcpyAsync(c->h_ev, c->d_ev, (size_t) slots*b->n_ch*2*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     if (events)
         *events = c->h_ev;
     if (counts)
@@ -2099,20 +2092,20 @@ int spangpu_bank_cadence_list(spangpu_bank_t *b, const uint32_t **list)
         c->list_due = false;
         cadence_args(b, c, A, c->which);
         hipLaunchKernelGGL(cadence_list_kernel, dim3((b->n_ch + 255)/256), dim3(256), 0, joined(b), b->n_ch, A);
-        HIP_TRY(hipGetLastError());
+        SPG_TRY(hipGetLastError());
     }
     // as a rule a tick has few reports: one small copy brings the counters and the first of them
     const size_t cap = (size_t) c->slots_cap*b->n_ch;
     const size_t first = (cap < 4096)  ?  cap  :  4096;
-    HIP_TRY(hipMemcpyAsync(c->h_list, c->d_list, (2 + 3*first)*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipMemcpyAsync(c->h_list, c->d_list, (2 + 3*first)*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     const size_t n = c->h_list[c->which];
     if (n > cap)
         return fail(SPANGPU_ERR_STATE, "cadence event list overran its buffer");
     if (n > first)
     {
-        HIP_TRY(hipMemcpyAsync(c->h_list + 2 + 3*first, c->d_list + 2 + 3*first, 3*(n - first)*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
-        HIP_TRY(hipStreamSynchronize(joined(b)));
+        SPG_TRY(hipMemcpyAsync(c->h_list + 2 + 3*first, c->d_list + 2 + 3*first, 3*(n - first)*sizeof(uint32_t), hipMemcpyDeviceToHost, joined(b)));
+        SPG_TRY(hipStreamSynchronize(joined(b)));
     }
     if (list)
         *list = c->h_list + 2;
@@ -2136,11 +2129,11 @@ int spangpu_bank_cadence_reset(spangpu_bank_t *b, int channel)
         return fail(SPANGPU_ERR_STATE, "no cadences were given to this bank");
     if (channel < -1  ||  channel >= b->n_ch)
         return fail(SPANGPU_ERR_BAD_ARG, "bad channel");
-    HIP_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipSetDevice(b->device));
     const int first = (channel < 0)  ?  0  :  channel;
     const int n = (channel < 0)  ?  b->n_ch  :  1;
     hipLaunchKernelGGL(cadence_init_kernel, dim3((n + 255)/256), dim3(256), 0, joined(b), b->cad->d_state, b->n_ch, first, n);
-    HIP_TRY(hipGetLastError());
+    SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
 
@@ -2155,9 +2148,9 @@ int spangpu_bank_cadence_get_state(spangpu_bank_t *b, int channel, int32_t *word
         return fail(SPANGPU_ERR_STATE, "no cadences were given to this bank");
     if (channel < 0  ||  channel >= b->n_ch  ||  words == nullptr)
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
-    HIP_TRY(hipMemcpy2D(words, sizeof(int32_t), b->cad->d_state + channel, (size_t) b->n_ch*sizeof(int32_t), sizeof(int32_t), kCadWords,
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipMemcpy2D(words, sizeof(int32_t), b->cad->d_state + channel, (size_t) b->n_ch*sizeof(int32_t), sizeof(int32_t), kCadWords,
                         hipMemcpyDeviceToHost));
     if (words[2] < -1)
         words[2] = -1;          // -2 is the engine's own "none, and every cadence is looked at once at the next block" (cadence_dev.hpp)
@@ -2172,8 +2165,8 @@ int spangpu_bank_cadence_set_state(spangpu_bank_t *b, int channel, const int32_t
         return fail(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (words[2] < -1  ||  words[2] >= b->cad->n_tones  ||  words[3] < 0  ||  words[3] > 255)
         return fail(SPANGPU_ERR_BAD_ARG, "state words out of range");
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(joined(b)));
+    SPG_TRY(hipSetDevice(b->device));
+    SPG_TRY(hipStreamSynchronize(joined(b)));
     int32_t w[kCadWords];
     memcpy(w, words, sizeof(w));
     if (w[2] == -1)
@@ -2181,7 +2174,7 @@ int spangpu_bank_cadence_set_state(spangpu_bank_t *b, int channel, const int32_t
     // the elements of the followed cadence that have gone by are counted modulo its length on the device (head of the ring: 0)
     if (w[2] >= 0  &&  w[2] < kCadLdsTones  &&  b->cad->tone_len[w[2]] > 0)
         w[3] = w[3]%b->cad->tone_len[w[2]];
-    HIP_TRY(hipMemcpy2D(b->cad->d_state + channel, (size_t) b->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), kCadWords,
+    SPG_TRY(hipMemcpy2D(b->cad->d_state + channel, (size_t) b->n_ch*sizeof(int32_t), w, sizeof(int32_t), sizeof(int32_t), kCadWords,
                         hipMemcpyHostToDevice));
     return SPANGPU_OK;
 }
@@ -2235,16 +2228,16 @@ int spangpu_debug_decide(int kind, const float *e8, const float *energy, const u
     float *d_e = nullptr, *d_en = nullptr;
     uint32_t *d_w0 = nullptr, *d_out = nullptr;
     int32_t *d_w1 = nullptr;
-    HIP_TRY(hipMalloc(&d_e, (size_t) n*8*sizeof(float)));
-    HIP_TRY(hipMalloc(&d_en, (size_t) n*sizeof(float)));
-    HIP_TRY(hipMalloc(&d_w0, (size_t) n*4));
-    HIP_TRY(hipMalloc(&d_w1, (size_t) n*4));
-    HIP_TRY(hipMalloc(&d_out, (size_t) n*6*4));
-    HIP_TRY(hipMemcpy(d_e, e8, (size_t) n*8*sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_en, energy, (size_t) n*sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_w0, w0, (size_t) n*4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_w1, w1, (size_t) n*4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_out, 0, (size_t) n*6*4));
+    SPG_TRY(hipMalloc(&d_e, (size_t) n*8*sizeof(float)));
+    SPG_TRY(hipMalloc(&d_en, (size_t) n*sizeof(float)));
+    SPG_TRY(hipMalloc(&d_w0, (size_t) n*4));
+    SPG_TRY(hipMalloc(&d_w1, (size_t) n*4));
+    SPG_TRY(hipMalloc(&d_out, (size_t) n*6*4));
+    SPG_TRY(hipMemcpy(d_e, e8, (size_t) n*8*sizeof(float), hipMemcpyHostToDevice));
+    SPG_TRY(hipMemcpy(d_en, energy, (size_t) n*sizeof(float), hipMemcpyHostToDevice));
+    SPG_TRY(hipMemcpy(d_w0, w0, (size_t) n*4, hipMemcpyHostToDevice));
+    SPG_TRY(hipMemcpy(d_w1, w1, (size_t) n*4, hipMemcpyHostToDevice));
+    SPG_TRY(hipMemset(d_out, 0, (size_t) n*6*4));
     const dim3 grid((n + 255)/256), block(256);
     if (kind == SPANGPU_DTMF)
         hipLaunchKernelGGL(debug_decide_kernel<DtmfDet<false>>, grid, block, 0, 0, d_e, d_en, d_w0, d_w1, d_out, n, L);
@@ -2254,8 +2247,8 @@ int spangpu_debug_decide(int kind, const float *e8, const float *energy, const u
         hipLaunchKernelGGL(debug_decide_kernel<R2MfDet>, grid, block, 0, 0, d_e, d_en, d_w0, d_w1, d_out, n, L);
     else
         return fail(SPANGPU_ERR_UNSUPPORTED, "no lean block end for detector kind %d", kind);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out, (size_t) n*6*4, hipMemcpyDeviceToHost));
+    SPG_TRY(hipGetLastError());
+    SPG_TRY(hipMemcpy(out, d_out, (size_t) n*6*4, hipMemcpyDeviceToHost));
     (void) hipFree(d_e); (void) hipFree(d_en); (void) hipFree(d_w0); (void) hipFree(d_w1); (void) hipFree(d_out);
     return SPANGPU_OK;
 }
