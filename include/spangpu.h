@@ -786,6 +786,98 @@ SPANGPU_API int spangpu_v18_set_state(spangpu_v18_t *bank, int channel, const in
 SPANGPU_API int spangpu_baudot_encode(const uint8_t *text, int n, uint8_t *codes_out, int max, int *shift_state);
 SPANGPU_API int spangpu_baudot_decode(const uint8_t *codes, int n, uint8_t *text_out, int *shift_state);
 
+/* ---- Caller-ID banks (csrc/adsi_api.hip, csrc/adsi_dev.hpp, csrc/adsi_host.c) ----------------
+ * N caller-ID (ADSI) senders, or N receivers, in the four FSK standards of adsi.c: CLASS on Bell 202, CLIP, A-CLIP and J-CLIP
+ * on V.23 channel 1.  Messages go in as bytes and come out as bytes: a sender frames its message (alternating preamble, mark
+ * run, start / 8 data / stop bits per byte, postamble marks, end of data) in front of the FSK modulator, with the 2130 Hz +
+ * 2750 Hz alert tone ahead of it when armed; a receiver runs the asynchronous FSK demodulator with the start/stop framer,
+ * the sum check and J-CLIP's CRC-16 behind it.  Lanes of one wave may carry different standards.  One launch per call.
+ *
+ *   spangpu_adsi_tx_create()           adsi_tx_init(NULL, standard) x N                          src/adsi.c:732-757
+ *   spangpu_adsi_tx_put_message()      adsi_tx_put_message(s, msg, len): results[i] = 0 while a message is in progress,
+ *                                      -1 for one that is too long, else len                     src/adsi.c:626-723
+ *   spangpu_adsi_tx_set_preamble()     adsi_tx_set_preamble(s, ..): negative = the default       src/adsi.c:563-623
+ *   spangpu_adsi_tx_send_alert_tone()  adsi_tx_send_alert_tone(s)                                src/adsi.c:557-560
+ *   spangpu_adsi_tx()                  adsi_tx(s, amp, max_len) x N; lens[c] is what it returns (tone and modem samples
+ *                                      together), samples past it are 0                          src/adsi.c:525-555
+ *   spangpu_adsi_rx_create()           adsi_rx_init(NULL, standard, put_msg, user_data) x N      src/adsi.c:463-509
+ *   spangpu_adsi_rx() / _rx_var()      adsi_rx(s, amp, len) x N                                  src/adsi.c:436-454
+ *   spangpu_adsi_rx_messages()         the put_msg calls of the last rx call: counts[c] messages of channel c, message k
+ *                                      of lens[c*capacity + k] bytes at bytes[(c*capacity + k)*SPANGPU_ADSI_MSG_BYTES];
+ *                                      returns the capacity
+ *   spangpu_adsi_tx_restart() / spangpu_adsi_rx_restart()   adsi_tx_init() / adsi_rx_init() again on one channel
+ *
+ * ADSI_STANDARD_CLIP_DTMF and ADSI_STANDARD_TDD are not part of these banks: creation and restart refuse them (the DTMF
+ * variant belongs to the tone banks, TDD to the V.18 text banks).  A message handed to put_message is at least its type and
+ * its length byte (2 bytes).
+ */
+#define SPANGPU_ADSI_STANDARD_CLASS         1
+#define SPANGPU_ADSI_STANDARD_CLIP          2
+#define SPANGPU_ADSI_STANDARD_ACLIP         3
+#define SPANGPU_ADSI_STANDARD_JCLIP         4
+#define SPANGPU_ADSI_STANDARD_CLIP_DTMF     5       /* the field helpers only */
+#define SPANGPU_ADSI_STANDARD_TDD           6       /* the field helpers only */
+#define SPANGPU_ADSI_MSG_BYTES              256
+
+typedef struct spangpu_adsi_tx_s spangpu_adsi_tx_t;
+typedef struct spangpu_adsi_rx_s spangpu_adsi_rx_t;
+
+/* standards[]: channel c runs standards[c % n_standards] */
+SPANGPU_API int spangpu_adsi_tx_create(spangpu_adsi_tx_t **bank, int device, int n_channels, const int32_t *standards, int n_standards);
+SPANGPU_API void spangpu_adsi_tx_destroy(spangpu_adsi_tx_t *bank);
+SPANGPU_API int spangpu_adsi_tx_channels(const spangpu_adsi_tx_t *bank);
+SPANGPU_API int spangpu_adsi_tx_set_stream(spangpu_adsi_tx_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_adsi_tx_sync(spangpu_adsi_tx_t *bank);
+/* channels first .. first + n - 1: lens[i] bytes from msgs[i*stride] (host memory); results may be NULL */
+SPANGPU_API int spangpu_adsi_tx_put_message(spangpu_adsi_tx_t *bank, int first, int n, const uint8_t *msgs, int stride, const int32_t *lens,
+                                            int32_t *results);
+SPANGPU_API int spangpu_adsi_tx_set_preamble(spangpu_adsi_tx_t *bank, int channel, int preamble_len, int preamble_ones_len,
+                                             int postamble_ones_len, int stop_bits);
+SPANGPU_API int spangpu_adsi_tx_send_alert_tone(spangpu_adsi_tx_t *bank, int channel);
+/* pcm[c*stride + i]; lens ([n_channels], may be NULL) lives where pcm lives */
+SPANGPU_API int spangpu_adsi_tx(spangpu_adsi_tx_t *bank, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens);
+SPANGPU_API int spangpu_adsi_tx_restart(spangpu_adsi_tx_t *bank, int channel, int standard);
+/* Test / checkpoint access to one channel's state (layout: adsi_dev.hpp) and to its SPANGPU_ADSI_MSG_BYTES message bytes */
+SPANGPU_API int spangpu_adsi_tx_state_words(const spangpu_adsi_tx_t *bank);
+SPANGPU_API int spangpu_adsi_tx_get_state(spangpu_adsi_tx_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_adsi_tx_set_state(spangpu_adsi_tx_t *bank, int channel, const int32_t *words);
+SPANGPU_API int spangpu_adsi_tx_get_message(spangpu_adsi_tx_t *bank, int channel, uint8_t *msg);
+SPANGPU_API int spangpu_adsi_tx_set_message(spangpu_adsi_tx_t *bank, int channel, const uint8_t *msg);
+
+SPANGPU_API int spangpu_adsi_rx_create(spangpu_adsi_rx_t **bank, int device, int n_channels, const int32_t *standards, int n_standards);
+SPANGPU_API void spangpu_adsi_rx_destroy(spangpu_adsi_rx_t *bank);
+SPANGPU_API int spangpu_adsi_rx_channels(const spangpu_adsi_rx_t *bank);
+SPANGPU_API int spangpu_adsi_rx_set_stream(spangpu_adsi_rx_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_adsi_rx_sync(spangpu_adsi_rx_t *bank);
+SPANGPU_API int spangpu_adsi_rx(spangpu_adsi_rx_t *bank, const int16_t *amp, int mem_kind, int samples, long long stride);
+/* lens[] is host memory; a channel with lens[c] == 0 sits the call out */
+SPANGPU_API int spangpu_adsi_rx_var(spangpu_adsi_rx_t *bank, const int16_t *amp, int mem_kind, const int32_t *lens, int max_samples,
+                                    long long stride);
+/* Valid until the next call on this bank.  At 1200 baud a message takes at least 30 bit times, so a call completes at most
+   samples*1200/(8000*30) + 1 of them (spangpu_adsi_rx_msg_capacity()); a count above that is an error (SPANGPU_ERR_STATE),
+   never a record cut short. */
+SPANGPU_API int spangpu_adsi_rx_messages(spangpu_adsi_rx_t *bank, const uint8_t **bytes, const int32_t **lens, const int32_t **counts);
+SPANGPU_API int spangpu_adsi_rx_msg_capacity(const spangpu_adsi_rx_t *bank, int samples);
+SPANGPU_API int spangpu_adsi_rx_restart(spangpu_adsi_rx_t *bank, int channel, int standard);
+SPANGPU_API int spangpu_adsi_rx_state_words(const spangpu_adsi_rx_t *bank);
+SPANGPU_API int spangpu_adsi_rx_get_state(spangpu_adsi_rx_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_adsi_rx_set_state(spangpu_adsi_rx_t *bank, int channel, const int32_t *words);
+SPANGPU_API int spangpu_adsi_rx_get_message(spangpu_adsi_rx_t *bank, int channel, uint8_t *msg);
+SPANGPU_API int spangpu_adsi_rx_set_message(spangpu_adsi_rx_t *bank, int channel, const uint8_t *msg);
+/* Host code, no device needed (csrc/adsi_host.c).  pack_message: what adsi_tx_put_message() puts on the line for msg[len] --
+   the length byte and the sum check, or J-CLIP's DLE SOH header DLE STX framing, length stuffing, parity fill and CRC-16 --
+   into out[out_len >= SPANGPU_ADSI_MSG_BYTES]; returns the packed length, -1 for a message that is too long, or
+   SPANGPU_ERR_BAD_ARG (len < 2, a standard other than the four).  add_field / next_field / standard_to_str: adsi_add_field(),
+   adsi_next_field() and adsi_standard_to_str() with the standard as an argument, all six standards; *baudot_shift is the TDD
+   sender's shift state (0 letters, 1 figures, 2 an explicit shift first), and may be NULL for the others. */
+SPANGPU_API int spangpu_adsi_pack_message(int standard, const uint8_t *msg, int len, uint8_t *out, int out_len);
+SPANGPU_API int spangpu_adsi_add_field(int standard, int *baudot_shift, uint8_t *msg, int len, uint8_t field_type, const uint8_t *field_body,
+                                       int field_len);
+SPANGPU_API int spangpu_adsi_next_field(int standard, const uint8_t *msg, int msg_len, int pos, uint8_t *field_type, const uint8_t **field_body,
+                                        int *field_len);
+SPANGPU_API const char *spangpu_adsi_standard_to_str(int standard);
+SPANGPU_API uint16_t spangpu_adsi_crc16(const uint8_t *buf, int len, uint16_t crc);
+
 /* ---- signalling tone banks (sig_tone.c) -----------------
  * N in-band signalling tone receivers, or senders, of one tone type: 2280 Hz (AC15 and relatives), 2600 Hz, or
  * 2400 Hz / 2600 Hz (SS5).  A receiver detects the tone(s) -- notch filters as guard filters, a sharp detector that

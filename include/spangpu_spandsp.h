@@ -804,6 +804,154 @@ SPANGPU_V18_API int v18_get_current_mode(v18_state_t *s);
 SPANGPU_V18_API const char *v18_mode_to_str(int mode);
 SPANGPU_V18_API const char *v18_status_to_str(int status);
 
+/* ---- Caller ID in the four FSK standards (csrc/shim_adsi.c, csrc/adsi_host.c) ------------------------------------
+ * Reference declarations being replaced:
+ *   adsi_tx_init/_release/_free, adsi_tx, adsi_tx_put_message, adsi_tx_set_preamble, adsi_tx_send_alert_tone,
+ *   adsi_rx_init/_release/_free, adsi_rx, adsi_add_field, adsi_next_field, adsi_standard_to_str,
+ *   adsi_tx_get_logging_state, adsi_rx_get_logging_state          src/spandsp/adsi.h:393-519   src/adsi.c:436-771, 961-1237
+ * An object is a one-channel caller-ID bank (spangpu.h, "Caller-ID banks"): plumbing for a caller that moves over one call
+ * at a time; the path for scale is the bank.  adsi_tx_init() and adsi_rx_init() return NULL for ADSI_STANDARD_CLIP_DTMF and
+ * ADSI_STANDARD_TDD (and any other value), and without a GPU.  put_msg is called from inside adsi_rx(), once per delivered
+ * message, in order.  adsi_add_field(), adsi_next_field() and adsi_standard_to_str() are plain host code and take all six
+ * standards; they read only the object's `standard` (and, for TDD, `baudot_shift`).  adsi_tx_put_message() returns -1 for
+ * a message of fewer than 2 bytes, where the reference reads and writes outside the caller's bytes.
+ * These names are declared with a macro of their own, as the V.18 ones are: tests/test_adsi.py holds them against
+ * src/spandsp/adsi.h.
+ */
+#define SPANGPU_ADSI_API SPANGPU_API
+
+enum
+{
+    ADSI_STANDARD_NONE = 0,
+    ADSI_STANDARD_CLASS = 1,
+    ADSI_STANDARD_CLIP = 2,
+    ADSI_STANDARD_ACLIP = 3,
+    ADSI_STANDARD_JCLIP = 4,
+    ADSI_STANDARD_CLIP_DTMF = 5,
+    ADSI_STANDARD_TDD = 6
+};
+
+/* message types and field types, by their values in the standards (Telcordia GR-30 / SR-TSV-002476, ETSI ETS 300 659-1 and
+   ETS 300 778-1, NTT's caller ID service) */
+enum
+{
+    CLASS_SDMF_CALLERID = 0x04,
+    CLASS_MDMF_CALLERID = 0x80,
+    CLASS_SDMF_MSG_WAITING = 0x06,
+    CLASS_MDMF_MSG_WAITING = 0x82
+};
+
+enum
+{
+    MCLASS_DATETIME = 0x01,
+    MCLASS_CALLER_NUMBER = 0x02,
+    MCLASS_DIALED_NUMBER = 0x03,
+    MCLASS_ABSENCE1 = 0x04,
+    MCLASS_REDIRECT = 0x05,
+    MCLASS_QUALIFIER = 0x06,
+    MCLASS_CALLER_NAME = 0x07,
+    MCLASS_ABSENCE2 = 0x08,
+    MCLASS_ALT_ROUTE = 0x09
+};
+
+enum
+{
+    CLIP_MDMF_CALLERID = 0x80,
+    CLIP_MDMF_MSG_WAITING = 0x82,
+    CLIP_MDMF_CHARGE_INFO = 0x86,
+    CLIP_MDMF_SMS = 0x89
+};
+
+enum
+{
+    CLIP_DATETIME = 0x01,
+    CLIP_CALLER_NUMBER = 0x02,
+    CLIP_DIALED_NUMBER = 0x03,
+    CLIP_ABSENCE1 = 0x04,
+    CLIP_CALLER_NAME = 0x07,
+    CLIP_ABSENCE2 = 0x08,
+    CLIP_VISUAL_INDICATOR = 0x0B,
+    CLIP_MESSAGE_ID = 0x0D,
+    CLIP_CALLTYPE = 0x11,
+    CLIP_NUM_MSG = 0x13
+};
+
+enum
+{
+    ACLIP_SDMF_CALLERID = 0x04,
+    ACLIP_MDMF_CALLERID = 0x80
+};
+
+enum
+{
+    ACLIP_DATETIME = 0x01,
+    ACLIP_CALLER_NUMBER = 0x02,
+    ACLIP_DIALED_NUMBER = 0x03,
+    ACLIP_NUMBER_ABSENCE = 0x04,
+    ACLIP_REDIRECT = 0x05,
+    ACLIP_QUALIFIER = 0x06,
+    ACLIP_CALLER_NAME = 0x07,
+    ACLIP_NAME_ABSENCE = 0x08
+};
+
+#define JCLIP_MDMF_CALLERID             0x40
+
+enum
+{
+    JCLIP_CALLER_NUMBER = 0x02,
+    JCLIP_CALLER_NUM_DES = 0x21,
+    JCLIP_DIALED_NUMBER = 0x09,
+    JCLIP_DIALED_NUM_DES = 0x22,
+    JCLIP_ABSENCE = 0x04
+};
+
+#define CLIP_DTMF_HASH_TERMINATED       '#'
+#define CLIP_DTMF_C_TERMINATED          'C'
+#define CLIP_DTMF_HASH_CALLER_NUMBER    'A'
+#define CLIP_DTMF_HASH_ABSENCE          'D'
+#define CLIP_DTMF_HASH_UNSPECIFIED      0
+
+typedef struct adsi_tx_state_s adsi_tx_state_t;
+struct adsi_tx_state_s
+{
+    int standard;
+    int baudot_shift;
+    spangpu_adsi_tx_t *bank;
+    logging_state_t logging;
+    int16_t *row;
+    int row_cap;
+    int caller_storage;
+};
+
+typedef struct adsi_rx_state_s adsi_rx_state_t;
+struct adsi_rx_state_s
+{
+    int standard;
+    spangpu_adsi_rx_t *bank;
+    span_put_msg_func_t put_msg;
+    void *user_data;
+    logging_state_t logging;
+    int caller_storage;
+};
+
+SPANGPU_ADSI_API logging_state_t *adsi_rx_get_logging_state(adsi_rx_state_t *s);
+SPANGPU_ADSI_API adsi_rx_state_t *adsi_rx_init(adsi_rx_state_t *s, int standard, span_put_msg_func_t put_msg, void *user_data);
+SPANGPU_ADSI_API int adsi_rx_release(adsi_rx_state_t *s);
+SPANGPU_ADSI_API int adsi_rx_free(adsi_rx_state_t *s);
+SPANGPU_ADSI_API int adsi_rx(adsi_rx_state_t *s, const int16_t amp[], int len);
+SPANGPU_ADSI_API logging_state_t *adsi_tx_get_logging_state(adsi_tx_state_t *s);
+SPANGPU_ADSI_API adsi_tx_state_t *adsi_tx_init(adsi_tx_state_t *s, int standard);
+SPANGPU_ADSI_API int adsi_tx_release(adsi_tx_state_t *s);
+SPANGPU_ADSI_API int adsi_tx_free(adsi_tx_state_t *s);
+SPANGPU_ADSI_API void adsi_tx_set_preamble(adsi_tx_state_t *s, int preamble_len, int preamble_ones_len, int postamble_ones_len, int stop_bits);
+SPANGPU_ADSI_API int adsi_tx(adsi_tx_state_t *s, int16_t amp[], int max_len);
+SPANGPU_ADSI_API void adsi_tx_send_alert_tone(adsi_tx_state_t *s);
+SPANGPU_ADSI_API int adsi_tx_put_message(adsi_tx_state_t *s, const uint8_t *msg, int len);
+SPANGPU_ADSI_API int adsi_next_field(adsi_rx_state_t *s, const uint8_t *msg, int msg_len, int pos, uint8_t *field_type, uint8_t const **field_body,
+                                     int *field_len);
+SPANGPU_ADSI_API int adsi_add_field(adsi_tx_state_t *s, uint8_t *msg, int len, uint8_t field_type, uint8_t const *field_body, int field_len);
+SPANGPU_ADSI_API const char *adsi_standard_to_str(int standard);
+
 #if defined(__cplusplus)
 }
 #endif

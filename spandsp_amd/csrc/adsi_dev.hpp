@@ -1,0 +1,638 @@
+// adsi_dev.hpp -- device side of the caller-ID (ADSI) banks: N adsi_tx senders or N adsi_rx receivers in the four FSK
+// standards (CLASS on Bell 202; CLIP, A-CLIP and J-CLIP on V.23 channel 1), messages in and messages out, one channel per
+// lane, state in HBM, one launch per call.  Integer arithmetic throughout but for the alert tone, which is tone_gen()'s
+// binary32 arithmetic as txgen_dev.hpp restates it; the results equal the reference's by construction.
+//
+// What is restated (paths relative to the reference tree):
+//   adsi_tx_get_bit()          src/adsi.c:94-170       preamble, marks, start / 8 data / stop bits, postamble, end of data
+//   adsi_tx()                  src/adsi.c:525-555      the alert tone first, the modem in the remainder of the row
+//   adsi_tx_put_message()      src/adsi.c:637-646, 718-722   the busy check, start_tx() :409-433 and the bit sequencing;
+//                                                      the packing itself runs on the host (adsi_host.c)
+//   adsi_rx_put_bit()          src/adsi.c:192-328      the asynchronous framer, the sum check, J-CLIP's CRC and parity strip
+//   crc_itu16_calc()           src/crc.c:161-169       bit by bit
+//   tone_gen()                 src/tone_generate.c:128-229   for a descriptor of two tones, one on and one off section, no
+//                                                      repeat: the sample arithmetic is that of tx_bank_kernel (txgen_dev.hpp)
+// What is used as it stands: the modulator (ftx_walk() / ftx_render(), fsktx_dev.hpp) with the message framer as its bit
+// source, and the asynchronous demodulator over two waves (fsk_sig_block() / fsk_bit_block(), fsk_dev.hpp) with the message
+// framer as its put_bit.
+//
+// State is structure-of-arrays int32 words.  A sender bank: [kAdsiTxWords + kFskTxWords][n_channels], the message layer's
+// words, then the modulator's in the layout of fsktx_dev.hpp.  A receiver bank: [kAdsiRxWords + kFskScalars + 4*span]
+// [n_channels], the framer's words, then the demodulator's in the layout of fsk_dev.hpp.  A channel's message bytes (256,
+// either way) live in HBM beside the words, channel-major.
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+#include "fsk_dev.hpp"
+#define SPG_FTX_WITHOUT_KERNELS
+#include "fsktx_dev.hpp"
+
+namespace spg
+{
+
+enum
+{
+    ADT_STANDARD = 0,
+    ADT_PREAMBLE_LEN = 1,
+    ADT_PREAMBLE_ONES_LEN = 2,
+    ADT_POSTAMBLE_ONES_LEN = 3,
+    ADT_STOP_BITS = 4,
+    ADT_BYTE_NO = 5,
+    ADT_BIT_POS = 6,
+    ADT_BIT_NO = 7,
+    ADT_MSG_LEN = 8,
+    ADT_TX_SIGNAL_ON = 9,
+    ADT_TONE_SECTION = 10,      // alert_tone_gen: current_section (-1: finished), current_position, phase[0..1], duration[0..1]
+    ADT_TONE_POS = 11,
+    ADT_TONE_PHASE0 = 12,
+    ADT_TONE_PHASE1 = 13,
+    ADT_TONE_DUR0 = 14,
+    ADT_TONE_DUR1 = 15,
+    kAdsiTxWords = 16
+};
+
+enum
+{
+    ADR_STANDARD = 0,
+    ADR_CONSECUTIVE_ONES = 1,
+    ADR_BIT_POS = 2,
+    ADR_IN_PROGRESS = 3,
+    ADR_MSG_LEN = 4,
+    ADR_FRAMING_ERRORS = 5,
+    kAdsiRxWords = 8
+};
+
+constexpr int kAdsiMsg = 256;               // uint8_t msg[256], either way
+constexpr int kAdsiJclip = 4;               // ADSI_STANDARD_JCLIP
+constexpr int kAdsiDle = 0x10;
+
+// The message layer of one sender while a call runs
+struct AdsiTx
+{
+    int preamble_len, preamble_ones_len, postamble_ones_len, stop_bits;
+    int byte_no, bit_pos, bit_no, msg_len, signal_on;
+    const uint8_t *msg;         // this channel's kAdsiMsg bytes
+};
+
+// adsi_tx_get_bit(): 0 or 1, or -1 for SIG_STATUS_END_OF_DATA
+__device__ __forceinline__ int adsi_next_bit(AdsiTx &t)
+{
+    const int marks_end = t.preamble_len + t.preamble_ones_len;
+    if (t.bit_no < t.preamble_len)
+        return t.bit_no++ & 1;
+    if (t.bit_no < marks_end)
+    {
+        t.bit_no++;
+        return 1;
+    }
+    if (t.bit_no <= marks_end)
+    {
+        if (t.bit_pos == 0)
+        {
+            t.bit_pos++;
+            return 0;
+        }
+        if (t.bit_pos < 1 + 8)
+        {
+            // (byte_no stays below msg_len, or is 0 for a sender nothing was put into)
+            const int bit = (t.msg[t.byte_no & (kAdsiMsg - 1)] >> (t.bit_pos - 1)) & 1;
+            t.bit_pos++;
+            return bit;
+        }
+        if (t.bit_pos < 1 + 8 + t.stop_bits - 1)
+        {
+            t.bit_pos++;
+            return 1;
+        }
+        t.bit_pos = 0;
+        if (++t.byte_no >= t.msg_len)
+            t.bit_no++;
+        return 1;
+    }
+    if (t.bit_no <= marks_end + t.postamble_ones_len)
+    {
+        t.bit_no++;
+        return 1;
+    }
+    if (t.signal_on)
+    {
+        t.signal_on = 0;
+        t.msg_len = 0;
+    }
+    return -1;
+}
+
+struct AdsiTxLaunch
+{
+    int32_t *st;                // the bank's words
+    const int16_t *quarter;     // [257] in HBM
+    const float *sine;          // [2048] in HBM: the alert tone is a burst per call set-up, read where it lies
+    const uint8_t *msgs;        // [n_ch][kAdsiMsg]
+    int16_t *pcm;               // [n_ch][stride]
+    int32_t *lens;              // [n_ch] or null
+    long long stride;
+    int n_ch;
+    int samples;
+    int vec;
+    int32_t tone_rate[2];       // the alert tone descriptor: 2130 Hz + 2750 Hz at -13 dBm0 each
+    float tone_gain[2];
+};
+
+// adsi_tx() x N: the shape of fsktx_bank_kernel / v18_tx_kernel, with the message framer as the modulator's bit source.  A
+// channel's row is the alert tone's samples [0, T) -- for almost every call T is 0 -- and the modem's in [T, samples): the
+// modulator walks and renders in row coordinates, from T on.  The byte pull happens in phase 1, at a bit boundary.
+__global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunch L)
+{
+    __shared__ int16_t quarter[258];
+    __shared__ int32_t all_start[kFtxWaves][kFtxCpw][kFtxRunStride];
+    __shared__ int32_t all_phase[kFtxWaves][kFtxCpw][kFtxRunStride];
+    __shared__ int32_t all_rate[kFtxWaves][kFtxCpw][kFtxRunStride];
+    __shared__ __attribute__((aligned(16))) int32_t all_hdr[kFtxWaves][kFtxCpw][8];
+    __shared__ __attribute__((aligned(16))) int32_t all_tone[kFtxWaves][kFtxCpw][8];    // T, sound from, sound to, phase0, phase1
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    int32_t (*r_start)[kFtxRunStride] = all_start[wave];
+    int32_t (*r_phase)[kFtxRunStride] = all_phase[wave];
+    int32_t (*r_rate)[kFtxRunStride] = all_rate[wave];
+    int32_t (*r_hdr)[8] = all_hdr[wave];
+    int32_t (*r_tone)[8] = all_tone[wave];
+    const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
+    const int ch = ch0 + lane;
+    const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+
+    for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
+        quarter[i] = L.quarter[i];
+
+    const size_t n = (size_t) L.n_ch;
+    int32_t *sv = L.st + (owner  ?  ch  :  0);
+    int32_t *st = sv + (size_t) kAdsiTxWords*n;
+    const int samples = L.samples;
+    FtxMod m = {1, 0, 0, 0, 0, 0u};
+    int scaling = 0;
+    bool shutdown = true;
+    AdsiTx t;
+    t.preamble_len = t.preamble_ones_len = t.postamble_ones_len = t.stop_bits = 0;
+    t.byte_no = t.bit_pos = t.bit_no = t.msg_len = t.signal_on = 0;
+    t.msg = L.msgs + (size_t) (owner  ?  ch  :  0)*kAdsiMsg;
+    int section = -1;
+    int pos = 0;
+    uint32_t tph0 = 0u;
+    uint32_t tph1 = 0u;
+    int dur0 = 0;
+    int dur1 = 0;
+    if (owner)
+    {
+        t.preamble_len = sv[ADT_PREAMBLE_LEN*n];
+        t.preamble_ones_len = sv[ADT_PREAMBLE_ONES_LEN*n];
+        t.postamble_ones_len = sv[ADT_POSTAMBLE_ONES_LEN*n];
+        t.stop_bits = sv[ADT_STOP_BITS*n];
+        t.byte_no = sv[ADT_BYTE_NO*n];
+        t.bit_pos = sv[ADT_BIT_POS*n];
+        t.bit_no = sv[ADT_BIT_NO*n];
+        t.msg_len = sv[ADT_MSG_LEN*n];
+        t.signal_on = sv[ADT_TX_SIGNAL_ON*n];
+        section = sv[ADT_TONE_SECTION*n];
+        pos = sv[ADT_TONE_POS*n];
+        tph0 = (uint32_t) sv[ADT_TONE_PHASE0*n];
+        tph1 = (uint32_t) sv[ADT_TONE_PHASE1*n];
+        dur0 = sv[ADT_TONE_DUR0*n];
+        dur1 = sv[ADT_TONE_DUR1*n];
+        m.baud_rate = st[FT_BAUD_RATE*n];
+        m.rate0 = st[FT_RATE0*n];
+        m.rate1 = st[FT_RATE1*n];
+        scaling = st[FT_SCALING*n];
+        m.cur_rate = st[FT_CUR_RATE*n];
+        m.phase = (uint32_t) st[FT_PHASE*n];
+        m.baud_frac = st[FT_BAUD_FRAC*n];
+        shutdown = st[FT_SHUTDOWN*n] != 0;
+    }
+
+    // tone_gen(&s->alert_tone_gen, amp, max_len), tone_generate.c:139-228, for sections 0 (the two tones) and 1 (silence)
+    int tone_len = 0;
+    int snd_from = 0;
+    int snd_to = 0;
+    const uint32_t snd_ph0 = tph0;
+    const uint32_t snd_ph1 = tph1;
+    if (owner  &&  section >= 0)
+    {
+        while (tone_len < samples)
+        {
+            const int dur = (section == 0)  ?  dur0  :  ((section == 1)  ?  dur1  :  0);
+            int limit = tone_len + dur - pos;
+            limit = (limit > samples)  ?  samples  :  limit;
+            pos += limit - tone_len;
+            if (section == 0)
+            {
+                snd_from = tone_len;
+                snd_to = limit;
+                tph0 += (uint32_t) (limit - tone_len)*(uint32_t) L.tone_rate[0];
+                tph1 += (uint32_t) (limit - tone_len)*(uint32_t) L.tone_rate[1];
+            }
+            tone_len = limit;
+            if (pos >= dur)
+            {
+                pos = 0;
+                section++;
+                const int nd = (section == 1)  ?  dur1  :  0;
+                if (section > 3  ||  nd == 0)
+                {
+                    section = -1;       // no repeat
+                    break;
+                }
+            }
+        }
+    }
+    if (lane < kFtxCpw)
+    {
+        r_tone[lane][0] = owner  ?  tone_len  :  0;
+        r_tone[lane][1] = snd_from;
+        r_tone[lane][2] = snd_to;
+        r_tone[lane][3] = (int32_t) snd_ph0;
+        r_tone[lane][4] = (int32_t) snd_ph1;
+    }
+
+    // adsi.c:531-547: with tx_signal_on clear, or a row the tone fills, nothing is asked of the modulator; a modulator that
+    // is shut down returns 0
+    const bool asked = owner  &&  t.signal_on != 0  &&  tone_len < samples;
+    const bool was_shutdown = shutdown;
+    bool silent = !asked  ||  shutdown;
+    int done = owner  ?  tone_len  :  samples;
+    int len = samples;
+    int zero_from = 0x7FFFFFFF;
+    if (owner  &&  silent)
+    {
+        len = tone_len;
+        zero_from = tone_len;
+    }
+    __syncthreads();
+
+    // ---- the alert tone's samples: the wave's channels x chunks of 8, as in ftx_render() ----
+    if (__any(tone_len > 0))
+    {
+        const int nchan = (L.n_ch - ch0 < kFtxCpw)  ?  (L.n_ch - ch0)  :  kFtxCpw;
+        const int cpr = (samples + 7) >> 3;
+        const int total = nchan*cpr;
+        for (int idx = lane;  idx < total;  idx += 64)
+        {
+            const int c = idx/cpr;
+            const int i0 = (idx - c*cpr)*8;
+            const int4 hdr = *reinterpret_cast<const int4 *>(&r_tone[c][0]);        // T, sound from, sound to, phase0
+            const int b = (i0 + 8 < hdr.x)  ?  (i0 + 8)  :  hdr.x;
+            if (i0 >= b)
+                continue;
+            const uint32_t ph1 = (uint32_t) r_tone[c][4];
+            int v[8];
+#pragma unroll
+            for (int j = 0;  j < 8;  j++)
+            {
+                const int i = i0 + j;
+                v[j] = 0;
+                if (i >= hdr.y  &&  i < hdr.z)
+                {
+                    // dds_modf() twice and the sum, tone_generate.c:190-204; lfastrintf() on x86-64 truncates
+                    const uint32_t k = (uint32_t) (i - hdr.y);
+                    const float t0 = __fmul_rn(L.sine[((uint32_t) hdr.w + k*(uint32_t) L.tone_rate[0]) >> 21], L.tone_gain[0]);
+                    const float t1 = __fmul_rn(L.sine[(ph1 + k*(uint32_t) L.tone_rate[1]) >> 21], L.tone_gain[1]);
+                    v[j] = (int) __fadd_rn(t0, t1);
+                }
+            }
+            ftx_store8(L.pcm + (size_t) (ch0 + c)*L.stride + i0, v, 0, b - i0, L.vec != 0);
+        }
+    }
+
+    auto next_bit = [&]() __attribute__((always_inline)) { return adsi_next_bit(t); };
+
+    for (;;)
+    {
+        const int lo = done;
+        int nr = 0;
+        if (owner  &&  done < samples)
+        {
+            if (silent)
+                done = samples;
+            else
+                nr = ftx_walk(m, done, samples, shutdown, len, zero_from, r_start[lane], r_phase[lane], r_rate[lane], next_bit);
+            silent = silent  ||  shutdown;
+        }
+        if (lane < kFtxCpw)
+        {
+            r_hdr[lane][0] = lo;
+            r_hdr[lane][1] = done;
+            r_hdr[lane][2] = nr;
+            r_hdr[lane][3] = zero_from;
+            r_hdr[lane][4] = scaling;
+        }
+        __syncthreads();
+        ftx_render(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, samples, lane, L.vec != 0);
+        if (!__syncthreads_or(done < samples))
+            break;
+    }
+
+    if (owner)
+    {
+        sv[ADT_TONE_SECTION*n] = section;
+        sv[ADT_TONE_POS*n] = pos;
+        sv[ADT_TONE_PHASE0*n] = (int32_t) tph0;
+        sv[ADT_TONE_PHASE1*n] = (int32_t) tph1;
+        if (asked)
+        {
+            if (!was_shutdown)
+            {
+                st[FT_CUR_RATE*n] = m.cur_rate;
+                st[FT_PHASE*n] = (int32_t) m.phase;
+                st[FT_BAUD_FRAC*n] = m.baud_frac;
+                st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
+                sv[ADT_BYTE_NO*n] = t.byte_no;
+                sv[ADT_BIT_POS*n] = t.bit_pos;
+                sv[ADT_BIT_NO*n] = t.bit_no;
+                sv[ADT_MSG_LEN*n] = t.msg_len;
+            }
+            // adsi.c:542-543: a call that gets nothing out of the modulator turns the signal off
+            sv[ADT_TX_SIGNAL_ON*n] = (len - tone_len <= 0)  ?  0  :  t.signal_on;
+        }
+        st[FT_EVENT*n] = (shutdown  &&  !was_shutdown)  ?  1  :  0;
+        if (L.lens)
+            L.lens[ch] = len;
+    }
+}
+
+// adsi_tx_put_message() on channels [lo, hi), after the packing: packed[(c - lo)*kAdsiMsg ...], plens[c - lo] bytes of it,
+// or -1 for a message that is too long.  results[c - lo]: 0 a message is in progress (nothing changes), -1 too long, 1 taken.
+// start_tx() comes ahead of the length check, as in the reference: a sender whose signal is off has its modulator
+// restarted (fsk_tx_init(): the spec's words do not change within a standard) even by a message that is then refused.
+__global__ void adsi_put_kernel(int32_t *st, uint8_t *msgs, int n_ch, int lo, int hi, const uint8_t *packed, const int32_t *plens,
+                                int32_t *results)
+{
+    const int ch = lo + blockIdx.x*blockDim.x + threadIdx.x;
+    if (ch >= hi)
+        return;
+    const size_t n = (size_t) n_ch;
+    int32_t *sv = st + ch;
+    int32_t *ft = sv + (size_t) kAdsiTxWords*n;
+    if (sv[ADT_MSG_LEN*n] > 0)
+    {
+        results[ch - lo] = 0;
+        return;
+    }
+    if (sv[ADT_TX_SIGNAL_ON*n] == 0)
+    {
+        // fsk_tx_restart(), fsk.c:221-235
+        ft[FT_PHASE*n] = 0;
+        ft[FT_BAUD_FRAC*n] = 0;
+        ft[FT_CUR_RATE*n] = ft[FT_RATE1*n];
+        ft[FT_SHUTDOWN*n] = 0;
+        sv[ADT_TX_SIGNAL_ON*n] = 1;
+    }
+    const int len = plens[ch - lo];
+    if (len < 0  ||  len > kAdsiMsg)
+    {
+        results[ch - lo] = -1;
+        return;
+    }
+    const uint8_t *src = packed + (size_t) (ch - lo)*kAdsiMsg;
+    uint8_t *mine = msgs + (size_t) ch*kAdsiMsg;
+    for (int i = 0;  i < len;  i++)
+        mine[i] = src[i];
+    sv[ADT_MSG_LEN*n] = len;
+    sv[ADT_BYTE_NO*n] = 0;
+    sv[ADT_BIT_POS*n] = 0;
+    sv[ADT_BIT_NO*n] = 0;
+    results[ch - lo] = 1;
+}
+
+struct AdsiRxLaunch
+{
+    FskLaunch f;                // st = the demodulator's words inside the bank's; events / ev_count are not used
+    int32_t *sv;                // the bank's words (the framer's come first)
+    uint8_t *msgs;              // [n_ch][kAdsiMsg]: the message being collected
+    uint8_t *rec_bytes;         // [n_ch][cap][kAdsiMsg]: the call's record
+    int32_t *rec_lens;          // [n_ch][cap]
+    int32_t *counts;            // [n_ch]
+    int cap;
+};
+
+// The framer of one receiver while a call runs: adsi_rx_put_bit() as the demodulator's put_bit
+struct AdsiRx
+{
+    int standard, ones, bit_pos, in_progress, msg_len, framing_errors, count;
+    uint8_t *msg;               // this channel's kAdsiMsg bytes
+    uint8_t *rec_bytes;         // this channel's record
+    int32_t *rec_lens;
+    int cap;
+};
+
+// put_msg(user_data, msg, len): one more entry of the call's record
+__device__ __forceinline__ void adsi_deliver(const uint8_t *msg, int len, uint8_t *rec_bytes, int32_t *rec_lens, int cap, int count)
+{
+    if (count < cap)
+    {
+        uint8_t *to = rec_bytes + (size_t) count*kAdsiMsg;
+        for (int i = 0;  i < len;  i++)
+            to[i] = msg[i];
+        rec_lens[count] = len;
+    }
+}
+
+// A whole byte with a good stop bit, adsi.c:256-316: returns the new msg_len, with bit 16 set when a message was delivered.
+// Out of line and on values, so that the framer's words stay in registers: this runs once in ten bit times.
+__device__ __noinline__ int adsi_put_byte(uint8_t *msg, int standard, int in_progress, int msg_len, uint8_t *rec_bytes, int32_t *rec_lens,
+                                          int cap, int count)
+{
+    int delivered = 0;
+    if (msg_len >= kAdsiMsg)
+        return msg_len;
+    if (standard == kAdsiJclip)
+    {
+        // a message starts DLE SOH; only the DLE, with its parity bit, is looked for
+        if (msg_len != 0  ||  in_progress == (0x80 | kAdsiDle))
+            msg[msg_len++] = (uint8_t) in_progress;
+        if (msg_len >= 11  &&  msg_len == (msg[6] & 0x7F) + 11)
+        {
+            uint32_t crc = 0u;
+            for (int i = 2;  i < msg_len;  i++)
+            {
+                crc ^= msg[i];
+                for (int k = 0;  k < 8;  k++)
+                    crc = (crc & 1u)  ?  ((crc >> 1) ^ 0x8408u)  :  (crc >> 1);
+            }
+            if (crc == 0u)
+            {
+                for (int i = 0;  i < msg_len - 2;  i++)
+                    msg[i] &= 0x7F;
+                adsi_deliver(msg, msg_len - 2, rec_bytes, rec_lens, cap, count);
+                delivered = 0x10000;
+            }
+            msg_len = 0;
+        }
+    }
+    else
+    {
+        msg[msg_len++] = (uint8_t) in_progress;
+        if (msg_len >= 3  &&  msg_len == msg[1] + 3)
+        {
+            int sum = 0;
+            for (int i = 0;  i < msg_len - 1;  i++)
+                sum += msg[i];
+            if ((-sum & 0xFF) == msg[msg_len - 1])
+            {
+                adsi_deliver(msg, msg_len - 1, rec_bytes, rec_lens, cap, count);
+                delivered = 0x10000;
+            }
+            msg_len = 0;
+        }
+    }
+    return msg_len | delivered;
+}
+
+__device__ __forceinline__ void adsi_put_bit(AdsiRx &v, int bit)
+{
+    if (bit < 0)
+    {
+        if (bit == -2)
+        {
+            // SIG_STATUS_CARRIER_UP
+            v.ones = 0;
+            v.bit_pos = 0;
+            v.in_progress = 0;
+            v.msg_len = 0;
+        }
+        return;
+    }
+    bit &= 1;
+    if (v.bit_pos == 0)
+    {
+        if (bit == 0)
+        {
+            v.bit_pos = 1;
+            // more than 10 marks ahead of a start bit: the line was idle, message acquisition starts again
+            v.msg_len = (v.ones > 10)  ?  0  :  v.msg_len;
+            v.ones = 0;
+        }
+        else
+        {
+            v.ones++;
+        }
+    }
+    else if (v.bit_pos <= 8)
+    {
+        v.in_progress = (v.in_progress >> 1) | (bit  ?  0x80  :  0);
+        v.bit_pos++;
+    }
+    else
+    {
+        if (bit)
+        {
+            const int r = adsi_put_byte(v.msg, v.standard, v.in_progress, v.msg_len, v.rec_bytes, v.rec_lens, v.cap, v.count);
+            v.msg_len = r & 0xFFFF;
+            v.count += r >> 16;
+        }
+        else
+        {
+            v.framing_errors++;
+        }
+        v.bit_pos = 0;
+        v.in_progress = 0;
+    }
+}
+
+// adsi_rx() x N: fsk_pair_kernel's two waves per 64 channels (fsk_dev.hpp, "A receiver over two waves"), asynchronous,
+// with the message framer behind the bit clock.
+__global__ __launch_bounds__(128) void adsi_rx_kernel(const AdsiRxLaunch V)
+{
+    extern __shared__ int32_t win[];        // [4*span][64], then the two message buffers [2][kFskMsgWords][64]
+    __shared__ uint32_t wave[kFskWave];
+    const FskLaunch &L = V.f;
+    const int lane = threadIdx.x & 63;
+    const int side = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int ch = blockIdx.x*64 + lane;
+    const bool live = ch < L.n_ch;
+    const size_t n = (size_t) L.n_ch;
+    const int span = L.span;
+    int32_t *msg = win + 4*span*64;
+
+    fsk_fill_wave(wave, L.quarter, threadIdx.x, 128);
+    int32_t *st = L.st + (live  ?  ch  :  0);
+    fsk_load_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
+    __syncthreads();
+
+    const int mylen = !live  ?  0  :  L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
+    const int n_blk = (L.samples + 7) >> 3;
+    const int16_t *pcm_row = L.pcm + (size_t) (live  ?  ch  :  0)*L.stride;
+    if (side == 0)
+    {
+        FskSigSide s;
+        fsk_sig_load(s, st, n);
+        auto frame = [&](auto aligned) __attribute__((always_inline))
+        {
+            FskRow<decltype(aligned)::value> row;
+            fsk_row_begin(row, pcm_row, mylen);
+            for (int blk = 0;  blk <= n_blk;  blk++)
+            {
+                if (blk < n_blk)
+                    fsk_sig_block(s, win, wave, msg + (blk & 1)*kFskMsgWords*64, lane, span, row, blk*8, max(0, min(8, mylen - blk*8)));
+                __syncthreads();
+            }
+        };
+        if (L.vec)
+            frame(std::true_type{});
+        else
+            frame(std::false_type{});
+        if (live)
+            fsk_sig_store(s, st, n);
+    }
+    else
+    {
+        FskBitSide t;
+        fsk_bit_load(t, st, n);
+        int32_t *sv = V.sv + (live  ?  ch  :  0);
+        const size_t mine = live  ?  (size_t) ch  :  0;
+        AdsiRx v;
+        v.standard = sv[ADR_STANDARD*n];
+        v.ones = sv[ADR_CONSECUTIVE_ONES*n];
+        v.bit_pos = sv[ADR_BIT_POS*n];
+        v.in_progress = sv[ADR_IN_PROGRESS*n];
+        v.msg_len = sv[ADR_MSG_LEN*n];
+        v.framing_errors = sv[ADR_FRAMING_ERRORS*n];
+        v.count = 0;
+        v.msg = V.msgs + mine*kAdsiMsg;
+        v.rec_bytes = V.rec_bytes + mine*V.cap*kAdsiMsg;
+        v.rec_lens = V.rec_lens + mine*V.cap;
+        v.cap = live  ?  V.cap  :  0;
+        auto emit = [&](int b) __attribute__((always_inline)) { adsi_put_bit(v, b); };
+        auto frame = [&](auto aligned) __attribute__((always_inline))
+        {
+            FskRow<decltype(aligned)::value> row;
+            fsk_row_begin(row, pcm_row, mylen);
+            for (int blk = 0;  blk <= n_blk;  blk++)
+            {
+                if (blk > 0)
+                    fsk_bit_block<decltype(aligned)::value, false>(t, win, wave, msg + ((blk - 1) & 1)*kFskMsgWords*64, lane, span, row, (blk - 1)*8,
+                                  max(0, min(8, mylen - (blk - 1)*8)), emit);
+                __syncthreads();
+            }
+        };
+        if (L.vec)
+            frame(std::true_type{});
+        else
+            frame(std::false_type{});
+        if (live)
+        {
+            fsk_bit_store(t, st, n);
+            sv[ADR_CONSECUTIVE_ONES*n] = v.ones;
+            sv[ADR_BIT_POS*n] = v.bit_pos;
+            sv[ADR_IN_PROGRESS*n] = v.in_progress;
+            sv[ADR_MSG_LEN*n] = v.msg_len;
+            sv[ADR_FRAMING_ERRORS*n] = v.framing_errors;
+            V.counts[ch] = v.count;
+        }
+    }
+    if (live)
+        fsk_store_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
+}
+
+}   // namespace spg

@@ -166,6 +166,41 @@ def lib():
             "spangpu_v18_set_state": (ci, [vp, ci, vp]),
             "spangpu_baudot_encode": (ci, [vp, ci, vp, ci, vp]),
             "spangpu_baudot_decode": (ci, [vp, ci, vp, vp]),
+            "spangpu_adsi_tx_create": (ci, [C.POINTER(vp), ci, ci, vp, ci]),
+            "spangpu_adsi_tx_destroy": (None, [vp]),
+            "spangpu_adsi_tx_channels": (ci, [vp]),
+            "spangpu_adsi_tx_set_stream": (ci, [vp, vp]),
+            "spangpu_adsi_tx_sync": (ci, [vp]),
+            "spangpu_adsi_tx_put_message": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+            "spangpu_adsi_tx_set_preamble": (ci, [vp, ci, ci, ci, ci, ci]),
+            "spangpu_adsi_tx_send_alert_tone": (ci, [vp, ci]),
+            "spangpu_adsi_tx": (ci, [vp, ci, vp, ll, ci, vp]),
+            "spangpu_adsi_tx_restart": (ci, [vp, ci, ci]),
+            "spangpu_adsi_tx_state_words": (ci, [vp]),
+            "spangpu_adsi_tx_get_state": (ci, [vp, ci, vp]),
+            "spangpu_adsi_tx_set_state": (ci, [vp, ci, vp]),
+            "spangpu_adsi_tx_get_message": (ci, [vp, ci, vp]),
+            "spangpu_adsi_tx_set_message": (ci, [vp, ci, vp]),
+            "spangpu_adsi_rx_create": (ci, [C.POINTER(vp), ci, ci, vp, ci]),
+            "spangpu_adsi_rx_destroy": (None, [vp]),
+            "spangpu_adsi_rx_channels": (ci, [vp]),
+            "spangpu_adsi_rx_set_stream": (ci, [vp, vp]),
+            "spangpu_adsi_rx_sync": (ci, [vp]),
+            "spangpu_adsi_rx": (ci, [vp, vp, ci, ci, ll]),
+            "spangpu_adsi_rx_var": (ci, [vp, vp, ci, vp, ci, ll]),
+            "spangpu_adsi_rx_messages": (ci, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_adsi_rx_msg_capacity": (ci, [vp, ci]),
+            "spangpu_adsi_rx_restart": (ci, [vp, ci, ci]),
+            "spangpu_adsi_rx_state_words": (ci, [vp]),
+            "spangpu_adsi_rx_get_state": (ci, [vp, ci, vp]),
+            "spangpu_adsi_rx_set_state": (ci, [vp, ci, vp]),
+            "spangpu_adsi_rx_get_message": (ci, [vp, ci, vp]),
+            "spangpu_adsi_rx_set_message": (ci, [vp, ci, vp]),
+            "spangpu_adsi_pack_message": (ci, [ci, vp, ci, vp, ci]),
+            "spangpu_adsi_add_field": (ci, [ci, vp, vp, ci, C.c_uint8, vp, ci]),
+            "spangpu_adsi_next_field": (ci, [ci, vp, ci, ci, vp, C.POINTER(vp), vp]),
+            "spangpu_adsi_standard_to_str": (C.c_char_p, [ci]),
+            "spangpu_adsi_crc16": (C.c_uint16, [vp, ci, C.c_uint16]),
             "spangpu_awgn_create": (ci, [C.POINTER(vp), ci, ci, vp, vp]),
             "spangpu_awgn_destroy": (None, [vp]),
             "spangpu_awgn_channels": (ci, [vp]),
@@ -1952,6 +1987,178 @@ class V18Bank(_SenderBank):
         w = np.ascontiguousarray(w, np.int32)
         assert len(w) == self.words
         _check(lib().spangpu_v18_set_state(self.h, channel, w.ctypes.data))
+
+
+ADSI_CLASS, ADSI_CLIP, ADSI_ACLIP, ADSI_JCLIP, ADSI_CLIP_DTMF, ADSI_TDD = 1, 2, 3, 4, 5, 6
+ADSI_MSG_BYTES = 256
+
+
+def adsi_pack_message(standard, msg):
+    """What adsi_tx_put_message() puts on the line for `msg` (host code): the packed bytes, or -1 when it is too long."""
+    msg = bytes(msg)
+    out = np.zeros(ADSI_MSG_BYTES, np.uint8)
+    n = lib().spangpu_adsi_pack_message(standard, msg, len(msg), out.ctypes.data, ADSI_MSG_BYTES)
+    if n == -1:
+        return -1
+    _check(n)
+    return out[:n].tobytes()
+
+
+def adsi_add_field(standard, msg, field_type, body=b"", shift=None):
+    """adsi_add_field() on bytes (host code); `shift` is a one-element list holding the TDD shift state."""
+    msg, body = bytes(msg), bytes(body)
+    buf = np.zeros(len(msg) + 2*len(body) + 8, np.uint8)
+    buf[:len(msg)] = np.frombuffer(msg, np.uint8)
+    st = C.c_int(shift[0] if shift else 0)
+    n = lib().spangpu_adsi_add_field(standard, C.addressof(st), buf.ctypes.data, len(msg) if msg else -1, field_type, body, len(body))
+    if shift:
+        shift[0] = st.value
+    return buf[:n].tobytes()
+
+
+def adsi_fields(standard, msg):
+    """adsi_next_field() to its end: [(returned pos, type, len, body offset or -1)], the terminating return last."""
+    msg = bytes(msg)
+    buf = C.create_string_buffer(msg, len(msg) + 8)
+    base = C.addressof(buf)
+    rows, pos = [], -1
+    for _ in range(300):
+        t, body, n = C.c_uint8(0), C.c_void_p(None), C.c_int(0)
+        pos = lib().spangpu_adsi_next_field(standard, base, len(msg), pos, C.addressof(t), C.byref(body), C.addressof(n))
+        if pos < 0:
+            rows.append((pos, 0, 0, -1))
+            break
+        rows.append((pos, t.value, n.value, (body.value - base) if body.value else -1))
+    return rows
+
+
+class AdsiTxBank(_SenderBank):
+    """N caller-ID senders (adsi_tx_put_message / adsi_tx) in the four FSK standards, state in HBM."""
+    _prefix = "adsi_tx"
+
+    def __init__(self, standards, n_channels, device=0):
+        s = np.atleast_1d(np.asarray(standards, np.int32)).copy()
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_adsi_tx_create(C.byref(self.h), device, n_channels, s.ctypes.data, len(s)))
+        self.words = lib().spangpu_adsi_tx_state_words(self.h)
+
+    def put_message(self, msgs, first=0):
+        """One message per channel from `first` on; returns what adsi_tx_put_message() returns for each."""
+        bs = [bytes(m) for m in msgs]
+        n = len(bs)
+        stride = max(len(b) for b in bs)
+        buf = np.zeros((n, stride), np.uint8)
+        lens = np.zeros(n, np.int32)
+        for i, b in enumerate(bs):
+            buf[i, :len(b)] = np.frombuffer(b, np.uint8)
+            lens[i] = len(b)
+        res = np.zeros(n, np.int32)
+        _check(lib().spangpu_adsi_tx_put_message(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, res.ctypes.data))
+        return res
+
+    def tx_host(self, samples):
+        pcm = np.zeros((self.n, max(1, samples)), np.int16)
+        lens = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_adsi_tx(self.h, MEM_HOST, pcm.ctypes.data, pcm.shape[1], samples, lens.ctypes.data))
+        return pcm[:, :samples], lens
+
+    def tx_device(self, pcm_ptr, stride, samples, lens_ptr=None):
+        _check(lib().spangpu_adsi_tx(self.h, MEM_DEVICE, pcm_ptr, stride, samples, lens_ptr))
+
+    def set_preamble(self, channel, preamble_len=-1, preamble_ones_len=-1, postamble_ones_len=-1, stop_bits=-1):
+        _check(lib().spangpu_adsi_tx_set_preamble(self.h, channel, preamble_len, preamble_ones_len, postamble_ones_len, stop_bits))
+
+    def send_alert_tone(self, channel):
+        _check(lib().spangpu_adsi_tx_send_alert_tone(self.h, channel))
+
+    def restart(self, channel, standard):
+        _check(lib().spangpu_adsi_tx_restart(self.h, channel, standard))
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_adsi_tx_get_state(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_adsi_tx_set_state(self.h, channel, w.ctypes.data))
+
+    def get_message(self, channel):
+        m = np.zeros(ADSI_MSG_BYTES, np.uint8)
+        _check(self._f("get_message")(self.h, channel, m.ctypes.data))
+        return m
+
+    def set_message(self, channel, m):
+        m = np.ascontiguousarray(m, np.uint8)
+        assert len(m) == ADSI_MSG_BYTES
+        _check(self._f("set_message")(self.h, channel, m.ctypes.data))
+
+
+class AdsiRxBank(_SenderBank):
+    """N caller-ID receivers (adsi_rx) in the four FSK standards, state in HBM; messages() is the last call's put_msg record."""
+    _prefix = "adsi_rx"
+
+    def __init__(self, standards, n_channels, device=0):
+        s = np.atleast_1d(np.asarray(standards, np.int32)).copy()
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_adsi_rx_create(C.byref(self.h), device, n_channels, s.ctypes.data, len(s)))
+        self.words = lib().spangpu_adsi_rx_state_words(self.h)
+
+    def rx_host(self, amp):
+        amp = np.ascontiguousarray(amp, np.int16)
+        assert amp.shape[0] == self.n
+        _check(lib().spangpu_adsi_rx(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
+
+    def rx_device(self, ptr, samples, stride=0):
+        _check(lib().spangpu_adsi_rx(self.h, ptr, MEM_DEVICE, samples, stride))
+
+    def rx_host_var(self, amp, lens):
+        amp = np.ascontiguousarray(amp, np.int16)
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert amp.shape[0] == self.n and len(lens) == self.n
+        _check(lib().spangpu_adsi_rx_var(self.h, amp.ctypes.data, MEM_HOST, lens.ctypes.data, amp.shape[1], amp.shape[1]))
+
+    def messages(self):
+        """Per channel: the messages the last rx call delivered, in order, as bytes."""
+        by, ln, cnt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        cap = _check(lib().spangpu_adsi_rx_messages(self.h, C.byref(by), C.byref(ln), C.byref(cnt)))
+        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,))
+        out = [[] for _ in range(self.n)]
+        if counts.any():
+            lens = np.ctypeslib.as_array(C.cast(ln, C.POINTER(C.c_int32)), (self.n*cap,)).reshape(self.n, cap)
+            flat = np.ctypeslib.as_array(C.cast(by, C.POINTER(C.c_uint8)), (self.n*cap*ADSI_MSG_BYTES,)).reshape(self.n, cap, ADSI_MSG_BYTES)
+            for c in np.nonzero(counts)[0]:
+                out[c] = [flat[c, k, :lens[c, k]].tobytes() for k in range(counts[c])]
+        return out
+
+    def msg_capacity(self, samples):
+        return _check(lib().spangpu_adsi_rx_msg_capacity(self.h, samples))
+
+    def get_message(self, channel):
+        m = np.zeros(ADSI_MSG_BYTES, np.uint8)
+        _check(lib().spangpu_adsi_rx_get_message(self.h, channel, m.ctypes.data))
+        return m
+
+    def set_message(self, channel, m):
+        m = np.ascontiguousarray(m, np.uint8)
+        assert len(m) == ADSI_MSG_BYTES
+        _check(lib().spangpu_adsi_rx_set_message(self.h, channel, m.ctypes.data))
+
+    def restart(self, channel, standard):
+        _check(lib().spangpu_adsi_rx_restart(self.h, channel, standard))
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_adsi_rx_get_state(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_adsi_rx_set_state(self.h, channel, w.ctypes.data))
 
 
 class MctTxBank(_SenderBank):

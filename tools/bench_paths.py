@@ -1397,6 +1397,67 @@ def bench_v18(args, dev, stream):
         "cpu_baseline": None}
 
 
+def bench_adsi(args, dev, stream):
+    """A caller-ID sender bank (the four FSK standards cycled over the channels) rendering into HBM and a receiver bank reading
+    from there: adsi_tx() and adsi_rx() of every line per tick, timed separately.  A message is put again whenever the senders
+    have gone idle, outside the timed region, so the lines carry a burst most of the time; what arrives is checked."""
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    stds = [engine.ADSI_CLASS, engine.ADSI_CLIP, engine.ADSI_ACLIP, engine.ADSI_JCLIP]
+    sender = engine.AdsiTxBank(stds, n_ch)
+    receiver = engine.AdsiRxBank(stds, n_ch)
+    sender.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    receiver.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    out = torch.zeros(n_ch, FRAME, dtype=torch.int16, device=dev)
+    d_lens = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+    msgs = []
+    for c in range(n_ch):
+        s = stds[c % 4]
+        m = engine.adsi_add_field(s, b"", 0x40 if s == engine.ADSI_JCLIP else 0x80)
+        msgs.append(engine.adsi_add_field(s, m, 0x02, b"555%07d" % c))
+    per_tx, per_rx = [], []
+    total = args.warmup + args.steps
+    delivered = 0
+    t0 = None
+    for i in range(total):
+        if i % 30 == 0:         # a burst is 380 bits of preamble and 20 bytes or so: under 27 ticks of 160 samples
+            res = sender.put_message(msgs)
+            assert i == 0 or int(res.min()) > 0, "a sender was still busy"
+        if i == args.warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record(stream)
+        sender.tx_device(ctypes.c_void_p(out.data_ptr()), FRAME, FRAME, ctypes.c_void_p(d_lens.data_ptr()))
+        e[1].record(stream)
+        receiver.rx_device(ctypes.c_void_p(out.data_ptr()), FRAME, FRAME)
+        e[2].record(stream)
+        if i >= args.warmup:
+            per_tx.append((e[0], e[1]))
+            per_rx.append((e[1], e[2]))
+        got = receiver.messages()
+        for c in range(n_ch):
+            for m in got[c]:
+                assert (m[9:19] if stds[c % 4] == engine.ADSI_JCLIP else m[4:]) == msgs[c][4:], (c, m)
+                delivered += 1
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert delivered >= n_ch*((total - 29)//30), delivered
+    tx_ms = [a.elapsed_time(b) for a, b in per_tx]
+    rx_ms = [a.elapsed_time(b) for a, b in per_rx]
+    value = args.steps*n_ch*FRAME/dt/1e6
+    return {
+        "metric": "Msamples/s of a caller-ID bank pair (adsi_tx into HBM, adsi_rx from HBM; messages read back every tick)", "value": value,
+        "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt*1e3/args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32",
+        "data": "synthetic",
+        "config": {"workload": "caller-ID banks, CLASS / CLIP / A-CLIP / J-CLIP cycled, %d channels x %d-sample frames" % (n_ch, FRAME),
+                   "channels_per_gpu": n_ch, "messages_delivered": delivered},
+        "kernels": {"adsi_tx_kernel": {"avg_launch_us": sum(tx_ms)/len(tx_ms)*1e3, "min_launch_us": min(tx_ms)*1e3},
+                    "adsi_rx_kernel": {"avg_launch_us": sum(rx_ms)/len(rx_ms)*1e3, "min_launch_us": min(rx_ms)*1e3}},
+        "cpu_baseline": None}
+
+
 def bench_sender(args, dev, stream, which):
     """SURVEY 8(f)-1, the last two sources: the FSK transmitter bank (V.21 channel 2, bits from the per-channel LFSR) or the
     connect tone transmitter bank (ANSam/PR, the busiest type: 15 Hz AM and phase hops) writing 160-sample frames into HBM."""
@@ -1665,7 +1726,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
@@ -1736,6 +1797,9 @@ def main():
         return
     if args.workload == "v18":
         emit(bench_v18(args, dev, stream), "v18", args.channels or None)
+        return
+    if args.workload == "adsi":
+        emit(bench_adsi(args, dev, stream), "adsi", args.channels or None)
         return
     if args.workload in ("fsk_tx", "mct_tx"):
         emit(bench_sender(args, dev, stream, args.workload), args.workload, args.channels or None)
