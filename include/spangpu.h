@@ -589,6 +589,9 @@ SPANGPU_API int spangpu_fsk_rx(spangpu_fsk_t *fsk, const int16_t *amp, int mem, 
 SPANGPU_API int spangpu_fsk_rx_var(spangpu_fsk_t *fsk, const int16_t *amp, int mem, const int32_t *lens, int max_samples, long long stride);
 /* events[channel*cap + i], i < counts[channel]; returns cap.  Valid until the next call on this bank. */
 SPANGPU_API int spangpu_fsk_events(spangpu_fsk_t *fsk, const int16_t **events, const int32_t **counts);
+/* The last call's events device to device (for an HDLC receiver bank, spangpu_hdlc_rx_put_events() with elem_bytes 2):
+   dst = int32 counts[n_ch], int16 events[n_ch][per_channel].  Asynchronous on the bank's stream. */
+SPANGPU_API int spangpu_fsk_copy_events(spangpu_fsk_t *fsk, void *dev_dst, size_t dst_bytes, int per_channel);
 /* Tuning / A-B testing: how many wavefronts work on 64 receivers (FSK banks, connect-tone banks and signalling-tone
    receiver banks made or run from now on): 0 = the library's choice, 1 = the whole receiver in one lane of one wavefront,
    2 = the receiver cut into two instruction streams on two wavefronts (fsk_dev.hpp).  Results are identical. */
@@ -692,6 +695,10 @@ SPANGPU_API int spangpu_fsktx_restart(spangpu_fsktx_t *tx, int channel, const sp
    many of them its ring had room for. */
 SPANGPU_API int spangpu_fsktx_put_bits(spangpu_fsktx_t *tx, int first, int n, const uint8_t *bits, int stride, const int32_t *lens,
                                        int32_t *accepted);
+/* The same from rows and lengths already in device memory (an HDLC sender bank's): no copy and no wait, asynchronous on the
+   bank's stream.  dev_lens[i] <= 8*stride is the caller's to keep; dev_accepted may be NULL. */
+SPANGPU_API int spangpu_bits_to_fsktx(spangpu_fsktx_t *tx, int first, int n, const uint8_t *dev_bits, int stride, const int32_t *dev_lens,
+                                              int32_t *dev_accepted);
 SPANGPU_API int spangpu_fsktx_queued(spangpu_fsktx_t *tx, int channel);
 SPANGPU_API int spangpu_fsktx_end_of_data(spangpu_fsktx_t *tx, int channel, int on);
 /* the channels that shut down in the last spangpu_fsktx_tx(); returns how many.  Valid until the next call on this bank. */
@@ -878,6 +885,109 @@ SPANGPU_API int spangpu_adsi_next_field(int standard, const uint8_t *msg, int ms
 SPANGPU_API const char *spangpu_adsi_standard_to_str(int standard);
 SPANGPU_API uint16_t spangpu_adsi_crc16(const uint8_t *buf, int len, uint16_t crc);
 
+/* ---- HDLC framing banks (csrc/hdlc_api.hip, csrc/hdlc_dev.hpp) -------------------------------
+ * N HDLC receivers, or N senders, of hdlc.c: the framer the synchronous modems are used with (T.30 control frames on V.21,
+ * ECM image frames on V.29 / V.27ter / V.17, the data modems).  A receiver bank takes the rows of events a receiver bank
+ * already keeps on the device -- data bits and SIG_STATUS_* reports in the order of the put_bit calls -- and hands back, per
+ * channel and call, the frame_handler and status_handler calls the reference would have made.  A sender bank turns queued
+ * frames into rows of bits in the packing the bit rings of the FSK and modem sender banks take.  All integer: every result
+ * equals the reference's.  One launch per call, one lane per channel.
+ *
+ *   spangpu_hdlc_rx_create()           hdlc_rx_init(NULL, crc32, report_bad_frames, framing_ok_threshold, ..) x N
+ *   spangpu_hdlc_rx_put_events()       hdlc_rx_put_bit(s, e) for the counts[c] entries of row c (counts NULL: all `cap`); entries
+ *                                      are int8 or int16 (elem_bytes 1 or 2), row c at events + c*cap entries; counts lives
+ *                                      where events lives
+ *   spangpu_hdlc_rx_put_modem_events() the same on the block spangpu_modem_copy_events() wrote (device memory)
+ *   spangpu_hdlc_rx_put()              hdlc_rx_put(s, bytes + c*stride, lens[c]) x N (lens NULL: all `stride`)
+ *   spangpu_hdlc_rx_records()          the handler calls of the last put, in call order: counts[c] records at
+ *                                      recs[c*rec_cap ..]; a record >= 0 is a frame_handler call, length in bits 0-15 and
+ *                                      ok in bit 16, its octets behind those of the channel's earlier frames at
+ *                                      bytes[c*byte_cap ..]; a record < 0 is a status_handler call with that SIG_STATUS_*
+ *                                      code (framing OK, abort, octet report, and the modem's own reports passed on);
+ *                                      counts[n_channels + c] is the channel's octets.  rec_cap (returned) and byte_cap
+ *                                      are spangpu_hdlc_rx_capacity() of the call's entries per row (8*stride for put).
+ *   spangpu_hdlc_tx_create()           hdlc_tx_init(NULL, crc32, inter_frame_flags, false, ..) x N; progressive mode is
+ *                                      refused (SPANGPU_ERR_UNSUPPORTED)
+ *   spangpu_hdlc_tx_frames() ..        commands into a channel's queue of queue_depth slots: FRAME = hdlc_tx_frame(), then
+ *                                      hdlc_tx_corrupt_frame() where flags[i] & 1; FLAGS = hdlc_tx_flags(len); ABORT =
+ *                                      hdlc_tx_abort(); END = hdlc_tx_frame(s, NULL, 0).  lens[i] < 0: nothing for that
+ *                                      channel, 0: END.  results[i] is 0, or -1 where the queue is full or the frame is
+ *                                      longer than the channel's max_frame_len.
+ *   spangpu_hdlc_tx_get_bits()         hdlc_tx_get_bit(s) x want[c] (want NULL: want_all), packed LSB first into
+ *                                      bits[c*stride ..]; lens[c] is the number produced, short of want[c] only where
+ *                                      get_byte answered SIG_STATUS_END_OF_DATA
+ *   spangpu_hdlc_tx_events()           the ends and underflows of the last get_bits: returns their number; kinds[i] is
+ *                                      SIG_STATUS_END_OF_DATA (-7), or k > 0: k underflow reports found the queue empty
+ *
+ * The queue stands for the reference's underflow handler.  The head command is taken (a) wherever hdlc_tx_get_byte() would
+ * call the handler -- one command; an empty queue there counts as an underflow -- and (b) at the top of a get_bits call for
+ * a channel that has no frame in progress: commands are applied until a frame is loaded or the queue is empty.  This is a
+ * reference sender whose handler pops a FIFO, and whose owner offers the FIFO between calls while the sender idles.
+ *
+ * A bank that reads another bank's device buffer does not order the two streams: put both banks on one stream with
+ * _set_stream(), as the other device-resident loops do.  A channel with counts[c] / want[c] == 0 sits the call out, its
+ * state untouched.
+ */
+typedef struct spangpu_hdlc_rx_s spangpu_hdlc_rx_t;
+typedef struct spangpu_hdlc_tx_s spangpu_hdlc_tx_t;
+
+SPANGPU_API int spangpu_hdlc_rx_create(spangpu_hdlc_rx_t **bank, int device, int n_channels, int crc32, int report_bad_frames,
+                                       int framing_ok_threshold);
+SPANGPU_API void spangpu_hdlc_rx_destroy(spangpu_hdlc_rx_t *bank);
+SPANGPU_API int spangpu_hdlc_rx_channels(const spangpu_hdlc_rx_t *bank);
+SPANGPU_API int spangpu_hdlc_rx_set_stream(spangpu_hdlc_rx_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_hdlc_rx_sync(spangpu_hdlc_rx_t *bank);
+SPANGPU_API int spangpu_hdlc_rx_put_events(spangpu_hdlc_rx_t *bank, int mem_kind, const void *events, int elem_bytes, long long cap,
+                                           const int32_t *counts);
+SPANGPU_API int spangpu_hdlc_rx_put_modem_events(spangpu_hdlc_rx_t *bank, const void *dev_block, int per_channel);
+SPANGPU_API int spangpu_hdlc_rx_put(spangpu_hdlc_rx_t *bank, int mem_kind, const uint8_t *bytes, long long stride, const int32_t *lens);
+/* Valid until the next call on this bank.  A count above the capacity is an error (SPANGPU_ERR_STATE), never a list cut short. */
+SPANGPU_API int spangpu_hdlc_rx_records(spangpu_hdlc_rx_t *bank, const int32_t **recs, const int32_t **counts, const uint8_t **bytes);
+/* What no row of `events` entries can exceed, whatever the channel's state: events + events/8 + 1 records (one handler call
+   per entry, and a second one -- the octet report -- with an abort, which takes eight bits), 403 + events/8 octets (what a
+   frame carried into the call can deliver, then eight bits per octet), rounded up to a multiple of 4. */
+SPANGPU_API int spangpu_hdlc_rx_capacity(long long events, int *rec_cap, int *byte_cap);
+/* channel -1: every channel */
+SPANGPU_API int spangpu_hdlc_rx_set_max_frame_len(spangpu_hdlc_rx_t *bank, int channel, int len);
+SPANGPU_API int spangpu_hdlc_rx_set_octet_counting_report_interval(spangpu_hdlc_rx_t *bank, int channel, int interval);
+SPANGPU_API int spangpu_hdlc_rx_restart(spangpu_hdlc_rx_t *bank, int channel);
+/* stats[5]: bytes, good_frames, crc_errors, length_errors, aborts (hdlc_rx_stats_t) */
+SPANGPU_API int spangpu_hdlc_rx_get_stats(spangpu_hdlc_rx_t *bank, int channel, int32_t *stats);
+/* Test / checkpoint access to one channel's state (layout: hdlc_dev.hpp) and to the SPANGPU_HDLC_BUFFER_BYTES of its frame
+   buffer, which travel with the words when a channel is moved */
+#define SPANGPU_HDLC_BUFFER_BYTES           404
+SPANGPU_API int spangpu_hdlc_rx_state_words(const spangpu_hdlc_rx_t *bank);
+SPANGPU_API int spangpu_hdlc_rx_get_state(spangpu_hdlc_rx_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_hdlc_rx_set_state(spangpu_hdlc_rx_t *bank, int channel, const int32_t *words);
+SPANGPU_API int spangpu_hdlc_rx_get_buffer(spangpu_hdlc_rx_t *bank, int channel, uint8_t *buffer);
+SPANGPU_API int spangpu_hdlc_rx_set_buffer(spangpu_hdlc_rx_t *bank, int channel, const uint8_t *buffer);
+
+SPANGPU_API int spangpu_hdlc_tx_create(spangpu_hdlc_tx_t **bank, int device, int n_channels, int crc32, int inter_frame_flags, int progressive,
+                                       int queue_depth);
+SPANGPU_API void spangpu_hdlc_tx_destroy(spangpu_hdlc_tx_t *bank);
+SPANGPU_API int spangpu_hdlc_tx_channels(const spangpu_hdlc_tx_t *bank);
+SPANGPU_API int spangpu_hdlc_tx_set_stream(spangpu_hdlc_tx_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_hdlc_tx_sync(spangpu_hdlc_tx_t *bank);
+/* channels first .. first + n - 1: lens[i] bytes from frames[i*stride] (host memory); flags and results may be NULL */
+SPANGPU_API int spangpu_hdlc_tx_frames(spangpu_hdlc_tx_t *bank, int first, int n, const uint8_t *frames, int stride, const int32_t *lens,
+                                       const int32_t *flags, int32_t *results);
+SPANGPU_API int spangpu_hdlc_tx_flags(spangpu_hdlc_tx_t *bank, int first, int n, int len, int32_t *results);
+SPANGPU_API int spangpu_hdlc_tx_abort(spangpu_hdlc_tx_t *bank, int first, int n, int32_t *results);
+SPANGPU_API int spangpu_hdlc_tx_end(spangpu_hdlc_tx_t *bank, int first, int n, int32_t *results);
+SPANGPU_API int spangpu_hdlc_tx_queued(spangpu_hdlc_tx_t *bank, int channel);
+SPANGPU_API int spangpu_hdlc_tx_set_max_frame_len(spangpu_hdlc_tx_t *bank, int channel, int len);
+/* hdlc_tx_restart(); the channel's queue is emptied */
+SPANGPU_API int spangpu_hdlc_tx_restart(spangpu_hdlc_tx_t *bank, int channel);
+/* bits and lens ([n_channels], may be NULL) live where mem_kind says; want is host memory */
+SPANGPU_API int spangpu_hdlc_tx_get_bits(spangpu_hdlc_tx_t *bank, int mem_kind, uint8_t *bits, long long stride, const int32_t *want, int want_all,
+                                         int32_t *lens);
+SPANGPU_API int spangpu_hdlc_tx_events(spangpu_hdlc_tx_t *bank, const int32_t **channels, const int32_t **kinds);
+SPANGPU_API int spangpu_hdlc_tx_state_words(const spangpu_hdlc_tx_t *bank);
+SPANGPU_API int spangpu_hdlc_tx_get_state(spangpu_hdlc_tx_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_hdlc_tx_set_state(spangpu_hdlc_tx_t *bank, int channel, const int32_t *words);
+SPANGPU_API int spangpu_hdlc_tx_get_buffer(spangpu_hdlc_tx_t *bank, int channel, uint8_t *buffer);
+SPANGPU_API int spangpu_hdlc_tx_set_buffer(spangpu_hdlc_tx_t *bank, int channel, const uint8_t *buffer);
+
 /* ---- signalling tone banks (sig_tone.c) -----------------
  * N in-band signalling tone receivers, or senders, of one tone type: 2280 Hz (AC15 and relatives), 2600 Hz, or
  * 2400 Hz / 2600 Hz (SS5).  A receiver detects the tone(s) -- notch filters as guard filters, a sharp detector that
@@ -1013,6 +1123,10 @@ SPANGPU_API int spangpu_modemtx_tx_continue(spangpu_modemtx_t *tx, int mem, int1
    accepted[i] (may be NULL) = how many of them its ring had room for. */
 SPANGPU_API int spangpu_modemtx_put_bits(spangpu_modemtx_t *tx, int first, int n, const uint8_t *bits, int stride, const int32_t *lens,
                                          int32_t *accepted);
+/* The same from rows and lengths already in device memory (an HDLC sender bank's): no copy and no wait, asynchronous on the
+   bank's stream.  dev_lens[i] <= 8*stride is the caller's to keep; dev_accepted may be NULL. */
+SPANGPU_API int spangpu_bits_to_modemtx(spangpu_modemtx_t *tx, int first, int n, const uint8_t *dev_bits, int stride,
+                                                const int32_t *dev_lens, int32_t *dev_accepted);
 SPANGPU_API int spangpu_modemtx_queued(spangpu_modemtx_t *tx, int channel);
 SPANGPU_API int spangpu_modemtx_end_of_data(spangpu_modemtx_t *tx, int channel, int on);
 /* The status calls of the last spangpu_modemtx_tx(): channels[i] got kinds[i] (SPANGPU_MODEMTX_END_OF_DATA or

@@ -237,4 +237,22 @@ int bitring_put(BankCore *c, BitPut *p, int32_t *rd_row, int32_t *count_row, uin
     return SPANGPU_OK;
 }
 
+int bitring_put_device(BankCore *c, BitPut *p, int32_t *rd_row, int32_t *count_row, uint32_t *queue, int qring, int qcap, int first, int n,
+                       const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted)
+{
+    if (!range_ok(c, first, n)  ||  bits == NULL  ||  lens == NULL  ||  stride <= 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    SPG_TRY(hipSetDevice(c->device));
+    if (accepted == NULL)
+    {
+        if (p->d_acc == NULL  &&  hipMalloc(&p->d_acc, (size_t) c->n_ch*sizeof(int32_t)) != hipSuccess)
+            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "bit staging");
+        accepted = p->d_acc;
+    }
+    hipLaunchKernelGGL(bitring_put_kernel, dim3((n + 63)/64), dim3(64), 0, c->stream, rd_row, count_row, queue, c->n_ch, qring, qcap,
+                       first, first + n, bits, stride, lens, accepted);
+    SPG_TRY(hipGetLastError());
+    return SPANGPU_OK;
+}
+
 }   // namespace spg

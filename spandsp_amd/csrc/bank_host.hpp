@@ -195,6 +195,12 @@ struct BitPut
 int bitring_put(BankCore *c, BitPut *p, int32_t *rd_row, int32_t *count_row, uint32_t *queue, int qring, int qcap, int first, int n,
                 const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted);
 
+// the same from rows and lengths that are already in device memory, with no copy and no wait: asynchronous on the bank's
+// stream.  Nobody checks a length against its row here: lens[i] <= 8*stride is the caller's to keep.  accepted (device
+// memory) may be NULL.
+int bitring_put_device(BankCore *c, BitPut *p, int32_t *rd_row, int32_t *count_row, uint32_t *queue, int qring, int qcap, int first, int n,
+                       const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted);
+
 static inline void bitput_free(BitPut *p)
 {
     (void) hipFree(p->d_bits);

@@ -492,6 +492,27 @@ int spangpu_fsk_events(spangpu_fsk_t *f, const int16_t **events, const int32_t *
     return f->last_cap;
 }
 
+// The last call's events device to device, the twin of spangpu_modem_copy_events(): dst = int32 counts[n_ch], then int16
+// events[n_ch][per_channel].  Asynchronous on the bank's stream; a channel that made more than per_channel events shows it
+// by its count.
+int spangpu_fsk_copy_events(spangpu_fsk_t *f, void *dev_dst, size_t dst_bytes, int per_channel)
+{
+    if (f == NULL  ||  dev_dst == NULL  ||  per_channel <= 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    if (f->last_cap <= 0)
+        return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_fsk_rx() yet");
+    const size_t need = (size_t) f->c.n_ch*(sizeof(int32_t) + (size_t) per_channel*sizeof(int16_t));
+    if (dst_bytes < need)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "destination too small");
+    SPG_TRY(hipSetDevice(f->c.device));
+    SPG_TRY(hipMemcpyAsync(dev_dst, f->ev_count, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, f->c.stream));
+    const int w = (per_channel < f->last_cap)  ?  per_channel  :  f->last_cap;
+    SPG_TRY(hipMemcpy2DAsync((char *) dev_dst + (size_t) f->c.n_ch*sizeof(int32_t), (size_t) per_channel*sizeof(int16_t), f->events,
+                             (size_t) f->last_cap*sizeof(int16_t), (size_t) w*sizeof(int16_t), (size_t) f->c.n_ch, hipMemcpyDeviceToDevice,
+                             f->c.stream));
+    return SPANGPU_OK;
+}
+
 int spangpu_fsk_get_state(spangpu_fsk_t *f, int channel, int32_t *words)
 {
     if (f == NULL  ||  words == NULL  ||  !channel_ok(&f->c, channel))

@@ -271,6 +271,16 @@ int spangpu_fsktx_put_bits(spangpu_fsktx_t *t, int first, int n, const uint8_t *
                        t->qcap, first, n, bits, stride, lens, accepted);
 }
 
+// spangpu_fsktx_put_bits() from rows and lengths in device memory (another bank's output): no copy, no wait
+int spangpu_bits_to_fsktx(spangpu_fsktx_t *t, int first, int n, const uint8_t *dev_bits, int stride, const int32_t *dev_lens,
+                                  int32_t *dev_accepted)
+{
+    if (t == NULL  ||  t->source != FTX_SRC_QUEUE)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    return bitring_put_device(&t->c, &t->put, t->c.st + (size_t) FT_QRD*t->c.n_ch, t->c.st + (size_t) FT_QCOUNT*t->c.n_ch, t->queue, t->qring,
+                              t->qcap, first, n, dev_bits, stride, dev_lens, dev_accepted);
+}
+
 int spangpu_fsktx_set_framing(spangpu_fsktx_t *t, int channel, int data_bits, int parity, int stop_bits)
 {
     if (t == NULL  ||  channel < -1  ||  channel >= t->c.n_ch  ||  !framing_ok(data_bits, parity, stop_bits))

@@ -484,6 +484,16 @@ int spangpu_modemtx_put_bits(spangpu_modemtx_t *t, int first, int n, const uint8
                        t->qcap, first, n, bits, stride, lens, accepted);
 }
 
+// spangpu_modemtx_put_bits() from rows and lengths in device memory (another bank's output): no copy, no wait
+int spangpu_bits_to_modemtx(spangpu_modemtx_t *t, int first, int n, const uint8_t *dev_bits, int stride, const int32_t *dev_lens,
+                                    int32_t *dev_accepted)
+{
+    if (t == NULL  ||  t->source != kTxSrcQueue)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    return bitring_put_device(&t->c, &t->put, t->qst + (size_t) VQ_RD*t->c.n_ch, t->qst + (size_t) VQ_COUNT*t->c.n_ch, t->queue, t->qring,
+                              t->qcap, first, n, dev_bits, stride, dev_lens, dev_accepted);
+}
+
 int spangpu_modemtx_queued(spangpu_modemtx_t *t, int channel)
 {
     if (t == NULL  ||  !channel_ok(&t->c, channel)  ||  t->source != kTxSrcQueue)

@@ -116,6 +116,7 @@ def lib():
             "spangpu_modemtx_tx_lens": (ci, [vp, ci, vp, ll, ci, vp]),
             "spangpu_modemtx_tx_continue": (ci, [vp, ci, vp, ll, ci, vp]),
             "spangpu_modemtx_put_bits": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+            "spangpu_bits_to_modemtx": (ci, [vp, ci, ci, vp, ci, vp, vp]),
             "spangpu_modemtx_queued": (ci, [vp, ci]),
             "spangpu_modemtx_end_of_data": (ci, [vp, ci, ci]),
             "spangpu_modemtx_events": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
@@ -130,6 +131,7 @@ def lib():
             "spangpu_fsktx_power": (ci, [vp, ci, cf]),
             "spangpu_fsktx_restart": (ci, [vp, ci, vp]),
             "spangpu_fsktx_put_bits": (ci, [vp, ci, ci, vp, ci, vp, vp]),
+            "spangpu_bits_to_fsktx": (ci, [vp, ci, ci, vp, ci, vp, vp]),
             "spangpu_fsktx_queued": (ci, [vp, ci]),
             "spangpu_fsktx_end_of_data": (ci, [vp, ci, ci]),
             "spangpu_fsktx_events": (ci, [vp, C.POINTER(vp)]),
@@ -201,6 +203,44 @@ def lib():
             "spangpu_adsi_next_field": (ci, [ci, vp, ci, ci, vp, C.POINTER(vp), vp]),
             "spangpu_adsi_standard_to_str": (C.c_char_p, [ci]),
             "spangpu_adsi_crc16": (C.c_uint16, [vp, ci, C.c_uint16]),
+            "spangpu_hdlc_rx_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci]),
+            "spangpu_hdlc_rx_destroy": (None, [vp]),
+            "spangpu_hdlc_rx_channels": (ci, [vp]),
+            "spangpu_hdlc_rx_set_stream": (ci, [vp, vp]),
+            "spangpu_hdlc_rx_sync": (ci, [vp]),
+            "spangpu_hdlc_rx_put_events": (ci, [vp, ci, vp, ci, ll, vp]),
+            "spangpu_hdlc_rx_put_modem_events": (ci, [vp, vp, ci]),
+            "spangpu_hdlc_rx_put": (ci, [vp, ci, vp, ll, vp]),
+            "spangpu_hdlc_rx_records": (ci, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_hdlc_rx_capacity": (ci, [ll, C.POINTER(ci), C.POINTER(ci)]),
+            "spangpu_hdlc_rx_set_max_frame_len": (ci, [vp, ci, ci]),
+            "spangpu_hdlc_rx_set_octet_counting_report_interval": (ci, [vp, ci, ci]),
+            "spangpu_hdlc_rx_restart": (ci, [vp, ci]),
+            "spangpu_hdlc_rx_get_stats": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_rx_state_words": (ci, [vp]),
+            "spangpu_hdlc_rx_get_state": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_rx_set_state": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_rx_get_buffer": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_rx_set_buffer": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_tx_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, ci]),
+            "spangpu_hdlc_tx_destroy": (None, [vp]),
+            "spangpu_hdlc_tx_channels": (ci, [vp]),
+            "spangpu_hdlc_tx_set_stream": (ci, [vp, vp]),
+            "spangpu_hdlc_tx_sync": (ci, [vp]),
+            "spangpu_hdlc_tx_frames": (ci, [vp, ci, ci, vp, ci, vp, vp, vp]),
+            "spangpu_hdlc_tx_flags": (ci, [vp, ci, ci, ci, vp]),
+            "spangpu_hdlc_tx_abort": (ci, [vp, ci, ci, vp]),
+            "spangpu_hdlc_tx_end": (ci, [vp, ci, ci, vp]),
+            "spangpu_hdlc_tx_queued": (ci, [vp, ci]),
+            "spangpu_hdlc_tx_set_max_frame_len": (ci, [vp, ci, ci]),
+            "spangpu_hdlc_tx_restart": (ci, [vp, ci]),
+            "spangpu_hdlc_tx_get_bits": (ci, [vp, ci, vp, ll, vp, ci, vp]),
+            "spangpu_hdlc_tx_events": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_hdlc_tx_state_words": (ci, [vp]),
+            "spangpu_hdlc_tx_get_state": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_tx_set_state": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_tx_get_buffer": (ci, [vp, ci, vp]),
+            "spangpu_hdlc_tx_set_buffer": (ci, [vp, ci, vp]),
             "spangpu_awgn_create": (ci, [C.POINTER(vp), ci, ci, vp, vp]),
             "spangpu_awgn_destroy": (None, [vp]),
             "spangpu_awgn_channels": (ci, [vp]),
@@ -254,6 +294,7 @@ def lib():
             "spangpu_fsk_rx": (ci, [vp, vp, ci, ci, ll]),
             "spangpu_fsk_rx_var": (ci, [vp, vp, ci, vp, ci, ll]),
             "spangpu_fsk_events": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_fsk_copy_events": (ci, [vp, vp, C.c_size_t, ci]),
             "spangpu_fsk_state_words": (ci, [vp]),
             "spangpu_fsk_get_state": (ci, [vp, ci, vp]),
             "spangpu_fsk_set_state": (ci, [vp, ci, vp]),
@@ -1676,6 +1717,10 @@ class FskBank:
         flat = np.ctypeslib.as_array(C.cast(ev, C.POINTER(C.c_int16)), (self.n*cap,)).reshape(self.n, cap)
         return [flat[c, :counts[c]].copy() for c in range(self.n)]
 
+    def copy_events(self, dst_ptr, nbytes, per_channel):
+        """The last call's events device to device: int32 counts[n], int16 events[n][per_channel]."""
+        _check(lib().spangpu_fsk_copy_events(self.h, dst_ptr, nbytes, per_channel))
+
     def get_state(self, channel):
         w = np.zeros(self.words, np.int32)
         _check(lib().spangpu_fsk_get_state(self.h, channel, w.ctypes.data))
@@ -1855,6 +1900,10 @@ class FskTxBank(_SenderBank):
         acc = np.zeros(n, np.int32)
         _check(lib().spangpu_fsktx_put_bits(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, acc.ctypes.data))
         return acc
+
+    def put_bits_device(self, bits_ptr, stride, lens_ptr, first=0, n=None, accepted_ptr=None):
+        """put_bits from rows and lengths in device memory (an HdlcTxBank's): no copy, no wait."""
+        _check(lib().spangpu_bits_to_fsktx(self.h, first, self.n - first if n is None else n, bits_ptr, stride, lens_ptr, accepted_ptr))
 
     def queued(self, channel):
         return _check(lib().spangpu_fsktx_queued(self.h, channel))
@@ -2161,6 +2210,187 @@ class AdsiRxBank(_SenderBank):
         _check(lib().spangpu_adsi_rx_set_state(self.h, channel, w.ctypes.data))
 
 
+# ---- HDLC framing banks (include/spangpu.h "HDLC framing banks") ---------------------------
+HDLC_BUFFER_BYTES = 404
+HDLC_FRAME_OK = 0x10000
+
+
+def hdlc_rx_capacity(events):
+    """(records, octets) no row of `events` entries can exceed."""
+    r, y = C.c_int(0), C.c_int(0)
+    _check(lib().spangpu_hdlc_rx_capacity(events, C.byref(r), C.byref(y)))
+    return r.value, y.value
+
+
+class _HdlcBank(_SenderBank):
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(self._f("get_state")(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(self._f("set_state")(self.h, channel, w.ctypes.data))
+
+    def get_buffer(self, channel):
+        m = np.zeros(HDLC_BUFFER_BYTES, np.uint8)
+        _check(self._f("get_buffer")(self.h, channel, m.ctypes.data))
+        return m
+
+    def set_buffer(self, channel, m):
+        m = np.ascontiguousarray(m, np.uint8)
+        assert len(m) == HDLC_BUFFER_BYTES
+        _check(self._f("set_buffer")(self.h, channel, m.ctypes.data))
+
+    def set_max_frame_len(self, channel, n):
+        _check(self._f("set_max_frame_len")(self.h, channel, n))
+
+    def restart(self, channel):
+        _check(self._f("restart")(self.h, channel))
+
+
+class HdlcRxBank(_HdlcBank):
+    """N HDLC receivers (hdlc_rx_put_bit / hdlc_rx_put) over rows of events or octets; records() is the last call's
+    frame_handler and status_handler calls."""
+    _prefix = "hdlc_rx"
+
+    def __init__(self, n_channels, crc32=False, report_bad_frames=False, framing_ok_threshold=1, device=0):
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_hdlc_rx_create(C.byref(self.h), device, n_channels, int(crc32), int(report_bad_frames), framing_ok_threshold))
+        self.words = lib().spangpu_hdlc_rx_state_words(self.h)
+        self._entries = 0
+
+    def put_events_host(self, events, counts=None):
+        """events: [n, cap] int8 or int16; counts: per channel, None for whole rows."""
+        assert events.dtype in (np.int8, np.int16) and events.shape[0] == self.n and events.flags.c_contiguous
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.int32)
+            assert len(counts) == self.n
+        _check(lib().spangpu_hdlc_rx_put_events(self.h, MEM_HOST, events.ctypes.data, events.itemsize, events.shape[1],
+                                                counts.ctypes.data if counts is not None else None))
+        self._entries = events.shape[1]
+
+    def put_events_device(self, events_ptr, elem_bytes, cap, counts_ptr=None):
+        _check(lib().spangpu_hdlc_rx_put_events(self.h, MEM_DEVICE, events_ptr, elem_bytes, cap, counts_ptr))
+        self._entries = cap
+
+    def put_modem_events(self, block_ptr, per_channel):
+        _check(lib().spangpu_hdlc_rx_put_modem_events(self.h, block_ptr, per_channel))
+        self._entries = per_channel
+
+    def put_host(self, octets, lens=None):
+        """octets: [n, stride] uint8, most significant bit first."""
+        assert octets.dtype == np.uint8 and octets.shape[0] == self.n and octets.flags.c_contiguous
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, np.int32)
+            assert len(lens) == self.n
+        _check(lib().spangpu_hdlc_rx_put(self.h, MEM_HOST, octets.ctypes.data, octets.shape[1], lens.ctypes.data if lens is not None else None))
+        self._entries = 8*octets.shape[1]
+
+    def records(self):
+        """Per channel: [(len, ok, bytes) for a frame | code < 0 for a status], in call order."""
+        rp, cp, bp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rec_cap = _check(lib().spangpu_hdlc_rx_records(self.h, C.byref(rp), C.byref(cp), C.byref(bp)))
+        byte_cap = hdlc_rx_capacity(self._entries)[1]
+        counts = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (2*self.n,))
+        out = [[] for _ in range(self.n)]
+        if counts[:self.n].any():
+            recs = np.ctypeslib.as_array(C.cast(rp, C.POINTER(C.c_int32)), (self.n*rec_cap,)).reshape(self.n, rec_cap)
+            by = np.ctypeslib.as_array(C.cast(bp, C.POINTER(C.c_uint8)), (self.n*byte_cap,)).reshape(self.n, byte_cap)
+            for c in np.nonzero(counts[:self.n])[0]:
+                at = 0
+                for r in recs[c, :counts[c]]:
+                    r = int(r)
+                    if r < 0:
+                        out[c].append(r)
+                    else:
+                        n = r & 0xFFFF
+                        out[c].append((n, bool(r & HDLC_FRAME_OK), by[c, at:at + n].tobytes()))
+                        at += n
+                assert at == counts[self.n + c]
+        return out
+
+    def set_octet_counting_report_interval(self, channel, interval):
+        _check(lib().spangpu_hdlc_rx_set_octet_counting_report_interval(self.h, channel, interval))
+
+    def get_stats(self, channel):
+        """bytes, good_frames, crc_errors, length_errors, aborts"""
+        w = np.zeros(5, np.int32)
+        _check(lib().spangpu_hdlc_rx_get_stats(self.h, channel, w.ctypes.data))
+        return w
+
+
+class HdlcTxBank(_HdlcBank):
+    """N HDLC senders (hdlc_tx_get_bit) fed from a per-channel command queue that stands for the underflow handler."""
+    _prefix = "hdlc_tx"
+
+    def __init__(self, n_channels, crc32=False, inter_frame_flags=1, queue_depth=4, progressive=False, device=0):
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_hdlc_tx_create(C.byref(self.h), device, n_channels, int(crc32), inter_frame_flags, int(progressive), queue_depth))
+        self.words = lib().spangpu_hdlc_tx_state_words(self.h)
+
+    def frames(self, frames, first=0, corrupt=None):
+        """One frame per channel from `first` on (None: nothing for that channel, b"": the end of the data); the results."""
+        n = len(frames)
+        stride = max([1] + [len(f) for f in frames if f is not None])
+        buf = np.zeros((n, stride), np.uint8)
+        lens = np.full(n, -1, np.int32)
+        for i, f in enumerate(frames):
+            if f is not None:
+                buf[i, :len(f)] = np.frombuffer(bytes(f), np.uint8)
+                lens[i] = len(f)
+        fl = np.zeros(n, np.int32) if corrupt is None else np.ascontiguousarray(corrupt, np.int32)
+        res = np.zeros(n, np.int32)
+        _check(lib().spangpu_hdlc_tx_frames(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, fl.ctypes.data, res.ctypes.data))
+        return res
+
+    def _command(self, name, first, n, *args):
+        res = np.zeros(n, np.int32)
+        _check(self._f(name)(self.h, first, n, *args, res.ctypes.data))
+        return res
+
+    def flags(self, count, first=0, n=None):
+        return self._command("flags", first, self.n - first if n is None else n, count)
+
+    def abort(self, first=0, n=None):
+        return self._command("abort", first, self.n - first if n is None else n)
+
+    def end(self, first=0, n=None):
+        return self._command("end", first, self.n - first if n is None else n)
+
+    def queued(self, channel):
+        return _check(lib().spangpu_hdlc_tx_queued(self.h, channel))
+
+    def get_bits_host(self, want):
+        """want: one number, or one per channel.  Returns (bits [n, stride] packed LSB first, lens)."""
+        per = None if np.isscalar(want) else np.ascontiguousarray(want, np.int32)
+        most = int(want) if per is None else int(per.max())
+        stride = max(1, (most + 7)//8)
+        bits = np.zeros((self.n, stride), np.uint8)
+        lens = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_hdlc_tx_get_bits(self.h, MEM_HOST, bits.ctypes.data, stride, per.ctypes.data if per is not None else None,
+                                              most if per is None else 0, lens.ctypes.data))
+        return bits, lens
+
+    def get_bits_device(self, bits_ptr, stride, want_all, lens_ptr=None, want=None):
+        per = None if want is None else np.ascontiguousarray(want, np.int32)
+        _check(lib().spangpu_hdlc_tx_get_bits(self.h, MEM_DEVICE, bits_ptr, stride, per.ctypes.data if per is not None else None, want_all,
+                                              lens_ptr))
+
+    def events(self):
+        """[(channel, kind)] of the last get_bits: kind -7 = the end of the data, k > 0 = k underflows on an empty queue."""
+        cp, kp = C.c_void_p(), C.c_void_p()
+        k = _check(lib().spangpu_hdlc_tx_events(self.h, C.byref(cp), C.byref(kp)))
+        if k == 0:
+            return []
+        ch = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (k,))
+        kd = np.ctypeslib.as_array(C.cast(kp, C.POINTER(C.c_int32)), (k,))
+        return [(int(a), int(b)) for a, b in zip(ch, kd)]
+
+
 class MctTxBank(_SenderBank):
     """N modem connect tone generators of one tone type (modem_connect_tones_tx), state in HBM."""
     _prefix = "mcttx"
@@ -2380,6 +2610,10 @@ class ModemTxBank:
         acc = np.zeros(n, np.int32)
         _check(lib().spangpu_modemtx_put_bits(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, acc.ctypes.data))
         return acc
+
+    def put_bits_device(self, bits_ptr, stride, lens_ptr, first=0, n=None, accepted_ptr=None):
+        """put_bits from rows and lengths in device memory (an HdlcTxBank's): no copy, no wait."""
+        _check(lib().spangpu_bits_to_modemtx(self.h, first, self.n - first if n is None else n, bits_ptr, stride, lens_ptr, accepted_ptr))
 
     def queued(self, channel):
         return _check(lib().spangpu_modemtx_queued(self.h, channel))

@@ -1458,6 +1458,73 @@ def bench_adsi(args, dev, stream):
         "cpu_baseline": None}
 
 
+def bench_hdlc(args, dev, stream):
+    """An HDLC sender bank producing 192 bits per line and tick (what V.29 9600 takes) into HBM, and an HDLC receiver bank
+    framing 192 events per line and tick from HBM: hdlc_tx_get_bit() and hdlc_rx_put_bit() of every line, timed separately.
+    The sender's bits, unpacked to one event each on the device between the two timed regions, are the receiver's input; a
+    255-octet frame is queued to every line every 12 ticks, outside the timed regions; the record lists are read back every
+    tick, and what arrives is checked."""
+    from spandsp_amd import engine
+    n_ch = args.channels or 16384
+    per = 192
+    sender = engine.HdlcTxBank(n_ch, crc32=False, inter_frame_flags=2, queue_depth=4)
+    receiver = engine.HdlcRxBank(n_ch, crc32=False, framing_ok_threshold=2)
+    sender.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    receiver.set_stream(ctypes.c_void_p(stream.cuda_stream))
+    bits = torch.zeros(n_ch, per//8, dtype=torch.uint8, device=dev)
+    d_lens = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+    shifts = torch.arange(8, dtype=torch.uint8, device=dev)
+    frame = bytes((i*7 + 3) & 0xFF for i in range(255))
+    assert int(sender.flags(4).min()) == 0
+    per_tx, per_rx = [], []
+    total = args.warmup + args.steps
+    delivered, to_host = 0, 0
+    t0 = None
+    for i in range(total):
+        if i % 12 == 0:         # 255 + 2 octets, stuffed, and two flags: under 12 ticks of 24 octets
+            assert int(sender.frames([frame]*n_ch).min()) == 0, "a queue was full"
+        if i == args.warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(stream)
+        sender.get_bits_device(ctypes.c_void_p(bits.data_ptr()), per//8, per, ctypes.c_void_p(d_lens.data_ptr()))
+        e[1].record(stream)
+        events = ((bits.unsqueeze(-1) >> shifts) & 1).reshape(n_ch, per).to(torch.int8).contiguous()
+        e[2].record(stream)
+        receiver.put_events_device(ctypes.c_void_p(events.data_ptr()), 1, per, None)
+        e[3].record(stream)
+        if i >= args.warmup:
+            per_tx.append((e[0], e[1]))
+            per_rx.append((e[2], e[3]))
+        recs = receiver.records()
+        for c in range(n_ch):
+            for r in recs[c]:
+                if not isinstance(r, int):
+                    assert r == (255, True, frame), (c, r[:2])
+                    delivered += 1
+                    to_host += 255
+                to_host += 4
+        to_host += 8*n_ch       # the two counts per line
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert delivered >= n_ch*((total - 13)//12), delivered
+    tx_ms = [a.elapsed_time(b) for a, b in per_tx]
+    rx_ms = [a.elapsed_time(b) for a, b in per_rx]
+    value = args.steps*n_ch*per/dt/1e6
+    return {
+        "metric": "Mbit/s of an HDLC bank pair (hdlc_tx_get_bit into HBM, hdlc_rx_put_bit from HBM; records read back every tick)", "value": value,
+        "unit": "Mbit/s", "realtime_channels": value*1e6/9600.0, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt*1e3/args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32",
+        "data": "synthetic",
+        "config": {"workload": "HDLC framing banks, CRC-16, 255-octet frames back to back, %d channels x %d events a tick" % (n_ch, per),
+                   "channels_per_gpu": n_ch, "frames_delivered": delivered, "bytes_to_host_per_tick": to_host/total,
+                   "event_bytes_per_tick": n_ch*per},
+        "kernels": {"hdlc_tx_kernel": {"avg_launch_us": sum(tx_ms)/len(tx_ms)*1e3, "min_launch_us": min(tx_ms)*1e3},
+                    "hdlc_rx_kernel": {"avg_launch_us": sum(rx_ms)/len(rx_ms)*1e3, "min_launch_us": min(rx_ms)*1e3}},
+        "cpu_baseline": None}
+
+
 def bench_sender(args, dev, stream, which):
     """SURVEY 8(f)-1, the last two sources: the FSK transmitter bank (V.21 channel 2, bits from the per-channel LFSR) or the
     connect tone transmitter bank (ANSam/PR, the busiest type: 15 Hz AM and phase hops) writing 160-sample frames into HBM."""
@@ -1726,7 +1793,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
@@ -1800,6 +1867,9 @@ def main():
         return
     if args.workload == "adsi":
         emit(bench_adsi(args, dev, stream), "adsi", args.channels or None)
+        return
+    if args.workload == "hdlc":
+        emit(bench_hdlc(args, dev, stream), "hdlc", args.channels or None)
         return
     if args.workload in ("fsk_tx", "mct_tx"):
         emit(bench_sender(args, dev, stream, args.workload), args.workload, args.channels or None)
