@@ -436,6 +436,11 @@ SPANGPU_API int spangpu_modem_rx(spangpu_modem_t *modem, const int16_t *amp, int
    0 = it sits the call out, untouched.  lens[] is host memory. */
 SPANGPU_API int spangpu_modem_rx_var(spangpu_modem_t *modem, const int16_t *amp, int mem, const int32_t *lens, int max_samples,
                                      long long stride);
+/* The same with the lengths in device memory ([n_channels], int32): channel c takes min(max(lens_dev[c], 0), samples) samples
+   of row c, and a channel that takes none sits the call out with a zero event count.  Nothing is read back; lens_dev stays
+   as it is until the work queued on the bank's stream has run.  Both lane mappings honour it. */
+SPANGPU_API int spangpu_modem_rx_lens_dev(spangpu_modem_t *modem, const int16_t *amp, int mem, int samples, long long stride,
+                                          const int32_t *lens_dev);
 SPANGPU_API int spangpu_modem_events(spangpu_modem_t *modem, const int8_t **events, const int32_t **counts);
 /* The last call's events device to device (for a gather across GPUs): dst = int32 counts[n_ch], int8 events[n_ch][per_channel].
    Asynchronous on the bank's stream. */
@@ -587,6 +592,8 @@ SPANGPU_API int spangpu_fsk_sync(spangpu_fsk_t *fsk);
 SPANGPU_API int spangpu_fsk_rx(spangpu_fsk_t *fsk, const int16_t *amp, int mem, int samples, long long stride);
 /* a tick in which channels are missing or bring short frames: lens[c] samples of row c; 0 = untouched (host array) */
 SPANGPU_API int spangpu_fsk_rx_var(spangpu_fsk_t *fsk, const int16_t *amp, int mem, const int32_t *lens, int max_samples, long long stride);
+/* the same with the lengths in device memory: min(max(lens_dev[c], 0), samples) samples of row c (spangpu_modem_rx_lens_dev()) */
+SPANGPU_API int spangpu_fsk_rx_lens_dev(spangpu_fsk_t *fsk, const int16_t *amp, int mem, int samples, long long stride, const int32_t *lens_dev);
 /* events[channel*cap + i], i < counts[channel]; returns cap.  Valid until the next call on this bank. */
 SPANGPU_API int spangpu_fsk_events(spangpu_fsk_t *fsk, const int16_t **events, const int32_t **counts);
 /* The last call's events device to device (for an HDLC receiver bank, spangpu_hdlc_rx_put_events() with elem_bytes 2):
@@ -987,6 +994,100 @@ SPANGPU_API int spangpu_hdlc_tx_get_state(spangpu_hdlc_tx_t *bank, int channel, 
 SPANGPU_API int spangpu_hdlc_tx_set_state(spangpu_hdlc_tx_t *bank, int channel, const int32_t *words);
 SPANGPU_API int spangpu_hdlc_tx_get_buffer(spangpu_hdlc_tx_t *bank, int channel, uint8_t *buffer);
 SPANGPU_API int spangpu_hdlc_tx_set_buffer(spangpu_hdlc_tx_t *bank, int channel, const uint8_t *buffer);
+
+/* ---- FAX receive front-end banks (csrc/faxfe_api.hip, csrc/faxfe_dev.hpp) ---------------------
+ * The receive half of N fax_modems_state_t objects under fax_rx(): the fast modem and the V.21 receiver on the same samples,
+ * both bit streams into one shared HDLC framer (or, without hdlc_mode, the fast modem's into the non-ECM put_bit), and the
+ * handler that takes the next tick chosen per channel on the device -- both receivers until the fast modem reports
+ * SIG_STATUS_TRAINING_SUCCEEDED (then it alone) or a good frame arrives (then the V.21 receiver alone).  Only frames, the
+ * non-ECM bits and one handler word per line cross to the host.  All of the bank's own arithmetic is integer: every result
+ * equals the reference's wherever the inner receivers' do.
+ *
+ *   spangpu_faxfe_create()             fax_modems_init(): receive side                                src/fax_modems.c:618-677
+ *                                      one modem receiver bank per kind in kinds_mask, a V.21 channel 2 bank (synchronous,
+ *                                      cutoff -39.09 dBm0), an HDLC receiver bank (CRC-16, bad frames reported, framing OK
+ *                                      after 5 flags) that no later call re-initialises; span_dummy_rx installed :661-670
+ *   spangpu_faxfe_start_slow_modem()   fax_modems_start_slow_modem(s, FAX_MODEM_V21_RX)               src/fax_modems.c:336-372
+ *                                      fsk_rx_init(), the cutoff, fsk_rx installed, rx_frame_received cleared
+ *   spangpu_faxfe_start_fast_modem()   fax_modems_start_fast_modem(s, FAX_MODEM_xxx_RX, ..)           src/fax_modems.c:375-513
+ *                                      another kind than the channel's last: xxx_rx_init() (V.29: cutoff -45.5 dBm0),
+ *                                      short_train cleared :402-424; the same kind: xxx_rx_restart(), V.17 with
+ *                                      short_train :457-477; fax_modems_xxx_v21_rx installed, rx_frame_received cleared
+ *   spangpu_faxfe_rx()                 fax_rx(): dc_restore() (if the bank was made with it), then    src/fax.c:176-184
+ *                                      s->rx_handler(s->rx_user_data, amp, len)
+ *                                        fax_modems_xxx_v21_rx(): xxx_rx(), fsk_rx(), then V.21 alone  src/fax_modems.c:213-229,
+ *                                        once rx_frame_received                                        :260-276, :307-323
+ *                                        xxx_rx_status_handler(): the fast modem alone on              src/fax_modems.c:195-211,
+ *                                        SIG_STATUS_TRAINING_SUCCEEDED; every status on to put_bit     :242-258, :289-305
+ *                                        fax_modems_hdlc_accept(): a good frame sets rx_frame_received src/fax_modems.c:158-172
+ *   spangpu_faxfe_frames()             the hdlc_accept calls of the last tick, in the record form of spangpu_hdlc_rx_records()
+ *                                      (a status arrives as the reference delivers it: a record < 0)
+ *   spangpu_faxfe_put_bits()           the non-ECM put_bit calls of the last tick: counts[c] int8 entries at events[c*cap ..]
+ *   spangpu_faxfe_handlers()           per channel SPANGPU_FAXFE_HANDLER_* and rx_frame_received (either array may be NULL)
+ *
+ * `which` takes the values of the reference's FAX_MODEM_* (src/spandsp/fax_modems.h:31-53).  The tone receivers, the senders
+ * and V.34 are refused with SPANGPU_ERR_UNSUPPORTED, like a kind that is not in kinds_mask; a rate the kind does not have with
+ * SPANGPU_ERR_BAD_ARG.  A refused call changes nothing.  The control calls act between ticks, ordered on the bank's stream.
+ *
+ * A tick is one sequence on the bank's stream: the frames are staged once (samples <= max_samples), dc_restore() runs over
+ * the rows of the channels that have a handler, each fast bank that has a channel assigned and the V.21 bank run off
+ * per-channel lengths in device memory (spangpu_modem_rx_lens_dev(), spangpu_fsk_rx_lens_dev()), and one kernel walks each
+ * channel's two event rows -- the fast modem's first -- and writes the lengths of the next tick.  A receiver whose handler
+ * left sits out, its state as it was.  A new channel has no handler, and nothing runs for it.  The V.27ter and V.17 banks
+ * run one bit rate each, so a kind's other rates live in further banks the bank makes when a channel first asks for one
+ * (spangpu_faxfe_fast_bank() with that rate).  A V.27ter or V.17 channel restarts at the rate it was started with: the same kind
+ * at another rate is refused (SPANGPU_ERR_UNSUPPORTED) -- the restart would have to move the channel to another bank, and no
+ * fixture holds the reference's restart at a changed rate yet.  A V.29 channel may change its rate on a restart.
+ *
+ * The record and octet capacities are spangpu_hdlc_rx_capacity() of the two rows' capacities added; a list that did not fit,
+ * or a receiver's row that did not, is an error of spangpu_faxfe_frames() / _put_bits() (SPANGPU_ERR_STATE), never cut short.
+ *
+ * Not here: the transmit half of fax_modems (silence_gen, the next-handler chain), the CED / CNG tone receive handlers,
+ * the xxx_rx_fillin handlers, fax_modems_set_rx_active() and deferred handler updates, V.34, and the fax_modems_* calls by
+ * name (t30.c and fax.c reach into the struct: banks are the form, as for HDLC).
+ */
+typedef struct spangpu_faxfe_s spangpu_faxfe_t;
+
+#define SPANGPU_FAXFE_V27TER                1       /* kinds_mask */
+#define SPANGPU_FAXFE_V29                   2
+#define SPANGPU_FAXFE_V17                   4
+#define SPANGPU_FAXFE_V21_RX                12      /* FAX_MODEM_V21_RX .. FAX_MODEM_V34_RX */
+#define SPANGPU_FAXFE_V17_RX                13
+#define SPANGPU_FAXFE_V27TER_RX             14
+#define SPANGPU_FAXFE_V29_RX                15
+#define SPANGPU_FAXFE_V34_RX                17
+#define SPANGPU_FAXFE_HANDLER_NONE          0       /* span_dummy_rx */
+#define SPANGPU_FAXFE_HANDLER_FAST_AND_V21  1       /* fax_modems_xxx_v21_rx */
+#define SPANGPU_FAXFE_HANDLER_FAST_ONLY     2       /* xxx_rx */
+#define SPANGPU_FAXFE_HANDLER_V21_ONLY      3       /* fsk_rx */
+
+SPANGPU_API int spangpu_faxfe_create(spangpu_faxfe_t **bank, int device, int n_channels, int kinds_mask, int max_samples, int dc_restore);
+SPANGPU_API void spangpu_faxfe_destroy(spangpu_faxfe_t *bank);
+SPANGPU_API int spangpu_faxfe_channels(const spangpu_faxfe_t *bank);
+/* every inner bank follows; the null stream is refused (a modem receiver bank reads it as "a stream of your own") */
+SPANGPU_API int spangpu_faxfe_set_stream(spangpu_faxfe_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_faxfe_sync(spangpu_faxfe_t *bank);
+SPANGPU_API int spangpu_faxfe_start_slow_modem(spangpu_faxfe_t *bank, int channel, int which);
+SPANGPU_API int spangpu_faxfe_start_fast_modem(spangpu_faxfe_t *bank, int channel, int which, int bit_rate, int short_train, int hdlc_mode);
+SPANGPU_API int spangpu_faxfe_rx(spangpu_faxfe_t *bank, const int16_t *amp, int mem, int samples, long long stride);
+/* Valid until the next call on this bank.  frames: returns rec_cap, counts[n_channels + c] is the channel's octets;
+   put_bits: returns the row capacity.  capacities: those of the last tick. */
+SPANGPU_API int spangpu_faxfe_frames(spangpu_faxfe_t *bank, const int32_t **recs, const int32_t **counts, const uint8_t **bytes);
+SPANGPU_API int spangpu_faxfe_put_bits(spangpu_faxfe_t *bank, const int8_t **events, const int32_t **counts);
+SPANGPU_API int spangpu_faxfe_capacities(const spangpu_faxfe_t *bank, int *rec_cap, int *byte_cap, int *put_cap);
+SPANGPU_API int spangpu_faxfe_handlers(spangpu_faxfe_t *bank, int32_t *handler, int32_t *frame_received);
+/* The inner banks, for their get_state / set_state / refstate calls on a channel between ticks; they are the bank's, not the
+   caller's to destroy or to run.  kind: SPANGPU_V27TER / _V29 / _V17; bit_rate 0: the bank made with the front end (V.27ter
+   4800, V.29, V.17 14400).  NULL: no such bank (yet). */
+SPANGPU_API spangpu_modem_t *spangpu_faxfe_fast_bank(spangpu_faxfe_t *bank, int kind, int bit_rate);
+SPANGPU_API spangpu_fsk_t *spangpu_faxfe_v21_bank(spangpu_faxfe_t *bank);
+SPANGPU_API spangpu_hdlc_rx_t *spangpu_faxfe_framer(spangpu_faxfe_t *bank);
+/* One channel's front-end words (layout: faxfe_dev.hpp): handler, fast_modem, bit_rate, short_train, hdlc_mode,
+   rx_frame_received, the dc_restore state, and the inner fast bank the channel's modem lives in.  set_words checks the last
+   against fast_modem and bit_rate, and puts the channel's lengths for the next tick in line with its handler. */
+SPANGPU_API int spangpu_faxfe_state_words(const spangpu_faxfe_t *bank);
+SPANGPU_API int spangpu_faxfe_get_words(spangpu_faxfe_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_faxfe_set_words(spangpu_faxfe_t *bank, int channel, const int32_t *words);
 
 /* ---- signalling tone banks (sig_tone.c) -----------------
  * N in-band signalling tone receivers, or senders, of one tone type: 2280 Hz (AC15 and relatives), 2600 Hz, or

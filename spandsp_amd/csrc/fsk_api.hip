@@ -313,6 +313,26 @@ extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_words_fillin(i
     }
 }
 
+// the event rows of the last spangpu_fsk_rx(), where they lie on the device (faxfe_api.hip); not part of the ABI
+extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_event_rows(const spangpu_fsk_t *f, const int16_t **events, const int32_t **counts, int *cap)
+{
+    *events = f->events;
+    *counts = f->ev_count;
+    *cap = f->last_cap;
+}
+
+// fsk_rx_set_signal_cutoff() of every channel: two rows of the state (faxfe_api.hip); not part of the ABI
+extern "C" __attribute__((visibility("hidden"))) int spangpu_fsk_cutoff_all(spangpu_fsk_t *f, float cutoff_dbm0)
+{
+    int32_t w[kFskScalars];
+    cutoff_words(w, cutoff_dbm0);
+    SPG_TRY(hipSetDevice(f->c.device));
+    SPG_TRY(hipMemsetD32Async((hipDeviceptr_t) (f->c.st + (size_t) FS_ON_POWER*f->c.n_ch), w[FS_ON_POWER], (size_t) f->c.n_ch, f->c.stream));
+    SPG_TRY(hipMemsetD32Async((hipDeviceptr_t) (f->c.st + (size_t) FS_OFF_POWER*f->c.n_ch), w[FS_OFF_POWER], (size_t) f->c.n_ch, f->c.stream));
+    SPG_TRY(hipStreamSynchronize(f->c.stream));
+    return SPANGPU_OK;
+}
+
 extern "C" {
 
 int spangpu_fsk_preset(int which, spangpu_fsk_spec_t *spec)
@@ -464,6 +484,18 @@ int spangpu_fsk_rx_var(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, const
     SPG_TRY(hipMemcpyAsync(f->d_lens, f->h_lens, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, f->c.stream));
     f->next_lens = f->d_lens;
     const int rc = spangpu_fsk_rx(f, amp, mem_kind, longest, stride);
+    f->next_lens = NULL;
+    return rc;
+}
+
+// spangpu_fsk_rx_var() with the lengths already in device memory, the twin of spangpu_modem_rx_lens_dev(): channel c takes
+// min(max(lens_dev[c], 0), samples) samples of its row, a channel that takes none sits the call out with a zero event count.
+int spangpu_fsk_rx_lens_dev(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, int samples, long long stride, const int32_t *lens_dev)
+{
+    if (f == NULL  ||  lens_dev == NULL)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    f->next_lens = lens_dev;
+    const int rc = spangpu_fsk_rx(f, amp, mem_kind, samples, stride);
     f->next_lens = NULL;
     return rc;
 }

@@ -82,6 +82,14 @@ static int buffer_rw(BankCore *c, uint32_t *buf, int channel, uint8_t *bytes, bo
     return rc;
 }
 
+// a receiver bank's words and frame buffers, where they lie on the device, for a bank family that frames on the device inside
+// a kernel of its own (faxfe_api.hip); not part of the ABI
+extern "C" __attribute__((visibility("hidden"))) void spangpu_framer_rows(spangpu_hdlc_rx_t *b, int32_t **st, uint32_t **buf)
+{
+    *st = b->c.st;
+    *buf = b->buf;
+}
+
 extern "C" {
 
 /*

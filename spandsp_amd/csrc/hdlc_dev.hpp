@@ -659,8 +659,10 @@ HDLC_HD void hdlc_tx_words_init(int32_t *w, int crc32, int inter_frame_flags)
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------
+// (a unit that wants the step functions alone, for a kernel of its own, defines SPG_HDLC_STEP_FUNCTIONS_ONLY: the sender's
+// kernels are not templates and belong to one unit)
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__)  &&  !defined(SPG_HDLC_STEP_FUNCTIONS_ONLY)
 
 struct HdlcRxLaunch
 {

@@ -566,6 +566,20 @@ int spangpu_modem_rx_var(spangpu_modem_t *m, const int16_t *amp, int mem, const 
     return rc;
 }
 
+// spangpu_modem_rx_var() with the lengths already in device memory (a bank that decides on the device who takes part, such as
+// the FAX front end): channel c takes min(max(lens_dev[c], 0), samples) samples of its row, and a channel that takes none
+// sits the call out with a zero event count.  Nothing is read back and, for device frames, nothing is waited for; lens_dev
+// must stay as it is until the work queued on the bank's stream has run.
+int spangpu_modem_rx_lens_dev(spangpu_modem_t *m, const int16_t *amp, int mem, int samples, long long stride, const int32_t *lens_dev)
+{
+    if (m == nullptr  ||  lens_dev == nullptr)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    m->next_lens = lens_dev;
+    const int rc = spangpu_modem_rx(m, amp, mem, samples, stride);
+    m->next_lens = nullptr;
+    return rc;
+}
+
 // The tap behind xxx_rx_set_qam_report_handler(): from the next spangpu_modem_rx() on, every channel's
 // qam_report(user, constel, target, symbol) calls are recorded beside its put_bit stream.
 int spangpu_modem_qam_tap(spangpu_modem_t *m, int enable)
@@ -1030,6 +1044,40 @@ static int v17_restart_words(uint32_t *w, int bit_rate, int short_train)
     iw[XI_TOTAL_CORR] = 0;
     iw[XI_BAUD_HALF] = 0;
     return 0;
+}
+
+// For the bank families that carry modem receivers inside them (faxfe_api.hip); not part of the ABI.
+// One channel's words as xxx_rx_init(s, bit_rate, ..) leaves them, with a carrier detector cutoff: -1 for a rate the kind lacks.
+extern "C" __attribute__((visibility("hidden"))) int spangpu_modem_words_fresh(int kind, uint32_t *w, int bit_rate, float cutoff_dbm0)
+{
+    switch (kind)
+    {
+    case SPANGPU_V17: return v17_initial_words(w, bit_rate, cutoff_dbm0);
+    case SPANGPU_V29: return v29_initial_words(w, bit_rate, cutoff_dbm0);
+    case SPANGPU_V27TER: return v27_initial_words(w, bit_rate, cutoff_dbm0);
+    }
+    return -1;
+}
+
+// xxx_rx_restart(s, bit_rate, train_flag) on one channel's words
+extern "C" __attribute__((visibility("hidden"))) int spangpu_modem_words_restart(int kind, uint32_t *w, int bit_rate, int train_flag)
+{
+    switch (kind)
+    {
+    case SPANGPU_V17: return v17_restart_words(w, bit_rate, train_flag);
+    case SPANGPU_V29: return v29_restart_words(w, bit_rate, train_flag);
+    case SPANGPU_V27TER: return v27_restart_words(w, bit_rate);
+    }
+    return -1;
+}
+
+// the event rows of the last spangpu_modem_rx(), where they lie on the device
+extern "C" __attribute__((visibility("hidden"))) void spangpu_modem_event_rows(const spangpu_modem_t *m, const int8_t **events, const int32_t **counts,
+                                                                               int *cap)
+{
+    *events = m->events;
+    *counts = m->ev_count;
+    *cap = m->last_cap;
 }
 
 // one channel's words, after the work queued on the bank's stream

@@ -241,6 +241,26 @@ def lib():
             "spangpu_hdlc_tx_set_state": (ci, [vp, ci, vp]),
             "spangpu_hdlc_tx_get_buffer": (ci, [vp, ci, vp]),
             "spangpu_hdlc_tx_set_buffer": (ci, [vp, ci, vp]),
+            "spangpu_modem_rx_lens_dev": (ci, [vp, vp, ci, ci, ll, vp]),
+            "spangpu_fsk_rx_lens_dev": (ci, [vp, vp, ci, ci, ll, vp]),
+            "spangpu_faxfe_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci]),
+            "spangpu_faxfe_destroy": (None, [vp]),
+            "spangpu_faxfe_channels": (ci, [vp]),
+            "spangpu_faxfe_set_stream": (ci, [vp, vp]),
+            "spangpu_faxfe_sync": (ci, [vp]),
+            "spangpu_faxfe_start_slow_modem": (ci, [vp, ci, ci]),
+            "spangpu_faxfe_start_fast_modem": (ci, [vp, ci, ci, ci, ci, ci]),
+            "spangpu_faxfe_rx": (ci, [vp, vp, ci, ci, ll]),
+            "spangpu_faxfe_frames": (ci, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_faxfe_put_bits": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
+            "spangpu_faxfe_capacities": (ci, [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+            "spangpu_faxfe_handlers": (ci, [vp, vp, vp]),
+            "spangpu_faxfe_fast_bank": (vp, [vp, ci, ci]),
+            "spangpu_faxfe_v21_bank": (vp, [vp]),
+            "spangpu_faxfe_framer": (vp, [vp]),
+            "spangpu_faxfe_state_words": (ci, [vp]),
+            "spangpu_faxfe_get_words": (ci, [vp, ci, vp]),
+            "spangpu_faxfe_set_words": (ci, [vp, ci, vp]),
             "spangpu_awgn_create": (ci, [C.POINTER(vp), ci, ci, vp, vp]),
             "spangpu_awgn_destroy": (None, [vp]),
             "spangpu_awgn_channels": (ci, [vp]),
@@ -2389,6 +2409,143 @@ class HdlcTxBank(_HdlcBank):
         ch = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (k,))
         kd = np.ctypeslib.as_array(C.cast(kp, C.POINTER(C.c_int32)), (k,))
         return [(int(a), int(b)) for a, b in zip(ch, kd)]
+
+
+# ---- FAX receive front-end banks (include/spangpu.h "FAX receive front-end banks") ---------------------
+FAXFE_V27TER, FAXFE_V29, FAXFE_V17 = 1, 2, 4                                        # kinds_mask
+FAX_MODEM_V21_RX, FAX_MODEM_V17_RX, FAX_MODEM_V27TER_RX, FAX_MODEM_V29_RX = 12, 13, 14, 15
+FAXFE_NONE, FAXFE_FAST_AND_V21, FAXFE_FAST_ONLY, FAXFE_V21_ONLY = 0, 1, 2, 3        # handlers
+# the front-end words of a channel (faxfe_dev.hpp)
+(FAXFE_W_HANDLER, FAXFE_W_FAST_MODEM, FAXFE_W_BIT_RATE, FAXFE_W_SHORT_TRAIN, FAXFE_W_HDLC_MODE, FAXFE_W_RX_FRAME_RECEIVED,
+ FAXFE_W_DC_STATE, FAXFE_W_SLOT) = range(8)
+
+
+def _borrowed(cls, handle, n, **attrs):
+    """An inner bank of another bank under the class that speaks for its kind; the handle is not this object's to destroy."""
+    o = object.__new__(cls)
+    o.h = C.c_void_p(handle)
+    o.n = n
+    o.close = lambda: None
+    for k, v in attrs.items():
+        setattr(o, k, v)
+    return o
+
+
+class FaxFrontEnd:
+    """The receive half of N fax_modems objects under fax_rx(): the fast modem and the V.21 receiver on the same frames, one
+    shared HDLC framer, the handler of the next tick chosen per channel on the device."""
+
+    def __init__(self, n_channels, kinds_mask=FAXFE_V27TER | FAXFE_V29 | FAXFE_V17, max_samples=160, dc_restore=False, device=0):
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_faxfe_create(C.byref(self.h), device, n_channels, kinds_mask, max_samples, int(dc_restore)))
+        self.words = lib().spangpu_faxfe_state_words(self.h)
+
+    def close(self):
+        if self.h:
+            lib().spangpu_faxfe_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        _check(lib().spangpu_faxfe_set_stream(self.h, hip_stream))
+
+    def sync(self):
+        _check(lib().spangpu_faxfe_sync(self.h))
+
+    def start_slow_modem(self, channel, which=FAX_MODEM_V21_RX):
+        _check(lib().spangpu_faxfe_start_slow_modem(self.h, channel, which))
+
+    def start_fast_modem(self, channel, which, bit_rate, short_train=False, hdlc_mode=False):
+        _check(lib().spangpu_faxfe_start_fast_modem(self.h, channel, which, bit_rate, int(short_train), int(hdlc_mode)))
+
+    def rx_host(self, amp):
+        amp = np.ascontiguousarray(amp, np.int16)
+        assert amp.shape[0] == self.n
+        _check(lib().spangpu_faxfe_rx(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
+
+    def rx_device(self, ptr, samples, stride=0):
+        _check(lib().spangpu_faxfe_rx(self.h, ptr, MEM_DEVICE, samples, stride))
+
+    def capacities(self):
+        r, y, p = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().spangpu_faxfe_capacities(self.h, C.byref(r), C.byref(y), C.byref(p)))
+        return r.value, y.value, p.value
+
+    def frames_raw(self):
+        """(recs [n, rec_cap], record counts [n], octets [n, byte_cap], octet counts [n]) of the last tick, as the ABI has them;
+        only the columns some channel filled are current."""
+        rp, cp, bp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rec_cap = _check(lib().spangpu_faxfe_frames(self.h, C.byref(rp), C.byref(cp), C.byref(bp)))
+        byte_cap = self.capacities()[1]
+        counts = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (2*self.n,))
+        recs = np.ctypeslib.as_array(C.cast(rp, C.POINTER(C.c_int32)), (self.n*rec_cap,)).reshape(self.n, rec_cap)
+        by = np.ctypeslib.as_array(C.cast(bp, C.POINTER(C.c_uint8)), (self.n*byte_cap,)).reshape(self.n, byte_cap)
+        return recs, counts[:self.n], by, counts[self.n:]
+
+    def frames(self):
+        """Per channel: [(len, ok, bytes) for an hdlc_accept call with a frame | code < 0 for one with a status], in call order."""
+        recs, nrecs, by, nbytes = self.frames_raw()
+        out = [[] for _ in range(self.n)]
+        for c in np.nonzero(nrecs)[0]:
+            at = 0
+            for r in recs[c, :nrecs[c]]:
+                r = int(r)
+                if r < 0:
+                    out[c].append(r)
+                else:
+                    k = r & 0xFFFF
+                    out[c].append((k, bool(r & HDLC_FRAME_OK), by[c, at:at + k].tobytes()))
+                    at += k
+            assert at == nbytes[c]
+        return out
+
+    def put_bits(self):
+        """Per channel: the int8 values of the last tick's non-ECM put_bit calls, in order."""
+        ep, cp = C.c_void_p(), C.c_void_p()
+        cap = _check(lib().spangpu_faxfe_put_bits(self.h, C.byref(ep), C.byref(cp)))
+        counts = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (self.n,))
+        ev = np.ctypeslib.as_array(C.cast(ep, C.POINTER(C.c_int8)), (self.n*cap,)).reshape(self.n, cap)
+        return [ev[c, :counts[c]].copy() for c in range(self.n)]
+
+    def handlers(self):
+        """(handler [n], rx_frame_received [n])"""
+        h = np.zeros(self.n, np.int32)
+        f = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_faxfe_handlers(self.h, h.ctypes.data, f.ctypes.data))
+        return h, f
+
+    def fast_bank(self, kind, bit_rate=0):
+        """The inner modem receiver bank of a kind (and, for the rates a kind's first bank does not run, of that rate), or None."""
+        p = lib().spangpu_faxfe_fast_bank(self.h, kind, bit_rate)
+        if not p:
+            return None
+        nf, ni = C.c_int(), C.c_int()
+        nw = _check(lib().spangpu_modem_state_words(kind, C.byref(nf), C.byref(ni)))
+        return _borrowed(ModemBank, p, self.n, kind=kind, n_words=nw, n_floats=nf.value, n_ints=ni.value)
+
+    def v21_bank(self):
+        p = lib().spangpu_faxfe_v21_bank(self.h)
+        return _borrowed(FskBank, p, self.n, words=lib().spangpu_fsk_state_words(p))
+
+    def framer(self):
+        p = lib().spangpu_faxfe_framer(self.h)
+        return _borrowed(HdlcRxBank, p, self.n, words=lib().spangpu_hdlc_rx_state_words(p))
+
+    def get_words(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_faxfe_get_words(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_words(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_faxfe_set_words(self.h, channel, w.ctypes.data))
 
 
 class MctTxBank(_SenderBank):

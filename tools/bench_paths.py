@@ -1267,6 +1267,123 @@ def bench_fax_rx(args, dev, stream):
         "roofline": None, "cpu_baseline": None}
 
 
+def bench_fax_fe(args, dev, stream):
+    """The receive front end of N FAX terminals as one bank (spangpu_faxfe_*): the frames staged once, the V.29 and the V.21
+    receiver off per-channel lengths on the device, both event rows into the shared framer or the non-ECM rows, the handler of
+    the next tick chosen on the device -- all on one stream, on the signals of the fax_rx workload, inputs resident in HBM.
+    Timed, per tick between two events on the stream: the tick (a) while every line runs both receivers, (b) after every line
+    has switched to its fast modem alone.  The lines are in step and train some 16 ticks in, so (a) is gathered over several
+    fresh banks.  A first, untimed pass finds the tick on which the lines switch; on the way the results of the first 64 lines
+    are held against what the host derives from the inner banks' event rows read back: the non-ECM row is the fast modem's
+    row, the status records are the V.21 row's status entries in order, and the handler follows SIG_STATUS_TRAINING_SUCCEEDED
+    and rx_frame_received.  (The route kernel's own time is not seen from here: rocprofv3 --kernel-trace --stats over this
+    workload gives it, profiles/faxfe_bank.md.)"""
+    from spandsp_amd import engine
+    n_ch = args.channels or 16384
+    check = min(64, n_ch)
+    nf = args.steps + args.warmup + 40          # the lines train some 16 ticks in
+    frames, _, _ = synth_v29_on_device(n_ch, nf, dev, stream, seed=0x2929, modem="v29", line="in_step")
+    frame_bytes = n_ch*FRAME*2
+    passed_on = (-1, -2, -3, -4, -5, -7)        # the statuses rx_special_condition() hands to the handler (hdlc.c)
+
+    def make(n):
+        fe = engine.FaxFrontEnd(n, kinds_mask=engine.FAXFE_V29, max_samples=FRAME)
+        fe.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        for c in range(n):
+            fe.start_fast_modem(c, engine.FAX_MODEM_V29_RX, 9600, False, False)
+        return fe
+
+    def tick(fe, i):
+        fe.rx_device(ctypes.c_void_p(frames.data_ptr() + i*frame_bytes), FRAME, FRAME)
+
+    # pass 1: where the lines switch, and the first 64 lines against the host's reading of the receivers' rows
+    big = make(n_ch)
+    fast_bank = big.fast_bank(engine.V29)
+    v21_bank = big.v21_bank()
+    first_switch = last_switch = None
+    put_bits = 0
+    statuses = 0
+    before = np.full(n_ch, engine.FAXFE_FAST_AND_V21, np.int32)
+    for i in range(nf):
+        tick(big, i)
+        h, frx = big.handlers()
+        recs, nrecs, _, _ = big.frames_raw()
+        put = big.put_bits()
+        ef = fast_bank.events()
+        ev = v21_bank.events()
+        for c in range(check):
+            runs_fast = before[c] in (engine.FAXFE_FAST_AND_V21, engine.FAXFE_FAST_ONLY)
+            runs_v21 = before[c] in (engine.FAXFE_FAST_AND_V21, engine.FAXFE_V21_ONLY)
+            assert np.array_equal(put[c], ef[c] if runs_fast else ef[c][:0]), (i, c, "non-ECM row")
+            assert runs_fast or len(ef[c]) == 0, (i, c, "a fast modem that sat out spoke")
+            assert runs_v21 or len(ev[c]) == 0, (i, c, "a V.21 receiver that sat out spoke")
+            want = [int(e) for e in ev[c] if int(e) in passed_on]
+            got = [int(r) for r in recs[c, :nrecs[c]] if int(r) in passed_on]
+            assert got == want, (i, c, "status records", got, want)
+            expect = before[c]
+            if before[c] == engine.FAXFE_FAST_AND_V21:
+                if -4 in ef[c]:
+                    expect = engine.FAXFE_FAST_ONLY
+                if frx[c]:
+                    expect = engine.FAXFE_V21_ONLY
+            assert h[c] == expect, (i, c, "handler", h[c], expect)
+            # (rx_frame_received only with a good frame among the tick's records, now or earlier)
+            put_bits += len(put[c])
+            statuses += len(want)
+        if first_switch is None and (h != engine.FAXFE_FAST_AND_V21).any():
+            first_switch = i
+        if last_switch is None and (h == engine.FAXFE_FAST_ONLY).all():
+            last_switch = i
+        before = h.copy()
+    assert first_switch is not None and last_switch is not None, "the lines did not train"
+    assert put_bits > 0
+    big.close()
+
+    def timed(fe, lo, hi):
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(lo, hi)]
+        for k, i in enumerate(range(lo, hi)):
+            evs[k][0].record(stream)
+            tick(fe, i)
+            evs[k][1].record(stream)
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in evs]
+    # pass 2: fresh banks, the ticks back to back; (a) from the tick the carrier is up on (tick 2) to the last before a switch
+    a_lo = min(max(2, args.warmup), max(0, first_switch - 4))
+    per_a = []
+    rounds = 0
+    fe = None
+    while len(per_a) < args.steps and rounds < 6:
+        if fe is not None:
+            fe.close()
+        fe = make(n_ch)
+        for i in range(a_lo):
+            tick(fe, i)
+        per_a += timed(fe, a_lo, first_switch)
+        rounds += 1
+    for i in range(first_switch, last_switch + 1 + args.warmup):
+        tick(fe, i)
+    b_lo = last_switch + 1 + args.warmup
+    per_b = timed(fe, b_lo, min(nf, b_lo + args.steps))
+    h, _ = fe.handlers()
+    assert (h == engine.FAXFE_FAST_ONLY).all()
+    fe.close()
+    t_a = sum(per_a)/len(per_a)*1e-3
+    t_b = sum(per_b)/len(per_b)*1e-3
+    value = n_ch*FRAME/t_a/1e6
+    return {
+        "metric": "Msamples/s of a batched FAX receive front-end bank, V.29 + V.21 + framer + handler switching on the device (8 kHz channels at real-time = value*1e6/8000)",
+        "value": value, "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0, "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": t_a*1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32+int32", "data": "synthetic",
+        "config": {"workload": "spangpu_faxfe_rx: v29_rx 9600 bps + fsk_rx V.21 ch 2 + hdlc_rx + handler switching, %d channels x %d-sample frames, one stream" % (n_ch, FRAME),
+                   "channels_per_gpu": n_ch, "ms_per_tick_both_receivers": t_a*1e3, "min_ms_both_receivers": min(per_a),
+                   "ticks_timed_both_receivers": len(per_a), "banks_they_were_gathered_over": rounds,
+                   "ms_per_tick_after_the_switch": t_b*1e3, "min_ms_after_the_switch": min(per_b), "ticks_timed_after_the_switch": len(per_b),
+                   "first_tick_a_line_switched": first_switch, "tick_all_lines_had_switched": last_switch,
+                   "lines_checked_on_the_host": check, "non_ecm_bits_of_those_lines": put_bits, "status_records_of_those_lines": statuses},
+        "roofline": None, "cpu_baseline": None}
+
+
 def bench_dtmf_tx(args, dev, stream):
     """a DTMF sender bank (dtmf_tx x N) writing 160-sample frames into HBM, digits queued up front."""
     from spandsp_amd import engine
@@ -1793,7 +1910,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
@@ -1870,6 +1987,9 @@ def main():
         return
     if args.workload == "hdlc":
         emit(bench_hdlc(args, dev, stream), "hdlc", args.channels or None)
+        return
+    if args.workload == "fax_fe":
+        emit(bench_fax_fe(args, dev, stream), "fax_fe", args.channels or None)
         return
     if args.workload in ("fsk_tx", "mct_tx"):
         emit(bench_sender(args, dev, stream, args.workload), args.workload, args.channels or None)
