@@ -433,7 +433,8 @@ SPANGPU_API int spangpu_modem_set_stream(spangpu_modem_t *modem, void *hip_strea
 SPANGPU_API int spangpu_modem_sync(spangpu_modem_t *modem);
 SPANGPU_API int spangpu_modem_rx(spangpu_modem_t *modem, const int16_t *amp, int mem, int samples, long long stride);
 /* A tick in which not every receiver has a frame (or frames differ in length): channel c takes lens[c] samples of row c;
-   0 = it sits the call out, untouched.  lens[] is host memory. */
+   0 = it sits the call out, untouched.  lens[] is host memory.  A tick in which every length is 0 makes no launch: the
+   read-back that follows still shows the call before it. */
 SPANGPU_API int spangpu_modem_rx_var(spangpu_modem_t *modem, const int16_t *amp, int mem, const int32_t *lens, int max_samples,
                                      long long stride);
 /* The same with the lengths in device memory ([n_channels], int32): channel c takes min(max(lens_dev[c], 0), samples) samples
@@ -590,7 +591,8 @@ SPANGPU_API int spangpu_fsk_channels(const spangpu_fsk_t *fsk);
 SPANGPU_API int spangpu_fsk_set_stream(spangpu_fsk_t *fsk, void *hip_stream);
 SPANGPU_API int spangpu_fsk_sync(spangpu_fsk_t *fsk);
 SPANGPU_API int spangpu_fsk_rx(spangpu_fsk_t *fsk, const int16_t *amp, int mem, int samples, long long stride);
-/* a tick in which channels are missing or bring short frames: lens[c] samples of row c; 0 = untouched (host array) */
+/* a tick in which channels are missing or bring short frames: lens[c] samples of row c; 0 = untouched (host array).  A tick
+   in which every length is 0 makes no launch: the read-back that follows still shows the call before it. */
 SPANGPU_API int spangpu_fsk_rx_var(spangpu_fsk_t *fsk, const int16_t *amp, int mem, const int32_t *lens, int max_samples, long long stride);
 /* the same with the lengths in device memory: min(max(lens_dev[c], 0), samples) samples of row c (spangpu_modem_rx_lens_dev()) */
 SPANGPU_API int spangpu_fsk_rx_lens_dev(spangpu_fsk_t *fsk, const int16_t *amp, int mem, int samples, long long stride, const int32_t *lens_dev);
@@ -641,6 +643,8 @@ SPANGPU_API int spangpu_mct_channels(const spangpu_mct_t *mct);
 SPANGPU_API int spangpu_mct_set_stream(spangpu_mct_t *mct, void *hip_stream);
 SPANGPU_API int spangpu_mct_sync(spangpu_mct_t *mct);
 SPANGPU_API int spangpu_mct_rx(spangpu_mct_t *mct, const int16_t *amp, int mem, int samples, long long stride);
+/* lens[c] samples of row c; 0 = untouched (host array).  A tick in which every length is 0 makes no launch: the read-back
+   that follows still shows the call before it. */
 SPANGPU_API int spangpu_mct_rx_var(spangpu_mct_t *mct, const int16_t *amp, int mem, const int32_t *lens, int max_samples, long long stride);
 /* events[(channel*cap + i)*2 + {0: tone, 1: level}], i < counts[channel]; returns cap.  Valid until the next call. */
 SPANGPU_API int spangpu_mct_events(spangpu_mct_t *mct, const int32_t **events, const int32_t **counts);
@@ -1134,6 +1138,8 @@ SPANGPU_API int spangpu_sigtone_rx_sync(spangpu_sigtone_rx_t *bank);
 SPANGPU_API int spangpu_sigtone_rx_set_mode(spangpu_sigtone_rx_t *bank, int channel, int mode);
 /* amp is read AND written: [n_channels] rows of `samples`, `stride` apart */
 SPANGPU_API int spangpu_sigtone_rx(spangpu_sigtone_rx_t *bank, int16_t *amp, int mem, int samples, long long stride);
+/* lens[c] samples of row c; 0 = state and row untouched (host array).  A tick in which every length is 0 makes no launch:
+   the read-back that follows still shows the call before it. */
 SPANGPU_API int spangpu_sigtone_rx_var(spangpu_sigtone_rx_t *bank, int16_t *amp, int mem, const int32_t *lens, int max_samples, long long stride);
 /* events[(channel*cap + i)*3 + {0: sample of the call, 1: signalling_state, 2: duration}], i < counts[channel];
    returns cap.  Valid until the next call. */

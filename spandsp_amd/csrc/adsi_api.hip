@@ -41,18 +41,15 @@ struct spangpu_adsi_rx_s
     int span;
     int16_t *quarter;
     uint8_t *msgs;
-    int32_t *d_rxlens;          // [n_ch]: per-channel lengths of an rx_var call
-    int32_t *h_rxlens;          // pinned
-    uint8_t *rec_bytes;         // [n_ch][cap][kAdsiMsg]
-    int32_t *rec_lens;          // [n_ch][cap]
-    int32_t *counts;
+    VarLens rxlens;             // per-channel lengths of an rx_var call
+    uint8_t *rec_bytes;         // [n_ch][last_cap][kAdsiMsg]
+    uint8_t *h_bytes;
+    int32_t *rec_lens;          // [n_ch][last_cap]
+    int32_t *h_lens;
+    CountRows counts;
     int cap;
     int lens_cap;
     int last_cap;
-    uint8_t *h_bytes;
-    int32_t *h_lens;
-    int32_t *h_counts;
-    size_t h_cap;
 };
 
 static int standard_ok(int standard)
@@ -410,15 +407,14 @@ void spangpu_adsi_rx_destroy(spangpu_adsi_rx_t *b)
     stage_free(&b->pcm);
     (void) hipFree(b->quarter);
     (void) hipFree(b->msgs);
-    (void) hipFree(b->d_rxlens);
-    if (b->h_rxlens)
-        (void) hipHostFree(b->h_rxlens);
+    lens_free(&b->rxlens);
     (void) hipFree(b->rec_bytes);
     (void) hipFree(b->rec_lens);
-    (void) hipFree(b->counts);
-    free(b->h_bytes);
-    free(b->h_lens);
-    free(b->h_counts);
+    if (b->h_bytes)
+        (void) hipHostFree(b->h_bytes);
+    if (b->h_lens)
+        (void) hipHostFree(b->h_lens);
+    counts_free(&b->counts);
     free(b);
 }
 
@@ -443,9 +439,8 @@ int spangpu_adsi_rx_create(spangpu_adsi_rx_t **out, int device, int n_channels, 
     const size_t n = (size_t) n_channels;
     int32_t *one = (int32_t *) calloc(n_words, sizeof(int32_t));
     int32_t *host = (int32_t *) calloc((size_t) n_words*n, sizeof(int32_t));
-    b->h_counts = (int32_t *) malloc(n*sizeof(int32_t));
-    if (one == NULL  ||  host == NULL  ||  b->h_counts == NULL  ||  hipMalloc(&b->msgs, n*kAdsiMsg) != hipSuccess
-        ||  hipMalloc(&b->counts, n*sizeof(int32_t)) != hipSuccess)
+    if (one == NULL  ||  host == NULL  ||  hipMalloc(&b->msgs, n*kAdsiMsg) != hipSuccess
+        ||  counts_create(&b->c, &b->counts, 1, 1) != SPANGPU_OK)
     {
         free(one);
         free(host);
@@ -499,12 +494,12 @@ int spangpu_adsi_rx_msg_capacity(const spangpu_adsi_rx_t *b, int samples)
     return (int) ((long long) samples*1200/(8000LL*30)) + 1;
 }
 
-static int rx_launch(spangpu_adsi_rx_s *b, const int16_t *amp, int mem_kind, int samples, long long stride, const int32_t *d_lens)
+static int rx_launch(spangpu_adsi_rx_s *b, const int16_t *amp, int mem_kind, int samples, long long stride)
 {
     SPG_TRY(hipSetDevice(b->c.device));
     const int cap = spangpu_adsi_rx_msg_capacity(b, samples);
-    int rc = grow(&b->rec_bytes, &b->cap, cap, (size_t) b->c.n_ch*kAdsiMsg, b->c.stream);
-    if (rc != SPANGPU_OK  ||  (rc = grow(&b->rec_lens, &b->lens_cap, cap, (size_t) b->c.n_ch, b->c.stream)) != SPANGPU_OK)
+    int rc = grow_pair(&b->rec_bytes, &b->h_bytes, &b->cap, cap, (size_t) b->c.n_ch*kAdsiMsg, b->c.stream);
+    if (rc != SPANGPU_OK  ||  (rc = grow_pair(&b->rec_lens, &b->h_lens, &b->lens_cap, cap, (size_t) b->c.n_ch, b->c.stream)) != SPANGPU_OK)
         return rc;
     AdsiRxLaunch V;
     memset(&V, 0, sizeof(V));
@@ -513,7 +508,7 @@ static int rx_launch(spangpu_adsi_rx_s *b, const int16_t *amp, int mem_kind, int
     L.quarter = b->quarter;
     L.n_ch = b->c.n_ch;
     L.samples = samples;
-    L.lens = d_lens;
+    L.lens = b->rxlens.next;
     L.span = b->span;
     // the caller's buffer is only borrowed for the call: the copy in is waited for
     if ((rc = stage_in(&b->c, &b->pcm, mem_kind, amp, stride, samples, true, &L.pcm, &L.stride, &L.vec)) != SPANGPU_OK)
@@ -522,7 +517,7 @@ static int rx_launch(spangpu_adsi_rx_s *b, const int16_t *amp, int mem_kind, int
     V.msgs = b->msgs;
     V.rec_bytes = b->rec_bytes;
     V.rec_lens = b->rec_lens;
-    V.counts = b->counts;
+    V.counts = b->counts.dev;
     V.cap = cap;
     const size_t lds = (size_t) (4*b->span*64 + 2*kFskMsgWords*64)*sizeof(int32_t);
     hipLaunchKernelGGL(adsi_rx_kernel, dim3((b->c.n_ch + 63)/64), dim3(128), lds, b->c.stream, V);
@@ -538,7 +533,7 @@ int spangpu_adsi_rx(spangpu_adsi_rx_t *b, const int16_t *amp, int mem_kind, int 
     const int rc = rx_args_ok(b, mem_kind, amp, samples, &stride);
     if (rc != SPANGPU_OK)
         return rc;
-    return rx_launch(b, amp, mem_kind, samples, stride, NULL);
+    return rx_launch(b, amp, mem_kind, samples, stride);
 }
 
 // spangpu_adsi_rx() for a tick in which not every channel has a frame, or frames differ in length: channel c takes lens[c]
@@ -549,25 +544,21 @@ int spangpu_adsi_rx_var(spangpu_adsi_rx_t *b, const int16_t *amp, int mem_kind, 
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (mem_kind_ok(mem_kind) != SPANGPU_OK)
         return SPANGPU_ERR_BAD_ARG;
-    for (int c = 0;  c < b->c.n_ch;  c++)
-    {
-        if (lens[c] < 0  ||  lens[c] > max_samples)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
-    }
+    int longest;
+    bool all;
+    int rc = lens_check(lens, b->c.n_ch, max_samples, &longest, &all);
+    if (rc != SPANGPU_OK)
+        return rc;
     if (stride <= 0)
         stride = max_samples;
     if (stride < max_samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < max_samples");
-    SPG_TRY(hipSetDevice(b->c.device));
-    if (b->d_rxlens == NULL)
-    {
-        SPG_TRY(hipMalloc(&b->d_rxlens, (size_t) b->c.n_ch*sizeof(int32_t)));
-        SPG_TRY(hipHostMalloc(&b->h_rxlens, (size_t) b->c.n_ch*sizeof(int32_t)));
-    }
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
-    memcpy(b->h_rxlens, lens, (size_t) b->c.n_ch*sizeof(int32_t));
-    SPG_TRY(hipMemcpyAsync(b->d_rxlens, b->h_rxlens, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, b->c.stream));
-    return rx_launch(b, amp, mem_kind, max_samples, stride, b->d_rxlens);
+    // always a launch of max_samples with the lengths: a call nobody takes part in leaves an empty record
+    if ((rc = lens_upload(&b->c, &b->rxlens, lens)) != SPANGPU_OK)
+        return rc;
+    rc = rx_launch(b, amp, mem_kind, max_samples, stride);
+    b->rxlens.next = NULL;
+    return rc;
 }
 
 int spangpu_adsi_rx_messages(spangpu_adsi_rx_t *b, const uint8_t **bytes, const int32_t **lens, const int32_t **counts)
@@ -576,39 +567,21 @@ int spangpu_adsi_rx_messages(spangpu_adsi_rx_t *b, const uint8_t **bytes, const 
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_adsi_rx() yet");
-    SPG_TRY(hipSetDevice(b->c.device));
-    const size_t slots = (size_t) b->c.n_ch*b->last_cap;
-    if (slots > b->h_cap)
-    {
-        free(b->h_bytes);
-        free(b->h_lens);
-        b->h_cap = 0;
-        b->h_bytes = (uint8_t *) malloc(slots*kAdsiMsg);
-        b->h_lens = (int32_t *) malloc(slots*sizeof(int32_t));
-        if (b->h_bytes == NULL  ||  b->h_lens == NULL)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host message records");
-        b->h_cap = slots;
-    }
-    SPG_TRY(hipMemcpyAsync(b->h_counts, b->counts, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
+    int rc = counts_fetch(&b->c, &b->counts, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
     // the record is sized from the shortest message; a count above it would mean the sizing is wrong, and is not cut short quietly
-    bool any = false;
-    for (int c = 0;  c < b->c.n_ch;  c++)
-    {
-        if (b->h_counts[c] > b->last_cap)
-            return spangpu_set_error(SPANGPU_ERR_STATE, "a channel delivered more messages than a call of this length can carry");
-        any = any  ||  b->h_counts[c] > 0;
-    }
-    // (a message arrives once per call set-up: most calls have nothing to bring back)
-    if (any)
-    {
-        SPG_TRY(hipMemcpyAsync(b->h_bytes, b->rec_bytes, slots*kAdsiMsg, hipMemcpyDeviceToHost, b->c.stream));
-        SPG_TRY(hipMemcpyAsync(b->h_lens, b->rec_lens, slots*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
-        SPG_TRY(hipStreamSynchronize(b->c.stream));
-    }
+    int most;
+    if (!count_row_scan(b->counts.pinned, b->c.n_ch, b->last_cap, &most))
+        return spangpu_set_error(SPANGPU_ERR_STATE, "a channel delivered more messages than a call of this length can carry");
+    // (a message arrives once per call set-up: most calls have no column to bring back)
+    if ((rc = rows_fetch(&b->c, b->h_bytes, b->rec_bytes, kAdsiMsg, b->last_cap, most)) != SPANGPU_OK
+        ||  (rc = rows_fetch(&b->c, b->h_lens, b->rec_lens, sizeof(int32_t), b->last_cap, most)) != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
     *bytes = b->h_bytes;
     *lens = b->h_lens;
-    *counts = b->h_counts;
+    *counts = b->counts.pinned;
     return b->last_cap;
 }
 

@@ -3,6 +3,7 @@
 
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "bank_host.hpp"
 
@@ -165,6 +166,47 @@ int stage_in(BankCore *c, PcmStage *s, int mem_kind, const int16_t *amp, long lo
     *k_stride = host  ?  (long long) s->pcm_cap  :  stride;
     if (vec)
         *vec = vec_of(*k_pcm, *k_stride);
+    return SPANGPU_OK;
+}
+
+int lens_upload(BankCore *c, VarLens *v, const int32_t *lens)
+{
+    const size_t bytes = (size_t) c->n_ch*sizeof(int32_t);
+    SPG_TRY(hipSetDevice(c->device));
+    if (v->dev == NULL)
+    {
+        SPG_TRY(hipMalloc(&v->dev, bytes));
+        SPG_TRY(hipHostMalloc(&v->pinned, bytes));
+    }
+    SPG_TRY(hipStreamSynchronize(c->stream));
+    memcpy(v->pinned, lens, bytes);
+    SPG_TRY(hipMemcpyAsync(v->dev, v->pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    v->next = v->dev;
+    return SPANGPU_OK;
+}
+
+int counts_create(BankCore *c, CountRows *k, int rows, int pinned_rows)
+{
+    const size_t row = (size_t) c->n_ch*sizeof(int32_t);
+    if (hipMalloc(&k->dev, rows*row) != hipSuccess  ||  hipHostMalloc(&k->pinned, pinned_rows*row) != hipSuccess)
+        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "result counts");
+    return SPANGPU_OK;
+}
+
+int counts_fetch(BankCore *c, CountRows *k, int rows)
+{
+    SPG_TRY(hipSetDevice(c->device));
+    SPG_TRY(hipMemcpyAsync(k->pinned, k->dev, (size_t) rows*c->n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    SPG_TRY(hipStreamSynchronize(c->stream));
+    return SPANGPU_OK;
+}
+
+int rows_fetch(BankCore *c, void *pinned, const void *dev, size_t elem, int cap, int columns)
+{
+    columns = (columns > cap)  ?  cap  :  columns;
+    if (columns > 0)
+        SPG_TRY(hipMemcpy2DAsync(pinned, (size_t) cap*elem, dev, (size_t) cap*elem, (size_t) columns*elem, (size_t) c->n_ch,
+                                 hipMemcpyDeviceToHost, c->stream));
     return SPANGPU_OK;
 }
 

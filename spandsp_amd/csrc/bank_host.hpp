@@ -8,12 +8,20 @@
 // its device, channel count and stream alone (its four-row staging is its own).  The sets of banks over several devices
 // (shard_api.hip) sit on shard_core.hpp, which holds banks of these kinds.  The tone bank (spangpu_api.hip), the feeds and the
 // primitives take SPG_TRY only: two joined streams and slot rings are another shape.
+// The six banks with an _rx_var entry point (fsk, mct, sigtone, modem, v18, adsi _api.hip) keep that call's per-channel lengths
+// in a VarLens; those six and the HDLC receiver and FAX front-end banks (hdlc_api.hip, faxfe_api.hip) hand a call's result
+// rows to the host through CountRows, count_row_scan() and rows_fetch().
 //
 // The behaviours this sharing makes uniform:
 //  - every sender's tx refuses more than kMaxSamples samples a call (tx_args_ok); before, the tone and modem senders did not;
 //  - set_stream and sync of the modem receiver and echo canceller banks make the bank's device current first, as the core's
 //    always did; before, those two acted on whatever device the calling thread had current;
-//  - spangpu_modem_rx() refuses a row stride shorter than the call (rx_args_ok), like the other receivers.
+//  - spangpu_modem_rx() refuses a row stride shorter than the call (rx_args_ok), like the other receivers;
+//  - every read-back of result rows hands out pinned host blocks, made in the rx call (grow_pair); before, fsk, mct, sigtone,
+//    v18 and adsi grew pageable blocks inside the read-back;
+//  - every read-back brings the counts first and then only the columns some channel filled (before, only hdlc and faxfe
+//    did; adsi's "only if any count is non-zero" is the case of no column): two waits where small banks had one;
+//  - so host entries past a channel's count may hold an earlier call's data.  spangpu.h promises entries below the count only.
 // Everything else a family does differently is a parameter or stays at its call site.
 
 #pragma once
@@ -177,6 +185,76 @@ static inline int grow_pair(T **dev, T **pinned, C *cap, C need, size_t per, hip
     }
     return SPANGPU_OK;
 }
+
+// ---- the per-channel lengths of an _rx_var call ------------------------------------------------------------------------
+
+struct VarLens
+{
+    const int32_t *next;    // what the launch being prepared reads (device memory: dev, or a caller's), or NULL
+    int32_t *dev;           // [n_ch]
+    int32_t *pinned;        // [n_ch]
+};
+
+// lens[0 .. n_ch) against 0..max_samples; the longest, and whether all are equal.  No HIP call.
+static inline int lens_check(const int32_t *lens, int n_ch, int max_samples, int *longest, bool *all_equal)
+{
+    int lo = max_samples;
+    int hi = 0;
+    for (int c = 0;  c < n_ch;  c++)
+    {
+        if (lens[c] < 0  ||  lens[c] > max_samples)
+            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
+        lo = (lens[c] < lo)  ?  lens[c]  :  lo;
+        hi = (lens[c] > hi)  ?  lens[c]  :  hi;
+    }
+    *longest = hi;
+    *all_equal = (lo == hi);
+    return SPANGPU_OK;
+}
+
+// Both blocks on first use; then the stream is waited for (the last copy out of the pinned block is done), the lengths go
+// into the pinned block and their copy to the device is queued.  v->next = v->dev: the caller clears it after its launch.
+int lens_upload(BankCore *c, VarLens *v, const int32_t *lens);
+
+static inline void lens_free(VarLens *v)
+{
+    (void) hipFree(v->dev);
+    if (v->pinned)
+        (void) hipHostFree(v->pinned);
+}
+
+// ---- a call's result rows on their way to the host: counts[rows][n_ch] first, then of each block [n_ch][cap] the columns
+// some channel filled (blocks and their pinned twins: grow_pair(), before the launch) ---------------------------------------
+
+struct CountRows
+{
+    int32_t *dev;           // [rows][n_ch]
+    int32_t *pinned;        // the same, and whatever rows more the bank asked for
+};
+
+int counts_create(BankCore *c, CountRows *k, int rows, int pinned_rows);
+int counts_fetch(BankCore *c, CountRows *k, int rows);        // device current, one copy, one wait
+
+static inline void counts_free(CountRows *k)
+{
+    (void) hipFree(k->dev);
+    if (k->pinned)
+        (void) hipHostFree(k->pinned);
+}
+
+// one row of counts: the largest (0 at least); false where a count is above cap.  No HIP call.
+static inline bool count_row_scan(const int32_t *row, int n_ch, int cap, int *most)
+{
+    int hi = 0;
+    for (int c = 0;  c < n_ch;  c++)
+        hi = (row[c] > hi)  ?  row[c]  :  hi;
+    *most = hi;
+    return hi <= cap;
+}
+
+// queues the copy of the first `columns` (at most cap) elements, elem bytes each, of every channel's row of `cap`; none:
+// nothing.  The caller waits once behind all its blocks.
+int rows_fetch(BankCore *c, void *pinned, const void *dev, size_t elem, int cap, int columns);
 
 // dds_int.c: one quadrant of a sine, 257 entries, in device memory (hipFree() it)
 int quarter_sine_upload(int16_t **quarter);

@@ -54,8 +54,7 @@ struct spangpu_faxfe_s
     int8_t *put;                        // [n_ch][put_cap]
     int8_t *h_put;
     int put_room;
-    int32_t *counts;                    // [4][n_ch]
-    int32_t *h_counts;                  // pinned, and two more rows for spangpu_faxfe_handlers()
+    CountRows counts;                   // [4][n_ch]; the pinned block has two more rows for spangpu_faxfe_handlers()
     int rec_cap;                        // of the last tick; 0: none yet
     int byte_cap;
     int put_cap;
@@ -176,15 +175,13 @@ void spangpu_faxfe_destroy(spangpu_faxfe_t *b)
     (void) hipFree(b->recs);
     (void) hipFree(b->bytes);
     (void) hipFree(b->put);
-    (void) hipFree(b->counts);
+    counts_free(&b->counts);
     if (b->h_recs)
         (void) hipHostFree(b->h_recs);
     if (b->h_bytes)
         (void) hipHostFree(b->h_bytes);
     if (b->h_put)
         (void) hipHostFree(b->h_put);
-    if (b->h_counts)
-        (void) hipHostFree(b->h_counts);
     free(b);
 }
 
@@ -214,7 +211,7 @@ int spangpu_faxfe_create(spangpu_faxfe_t **out, int device, int n_channels, int 
     if (b->h_slot == NULL
         ||  hipMalloc(&b->lens, (kFaxFeSlots + 1)*n*sizeof(int32_t)) != hipSuccess
         ||  hipMalloc(&b->pcm, n*(size_t) b->pcm_stride*sizeof(int16_t)) != hipSuccess
-        ||  hipMalloc(&b->counts, 4*n*sizeof(int32_t)) != hipSuccess  ||  hipHostMalloc(&b->h_counts, 6*n*sizeof(int32_t)) != hipSuccess)
+        ||  counts_create(&b->c, &b->counts, 4, 6) != SPANGPU_OK)
     {
         spangpu_faxfe_destroy(b);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the FAX front-end bank failed");
@@ -464,7 +461,7 @@ int spangpu_faxfe_rx(spangpu_faxfe_t *b, const int16_t *amp, int mem, int sample
     L.recs = b->recs;
     L.bytes = b->bytes;
     L.put = b->put;
-    L.counts = b->counts;
+    L.counts = b->counts.dev;
     L.rec_cap = rec_cap;
     L.byte_cap = byte_cap;
     L.put_cap = put_cap;
@@ -486,20 +483,21 @@ int spangpu_faxfe_capacities(const spangpu_faxfe_t *b, int *rec_cap, int *byte_c
     return SPANGPU_OK;
 }
 
-// the last tick's counts; a list or a row that did not fit is an error, never cut short quietly
-static int fetch_counts(spangpu_faxfe_s *b)
+// the last tick's counts, and the most of the first three rows; a list or a row that did not fit (the fourth row says so
+// too) is an error, never cut short quietly
+static int fetch_counts(spangpu_faxfe_s *b, int most[4])
 {
     if (b->rec_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_faxfe_rx() yet");
-    SPG_TRY(hipSetDevice(b->c.device));
-    const size_t n = (size_t) b->c.n_ch;
-    SPG_TRY(hipMemcpyAsync(b->h_counts, b->counts, 4*n*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
-    for (size_t c = 0;  c < n;  c++)
-    {
-        if (b->h_counts[c] > b->rec_cap  ||  b->h_counts[n + c] > b->byte_cap  ||  b->h_counts[2*n + c] > b->put_cap  ||  b->h_counts[3*n + c])
-            return spangpu_set_error(SPANGPU_ERR_STATE, "a channel delivered more than a tick of this length can carry");
-    }
+    const int rc = counts_fetch(&b->c, &b->counts, 4);
+    if (rc != SPANGPU_OK)
+        return rc;
+    const int caps[4] = {b->rec_cap, b->byte_cap, b->put_cap, 0};
+    bool fits = true;
+    for (int row = 0;  row < 4;  row++)
+        fits &= count_row_scan(b->counts.pinned + (size_t) row*b->c.n_ch, b->c.n_ch, caps[row], &most[row]);
+    if (!fits)
+        return spangpu_set_error(SPANGPU_ERR_STATE, "a channel delivered more than a tick of this length can carry");
     return SPANGPU_OK;
 }
 
@@ -507,27 +505,16 @@ int spangpu_faxfe_frames(spangpu_faxfe_t *b, const int32_t **recs, const int32_t
 {
     if (b == NULL  ||  recs == NULL  ||  counts == NULL  ||  bytes == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int rc = fetch_counts(b);
+    int most[4];
+    int rc = fetch_counts(b, most);
     if (rc != SPANGPU_OK)
         return rc;
-    const size_t n = (size_t) b->c.n_ch;
-    int most_recs = 0;
-    int most_bytes = 0;
-    for (size_t c = 0;  c < n;  c++)
-    {
-        most_recs = (b->h_counts[c] > most_recs)  ?  b->h_counts[c]  :  most_recs;
-        most_bytes = (b->h_counts[n + c] > most_bytes)  ?  b->h_counts[n + c]  :  most_bytes;
-    }
-    // only the columns some channel filled cross to the host
-    if (most_recs)
-        SPG_TRY(hipMemcpy2DAsync(b->h_recs, (size_t) b->rec_cap*sizeof(int32_t), b->recs, (size_t) b->rec_cap*sizeof(int32_t),
-                                 (size_t) most_recs*sizeof(int32_t), n, hipMemcpyDeviceToHost, b->c.stream));
-    if (most_bytes)
-        SPG_TRY(hipMemcpy2DAsync(b->h_bytes, (size_t) b->byte_cap, b->bytes, (size_t) b->byte_cap, (size_t) most_bytes, n,
-                                 hipMemcpyDeviceToHost, b->c.stream));
+    if ((rc = rows_fetch(&b->c, b->h_recs, b->recs, sizeof(int32_t), b->rec_cap, most[0])) != SPANGPU_OK
+        ||  (rc = rows_fetch(&b->c, b->h_bytes, b->bytes, 1, b->byte_cap, most[1])) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(b->c.stream));
     *recs = b->h_recs;
-    *counts = b->h_counts;
+    *counts = b->counts.pinned;
     *bytes = b->h_bytes;
     return b->rec_cap;
 }
@@ -536,18 +523,13 @@ int spangpu_faxfe_put_bits(spangpu_faxfe_t *b, const int8_t **events, const int3
 {
     if (b == NULL  ||  events == NULL  ||  counts == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int rc = fetch_counts(b);
-    if (rc != SPANGPU_OK)
+    int most[4];
+    int rc = fetch_counts(b, most);
+    if (rc != SPANGPU_OK  ||  (rc = rows_fetch(&b->c, b->h_put, b->put, 1, b->put_cap, most[2])) != SPANGPU_OK)
         return rc;
-    const size_t n = (size_t) b->c.n_ch;
-    int most = 0;
-    for (size_t c = 0;  c < n;  c++)
-        most = (b->h_counts[2*n + c] > most)  ?  b->h_counts[2*n + c]  :  most;
-    if (most)
-        SPG_TRY(hipMemcpy2DAsync(b->h_put, (size_t) b->put_cap, b->put, (size_t) b->put_cap, (size_t) most, n, hipMemcpyDeviceToHost, b->c.stream));
     SPG_TRY(hipStreamSynchronize(b->c.stream));
     *events = b->h_put;
-    *counts = b->h_counts + 2*n;
+    *counts = b->counts.pinned + 2*(size_t) b->c.n_ch;
     return b->put_cap;
 }
 
@@ -557,7 +539,7 @@ int spangpu_faxfe_handlers(spangpu_faxfe_t *b, int32_t *handler, int32_t *frame_
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     SPG_TRY(hipSetDevice(b->c.device));
     const size_t n = (size_t) b->c.n_ch;
-    int32_t *h = b->h_counts + 4*n;
+    int32_t *h = b->counts.pinned + 4*n;
     SPG_TRY(hipMemcpyAsync(h, b->c.st + (size_t) FE_HANDLER*n, n*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
     SPG_TRY(hipMemcpyAsync(h + n, b->c.st + (size_t) FE_RX_FRAME_RECEIVED*n, n*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
     SPG_TRY(hipStreamSynchronize(b->c.stream));

@@ -196,21 +196,17 @@ extern "C" __attribute__((visibility("hidden"))) int spangpu_fsk_waves_choice(vo
 
 struct spangpu_fsk_s
 {
-    const int32_t *next_lens;   // per-channel lengths of the call being prepared (device), or NULL
-    int32_t *d_lens;            // [n_ch], device
-    int32_t *h_lens;            // [n_ch], pinned
+    VarLens lens;               // per-channel lengths of the call being prepared
     BankCore c;
     PcmStage pcm;               // staging for host-resident frames
     int span;
     spangpu_fsk_spec_t spec;
     int16_t *quarter;
-    int16_t *events;
-    int32_t *ev_count;
+    int16_t *events;            // [n_ch][ev_cap]
+    int16_t *h_events;
+    CountRows count;
     int ev_cap;
     int last_cap;
-    int16_t *h_events;
-    int32_t *h_count;
-    size_t h_events_cap;
 };
 
 // preset_fsk_specs[], src/fsk.c:60-155: freq_zero, freq_one, tx_level, min_level, baud_rate x 100
@@ -317,7 +313,7 @@ extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_words_fillin(i
 extern "C" __attribute__((visibility("hidden"))) void spangpu_fsk_event_rows(const spangpu_fsk_t *f, const int16_t **events, const int32_t **counts, int *cap)
 {
     *events = f->events;
-    *counts = f->ev_count;
+    *counts = f->count.dev;
     *cap = f->last_cap;
 }
 
@@ -363,9 +359,7 @@ int spangpu_fsk_create(spangpu_fsk_t **out, int device, int n_channels, const sp
         return rc;
     }
     int32_t *one = (int32_t *) calloc(words, sizeof(int32_t));
-    if (hipMalloc(&f->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
-        ||  (f->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL
-        ||  one == NULL)
+    if (counts_create(&f->c, &f->count, 1, 1) != SPANGPU_OK  ||  one == NULL)
     {
         free(one);
         spangpu_fsk_destroy(f);
@@ -391,12 +385,11 @@ void spangpu_fsk_destroy(spangpu_fsk_t *f)
     core_destroy(&f->c);
     stage_free(&f->pcm);
     (void) hipFree(f->quarter);
-    (void) hipFree(f->d_lens);
-    if (f->h_lens) (void) hipHostFree(f->h_lens);
+    lens_free(&f->lens);
     (void) hipFree(f->events);
-    (void) hipFree(f->ev_count);
-    free(f->h_events);
-    free(f->h_count);
+    if (f->h_events)
+        (void) hipHostFree(f->h_events);
+    counts_free(&f->count);
     free(f);
 }
 
@@ -424,17 +417,17 @@ int spangpu_fsk_rx(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, int sampl
         return rc;
     SPG_TRY(hipSetDevice(f->c.device));
     // at most one event per sample (a status change and a bit can share one sample: + 2)
-    if ((rc = grow(&f->events, &f->ev_cap, samples + 2, (size_t) f->c.n_ch, f->c.stream)) != SPANGPU_OK)
+    if ((rc = grow_pair(&f->events, &f->h_events, &f->ev_cap, samples + 2, (size_t) f->c.n_ch, f->c.stream)) != SPANGPU_OK)
         return rc;
     FskLaunch L;
     memset(&L, 0, sizeof(L));
     L.st = f->c.st;
     L.quarter = f->quarter;
     L.events = f->events;
-    L.ev_count = f->ev_count;
+    L.ev_count = f->count.dev;
     L.n_ch = f->c.n_ch;
     L.samples = samples;
-    L.lens = f->next_lens;
+    L.lens = f->lens.next;
     L.span = f->span;
     L.ev_cap = f->ev_cap;
     // the caller's buffer is only borrowed for the call: the copy in is waited for
@@ -456,35 +449,18 @@ int spangpu_fsk_rx_var(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, const
 {
     if (f == NULL  ||  amp == NULL  ||  lens == NULL  ||  max_samples <= 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    int longest = 0;
-    bool all = true;
-    for (int c = 0;  c < f->c.n_ch;  c++)
-    {
-        if (lens[c] < 0  ||  lens[c] > max_samples)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
-        if (lens[c] > longest)
-            longest = lens[c];
-    }
-    if (longest == 0)
-        return SPANGPU_OK;
-    for (int c = 0;  c < f->c.n_ch;  c++)
-        all &= (lens[c] == longest);
+    int longest;
+    bool all;
+    int rc = lens_check(lens, f->c.n_ch, max_samples, &longest, &all);
+    // nobody brings a sample: no launch; everybody the same: the plain call
+    if (rc != SPANGPU_OK  ||  longest == 0)
+        return rc;
     if (stride <= 0)
         stride = max_samples;
-    if (all)
-        return spangpu_fsk_rx(f, amp, mem_kind, longest, stride);
-    SPG_TRY(hipSetDevice(f->c.device));
-    if (f->d_lens == NULL)
-    {
-        SPG_TRY(hipMalloc(&f->d_lens, (size_t) f->c.n_ch*sizeof(int32_t)));
-        SPG_TRY(hipHostMalloc(&f->h_lens, (size_t) f->c.n_ch*sizeof(int32_t)));
-    }
-    SPG_TRY(hipStreamSynchronize(f->c.stream));
-    memcpy(f->h_lens, lens, (size_t) f->c.n_ch*sizeof(int32_t));
-    SPG_TRY(hipMemcpyAsync(f->d_lens, f->h_lens, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, f->c.stream));
-    f->next_lens = f->d_lens;
-    const int rc = spangpu_fsk_rx(f, amp, mem_kind, longest, stride);
-    f->next_lens = NULL;
+    if (!all  &&  (rc = lens_upload(&f->c, &f->lens, lens)) != SPANGPU_OK)
+        return rc;
+    rc = spangpu_fsk_rx(f, amp, mem_kind, longest, stride);
+    f->lens.next = NULL;
     return rc;
 }
 
@@ -494,9 +470,9 @@ int spangpu_fsk_rx_lens_dev(spangpu_fsk_t *f, const int16_t *amp, int mem_kind, 
 {
     if (f == NULL  ||  lens_dev == NULL)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    f->next_lens = lens_dev;
+    f->lens.next = lens_dev;
     const int rc = spangpu_fsk_rx(f, amp, mem_kind, samples, stride);
-    f->next_lens = NULL;
+    f->lens.next = NULL;
     return rc;
 }
 
@@ -506,21 +482,17 @@ int spangpu_fsk_events(spangpu_fsk_t *f, const int16_t **events, const int32_t *
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (f->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_fsk_rx() yet");
-    SPG_TRY(hipSetDevice(f->c.device));
-    const size_t bytes = (size_t) f->c.n_ch*f->last_cap*sizeof(int16_t);
-    if (bytes > f->h_events_cap)
-    {
-        free(f->h_events);
-        f->h_events_cap = 0;
-        if ((f->h_events = (int16_t *) malloc(bytes)) == NULL)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host event buffer");
-        f->h_events_cap = bytes;
-    }
-    SPG_TRY(hipMemcpyAsync(f->h_events, f->events, bytes, hipMemcpyDeviceToHost, f->c.stream));
-    SPG_TRY(hipMemcpyAsync(f->h_count, f->ev_count, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, f->c.stream));
+    int rc = counts_fetch(&f->c, &f->count, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
+    // (samples + 2 events a call at the very most: a count cannot exceed the capacity)
+    int most;
+    (void) count_row_scan(f->count.pinned, f->c.n_ch, f->last_cap, &most);
+    if ((rc = rows_fetch(&f->c, f->h_events, f->events, sizeof(int16_t), f->last_cap, most)) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(f->c.stream));
     *events = f->h_events;
-    *counts = f->h_count;
+    *counts = f->count.pinned;
     return f->last_cap;
 }
 
@@ -537,7 +509,7 @@ int spangpu_fsk_copy_events(spangpu_fsk_t *f, void *dev_dst, size_t dst_bytes, i
     if (dst_bytes < need)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "destination too small");
     SPG_TRY(hipSetDevice(f->c.device));
-    SPG_TRY(hipMemcpyAsync(dev_dst, f->ev_count, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, f->c.stream));
+    SPG_TRY(hipMemcpyAsync(dev_dst, f->count.dev, (size_t) f->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, f->c.stream));
     const int w = (per_channel < f->last_cap)  ?  per_channel  :  f->last_cap;
     SPG_TRY(hipMemcpy2DAsync((char *) dev_dst + (size_t) f->c.n_ch*sizeof(int32_t), (size_t) per_channel*sizeof(int16_t), f->events,
                              (size_t) f->last_cap*sizeof(int16_t), (size_t) w*sizeof(int16_t), (size_t) f->c.n_ch, hipMemcpyDeviceToDevice,

@@ -28,8 +28,7 @@ struct spangpu_hdlc_rx_s
     uint8_t *bytes;             // [n_ch][byte_cap]
     uint8_t *h_bytes;           // pinned
     int byte_room;
-    int32_t *counts;            // [2][n_ch]: records, then octets
-    int32_t *h_counts;          // pinned
+    CountRows counts;           // [2][n_ch]: records, then octets
     int rec_cap;                // of the last call; 0: none yet
     int byte_cap;
 };
@@ -121,13 +120,11 @@ void spangpu_hdlc_rx_destroy(spangpu_hdlc_rx_t *b)
     (void) hipFree(b->d_counts);
     (void) hipFree(b->recs);
     (void) hipFree(b->bytes);
-    (void) hipFree(b->counts);
+    counts_free(&b->counts);
     if (b->h_recs)
         (void) hipHostFree(b->h_recs);
     if (b->h_bytes)
         (void) hipHostFree(b->h_bytes);
-    if (b->h_counts)
-        (void) hipHostFree(b->h_counts);
     free(b);
 }
 
@@ -149,7 +146,7 @@ int spangpu_hdlc_rx_create(spangpu_hdlc_rx_t **out, int device, int n_channels, 
     }
     const size_t n = (size_t) n_channels;
     if (hipMalloc(&b->buf, n*kHdlcBufWords*sizeof(uint32_t)) != hipSuccess  ||  hipMalloc(&b->d_counts, n*sizeof(int32_t)) != hipSuccess
-        ||  hipMalloc(&b->counts, 2*n*sizeof(int32_t)) != hipSuccess  ||  hipHostMalloc(&b->h_counts, 2*n*sizeof(int32_t)) != hipSuccess)
+        ||  counts_create(&b->c, &b->counts, 2, 2) != SPANGPU_OK)
     {
         spangpu_hdlc_rx_destroy(b);
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the HDLC receiver bank failed");
@@ -240,8 +237,8 @@ static int rx_launch(spangpu_hdlc_rx_s *b, int mem_kind, const void *rows, int e
     L.vec = (((size_t) cap*esz) % 16 == 0  &&  (reinterpret_cast<uintptr_t>(L.events) & 15) == 0)  ?  1  :  0;
     L.recs = b->recs;
     L.bytes = b->bytes;
-    L.rec_counts = b->counts;
-    L.byte_counts = b->counts + n;
+    L.rec_counts = b->counts.dev;
+    L.byte_counts = b->counts.dev + n;
     L.rec_cap = rec_cap;
     L.byte_cap = byte_cap;
     const dim3 grid((b->c.n_ch + 63)/64);
@@ -283,31 +280,22 @@ int spangpu_hdlc_rx_records(spangpu_hdlc_rx_t *b, const int32_t **recs, const in
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->rec_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no put yet");
-    SPG_TRY(hipSetDevice(b->c.device));
-    const size_t n = (size_t) b->c.n_ch;
-    SPG_TRY(hipMemcpyAsync(b->h_counts, b->counts, 2*n*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
+    int rc = counts_fetch(&b->c, &b->counts, 2);
+    if (rc != SPANGPU_OK)
+        return rc;
     // the lists are sized from what a call can deliver at most: a count above that means the sizing is wrong, and is not
     // cut short quietly
-    int most_recs = 0;
-    int most_bytes = 0;
-    for (size_t c = 0;  c < n;  c++)
-    {
-        if (b->h_counts[c] > b->rec_cap  ||  b->h_counts[n + c] > b->byte_cap)
-            return spangpu_set_error(SPANGPU_ERR_STATE, "a channel delivered more than a call of this length can carry");
-        most_recs = (b->h_counts[c] > most_recs)  ?  b->h_counts[c]  :  most_recs;
-        most_bytes = (b->h_counts[n + c] > most_bytes)  ?  b->h_counts[n + c]  :  most_bytes;
-    }
-    // only the columns some channel filled cross to the host
-    if (most_recs)
-        SPG_TRY(hipMemcpy2DAsync(b->h_recs, (size_t) b->rec_cap*sizeof(int32_t), b->recs, (size_t) b->rec_cap*sizeof(int32_t),
-                                 (size_t) most_recs*sizeof(int32_t), n, hipMemcpyDeviceToHost, b->c.stream));
-    if (most_bytes)
-        SPG_TRY(hipMemcpy2DAsync(b->h_bytes, (size_t) b->byte_cap, b->bytes, (size_t) b->byte_cap, (size_t) most_bytes, n,
-                                 hipMemcpyDeviceToHost, b->c.stream));
+    const int32_t *h = b->counts.pinned;
+    int most_recs;
+    int most_bytes;
+    if (!count_row_scan(h, b->c.n_ch, b->rec_cap, &most_recs)  ||  !count_row_scan(h + b->c.n_ch, b->c.n_ch, b->byte_cap, &most_bytes))
+        return spangpu_set_error(SPANGPU_ERR_STATE, "a channel delivered more than a call of this length can carry");
+    if ((rc = rows_fetch(&b->c, b->h_recs, b->recs, sizeof(int32_t), b->rec_cap, most_recs)) != SPANGPU_OK
+        ||  (rc = rows_fetch(&b->c, b->h_bytes, b->bytes, 1, b->byte_cap, most_bytes)) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(b->c.stream));
     *recs = b->h_recs;
-    *counts = b->h_counts;
+    *counts = h;
     *bytes = b->h_bytes;
     return b->rec_cap;
 }

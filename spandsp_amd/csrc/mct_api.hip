@@ -16,21 +16,17 @@ using namespace spg;
 
 struct spangpu_mct_s
 {
-    const int32_t *next_lens;   // per-channel lengths of the call being prepared (device), or NULL
-    int32_t *d_lens;            // [n_ch], device
-    int32_t *h_lens;            // [n_ch], pinned
+    VarLens lens;               // per-channel lengths of the call being prepared
     BankCore c;
     PcmStage pcm;
     int tone_type;              // after modem_connect_tones_rx_init()'s folding of the ANS variants
     int latch;
     int16_t *quarter;
-    int32_t *events;
-    int32_t *ev_count;
+    int32_t *events;            // [n_ch][ev_cap][2]
+    int32_t *h_events;
+    CountRows count;
     int ev_cap;
     int last_cap;
-    int32_t *h_events;
-    int32_t *h_count;
-    size_t h_events_cap;
 };
 
 static const float kMaxPower = 3.14f + 3.02f;       // DBM0_MAX_POWER
@@ -103,9 +99,7 @@ int spangpu_mct_create(spangpu_mct_t **out, int device, int tone_type, int n_cha
         return rc;
     }
     int32_t *one = (int32_t *) calloc(words, sizeof(int32_t));
-    if (hipMalloc(&m->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
-        ||  (m->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL
-        ||  one == NULL)
+    if (counts_create(&m->c, &m->count, 1, 1) != SPANGPU_OK  ||  one == NULL)
     {
         free(one);
         spangpu_mct_destroy(m);
@@ -146,12 +140,11 @@ void spangpu_mct_destroy(spangpu_mct_t *m)
     core_destroy(&m->c);
     stage_free(&m->pcm);
     (void) hipFree(m->quarter);
-    (void) hipFree(m->d_lens);
-    if (m->h_lens) (void) hipHostFree(m->h_lens);
+    lens_free(&m->lens);
     (void) hipFree(m->events);
-    (void) hipFree(m->ev_count);
-    free(m->h_events);
-    free(m->h_count);
+    if (m->h_events)
+        (void) hipHostFree(m->h_events);
+    counts_free(&m->count);
     free(m);
 }
 
@@ -180,17 +173,17 @@ int spangpu_mct_rx(spangpu_mct_t *m, const int16_t *amp, int mem_kind, int sampl
     SPG_TRY(hipSetDevice(m->c.device));
     // a tone needs >= 415 ms to be declared and can only be withdrawn once declared: two reports per ~3300
     // samples at the very most; the preamble hunter needs 40 bits (1067 samples) per declaration
-    if ((rc = grow(&m->events, &m->ev_cap, 8 + samples/256, (size_t) m->c.n_ch*2, m->c.stream)) != SPANGPU_OK)
+    if ((rc = grow_pair(&m->events, &m->h_events, &m->ev_cap, 8 + samples/256, (size_t) m->c.n_ch*2, m->c.stream)) != SPANGPU_OK)
         return rc;
     MctLaunch L;
     memset(&L, 0, sizeof(L));
     L.st = m->c.st;
     L.quarter = m->quarter;
     L.events = m->events;
-    L.ev_count = m->ev_count;
+    L.ev_count = m->count.dev;
     L.n_ch = m->c.n_ch;
     L.samples = samples;
-    L.lens = m->next_lens;
+    L.lens = m->lens.next;
     L.ev_cap = m->ev_cap;
     L.latch = m->latch;
     // the caller's buffer is only borrowed for the call: the copy in is waited for
@@ -216,35 +209,18 @@ int spangpu_mct_rx_var(spangpu_mct_t *m, const int16_t *amp, int mem_kind, const
 {
     if (m == NULL  ||  amp == NULL  ||  lens == NULL  ||  max_samples <= 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    int longest = 0;
-    bool all = true;
-    for (int c = 0;  c < m->c.n_ch;  c++)
-    {
-        if (lens[c] < 0  ||  lens[c] > max_samples)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
-        if (lens[c] > longest)
-            longest = lens[c];
-    }
-    if (longest == 0)
-        return SPANGPU_OK;
-    for (int c = 0;  c < m->c.n_ch;  c++)
-        all &= (lens[c] == longest);
+    int longest;
+    bool all;
+    int rc = lens_check(lens, m->c.n_ch, max_samples, &longest, &all);
+    // nobody brings a sample: no launch; everybody the same: the plain call
+    if (rc != SPANGPU_OK  ||  longest == 0)
+        return rc;
     if (stride <= 0)
         stride = max_samples;
-    if (all)
-        return spangpu_mct_rx(m, amp, mem_kind, longest, stride);
-    SPG_TRY(hipSetDevice(m->c.device));
-    if (m->d_lens == NULL)
-    {
-        SPG_TRY(hipMalloc(&m->d_lens, (size_t) m->c.n_ch*sizeof(int32_t)));
-        SPG_TRY(hipHostMalloc(&m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t)));
-    }
-    SPG_TRY(hipStreamSynchronize(m->c.stream));
-    memcpy(m->h_lens, lens, (size_t) m->c.n_ch*sizeof(int32_t));
-    SPG_TRY(hipMemcpyAsync(m->d_lens, m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, m->c.stream));
-    m->next_lens = m->d_lens;
-    const int rc = spangpu_mct_rx(m, amp, mem_kind, longest, stride);
-    m->next_lens = NULL;
+    if (!all  &&  (rc = lens_upload(&m->c, &m->lens, lens)) != SPANGPU_OK)
+        return rc;
+    rc = spangpu_mct_rx(m, amp, mem_kind, longest, stride);
+    m->lens.next = NULL;
     return rc;
 }
 
@@ -254,28 +230,25 @@ int spangpu_mct_events(spangpu_mct_t *m, const int32_t **events, const int32_t *
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_mct_rx() yet");
-    SPG_TRY(hipSetDevice(m->c.device));
-    const size_t bytes = (size_t) m->c.n_ch*m->last_cap*2*sizeof(int32_t);
-    if (bytes > m->h_events_cap)
-    {
-        free(m->h_events);
-        m->h_events_cap = 0;
-        if ((m->h_events = (int32_t *) malloc(bytes)) == NULL)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host event buffer");
-        m->h_events_cap = bytes;
-    }
-    SPG_TRY(hipMemcpyAsync(m->h_events, m->events, bytes, hipMemcpyDeviceToHost, m->c.stream));
-    SPG_TRY(hipMemcpyAsync(m->h_count, m->ev_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->c.stream));
+    int rc = counts_fetch(&m->c, &m->count, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
+    // (a count above the capacity is cut short: the entries that fitted are handed out)
+    int most;
+    (void) count_row_scan(m->count.pinned, m->c.n_ch, m->last_cap, &most);
+    if ((rc = rows_fetch(&m->c, m->h_events, m->events, 2*sizeof(int32_t), m->last_cap, most)) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(m->c.stream));
+    const int32_t *h_count = m->count.pinned;
     for (int c = 0;  c < m->c.n_ch;  c++)
     {
         int32_t *e = m->h_events + (size_t) c*m->last_cap*2;
-        const int cnt = (m->h_count[c] < m->last_cap)  ?  m->h_count[c]  :  m->last_cap;
+        const int cnt = (h_count[c] < m->last_cap)  ?  h_count[c]  :  m->last_cap;
         for (int i = 0;  i < cnt;  i++)
             e[2*i + 1] = level_of(e[2*i], e[2*i + 1]);
     }
     *events = m->h_events;
-    *counts = m->h_count;
+    *counts = h_count;
     return m->last_cap;
 }
 

@@ -34,26 +34,23 @@ static std::atomic<int> g_modem_mapping{0};     // spangpu_tune_modem_mapping():
 
 struct spangpu_modem_s
 {
-    const int32_t *next_lens;   // per-channel lengths of the call being prepared (device: pcm.d_lens), or nullptr
-    int32_t *h_lens;            // [n_ch], pinned
+    VarLens lens;               // per-channel lengths of the call being prepared
     BankCore c;                 // st = [state words of the kind][n_ch]; uint32_t towards the kernels
-    PcmStage pcm;               // staging for host-resident frames, and the device copy of a call's lengths
+    PcmStage pcm;               // staging for host-resident frames
     int kind;
     int n_floats;
     int bit_rate;
     void *tab;
-    int8_t *events;
-    int32_t *ev_count;
-    int ev_cap;
+    int8_t *events;             // [n_ch][ev_cap]
     int8_t *h_events;
-    int32_t *h_count;
+    CountRows count;
+    int ev_cap;
     int last_cap;
     bool qam_tap;               // spangpu_modem_qam_tap(): run the kernel variant that records the qam_report calls
     uint32_t *qam;              // [n_ch][qam_cap][7]
-    int32_t *qam_count;
-    int qam_cap;
     uint32_t *h_qam;
-    int32_t *h_qam_count;
+    CountRows qam_count;        // made with the first call that has the tap on
+    int qam_cap;
     int last_qam_cap;
     uint32_t *d_packed;         // spangpu_modem_events_packed(): [n_ch][packed_wpc] rows, then the status list
     uint32_t *h_packed;
@@ -195,17 +192,17 @@ static L make_launch(const spangpu_modem_t *m, const int16_t *amp, long long str
     l.amp = amp;
     l.stride = stride;
     l.samples = samples;
-    l.lens = m->next_lens;
+    l.lens = m->lens.next;
     l.n_ch = m->c.n_ch;
     if constexpr (!std::is_same<L, V29Launch>::value)
         l.bit_rate = m->bit_rate;                   // V.17 and V.27ter banks run one rate; a V.29 channel carries its own
     l.state = (uint32_t *) m->c.st;
     l.events = m->events;
-    l.ev_count = m->ev_count;
+    l.ev_count = m->count.dev;
     l.ev_cap = m->ev_cap;
     l.tab = (decltype(l.tab)) m->tab;
     l.qam = m->qam;
-    l.qam_count = m->qam_count;
+    l.qam_count = m->qam_count.dev;
     l.qam_cap = m->qam_cap;
     return l;
 }
@@ -346,13 +343,11 @@ int spangpu_modem_create(spangpu_modem_t **out, int device, int kind, int n_chan
         spangpu_modem_destroy(m);
         return rc;
     }
-    const size_t n = (size_t) n_channels;
     const size_t tab_bytes = (kind == SPANGPU_V29)  ?  sizeof(V29Tables)  :  (kind == SPANGPU_V17)  ?  sizeof(V17Tables)  :  sizeof(V27Tables);
     void *ht = calloc(1, tab_bytes);
     if (ht == nullptr
         ||  hipMalloc(&m->tab, tab_bytes) != hipSuccess
-        ||  hipMalloc(&m->ev_count, n*sizeof(int32_t)) != hipSuccess
-        ||  hipHostMalloc(&m->h_count, n*sizeof(int32_t)) != hipSuccess)
+        ||  counts_create(&m->c, &m->count, 1, 1) != SPANGPU_OK)
     {
         free(ht);
         spangpu_modem_destroy(m);
@@ -451,15 +446,13 @@ int spangpu_modem_destroy(spangpu_modem_t *m)
     core_destroy(&m->c);
     stage_free(&m->pcm);
     if (m->tab) (void) hipFree(m->tab);
-    if (m->h_lens) (void) hipHostFree(m->h_lens);
+    lens_free(&m->lens);
     if (m->events) (void) hipFree(m->events);
-    if (m->ev_count) (void) hipFree(m->ev_count);
     if (m->h_events) (void) hipHostFree(m->h_events);
-    if (m->h_count) (void) hipHostFree(m->h_count);
+    counts_free(&m->count);
     if (m->qam) (void) hipFree(m->qam);
-    if (m->qam_count) (void) hipFree(m->qam_count);
     if (m->h_qam) (void) hipHostFree(m->h_qam);
-    if (m->h_qam_count) (void) hipHostFree(m->h_qam_count);
+    counts_free(&m->qam_count);
     if (m->d_packed) (void) hipFree(m->d_packed);
     if (m->h_packed) (void) hipHostFree(m->h_packed);
     free(m);
@@ -503,11 +496,8 @@ int spangpu_modem_rx(spangpu_modem_t *m, const int16_t *amp, int mem, int sample
         const int qcap = 2*((samples*3 + 9)/10 + 2);
         if ((rc = grow_pair(&m->qam, &m->h_qam, &m->qam_cap, qcap, (size_t) m->c.n_ch*7, m->c.stream)) != SPANGPU_OK)
             return rc;
-        if (m->qam_count == nullptr)
-        {
-            SPG_TRY(hipMalloc(&m->qam_count, (size_t) m->c.n_ch*sizeof(int32_t)));
-            SPG_TRY(hipHostMalloc(&m->h_qam_count, (size_t) m->c.n_ch*sizeof(int32_t)));
-        }
+        if (m->qam_count.dev == nullptr  &&  (rc = counts_create(&m->c, &m->qam_count, 1, 1)) != SPANGPU_OK)
+            return rc;
     }
     // amp[] of a host caller is only borrowed for the duration of the call: the copy in is waited for
     const int16_t *d_amp;
@@ -534,35 +524,18 @@ int spangpu_modem_rx_var(spangpu_modem_t *m, const int16_t *amp, int mem, const 
 {
     if (m == nullptr  ||  amp == nullptr  ||  lens == nullptr  ||  max_samples < 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    int longest = 0;
-    bool all = true;
-    for (int c = 0;  c < m->c.n_ch;  c++)
-    {
-        if (lens[c] < 0  ||  lens[c] > max_samples)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
-        if (lens[c] > longest)
-            longest = lens[c];
-    }
-    if (longest == 0)
-        return 0;
-    for (int c = 0;  c < m->c.n_ch;  c++)
-        all &= (lens[c] == longest);
+    int longest;
+    bool all;
+    int rc = lens_check(lens, m->c.n_ch, max_samples, &longest, &all);
+    // nobody brings a sample: no launch; everybody the same: the plain call
+    if (rc != SPANGPU_OK  ||  longest == 0)
+        return rc;
     if (stride <= 0)
         stride = max_samples;
-    if (all)
-        return spangpu_modem_rx(m, amp, mem, longest, stride);
-    SPG_TRY(hipSetDevice(m->c.device));
-    int rc = stage_lens(&m->c, &m->pcm);
-    if (rc != SPANGPU_OK)
+    if (!all  &&  (rc = lens_upload(&m->c, &m->lens, lens)) != SPANGPU_OK)
         return rc;
-    if (m->h_lens == nullptr)
-        SPG_TRY(hipHostMalloc(&m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t)));
-    SPG_TRY(hipStreamSynchronize(m->c.stream));
-    memcpy(m->h_lens, lens, (size_t) m->c.n_ch*sizeof(int32_t));
-    SPG_TRY(hipMemcpyAsync(m->pcm.d_lens, m->h_lens, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, m->c.stream));
-    m->next_lens = m->pcm.d_lens;
     rc = spangpu_modem_rx(m, amp, mem, longest, stride);
-    m->next_lens = nullptr;
+    m->lens.next = nullptr;
     return rc;
 }
 
@@ -574,9 +547,9 @@ int spangpu_modem_rx_lens_dev(spangpu_modem_t *m, const int16_t *amp, int mem, i
 {
     if (m == nullptr  ||  lens_dev == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    m->next_lens = lens_dev;
+    m->lens.next = lens_dev;
     const int rc = spangpu_modem_rx(m, amp, mem, samples, stride);
-    m->next_lens = nullptr;
+    m->lens.next = nullptr;
     return rc;
 }
 
@@ -599,12 +572,17 @@ int spangpu_modem_qam_reports(spangpu_modem_t *m, const uint32_t **records, cons
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_qam_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() with the tap on yet");
-    SPG_TRY(hipSetDevice(m->c.device));
-    SPG_TRY(hipMemcpyAsync(m->h_qam, m->qam, (size_t) m->c.n_ch*m->last_qam_cap*7*sizeof(uint32_t), hipMemcpyDeviceToHost, m->c.stream));
-    SPG_TRY(hipMemcpyAsync(m->h_qam_count, m->qam_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->c.stream));
+    int rc = counts_fetch(&m->c, &m->qam_count, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
+    // (a count above the capacity is the caller's to see: the records that fitted are handed out)
+    int most;
+    (void) count_row_scan(m->qam_count.pinned, m->c.n_ch, m->last_qam_cap, &most);
+    if ((rc = rows_fetch(&m->c, m->h_qam, m->qam, 7*sizeof(uint32_t), m->last_qam_cap, most)) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(m->c.stream));
     *records = m->h_qam;
-    *counts = m->h_qam_count;
+    *counts = m->qam_count.pinned;
     return m->last_qam_cap;
 }
 
@@ -617,17 +595,17 @@ int spangpu_modem_events(spangpu_modem_t *m, const int8_t **events, const int32_
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (m->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_modem_rx() yet");
-    SPG_TRY(hipSetDevice(m->c.device));
-    SPG_TRY(hipMemcpyAsync(m->h_events, m->events, (size_t) m->c.n_ch*m->last_cap, hipMemcpyDeviceToHost, m->c.stream));
-    SPG_TRY(hipMemcpyAsync(m->h_count, m->ev_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, m->c.stream));
+    int rc = counts_fetch(&m->c, &m->count, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
+    int most;
+    if (!count_row_scan(m->count.pinned, m->c.n_ch, m->last_cap, &most))
+        return spangpu_set_error(SPANGPU_ERR_STATE, "modem event buffer overflow: a channel produced more events than the call's frame length allows");
+    if ((rc = rows_fetch(&m->c, m->h_events, m->events, 1, m->last_cap, most)) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(m->c.stream));
-    for (int c = 0;  c < m->c.n_ch;  c++)
-    {
-        if (m->h_count[c] > m->last_cap)
-            return spangpu_set_error(SPANGPU_ERR_STATE, "modem event buffer overflow: a channel produced more events than the call's frame length allows");
-    }
     *events = m->h_events;
-    *counts = m->h_count;
+    *counts = m->count.pinned;
     return m->last_cap;
 }
 
@@ -645,7 +623,7 @@ int spangpu_modem_copy_events(spangpu_modem_t *m, void *dev_dst, size_t dst_byte
     if (dst_bytes < need)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "destination too small");
     SPG_TRY(hipSetDevice(m->c.device));
-    SPG_TRY(hipMemcpyAsync(dev_dst, m->ev_count, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, m->c.stream));
+    SPG_TRY(hipMemcpyAsync(dev_dst, m->count.dev, (size_t) m->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToDevice, m->c.stream));
     const int w = (per_channel < m->last_cap)  ?  per_channel  :  m->last_cap;
     SPG_TRY(hipMemcpy2DAsync((char *) dev_dst + (size_t) m->c.n_ch*sizeof(int32_t), (size_t) per_channel, m->events, (size_t) m->last_cap,
                              (size_t) w, (size_t) m->c.n_ch, hipMemcpyDeviceToDevice, m->c.stream));
@@ -740,7 +718,7 @@ int spangpu_modem_pack_events(spangpu_modem_t *m, uint32_t *packed_device, int w
     SPG_TRY(hipSetDevice(m->c.device));
     SPG_TRY(hipMemsetAsync(status_device, 0, sizeof(uint32_t), m->c.stream));
     hipLaunchKernelGGL(modem_pack_kernel, dim3((m->c.n_ch + 255)/256), dim3(256), 0, m->c.stream, (const int8_t *) m->events,
-                       (const int32_t *) m->ev_count, m->c.n_ch, m->last_cap, packed_device, words_per_channel, status_device, status_cap);
+                       (const int32_t *) m->count.dev, m->c.n_ch, m->last_cap, packed_device, words_per_channel, status_device, status_cap);
     SPG_TRY(hipGetLastError());
     return SPANGPU_OK;
 }
@@ -844,11 +822,11 @@ int spangpu_modem_events_packed(spangpu_modem_t *m, const int8_t **events, const
     const uint32_t *h_status = m->h_packed + (size_t) m->c.n_ch*m->packed_wpc;
     if (h_status[0] > (uint32_t) m->packed_status_cap)
         return spangpu_modem_events(m, events, counts);     // (more status reports in one call than channels: the plain way)
-    rc = spangpu_modem_unpack_events(m->h_packed, m->packed_wpc, h_status, m->packed_status_cap, m->c.n_ch, m->h_events, m->last_cap, m->h_count);
+    rc = spangpu_modem_unpack_events(m->h_packed, m->packed_wpc, h_status, m->packed_status_cap, m->c.n_ch, m->h_events, m->last_cap, m->count.pinned);
     if (rc < 0)
         return spangpu_modem_events(m, events, counts);     // (a row too short -- an event buffer overflow shows there: same error path)
     *events = m->h_events;
-    *counts = m->h_count;
+    *counts = m->count.pinned;
     return m->last_cap;
 }
 
@@ -1076,7 +1054,7 @@ extern "C" __attribute__((visibility("hidden"))) void spangpu_modem_event_rows(c
                                                                                int *cap)
 {
     *events = m->events;
-    *counts = m->ev_count;
+    *counts = m->count.dev;
     *cap = m->last_cap;
 }
 

@@ -51,16 +51,12 @@ struct spangpu_sigtone_rx_s
     BankCore c;
     PcmStage pcm;
     int tone_type;
-    int32_t *d_lens;            // per-channel lengths of an rx_var call
-    int32_t *h_lens;
-    const int32_t *next_lens;
-    int32_t *events;
-    int32_t *ev_count;
+    VarLens lens;               // per-channel lengths of an rx_var call
+    int32_t *events;            // [n_ch][ev_cap][3]
+    int32_t *h_events;
+    CountRows count;
     int ev_cap;
     int last_cap;
-    int32_t *h_events;
-    int32_t *h_count;
-    size_t h_events_cap;
     int32_t thresholds[3];
 };
 
@@ -91,11 +87,10 @@ int spangpu_sigtone_rx_create(spangpu_sigtone_rx_t **out, int device, int tone_t
         spangpu_sigtone_rx_destroy(b);
         return rc;
     }
-    if (hipMalloc(&b->ev_count, (size_t) n_channels*sizeof(int32_t)) != hipSuccess
-        ||  (b->h_count = (int32_t *) malloc((size_t) n_channels*sizeof(int32_t))) == NULL)
+    if ((rc = counts_create(&b->c, &b->count, 1, 1)) != SPANGPU_OK)
     {
         spangpu_sigtone_rx_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the signalling tone bank failed");
+        return rc;
     }
     // memset(s, 0, sizeof(*s)) and last_sample_tone_present = -1 (sig_tone.c:690-704)
     int32_t one[kSigRxWords];
@@ -116,12 +111,11 @@ void spangpu_sigtone_rx_destroy(spangpu_sigtone_rx_t *b)
         return;
     core_destroy(&b->c);
     stage_free(&b->pcm);
-    (void) hipFree(b->d_lens);
-    if (b->h_lens) (void) hipHostFree(b->h_lens);
+    lens_free(&b->lens);
     (void) hipFree(b->events);
-    (void) hipFree(b->ev_count);
-    free(b->h_events);
-    free(b->h_count);
+    if (b->h_events)
+        (void) hipHostFree(b->h_events);
+    counts_free(&b->count);
     free(b);
 }
 
@@ -177,16 +171,16 @@ int spangpu_sigtone_rx(spangpu_sigtone_rx_t *b, int16_t *amp, int mem_kind, int 
     SPG_TRY(hipSetDevice(b->c.device));
     // a tone is declared after 3 ms of consistent detection and withdrawn after 8 ms (or at once in flat mode, which
     // takes 225 ms to enter): 24 samples between two reports at the very least
-    if ((rc = grow(&b->events, &b->ev_cap, 4 + samples/16, (size_t) b->c.n_ch*3, b->c.stream)) != SPANGPU_OK)
+    if ((rc = grow_pair(&b->events, &b->h_events, &b->ev_cap, 4 + samples/16, (size_t) b->c.n_ch*3, b->c.stream)) != SPANGPU_OK)
         return rc;
     SigRxLaunch L;
     memset(&L, 0, sizeof(L));
     L.st = b->c.st;
     L.events = b->events;
-    L.ev_count = b->ev_count;
+    L.ev_count = b->count.dev;
     L.n_ch = b->c.n_ch;
     L.samples = samples;
-    L.lens = b->next_lens;
+    L.lens = b->lens.next;
     L.ev_cap = b->ev_cap;
     L.flat_threshold = b->thresholds[0];
     L.sharp_threshold = b->thresholds[1];
@@ -215,35 +209,18 @@ int spangpu_sigtone_rx_var(spangpu_sigtone_rx_t *b, int16_t *amp, int mem_kind, 
 {
     if (b == NULL  ||  amp == NULL  ||  lens == NULL  ||  max_samples <= 0)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    int longest = 0;
-    bool all = true;
-    for (int c = 0;  c < b->c.n_ch;  c++)
-    {
-        if (lens[c] < 0  ||  lens[c] > max_samples)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
-        if (lens[c] > longest)
-            longest = lens[c];
-    }
-    if (longest == 0)
-        return SPANGPU_OK;
-    for (int c = 0;  c < b->c.n_ch;  c++)
-        all &= (lens[c] == longest);
+    int longest;
+    bool all;
+    int rc = lens_check(lens, b->c.n_ch, max_samples, &longest, &all);
+    // nobody brings a sample: no launch; everybody the same: the plain call
+    if (rc != SPANGPU_OK  ||  longest == 0)
+        return rc;
     if (stride <= 0)
         stride = max_samples;
-    if (all)
-        return spangpu_sigtone_rx(b, amp, mem_kind, longest, stride);
-    SPG_TRY(hipSetDevice(b->c.device));
-    if (b->d_lens == NULL)
-    {
-        SPG_TRY(hipMalloc(&b->d_lens, (size_t) b->c.n_ch*sizeof(int32_t)));
-        SPG_TRY(hipHostMalloc(&b->h_lens, (size_t) b->c.n_ch*sizeof(int32_t)));
-    }
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
-    memcpy(b->h_lens, lens, (size_t) b->c.n_ch*sizeof(int32_t));
-    SPG_TRY(hipMemcpyAsync(b->d_lens, b->h_lens, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, b->c.stream));
-    b->next_lens = b->d_lens;
-    const int rc = spangpu_sigtone_rx(b, amp, mem_kind, longest, stride);
-    b->next_lens = NULL;
+    if (!all  &&  (rc = lens_upload(&b->c, &b->lens, lens)) != SPANGPU_OK)
+        return rc;
+    rc = spangpu_sigtone_rx(b, amp, mem_kind, longest, stride);
+    b->lens.next = NULL;
     return rc;
 }
 
@@ -253,26 +230,17 @@ int spangpu_sigtone_rx_events(spangpu_sigtone_rx_t *b, const int32_t **events, c
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_sigtone_rx() yet");
-    SPG_TRY(hipSetDevice(b->c.device));
-    const size_t bytes = (size_t) b->c.n_ch*b->last_cap*3*sizeof(int32_t);
-    if (bytes > b->h_events_cap)
-    {
-        free(b->h_events);
-        b->h_events_cap = 0;
-        if ((b->h_events = (int32_t *) malloc(bytes)) == NULL)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host event buffer");
-        b->h_events_cap = bytes;
-    }
-    SPG_TRY(hipMemcpyAsync(b->h_events, b->events, bytes, hipMemcpyDeviceToHost, b->c.stream));
-    SPG_TRY(hipMemcpyAsync(b->h_count, b->ev_count, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
+    int rc = counts_fetch(&b->c, &b->count, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
+    int most;
+    if (!count_row_scan(b->count.pinned, b->c.n_ch, b->last_cap, &most))
+        return spangpu_set_error(SPANGPU_ERR_STATE, "a channel reported more often than the event buffer holds");
+    if ((rc = rows_fetch(&b->c, b->h_events, b->events, 3*sizeof(int32_t), b->last_cap, most)) != SPANGPU_OK)
+        return rc;
     SPG_TRY(hipStreamSynchronize(b->c.stream));
-    for (int c = 0;  c < b->c.n_ch;  c++)
-    {
-        if (b->h_count[c] > b->last_cap)
-            return spangpu_set_error(SPANGPU_ERR_STATE, "a channel reported more often than the event buffer holds");
-    }
     *events = b->h_events;
-    *counts = b->h_count;
+    *counts = b->count.pinned;
     return b->last_cap;
 }
 

@@ -29,15 +29,12 @@ struct spangpu_v18_s
     int16_t *quarter;
     uint8_t *ring;
     uint8_t *tables;
-    int32_t *d_rxlens;          // [n_ch]: per-channel lengths of an rx_var call
-    int32_t *h_rxlens;          // pinned
-    uint8_t *chars;
-    int32_t *counts;
+    VarLens rxlens;             // per-channel lengths of an rx_var call
+    uint8_t *chars;             // [n_ch][last_cap]
+    uint8_t *h_chars;
+    CountRows counts;
     int cap;
     int last_cap;
-    uint8_t *h_chars;
-    int32_t *h_counts;
-    size_t h_chars_cap;
     uint8_t *d_text;
     int32_t *d_tlens;
     int32_t *d_res;
@@ -139,16 +136,14 @@ void spangpu_v18_destroy(spangpu_v18_t *b)
     (void) hipFree(b->quarter);
     (void) hipFree(b->ring);
     (void) hipFree(b->tables);
-    (void) hipFree(b->d_rxlens);
-    if (b->h_rxlens)
-        (void) hipHostFree(b->h_rxlens);
+    lens_free(&b->rxlens);
     (void) hipFree(b->chars);
-    (void) hipFree(b->counts);
+    if (b->h_chars)
+        (void) hipHostFree(b->h_chars);
+    counts_free(&b->counts);
     (void) hipFree(b->d_text);
     (void) hipFree(b->d_tlens);
     (void) hipFree(b->d_res);
-    free(b->h_chars);
-    free(b->h_counts);
     free(b);
 }
 
@@ -180,11 +175,10 @@ int spangpu_v18_create(spangpu_v18_t **out, int device, int n_channels, const in
     const size_t words = (size_t) n_words*n;
     int32_t *one = (int32_t *) calloc(n_words, sizeof(int32_t));
     int32_t *host = (int32_t *) calloc(words, sizeof(int32_t));
-    b->h_counts = (int32_t *) malloc(n*sizeof(int32_t));
-    if (one == NULL  ||  host == NULL  ||  b->h_counts == NULL
+    if (one == NULL  ||  host == NULL
         ||  hipMalloc(&b->ring, n*kV18Ring) != hipSuccess
         ||  hipMalloc(&b->tables, 192) != hipSuccess
-        ||  hipMalloc(&b->counts, n*sizeof(int32_t)) != hipSuccess)
+        ||  counts_create(&b->c, &b->counts, 1, 1) != SPANGPU_OK)
     {
         free(one);
         free(host);
@@ -309,11 +303,11 @@ int spangpu_v18_text_capacity(const spangpu_v18_t *b, int samples)
     return (int) ((long long) samples*b->max_baud/(800000LL*7)) + 2;
 }
 
-static int rx_launch(spangpu_v18_s *b, const int16_t *amp, int mem_kind, int samples, long long stride, const int32_t *d_lens)
+static int rx_launch(spangpu_v18_s *b, const int16_t *amp, int mem_kind, int samples, long long stride)
 {
     SPG_TRY(hipSetDevice(b->c.device));
     const int cap = spangpu_v18_text_capacity(b, samples);
-    int rc = grow(&b->chars, &b->cap, cap, (size_t) b->c.n_ch, b->c.stream);
+    int rc = grow_pair(&b->chars, &b->h_chars, &b->cap, cap, (size_t) b->c.n_ch, b->c.stream);
     if (rc != SPANGPU_OK)
         return rc;
     V18RxLaunch V;
@@ -323,7 +317,7 @@ static int rx_launch(spangpu_v18_s *b, const int16_t *amp, int mem_kind, int sam
     L.quarter = b->quarter;
     L.n_ch = b->c.n_ch;
     L.samples = samples;
-    L.lens = d_lens;
+    L.lens = b->rxlens.next;
     L.span = b->span;
     // the caller's buffer is only borrowed for the call: the copy in is waited for
     if ((rc = stage_in(&b->c, &b->pcm, mem_kind, amp, stride, samples, true, &L.pcm, &L.stride, &L.vec)) != SPANGPU_OK)
@@ -331,7 +325,7 @@ static int rx_launch(spangpu_v18_s *b, const int16_t *amp, int mem_kind, int sam
     V.sv = b->c.st;
     V.tables = b->tables;
     V.chars = b->chars;
-    V.counts = b->counts;
+    V.counts = b->counts.dev;
     V.cap = cap;
     const size_t lds = (size_t) (4*b->span*64 + 2*kFskMsgWords*64)*sizeof(int32_t);
     hipLaunchKernelGGL(v18_rx_kernel, dim3((b->c.n_ch + 63)/64), dim3(128), lds, b->c.stream, V);
@@ -347,7 +341,7 @@ int spangpu_v18_rx(spangpu_v18_t *b, const int16_t *amp, int mem_kind, int sampl
     const int rc = rx_args_ok(b, mem_kind, amp, samples, &stride);
     if (rc != SPANGPU_OK)
         return rc;
-    return rx_launch(b, amp, mem_kind, samples, stride, NULL);
+    return rx_launch(b, amp, mem_kind, samples, stride);
 }
 
 // spangpu_v18_rx() for a tick in which not every channel has a frame, or frames differ in length: channel c takes lens[c]
@@ -358,25 +352,21 @@ int spangpu_v18_rx_var(spangpu_v18_t *b, const int16_t *amp, int mem_kind, const
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (mem_kind != SPANGPU_MEM_HOST  &&  mem_kind != SPANGPU_MEM_DEVICE)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad mem kind");
-    for (int c = 0;  c < b->c.n_ch;  c++)
-    {
-        if (lens[c] < 0  ||  lens[c] > max_samples)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a channel's length is outside 0..max_samples");
-    }
+    int longest;
+    bool all;
+    int rc = lens_check(lens, b->c.n_ch, max_samples, &longest, &all);
+    if (rc != SPANGPU_OK)
+        return rc;
     if (stride <= 0)
         stride = max_samples;
     if (stride < max_samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "stride < max_samples");
-    SPG_TRY(hipSetDevice(b->c.device));
-    if (b->d_rxlens == NULL)
-    {
-        SPG_TRY(hipMalloc(&b->d_rxlens, (size_t) b->c.n_ch*sizeof(int32_t)));
-        SPG_TRY(hipHostMalloc(&b->h_rxlens, (size_t) b->c.n_ch*sizeof(int32_t)));
-    }
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
-    memcpy(b->h_rxlens, lens, (size_t) b->c.n_ch*sizeof(int32_t));
-    SPG_TRY(hipMemcpyAsync(b->d_rxlens, b->h_rxlens, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyHostToDevice, b->c.stream));
-    return rx_launch(b, amp, mem_kind, max_samples, stride, b->d_rxlens);
+    // always a launch of max_samples with the lengths: a call nobody takes part in leaves an empty record
+    if ((rc = lens_upload(&b->c, &b->rxlens, lens)) != SPANGPU_OK)
+        return rc;
+    rc = rx_launch(b, amp, mem_kind, max_samples, stride);
+    b->rxlens.next = NULL;
+    return rc;
 }
 
 int spangpu_v18_text(spangpu_v18_t *b, const uint8_t **chars, const int32_t **counts)
@@ -385,27 +375,18 @@ int spangpu_v18_text(spangpu_v18_t *b, const uint8_t **chars, const int32_t **co
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     if (b->last_cap <= 0)
         return spangpu_set_error(SPANGPU_ERR_STATE, "no spangpu_v18_rx() yet");
-    SPG_TRY(hipSetDevice(b->c.device));
-    const size_t bytes = (size_t) b->c.n_ch*b->last_cap;
-    if (bytes > b->h_chars_cap)
-    {
-        free(b->h_chars);
-        b->h_chars_cap = 0;
-        if ((b->h_chars = (uint8_t *) malloc(bytes)) == NULL)
-            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "host text records");
-        b->h_chars_cap = bytes;
-    }
-    SPG_TRY(hipMemcpyAsync(b->h_chars, b->chars, bytes, hipMemcpyDeviceToHost, b->c.stream));
-    SPG_TRY(hipMemcpyAsync(b->h_counts, b->counts, (size_t) b->c.n_ch*sizeof(int32_t), hipMemcpyDeviceToHost, b->c.stream));
-    SPG_TRY(hipStreamSynchronize(b->c.stream));
+    int rc = counts_fetch(&b->c, &b->counts, 1);
+    if (rc != SPANGPU_OK)
+        return rc;
     // the record is sized from the frame format; a count above it would mean the sizing is wrong, and is not cut short quietly
-    for (int c = 0;  c < b->c.n_ch;  c++)
-    {
-        if (b->h_counts[c] > b->last_cap)
-            return spangpu_set_error(SPANGPU_ERR_STATE, "a channel decoded more characters than a call of this length can carry");
-    }
+    int most;
+    if (!count_row_scan(b->counts.pinned, b->c.n_ch, b->last_cap, &most))
+        return spangpu_set_error(SPANGPU_ERR_STATE, "a channel decoded more characters than a call of this length can carry");
+    if ((rc = rows_fetch(&b->c, b->h_chars, b->chars, 1, b->last_cap, most)) != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
     *chars = b->h_chars;
-    *counts = b->h_counts;
+    *counts = b->counts.pinned;
     return b->last_cap;
 }
 

@@ -1468,8 +1468,79 @@ def v17_signal_space():
     return {"v17_constellation": buf, "v17_maps": maps, "v17_map_4800": m48}
 
 
-class ModemBank:
+def _rows(ptr, ctype, counts_ptr, n, cap, width=1):
+    """Per channel: the first counts[c] of the cap entries (width elements of ctype each) the library holds for it at ptr."""
+    counts = np.ctypeslib.as_array(C.cast(counts_ptr, C.POINTER(C.c_int32)), (n,))
+    assert counts.max(initial=0) <= cap, "result buffer overflow"
+    flat = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (n*cap*width,)).reshape((n, cap) + ((width,) if width > 1 else ()))
+    return [flat[c, :counts[c]].copy() for c in range(n)]
+
+
+def _frames_of(recs, octets):
+    """Per channel: [(len, ok, bytes) for a frame | code < 0 for a status], in call order, from its records and its octets."""
+    out = []
+    for rc, by in zip(recs, octets):
+        at, row = 0, []
+        for r in rc:
+            r = int(r)
+            if r < 0:
+                row.append(r)
+            else:
+                n = r & 0xFFFF
+                row.append((n, bool(r & HDLC_FRAME_OK), by[at:at + n].tobytes()))
+                at += n
+        assert at == len(by)
+        out.append(row)
+    return out
+
+
+class _Bank:
+    """What every bank named spangpu_<_prefix>_* shares: the handle's life, its stream."""
+    _prefix = None
+
+    def _f(self, name):
+        return getattr(lib(), "spangpu_%s_%s" % (self._prefix, name))
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        _check(self._f("set_stream")(self.h, hip_stream))
+
+    def sync(self):
+        _check(self._f("sync")(self.h))
+
+
+class _ReceiverBank(_Bank):
+    """What the receiver banks share: one call of every channel over host or device rows, whole or with per-channel lengths."""
+
+    def rx_host(self, amp):
+        amp = np.ascontiguousarray(amp, np.int16)
+        assert amp.shape[0] == self.n
+        _check(self._f("rx")(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
+
+    def rx_device(self, ptr, samples, stride=0):
+        _check(self._f("rx")(self.h, ptr, MEM_DEVICE, samples, stride))
+
+    def rx_host_var(self, amp, lens):
+        """A tick with per-channel frame lengths (0 = the receiver sits it out, untouched)."""
+        amp = np.ascontiguousarray(amp, np.int16)
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert amp.shape[0] == self.n and lens.shape == (self.n,)
+        _check(self._f("rx_var")(self.h, amp.ctypes.data, MEM_HOST, lens.ctypes.data, amp.shape[1], amp.shape[1]))
+
+
+class ModemBank(_ReceiverBank):
     """N modem receivers of one kind and bit rate, state resident in HBM."""
+    _prefix = "modem"
 
     def __init__(self, kind, n_channels, bit_rate, device=0):
         self.n = n_channels
@@ -1481,41 +1552,9 @@ class ModemBank:
         self.h = C.c_void_p()
         _check(lib().spangpu_modem_create(C.byref(self.h), device, kind, n_channels, bit_rate))
 
-    def close(self):
-        if self.h:
-            lib().spangpu_modem_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream):
-        _check(lib().spangpu_modem_set_stream(self.h, hip_stream))
-
     def get_stream(self):
         """the hipStream_t the bank launches on, as an integer"""
         return lib().spangpu_modem_get_stream(self.h) or 0
-
-    def sync(self):
-        _check(lib().spangpu_modem_sync(self.h))
-
-    def rx_host(self, frames):
-        frames = np.ascontiguousarray(frames, np.int16)
-        assert frames.shape[0] == self.n
-        _check(lib().spangpu_modem_rx(self.h, frames.ctypes.data, MEM_HOST, frames.shape[1], frames.shape[1]))
-
-    def rx_device(self, ptr, samples, stride):
-        _check(lib().spangpu_modem_rx(self.h, ptr, MEM_DEVICE, samples, stride))
-
-    def rx_host_var(self, frames, lens):
-        """A tick with per-channel frame lengths (0 = the receiver sits it out, untouched)."""
-        frames = np.ascontiguousarray(frames, np.int16)
-        lens = np.ascontiguousarray(lens, np.int32)
-        assert frames.shape[0] == self.n and lens.shape == (self.n,)
-        _check(lib().spangpu_modem_rx_var(self.h, frames.ctypes.data, MEM_HOST, lens.ctypes.data, frames.shape[1], frames.shape[1]))
 
     def events(self, packed=False):
         """List (per channel) of int8 arrays: 0/1 bits and negative SIG_STATUS codes, in order.  packed: by way of the
@@ -1524,10 +1563,7 @@ class ModemBank:
         cnt = C.c_void_p()
         fn = lib().spangpu_modem_events_packed if packed else lib().spangpu_modem_events
         cap = _check(fn(self.h, C.byref(ev), C.byref(cnt)))
-        counts = np.frombuffer((C.c_char*(4*self.n)).from_address(cnt.value), dtype=np.int32).copy()
-        raw = np.frombuffer((C.c_char*(cap*self.n)).from_address(ev.value), dtype=np.int8).reshape(self.n, cap)
-        assert counts.max(initial=0) <= cap, "event buffer overflow"
-        return [raw[c, :counts[c]].copy() for c in range(self.n)]
+        return _rows(ev, C.c_int8, cnt, self.n, cap)
 
     def copy_events(self, dst_ptr, nbytes, per_channel):
         """The last call's events, device to device: int32 counts[n_ch] then int8 events[n_ch][per_channel]."""
@@ -1542,10 +1578,7 @@ class ModemBank:
         rec = C.c_void_p()
         cnt = C.c_void_p()
         cap = _check(lib().spangpu_modem_qam_reports(self.h, C.byref(rec), C.byref(cnt)))
-        counts = np.frombuffer((C.c_char*(4*self.n)).from_address(cnt.value), dtype=np.int32).copy()
-        raw = np.frombuffer((C.c_char*(28*cap*self.n)).from_address(rec.value), dtype=np.uint32).reshape(self.n, cap, 7)
-        assert counts.max(initial=0) <= cap, "report buffer overflow"
-        return [raw[c, :counts[c]].copy() for c in range(self.n)]
+        return _rows(rec, C.c_uint32, cnt, self.n, cap, 7)
 
     def get_state(self, channel):
         w = np.zeros(self.n_words, np.uint32)
@@ -1686,8 +1719,9 @@ def fsk_preset(which):
     return sp
 
 
-class FskBank:
+class FskBank(_ReceiverBank):
     """N FSK receivers of one spec (fsk_rx), state in HBM."""
+    _prefix = "fsk"
 
     def __init__(self, spec, n_channels, framing_mode=FSK_FRAME_MODE_SYNC, device=0):
         self.spec = fsk_preset(spec) if isinstance(spec, int) else spec
@@ -1696,46 +1730,12 @@ class FskBank:
         _check(lib().spangpu_fsk_create(C.byref(self.h), device, n_channels, C.byref(self.spec), framing_mode))
         self.words = lib().spangpu_fsk_state_words(self.h)
 
-    def close(self):
-        if self.h:
-            lib().spangpu_fsk_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream):
-        _check(lib().spangpu_fsk_set_stream(self.h, hip_stream))
-
-    def sync(self):
-        _check(lib().spangpu_fsk_sync(self.h))
-
-    def rx_host(self, amp):
-        amp = np.ascontiguousarray(amp, np.int16)
-        assert amp.shape[0] == self.n
-        _check(lib().spangpu_fsk_rx(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
-
-    def rx_device(self, ptr, samples, stride=0):
-        _check(lib().spangpu_fsk_rx(self.h, ptr, MEM_DEVICE, samples, stride))
-
-    def rx_host_var(self, amp, lens):
-        """A tick with per-channel frame lengths (0 = the receiver sits it out, untouched)."""
-        amp = np.ascontiguousarray(amp, np.int16)
-        lens = np.ascontiguousarray(lens, np.int32)
-        _check(lib().spangpu_fsk_rx_var(self.h, amp.ctypes.data, MEM_HOST, lens.ctypes.data, amp.shape[1], amp.shape[1]))
-
     def events(self):
         """Per channel: the int16 put_bit() values of the last frame, in order."""
         ev = C.c_void_p()
         cnt = C.c_void_p()
         cap = _check(lib().spangpu_fsk_events(self.h, C.byref(ev), C.byref(cnt)))
-        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,)).copy()
-        assert counts.max(initial=0) <= cap
-        flat = np.ctypeslib.as_array(C.cast(ev, C.POINTER(C.c_int16)), (self.n*cap,)).reshape(self.n, cap)
-        return [flat[c, :counts[c]].copy() for c in range(self.n)]
+        return _rows(ev, C.c_int16, cnt, self.n, cap)
 
     def copy_events(self, dst_ptr, nbytes, per_channel):
         """The last call's events device to device: int32 counts[n], int16 events[n][per_channel]."""
@@ -1769,8 +1769,9 @@ class FskBank:
  MCT_BELL_ANS, MCT_CALLING_TONE) = range(10)
 
 
-class MctBank:
+class MctBank(_ReceiverBank):
     """N modem connect tone detectors of one tone type (modem_connect_tones_rx), state in HBM."""
+    _prefix = "mct"
 
     def __init__(self, tone_type, n_channels, use_callback=True, device=0):
         self.n = n_channels
@@ -1778,46 +1779,12 @@ class MctBank:
         _check(lib().spangpu_mct_create(C.byref(self.h), device, tone_type, n_channels, int(use_callback)))
         self.words = lib().spangpu_mct_state_words(self.h)
 
-    def close(self):
-        if self.h:
-            lib().spangpu_mct_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream):
-        _check(lib().spangpu_mct_set_stream(self.h, hip_stream))
-
-    def sync(self):
-        _check(lib().spangpu_mct_sync(self.h))
-
-    def rx_host(self, amp):
-        amp = np.ascontiguousarray(amp, np.int16)
-        assert amp.shape[0] == self.n
-        _check(lib().spangpu_mct_rx(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
-
-    def rx_device(self, ptr, samples, stride=0):
-        _check(lib().spangpu_mct_rx(self.h, ptr, MEM_DEVICE, samples, stride))
-
-    def rx_host_var(self, amp, lens):
-        """A tick with per-channel frame lengths (0 = the detector sits it out, untouched)."""
-        amp = np.ascontiguousarray(amp, np.int16)
-        lens = np.ascontiguousarray(lens, np.int32)
-        _check(lib().spangpu_mct_rx_var(self.h, amp.ctypes.data, MEM_HOST, lens.ctypes.data, amp.shape[1], amp.shape[1]))
-
     def events(self):
         """Per channel: [k, 2] int32 (tone, level) reports of the last frame, in order."""
         ev = C.c_void_p()
         cnt = C.c_void_p()
         cap = _check(lib().spangpu_mct_events(self.h, C.byref(ev), C.byref(cnt)))
-        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,)).copy()
-        assert counts.max(initial=0) <= cap
-        flat = np.ctypeslib.as_array(C.cast(ev, C.POINTER(C.c_int32)), (self.n*cap*2,)).reshape(self.n, cap, 2)
-        return [flat[c, :counts[c]].copy() for c in range(self.n)]
+        return _rows(ev, C.c_int32, cnt, self.n, cap, 2)
 
     def get(self, channel):
         return _check(lib().spangpu_mct_get(self.h, channel))
@@ -1847,29 +1814,8 @@ def fsktx_bits_due(baud_rate, baud_frac, samples):
     return _check(lib().spangpu_fsktx_bits_due(baud_rate, baud_frac, samples))
 
 
-class _SenderBank:
+class _SenderBank(_Bank):
     """What FskTxBank and MctTxBank share: one call of every channel into host or device rows."""
-    _prefix = None
-
-    def _f(self, name):
-        return getattr(lib(), "spangpu_%s_%s" % (self._prefix, name))
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream):
-        _check(self._f("set_stream")(self.h, hip_stream))
-
-    def sync(self):
-        _check(self._f("sync")(self.h))
 
     def tx_host(self, samples):
         pcm = np.zeros((self.n, max(1, samples)), np.int16)
@@ -1990,7 +1936,7 @@ def baudot_decode(codes, shift_state=0):
     return out[:k].tobytes(), st.value
 
 
-class V18Bank(_SenderBank):
+class V18Bank(_SenderBank, _ReceiverBank):
     """N Baudot text telephones (v18_put / v18_tx / v18_rx in a Weitbrecht mode, no automoding), state in HBM."""
     _prefix = "v18"
 
@@ -2015,20 +1961,6 @@ class V18Bank(_SenderBank):
         _check(lib().spangpu_v18_put(self.h, first, n, buf.ctypes.data, stride, lens.ctypes.data, res.ctypes.data))
         return res
 
-    def rx_host(self, amp):
-        amp = np.ascontiguousarray(amp, np.int16)
-        assert amp.shape[0] == self.n
-        _check(lib().spangpu_v18_rx(self.h, amp.ctypes.data, MEM_HOST, amp.shape[1], amp.shape[1]))
-
-    def rx_device(self, ptr, samples, stride=0):
-        _check(lib().spangpu_v18_rx(self.h, ptr, MEM_DEVICE, samples, stride))
-
-    def rx_host_var(self, amp, lens):
-        amp = np.ascontiguousarray(amp, np.int16)
-        lens = np.ascontiguousarray(lens, np.int32)
-        assert amp.shape[0] == self.n and len(lens) == self.n
-        _check(lib().spangpu_v18_rx_var(self.h, amp.ctypes.data, MEM_HOST, lens.ctypes.data, amp.shape[1], amp.shape[1]))
-
     def fillin(self, channel, n):
         _check(lib().spangpu_v18_fillin(self.h, channel, n))
 
@@ -2037,9 +1969,7 @@ class V18Bank(_SenderBank):
         ch = C.c_void_p()
         cnt = C.c_void_p()
         cap = _check(lib().spangpu_v18_text(self.h, C.byref(ch), C.byref(cnt)))
-        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,)).copy()
-        flat = np.ctypeslib.as_array(C.cast(ch, C.POINTER(C.c_uint8)), (self.n*cap,)).reshape(self.n, cap)
-        return [flat[c, :counts[c]].tobytes() for c in range(self.n)]
+        return [t.tobytes() for t in _rows(ch, C.c_uint8, cnt, self.n, cap)]
 
     def text_capacity(self, samples):
         return _check(lib().spangpu_v18_text_capacity(self.h, samples))
@@ -2194,14 +2124,9 @@ class AdsiRxBank(_SenderBank):
         """Per channel: the messages the last rx call delivered, in order, as bytes."""
         by, ln, cnt = C.c_void_p(), C.c_void_p(), C.c_void_p()
         cap = _check(lib().spangpu_adsi_rx_messages(self.h, C.byref(by), C.byref(ln), C.byref(cnt)))
-        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,))
-        out = [[] for _ in range(self.n)]
-        if counts.any():
-            lens = np.ctypeslib.as_array(C.cast(ln, C.POINTER(C.c_int32)), (self.n*cap,)).reshape(self.n, cap)
-            flat = np.ctypeslib.as_array(C.cast(by, C.POINTER(C.c_uint8)), (self.n*cap*ADSI_MSG_BYTES,)).reshape(self.n, cap, ADSI_MSG_BYTES)
-            for c in np.nonzero(counts)[0]:
-                out[c] = [flat[c, k, :lens[c, k]].tobytes() for k in range(counts[c])]
-        return out
+        lens = _rows(ln, C.c_int32, cnt, self.n, cap)
+        msgs = _rows(by, C.c_uint8, cnt, self.n, cap, ADSI_MSG_BYTES)
+        return [[m[:k].tobytes() for m, k in zip(msgs[c], lens[c])] for c in range(self.n)]
 
     def msg_capacity(self, samples):
         return _check(lib().spangpu_adsi_rx_msg_capacity(self.h, samples))
@@ -2314,23 +2239,7 @@ class HdlcRxBank(_HdlcBank):
         rp, cp, bp = C.c_void_p(), C.c_void_p(), C.c_void_p()
         rec_cap = _check(lib().spangpu_hdlc_rx_records(self.h, C.byref(rp), C.byref(cp), C.byref(bp)))
         byte_cap = hdlc_rx_capacity(self._entries)[1]
-        counts = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (2*self.n,))
-        out = [[] for _ in range(self.n)]
-        if counts[:self.n].any():
-            recs = np.ctypeslib.as_array(C.cast(rp, C.POINTER(C.c_int32)), (self.n*rec_cap,)).reshape(self.n, rec_cap)
-            by = np.ctypeslib.as_array(C.cast(bp, C.POINTER(C.c_uint8)), (self.n*byte_cap,)).reshape(self.n, byte_cap)
-            for c in np.nonzero(counts[:self.n])[0]:
-                at = 0
-                for r in recs[c, :counts[c]]:
-                    r = int(r)
-                    if r < 0:
-                        out[c].append(r)
-                    else:
-                        n = r & 0xFFFF
-                        out[c].append((n, bool(r & HDLC_FRAME_OK), by[c, at:at + n].tobytes()))
-                        at += n
-                assert at == counts[self.n + c]
-        return out
+        return _frames_of(_rows(rp, C.c_int32, cp, self.n, rec_cap), _rows(bp, C.c_uint8, C.c_void_p(cp.value + 4*self.n), self.n, byte_cap))
 
     def set_octet_counting_report_interval(self, channel, interval):
         _check(lib().spangpu_hdlc_rx_set_octet_counting_report_interval(self.h, channel, interval))
@@ -2490,28 +2399,16 @@ class FaxFrontEnd:
 
     def frames(self):
         """Per channel: [(len, ok, bytes) for an hdlc_accept call with a frame | code < 0 for one with a status], in call order."""
-        recs, nrecs, by, nbytes = self.frames_raw()
-        out = [[] for _ in range(self.n)]
-        for c in np.nonzero(nrecs)[0]:
-            at = 0
-            for r in recs[c, :nrecs[c]]:
-                r = int(r)
-                if r < 0:
-                    out[c].append(r)
-                else:
-                    k = r & 0xFFFF
-                    out[c].append((k, bool(r & HDLC_FRAME_OK), by[c, at:at + k].tobytes()))
-                    at += k
-            assert at == nbytes[c]
-        return out
+        rp, cp, bp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rec_cap = _check(lib().spangpu_faxfe_frames(self.h, C.byref(rp), C.byref(cp), C.byref(bp)))
+        byte_cap = self.capacities()[1]
+        return _frames_of(_rows(rp, C.c_int32, cp, self.n, rec_cap), _rows(bp, C.c_uint8, C.c_void_p(cp.value + 4*self.n), self.n, byte_cap))
 
     def put_bits(self):
         """Per channel: the int8 values of the last tick's non-ECM put_bit calls, in order."""
         ep, cp = C.c_void_p(), C.c_void_p()
         cap = _check(lib().spangpu_faxfe_put_bits(self.h, C.byref(ep), C.byref(cp)))
-        counts = np.ctypeslib.as_array(C.cast(cp, C.POINTER(C.c_int32)), (self.n,))
-        ev = np.ctypeslib.as_array(C.cast(ep, C.POINTER(C.c_int8)), (self.n*cap,)).reshape(self.n, cap)
-        return [ev[c, :counts[c]].copy() for c in range(self.n)]
+        return _rows(ep, C.c_int8, cp, self.n, cap)
 
     def handlers(self):
         """(handler [n], rx_frame_received [n])"""
@@ -2569,31 +2466,15 @@ SIG_TONE_TX_PASSTHROUGH, SIG_TONE_RX_PASSTHROUGH, SIG_TONE_RX_FILTER_TONE = 0x01
 SIG_TONE_TX_UPDATE_REQUEST = 0x100
 
 
-class SigToneRxBank:
+class SigToneRxBank(_ReceiverBank):
     """N in-band signalling tone receivers of one tone type (sig_tone_rx), state in HBM; frames are rewritten in place."""
+    _prefix = "sigtone_rx"
 
     def __init__(self, tone_type, n_channels, device=0):
         self.n = n_channels
         self.h = C.c_void_p()
         _check(lib().spangpu_sigtone_rx_create(C.byref(self.h), device, tone_type, n_channels))
         self.words = lib().spangpu_sigtone_rx_state_words(self.h)
-
-    def close(self):
-        if self.h:
-            lib().spangpu_sigtone_rx_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_stream(self, hip_stream):
-        _check(lib().spangpu_sigtone_rx_set_stream(self.h, hip_stream))
-
-    def sync(self):
-        _check(lib().spangpu_sigtone_rx_sync(self.h))
 
     def set_mode(self, mode, channel=-1):
         _check(lib().spangpu_sigtone_rx_set_mode(self.h, channel, mode))
@@ -2620,9 +2501,7 @@ class SigToneRxBank:
         ev = C.c_void_p()
         cnt = C.c_void_p()
         cap = _check(lib().spangpu_sigtone_rx_events(self.h, C.byref(ev), C.byref(cnt)))
-        counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_int32)), (self.n,)).copy()
-        flat = np.ctypeslib.as_array(C.cast(ev, C.POINTER(C.c_int32)), (self.n*cap*3,)).reshape(self.n, cap, 3)
-        return [flat[c, :counts[c]].copy() for c in range(self.n)]
+        return _rows(ev, C.c_int32, cnt, self.n, cap, 3)
 
     def get_state(self, channel):
         w = np.zeros(self.words, np.int32)
