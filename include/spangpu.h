@@ -1046,9 +1046,9 @@ SPANGPU_API int spangpu_hdlc_tx_set_buffer(spangpu_hdlc_tx_t *bank, int channel,
  * The record and octet capacities are spangpu_hdlc_rx_capacity() of the two rows' capacities added; a list that did not fit,
  * or a receiver's row that did not, is an error of spangpu_faxfe_frames() / _put_bits() (SPANGPU_ERR_STATE), never cut short.
  *
- * Not here: the transmit half of fax_modems (silence_gen, the next-handler chain), the CED / CNG tone receive handlers,
- * the xxx_rx_fillin handlers, fax_modems_set_rx_active() and deferred handler updates, V.34, and the fax_modems_* calls by
- * name (t30.c and fax.c reach into the struct: banks are the form, as for HDLC).
+ * Not here: the CED / CNG tone receive handlers, the xxx_rx_fillin handlers, fax_modems_set_rx_active() and deferred handler
+ * updates, V.34, and the fax_modems_* calls by name (t30.c and fax.c reach into the struct: banks are the form, as for HDLC).
+ * The transmit half is a bank family of its own: "FAX transmit front-end banks" below.
  */
 typedef struct spangpu_faxfe_s spangpu_faxfe_t;
 
@@ -1259,6 +1259,143 @@ SPANGPU_API int spangpu_modemtx_state_words(void);
 SPANGPU_API int spangpu_modemtx_get_state(spangpu_modemtx_t *tx, int channel, int32_t *words);
 /* The pulse shaper tables as built by this library (host code): which = 0 V.29, 1 V.27ter 4800 bps, 2 V.27ter 2400 bps */
 SPANGPU_API int spangpu_modemtx_table(int which, float *out, int max);
+/* The sender banks' calls below are named spangpu_txline_* and spangpu_txspans_* and not after their banks (spangpu_modemtx_*,
+   spangpu_fsktx_*, spangpu_mcttx_*): tests/test_modemtx_cursor.py and tests/test_fsktx_abi.py pin how many names of those three
+   prefixes this header holds, and existing tests stay as they are.
+   A channel's words back (checked where they index a table), and the bit ring of a channel of a queue-sourced bank:
+   ring_words() words -- read position, fill, the end-of-data flag, then the ring -- read (write 0) or written (write 1). */
+SPANGPU_API int spangpu_txline_modem_set_state(spangpu_modemtx_t *tx, int channel, const int32_t *words);
+SPANGPU_API int spangpu_txline_modem_ring_words(const spangpu_modemtx_t *tx);
+SPANGPU_API int spangpu_txline_modem_ring_rw(spangpu_modemtx_t *tx, int channel, int32_t *words, int write);
+/* xxx_tx_init() of one channel: the words spangpu_modemtx_create_ex() gives a channel, at this rate and TEP, and an empty ring */
+SPANGPU_API int spangpu_txline_modem_init(spangpu_modemtx_t *tx, int channel, int bit_rate, int tep);
+SPANGPU_API int spangpu_txline_fsk_set_state(spangpu_fsktx_t *tx, int channel, const int32_t *words);
+SPANGPU_API int spangpu_txline_mct_set_state(spangpu_mcttx_t *tx, int channel, const int32_t *words);
+
+/* ---- Sender banks over per-channel spans (csrc/txspan_dev.hpp) ----------------------------------
+ * One xxx_tx() call per channel into row[start .. start + count) of a [channel][stride] buffer in device memory, with start,
+ * count and a sender id per channel read from device memory: spans_dev[0][c] start, [1][c] count, [2][c] sender id (a fourth
+ * row is the planner's own), each row n_channels long.  A channel whose id is not `sender`, or whose count is 0, sits the
+ * launch out: its state and its row stay untouched.  ret_dev[c] is what the channel's call returned; it is written for the
+ * channels that ran.  Spans are bounded to the row.  Nothing is waited for: asynchronous on the bank's stream.
+ * The FSK sender's get_bit is hdlc_tx_get_bit() on `framer`'s channel of the same number, called where fsk_tx() calls it; a
+ * modem sender's too where hdlc_mode_dev[c] is set, and the bank's ring (with its end-of-data flag) where it is not.  The
+ * framer's queue is offered at the top of the span.  counts_dev[0][c] / [1][c]: the underflow handler calls of the span, and
+ * how many of them found the queue empty.  The framer runs on the same stream as the sender.
+ */
+SPANGPU_API int spangpu_txspans_modem(spangpu_modemtx_t *tx, int16_t *pcm_dev, long long stride, int samples, const int32_t *spans_dev,
+                                             int sender, int32_t *ret_dev, spangpu_hdlc_tx_t *framer, const int32_t *hdlc_mode_dev,
+                                             int32_t *counts_dev);
+SPANGPU_API int spangpu_txspans_fsk(spangpu_fsktx_t *tx, int16_t *pcm_dev, long long stride, int samples, const int32_t *spans_dev,
+                                           int sender, int32_t *ret_dev, spangpu_hdlc_tx_t *framer, int32_t *counts_dev);
+SPANGPU_API int spangpu_txspans_mct(spangpu_mcttx_t *tx, int16_t *pcm_dev, long long stride, int samples, const int32_t *spans_dev,
+                                           int sender, int32_t *ret_dev);
+
+/* ---- FAX transmit front-end banks (csrc/faxtx_api.hip, csrc/faxtx_dev.hpp) ---------------------
+ * The transmit half of N fax_modems_state_t objects, driven as fax.c drives it: the silence generator in front of a sender,
+ * the change of handler in the middle of a block, hdlc_tx_get_bit() as the modulators' get_bit, and the
+ * T30_FRONT_END_SEND_STEP_COMPLETE reports -- all per channel on the device.  The bank's own arithmetic is integer: every
+ * sample and every report equals the reference's wherever the inner senders' do.
+ *
+ *   spangpu_faxtx_create()             fax_modems_init(): transmit side                               src/fax_modems.c:618-677
+ *                                      hdlc_tx_init(CRC-16, 2 flags between frames), silence_gen_init(0); silence_gen
+ *                                      installed, transmit false, current_tx_type 0, fast_modem 0
+ *   spangpu_faxtx_set_tx_type()        fax_set_tx_type(), type a SPANGPU_T30_MODEM_*                  src/fax.c:327-421
+ *                                      nothing when type == current_tx_type                           :347-349
+ *                                      PAUSE: silence_gen_alter(short_train ms) -- it adds to what     :352-357,
+ *                                      remains                                                        src/silence_gen.c:96-108
+ *                                      CED / CNG: modem_connect_tones_tx_init(), the tone installed,  :358-364
+ *                                      no next handler
+ *                                      V21: fsk_tx_init(), hdlc_tx_flags(32), 75 ms of silence with   :365-377
+ *                                      fsk_tx as the next handler
+ *                                      V17 / V27TER / V29: 75 ms, hdlc_tx_flags(bit_rate/40), then    :378-404
+ *                                        fax_modems_start_fast_modem(): xxx_tx_init() and short_train src/fax_modems.c:402-447,
+ *                                        cleared when fast_modem differs, else xxx_tx_restart() (V.17 :448-510
+ *                                        with short_train)
+ *                                      DONE and the rest: silence of 0, transmit false                :405-414
+ *   spangpu_faxtx_restart()            fax_modems_restart(): current_tx_type = -1                     src/fax_modems.c:611-615
+ *   spangpu_faxtx_set_tep_mode()       fax_modems_set_tep_mode()                                      src/fax_modems.c:599-602
+ *   spangpu_faxtx_tx()                 fax_tx() with transmit_on_idle: the row is always `samples`    src/fax.c:221-256
+ *                                      the handler runs on what is left of the row; where it returns
+ *                                      short, fax_modems_set_next_tx_type(): the next handler goes on src/fax_modems.c:581-596
+ *                                      at that sample, or silence of 0, transmit false and one
+ *                                      SEND_STEP_COMPLETE unless current_tx_type is NONE or DONE
+ *   spangpu_faxtx_status()             per channel for the last tick (any array may be NULL): lens, what fax_tx() returns
+ *                                      without transmit_on_idle; steps, the t30_front_end_status(SEND_STEP_COMPLETE) calls --
+ *                                      fax_tx()'s own and one per call of the HDLC underflow handler (src/fax.c:161-167);
+ *                                      underflows, how many of the latter found the command queue empty; handler,
+ *                                      SPANGPU_FAXTX_HANDLER_* after the tick; transmit
+ *   spangpu_faxtx_framer()             its spangpu_hdlc_tx_frames() / _flags() / _end() / _restart() are
+ *                                      fax_modems_hdlc_tx_frame() and _hdlc_tx_flags()                src/fax_modems.c:175-186, :189-192
+ *   spangpu_faxtx_fast_bank(kind)      its spangpu_modemtx_put_bits() / _end_of_data() are the non-ECM get_bit
+ *
+ * V34HDX is refused (SPANGPU_ERR_UNSUPPORTED), like a kind that is not in kinds_mask (SPANGPU_FAXFE_V27TER | _V29 | _V17, 0: no
+ * fast modem); a rate the kind does not have with SPANGPU_ERR_BAD_ARG.  A refused call changes nothing.  The control calls act
+ * between ticks, ordered on the bank's stream; set_tx_type applies hdlc_tx_flags() to the channel's HDLC words directly, and what
+ * is queued for the framer stays queued.  The head command of the framer's queue is taken wherever hdlc_tx_get_byte() would call
+ * the underflow handler, and the queue is offered (commands until a frame is in or none is left) at the top of each span in
+ * which a sender that takes its bits from the framer runs.  What the reference's T.30 does inside the SEND_STEP_COMPLETE
+ * callback -- a new set_tx_type in mid-row -- happens here between ticks; the rest of the row is silence.
+ *
+ * A tick is one sequence on the bank's stream: a kernel plans the row of every channel (the silence, and the span the sender
+ * installed behind it is offered), the tone banks, the V.21 bank and each fast bank that has a channel assigned run over their
+ * channels' spans (spangpu_txspans_mct() and its likes above), and a kernel resolves what they returned and writes the
+ * zeros.  A host caller's rows are staged and copied out (samples <= max_samples); a device caller's rows are written in place,
+ * at any stride >= samples.  Neighbouring channels are on different handlers as a rule.
+ *
+ * The words (layout: faxtx_dev.hpp): handler, next_handler, transmit, current_tx_type, tx_bit_rate, fast_modem, bit_rate,
+ * short_train, hdlc_mode, use_tep, the silence generator's remaining_samples and total_samples, and which tone
+ * modem_connect_tones_tx_init() last set up (a tone that is running goes on after spangpu_faxtx_restart(), as the reference's
+ * connect_tx does: the restart touches current_tx_type alone).  The reference keeps
+ * fast_modem in one field for both halves of a fax_modems_state_t; this bank keeps its own, and an owner of both halves (a
+ * spangpu_faxfe_t beside this bank) that wants the reference's coupling writes it through set_words.
+ *
+ * Not here: a per-channel queue of pending tx types popped on the device in mid-row, V.34 and SSL FAX, T.30 itself, and the
+ * fax_modems_* / fax_* calls by name.
+ */
+typedef struct spangpu_faxtx_s spangpu_faxtx_t;
+
+#define SPANGPU_T30_MODEM_NONE              0       /* T30_MODEM_*, spandsp/t30.h:328-337 */
+#define SPANGPU_T30_MODEM_PAUSE             1
+#define SPANGPU_T30_MODEM_CED               2
+#define SPANGPU_T30_MODEM_CNG               3
+#define SPANGPU_T30_MODEM_V21               4
+#define SPANGPU_T30_MODEM_V27TER            5
+#define SPANGPU_T30_MODEM_V29               6
+#define SPANGPU_T30_MODEM_V17               7
+#define SPANGPU_T30_MODEM_V34HDX            8
+#define SPANGPU_T30_MODEM_DONE              9
+#define SPANGPU_FAXTX_V17_TX                9       /* FAX_MODEM_V17_TX .. FAX_MODEM_V29_TX: the fast_modem word */
+#define SPANGPU_FAXTX_V27TER_TX             10
+#define SPANGPU_FAXTX_V29_TX                11
+#define SPANGPU_FAXTX_HANDLER_SILENCE       0       /* silence_gen */
+#define SPANGPU_FAXTX_HANDLER_TONE          1       /* modem_connect_tones_tx */
+#define SPANGPU_FAXTX_HANDLER_V21           2       /* fsk_tx */
+#define SPANGPU_FAXTX_HANDLER_FAST          3       /* v17_tx, v27ter_tx, v29_tx */
+
+SPANGPU_API int spangpu_faxtx_create(spangpu_faxtx_t **bank, int device, int n_channels, int kinds_mask, int max_samples, int use_tep);
+SPANGPU_API void spangpu_faxtx_destroy(spangpu_faxtx_t *bank);
+SPANGPU_API int spangpu_faxtx_channels(const spangpu_faxtx_t *bank);
+/* every inner bank follows; the null stream is refused, as for the receive side */
+SPANGPU_API int spangpu_faxtx_set_stream(spangpu_faxtx_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_faxtx_sync(spangpu_faxtx_t *bank);
+SPANGPU_API int spangpu_faxtx_set_tx_type(spangpu_faxtx_t *bank, int channel, int type, int bit_rate, int short_train, int use_hdlc);
+SPANGPU_API int spangpu_faxtx_restart(spangpu_faxtx_t *bank, int channel);
+SPANGPU_API int spangpu_faxtx_set_tep_mode(spangpu_faxtx_t *bank, int channel, int on);
+SPANGPU_API int spangpu_faxtx_tx(spangpu_faxtx_t *bank, int16_t *amp, int mem, int samples, long long stride);
+SPANGPU_API int spangpu_faxtx_status(spangpu_faxtx_t *bank, int32_t *lens, int32_t *steps, int32_t *underflows, int32_t *handler,
+                                     int32_t *transmit);
+/* The inner banks, for their queue, put_bits and state calls on a channel between ticks; they are the bank's, not the caller's to
+   destroy or to run.  kind: SPANGPU_V27TER / _V29 / _V17; tone: SPANGPU_MCT_ANS (CED) or SPANGPU_MCT_FAX_CNG.  NULL: no such bank. */
+SPANGPU_API spangpu_hdlc_tx_t *spangpu_faxtx_framer(spangpu_faxtx_t *bank);
+SPANGPU_API spangpu_modemtx_t *spangpu_faxtx_fast_bank(spangpu_faxtx_t *bank, int kind);
+SPANGPU_API spangpu_fsktx_t *spangpu_faxtx_v21_bank(spangpu_faxtx_t *bank);
+SPANGPU_API spangpu_mcttx_t *spangpu_faxtx_tone_bank(spangpu_faxtx_t *bank, int tone);
+/* One channel's front-end words.  set_words refuses words that name a sender the bank does not have, or a next handler behind
+   anything but silence. */
+SPANGPU_API int spangpu_faxtx_state_words(const spangpu_faxtx_t *bank);
+SPANGPU_API int spangpu_faxtx_get_words(spangpu_faxtx_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_faxtx_set_words(spangpu_faxtx_t *bank, int channel, const int32_t *words);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Noise source banks: batched awgn() -- one independent Gaussian noise generator per channel (Numerical Recipes

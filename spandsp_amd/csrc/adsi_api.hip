@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/spangpu.h"
+#define SPG_HDLC_STEP_FUNCTIONS_ONLY        // the HDLC banks' own kernels belong to hdlc_api.hip
 #include "adsi_dev.hpp"
 #include "bank_host.hpp"
 #include "modem_tables.h"

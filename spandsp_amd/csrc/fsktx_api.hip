@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/spangpu.h"
+#define SPG_HDLC_STEP_FUNCTIONS_ONLY        // the HDLC banks' own kernels belong to hdlc_api.hip
 #include "modem_tables.h"
 #include "fsktx_dev.hpp"
 #include "bank_host.hpp"
@@ -383,6 +384,54 @@ int spangpu_fsktx_tx(spangpu_fsktx_t *t, int mem_kind, int16_t *pcm, long long s
     return stage_out_back(&t->c, &t->pcm, mem_kind, pcm, stride, samples, lens);
 }
 
+// (what the HDLC sender bank's unit hands to the units whose kernels call hdlc_tx_get_bit() themselves; not part of the ABI)
+extern "C" void spangpu_hdlc_tx_rows(spangpu_hdlc_tx_t *b, int32_t **st, uint32_t **buf, int32_t **q_hdr, uint32_t **q_data, int *depth);
+
+// One fsk_tx() call per channel over its own span of the row (txspan_dev.hpp), its get_bit the framer's hdlc_tx_get_bit();
+// everything in device memory, nothing waited for.
+int spangpu_txspans_fsk(spangpu_fsktx_t *t, int16_t *pcm, long long stride, int samples, const int32_t *spans, int sender,
+                               int32_t *ret, spangpu_hdlc_tx_t *framer, int32_t *counts)
+{
+    int rc = tx_args_ok(t, SPANGPU_MEM_DEVICE, pcm, stride, samples);
+    if (rc != SPANGPU_OK)
+        return rc;
+    if (spans == NULL  ||  ret == NULL  ||  framer == NULL  ||  counts == NULL  ||  spangpu_hdlc_tx_channels(framer) != t->c.n_ch)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a framer of as many channels)");
+    if (samples == 0)
+        return SPANGPU_OK;
+    SPG_TRY(hipSetDevice(t->c.device));
+    FskTxLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.st = t->c.st;
+    L.quarter = t->quarter;
+    L.pcm = pcm;
+    L.stride = stride;
+    L.n_ch = t->c.n_ch;
+    L.samples = samples;
+    L.sp.span = spans;
+    L.sp.id = sender;
+    L.sp.ret = ret;
+    uint32_t *q_data;
+    spangpu_hdlc_tx_rows(framer, &L.sp.hst, &L.sp.hbuf, &L.sp.q_hdr, &q_data, &L.sp.depth);
+    L.sp.q_data = q_data;
+    L.sp.cnt = counts;
+    hipLaunchKernelGGL(fsktx_span_kernel, dim3((t->c.n_ch + kFtxCpw*kFtxWaves - 1)/(kFtxCpw*kFtxWaves)), dim3(64*kFtxWaves), 0,
+                       t->c.stream, L);
+    SPG_TRY(hipGetLastError());
+    return SPANGPU_OK;
+}
+
+int spangpu_txline_fsk_set_state(spangpu_fsktx_t *t, int channel, const int32_t *words)
+{
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    // (the walk divides by the baud rate and steps baud_frac up to 800000; the ring position indexes the ring)
+    if (words[FT_BAUD_RATE] <= 0  ||  words[FT_BAUD_RATE] > kFtxBaudUnit  ||  words[FT_BAUD_FRAC] < 0  ||  words[FT_BAUD_FRAC] >= kFtxBaudUnit
+        ||  words[FT_QRD] < 0  ||  words[FT_QRD] >= ((t->qring > 0)  ?  t->qring  :  1)  ||  words[FT_QCOUNT] < 0  ||  words[FT_QCOUNT] > t->qcap)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "not the words of a channel of this bank");
+    return core_rw_words(&t->c, channel, 0, kFskTxWords, const_cast<int32_t *>(words), true);
+}
+
 int spangpu_fsktx_events(spangpu_fsktx_t *t, const int32_t **channels)
 {
     if (t == NULL)
@@ -553,6 +602,40 @@ int spangpu_mcttx_tx(spangpu_mcttx_t *t, int mem_kind, int16_t *pcm, long long s
                        t->c.stream, L);
     SPG_TRY(hipGetLastError());
     return stage_out_back(&t->c, &t->pcm, mem_kind, pcm, stride, samples, lens);
+}
+
+// modem_connect_tones_tx() once per channel over its own span of the row (txspan_dev.hpp)
+int spangpu_txspans_mct(spangpu_mcttx_t *t, int16_t *pcm, long long stride, int samples, const int32_t *spans, int sender, int32_t *ret)
+{
+    int rc = tx_args_ok(t, SPANGPU_MEM_DEVICE, pcm, stride, samples);
+    if (rc != SPANGPU_OK)
+        return rc;
+    if (spans == NULL  ||  ret == NULL)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    if (samples == 0)
+        return SPANGPU_OK;
+    SPG_TRY(hipSetDevice(t->c.device));
+    MctTxLaunch L = t->proto;
+    L.st = t->c.st;
+    L.quarter = t->quarter;
+    L.pcm = pcm;
+    L.stride = stride;
+    L.n_ch = t->c.n_ch;
+    L.samples = samples;
+    L.sp.span = spans;
+    L.sp.id = sender;
+    L.sp.ret = ret;
+    hipLaunchKernelGGL(mcttx_span_kernel, dim3((t->c.n_ch + kFtxCpw*kFtxWaves - 1)/(kFtxCpw*kFtxWaves)), dim3(64*kFtxWaves), 0,
+                       t->c.stream, L);
+    SPG_TRY(hipGetLastError());
+    return SPANGPU_OK;
+}
+
+int spangpu_txline_mct_set_state(spangpu_mcttx_t *t, int channel, const int32_t *words)
+{
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel)  ||  words[MTX_TIMER] < 0  ||  words[MTX_HOP] < 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    return core_rw_words(&t->c, channel, 0, kMctTxWords, const_cast<int32_t *>(words), true);
 }
 
 // ---- host helpers: async_tx framing and the bit clock, no device needed ---------------------------------------------------

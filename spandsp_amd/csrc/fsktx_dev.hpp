@@ -15,6 +15,10 @@
 //            fall in, so the stores of a channel's row are full and contiguous.
 // A channel with more runs than fit takes another round.  State is structure-of-arrays int32 words [words][n_channels].
 //
+// Under the FAX transmit front end (txspan_dev.hpp) the same two kernel bodies run with every channel on its own span of the
+// row: phase 1 walks the channel's `count` samples, phase 2 renders them at row[start ..], unaligned.  The FSK sender then takes
+// hdlc_tx_get_bit() as its get_bit.
+//
 // Samples a channel does not produce (after shutdown, after a finite tone's end, the sample the reference skips when a
 // cadence wraps inside a call) are written as 0; the per-channel length is what the reference would have returned.
 
@@ -22,6 +26,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "txspan_dev.hpp"
 
 namespace spg
 {
@@ -107,6 +113,7 @@ struct FskTxLaunch
     int source;
     int qring;                  // ring size in bits, a multiple of 32
     int vec;                    // rows are 16-byte aligned
+    TxSpans sp;                 // fsktx_span_kernel only
 };
 
 // The modulator's words while a call runs (fsk.c: baud_rate, phase_rates[], current_phase_rate, phase_acc, baud_frac)
@@ -170,7 +177,9 @@ __device__ __forceinline__ int ftx_walk(FtxMod &m, int &done, int samples, bool 
     return nr;
 }
 
-// Phase 2 of a round for a wave: the samples of its channels' runs, 8 per lane.  r_hdr[c] = lo, hi, runs, zero_from, scaling.
+// Phase 2 of a round for a wave: the samples of its channels' runs, 8 per lane.  r_hdr[c] = lo, hi, runs, zero_from, scaling, and
+// with SPANS the sample of the row the channel's call starts at.
+template <bool SPANS = false>
 __device__ __forceinline__ void ftx_render(const int16_t *quarter, const int32_t (*r_hdr)[8], const int32_t (*r_start)[kFtxRunStride],
                                            const int32_t (*r_phase)[kFtxRunStride], const int32_t (*r_rate)[kFtxRunStride], int16_t *pcm,
                                            long long stride, int ch0, int n_ch, int samples, int lane, bool vec)
@@ -222,14 +231,15 @@ __device__ __forceinline__ void ftx_render(const int16_t *quarter, const int32_t
                 ph += (uint32_t) rate;
             }
         }
-        ftx_store8(pcm + (size_t) (ch0 + c)*stride + i0, v, a - i0, b - i0, vec);
+        ftx_store8(pcm + (size_t) (ch0 + c)*stride + (SPANS  ?  r_hdr[c][5]  :  0) + i0, v, a - i0, b - i0, vec);
     }
 }
 
 // (a second unit that includes this header for ftx_walk() / ftx_render() alone -- v18_dev.hpp -- leaves the kernels out)
 #if !defined(SPG_FTX_WITHOUT_KERNELS)
 
-__global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLaunch L)
+template <bool SPANS>
+__device__ __forceinline__ void fsktx_bank_body(const FskTxLaunch &L)
 {
     __shared__ int16_t quarter[258];
     __shared__ int32_t all_start[kFtxWaves][kFtxCpw][kFtxRunStride];
@@ -245,14 +255,23 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
     int32_t (*r_hdr)[8] = all_hdr[wave];
     const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
     const int ch = ch0 + lane;
-    const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+    const size_t n = (size_t) L.n_ch;
+    bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+    // the call my channel makes: the whole row, or its span of it (a channel without one is nobody's: nothing of it is touched)
+    int samples = L.samples;
+    int start = 0;
+    if (SPANS)
+    {
+        if (owner)
+            owner = span_of(L.sp, n, ch, L.samples, start, samples);
+        samples = owner  ?  samples  :  0;
+    }
 
     for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
         quarter[i] = L.quarter[i];
 
-    const size_t n = (size_t) L.n_ch;
     int32_t *st = L.st + (owner  ?  ch  :  0);
-    const int samples = L.samples;
+    SpanFramer fr;
     FtxMod m = {1, 0, 0, 0, 0, 0u};
     int scaling = 0;
     bool shutdown = true;
@@ -270,7 +289,11 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
         m.phase = (uint32_t) st[FT_PHASE*n];
         m.baud_frac = st[FT_BAUD_FRAC*n];
         shutdown = st[FT_SHUTDOWN*n] != 0;
-        if (L.source == FTX_SRC_LFSR)
+        if (SPANS)
+        {
+            fr.open(L.sp, n, ch);
+        }
+        else if (L.source == FTX_SRC_LFSR)
         {
             lfsr = (uint32_t) st[FT_LFSR*n];
         }
@@ -295,7 +318,11 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
     auto next_bit = [&]() __attribute__((always_inline))
     {
         int bit;
-        if (L.source == FTX_SRC_LFSR)
+        if (SPANS)
+        {
+            bit = fr.bit();         // hdlc_tx_get_bit(): 0, 1 or SIG_STATUS_END_OF_DATA
+        }
+        else if (L.source == FTX_SRC_LFSR)
         {
             bit = (int) (((lfsr >> 14) ^ (lfsr >> 13)) & 1u);
             lfsr = ((lfsr << 1) | (uint32_t) bit) & 0x7FFFu;
@@ -332,11 +359,13 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
             r_hdr[lane][2] = nr;
             r_hdr[lane][3] = zero_from;
             r_hdr[lane][4] = scaling;
+            if (SPANS)
+                r_hdr[lane][5] = start;
         }
         __syncthreads();
 
         // ---- phase 2: the samples of those runs, 8 per lane ----
-        ftx_render(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, samples, lane, L.vec != 0);
+        ftx_render<SPANS>(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, L.samples, lane, !SPANS  &&  L.vec != 0);
         if (!__syncthreads_or(done < samples))
             break;
     }
@@ -349,7 +378,11 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
             st[FT_PHASE*n] = (int32_t) m.phase;
             st[FT_BAUD_FRAC*n] = m.baud_frac;
             st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
-            if (L.source == FTX_SRC_LFSR)
+            if (SPANS)
+            {
+                // (nothing of the bank's own bit sources moved)
+            }
+            else if (L.source == FTX_SRC_LFSR)
             {
                 st[FT_LFSR*n] = (int32_t) lfsr;
             }
@@ -360,9 +393,25 @@ __global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLau
             }
         }
         st[FT_EVENT*n] = (shutdown  &&  !was_shutdown)  ?  1  :  0;
-        if (L.lens)
+        if (SPANS)
+        {
+            fr.close(L.sp, n, ch);
+            L.sp.ret[ch] = len;
+        }
+        else if (L.lens)
             L.lens[ch] = len;
     }
+}
+
+__global__ __launch_bounds__(64*kFtxWaves) void fsktx_bank_kernel(const FskTxLaunch L)
+{
+    fsktx_bank_body<false>(L);
+}
+
+// every channel on its own span of the row, its bits from hdlc_tx_get_bit() (txspan_dev.hpp)
+__global__ __launch_bounds__(64*kFtxWaves) void fsktx_span_kernel(const FskTxLaunch L)
+{
+    fsktx_bank_body<true>(L);
 }
 
 // ---- modem_connect_tones_tx() -----------------------------------------------------------------------------------------
@@ -399,9 +448,11 @@ struct MctTxLaunch
     int mod_level;
     int tone_len;           // finite: samples of tone at the end of the timer; cadenced: samples of silence per cycle
     int period;             // cadenced: samples per cycle
+    TxSpans sp;             // mcttx_span_kernel only
 };
 
-__global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLaunch L)
+template <bool SPANS>
+__device__ __forceinline__ void mcttx_bank_body(const MctTxLaunch &L)
 {
     __shared__ int16_t quarter[258];
     __shared__ __attribute__((aligned(16))) int32_t all_runs[kFtxWaves][kFtxCpw][kMtxRuns][4];  // start, end, phase
@@ -413,14 +464,21 @@ __global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLau
     int32_t (*r_hdr)[8] = all_hdr[wave];
     const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
     const int ch = ch0 + lane;
-    const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+    const size_t n = (size_t) L.n_ch;
+    bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
+    int samples = L.samples;
+    int start = 0;
+    if (SPANS)
+    {
+        if (owner)
+            owner = span_of(L.sp, n, ch, L.samples, start, samples);
+        samples = owner  ?  samples  :  0;
+    }
 
     for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
         quarter[i] = L.quarter[i];
 
-    const size_t n = (size_t) L.n_ch;
     int32_t *st = L.st + (owner  ?  ch  :  0);
-    const int samples = L.samples;
     int timer = 0;
     int hop = 0;
     uint32_t tone_phase = 0u;
@@ -519,13 +577,15 @@ __global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLau
             r_hdr[lane][2] = nr;
             r_hdr[lane][3] = hop0;
             r_hdr[lane][4] = (int32_t) mod0;
+            if (SPANS)
+                r_hdr[lane][5] = start;
         }
         __syncthreads();
 
         // ---- phase 2 ----
         {
             const int nchan = (L.n_ch - ch0 < kFtxCpw)  ?  (L.n_ch - ch0)  :  kFtxCpw;
-            const int cpr = (samples + 7) >> 3;
+            const int cpr = (L.samples + 7) >> 3;
             const int total = nchan*cpr;
             for (int idx = lane;  idx < total;  idx += 64)
             {
@@ -565,7 +625,7 @@ __global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLau
                         }
                     }
                 }
-                ftx_store8(L.pcm + (size_t) (ch0 + c)*L.stride + i0, v, a - i0, b - i0, L.vec != 0);
+                ftx_store8(L.pcm + (size_t) (ch0 + c)*L.stride + (SPANS  ?  r_hdr[c][5]  :  0) + i0, v, a - i0, b - i0, !SPANS  &&  L.vec != 0);
             }
         }
         if (!__syncthreads_or(done < samples))
@@ -578,9 +638,21 @@ __global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLau
         st[MTX_HOP*n] = hop;
         st[MTX_TONE_PHASE*n] = (int32_t) tone_phase;
         st[MTX_MOD_PHASE*n] = (int32_t) mod_phase;
-        if (L.lens)
+        if (SPANS)
+            L.sp.ret[ch] = len;
+        else if (L.lens)
             L.lens[ch] = len;
     }
+}
+
+__global__ __launch_bounds__(64*kFtxWaves) void mcttx_bank_kernel(const MctTxLaunch L)
+{
+    mcttx_bank_body<false>(L);
+}
+
+__global__ __launch_bounds__(64*kFtxWaves) void mcttx_span_kernel(const MctTxLaunch L)
+{
+    mcttx_bank_body<true>(L);
 }
 
 #endif

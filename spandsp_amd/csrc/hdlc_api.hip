@@ -89,6 +89,17 @@ extern "C" __attribute__((visibility("hidden"))) void spangpu_framer_rows(spangp
     *buf = b->buf;
 }
 
+// the same of a sender bank, for the sender kernels that call hdlc_tx_get_bit() themselves (txspan_dev.hpp)
+extern "C" __attribute__((visibility("hidden"))) void spangpu_hdlc_tx_rows(spangpu_hdlc_tx_t *b, int32_t **st, uint32_t **buf, int32_t **q_hdr,
+                                                                           uint32_t **q_data, int *depth)
+{
+    *st = b->c.st;
+    *buf = b->buf;
+    *q_hdr = b->q_hdr;
+    *q_data = b->q_data;
+    *depth = b->depth;
+}
+
 extern "C" {
 
 /*

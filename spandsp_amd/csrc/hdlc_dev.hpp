@@ -428,6 +428,7 @@ struct HdlcTxQueue
     const uint32_t *data;   // [depth][101] words
     int depth;
     int underflows;         // handler calls that found it empty
+    int calls = 0;          // all handler calls (each is one SEND_STEP_COMPLETE under the FAX transmit front end)
 };
 
 // hdlc_tx_frame(s, slot, len), then hdlc_tx_corrupt_frame(s) where asked for
@@ -456,6 +457,17 @@ HDLC_HD void hdlc_tx_load_frame(int32_t *w, HdlcBuf &buf, const uint32_t *src, i
     w[HT_CRC] = (int32_t) crc;
 }
 
+// hdlc_tx_flags(): not inside a frame
+HDLC_HD void hdlc_tx_flags_now(int32_t *w, int len)
+{
+    if (w[HT_POS] == 0)
+    {
+        w[HT_FLAG_OCTETS] = (len < 0)  ?  (w[HT_FLAG_OCTETS] - len)  :  len;
+        w[HT_REPORT_FLAG_UNDERFLOW] = 1;
+        w[HT_TX_END] = 0;
+    }
+}
+
 // One command off the queue, as the reference's call of that name would act on the state now.  False: nothing queued.
 HDLC_HD bool hdlc_tx_take(int32_t *w, HdlcBuf &buf, HdlcTxQueue &q)
 {
@@ -472,13 +484,7 @@ HDLC_HD bool hdlc_tx_take(int32_t *w, HdlcBuf &buf, HdlcTxQueue &q)
         hdlc_tx_load_frame(w, buf, q.data + (size_t) slot*kHdlcBufWords, arg, (h & kHdlcCmdCorrupt) != 0);
         break;
     case kHdlcCmdFlags:
-        // hdlc_tx_flags(): not inside a frame
-        if (w[HT_POS] == 0)
-        {
-            w[HT_FLAG_OCTETS] = (arg < 0)  ?  (w[HT_FLAG_OCTETS] - arg)  :  arg;
-            w[HT_REPORT_FLAG_UNDERFLOW] = 1;
-            w[HT_TX_END] = 0;
-        }
+        hdlc_tx_flags_now(w, arg);
         break;
     case kHdlcCmdAbort:
         w[HT_FLAG_OCTETS]++;
@@ -494,6 +500,7 @@ HDLC_HD bool hdlc_tx_take(int32_t *w, HdlcBuf &buf, HdlcTxQueue &q)
 // where the reference calls its underflow handler
 HDLC_HD void hdlc_tx_underflow(int32_t *w, HdlcBuf &buf, HdlcTxQueue &q)
 {
+    q.calls++;
     if (!hdlc_tx_take(w, buf, q))
         q.underflows++;
 }

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/spangpu.h"
+#define SPG_HDLC_STEP_FUNCTIONS_ONLY        // the HDLC banks' own kernels belong to hdlc_api.hip
 #include "modem_tables.h"
 #include "modemtx_dev.hpp"
 #include "bank_host.hpp"
@@ -474,6 +475,100 @@ static int tx_call(spangpu_modemtx_t *t, int mem_kind, int16_t *pcm, long long s
         lens[c] = samples;
     // (the modem senders return the length of the call, as xxx_tx() does; every other sender returns SPANGPU_OK)
     return samples;
+}
+
+// (what the HDLC sender bank's unit hands to the units whose kernels call hdlc_tx_get_bit() themselves; not part of the ABI)
+extern "C" void spangpu_hdlc_tx_rows(spangpu_hdlc_tx_t *b, int32_t **st, uint32_t **buf, int32_t **q_hdr, uint32_t **q_data, int *depth);
+
+// One xxx_tx() call per channel over its own span of the row (txspan_dev.hpp), everything in device memory, nothing waited for.
+int spangpu_txspans_modem(spangpu_modemtx_t *t, int16_t *pcm, long long stride, int samples, const int32_t *spans, int sender,
+                                 int32_t *ret, spangpu_hdlc_tx_t *framer, const int32_t *hdlc_mode, int32_t *counts)
+{
+    int rc = tx_args_ok(t, SPANGPU_MEM_DEVICE, pcm, stride, samples);
+    if (rc != SPANGPU_OK)
+        return rc;
+    if (t->source != kTxSrcQueue  ||  spans == NULL  ||  ret == NULL  ||  framer == NULL  ||  hdlc_mode == NULL  ||  counts == NULL
+        ||  spangpu_hdlc_tx_channels(framer) != t->c.n_ch)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source, a framer of as many channels)");
+    if (samples == 0)
+        return SPANGPU_OK;
+    SPG_TRY(hipSetDevice(t->c.device));
+    V29TxLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.st = t->c.st;
+    L.sine = t->sine;
+    L.shaper = t->shaper;
+    L.constel = t->constel;
+    L.n_ch = t->c.n_ch;
+    L.samples = samples;
+    L.pcm = pcm;
+    L.stride = stride;
+    L.qring = t->qring;
+    L.queue = t->queue;
+    L.qst = t->qst;
+    L.sp.span = spans;
+    L.sp.id = sender;
+    L.sp.ret = ret;
+    uint32_t *q_data;
+    spangpu_hdlc_tx_rows(framer, &L.sp.hst, &L.sp.hbuf, &L.sp.q_hdr, &q_data, &L.sp.depth);
+    L.sp.q_data = q_data;
+    L.sp.mode = hdlc_mode;
+    L.sp.cnt = counts;
+    launch_bank<kTxSrcFax>(t, L);
+    SPG_TRY(hipGetLastError());
+    return SPANGPU_OK;
+}
+
+// xxx_tx_init() of one channel: the words spangpu_modemtx_create_ex() would give it, and an empty ring
+int spangpu_txline_modem_init(spangpu_modemtx_t *t, int channel, int bit_rate, int tep)
+{
+    if (t == NULL  ||  !channel_ok(&t->c, channel))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    int32_t w[kV29TxWords];
+    memset(w, 0, sizeof(w));
+    w[VT_BIT_RATE] = bit_rate;
+    w[VT_CARRIER_RATE] = spg_dds_phase_ratef((t->kind == kTxV29)  ?  1700.0f  :  1800.0f);
+    power_words(w, t->kind, -14.0f);
+    if (restart_words(w, t->kind, bit_rate, tep) != 0)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bit rate not valid for this modem");
+    int rc = core_rw_words(&t->c, channel, 0, kV29TxWords, w, true);
+    if (rc != SPANGPU_OK  ||  t->source != kTxSrcQueue)
+        return rc;
+    int32_t q[VQ_EOD + 1] = {0, 0, 0};
+    return core_rw_at(&t->c, t->qst, channel, VQ_RD, VQ_EOD + 1, q, true);
+}
+
+int spangpu_txline_modem_set_state(spangpu_modemtx_t *t, int channel, const int32_t *words)
+{
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    // (what indexes a table: the rate picks the constellation and the shaper, the ring position and the baud phase the coefficients)
+    int32_t probe[kV29TxWords];
+    memcpy(probe, words, sizeof(probe));
+    const int period = (t->kind != kTxV27ter)  ?  10  :  (words[VT_BIT_RATE] == 4800)  ?  5  :  20;
+    if (restart_words(probe, t->kind, words[VT_BIT_RATE], 0) != 0  ||  words[VT_RRC_STEP] < 0  ||  words[VT_RRC_STEP] >= 9
+        ||  words[VT_BAUD_PHASE] < 0  ||  words[VT_BAUD_PHASE] >= period  ||  (t->kind == kTxV17  &&  (words[VT_GAIN] & ~3))
+        ||  (t->kind == kTxV17  &&  (words[VT_TRAIN_SCRAMBLE] & ~7)))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "not the words of a channel of this bank");
+    return core_rw_words(&t->c, channel, 0, kV29TxWords, const_cast<int32_t *>(words), true);
+}
+
+// the ring of one channel: VQ_RD, VQ_COUNT, VQ_EOD, then the ring's words (qring/32 of them); write: the same back
+int spangpu_txline_modem_ring_words(const spangpu_modemtx_t *t)
+{
+    return (t == NULL  ||  t->source != kTxSrcQueue)  ?  SPANGPU_ERR_BAD_ARG  :  (3 + t->qring/32);
+}
+
+int spangpu_txline_modem_ring_rw(spangpu_modemtx_t *t, int channel, int32_t *words, int write)
+{
+    if (t == NULL  ||  words == NULL  ||  !channel_ok(&t->c, channel)  ||  t->source != kTxSrcQueue)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (a bank with the bit queue as its source)");
+    if (write  &&  (words[0] < 0  ||  words[0] >= t->qring  ||  words[1] < 0  ||  words[1] > t->qcap))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "not the ring of a channel of this bank");
+    int rc = core_rw_at(&t->c, t->qst, channel, VQ_RD, 3, words, write != 0);
+    if (rc == SPANGPU_OK)
+        rc = core_rw_at(&t->c, (int32_t *) t->queue, channel, 0, t->qring/32, words + 3, write != 0);
+    return rc;
 }
 
 int spangpu_modemtx_put_bits(spangpu_modemtx_t *t, int first, int n, const uint8_t *bits, int stride, const int32_t *lens, int32_t *accepted)

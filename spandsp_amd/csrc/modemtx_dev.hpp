@@ -25,6 +25,9 @@
 //                 (v29tx.c:180-199, v27ter_tx.c:215-235: 32 bauds of scrambled ones; v17tx.c:273-289: ones up to
 //                 V17_TRAINING_SHUTDOWN_A, then silence).  Ring position, fill, the flag and the events of the last call are
 //                 words of their own (VQ_*) beside the 32 state words.
+//   kTxSrcFax     the bank under the FAX transmit front end (txspan_dev.hpp): every channel runs its own span of the row, and
+//                 takes its bits from hdlc_tx_get_bit() on the front end's framer where its hdlc_mode word is set, from the ring
+//                 as under kTxSrcQueue where it is not.  SIG_STATUS_END_OF_DATA from the framer acts as the ring's.
 //
 // The nine-symbol pulse shaping buffer is kept oldest-first in registers (a shift per baud); the ring position
 // of the reference only decides where its dot product splits into two partial sums, and that split is
@@ -34,6 +37,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "txspan_dev.hpp"
 
 namespace spg
 {
@@ -74,6 +79,7 @@ constexpr int kVqShutdownComplete = 2;
 
 constexpr int kTxSrcLfsr = 0;
 constexpr int kTxSrcQueue = 1;
+constexpr int kTxSrcFax = 2;
 
 constexpr int kVtSeg1 = 480;
 constexpr int kVtSeg2 = kVtSeg1 + 48;
@@ -121,6 +127,8 @@ struct V29TxLaunch
     int32_t *qst;               // [kVqWords][n_ch]
     int32_t *lens;              // [n_ch] or null: what xxx_tx() returns, `samples` or 0
     int more;                   // this launch goes on with the xxx_tx() call of the last one: no test for the end of the shutdown
+    // bit source kTxSrcFax only
+    TxSpans sp;
 };
 
 // v29tx_constellation_maps.h: index = amplitude bit << 3 | phase octant
@@ -171,6 +179,14 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
 
     int32_t *st = L.st + ch;
     const size_t n = (size_t) L.n_ch;
+    // the call this channel makes: the whole row, or its span of it
+    int start = 0;
+    int samples = L.samples;
+    if (SRC == kTxSrcFax)
+    {
+        if (!span_of(L.sp, n, ch, L.samples, start, samples))
+            return;
+    }
     const int bit_rate = st[VT_BIT_RATE*n];
     // V.27ter keeps one gain per rate: word 1 for 2400 bps, word 2 for 4800 bps
     const float gain = __int_as_float(st[(((KIND == kTxV27ter  &&  bit_rate == 2400)  ||  KIND == kTxV17)  ?  VT_BASE_GAIN  :  VT_GAIN)*n]);
@@ -205,7 +221,15 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     int events = 0;
     uint32_t qword = 0u;
     bool qstale = true;         // the ring word qrd is in has not been loaded in this call
-    if (SRC == kTxSrcQueue)
+    bool framed = false;        // kTxSrcFax: get_bit is hdlc_tx_get_bit
+    SpanFramer fr;
+    if (SRC == kTxSrcFax)
+        framed = (L.sp.mode == nullptr)  ||  (L.sp.mode[ch] != 0);
+    if (SRC == kTxSrcFax  &&  framed)
+    {
+        fr.open(L.sp, n, ch);
+    }
+    else if (SRC != kTxSrcLfsr)
     {
         qrd = L.qst[VQ_RD*n + ch];
         qcount = L.qst[VQ_COUNT*n + ch];
@@ -214,6 +238,17 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     // the caller's get_bit(): asked only while not training
     auto queue_bit = [&]() -> int
     {
+        if (SRC == kTxSrcFax  &&  framed)
+        {
+            const int bit = fr.bit();
+            if (bit < 0)
+            {
+                in_training = 1;
+                events |= kVqEndOfData;
+                return 1;
+            }
+            return bit;
+        }
         if (qcount > 0)
         {
             if (qstale  ||  (qrd & 31) == 0)
@@ -286,13 +321,15 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     // the constellation of this lane's rate inside `constel`
     const int pts_at = (bit_rate == 14400)  ?  0  :  ((bit_rate == 12000)  ?  128  :  ((bit_rate == 9600)  ?  192  :  ((bit_rate == 7200)  ?  224  :  240)));
 
-    int16_t *row = L.pcm + (size_t) ch*L.stride;
+    int16_t *row = L.pcm + (size_t) ch*L.stride + start;
+    // (a span starts anywhere in a row of any stride: 16-byte stores only where this channel's span happens to start on 16 bytes)
+    const bool vec = (SRC == kTxSrcFax)  ?  ((reinterpret_cast<uintptr_t>(row) & 15u) == 0)  :  (L.vec != 0);
     const bool silent = (training_step >= ((KIND == kTxV29)  ?  kVtShutdownEnd  :  ((KIND == kTxV27ter)  ?  kV27ShutdownEnd  :  kV17ShutdownEnd)))
-                        &&  !(SRC == kTxSrcQueue  &&  L.more);
-    for (int base = 0;  base < L.samples;  base += 8)
+                        &&  !(SRC != kTxSrcLfsr  &&  L.more);
+    for (int base = 0;  base < samples;  base += 8)
     {
         uint32_t pk[4] = {0u, 0u, 0u, 0u};
-        const int todo = (L.samples - base < 8)  ?  (L.samples - base)  :  8;
+        const int todo = (samples - base < 8)  ?  (samples - base)  :  8;
 #pragma unroll
         for (int j = 0;  j < 8;  j++)
         {
@@ -362,7 +399,7 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                             {
                                 in_training = 0;
                             }
-                            else if (SRC == kTxSrcQueue  &&  training_step == kVtShutdownEnd)
+                            else if (SRC != kTxSrcLfsr  &&  training_step == kVtShutdownEnd)
                             {
                                 events |= kVqShutdownComplete;      // v29tx.c:192-197
                             }
@@ -435,7 +472,7 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                                     in_training = 0;
                             }
                         }
-                        else if (SRC == kTxSrcQueue  &&  in_training)
+                        else if (SRC != kTxSrcLfsr  &&  in_training)
                         {
                             // the shutdown, v17tx.c:273-289: ones up to V17_TRAINING_SHUTDOWN_A, then silence.  The reference
                             // returns the silence before its test for V17_TRAINING_SHUTDOWN_END, so it never reports
@@ -525,7 +562,7 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
                             {
                                 in_training = 0;
                             }
-                            else if (SRC == kTxSrcQueue  &&  training_step == kV27ShutdownEnd)
+                            else if (SRC != kTxSrcLfsr  &&  training_step == kV27ShutdownEnd)
                             {
                                 events |= kVqShutdownComplete;      // v27ter_tx.c:228-233
                             }
@@ -589,7 +626,7 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
             }
             pk[j >> 1] |= ((uint32_t) v & 0xFFFFu) << ((j & 1)*16);
         }
-        if (L.vec  &&  todo == 8)
+        if (vec  &&  todo == 8)
         {
             *reinterpret_cast<uint4 *>(row + base) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
         }
@@ -625,11 +662,20 @@ __global__ __launch_bounds__(64) void modemtx_bank_kernel(const V29TxLaunch L)
     }
     else
     {
-        L.qst[VQ_RD*n + ch] = qrd;
-        L.qst[VQ_COUNT*n + ch] = qcount;
+        if (SRC == kTxSrcFax  &&  framed)
+        {
+            fr.close(L.sp, n, ch);
+        }
+        else
+        {
+            L.qst[VQ_RD*n + ch] = qrd;
+            L.qst[VQ_COUNT*n + ch] = qcount;
+        }
         L.qst[VQ_EVENT*n + ch] = events;
         // the test for the end of the shutdown is made at the start of a call (v29tx.c:241): the call it ends in is whole
-        if (L.lens)
+        if (SRC == kTxSrcFax)
+            L.sp.ret[ch] = silent  ?  0  :  samples;
+        else if (L.lens)
             L.lens[ch] = silent  ?  0  :  L.samples;
     }
 }

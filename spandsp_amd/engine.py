@@ -261,6 +261,32 @@ def lib():
             "spangpu_faxfe_state_words": (ci, [vp]),
             "spangpu_faxfe_get_words": (ci, [vp, ci, vp]),
             "spangpu_faxfe_set_words": (ci, [vp, ci, vp]),
+            "spangpu_faxtx_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci]),
+            "spangpu_faxtx_destroy": (None, [vp]),
+            "spangpu_faxtx_channels": (ci, [vp]),
+            "spangpu_faxtx_set_stream": (ci, [vp, vp]),
+            "spangpu_faxtx_sync": (ci, [vp]),
+            "spangpu_faxtx_set_tx_type": (ci, [vp, ci, ci, ci, ci, ci]),
+            "spangpu_faxtx_restart": (ci, [vp, ci]),
+            "spangpu_faxtx_set_tep_mode": (ci, [vp, ci, ci]),
+            "spangpu_faxtx_tx": (ci, [vp, vp, ci, ci, ll]),
+            "spangpu_faxtx_status": (ci, [vp, vp, vp, vp, vp, vp]),
+            "spangpu_faxtx_framer": (vp, [vp]),
+            "spangpu_faxtx_fast_bank": (vp, [vp, ci]),
+            "spangpu_faxtx_v21_bank": (vp, [vp]),
+            "spangpu_faxtx_tone_bank": (vp, [vp, ci]),
+            "spangpu_faxtx_state_words": (ci, [vp]),
+            "spangpu_faxtx_get_words": (ci, [vp, ci, vp]),
+            "spangpu_faxtx_set_words": (ci, [vp, ci, vp]),
+            "spangpu_txspans_modem": (ci, [vp, vp, ll, ci, vp, ci, vp, vp, vp, vp]),
+            "spangpu_txspans_fsk": (ci, [vp, vp, ll, ci, vp, ci, vp, vp, vp]),
+            "spangpu_txspans_mct": (ci, [vp, vp, ll, ci, vp, ci, vp]),
+            "spangpu_txline_modem_set_state": (ci, [vp, ci, vp]),
+            "spangpu_txline_modem_ring_words": (ci, [vp]),
+            "spangpu_txline_modem_ring_rw": (ci, [vp, ci, vp, ci]),
+            "spangpu_txline_modem_init": (ci, [vp, ci, ci, ci]),
+            "spangpu_txline_fsk_set_state": (ci, [vp, ci, vp]),
+            "spangpu_txline_mct_set_state": (ci, [vp, ci, vp]),
             "spangpu_awgn_create": (ci, [C.POINTER(vp), ci, ci, vp, vp]),
             "spangpu_awgn_destroy": (None, [vp]),
             "spangpu_awgn_channels": (ci, [vp]),
@@ -1831,10 +1857,16 @@ class _SenderBank(_Bank):
         _check(self._f("get_state")(self.h, channel, w.ctypes.data))
         return w
 
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self._f("state_words")()
+        _check(getattr(lib(), self._set_state_symbol)(self.h, channel, w.ctypes.data))
+
 
 class FskTxBank(_SenderBank):
     """N FSK modulators (fsk_tx), state in HBM.  Bits come from a per-channel LFSR or a per-channel bit queue."""
     _prefix = "fsktx"
+    _set_state_symbol = "spangpu_txline_fsk_set_state"
 
     def __init__(self, spec, n_channels, bit_source=FSKTX_LFSR, seeds=None, queue_bits=4096, device=0):
         self.spec = fsk_preset(spec) if isinstance(spec, int) else spec
@@ -2445,9 +2477,97 @@ class FaxFrontEnd:
         _check(lib().spangpu_faxfe_set_words(self.h, channel, w.ctypes.data))
 
 
+# ---- FAX transmit front-end banks (include/spangpu.h "FAX transmit front-end banks") --------------------
+(T30_MODEM_NONE, T30_MODEM_PAUSE, T30_MODEM_CED, T30_MODEM_CNG, T30_MODEM_V21, T30_MODEM_V27TER, T30_MODEM_V29, T30_MODEM_V17,
+ T30_MODEM_V34HDX, T30_MODEM_DONE) = range(10)
+FAX_MODEM_V17_TX, FAX_MODEM_V27TER_TX, FAX_MODEM_V29_TX = 9, 10, 11
+FAXTX_SILENCE, FAXTX_TONE, FAXTX_V21, FAXTX_FAST = 0, 1, 2, 3                      # handlers
+# the front-end words of a channel (faxtx_dev.hpp)
+(FAXTX_W_HANDLER, FAXTX_W_NEXT_HANDLER, FAXTX_W_TRANSMIT, FAXTX_W_CURRENT_TX_TYPE, FAXTX_W_TX_BIT_RATE, FAXTX_W_FAST_MODEM,
+ FAXTX_W_BIT_RATE, FAXTX_W_SHORT_TRAIN, FAXTX_W_HDLC_MODE, FAXTX_W_USE_TEP, FAXTX_W_SIL_REMAINING, FAXTX_W_SIL_TOTAL,
+ FAXTX_W_TONE) = range(13)
+
+
+class FaxTxFrontEnd:
+    """The transmit half of N fax_modems objects under fax_tx(): silence, tones, V.21 and the fast modems behind one handler
+    chain per channel on the device, the modulators' bits from a shared HDLC sender or the non-ECM rings."""
+
+    def __init__(self, n_channels, kinds_mask=FAXFE_V27TER | FAXFE_V29 | FAXFE_V17, max_samples=160, use_tep=False, device=0):
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_faxtx_create(C.byref(self.h), device, n_channels, kinds_mask, max_samples, int(use_tep)))
+        self.words = lib().spangpu_faxtx_state_words(self.h)
+
+    def close(self):
+        if self.h:
+            lib().spangpu_faxtx_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        _check(lib().spangpu_faxtx_set_stream(self.h, hip_stream))
+
+    def sync(self):
+        _check(lib().spangpu_faxtx_sync(self.h))
+
+    def set_tx_type(self, channel, type_, bit_rate=0, short_train=0, use_hdlc=False):
+        _check(lib().spangpu_faxtx_set_tx_type(self.h, channel, type_, bit_rate, int(short_train), int(use_hdlc)))
+
+    def restart(self, channel):
+        _check(lib().spangpu_faxtx_restart(self.h, channel))
+
+    def set_tep_mode(self, channel, on):
+        _check(lib().spangpu_faxtx_set_tep_mode(self.h, channel, int(on)))
+
+    def tx_host(self, samples):
+        amp = np.full((self.n, samples), 0x5A5A, np.int16)
+        _check(lib().spangpu_faxtx_tx(self.h, amp.ctypes.data, MEM_HOST, samples, samples))
+        return amp
+
+    def tx_device(self, ptr, samples, stride=0):
+        _check(lib().spangpu_faxtx_tx(self.h, ptr, MEM_DEVICE, samples, stride))
+
+    def status(self):
+        """(lens, steps, underflows, handler, transmit) of the last tick, [n] each"""
+        out = [np.zeros(self.n, np.int32) for _ in range(5)]
+        _check(lib().spangpu_faxtx_status(self.h, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def framer(self):
+        p = lib().spangpu_faxtx_framer(self.h)
+        return _borrowed(HdlcTxBank, p, self.n, words=lib().spangpu_hdlc_tx_state_words(p))
+
+    def fast_bank(self, kind):
+        p = lib().spangpu_faxtx_fast_bank(self.h, kind)
+        return _borrowed(ModemTxBank, p, self.n) if p else None
+
+    def v21_bank(self):
+        return _borrowed(FskTxBank, lib().spangpu_faxtx_v21_bank(self.h), self.n)
+
+    def tone_bank(self, tone):
+        p = lib().spangpu_faxtx_tone_bank(self.h, tone)
+        return _borrowed(MctTxBank, p, self.n) if p else None
+
+    def get_words(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_faxtx_get_words(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_words(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_faxtx_set_words(self.h, channel, w.ctypes.data))
+
+
 class MctTxBank(_SenderBank):
     """N modem connect tone generators of one tone type (modem_connect_tones_tx), state in HBM."""
     _prefix = "mcttx"
+    _set_state_symbol = "spangpu_txline_mct_set_state"
 
     def __init__(self, tone_type, n_channels, device=0):
         self.tone_type = tone_type
@@ -2718,6 +2838,25 @@ class ModemTxBank:
         w = np.zeros(lib().spangpu_modemtx_state_words(), np.uint32)
         _check(lib().spangpu_modemtx_get_state(self.h, channel, w.ctypes.data))
         return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.uint32)
+        assert len(w) == lib().spangpu_modemtx_state_words()
+        _check(lib().spangpu_txline_modem_set_state(self.h, channel, w.ctypes.data))
+
+    def get_ring(self, channel):
+        """a queue-sourced bank's ring of one channel: read position, fill, the end-of-data flag, then the ring's words"""
+        w = np.zeros(_check(lib().spangpu_txline_modem_ring_words(self.h)), np.int32)
+        _check(lib().spangpu_txline_modem_ring_rw(self.h, channel, w.ctypes.data, 0))
+        return w
+
+    def set_ring(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == _check(lib().spangpu_txline_modem_ring_words(self.h))
+        _check(lib().spangpu_txline_modem_ring_rw(self.h, channel, w.ctypes.data, 1))
+
+    def init_channel(self, channel, bit_rate, tep=False):
+        _check(lib().spangpu_txline_modem_init(self.h, channel, bit_rate, int(tep)))
 
 
 class V29TxBank(ModemTxBank):

@@ -1267,6 +1267,135 @@ def bench_fax_rx(args, dev, stream):
         "roofline": None, "cpu_baseline": None}
 
 
+def bench_fax_tx(args, dev, stream):
+    """The transmit front end of N FAX terminals as one bank (spangpu_faxtx_*), rows in HBM, all on one stream.  Timed, per tick
+    between two events on the stream, each over fresh lines in step:
+      (a) a tick of V.29 9600 page data with use_hdlc: hdlc_tx_get_bit() inside the modem sender's kernel, 260-octet frames
+          waiting in the framer's queue;
+      (b) a tick of V.21 (preamble flags, then a frame);
+      (c) the tick in which every line's 75 ms of silence ends at sample 120 and its V.29 sender starts: the switch;
+    and, in the same session, the way to do (a) without the front end: spangpu_hdlc_tx_get_bits -> spangpu_bits_to_modemtx ->
+    spangpu_modemtx_tx with the host's cursor saying how many bits the tick takes (tests/test_hdlc_gpu.py's V.29 loop).  Eight
+    lines of each are run side by side and compared sample for sample (both send the same frames); the line says the outcome."""
+    from spandsp_amd import engine
+    n_ch = args.channels or 16384
+    steps = min(args.steps, 40)                 # 8 frames of 260 octets a line last some 85 ticks behind training and preamble
+    warmup = max(args.warmup, 3)
+    rows = torch.zeros((n_ch, FRAME), dtype=torch.int16, device=dev)
+    ptr = ctypes.c_void_p(rows.data_ptr())
+    rng = np.random.RandomState(0xFA)
+    frames = [bytes(rng.randint(0, 256, 260).astype(np.uint8)) for _ in range(8)]
+    raw = ctypes.c_void_p(stream.cuda_stream)
+
+    def make(type_, rate, use_hdlc):
+        ft = engine.FaxTxFrontEnd(n_ch, kinds_mask=engine.FAXFE_V29, max_samples=FRAME)
+        ft.set_stream(raw)
+        for c in range(n_ch):
+            ft.set_tx_type(c, type_, rate, 0, use_hdlc)
+        for f in frames:
+            assert not ft.framer().frames([f]*n_ch).any()
+        return ft
+
+    def timed(fn, count):
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(count)]
+        for a, b in evs:
+            a.record(stream)
+            fn()
+            b.record(stream)
+        torch.cuda.synchronize()
+        return [a.elapsed_time(b) for a, b in evs]
+
+    # (a) 75 ms of silence, 253 ms of training, 200 ms of flags: data from tick 34 on
+    ft = make(engine.T30_MODEM_V29, 9600, True)
+    tick = lambda: ft.tx_device(ptr, FRAME, FRAME)
+    for _ in range(36 + warmup):
+        tick()
+    per_a = timed(tick, steps)
+    _, st, un, h, tr = ft.status()
+    assert (h == engine.FAXTX_FAST).all() and tr.all() and not un.any(), "the lines left their page data inside the timed ticks"
+    ft.close()
+    # (c) the switch, one timed tick per fresh bank state: restart the lines instead of making banks
+    ft = make(engine.T30_MODEM_V29, 9600, True)
+    per_c = []
+    for _ in range(3):
+        tick()
+    per_c += timed(tick, 1)
+    lens, st, un, h, tr = ft.status()
+    assert (h == engine.FAXTX_FAST).all() and (lens == FRAME).all()
+    ft.close()
+    # (b) V.21: 75 ms of silence, then 32 flags (0.85 s) and the frames
+    ft = make(engine.T30_MODEM_V21, 300, True)
+    for _ in range(4 + warmup):
+        tick()
+    per_b = timed(tick, steps)
+    _, st, un, h, tr = ft.status()
+    assert (h == engine.FAXTX_V21).all() and tr.all()
+    ft.close()
+
+    # the parent's way of (a): the HDLC bank's bits through a row in HBM into the modem sender's ring, the host's cursor
+    def chain(n):
+        hd = engine.HdlcTxBank(n, inter_frame_flags=2, queue_depth=9)       # the preamble is a command here
+        tx = engine.V29TxBank(n, 9600, bit_source=engine.MODEMTX_QUEUE, queue_bits=4096)
+        hd.set_stream(raw)
+        tx.set_stream(raw)
+        assert not hd.flags(240).any()
+        for f in frames:
+            assert not hd.frames([f]*n).any()
+        return hd, tx, engine.ModemTxCursor(engine.V29, 9600)
+    hd, tx, cursor = chain(n_ch)
+    stride = 32
+    bits = torch.zeros((n_ch, stride), dtype=torch.uint8, device=dev)
+    lens_d = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+
+    def chain_tick():
+        want = cursor.advance(FRAME)
+        hd.get_bits_device(ctypes.c_void_p(bits.data_ptr()), stride, want, ctypes.c_void_p(lens_d.data_ptr()))
+        tx.put_bits_device(ctypes.c_void_p(bits.data_ptr()), stride, ctypes.c_void_p(lens_d.data_ptr()))
+        tx.tx_device(ptr, FRAME, FRAME)
+    # (the front end's line is 600 samples of silence ahead: 3 ticks and 120 samples; both are in page data from tick 34 on)
+    for _ in range(32 + warmup):
+        chain_tick()
+    per_p = timed(chain_tick, steps)
+    hd.close()
+    tx.close()
+
+    # the same samples: 8 lines of each, the front end's row shifted by its 600 samples of silence
+    small = 8
+    n_keep, n_ch = n_ch, small
+    ft = make(engine.T30_MODEM_V29, 9600, True)
+    hd, tx, cursor = chain(small)
+    got, ref = [], []
+    for _ in range(60):
+        got.append(ft.tx_host(FRAME))
+        want = cursor.advance(FRAME)
+        bb, ll = hd.get_bits_host(want)
+        unpacked = [np.unpackbits(bb[c], bitorder="little")[:ll[c]] for c in range(small)]
+        tx.put_bits(unpacked)
+        ref.append(tx.tx_host(FRAME))
+    got = np.concatenate(got, axis=1)
+    ref = np.concatenate(ref, axis=1)
+    same = bool(np.array_equal(got[:, 600:], ref[:, :-600]) and not got[:, :600].any() and np.abs(ref[:, 5000:]).max() > 1000)
+    ft.close()
+    hd.close()
+    tx.close()
+    n_ch = n_keep
+
+    mean = lambda x: sum(x)/len(x)
+    t_a = mean(per_a)*1e-3
+    value = n_ch*FRAME/t_a/1e6
+    return {
+        "metric": "Msamples/s of a batched FAX transmit front-end bank, V.29 9600 page data with hdlc_tx_get_bit() in the sender's kernel (8 kHz channels at real-time = value*1e6/8000)",
+        "value": value, "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0, "n_gpus": 1, "steps": steps,
+        "warmup": warmup, "ms_per_step": t_a*1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32+int32", "data": "synthetic",
+        "config": {"workload": "spangpu_faxtx_tx: %d channels x %d-sample rows in HBM, one stream" % (n_ch, FRAME), "channels_per_gpu": n_ch,
+                   "ms_per_tick_v29_hdlc": mean(per_a), "min_ms_v29_hdlc": min(per_a), "max_ms_v29_hdlc": max(per_a),
+                   "ms_per_tick_v21": mean(per_b), "min_ms_v21": min(per_b), "max_ms_v21": max(per_b),
+                   "ms_switch_tick": per_c[0],
+                   "ms_per_tick_chain_get_bits_put_bits_tx": mean(per_p), "min_ms_chain": min(per_p), "max_ms_chain": max(per_p),
+                   "front_end_over_chain": mean(per_a)/mean(per_p), "same_samples_as_chain_8_lines": same}}
+
+
 def bench_fax_fe(args, dev, stream):
     """The receive front end of N FAX terminals as one bank (spangpu_faxfe_*): the frames staged once, the V.29 and the V.21
     receiver off per-channel lengths on the device, both event rows into the shared framer or the non-ECM rows, the handler of
@@ -1910,7 +2039,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
@@ -1990,6 +2119,9 @@ def main():
         return
     if args.workload == "fax_fe":
         emit(bench_fax_fe(args, dev, stream), "fax_fe", args.channels or None)
+        return
+    if args.workload == "fax_tx":
+        emit(bench_fax_tx(args, dev, stream), "fax_tx", args.channels or None)
         return
     if args.workload in ("fsk_tx", "mct_tx"):
         emit(bench_sender(args, dev, stream, args.workload), args.workload, args.channels or None)
