@@ -1446,6 +1446,12 @@ int spangpu_banks_rx(spangpu_bank_t *const *banks, const int16_t *const *amps, i
         M.first[k] = first;
     M.n = n_banks;
     static_assert(kFastWPB == kWavesPerBlock, "the workgroup ranges above serve both kernel families");
+    if (all_fast)
+    {
+        // the streaming kernels read their prologue's flags from the aligned16 slot (tone_fast.hpp: kFast...)
+        for (int k = 0;  k < n_banks;  k++)
+            M.bank[k].aligned16 = tone_fast_flags(M.bank[k]);
+    }
     if (all_fast  &&  lpc == 1  &&  use_loader(total_ch))
         hipLaunchKernelGGL((tone_multi_fast_kernel<1, kRingLoader, true>), dim3(first), dim3(kWave*(kWavesPerBlock + 1)), 0, banks[0]->stream, M);
     else if (all_fast  &&  lpc == 1)

@@ -31,6 +31,20 @@ namespace spg {
 
 constexpr int kPiece = 64;                          // bytes of one row per segment
 
+// What a streaming kernel finds in the `aligned16` slot of its arguments.  That the rows are aligned is a precondition of these
+// kernels, as the layout is (whose slot carries wg0), and the slot is one of the sixteen dwords that arrive in SGPRs with the
+// wave: it carries everything a consumer wave's prologue tests before its state loads go out, so that none of those tests
+// waits for a scalar load of the argument block.  tone_fast_flags() on the host makes the word.
+constexpr int kFastAligned = 1;
+constexpr int kFastLens = 2;                        // L.lens != nullptr: the call has an active mask
+constexpr int kFastManyBlocks = 4;                  // L.maxb > 2: records past the second are stored from end_block()
+constexpr int kFastCadence = 8;                     // L.cad.state != nullptr
+
+static inline int tone_fast_flags(const ToneLaunch &L)
+{
+    return kFastAligned | (L.lens  ?  kFastLens  :  0) | ((L.maxb > 2)  ?  kFastManyBlocks  :  0) | (L.cad.state  ?  kFastCadence  :  0);
+}
+
 template <int LPC, int R, bool G711, int WPB>
 struct FastLds
 {
@@ -327,8 +341,12 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
     // A call with an active mask (L.lens holds 0 or `samples` per channel; other lengths go to the general kernel): a
     // channel sitting the call out rides along as a shadow lane -- nothing of it is stored but empty record slots --
     // and a wave with no channel taking part only keeps the workgroup's barriers.
+    const int flags = L.aligned16;                  // (kFast... above)
+    const bool has_lens = (flags & kFastLens) != 0;
+    const bool has_cad = (flags & kFastCadence) != 0;
+    const bool many_blocks = (flags & kFastManyBlocks) != 0;
     bool live = in_bank;
-    if (L.lens)
+    if (has_lens)
     {
         live = in_bank  &&  (L.lens[ch] > 0);
         if (in_bank  &&  !live  &&  sub == 0)
@@ -455,7 +473,7 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
     int4 cad_te1 = make_int4(0, 0, 0, 0);
     if constexpr ((ABL & kToneCadence) != 0)
     {
-        if (L.cad.state)
+        if (has_cad)
         {
             cadence_state_load(L.cad, (int) ch, (int) nch, cad_regs);     // needed a frame from now: the latency costs nothing here
             // ... and this wave's copy of the tables: lane l asks for first[l] and elements l and l + 64 (the host only builds this
@@ -477,7 +495,7 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
     const int block = Det::block_len(L);
     int cs_first = __builtin_amdgcn_readfirstlane(cs);
     bool uniform = __all(cs == cs_first);           // true whenever the wave's channels were started together
-    if (L.lens)
+    if (has_lens)
     {
         // the phase the channels taking part share, if they do; the others adopt it for the ride
         const unsigned long long act = __ballot(live);
@@ -490,7 +508,7 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
     int4 (&cad_elem)[sizeof(cad_elem_all[0])/sizeof(int4)] = cad_elem_all[kCadCopies > 1  ?  wv  :  0];
     if constexpr ((ABL & kToneCadence) != 0)
     {
-        if (L.cad.state)
+        if (has_cad)
         {
             // (the loads came back with the state's; a wave's own LDS operations are performed in order: no barrier)
             if ((int) lane <= kCadLdsTones)
@@ -663,12 +681,9 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
     {
         return *(const int4 *) (lds_raw + a);
     };
-    int pos = 0;                                    // samples of the frame consumed so far (wave-uniform)
-    int cs_s = cs_first;
-    int slot = 0;                                   // ring slot of the current segment
-    for (int seg = 0;  seg < nseg;  seg++)
+    // ---- make segment `seg` resident in ring slot `slot`; keep the ring full ----------------------------
+    auto make_resident = [&](int seg, int slot)
     {
-        // ---- make this segment resident; keep the ring full ------------------------------------------
         if (LDR)
         {
             seg_barrier();                          // the loader has seen this segment land; everyone is done with the last one
@@ -698,20 +713,100 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
             if (seg + R - 1 < nseg)
                 issue_dma(seg + R - 1, (slot == 0)  ?  (R - 1)  :  (slot - 1));    // into the slot consumed last
         }
+    };
+    // The common segment: whole, and no block ends inside it -- straight-line code, all four chunk reads up front
+    auto common_segment = [&](uint32_t rd)
+    {
+        const int4 c0 = chunk_at(rd);
+        const int4 c1 = chunk_at(rd ^ 16u);
+        const int4 c2 = chunk_at(rd ^ 32u);
+        const int4 c3 = chunk_at(rd ^ 48u);
+        run_pairs(std::integral_constant<int, 4*PPC>(), [&](int k)
+        {
+            return pair_from((k < PPC)  ?  c0  :  (k < 2*PPC)  ?  c1  :  (k < 3*PPC)  ?  c2  :  c3, k%PPC);
+        });
+    };
+    int pos = 0;                                    // samples of the frame consumed so far (wave-uniform)
+    int cs_s = cs_first;
+    int slot = 0;                                   // ring slot of the current segment
+    // One channel per lane: the two production kinds of segment -- the common one and (kPairsAsm) the whole one with a block
+    // end on a pair boundary -- have a loop of their own, the hot loop below; a wave is in it whenever its next segment is of
+    // one of those kinds, and takes any other segment (a short last piece, an odd split, a block end in G.711 or filtered
+    // input, divergent phases) through the general code after it, one segment at a time.  The recurrence state then meets the
+    // register assignment of the rarely taken paths once per hand-over and not once per segment: merged into one loop, the
+    // four kinds cost every segment some thirty register copies at the joins and the back edge (profiles/tone_hot_loop.md).
+    constexpr bool kHot = (LPC == 1);
+    for (int seg = 0;  seg < nseg;  seg++)
+    {
+        if constexpr (kHot)
+        {
+            if (uniform)
+            {
+                auto next_segment = [&]()
+                {
+                    pos += 4*SPC;
+                    slot = (slot == R - 1)  ?  0  :  (slot + 1);
+                    stamp(3 + seg);
+                    seg++;
+                };
+                for (  ;  ;  )
+                {
+                    // The common segments in a loop of their own inside it: its back edge is the one a frame takes most.  Where
+                    // the asm body serves, a block end on the segment's last sample is that body's business too (p = 16): with
+                    // no block end in this loop, nothing in it joins a zeroed state with a running one.
+                    auto common_next = [&]() -> bool
+                    {
+                        return seg < nseg  &&  L.samples - pos >= 4*SPC  &&  block - cs_s >= 4*SPC + (kPairsAsm  ?  1  :  0);
+                    };
+                    for (bool more = common_next();  more;  more = common_next())
+                    {
+                        make_resident(seg, slot);
+                        common_segment(rd0 + (uint32_t) slot*kSlot);
+                        cs_s += 4*SPC;
+                        take_acc += 4*SPC;
+                        if constexpr (!kPairsAsm)
+                        {
+                            if (cs_s == block)
+                            {
+                                end_block(std::true_type());
+                                cs_s = 0;
+                            }
+                        }
+                        next_segment();
+                    }
+                    const int m = block - cs_s;                 // samples to the next block end
+                    if (!(kPairsAsm  &&  seg < nseg  &&  L.samples - pos >= 4*SPC  &&  block >= 4*SPC  &&  (m & 1) == 0))
+                        break;
+                    if constexpr (kPairsAsm)
+                    {
+                        // pairs [0, p), the block end, pairs [p, 16) -- through two copies of the one asm body (pairs_asm above)
+                        make_resident(seg, slot);
+                        const uint32_t ad = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) char *) lds_raw + rd0 + (uint32_t) slot*kSlot;
+                        float no_energy = 0.0f;
+                        const int p = __builtin_amdgcn_readfirstlane(m >> 1);
+                        pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, 0, p);
+                        take_acc += m;
+                        end_block(std::true_type());
+                        if (p < 4*PPC)
+                            pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, p, 4*PPC);
+                        cs_s = 4*SPC - m;
+                        take_acc += 4*SPC - m;
+                        next_segment();
+                    }
+                }
+                cs = cs_s;
+                if (seg >= nseg)
+                    break;
+            }
+        }
+        make_resident(seg, slot);
         const uint32_t rd = rd0 + (uint32_t) slot*kSlot;
         const int seglen = min(4*SPC, L.samples - pos);
 
-        if (uniform  &&  seglen == 4*SPC  &&  block - cs_s >= 4*SPC)
+        if (!kHot  &&  uniform  &&  seglen == 4*SPC  &&  block - cs_s >= 4*SPC)
         {
-            // the common segment: whole, and no block ends inside it -- straight-line code, all four chunk reads up front
-            const int4 c0 = chunk_at(rd);
-            const int4 c1 = chunk_at(rd ^ 16u);
-            const int4 c2 = chunk_at(rd ^ 32u);
-            const int4 c3 = chunk_at(rd ^ 48u);
-            run_pairs(std::integral_constant<int, 4*PPC>(), [&](int k)
-            {
-                return pair_from((k < PPC)  ?  c0  :  (k < 2*PPC)  ?  c1  :  (k < 3*PPC)  ?  c2  :  c3, k%PPC);
-            });
+            // (two lanes per channel: the common segment here, every other kind below)
+            common_segment(rd);
             cs_s += 4*SPC;
             take_acc += 4*SPC;
             if (cs_s == block)
@@ -720,32 +815,6 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
                 cs_s = 0;
             }
             cs = cs_s;
-        }
-        else if (uniform  &&  kPairsAsm  &&  seglen == 4*SPC  &&  block >= 4*SPC  &&  ((block - cs_s) & 1) == 0)
-        {
-            // A whole segment with a block end inside it, on a pair boundary: pairs [0, p), the block end, pairs [p, 16) --
-            // both through the one asm body (pairs_asm above)
-            if constexpr (kPairsAsm)
-            {
-                const int m = block - cs_s;
-                const uint32_t ad = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) char *) lds_raw + rd;
-                float no_energy = 0.0f;
-#pragma nounroll
-                for (int part = 0;  part < 2;  part++)
-                {
-                    const int k0 = __builtin_amdgcn_readfirstlane(part  ?  (m >> 1)  :  0);
-                    const int k1 = __builtin_amdgcn_readfirstlane(part  ?  4*PPC  :  (m >> 1));
-                    pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, k0, k1);
-                    if (part == 0)
-                    {
-                        take_acc += m;
-                        end_block(std::true_type());
-                    }
-                }
-                cs_s = 4*SPC - m;
-                take_acc += 4*SPC - m;
-                cs = cs_s;
-            }
         }
         else if (uniform)
         {
@@ -959,9 +1028,9 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
     {
         // Super-tone cadences: the lane that made a channel's records walks them here, before the wave ends -- a launch of
         // its own for this costs 10 us at 65 536 channels, nearly all of it latency that overlaps nothing.
-        if (L.cad.state)
+        if (has_cad)
         {
-            if (L.maxb > 2)
+            if (many_blocks)
                 __threadfence_block();          // records past the second were stored by end_block(): read them back whole
             // (the compact list is made on demand by cadence_list_kernel: an atomic per wave on its counter, a thousand of
             // them on one address, took longer here than the whole walk)
@@ -977,7 +1046,7 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
 // segment first.
 template <class Det, int LPC, int R, bool G711, bool NT, int WPB, int ABL = 0, bool LDR = false>
 __global__ __launch_bounds__(kWave*(WPB + (LDR  ?  1  :  0))) __attribute__((amdgpu_waves_per_eu(LDR  ?  2  :  3)))
-void tone_fast_kernel(const int16_t *amp, long long stride, int samples, int n_ch, int wg0, int aligned16,
+void tone_fast_kernel(const int16_t *amp, long long stride, int samples, int n_ch, int wg0, int aligned16 /* flags */,
                       float *sf, int32_t *si, uint32_t *rec, const ToneLaunch L0)
 {
     __shared__ __attribute__((aligned(1024))) char lds_raw[FastLds<LPC, R, G711, WPB>::kBytes];
@@ -987,7 +1056,7 @@ void tone_fast_kernel(const int16_t *amp, long long stride, int samples, int n_c
     L.samples = samples;
     L.n_ch = n_ch;
     L.layout = 0;               // (a precondition of this kernel; its slot among the preloaded arguments carries wg0)
-    L.aligned16 = aligned16;
+    L.aligned16 = aligned16;    // (... and this one the kFast... flags)
     L.sf = sf;
     L.si = si;
     L.rec = rec;
@@ -1000,7 +1069,7 @@ template <class Det, int LPC, int R, bool G711, bool NT, int WPB, int ABL = 0, b
 static inline void launch_tone_fast(const ToneLaunch &L, int blocks, hipStream_t st)
 {
     hipLaunchKernelGGL((tone_fast_kernel<Det, LPC, R, G711, NT, WPB, ABL, LDR>), dim3(blocks), dim3(kWave*(WPB + (LDR  ?  1  :  0))), 0, st,
-                       L.amp, L.stride, L.samples, L.n_ch, L.wg0, L.aligned16, L.sf, L.si, L.rec, L);
+                       L.amp, L.stride, L.samples, L.n_ch, L.wg0, tone_fast_flags(L), L.sf, L.si, L.rec, L);
 }
 
 // Several banks in ONE launch (see tone_multi_kernel in tone_dev.hpp): workgroups [first[k], first[k + 1]) belong to
