@@ -1608,6 +1608,62 @@ SPANGPU_API int spangpu_fixed_sqrt32_batch(int device, const uint32_t *x, uint16
 SPANGPU_API int spangpu_dds_complexf_batch(int device, uint32_t *phase_acc, const int32_t *phase_rate, float *out, int items, int n, int mem);
 SPANGPU_API int spangpu_arctan2_batch(int device, const float *y, const float *x, int32_t *out, int items, int mem);
 
+/* ---- G.726 codec banks (csrc/g726_api.hip, csrc/g726_dev.hpp) ---------------------------------
+ * N G.726 ADPCM codecs, one lane per channel, each with a bit rate (16000, 24000, 32000 or 40000), an external coding and a
+ * packing of its own; rates[], codings[] and packings[] (n entries each) are cycled over the channels.  A bank encodes or
+ * decodes (a g726_state_t does one of the two as well: both sides share the bit residue).
+ *
+ *   spangpu_g726_create()              g726_init(NULL, bit_rate, ext_coding, packing) x N        src/g726.c:1175-1238
+ *   spangpu_g726_encode()              g726_encode(s, g726_data, amp, len) x N                   src/g726.c:1109-1172
+ *   spangpu_g726_decode()              g726_decode(s, amp, g726_data, g726_bytes) x N            src/g726.c:1044-1106
+ *   spangpu_g726_restart()             g726_init(s, bit_rate, ext_coding, packing) on one channel
+ *
+ * Rows.  Strides are in bytes.  Channel c's PCM row holds int16_t samples where its coding is linear and G.711 bytes where
+ * it is u-law or A-law, as the reference casts the one pointer; its code row holds one code per byte, or packed bytes.
+ * lens[c] (host memory; NULL: max_samples / max_bytes for all) is what channel c brings: samples to encode, bytes to decode.
+ * A channel with 0 sits the call out: its state stays as it was, its count is 0, and its row in device memory is not written.
+ * A row must hold the bank's worst channel: 2*max_samples bytes of PCM in a bank with a linear channel (max_samples with
+ * none), spangpu_g726_encode_capacity(bank, max_samples) bytes of codes; for decoding spangpu_g726_decode_capacity(bank,
+ * max_bytes) samples of the widest coding.
+ * Alignment.  Rows in device memory are read and written in aligned 16-byte chunks, the last one whole: the base pointer
+ * and the stride are multiples of 16 bytes, the stride is at least the row's bytes rounded up to 16, and the bytes of an
+ * output row between its count and the next 16-byte boundary are overwritten.  Anything else is SPANGPU_ERR_BAD_ARG.
+ * Rows in host memory are copied: any stride that holds the row will do, and bytes past the count are not defined.
+ * Counts.  bytes_out / samples_out (host memory, n_channels entries) may be NULL; with it NULL and both rows in device
+ * memory the call only queues work on the bank's stream.  The counts of the last call stay in device memory
+ * (spangpu_g726_counts_dev(), n_channels int32_t): a decoder's can go to spangpu_fsk_rx_lens_dev() /
+ * spangpu_modem_rx_lens_dev() on the same stream with no read-back.
+ * State words: yl, yu, dms, dml, ap, a[2], b[6], pk[2], dq[6], sr[2], td, bs.bitstream, bs.residue, then rate, ext_coding,
+ * bits_per_sample, packing (30).  set_state moves a stream, its configuration and bit residue included, to another channel. */
+#define SPANGPU_G726_ENCODING_LINEAR        0
+#define SPANGPU_G726_ENCODING_ULAW          1
+#define SPANGPU_G726_ENCODING_ALAW          2
+#define SPANGPU_G726_PACKING_NONE           0
+#define SPANGPU_G726_PACKING_LEFT           1
+#define SPANGPU_G726_PACKING_RIGHT          2
+
+typedef struct spangpu_g726_s spangpu_g726_t;
+
+SPANGPU_API int spangpu_g726_create(spangpu_g726_t **bank, int device, int n_channels, const int32_t *rates, const int32_t *codings,
+                                    const int32_t *packings, int n);
+SPANGPU_API void spangpu_g726_destroy(spangpu_g726_t *bank);
+SPANGPU_API int spangpu_g726_channels(const spangpu_g726_t *bank);
+SPANGPU_API int spangpu_g726_set_stream(spangpu_g726_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_g726_sync(spangpu_g726_t *bank);
+SPANGPU_API int spangpu_g726_encode(spangpu_g726_t *bank, const void *amp, int amp_mem_kind, long long amp_stride_bytes, const int32_t *lens,
+                                    int max_samples, uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes, int32_t *bytes_out);
+SPANGPU_API int spangpu_g726_decode(spangpu_g726_t *bank, const uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes,
+                                    const int32_t *lens, int max_bytes, void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                    int32_t *samples_out);
+/* bytes (samples) a row must hold for the worst channel of the bank, residue included */
+SPANGPU_API long long spangpu_g726_encode_capacity(const spangpu_g726_t *bank, int samples);
+SPANGPU_API long long spangpu_g726_decode_capacity(const spangpu_g726_t *bank, int bytes);
+SPANGPU_API const int32_t *spangpu_g726_counts_dev(const spangpu_g726_t *bank);
+SPANGPU_API int spangpu_g726_restart(spangpu_g726_t *bank, int channel, int rate, int coding, int packing);
+SPANGPU_API int spangpu_g726_state_words(const spangpu_g726_t *bank);
+SPANGPU_API int spangpu_g726_get_state(spangpu_g726_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_g726_set_state(spangpu_g726_t *bank, int channel, const int32_t *words);
+
 #if defined(__cplusplus)
 }
 #endif

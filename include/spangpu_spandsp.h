@@ -952,6 +952,55 @@ SPANGPU_ADSI_API int adsi_next_field(adsi_rx_state_t *s, const uint8_t *msg, int
 SPANGPU_ADSI_API int adsi_add_field(adsi_tx_state_t *s, uint8_t *msg, int len, uint8_t field_type, uint8_t const *field_body, int field_len);
 SPANGPU_ADSI_API const char *adsi_standard_to_str(int standard);
 
+/* ---- G.726 ADPCM (csrc/shim_g726.c) ---------------------------------------------------------------------------------
+ * Reference declarations being replaced:
+ *   g726_init, g726_release, g726_free, g726_encode, g726_decode            src/spandsp/g726.h:81-113   src/g726.c:1044-1251
+ * An object is a one-channel codec bank (spangpu.h, "G.726 codec banks"): plumbing for a caller that moves over one call at
+ * a time; the path for scale is the bank.  g726_init() returns NULL for a bit rate other than 16000, 24000, 32000 and 40000,
+ * as the reference does, for a coding or packing outside its enums, and without a GPU.  `s` may be the caller's own storage
+ * (this header has the whole struct, as the reference's private header has): g726_release() then gives up what the object
+ * holds on the device and g726_free() leaves the storage alone.  amp[] is int16_t samples or G.711 bytes according to
+ * ext_coding, as in the reference.  A codec call hands its output back in the same call, so these objects are not members
+ * of channel groups (a group's calls are deferred to one replay).
+ * These names are declared with a macro of their own, as the ADSI ones are: tests/test_g726.py holds them against
+ * src/spandsp/g726.h.
+ */
+#define SPANGPU_G726_API SPANGPU_API
+
+enum
+{
+    G726_ENCODING_LINEAR = 0,
+    G726_ENCODING_ULAW,
+    G726_ENCODING_ALAW
+};
+
+enum
+{
+    G726_PACKING_NONE = 0,
+    G726_PACKING_LEFT = 1,
+    G726_PACKING_RIGHT = 2
+};
+
+typedef struct g726_state_s g726_state_t;
+
+struct g726_state_s
+{
+    int rate;
+    int ext_coding;
+    int bits_per_sample;
+    int packing;
+    spangpu_g726_t *bank;
+    uint8_t *row;               /* what a call's piece comes back in, before the caller's buffer gets its count of it */
+    size_t row_cap;
+    int caller_storage;
+};
+
+SPANGPU_G726_API g726_state_t *g726_init(g726_state_t *s, int bit_rate, int ext_coding, int packing);
+SPANGPU_G726_API int g726_release(g726_state_t *s);
+SPANGPU_G726_API int g726_free(g726_state_t *s);
+SPANGPU_G726_API int g726_decode(g726_state_t *s, int16_t amp[], const uint8_t g726_data[], int g726_bytes);
+SPANGPU_G726_API int g726_encode(g726_state_t *s, uint8_t g726_data[], const int16_t amp[], int len);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -489,6 +489,21 @@ def lib():
             "echo_can_snapshot": (None, [vp]),
             "echo_can_update": (C.c_int16, [vp, C.c_int16, C.c_int16]),
             "echo_can_hpf_tx": (C.c_int16, [vp, C.c_int16]),
+            # G.726 codec banks
+            "spangpu_g726_create": (ci, [C.POINTER(vp), ci, ci, vp, vp, vp, ci]),
+            "spangpu_g726_destroy": (None, [vp]),
+            "spangpu_g726_channels": (ci, [vp]),
+            "spangpu_g726_set_stream": (ci, [vp, vp]),
+            "spangpu_g726_sync": (ci, [vp]),
+            "spangpu_g726_encode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_g726_decode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_g726_encode_capacity": (ll, [vp, ci]),
+            "spangpu_g726_decode_capacity": (ll, [vp, ci]),
+            "spangpu_g726_counts_dev": (vp, [vp]),
+            "spangpu_g726_restart": (ci, [vp, ci, ci, ci, ci]),
+            "spangpu_g726_state_words": (ci, [vp]),
+            "spangpu_g726_get_state": (ci, [vp, ci, vp]),
+            "spangpu_g726_set_state": (ci, [vp, ci, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -2185,6 +2200,102 @@ class AdsiRxBank(_SenderBank):
         w = np.ascontiguousarray(w, np.int32)
         assert len(w) == self.words
         _check(lib().spangpu_adsi_rx_set_state(self.h, channel, w.ctypes.data))
+
+
+# ---- G.726 codec banks (include/spangpu.h "G.726 codec banks") -----------------------------
+G726_LINEAR, G726_ULAW, G726_ALAW = 0, 1, 2
+G726_PACKING_NONE, G726_PACKING_LEFT, G726_PACKING_RIGHT = 0, 1, 2
+
+
+class G726Bank(_Bank):
+    """N G.726 codecs (g726_encode / g726_decode), each channel with its own rate, external coding and packing (the three
+    lists are cycled over the channels), state in HBM.  A PCM row is bytes: int16 samples where the channel's coding is
+    linear, G.711 bytes where it is not."""
+    _prefix = "g726"
+
+    def __init__(self, n_channels, rates=32000, codings=G726_LINEAR, packings=G726_PACKING_NONE, device=0):
+        r, c, p = (np.atleast_1d(np.asarray(v, np.int32)).copy() for v in (rates, codings, packings))
+        n = max(len(r), len(c), len(p))
+        r, c, p = (np.resize(v, n).astype(np.int32) for v in (r, c, p))
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_g726_create(C.byref(self.h), device, n_channels, r.ctypes.data, c.ctypes.data, p.ctypes.data, n))
+        self.words = lib().spangpu_g726_state_words(self.h)
+        self.codings = c[np.arange(n_channels) % n].copy()      # per channel: what a PCM row holds
+
+    def encode_capacity(self, samples):
+        return _check(lib().spangpu_g726_encode_capacity(self.h, samples))
+
+    def decode_capacity(self, nbytes):
+        return _check(lib().spangpu_g726_decode_capacity(self.h, nbytes))
+
+    def pcm_row_bytes(self, samples):
+        """bytes a PCM row of `samples` elements takes in this bank's widest coding"""
+        return 2*samples if (self.codings == G726_LINEAR).any() else samples
+
+    @staticmethod
+    def _lens(lens, n):
+        if lens is None:
+            return None, None
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert lens.shape == (n,)
+        return lens, lens.ctypes.data
+
+    def encode_host(self, pcm, samples, lens=None):
+        """pcm: [n][>= pcm_row_bytes(samples)] uint8 rows.  Returns (codes [n][encode_capacity(samples)] uint8, bytes [n])."""
+        pcm = np.ascontiguousarray(pcm).view(np.uint8)
+        assert pcm.shape[0] == self.n
+        lens, lp = self._lens(lens, self.n)
+        codes = np.zeros((self.n, max(1, self.encode_capacity(samples))), np.uint8)
+        counts = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_g726_encode(self.h, pcm.ctypes.data, MEM_HOST, pcm.shape[1], lp, samples, codes.ctypes.data, MEM_HOST,
+                                         codes.shape[1], counts.ctypes.data))
+        return codes, counts
+
+    def decode_host(self, codes, nbytes, lens=None):
+        """codes: [n][>= nbytes] uint8 rows.  Returns (pcm [n][pcm_row_bytes(decode_capacity(nbytes))] uint8, samples [n])."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert codes.shape[0] == self.n
+        lens, lp = self._lens(lens, self.n)
+        pcm = np.zeros((self.n, max(1, self.pcm_row_bytes(self.decode_capacity(nbytes)))), np.uint8)
+        counts = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_g726_decode(self.h, codes.ctypes.data, MEM_HOST, codes.shape[1], lp, nbytes, pcm.ctypes.data, MEM_HOST,
+                                         pcm.shape[1], counts.ctypes.data))
+        return pcm, counts
+
+    def encode_device(self, pcm_ptr, pcm_stride, samples, codes_ptr, codes_stride, lens=None, counts=False):
+        """Rows in device memory (16-byte aligned, strides in bytes, multiples of 16).  counts: read the byte counts back."""
+        lens, lp = self._lens(lens, self.n)
+        out = np.zeros(self.n, np.int32) if counts else None
+        _check(lib().spangpu_g726_encode(self.h, pcm_ptr, MEM_DEVICE, pcm_stride, lp, samples, codes_ptr, MEM_DEVICE, codes_stride,
+                                         out.ctypes.data if counts else None))
+        return out
+
+    def decode_device(self, codes_ptr, codes_stride, nbytes, pcm_ptr, pcm_stride, lens=None, counts=False):
+        lens, lp = self._lens(lens, self.n)
+        out = np.zeros(self.n, np.int32) if counts else None
+        _check(lib().spangpu_g726_decode(self.h, codes_ptr, MEM_DEVICE, codes_stride, lp, nbytes, pcm_ptr, MEM_DEVICE, pcm_stride,
+                                         out.ctypes.data if counts else None))
+        return out
+
+    def counts_dev(self):
+        """device pointer to the last call's per-channel counts (int32 [n])"""
+        return lib().spangpu_g726_counts_dev(self.h)
+
+    def restart(self, channel, rate, coding, packing):
+        _check(lib().spangpu_g726_restart(self.h, channel, rate, coding, packing))
+        self.codings[channel] = coding
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_g726_get_state(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_g726_set_state(self.h, channel, w.ctypes.data))
+        self.codings[channel] = w[27]
 
 
 # ---- HDLC framing banks (include/spangpu.h "HDLC framing banks") ---------------------------

@@ -16,6 +16,7 @@ import os
 import sys
 import threading
 import time
+import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -1704,6 +1705,125 @@ def bench_adsi(args, dev, stream):
         "cpu_baseline": None}
 
 
+def bench_g726(args, dev, stream):
+    """G.726 codec banks: g726_encode() of every line into HBM and g726_decode() from there, timed separately with events,
+    65 536 lines x 160 samples.  Once with every channel at --rate, linear, right-packed, once with the 36 configurations
+    (4 rates x 3 codings x 3 packings) mixed within every wave.  In the same session: the host-to-device copy of the int16
+    rows a codec path saves most of, and the signalling tone receiver, a one-lane bank of comparable length.  A 64-channel
+    bank is held against the committed fixture first."""
+    import g726_lines as GL
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    nf = GL.N//FRAME
+    g = GL.load()
+    the_lines = GL.lines()
+    # ---- the spot check: 64 channels, the 36 configurations, five frames of the ten-segment line ----
+    r36, c36, p36 = zip(*GL.CONFIGS)
+    enc, dec = engine.G726Bank(64, r36, c36, p36), engine.G726Bank(64, r36, c36, p36)
+    rows = [GL.pcm_row(the_lines[0], c) for c in GL.CODINGS]
+    checked = 0
+    for k in range(5):
+        pcm = np.zeros((64, 2*FRAME), np.uint8)
+        for c in range(64):
+            x = rows[c36[c % 36]][k*FRAME:(k + 1)*FRAME]
+            pcm[c, :x.nbytes] = x.view(np.uint8)
+        codes, counts = enc.encode_host(pcm, FRAME)
+        out, samples = dec.decode_host(codes, int(counts.max()), counts)
+        for c in range(64):
+            rate, coding, packing = GL.CONFIGS[c % 36]
+            bps = rate//8000
+            if packing == GL.PACK_NONE:
+                want = g["codes_%d" % rate][coding][0][k*FRAME:(k + 1)*FRAME]
+            else:
+                want = g["packed%d_%d" % (packing, rate)][coding][0][k*FRAME*bps//8:(k + 1)*FRAME*bps//8]
+            assert counts[c] == len(want) and np.array_equal(codes[c, :counts[c]], want), ("encode", c, k)
+            ref = g["out_lin_%d" % rate][0] if coding == GL.LINEAR else g["out_law_%d" % rate][coding - 1][0]
+            got = out[c, :2*FRAME].view(np.int16) if coding == GL.LINEAR else out[c, :FRAME]
+            assert samples[c] == FRAME and np.array_equal(got, ref[k*FRAME:(k + 1)*FRAME]), ("decode", c, k)
+            checked += 1
+    enc.close()
+    dec.close()
+
+    def run(configs, name):
+        r, cd, pk = zip(*configs)
+        n_cfg = len(configs)
+        enc, dec = engine.G726Bank(n_ch, r, cd, pk), engine.G726Bank(n_ch, r, cd, pk)
+        for b in (enc, dec):
+            b.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        # frames[f][c]: 320 bytes a row, int16 samples or 160 G.711 bytes, of line (c // n_cfg) % 3
+        src = np.zeros((3, 3, nf, 2*FRAME), np.uint8)
+        for coding in GL.CODINGS:
+            for li in range(3):
+                x = GL.pcm_row(the_lines[li], coding).reshape(nf, FRAME)
+                src[coding, li, :, :x.itemsize*FRAME] = x.view(np.uint8).reshape(nf, -1)
+        idx = np.arange(n_ch)
+        coding_of = np.array(cd)[idx % n_cfg]
+        frames = torch.tensor(src[coding_of, (idx//n_cfg) % 3], device=dev).permute(1, 0, 2).contiguous()      # [nf][n_ch][320]
+        cap = (enc.encode_capacity(FRAME) + 15) & ~15
+        codes = torch.zeros(n_ch, cap, dtype=torch.uint8, device=dev)
+        out_bytes = (enc.pcm_row_bytes(dec.decode_capacity(FRAME)) + 15) & ~15
+        out = torch.zeros(n_ch, out_bytes, dtype=torch.uint8, device=dev)
+        # 160 samples are a whole number of bytes at every rate: the bytes a channel brings to the decoder are the same every tick
+        bps = np.array(r)[idx % n_cfg]//8000
+        lens = np.where(np.array(pk)[idx % n_cfg] == GL.PACK_NONE, FRAME, FRAME*bps//8).astype(np.int32)
+        uniform = n_cfg == 1
+        per_e, per_d = [], []
+        total = args.warmup + min(args.steps, nf - args.warmup)
+        t0 = None
+        for i in range(total):
+            if i == args.warmup:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            e[0].record(stream)
+            enc.encode_device(ctypes.c_void_p(frames[i].data_ptr()), 2*FRAME, FRAME, ctypes.c_void_p(codes.data_ptr()), cap)
+            e[1].record(stream)
+            dec.decode_device(ctypes.c_void_p(codes.data_ptr()), cap, int(lens.max()), ctypes.c_void_p(out.data_ptr()), out_bytes,
+                              lens=None if uniform else lens)
+            e[2].record(stream)
+            if i >= args.warmup:
+                per_e.append((e[0], e[1]))
+                per_d.append((e[1], e[2]))
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        steps = total - args.warmup
+        counts = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+        ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(dec.counts_dev()), ctypes.c_size_t(4*n_ch), 3)
+        got = counts.cpu().numpy()
+        assert (got == FRAME).all(), "a decoder did not make a frame of its bytes"
+        e_ms = [a.elapsed_time(b) for a, b in per_e]
+        d_ms = [a.elapsed_time(b) for a, b in per_d]
+        enc.close()
+        dec.close()
+        return {"name": name, "configurations": n_cfg, "steps": steps, "ms_per_step": dt*1e3/steps,
+                "encode": {"avg_launch_us": sum(e_ms)/len(e_ms)*1e3, "min_launch_us": min(e_ms)*1e3},
+                "decode": {"avg_launch_us": sum(d_ms)/len(d_ms)*1e3, "min_launch_us": min(d_ms)*1e3},
+                "code_bytes_per_tick": int(lens.sum()), "pcm_bytes_per_tick": int(n_ch*FRAME*2)}
+
+    uni = run([(args.rate, GL.LINEAR, GL.PACK_RIGHT)], "%d bit/s, linear, right-packed" % args.rate)
+    mix = run(GL.CONFIGS, "36 configurations mixed within every wave")
+    h2d_ms = copy_alone_ms(n_ch*FRAME*2, "h2d", dev)
+    sig = bench_sigtone(types.SimpleNamespace(channels=n_ch, warmup=2, steps=20, no_cpu_baseline=True, cpu_channels=0), dev, stream)
+    sig_us = sig["roofline"]["avg_launch_us"]
+    value = n_ch*FRAME*2/(uni["ms_per_step"]*1e-3)/1e6
+    return {
+        "metric": "Msamples/s of a G.726 codec bank pair (g726_encode into HBM, g726_decode from HBM; both directions counted)",
+        "value": value, "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0/2, "n_gpus": 1, "steps": uni["steps"], "warmup": args.warmup,
+        "ms_per_step": uni["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+        "config": {"workload": "G.726 codec banks, %d channels x %d-sample frames" % (n_ch, FRAME), "channels_per_gpu": n_ch,
+                   "spot_checked_against_fixture": checked},
+        "kernels": {"uniform": uni, "mixed": mix},
+        "yardsticks": {"h2d_copy_of_int16_rows_ms": h2d_ms, "sigtone_rx_launch_us": sig_us,
+                       "encode_vs_copy": uni["encode"]["avg_launch_us"]/(h2d_ms*1e3), "decode_vs_copy": uni["decode"]["avg_launch_us"]/(h2d_ms*1e3),
+                       "mixed_encode_vs_copy": mix["encode"]["avg_launch_us"]/(h2d_ms*1e3), "mixed_decode_vs_copy": mix["decode"]["avg_launch_us"]/(h2d_ms*1e3),
+                       "encode_vs_sigtone": uni["encode"]["avg_launch_us"]/sig_us, "decode_vs_sigtone": uni["decode"]["avg_launch_us"]/sig_us,
+                       "mixed_to_uniform_encode": mix["encode"]["avg_launch_us"]/uni["encode"]["avg_launch_us"],
+                       "mixed_to_uniform_decode": mix["decode"]["avg_launch_us"]/uni["decode"]["avg_launch_us"]},
+        "roofline": None,
+        "cpu_baseline": None,
+        "cpu_baseline_reason": "g726.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
+
+
 def bench_hdlc(args, dev, stream):
     """An HDLC sender bank producing 192 bits per line and tick (what V.29 9600 takes) into HBM, and an HDLC receiver bank
     framing 192 events per line and tick from HBM: hdlc_tx_get_bit() and hdlc_rx_put_bit() of every line, timed separately.
@@ -2039,8 +2159,9 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
+    ap.add_argument("--rate", type=int, choices=[16000, 24000, 32000, 40000], default=32000, help="g726: the bit rate of the uniform run")
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
     ap.add_argument("--warmup", type=int, default=0)
@@ -2116,6 +2237,10 @@ def main():
         return
     if args.workload == "hdlc":
         emit(bench_hdlc(args, dev, stream), "hdlc", args.channels or None)
+        return
+    if args.workload == "g726":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        emit(bench_g726(args, dev, stream), "g726", args.channels or None)
         return
     if args.workload == "fax_fe":
         emit(bench_fax_fe(args, dev, stream), "fax_fe", args.channels or None)
