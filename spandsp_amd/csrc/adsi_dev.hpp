@@ -12,12 +12,12 @@
 //   crc_itu16_calc()           src/crc.c:161-169       bit by bit
 //   tone_gen()                 src/tone_generate.c:128-229   for a descriptor of two tones, one on and one off section, no
 //                                                      repeat: the sample arithmetic is that of tx_bank_kernel (txgen_dev.hpp)
-// What is used as it stands: the modulator (ftx_walk() / ftx_render(), fsktx_dev.hpp) with the message framer as its bit
-// source, and the asynchronous demodulator over two waves (fsk_sig_block() / fsk_bit_block(), fsk_dev.hpp) with the message
-// framer as its put_bit.
+// What is used as it stands: the modulator and its round loop (ftx_rounds(), fskmod_dev.hpp) with the message framer as
+// its bit source, and the asynchronous demodulator over two waves (fsk_pair_body(), fsk_dev.hpp) with the message framer
+// as its sink.
 //
 // State is structure-of-arrays int32 words.  A sender bank: [kAdsiTxWords + kFskTxWords][n_channels], the message layer's
-// words, then the modulator's in the layout of fsktx_dev.hpp.  A receiver bank: [kAdsiRxWords + kFskScalars + 4*span]
+// words, then the modulator's in the layout of fskmod_dev.hpp.  A receiver bank: [kAdsiRxWords + kFskScalars + 4*span]
 // [n_channels], the framer's words, then the demodulator's in the layout of fsk_dev.hpp.  A channel's message bytes (256,
 // either way) live in HBM beside the words, channel-major.
 
@@ -25,11 +25,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <type_traits>
 
 #include "fsk_dev.hpp"
-#define SPG_FTX_WITHOUT_KERNELS
-#include "fsktx_dev.hpp"
+#include "fskmod_dev.hpp"
 
 namespace spg
 {
@@ -142,39 +140,25 @@ struct AdsiTxLaunch
     float tone_gain[2];
 };
 
-// adsi_tx() x N: the shape of fsktx_bank_kernel / v18_tx_kernel, with the message framer as the modulator's bit source.  A
-// channel's row is the alert tone's samples [0, T) -- for almost every call T is 0 -- and the modem's in [T, samples): the
-// modulator walks and renders in row coordinates, from T on.  The byte pull happens in phase 1, at a bit boundary.
+// adsi_tx() x N: the FSK modulator (fskmod_dev.hpp) with the message framer as its bit source.  A channel's row is the alert
+// tone's samples [0, T) -- for almost every call T is 0 -- and the modem's in [T, samples): the modulator walks and renders
+// in row coordinates, from T on.  The byte pull happens in phase 1, at a bit boundary.
 __global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunch L)
 {
-    __shared__ int16_t quarter[258];
-    __shared__ int32_t all_start[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ int32_t all_phase[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ int32_t all_rate[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ __attribute__((aligned(16))) int32_t all_hdr[kFtxWaves][kFtxCpw][8];
     __shared__ __attribute__((aligned(16))) int32_t all_tone[kFtxWaves][kFtxCpw][8];    // T, sound from, sound to, phase0, phase1
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    int32_t (*r_start)[kFtxRunStride] = all_start[wave];
-    int32_t (*r_phase)[kFtxRunStride] = all_phase[wave];
-    int32_t (*r_rate)[kFtxRunStride] = all_rate[wave];
-    int32_t (*r_hdr)[8] = all_hdr[wave];
     int32_t (*r_tone)[8] = all_tone[wave];
     const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
     const int ch = ch0 + lane;
     const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
-
-    for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
-        quarter[i] = L.quarter[i];
+    const FtxLds lds = ftx_lds(L.quarter);
 
     const size_t n = (size_t) L.n_ch;
     int32_t *sv = L.st + (owner  ?  ch  :  0);
     int32_t *st = sv + (size_t) kAdsiTxWords*n;
     const int samples = L.samples;
-    FtxMod m = {1, 0, 0, 0, 0, 0u};
-    int scaling = 0;
-    bool shutdown = true;
     AdsiTx t;
     t.preamble_len = t.preamble_ones_len = t.postamble_ones_len = t.stop_bits = 0;
     t.byte_no = t.bit_pos = t.bit_no = t.msg_len = t.signal_on = 0;
@@ -202,15 +186,9 @@ __global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunc
         tph1 = (uint32_t) sv[ADT_TONE_PHASE1*n];
         dur0 = sv[ADT_TONE_DUR0*n];
         dur1 = sv[ADT_TONE_DUR1*n];
-        m.baud_rate = st[FT_BAUD_RATE*n];
-        m.rate0 = st[FT_RATE0*n];
-        m.rate1 = st[FT_RATE1*n];
-        scaling = st[FT_SCALING*n];
-        m.cur_rate = st[FT_CUR_RATE*n];
-        m.phase = (uint32_t) st[FT_PHASE*n];
-        m.baud_frac = st[FT_BAUD_FRAC*n];
-        shutdown = st[FT_SHUTDOWN*n] != 0;
     }
+    FtxChan c;
+    ftx_chan_load(c, st, n, owner);
 
     // tone_gen(&s->alert_tone_gen, amp, max_len), tone_generate.c:139-228, for sections 0 (the two tones) and 1 (silence)
     int tone_len = 0;
@@ -259,8 +237,7 @@ __global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunc
     // adsi.c:531-547: with tx_signal_on clear, or a row the tone fills, nothing is asked of the modulator; a modulator that
     // is shut down returns 0
     const bool asked = owner  &&  t.signal_on != 0  &&  tone_len < samples;
-    const bool was_shutdown = shutdown;
-    bool silent = !asked  ||  shutdown;
+    const bool silent = !asked  ||  c.shutdown;
     int done = owner  ?  tone_len  :  samples;
     int len = samples;
     int zero_from = 0x7FFFFFFF;
@@ -305,33 +282,8 @@ __global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunc
         }
     }
 
-    auto next_bit = [&]() __attribute__((always_inline)) { return adsi_next_bit(t); };
-
-    for (;;)
-    {
-        const int lo = done;
-        int nr = 0;
-        if (owner  &&  done < samples)
-        {
-            if (silent)
-                done = samples;
-            else
-                nr = ftx_walk(m, done, samples, shutdown, len, zero_from, r_start[lane], r_phase[lane], r_rate[lane], next_bit);
-            silent = silent  ||  shutdown;
-        }
-        if (lane < kFtxCpw)
-        {
-            r_hdr[lane][0] = lo;
-            r_hdr[lane][1] = done;
-            r_hdr[lane][2] = nr;
-            r_hdr[lane][3] = zero_from;
-            r_hdr[lane][4] = scaling;
-        }
-        __syncthreads();
-        ftx_render(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, samples, lane, L.vec != 0);
-        if (!__syncthreads_or(done < samples))
-            break;
-    }
+    ftx_rounds(lds, c, owner, silent, done, samples, len, zero_from, 0, L.pcm, L.stride, ch0, L.n_ch, samples, L.vec != 0,
+               [&]() __attribute__((always_inline)) { return adsi_next_bit(t); });
 
     if (owner)
     {
@@ -341,12 +293,9 @@ __global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunc
         sv[ADT_TONE_PHASE1*n] = (int32_t) tph1;
         if (asked)
         {
-            if (!was_shutdown)
+            if (!c.was_shutdown)
             {
-                st[FT_CUR_RATE*n] = m.cur_rate;
-                st[FT_PHASE*n] = (int32_t) m.phase;
-                st[FT_BAUD_FRAC*n] = m.baud_frac;
-                st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
+                ftx_chan_store(c, st, n);
                 sv[ADT_BYTE_NO*n] = t.byte_no;
                 sv[ADT_BIT_POS*n] = t.bit_pos;
                 sv[ADT_BIT_NO*n] = t.bit_no;
@@ -355,7 +304,7 @@ __global__ __launch_bounds__(64*kFtxWaves) void adsi_tx_kernel(const AdsiTxLaunc
             // adsi.c:542-543: a call that gets nothing out of the modulator turns the signal off
             sv[ADT_TX_SIGNAL_ON*n] = (len - tone_len <= 0)  ?  0  :  t.signal_on;
         }
-        st[FT_EVENT*n] = (shutdown  &&  !was_shutdown)  ?  1  :  0;
+        ftx_event_store(c, st, n);
         if (L.lens)
             L.lens[ch] = len;
     }
@@ -540,58 +489,16 @@ __device__ __forceinline__ void adsi_put_bit(AdsiRx &v, int bit)
     }
 }
 
-// adsi_rx() x N: fsk_pair_kernel's two waves per 64 channels (fsk_dev.hpp, "A receiver over two waves"), asynchronous,
-// with the message framer behind the bit clock.
-__global__ __launch_bounds__(128) void adsi_rx_kernel(const AdsiRxLaunch V)
+// The sink of fsk_pair_body() (fsk_dev.hpp): the framer's words in and out around adsi_put_bit()
+struct AdsiRxSink
 {
-    extern __shared__ int32_t win[];        // [4*span][64], then the two message buffers [2][kFskMsgWords][64]
-    __shared__ uint32_t wave[kFskWave];
-    const FskLaunch &L = V.f;
-    const int lane = threadIdx.x & 63;
-    const int side = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    const int ch = blockIdx.x*64 + lane;
-    const bool live = ch < L.n_ch;
-    const size_t n = (size_t) L.n_ch;
-    const int span = L.span;
-    int32_t *msg = win + 4*span*64;
+    const AdsiRxLaunch &V;
+    int32_t *sv;
+    AdsiRx v;
 
-    fsk_fill_wave(wave, L.quarter, threadIdx.x, 128);
-    int32_t *st = L.st + (live  ?  ch  :  0);
-    fsk_load_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
-    __syncthreads();
-
-    const int mylen = !live  ?  0  :  L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
-    const int n_blk = (L.samples + 7) >> 3;
-    const int16_t *pcm_row = L.pcm + (size_t) (live  ?  ch  :  0)*L.stride;
-    if (side == 0)
+    __device__ __forceinline__ void open(bool live, int ch, size_t n, int mylen)
     {
-        FskSigSide s;
-        fsk_sig_load(s, st, n);
-        auto frame = [&](auto aligned) __attribute__((always_inline))
-        {
-            FskRow<decltype(aligned)::value> row;
-            fsk_row_begin(row, pcm_row, mylen);
-            for (int blk = 0;  blk <= n_blk;  blk++)
-            {
-                if (blk < n_blk)
-                    fsk_sig_block(s, win, wave, msg + (blk & 1)*kFskMsgWords*64, lane, span, row, blk*8, max(0, min(8, mylen - blk*8)));
-                __syncthreads();
-            }
-        };
-        if (L.vec)
-            frame(std::true_type{});
-        else
-            frame(std::false_type{});
-        if (live)
-            fsk_sig_store(s, st, n);
-    }
-    else
-    {
-        FskBitSide t;
-        fsk_bit_load(t, st, n);
-        int32_t *sv = V.sv + (live  ?  ch  :  0);
-        const size_t mine = live  ?  (size_t) ch  :  0;
-        AdsiRx v;
+        sv = V.sv + ch;
         v.standard = sv[ADR_STANDARD*n];
         v.ones = sv[ADR_CONSECUTIVE_ONES*n];
         v.bit_pos = sv[ADR_BIT_POS*n];
@@ -599,40 +506,34 @@ __global__ __launch_bounds__(128) void adsi_rx_kernel(const AdsiRxLaunch V)
         v.msg_len = sv[ADR_MSG_LEN*n];
         v.framing_errors = sv[ADR_FRAMING_ERRORS*n];
         v.count = 0;
-        v.msg = V.msgs + mine*kAdsiMsg;
-        v.rec_bytes = V.rec_bytes + mine*V.cap*kAdsiMsg;
-        v.rec_lens = V.rec_lens + mine*V.cap;
+        v.msg = V.msgs + (size_t) ch*kAdsiMsg;
+        v.rec_bytes = V.rec_bytes + (size_t) ch*V.cap*kAdsiMsg;
+        v.rec_lens = V.rec_lens + (size_t) ch*V.cap;
         v.cap = live  ?  V.cap  :  0;
-        auto emit = [&](int b) __attribute__((always_inline)) { adsi_put_bit(v, b); };
-        auto frame = [&](auto aligned) __attribute__((always_inline))
-        {
-            FskRow<decltype(aligned)::value> row;
-            fsk_row_begin(row, pcm_row, mylen);
-            for (int blk = 0;  blk <= n_blk;  blk++)
-            {
-                if (blk > 0)
-                    fsk_bit_block<decltype(aligned)::value, false>(t, win, wave, msg + ((blk - 1) & 1)*kFskMsgWords*64, lane, span, row, (blk - 1)*8,
-                                  max(0, min(8, mylen - (blk - 1)*8)), emit);
-                __syncthreads();
-            }
-        };
-        if (L.vec)
-            frame(std::true_type{});
-        else
-            frame(std::false_type{});
-        if (live)
-        {
-            fsk_bit_store(t, st, n);
-            sv[ADR_CONSECUTIVE_ONES*n] = v.ones;
-            sv[ADR_BIT_POS*n] = v.bit_pos;
-            sv[ADR_IN_PROGRESS*n] = v.in_progress;
-            sv[ADR_MSG_LEN*n] = v.msg_len;
-            sv[ADR_FRAMING_ERRORS*n] = v.framing_errors;
-            V.counts[ch] = v.count;
-        }
     }
-    if (live)
-        fsk_store_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
+
+    __device__ __forceinline__ void put(FskBitSide &, int bit)
+    {
+        adsi_put_bit(v, bit);
+    }
+
+    __device__ __forceinline__ void close(FskBitSide &, int ch, size_t n)
+    {
+        sv[ADR_CONSECUTIVE_ONES*n] = v.ones;
+        sv[ADR_BIT_POS*n] = v.bit_pos;
+        sv[ADR_IN_PROGRESS*n] = v.in_progress;
+        sv[ADR_MSG_LEN*n] = v.msg_len;
+        sv[ADR_FRAMING_ERRORS*n] = v.framing_errors;
+        V.counts[ch] = v.count;
+    }
+};
+
+// adsi_rx() x N: the two-wave receiver (fsk_pair_body(), fsk_dev.hpp), asynchronous, with the message framer behind the
+// bit clock.
+__global__ __launch_bounds__(128) void adsi_rx_kernel(const AdsiRxLaunch V)
+{
+    AdsiRxSink sink = {V};
+    fsk_pair_body<FSK_FRAMING_NEVER>(V.f, sink);
 }
 
 }   // namespace spg

@@ -91,88 +91,35 @@ __global__ __launch_bounds__(64) void fsk_bank_kernel(const FskLaunch L)
     L.ev_count[ch] = r.n_ev;
 }
 
-// The same receiver as two waves per 64 channels (fsk_dev.hpp, "A receiver over two waves"): wave 0 is the signal
-// side, wave 1 the bit side, one block behind.
+// put_bit() of the plain receiver: one more entry of the channel's int16 event list
+struct FskEventSink
+{
+    const FskLaunch &L;
+    int16_t *ev;
+
+    __device__ __forceinline__ void open(bool live, int ch, size_t n, int mylen)
+    {
+        ev = L.events + (size_t) ch*L.ev_cap;
+    }
+
+    __device__ __forceinline__ void put(FskBitSide &t, int v)
+    {
+        if (t.n_ev < L.ev_cap)
+            ev[t.n_ev] = (int16_t) v;
+        t.n_ev++;
+    }
+
+    __device__ __forceinline__ void close(FskBitSide &t, int ch, size_t n)
+    {
+        L.ev_count[ch] = t.n_ev;
+    }
+};
+
+// The same receiver as two waves per 64 channels (fsk_pair_body(), fsk_dev.hpp): the framing is each channel's own
 __global__ __launch_bounds__(128) void fsk_pair_kernel(const FskLaunch L)
 {
-    extern __shared__ int32_t win[];        // [4*span][64], then the two message buffers [2][kFskMsgWords][64]
-    __shared__ uint32_t wave[kFskWave];
-    const int lane = threadIdx.x & 63;
-    const int side = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    const int ch = blockIdx.x*64 + lane;
-    const bool live = ch < L.n_ch;
-    const size_t n = (size_t) L.n_ch;
-    const int span = L.span;
-    int32_t *msg = win + 4*span*64;
-
-    fsk_fill_wave(wave, L.quarter, threadIdx.x, 128);
-    int32_t *st = L.st + (live  ?  ch  :  0);
-    fsk_load_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
-    __syncthreads();
-
-    const int mylen = !live  ?  0  :  L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
-    const int n_blk = (L.samples + 7) >> 3;
-    const int16_t *pcm_row = L.pcm + (size_t) (live  ?  ch  :  0)*L.stride;
-    if (side == 0)
-    {
-        FskSigSide s;
-        fsk_sig_load(s, st, n);
-        auto frame = [&](auto aligned) __attribute__((always_inline))
-        {
-            FskRow<decltype(aligned)::value> row;
-            fsk_row_begin(row, pcm_row, mylen);
-            for (int blk = 0;  blk <= n_blk;  blk++)
-            {
-                if (blk < n_blk)
-                    fsk_sig_block(s, win, wave, msg + (blk & 1)*kFskMsgWords*64, lane, span, row, blk*8, max(0, min(8, mylen - blk*8)));
-                __syncthreads();
-            }
-        };
-        if (L.vec)
-            frame(std::true_type{});
-        else
-            frame(std::false_type{});
-        if (live)
-            fsk_sig_store(s, st, n);
-    }
-    else
-    {
-        FskBitSide t;
-        fsk_bit_load(t, st, n);
-        int16_t *ev = L.events + (size_t) (live  ?  ch  :  0)*L.ev_cap;
-        const int ev_cap = L.ev_cap;
-        auto emit = [&](int v) __attribute__((always_inline))
-        {
-            if (t.n_ev < ev_cap)
-                ev[t.n_ev] = (int16_t) v;
-            t.n_ev++;
-        };
-        auto frame = [&](auto aligned, auto framed) __attribute__((always_inline))
-        {
-            FskRow<decltype(aligned)::value> row;
-            fsk_row_begin(row, pcm_row, mylen);
-            for (int blk = 0;  blk <= n_blk;  blk++)
-            {
-                if (blk > 0)
-                    fsk_bit_block<decltype(aligned)::value, decltype(framed)::value>(t, win, wave, msg + ((blk - 1) & 1)*kFskMsgWords*64, lane, span, row, (blk - 1)*8,
-                                  max(0, min(8, mylen - (blk - 1)*8)), emit);
-                __syncthreads();
-            }
-        };
-        if (!L.vec)
-            frame(std::false_type{}, std::true_type{});
-        else if (__any(live  &&  t.b.framing == 2))
-            frame(std::true_type{}, std::true_type{});
-        else
-            frame(std::true_type{}, std::false_type{});
-        if (live)
-        {
-            fsk_bit_store(t, st, n);
-            L.ev_count[ch] = t.n_ev;
-        }
-    }
-    if (live)
-        fsk_store_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
+    FskEventSink sink = {L, nullptr};
+    fsk_pair_body<FSK_FRAMING_BY_STATE>(L, sink);
 }
 
 }   // namespace spg

@@ -21,6 +21,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "dds_dev.hpp"
+
 namespace spg
 {
 
@@ -87,16 +89,6 @@ struct FskRegs
     int32_t n_ev;
 };
 
-// dds_lookup(), dds_int.c: one quadrant of a sine, mirrored and negated
-__device__ __forceinline__ int32_t fsk_lookup(const int16_t *quarter, uint32_t phase)
-{
-    const uint32_t p = phase >> 22;
-    uint32_t step = p & 255u;
-    step = (p & 256u)  ?  (256u - step)  :  step;
-    const int32_t amp = quarter[step];
-    return (p & 512u)  ?  -amp  :  amp;
-}
-
 // The kernels look the oscillators up in the same sine unfolded over the whole circle, with the cosine beside it:
 // wave[p] = sin(p) in the low half, sin(p + 256) = cos(p) in the high half, p = phase >> 22 (dds_complexi() takes
 // the cosine at phase + 2^30, which is p + 256 with no carry from below).  One LDS read and a shift per oscillator
@@ -108,8 +100,8 @@ __device__ __forceinline__ void fsk_fill_wave(uint32_t *wave, const int16_t *qua
 {
     for (int p = tid;  p < kFskWave;  p += n_threads)
     {
-        const uint32_t sn = (uint32_t) fsk_lookup(quarter_hbm, (uint32_t) p << 22) & 0xFFFFu;
-        const uint32_t cs = (uint32_t) fsk_lookup(quarter_hbm, (uint32_t) ((p + 256) & 1023) << 22) & 0xFFFFu;
+        const uint32_t sn = (uint32_t) dds_int_lookup(quarter_hbm, (uint32_t) p << 22) & 0xFFFFu;
+        const uint32_t cs = (uint32_t) dds_int_lookup(quarter_hbm, (uint32_t) ((p + 256) & 1023) << 22) & 0xFFFFu;
         wave[p] = sn | (cs << 16);
     }
 }
@@ -506,6 +498,15 @@ __device__ __forceinline__ void fsk_row_block(FskRow<VEC> &w, int base, int todo
 // over, per block of eight samples, what the detector made of each sample (a FSK_KIND_* nibble) and tone 0's
 // |dot|^2; the bit side follows one block behind (two message buffers in LDS, one barrier per block).  Each
 // side owns its half of every window slot and of the state words, in LDS and in HBM.
+//
+// fsk_pair_body() is that receiver whole, for every family that has an FSK demodulator in it: the LDS windows, message
+// buffers and sine, both sides' block loops, the aligned / unaligned copies and the two half-stores.  What a family does
+// with a demodulated bit is its SINK, a small struct the bit side calls:
+//   open(live, ch_or_0, n, mylen)      after fsk_bit_load(): the family's own words in, its output rows found.  A lane
+//                                      past the bank's end comes with live = false, channel 0 and mylen = 0;
+//   put(FskBitSide &, int bit)         put_bit(): a bit, a SIG_STATUS_* code or (framed) a character;
+//   close(FskBitSide &, ch, n)         for a live channel, after fsk_bit_store(): the family's words and counts out.
+// FRAMING says which copy of the bit clock the aligned and the unaligned rows run (fsk_bits<FRAMED>).
 
 constexpr int kFskMsgWords = 9;             // per lane and block: the kinds, then eight sums
 
@@ -713,6 +714,105 @@ __device__ __forceinline__ void fsk_bit_block(FskBitSide &t, int32_t *win, const
             }
         }
     }
+}
+
+enum
+{
+    FSK_FRAMING_BY_STATE = 0,   // unaligned rows framed; aligned rows framed only if a live channel frames characters
+    FSK_FRAMING_ALWAYS = 1,
+    FSK_FRAMING_NEVER = 2
+};
+
+// The body of a two-wave receiver kernel (128 threads; dynamic LDS [4*span][64] for the windows, then the two message
+// buffers [2][kFskMsgWords][64]): wave 0 is the signal side, wave 1 the bit side, one block behind.
+template <int FRAMING, class Sink>
+__device__ __forceinline__ void fsk_pair_body(const FskLaunch &L, Sink &sink)
+{
+    extern __shared__ int32_t win[];
+    __shared__ uint32_t wave[kFskWave];     // a separate object, so that table reads can move across window writes
+    const int lane = threadIdx.x & 63;
+    const int side = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int ch = blockIdx.x*64 + lane;
+    const bool live = ch < L.n_ch;
+    const size_t n = (size_t) L.n_ch;
+    const int span = L.span;
+    int32_t *msg = win + 4*span*64;
+
+    fsk_fill_wave(wave, L.quarter, threadIdx.x, 128);
+    // (a lane past the end of the bank reads channel 0's words and rows, takes every barrier and stores nothing)
+    int32_t *st = L.st + (live  ?  ch  :  0);
+    fsk_load_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
+    __syncthreads();
+
+    const int mylen = !live  ?  0  :  L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
+    const int n_blk = (L.samples + 7) >> 3;
+    const int16_t *pcm_row = L.pcm + (size_t) (live  ?  ch  :  0)*L.stride;
+    if (side == 0)
+    {
+        FskSigSide s;
+        fsk_sig_load(s, st, n);
+        auto frame = [&](auto aligned) __attribute__((always_inline))
+        {
+            FskRow<decltype(aligned)::value> row;
+            fsk_row_begin(row, pcm_row, mylen);
+            for (int blk = 0;  blk <= n_blk;  blk++)
+            {
+                if (blk < n_blk)
+                    fsk_sig_block(s, win, wave, msg + (blk & 1)*kFskMsgWords*64, lane, span, row, blk*8, max(0, min(8, mylen - blk*8)));
+                __syncthreads();
+            }
+        };
+        if (L.vec)
+            frame(std::true_type{});
+        else
+            frame(std::false_type{});
+        if (live)
+            fsk_sig_store(s, st, n);
+    }
+    else
+    {
+        FskBitSide t;
+        fsk_bit_load(t, st, n);
+        sink.open(live, live  ?  ch  :  0, n, mylen);
+        auto emit = [&](int v) __attribute__((always_inline)) { sink.put(t, v); };
+        auto frame = [&](auto aligned, auto framed) __attribute__((always_inline))
+        {
+            FskRow<decltype(aligned)::value> row;
+            fsk_row_begin(row, pcm_row, mylen);
+            for (int blk = 0;  blk <= n_blk;  blk++)
+            {
+                if (blk > 0)
+                    fsk_bit_block<decltype(aligned)::value, decltype(framed)::value>(t, win, wave, msg + ((blk - 1) & 1)*kFskMsgWords*64, lane, span, row, (blk - 1)*8,
+                                  max(0, min(8, mylen - (blk - 1)*8)), emit);
+                __syncthreads();
+            }
+        };
+        if (FRAMING == FSK_FRAMING_BY_STATE)
+        {
+            // (unaligned rows are the rare case: one copy, the general one)
+            if (!L.vec)
+                frame(std::false_type{}, std::true_type{});
+            else if (__any(live  &&  t.b.framing == 2))
+                frame(std::true_type{}, std::true_type{});
+            else
+                frame(std::true_type{}, std::false_type{});
+        }
+        else
+        {
+            const std::integral_constant<bool, FRAMING == FSK_FRAMING_ALWAYS> framed;
+            if (L.vec)
+                frame(std::true_type{}, framed);
+            else
+                frame(std::false_type{}, framed);
+        }
+        if (live)
+        {
+            fsk_bit_store(t, st, n);
+            sink.close(t, ch, n);
+        }
+    }
+    if (live)
+        fsk_store_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
 }
 
 }   // namespace spg

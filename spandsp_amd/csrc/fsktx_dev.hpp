@@ -4,16 +4,11 @@
 // What is restated (reference paths relative to the reference tree):
 //   fsk_tx()                       src/fsk.c:162-198       fsk_tx_restart()   src/fsk.c:221-235
 //   modem_connect_tones_tx()       src/modem_connect_tones.c:114-299          _tx_init()   :302-403
-//   dds_lookup() / dds_mod()       src/dds_int.c:340-355, 380-387   (257 entry quarter sine, phase >> 22)
 //
-// Both generators are integer only, and their DDS phase accumulators are uint32 and wrap, so every sample is a closed
-// form of its index: phase(i) = phase0 + (number of samples before i)*rate (+ 2^31 per phase hop).  The kernels have the
-// two-phase shape of tx_bank_kernel (txgen_dev.hpp):
-//   phase 1 (one lane per channel): walk the channel's bit boundaries / cadence and leave RUNS -- stretches of samples
-//            with one phase rate -- in LDS, consuming bits as it goes; no per-sample work;
-//   phase 2 (all 64 lanes over the wave's channels): a lane renders 8 adjacent samples (16 bytes) from the run(s) they
-//            fall in, so the stores of a channel's row are full and contiguous.
-// A channel with more runs than fit takes another round.  State is structure-of-arrays int32 words [words][n_channels].
+// The FSK modulator -- the runs, their walk and their rendering, the round loop -- is fskmod_dev.hpp, which the V.18 and
+// caller-ID senders share; here are the FSK banks' bit sources around it, and the connect tone sender, which has the same
+// two phases per round (phase 1, a lane per channel, leaves tone bursts in LDS; phase 2, all 64 lanes, renders 8 samples
+// each) with a round of its own.  State is structure-of-arrays int32 words [words][n_channels].
 //
 // Under the FAX transmit front end (txspan_dev.hpp) the same two kernel bodies run with every channel on its own span of the
 // row: phase 1 walks the channel's `count` samples, phase 2 renders them at row[start ..], unaligned.  The FSK sender then takes
@@ -27,78 +22,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fskmod_dev.hpp"
 #include "txspan_dev.hpp"
 
 namespace spg
 {
 
-// dds_lookup(), dds_int.c:340-355
-__device__ __forceinline__ int ftx_dds_lookup(const int16_t *quarter, uint32_t phase)
-{
-    phase >>= 22;
-    uint32_t step = phase & 255u;
-    if (phase & 256u)
-        step = 256u - step;
-    int amp = quarter[step];
-    if (phase & 512u)
-        amp = -amp;
-    return amp;
-}
-
-// dds_mod() without the accumulator update, dds_int.c:380-387
-__device__ __forceinline__ int ftx_dds_mod(const int16_t *quarter, uint32_t phase, int scale)
-{
-    return (int) (int16_t) ((ftx_dds_lookup(quarter, phase)*scale) >> 15);
-}
-
-// Eight samples of one row: one 16-byte store when the chunk is whole and the row allows it.
-__device__ __forceinline__ void ftx_store8(int16_t *at, const int v[8], int first, int last, bool vec)
-{
-    if (vec  &&  first == 0  &&  last == 8)
-    {
-        uint4 w;
-        w.x = ((uint32_t) v[0] & 0xFFFFu) | ((uint32_t) v[1] << 16);
-        w.y = ((uint32_t) v[2] & 0xFFFFu) | ((uint32_t) v[3] << 16);
-        w.z = ((uint32_t) v[4] & 0xFFFFu) | ((uint32_t) v[5] << 16);
-        w.w = ((uint32_t) v[6] & 0xFFFFu) | ((uint32_t) v[7] << 16);
-        *reinterpret_cast<uint4 *>(at) = w;
-        return;
-    }
-#pragma unroll
-    for (int j = 0;  j < 8;  j++)
-    {
-        if (j >= first  &&  j < last)
-            at[j] = (int16_t) v[j];
-    }
-}
-
 // ---- fsk_tx() ---------------------------------------------------------------------------------------------------------
 
-enum
-{
-    FT_BAUD_RATE = 0,       // baud x 100
-    FT_RATE0 = 1,           // phase_rates[0] (space), [1] (mark)
-    FT_RATE1 = 2,
-    FT_SCALING = 3,
-    FT_CUR_RATE = 4,        // current_phase_rate
-    FT_PHASE = 5,           // phase_acc
-    FT_BAUD_FRAC = 6,
-    FT_SHUTDOWN = 7,
-    FT_LFSR = 8,            // bit source SPANGPU_FSKTX_LFSR: the x^15 + x^14 + 1 register
-    FT_QRD = 9,             // bit source SPANGPU_FSKTX_QUEUE: read position and fill of the channel's ring, in bits
-    FT_QCOUNT = 10,
-    FT_EOD = 11,            // an empty ring answers SIG_STATUS_END_OF_DATA instead of a mark
-    FT_EVENT = 12,          // the channel shut down in the last call
-    kFskTxWords = 13
-};
-
 enum { FTX_SRC_LFSR = 0, FTX_SRC_QUEUE = 1 };
-
-constexpr int kFtxBaudUnit = 8000*100;      // SAMPLE_RATE*100
-constexpr int kFtxWaves = 4;                // waves per workgroup; they share one copy of the quarter sine
-constexpr int kFtxCpw = 16;                 // channels per wave
-constexpr int kFtxRuns = 32;                // runs of a channel per round: 1200 baud x 160 samples has 25
-constexpr int kFtxRunStride = kFtxRuns + 1; // odd: the 16 owner lanes write 16 different LDS banks
 
 struct FskTxLaunch
 {
@@ -116,144 +48,11 @@ struct FskTxLaunch
     TxSpans sp;                 // fsktx_span_kernel only
 };
 
-// The modulator's words while a call runs (fsk.c: baud_rate, phase_rates[], current_phase_rate, phase_acc, baud_frac)
-struct FtxMod
-{
-    int baud_rate;
-    int rate0;
-    int rate1;
-    int cur_rate;
-    int baud_frac;
-    uint32_t phase;
-};
-
-// Phase 1 of a round for one channel: the runs from sample `done` on, at most kFtxRuns of them, into the channel's LDS rows.
-// next_bit() stands for get_bit(): 0 or 1, or a negative value for SIG_STATUS_END_OF_DATA (fsk.c:179-189: the sample is not
-// made, the channel is shut down, `len` is what fsk_tx() returns).  Returns the number of runs.
-template <class NextBit>
-__device__ __forceinline__ int ftx_walk(FtxMod &m, int &done, int samples, bool &shutdown, int &len, int &zero_from, int32_t *r_start,
-                                        int32_t *r_phase, int32_t *r_rate, NextBit &&next_bit)
-{
-    r_start[0] = done;
-    r_phase[0] = (int32_t) m.phase;
-    r_rate[0] = m.cur_rate;
-    int nr = 1;
-    while (nr < kFtxRuns)
-    {
-        // the first sample k >= 0 ahead with baud_frac + (k + 1)*baud_rate >= 800000 (fsk.c:176); advancing
-        // run by run keeps every product inside 32 bits whatever the length of the call
-        const int kb = (kFtxBaudUnit - m.baud_frac + m.baud_rate - 1)/m.baud_rate - 1;
-        if (kb >= samples - done)
-        {
-            const int k = samples - done;
-            m.phase += (uint32_t) k*(uint32_t) m.cur_rate;
-            m.baud_frac += k*m.baud_rate;
-            done = samples;
-            break;
-        }
-        m.phase += (uint32_t) kb*(uint32_t) m.cur_rate;
-        done += kb;
-        m.baud_frac += (kb + 1)*m.baud_rate - kFtxBaudUnit;
-        const int bit = next_bit();
-        if (bit < 0)
-        {
-            // SIG_STATUS_END_OF_DATA, fsk.c:179-189: this sample is not made
-            shutdown = true;
-            len = done;
-            zero_from = done;
-            done = samples;
-            break;
-        }
-        m.cur_rate = bit  ?  m.rate1  :  m.rate0;
-        r_start[nr] = done;
-        r_phase[nr] = (int32_t) m.phase;
-        r_rate[nr] = m.cur_rate;
-        nr++;
-        m.phase += (uint32_t) m.cur_rate;
-        done++;
-        if (done >= samples)
-            break;
-    }
-    return nr;
-}
-
-// Phase 2 of a round for a wave: the samples of its channels' runs, 8 per lane.  r_hdr[c] = lo, hi, runs, zero_from, scaling, and
-// with SPANS the sample of the row the channel's call starts at.
-template <bool SPANS = false>
-__device__ __forceinline__ void ftx_render(const int16_t *quarter, const int32_t (*r_hdr)[8], const int32_t (*r_start)[kFtxRunStride],
-                                           const int32_t (*r_phase)[kFtxRunStride], const int32_t (*r_rate)[kFtxRunStride], int16_t *pcm,
-                                           long long stride, int ch0, int n_ch, int samples, int lane, bool vec)
-{
-    const int nchan = (n_ch - ch0 < kFtxCpw)  ?  (n_ch - ch0)  :  kFtxCpw;
-    const int cpr = (samples + 7) >> 3;
-    const int total = nchan*cpr;
-    for (int idx = lane;  idx < total;  idx += 64)
-    {
-        const int c = idx/cpr;
-        const int i0 = (idx - c*cpr)*8;
-        const int4 hdr = *reinterpret_cast<const int4 *>(&r_hdr[c][0]);     // lo, hi, runs, zero_from
-        const int a = (i0 > hdr.x)  ?  i0  :  hdr.x;
-        const int b = (i0 + 8 < hdr.y)  ?  (i0 + 8)  :  hdr.y;
-        if (a >= b)
-            continue;
-        const int scale = r_hdr[c][4];
-        const int32_t *S = r_start[c];
-        int r = 0;
-#pragma unroll
-        for (int step = kFtxRuns/2;  step > 0;  step >>= 1)
-            r += (r + step < hdr.z  &&  S[r + step] <= a)  ?  step  :  0;
-        int rate = 0;
-        uint32_t ph = 0u;
-        int next = 0x7FFFFFFF;
-        if (hdr.z > 0)
-        {
-            rate = r_rate[c][r];
-            ph = (uint32_t) r_phase[c][r] + (uint32_t) (a - S[r])*(uint32_t) rate;
-            next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
-        }
-        int v[8];
-#pragma unroll
-        for (int j = 0;  j < 8;  j++)
-        {
-            const int i = i0 + j;
-            v[j] = 0;
-            if (i >= a  &&  i < b)
-            {
-                while (i >= next)
-                {
-                    r++;
-                    rate = r_rate[c][r];
-                    ph = (uint32_t) r_phase[c][r];
-                    next = (r + 1 < hdr.z)  ?  S[r + 1]  :  0x7FFFFFFF;
-                }
-                if (i < hdr.w  &&  hdr.z > 0)
-                    v[j] = ftx_dds_mod(quarter, ph, scale);
-                ph += (uint32_t) rate;
-            }
-        }
-        ftx_store8(pcm + (size_t) (ch0 + c)*stride + (SPANS  ?  r_hdr[c][5]  :  0) + i0, v, a - i0, b - i0, vec);
-    }
-}
-
-// (a second unit that includes this header for ftx_walk() / ftx_render() alone -- v18_dev.hpp -- leaves the kernels out)
-#if !defined(SPG_FTX_WITHOUT_KERNELS)
-
 template <bool SPANS>
 __device__ __forceinline__ void fsktx_bank_body(const FskTxLaunch &L)
 {
-    __shared__ int16_t quarter[258];
-    __shared__ int32_t all_start[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ int32_t all_phase[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ int32_t all_rate[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ __attribute__((aligned(16))) int32_t all_hdr[kFtxWaves][kFtxCpw][8];
-
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    int32_t (*r_start)[kFtxRunStride] = all_start[wave];
-    int32_t (*r_phase)[kFtxRunStride] = all_phase[wave];
-    int32_t (*r_rate)[kFtxRunStride] = all_rate[wave];
-    int32_t (*r_hdr)[8] = all_hdr[wave];
-    const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
+    const int ch0 = (blockIdx.x*kFtxWaves + (threadIdx.x >> 6))*kFtxCpw;
     const int ch = ch0 + lane;
     const size_t n = (size_t) L.n_ch;
     bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
@@ -266,29 +65,18 @@ __device__ __forceinline__ void fsktx_bank_body(const FskTxLaunch &L)
             owner = span_of(L.sp, n, ch, L.samples, start, samples);
         samples = owner  ?  samples  :  0;
     }
-
-    for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
-        quarter[i] = L.quarter[i];
+    const FtxLds lds = ftx_lds(L.quarter);
 
     int32_t *st = L.st + (owner  ?  ch  :  0);
     SpanFramer fr;
-    FtxMod m = {1, 0, 0, 0, 0, 0u};
-    int scaling = 0;
-    bool shutdown = true;
+    FtxChan c;
+    ftx_chan_load(c, st, n, owner);
     uint32_t lfsr = 0u;
     int qrd = 0;
     int qcount = 0;
     bool eod = false;
     if (owner)
     {
-        m.baud_rate = st[FT_BAUD_RATE*n];
-        m.rate0 = st[FT_RATE0*n];
-        m.rate1 = st[FT_RATE1*n];
-        scaling = st[FT_SCALING*n];
-        m.cur_rate = st[FT_CUR_RATE*n];
-        m.phase = (uint32_t) st[FT_PHASE*n];
-        m.baud_frac = st[FT_BAUD_FRAC*n];
-        shutdown = st[FT_SHUTDOWN*n] != 0;
         if (SPANS)
         {
             fr.open(L.sp, n, ch);
@@ -304,11 +92,10 @@ __device__ __forceinline__ void fsktx_bank_body(const FskTxLaunch &L)
             eod = st[FT_EOD*n] != 0;
         }
     }
-    const bool was_shutdown = shutdown;
     int done = owner  ?  0  :  samples;
     int len = samples;          // what fsk_tx() returns
     int zero_from = 0x7FFFFFFF;
-    if (owner  &&  shutdown)
+    if (owner  &&  c.shutdown)
     {
         len = 0;
         zero_from = 0;
@@ -339,45 +126,15 @@ __device__ __forceinline__ void fsktx_bank_body(const FskTxLaunch &L)
         }
         return bit;
     };
-
-    for (;;)
-    {
-        // ---- phase 1: the next runs of my channel ----
-        const int lo = done;
-        int nr = 0;
-        if (owner  &&  done < samples)
-        {
-            if (shutdown)
-                done = samples;
-            else
-                nr = ftx_walk(m, done, samples, shutdown, len, zero_from, r_start[lane], r_phase[lane], r_rate[lane], next_bit);
-        }
-        if (lane < kFtxCpw)
-        {
-            r_hdr[lane][0] = lo;
-            r_hdr[lane][1] = done;
-            r_hdr[lane][2] = nr;
-            r_hdr[lane][3] = zero_from;
-            r_hdr[lane][4] = scaling;
-            if (SPANS)
-                r_hdr[lane][5] = start;
-        }
-        __syncthreads();
-
-        // ---- phase 2: the samples of those runs, 8 per lane ----
-        ftx_render<SPANS>(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, L.samples, lane, !SPANS  &&  L.vec != 0);
-        if (!__syncthreads_or(done < samples))
-            break;
-    }
+    // (a span starts at any sample of its row: no 16-byte stores)
+    ftx_rounds<SPANS>(lds, c, owner, c.shutdown, done, samples, len, zero_from, start, L.pcm, L.stride, ch0, L.n_ch, L.samples,
+                      !SPANS  &&  L.vec != 0, next_bit);
 
     if (owner)
     {
-        if (!was_shutdown)
+        if (!c.was_shutdown)
         {
-            st[FT_CUR_RATE*n] = m.cur_rate;
-            st[FT_PHASE*n] = (int32_t) m.phase;
-            st[FT_BAUD_FRAC*n] = m.baud_frac;
-            st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
+            ftx_chan_store(c, st, n);
             if (SPANS)
             {
                 // (nothing of the bank's own bit sources moved)
@@ -392,7 +149,7 @@ __device__ __forceinline__ void fsktx_bank_body(const FskTxLaunch &L)
                 st[FT_QCOUNT*n] = qcount;
             }
         }
-        st[FT_EVENT*n] = (shutdown  &&  !was_shutdown)  ?  1  :  0;
+        ftx_event_store(c, st, n);
         if (SPANS)
         {
             fr.close(L.sp, n, ch);
@@ -655,6 +412,5 @@ __global__ __launch_bounds__(64*kFtxWaves) void mcttx_span_kernel(const MctTxLau
     mcttx_bank_body<true>(L);
 }
 
-#endif
 
 }   // namespace spg

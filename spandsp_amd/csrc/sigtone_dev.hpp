@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "dds_dev.hpp"
+
 namespace spg
 {
 
@@ -400,17 +402,6 @@ struct SigTxLaunch
     int32_t scaling[2][2];
 };
 
-__device__ __forceinline__ int32_t sig_dds_lookup(const int16_t *quarter, uint32_t phase)
-{
-    // dds_lookup(), dds_int.c:340-355
-    phase >>= 22;
-    uint32_t step = phase & 255u;
-    if (phase & 256u)
-        step = 256u - step;
-    const int32_t amp = quarter[step];
-    return (phase & 512u)  ?  -amp  :  amp;
-}
-
 __global__ __launch_bounds__(64) void sigtone_tx_kernel(const SigTxLaunch L)
 {
     __shared__ int16_t quarter[260];
@@ -485,7 +476,7 @@ __global__ __launch_bounds__(64) void sigtone_tx_kernel(const SigTxLaunch L)
                     for (int j = i;  j < i + seg;  j++)
                     {
                         // dds_mod() and sat_add16()
-                        const int32_t v = (int32_t) (int16_t) ((sig_dds_lookup(quarter, phase[k])*scale) >> 15);
+                        const int32_t v = (int32_t) (int16_t) ((dds_int_lookup(quarter, phase[k])*scale) >> 15);
                         phase[k] += (uint32_t) L.phase_rate[k];
                         const int32_t z = (int32_t) row[j] + v;
                         row[j] = (int16_t) min(max(z, -32768), 32767);

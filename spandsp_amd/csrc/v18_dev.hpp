@@ -9,23 +9,21 @@
 //   v18_tx() / v18_rx()        src/v18.c:1806-1871, 1874-1940   (V18_AUTOMODING_NONE: the _42 states)
 //   async_tx_get_bit()         src/async.c:277-338     5 data bits, no parity, 2 stop bits
 //   queue_read_byte()          src/queue.c:197-220     a ring of 129 bytes that takes 128
-// What is used as it stands: the modulator (ftx_walk() / ftx_render(), fsktx_dev.hpp) with the character framer as its bit
-// source, and the framed demodulator over two waves (fsk_sig_block() / fsk_bit_block(), fsk_dev.hpp) with the Baudot
-// decoder as its put_bit.
+// What is used as it stands: the modulator and its round loop (ftx_rounds(), fskmod_dev.hpp) with the character framer as
+// its bit source, and the framed demodulator over two waves (fsk_pair_body(), fsk_dev.hpp) with the Baudot decoder as its
+// sink.
 //
 // State is structure-of-arrays int32 words [kV18Words + kFskTxWords + kFskScalars + 4*span][n_channels]: the text layer's
-// words, then the sender's in the layout of fsktx_dev.hpp, then the receiver's in the layout of fsk_dev.hpp.  The sender
+// words, then the sender's in the layout of fskmod_dev.hpp, then the receiver's in the layout of fsk_dev.hpp.  The sender
 // and the receiver of a channel share V18_RX_SUPPRESSION; both kernels run on the bank's stream, in the caller's order.
 
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <type_traits>
 
 #include "fsk_dev.hpp"
-#define SPG_FTX_WITHOUT_KERNELS
-#include "fsktx_dev.hpp"
+#include "fskmod_dev.hpp"
 
 namespace spg
 {
@@ -164,36 +162,20 @@ struct V18TxLaunch
     int vec;
 };
 
-// v18_tx() x N: the shape of fsktx_bank_kernel, with the Baudot framer as the modulator's bit source.  The character pull
-// happens in phase 1, at the bit boundary that starts a character: nothing of it is on the per-sample path.
+// v18_tx() x N: the FSK modulator (fskmod_dev.hpp) with the Baudot framer as its bit source.  The character pull happens in
+// phase 1, at the bit boundary that starts a character: nothing of it is on the per-sample path.
 __global__ __launch_bounds__(64*kFtxWaves) void v18_tx_kernel(const V18TxLaunch L)
 {
-    __shared__ int16_t quarter[258];
-    __shared__ int32_t all_start[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ int32_t all_phase[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ int32_t all_rate[kFtxWaves][kFtxCpw][kFtxRunStride];
-    __shared__ __attribute__((aligned(16))) int32_t all_hdr[kFtxWaves][kFtxCpw][8];
-
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    int32_t (*r_start)[kFtxRunStride] = all_start[wave];
-    int32_t (*r_phase)[kFtxRunStride] = all_phase[wave];
-    int32_t (*r_rate)[kFtxRunStride] = all_rate[wave];
-    int32_t (*r_hdr)[8] = all_hdr[wave];
-    const int ch0 = (blockIdx.x*kFtxWaves + wave)*kFtxCpw;
+    const int ch0 = (blockIdx.x*kFtxWaves + (threadIdx.x >> 6))*kFtxCpw;
     const int ch = ch0 + lane;
     const bool owner = (lane < kFtxCpw)  &&  (ch < L.n_ch);
-
-    for (int i = threadIdx.x;  i < 257;  i += 64*kFtxWaves)
-        quarter[i] = L.quarter[i];
+    const FtxLds lds = ftx_lds(L.quarter);
 
     const size_t n = (size_t) L.n_ch;
     int32_t *sv = L.st + (owner  ?  ch  :  0);
     int32_t *st = sv + (size_t) kV18Words*n;
     const int samples = L.samples;
-    FtxMod m = {1, 0, 0, 0, 0, 0u};
-    int scaling = 0;
-    bool shutdown = true;
     V18Tx t;
     t.signal_on = 0;
     t.draining = 0;
@@ -219,19 +201,12 @@ __global__ __launch_bounds__(64*kFtxWaves) void v18_tx_kernel(const V18TxLaunch 
         t.bitpos = sv[V18_A_BITPOS*n];
         t.frame = sv[V18_A_FRAME*n];
         t.presend = sv[V18_A_PRESEND*n];
-        m.baud_rate = st[FT_BAUD_RATE*n];
-        m.rate0 = st[FT_RATE0*n];
-        m.rate1 = st[FT_RATE1*n];
-        scaling = st[FT_SCALING*n];
-        m.cur_rate = st[FT_CUR_RATE*n];
-        m.phase = (uint32_t) st[FT_PHASE*n];
-        m.baud_frac = st[FT_BAUD_FRAC*n];
-        shutdown = st[FT_SHUTDOWN*n] != 0;
     }
+    FtxChan c;
+    ftx_chan_load(c, st, n, owner);
     // v18.c:1842-1865: with tx_signal_on clear nothing is asked of the modulator; a modulator that is shut down returns 0
     const bool asked = owner  &&  t.signal_on != 0;
-    const bool was_shutdown = shutdown;
-    bool silent = !asked  ||  shutdown;
+    const bool silent = !asked  ||  c.shutdown;
     int done = owner  ?  0  :  samples;
     int len = samples;
     int zero_from = 0x7FFFFFFF;
@@ -242,44 +217,16 @@ __global__ __launch_bounds__(64*kFtxWaves) void v18_tx_kernel(const V18TxLaunch 
     }
     __syncthreads();
 
-    auto next_bit = [&]() __attribute__((always_inline)) { return v18_next_bit(t); };
-
-    for (;;)
-    {
-        const int lo = done;
-        int nr = 0;
-        if (owner  &&  done < samples)
-        {
-            if (silent)
-                done = samples;
-            else
-                nr = ftx_walk(m, done, samples, shutdown, len, zero_from, r_start[lane], r_phase[lane], r_rate[lane], next_bit);
-            silent = silent  ||  shutdown;
-        }
-        if (lane < kFtxCpw)
-        {
-            r_hdr[lane][0] = lo;
-            r_hdr[lane][1] = done;
-            r_hdr[lane][2] = nr;
-            r_hdr[lane][3] = zero_from;
-            r_hdr[lane][4] = scaling;
-        }
-        __syncthreads();
-        ftx_render(quarter, r_hdr, r_start, r_phase, r_rate, L.pcm, L.stride, ch0, L.n_ch, samples, lane, L.vec != 0);
-        if (!__syncthreads_or(done < samples))
-            break;
-    }
+    ftx_rounds(lds, c, owner, silent, done, samples, len, zero_from, 0, L.pcm, L.stride, ch0, L.n_ch, samples, L.vec != 0,
+               [&]() __attribute__((always_inline)) { return v18_next_bit(t); });
 
     if (owner)
     {
         if (asked)
         {
-            if (!was_shutdown)
+            if (!c.was_shutdown)
             {
-                st[FT_CUR_RATE*n] = m.cur_rate;
-                st[FT_PHASE*n] = (int32_t) m.phase;
-                st[FT_BAUD_FRAC*n] = m.baud_frac;
-                st[FT_SHUTDOWN*n] = shutdown  ?  1  :  0;
+                ftx_chan_store(c, st, n);
                 sv[V18_TX_DRAINING*n] = t.draining;
                 sv[V18_BAUDOT_TX_SHIFT*n] = t.shift;
                 sv[V18_NEXT_BYTE*n] = t.next_byte;
@@ -292,7 +239,7 @@ __global__ __launch_bounds__(64*kFtxWaves) void v18_tx_kernel(const V18TxLaunch 
             // v18.c:1856-1857: a call that gets nothing out of the modulator turns the signal off
             sv[V18_TX_SIGNAL_ON*n] = (len <= 0)  ?  0  :  t.signal_on;
         }
-        st[FT_EVENT*n] = (shutdown  &&  !was_shutdown)  ?  1  :  0;
+        ftx_event_store(c, st, n);
         if (L.lens)
             L.lens[ch] = len;
     }
@@ -341,126 +288,70 @@ struct V18RxLaunch
     int cap;
 };
 
-// The text layer of one receiver while a call runs: v18_tdd_put_async_byte() as the demodulator's put_bit
-struct V18Rx
+// The text layer of one receiver while a call runs: v18_tdd_put_async_byte() as the demodulator's put_bit, the sink of
+// fsk_pair_body() (fsk_dev.hpp)
+struct V18RxSink
 {
+    const V18RxLaunch &V;
+    int32_t *sv;
+    uint8_t *out;
+    int cap;
     int shift, suppression, status, count;
-};
 
-__device__ __forceinline__ void v18_put_byte(V18Rx &v, const uint8_t *decode, uint8_t *out, int cap, int byte)
-{
-    if (byte < 0)
+    __device__ __forceinline__ void open(bool live, int ch, size_t n, int mylen)
     {
-        // carrier up and down only reset rx_msg_len, which is always 0 between characters in these modes
-        v.status |= (byte == -2)  ?  1  :  2;
-        return;
-    }
-    if (v.suppression > 0)
-        return;
-    if (byte == kV18FigureShift)
-    {
-        v.shift = 1;
-    }
-    else if (byte == kV18LetterShift)
-    {
-        v.shift = 0;
-    }
-    else
-    {
-        if (v.count < cap)
-            out[v.count] = decode[v.shift*32 + (byte & 0x1F)];
-        v.count++;
-    }
-}
-
-// v18_rx() x N: fsk_pair_kernel's two waves per 64 channels (fsk_dev.hpp, "A receiver over two waves"), framed, with the
-// suppression timer stepped ahead of the samples and the Baudot decoder behind the framer.
-__global__ __launch_bounds__(128) void v18_rx_kernel(const V18RxLaunch V)
-{
-    extern __shared__ int32_t win[];        // [4*span][64], then the two message buffers [2][kFskMsgWords][64]
-    __shared__ uint32_t wave[kFskWave];
-    const FskLaunch &L = V.f;
-    const int lane = threadIdx.x & 63;
-    const int side = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    const int ch = blockIdx.x*64 + lane;
-    const bool live = ch < L.n_ch;
-    const size_t n = (size_t) L.n_ch;
-    const int span = L.span;
-    int32_t *msg = win + 4*span*64;
-
-    fsk_fill_wave(wave, L.quarter, threadIdx.x, 128);
-    int32_t *st = L.st + (live  ?  ch  :  0);
-    fsk_load_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
-    __syncthreads();
-
-    const int mylen = !live  ?  0  :  L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
-    const int n_blk = (L.samples + 7) >> 3;
-    const int16_t *pcm_row = L.pcm + (size_t) (live  ?  ch  :  0)*L.stride;
-    if (side == 0)
-    {
-        FskSigSide s;
-        fsk_sig_load(s, st, n);
-        auto frame = [&](auto aligned) __attribute__((always_inline))
-        {
-            FskRow<decltype(aligned)::value> row;
-            fsk_row_begin(row, pcm_row, mylen);
-            for (int blk = 0;  blk <= n_blk;  blk++)
-            {
-                if (blk < n_blk)
-                    fsk_sig_block(s, win, wave, msg + (blk & 1)*kFskMsgWords*64, lane, span, row, blk*8, max(0, min(8, mylen - blk*8)));
-                __syncthreads();
-            }
-        };
-        if (L.vec)
-            frame(std::true_type{});
-        else
-            frame(std::false_type{});
-        if (live)
-            fsk_sig_store(s, st, n);
-    }
-    else
-    {
-        FskBitSide t;
-        fsk_bit_load(t, st, n);
-        int32_t *sv = V.sv + (live  ?  ch  :  0);
-        V18Rx v;
-        v.shift = sv[V18_BAUDOT_RX_SHIFT*n];
-        v.suppression = sv[V18_RX_SUPPRESSION*n];
-        v.status = 0;
-        v.count = 0;
+        sv = V.sv + ch;
+        shift = sv[V18_BAUDOT_RX_SHIFT*n];
+        suppression = sv[V18_RX_SUPPRESSION*n];
+        status = 0;
+        count = 0;
         // v18.c:1876-1884, ahead of the samples
-        v.suppression = (v.suppression > mylen)  ?  (v.suppression - mylen)  :  0;
-        const uint8_t *decode = V.tables + 128;
-        uint8_t *out = V.chars + (size_t) (live  ?  ch  :  0)*V.cap;
-        const int cap = live  ?  V.cap  :  0;
-        auto emit = [&](int b) __attribute__((always_inline)) { v18_put_byte(v, decode, out, cap, b); };
-        auto frame = [&](auto aligned) __attribute__((always_inline))
+        suppression = (suppression > mylen)  ?  (suppression - mylen)  :  0;
+        out = V.chars + (size_t) ch*V.cap;
+        cap = live  ?  V.cap  :  0;
+    }
+
+    __device__ __forceinline__ void put(FskBitSide &, int byte)
+    {
+        if (byte < 0)
         {
-            FskRow<decltype(aligned)::value> row;
-            fsk_row_begin(row, pcm_row, mylen);
-            for (int blk = 0;  blk <= n_blk;  blk++)
-            {
-                if (blk > 0)
-                    fsk_bit_block<decltype(aligned)::value, true>(t, win, wave, msg + ((blk - 1) & 1)*kFskMsgWords*64, lane, span, row, (blk - 1)*8,
-                                  max(0, min(8, mylen - (blk - 1)*8)), emit);
-                __syncthreads();
-            }
-        };
-        if (L.vec)
-            frame(std::true_type{});
+            // carrier up and down only reset rx_msg_len, which is always 0 between characters in these modes
+            status |= (byte == -2)  ?  1  :  2;
+            return;
+        }
+        if (suppression > 0)
+            return;
+        if (byte == kV18FigureShift)
+        {
+            shift = 1;
+        }
+        else if (byte == kV18LetterShift)
+        {
+            shift = 0;
+        }
         else
-            frame(std::false_type{});
-        if (live)
         {
-            fsk_bit_store(t, st, n);
-            sv[V18_BAUDOT_RX_SHIFT*n] = v.shift;
-            sv[V18_RX_SUPPRESSION*n] = v.suppression;
-            sv[V18_RX_STATUS*n] = v.status;
-            V.counts[ch] = v.count;
+            if (count < cap)
+                out[count] = V.tables[128 + shift*32 + (byte & 0x1F)];
+            count++;
         }
     }
-    if (live)
-        fsk_store_window_half(win, st + (size_t) kFskScalars*n, n, span, lane, side);
+
+    __device__ __forceinline__ void close(FskBitSide &, int ch, size_t n)
+    {
+        sv[V18_BAUDOT_RX_SHIFT*n] = shift;
+        sv[V18_RX_SUPPRESSION*n] = suppression;
+        sv[V18_RX_STATUS*n] = status;
+        V.counts[ch] = count;
+    }
+};
+
+// v18_rx() x N: the two-wave receiver (fsk_pair_body(), fsk_dev.hpp), framed, with the suppression timer stepped ahead of
+// the samples and the Baudot decoder behind the framer.
+__global__ __launch_bounds__(128) void v18_rx_kernel(const V18RxLaunch V)
+{
+    V18RxSink sink = {V};
+    fsk_pair_body<FSK_FRAMING_ALWAYS>(V.f, sink);
 }
 
 }   // namespace spg

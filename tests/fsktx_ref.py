@@ -148,7 +148,9 @@ class DeviceRows:
         assert self.hip.hipMalloc(C.byref(self.lens), n*4) == 0
 
     def fill(self, byte):
+        # (hipMemset of device memory returns before it has run, and the banks' streams do not wait for the null stream)
         assert self.hip.hipMemset(self.ptr, byte, self.n*self.stride*2) == 0
+        assert self.hip.hipDeviceSynchronize() == 0
 
     def rows(self):
         host = np.zeros((self.n, self.stride), np.int16)
