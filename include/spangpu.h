@@ -1555,7 +1555,9 @@ SPANGPU_API int spangpu_modem_shard_sync(spangpu_modem_shard_t *shard);
 /* ---- The receivers' inner primitives as batched entry points of their own (csrc/prim_api.hip) ----
    N independent items per launch, one lane each, in the reference's scalar order of operations (every product and sum rounded
    by itself): bit-exact with the reference's strict build on any input.  Rows are item-major; a stride of 0 shares one row
-   among all items; complex values are {re, im} float pairs and their strides count complex elements; mem says where ALL the
+   among all items (never a row the call writes), any other stride is at least a row long; an array of rows need be no longer
+   than stride*(items - 1) + row elements, and nothing past that is read or written (csrc/prim_stage.hpp: the one rule of all
+   these calls).  Complex values are {re, im} float pairs and their strides count complex elements; mem says where ALL the
    arrays of a call live (SPANGPU_MEM_HOST: copied in and out; SPANGPU_MEM_DEVICE: used in place, the call waits for the kernel).
      spangpu_vec_circular_dot_prodf_batch    vec_circular_dot_prodf(x, y, n, pos)      src/vector_float.c:890-900,932-939
      spangpu_vec_circular_lmsf_batch         vec_circular_lmsf(x, y, n, pos, error)     src/vector_float.c:942,982-1000

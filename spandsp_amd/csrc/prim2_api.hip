@@ -15,6 +15,7 @@
 
 #include "../../include/spangpu.h"
 #include "bank_host.hpp"
+#include "prim_stage_hip.hpp"
 #include "modem_tables.h"
 #include "v29_common.hpp"
 
@@ -136,62 +137,6 @@ __global__ void arctan2_kernel(const float *y, const float *x, int32_t *out, int
     out[i] = spg::v29_arctan2(y[i], x[i]);
 }
 
-template <typename T>
-int to_device(const T *src, size_t count, int mem, T **dev, bool *owned)
-{
-    *owned = false;
-    if (mem == SPANGPU_MEM_DEVICE)
-    {
-        *dev = (T *) src;
-        return SPANGPU_OK;
-    }
-    SPG_TRY(hipMalloc((void **) dev, count*sizeof(T) + 16));
-    if (hipMemcpy(*dev, src, count*sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-    {
-        (void) hipFree(*dev);
-        *dev = nullptr;
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipMemcpy (host to device) failed");
-    }
-    *owned = true;
-    return SPANGPU_OK;
-}
-
-struct Held
-{
-    void *p[8];
-    int n = 0;
-    ~Held()
-    {
-        for (int i = 0;  i < n;  i++)
-            (void) hipFree(p[i]);
-    }
-    void keep(void *q, bool owned)
-    {
-        if (owned)
-            p[n++] = q;
-    }
-};
-
-int ready(int device, int items, int n, const void *a, const void *b, const void *c)
-{
-    if (items <= 0  ||  n <= 0  ||  a == nullptr  ||  b == nullptr  ||  c == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (spangpu_device_count() <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    SPG_TRY(hipSetDevice(device));
-    return SPANGPU_OK;
-}
-
-int finish(int mem, void *host, const void *dev, size_t bytes)
-{
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
-}
-
 // the receivers' sine and square root tables on a device, made once per device (host code: modem_tables.c)
 constexpr int kMaxDevices = 16;
 float *g_sine[kMaxDevices];
@@ -226,177 +171,156 @@ int tables(int device, const float **sine, const uint16_t **sq)
 
 }   // namespace
 
+using namespace spg;
+
 extern "C" {
 
 // complex values as {re, im} float pairs (complexf_t); strides in complex elements, 0 = the same row for every item
+// (len 1: a coefficient row of none, nothing of coeffs is read and the result is (0, 0), the reference's loop of no iterations)
 int spangpu_periodogram_batch(int device, const float *coeffs, long long c_stride, const float *amp, long long a_stride, float *out,
                               int items, int len, int mem)
 {
-    int rc = ready(device, items, len, coeffs, amp, out);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ec, ea, eo;
+    int rc;
+    if ((rc = call.args_ok(items, len, {coeffs, amp, out})) < 0  ||  (rc = call.arg(kPgramCoeffs, c_stride, items, len, &ec)) < 0
+        ||  (rc = call.arg(kPgramAmp, a_stride, items, len, &ea)) < 0  ||  (rc = call.arg(kPgramOut, 0, items, len, &eo)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
-    if (c_stride < 0  ||  a_stride < 0  ||  (c_stride != 0  &&  c_stride < len/2)  ||  (a_stride != 0  &&  a_stride < len))
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a stride is 0 (one row for all items) or at least a row long");
-    Held h;
-    float *dc, *da, *dout;
-    bool o;
-    if ((rc = to_device(coeffs, 2*(c_stride  ?  (size_t) c_stride*items  :  (size_t) (len/2) + 1), mem, &dc, &o)) < 0) return rc;
-    h.keep(dc, o);
-    if ((rc = to_device(amp, 2*(a_stride  ?  (size_t) a_stride*items  :  (size_t) len), mem, &da, &o)) < 0) return rc;
-    h.keep(da, o);
-    if ((rc = to_device((const float *) out, 2*(size_t) items, mem, &dout, &o)) < 0) return rc;
-    h.keep(dout, o);
-    hipLaunchKernelGGL(periodogram_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) dc, c_stride, (const float2 *) da, a_stride,
-                       (float2 *) dout, items, len);
-    return finish(mem, out, dout, 2*(size_t) items*sizeof(float));
+    float2 *dc, *da, *dout;
+    if ((rc = call.stage(kPgramCoeffs, (const float2 *) coeffs, ec, &dc)) < 0  ||  (rc = call.stage(kPgramAmp, (const float2 *) amp, ea, &da)) < 0
+        ||  (rc = call.stage(kPgramOut, (const float2 *) out, eo, &dout)) < 0)
+        return rc;
+    hipLaunchKernelGGL(periodogram_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dc, c_stride, da, a_stride, dout, items, len);
+    return call.finish();
 }
 
 // sum and diff: [items][len/2] complex each
 int spangpu_periodogram_prepare_batch(int device, const float *amp, long long a_stride, float *sum, float *diff, int items, int len, int mem)
 {
-    int rc = ready(device, items, len, amp, sum, diff);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ea, es, ed;
+    int rc;
+    if ((rc = call.args_ok(items, len, {amp, sum, diff})) < 0)
         return rc;
-    if (len < 2  ||  a_stride < 0  ||  (a_stride != 0  &&  a_stride < len))
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad length or stride");
-    Held h;
-    float *da, *ds, *dd;
-    bool o;
-    const size_t half = (size_t) (len/2);
-    if ((rc = to_device(amp, 2*(a_stride  ?  (size_t) a_stride*items  :  (size_t) len), mem, &da, &o)) < 0) return rc;
-    h.keep(da, o);
-    if ((rc = to_device((const float *) sum, 2*half*items, mem, &ds, &o)) < 0) return rc;
-    h.keep(ds, o);
-    if ((rc = to_device((const float *) diff, 2*half*items, mem, &dd, &o)) < 0) return rc;
-    h.keep(dd, o);
-    hipLaunchKernelGGL(periodogram_prepare_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) da, a_stride, (float2 *) ds, (float2 *) dd, items, len);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-    {
-        SPG_TRY(hipMemcpy(sum, ds, 2*half*items*sizeof(float), hipMemcpyDeviceToHost));
-        SPG_TRY(hipMemcpy(diff, dd, 2*half*items*sizeof(float), hipMemcpyDeviceToHost));
-    }
-    else
-    {
-        SPG_TRY(hipDeviceSynchronize());
-    }
-    return (int) half;
+    if (len < 2)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad length");
+    if ((rc = call.arg(kPrepAmp, a_stride, items, len, &ea)) < 0  ||  (rc = call.arg(kPrepSum, 0, items, len, &es)) < 0
+        ||  (rc = call.arg(kPrepDiff, 0, items, len, &ed)) < 0  ||  (rc = call.ready(device)) < 0)
+        return rc;
+    float2 *da, *ds, *dd;
+    if ((rc = call.stage(kPrepAmp, (const float2 *) amp, ea, &da)) < 0  ||  (rc = call.stage(kPrepSum, (const float2 *) sum, es, &ds)) < 0
+        ||  (rc = call.stage(kPrepDiff, (const float2 *) diff, ed, &dd)) < 0)
+        return rc;
+    hipLaunchKernelGGL(periodogram_prepare_kernel, dim3((items + 63)/64), dim3(64), 0, 0, da, a_stride, ds, dd, items, len);
+    if ((rc = call.finish()) < 0)
+        return rc;
+    return len/2;
 }
 
 int spangpu_periodogram_apply_batch(int device, const float *coeffs, long long c_stride, const float *sum, const float *diff, float *out,
                                     int items, int len, int mem)
 {
-    int rc = ready(device, items, len, coeffs, sum, diff);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ec, es, ed, eo;
+    int rc;
+    if ((rc = call.args_ok(items, len, {coeffs, sum, diff, out})) < 0)
         return rc;
-    if (out == nullptr  ||  len < 2  ||  c_stride < 0  ||  (c_stride != 0  &&  c_stride < len/2))
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    Held h;
-    float *dc, *ds, *dd, *dout;
-    bool o;
-    const size_t half = (size_t) (len/2);
-    if ((rc = to_device(coeffs, 2*(c_stride  ?  (size_t) c_stride*items  :  half), mem, &dc, &o)) < 0) return rc;
-    h.keep(dc, o);
-    if ((rc = to_device(sum, 2*half*items, mem, &ds, &o)) < 0) return rc;
-    h.keep(ds, o);
-    if ((rc = to_device(diff, 2*half*items, mem, &dd, &o)) < 0) return rc;
-    h.keep(dd, o);
-    if ((rc = to_device((const float *) out, 2*(size_t) items, mem, &dout, &o)) < 0) return rc;
-    h.keep(dout, o);
-    hipLaunchKernelGGL(periodogram_apply_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) dc, c_stride, (const float2 *) ds,
-                       (const float2 *) dd, (float2 *) dout, items, len);
-    return finish(mem, out, dout, 2*(size_t) items*sizeof(float));
+    if (len < 2)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad length");
+    if ((rc = call.arg(kApplyCoeffs, c_stride, items, len, &ec)) < 0  ||  (rc = call.arg(kApplySum, 0, items, len, &es)) < 0
+        ||  (rc = call.arg(kApplyDiff, 0, items, len, &ed)) < 0  ||  (rc = call.arg(kApplyOut, 0, items, len, &eo)) < 0
+        ||  (rc = call.ready(device)) < 0)
+        return rc;
+    float2 *dc, *ds, *dd, *dout;
+    if ((rc = call.stage(kApplyCoeffs, (const float2 *) coeffs, ec, &dc)) < 0  ||  (rc = call.stage(kApplySum, (const float2 *) sum, es, &ds)) < 0
+        ||  (rc = call.stage(kApplyDiff, (const float2 *) diff, ed, &dd)) < 0  ||  (rc = call.stage(kApplyOut, (const float2 *) out, eo, &dout)) < 0)
+        return rc;
+    hipLaunchKernelGGL(periodogram_apply_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dc, c_stride, ds, dd, dout, items, len);
+    return call.finish();
 }
 
-// phase_offset: the {re, im} periodogram_generate_phase_offset() made (host memory); last / result: [items] complex
+// phase_offset: the {re, im} periodogram_generate_phase_offset() made (host memory, whatever mem says); last / result: [items] complex
 int spangpu_periodogram_freq_error_batch(int device, const float *phase_offset, float scale, const float *last_result, const float *result,
                                          float *out, int items, int mem)
 {
-    int rc = ready(device, items, 1, phase_offset, last_result, result);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t el, er, eo;
+    int rc;
+    if ((rc = call.args_ok(items, 1, {phase_offset, last_result, result, out})) < 0  ||  (rc = call.arg(kFreqErrLast, 0, items, 1, &el)) < 0
+        ||  (rc = call.arg(kFreqErrNow, 0, items, 1, &er)) < 0  ||  (rc = call.arg(kFreqErrOut, 0, items, 1, &eo)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
-    if (out == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null output");
-    Held h;
-    float *dl, *dr, *dout;
-    bool o;
-    if ((rc = to_device(last_result, 2*(size_t) items, mem, &dl, &o)) < 0) return rc;
-    h.keep(dl, o);
-    if ((rc = to_device(result, 2*(size_t) items, mem, &dr, &o)) < 0) return rc;
-    h.keep(dr, o);
-    if ((rc = to_device((const float *) out, (size_t) items, mem, &dout, &o)) < 0) return rc;
-    h.keep(dout, o);
+    float2 *dl, *dr;
+    float *dout;
+    if ((rc = call.stage(kFreqErrLast, (const float2 *) last_result, el, &dl)) < 0  ||  (rc = call.stage(kFreqErrNow, (const float2 *) result, er, &dr)) < 0
+        ||  (rc = call.stage(kFreqErrOut, (const float *) out, eo, &dout)) < 0)
+        return rc;
     hipLaunchKernelGGL(periodogram_freq_error_kernel, dim3((items + 63)/64), dim3(64), 0, 0, make_float2(phase_offset[0], phase_offset[1]), scale,
-                       (const float2 *) dl, (const float2 *) dr, dout, items);
-    return finish(mem, out, dout, (size_t) items*sizeof(float));
+                       dl, dr, dout, items);
+    return call.finish();
 }
 
 int spangpu_fixed_sqrt32_batch(int device, const uint32_t *x, uint16_t *out, int items, int mem)
 {
-    int rc = ready(device, items, 1, x, out, out);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ex, eo;
+    int rc;
+    if ((rc = call.args_ok(items, 1, {x, out})) < 0  ||  (rc = call.arg(kSqrtX, 0, items, 1, &ex)) < 0
+        ||  (rc = call.arg(kSqrtOut, 0, items, 1, &eo)) < 0  ||  (rc = call.ready(device)) < 0)
         return rc;
     const float *sine;
     const uint16_t *sq;
     if ((rc = tables(device, &sine, &sq)) < 0)
         return rc;
-    Held h;
     uint32_t *dx;
     uint16_t *dout;
-    bool o;
-    if ((rc = to_device(x, (size_t) items, mem, &dx, &o)) < 0) return rc;
-    h.keep(dx, o);
-    if ((rc = to_device((const uint16_t *) out, (size_t) items, mem, &dout, &o)) < 0) return rc;
-    h.keep(dout, o);
-    hipLaunchKernelGGL(fixed_sqrt32_kernel, dim3((items + 255)/256), dim3(256), 0, 0, sq, (const uint32_t *) dx, dout, items);
-    return finish(mem, out, dout, (size_t) items*sizeof(uint16_t));
+    if ((rc = call.stage(kSqrtX, x, ex, &dx)) < 0  ||  (rc = call.stage(kSqrtOut, (const uint16_t *) out, eo, &dout)) < 0)
+        return rc;
+    hipLaunchKernelGGL(fixed_sqrt32_kernel, dim3((items + 255)/256), dim3(256), 0, 0, sq, dx, dout, items);
+    return call.finish();
 }
 
 // out: [items][n] complex; phase_acc[items] is advanced n times by phase_rate[items]
 int spangpu_dds_complexf_batch(int device, uint32_t *phase_acc, const int32_t *phase_rate, float *out, int items, int n, int mem)
 {
-    int rc = ready(device, items, n, phase_acc, phase_rate, out);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ea, er, eo;
+    int rc;
+    if ((rc = call.args_ok(items, n, {phase_acc, phase_rate, out})) < 0  ||  (rc = call.arg(kDdsAcc, 0, items, n, &ea)) < 0
+        ||  (rc = call.arg(kDdsRate, 0, items, n, &er)) < 0  ||  (rc = call.arg(kDdsOut, 0, items, n, &eo)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
     const float *sine;
     const uint16_t *sq;
     if ((rc = tables(device, &sine, &sq)) < 0)
         return rc;
-    Held h;
     uint32_t *da;
     int32_t *dr;
-    float *dout;
-    bool o;
-    if ((rc = to_device((const uint32_t *) phase_acc, (size_t) items, mem, &da, &o)) < 0) return rc;
-    h.keep(da, o);
-    if ((rc = to_device(phase_rate, (size_t) items, mem, &dr, &o)) < 0) return rc;
-    h.keep(dr, o);
-    if ((rc = to_device((const float *) out, 2*(size_t) items*n, mem, &dout, &o)) < 0) return rc;
-    h.keep(dout, o);
-    hipLaunchKernelGGL(dds_complexf_kernel, dim3((items + 63)/64), dim3(64), 0, 0, sine, da, (const int32_t *) dr, (float2 *) dout, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(phase_acc, da, (size_t) items*sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return finish(mem, out, dout, 2*(size_t) items*n*sizeof(float));
+    float2 *dout;
+    if ((rc = call.stage(kDdsAcc, (const uint32_t *) phase_acc, ea, &da)) < 0  ||  (rc = call.stage(kDdsRate, phase_rate, er, &dr)) < 0
+        ||  (rc = call.stage(kDdsOut, (const float2 *) out, eo, &dout)) < 0)
+        return rc;
+    hipLaunchKernelGGL(dds_complexf_kernel, dim3((items + 63)/64), dim3(64), 0, 0, sine, da, dr, dout, items, n);
+    return call.finish();
 }
 
 int spangpu_arctan2_batch(int device, const float *y, const float *x, int32_t *out, int items, int mem)
 {
-    int rc = ready(device, items, 1, y, x, out);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ey, ex, eo;
+    int rc;
+    if ((rc = call.args_ok(items, 1, {y, x, out})) < 0  ||  (rc = call.arg(kAtanY, 0, items, 1, &ey)) < 0
+        ||  (rc = call.arg(kAtanX, 0, items, 1, &ex)) < 0  ||  (rc = call.arg(kAtanOut, 0, items, 1, &eo)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
-    Held h;
     float *dy, *dx;
     int32_t *dout;
-    bool o;
-    if ((rc = to_device(y, (size_t) items, mem, &dy, &o)) < 0) return rc;
-    h.keep(dy, o);
-    if ((rc = to_device(x, (size_t) items, mem, &dx, &o)) < 0) return rc;
-    h.keep(dx, o);
-    if ((rc = to_device((const int32_t *) out, (size_t) items, mem, &dout, &o)) < 0) return rc;
-    h.keep(dout, o);
-    hipLaunchKernelGGL(arctan2_kernel, dim3((items + 255)/256), dim3(256), 0, 0, (const float *) dy, (const float *) dx, dout, items);
-    return finish(mem, out, dout, (size_t) items*sizeof(int32_t));
+    if ((rc = call.stage(kAtanY, y, ey, &dy)) < 0  ||  (rc = call.stage(kAtanX, x, ex, &dx)) < 0
+        ||  (rc = call.stage(kAtanOut, (const int32_t *) out, eo, &dout)) < 0)
+        return rc;
+    hipLaunchKernelGGL(arctan2_kernel, dim3((items + 255)/256), dim3(256), 0, 0, dy, dx, dout, items);
+    return call.finish();
 }
 
 }   // extern "C"

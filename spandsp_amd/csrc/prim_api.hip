@@ -11,12 +11,15 @@
 //   cvec_circular_dot_prodf  src/complex_vector_float.c:137-150, 187-196 (non-conjugating; the two parts added at the end)
 //   cvec_circular_lmsf       src/complex_vector_float.c:201-219
 //   power_meter_update       src/power_meter.c:65-70 (over a row of samples; the reading after the last one)
-// Rows are item-major ([item][n]); x and y of an item may be the same for all items (stride 0).
+// Rows are item-major ([item][n]); x and y of an item may be the same for all items (stride 0).  Which strides a call takes and
+// how many elements of an array it stages and copies back is prim_stage.hpp's rule, for this file and prim2_api.hip alike; the
+// entry points hold no count of their own (prim_stage_hip.hpp: check, stage, finish).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/spangpu.h"
 #include "bank_host.hpp"
+#include "prim_stage_hip.hpp"
 
 namespace {
 
@@ -181,276 +184,146 @@ __global__ void godard_baud_kernel(uint32_t *state, const uint32_t *desc, long l
     correction[i] = corr;
 }
 
-// bring a host array to the device (or pass a device pointer through); *owned says whether to free it
-template <typename T>
-int stage_in(const T *src, size_t count, int mem, T **dev, bool *owned)
-{
-    *owned = false;
-    if (mem == SPANGPU_MEM_DEVICE)
-    {
-        *dev = (T *) src;
-        return SPANGPU_OK;
-    }
-    SPG_TRY(hipMalloc((void **) dev, count*sizeof(T) + 16));
-    if (hipMemcpy(*dev, src, count*sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-    {
-        (void) hipFree(*dev);           // (the caller's Staged has not been told of it yet)
-        *dev = nullptr;
-        return spangpu_set_error(SPANGPU_ERR_HIP, "hipMemcpy (host to device) failed");
-    }
-    *owned = true;
-    return SPANGPU_OK;
-}
-
-struct Staged
-{
-    void *p[6];
-    int n = 0;
-    ~Staged()
-    {
-        for (int i = 0;  i < n;  i++)
-            (void) hipFree(p[i]);
-    }
-    void keep(void *q, bool owned)
-    {
-        if (owned)
-            p[n++] = q;
-    }
-};
-
-int check(int device, int items, int n, const void *a, const void *b, const void *c, const void *d)
-{
-    if (items <= 0  ||  n <= 0  ||  a == nullptr  ||  b == nullptr  ||  c == nullptr  ||  d == nullptr)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    if (spangpu_device_count() <= 0)
-        return spangpu_set_error(SPANGPU_ERR_NO_DEVICE, "no HIP device: libspangpu has no CPU fallback");
-    SPG_TRY(hipSetDevice(device));
-    return SPANGPU_OK;
-}
-
-// positions in host memory are looked at before anything is staged
-int check_pos(const int32_t *pos, int items, int n, int mem)
-{
-    if (mem != SPANGPU_MEM_HOST)
-        return SPANGPU_OK;
-    for (int i = 0;  i < items;  i++)
-    {
-        if (pos[i] < 0  ||  pos[i] > n)
-            return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a position outside its row (0 <= pos <= n)");
-    }
-    return SPANGPU_OK;
-}
-
 }   // namespace
+
+using namespace spg;
 
 extern "C" {
 
 int spangpu_vec_circular_dot_prodf_batch(int device, const float *x, long long x_stride, const float *y, long long y_stride, const int32_t *pos,
                                          float *z, int items, int n, int mem)
 {
-    int rc = check(device, items, n, x, y, pos, z);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ex, ey, ep, ez;
+    int rc;
+    if ((rc = call.args_ok(items, n, {x, y, pos, z})) < 0  ||  (rc = call.arg(kVecDotX, x_stride, items, n, &ex)) < 0
+        ||  (rc = call.arg(kVecDotY, y_stride, items, n, &ey)) < 0  ||  (rc = call.arg(kVecDotPos, 0, items, n, &ep)) < 0
+        ||  (rc = call.arg(kVecDotZ, 0, items, n, &ez)) < 0  ||  (rc = call.pos_ok(pos, items, n)) < 0  ||  (rc = call.ready(device)) < 0)
         return rc;
-    if ((rc = check_pos(pos, items, n, mem)) != SPANGPU_OK)
-        return rc;
-    Staged st;
     float *dx, *dy, *dz;
     int32_t *dp;
-    bool o;
-    if ((rc = stage_in(x, (size_t) (x_stride  ?  (size_t) x_stride*items  :  (size_t) n), mem, &dx, &o)) < 0) return rc;
-    st.keep(dx, o);
-    if ((rc = stage_in(y, (size_t) (y_stride  ?  (size_t) y_stride*items  :  (size_t) n), mem, &dy, &o)) < 0) return rc;
-    st.keep(dy, o);
-    if ((rc = stage_in(pos, (size_t) items, mem, &dp, &o)) < 0) return rc;
-    st.keep(dp, o);
-    if ((rc = stage_in(z, (size_t) items, mem, &dz, &o)) < 0) return rc;
-    st.keep(dz, o);
+    if ((rc = call.stage(kVecDotX, x, ex, &dx)) < 0  ||  (rc = call.stage(kVecDotY, y, ey, &dy)) < 0
+        ||  (rc = call.stage(kVecDotPos, pos, ep, &dp)) < 0  ||  (rc = call.stage(kVecDotZ, (const float *) z, ez, &dz)) < 0)
+        return rc;
     hipLaunchKernelGGL(vec_circ_dot_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dx, x_stride, dy, y_stride, dp, dz, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(z, dz, (size_t) items*sizeof(float), hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
+    return call.finish();
 }
 
 int spangpu_vec_circular_lmsf_batch(int device, const float *x, long long x_stride, float *y, long long y_stride, const int32_t *pos,
                                     const float *error, int items, int n, int mem)
 {
-    int rc = check(device, items, n, x, y, pos, error);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ex, ey, ep, ee;
+    int rc;
+    if ((rc = call.args_ok(items, n, {x, y, pos, error})) < 0  ||  (rc = call.arg(kVecLmsX, x_stride, items, n, &ex)) < 0
+        ||  (rc = call.arg(kVecLmsY, y_stride, items, n, &ey)) < 0  ||  (rc = call.arg(kVecLmsPos, 0, items, n, &ep)) < 0
+        ||  (rc = call.arg(kVecLmsErr, 0, items, n, &ee)) < 0  ||  (rc = call.pos_ok(pos, items, n)) < 0  ||  (rc = call.ready(device)) < 0)
         return rc;
-    if ((rc = check_pos(pos, items, n, mem)) != SPANGPU_OK)
-        return rc;
-    if (y_stride < n)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "the rows of y are written: they cannot overlap");
-    Staged st;
     float *dx, *dy, *de;
     int32_t *dp;
-    bool o;
-    if ((rc = stage_in(x, (size_t) (x_stride  ?  (size_t) x_stride*items  :  (size_t) n), mem, &dx, &o)) < 0) return rc;
-    st.keep(dx, o);
-    if ((rc = stage_in((const float *) y, (size_t) y_stride*items, mem, &dy, &o)) < 0) return rc;
-    st.keep(dy, o);
-    if ((rc = stage_in(pos, (size_t) items, mem, &dp, &o)) < 0) return rc;
-    st.keep(dp, o);
-    if ((rc = stage_in(error, (size_t) items, mem, &de, &o)) < 0) return rc;
-    st.keep(de, o);
+    if ((rc = call.stage(kVecLmsX, x, ex, &dx)) < 0  ||  (rc = call.stage(kVecLmsY, (const float *) y, ey, &dy)) < 0
+        ||  (rc = call.stage(kVecLmsPos, pos, ep, &dp)) < 0  ||  (rc = call.stage(kVecLmsErr, error, ee, &de)) < 0)
+        return rc;
     hipLaunchKernelGGL(vec_circ_lms_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dx, x_stride, dy, y_stride, dp, de, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(y, dy, (size_t) y_stride*items*sizeof(float), hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
+    return call.finish();
 }
 
 // complex values as {re, im} float pairs (complexf_t); strides in complex elements
 int spangpu_cvec_circular_dot_prodf_batch(int device, const float *x, long long x_stride, const float *y, long long y_stride, const int32_t *pos,
                                           float *z, int items, int n, int mem)
 {
-    int rc = check(device, items, n, x, y, pos, z);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ex, ey, ep, ez;
+    int rc;
+    if ((rc = call.args_ok(items, n, {x, y, pos, z})) < 0  ||  (rc = call.arg(kCvecDotX, x_stride, items, n, &ex)) < 0
+        ||  (rc = call.arg(kCvecDotY, y_stride, items, n, &ey)) < 0  ||  (rc = call.arg(kCvecDotPos, 0, items, n, &ep)) < 0
+        ||  (rc = call.arg(kCvecDotZ, 0, items, n, &ez)) < 0  ||  (rc = call.pos_ok(pos, items, n)) < 0  ||  (rc = call.ready(device)) < 0)
         return rc;
-    if ((rc = check_pos(pos, items, n, mem)) != SPANGPU_OK)
-        return rc;
-    Staged st;
-    float *dx, *dy, *dz;
+    const float2 *cx = (const float2 *) x, *cy = (const float2 *) y;
+    float2 *dx, *dy, *dz;
     int32_t *dp;
-    bool o;
-    if ((rc = stage_in(x, 2*(size_t) (x_stride  ?  (size_t) x_stride*items  :  (size_t) n), mem, &dx, &o)) < 0) return rc;
-    st.keep(dx, o);
-    if ((rc = stage_in(y, 2*(size_t) (y_stride  ?  (size_t) y_stride*items  :  (size_t) n), mem, &dy, &o)) < 0) return rc;
-    st.keep(dy, o);
-    if ((rc = stage_in(pos, (size_t) items, mem, &dp, &o)) < 0) return rc;
-    st.keep(dp, o);
-    if ((rc = stage_in(z, 2*(size_t) items, mem, &dz, &o)) < 0) return rc;
-    st.keep(dz, o);
-    hipLaunchKernelGGL(cvec_circ_dot_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) dx, x_stride, (const float2 *) dy, y_stride, dp,
-                       (float2 *) dz, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(z, dz, 2*(size_t) items*sizeof(float), hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
+    if ((rc = call.stage(kCvecDotX, cx, ex, &dx)) < 0  ||  (rc = call.stage(kCvecDotY, cy, ey, &dy)) < 0
+        ||  (rc = call.stage(kCvecDotPos, pos, ep, &dp)) < 0  ||  (rc = call.stage(kCvecDotZ, (const float2 *) z, ez, &dz)) < 0)
+        return rc;
+    hipLaunchKernelGGL(cvec_circ_dot_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dx, x_stride, dy, y_stride, dp, dz, items, n);
+    return call.finish();
 }
 
 int spangpu_cvec_circular_lmsf_batch(int device, const float *x, long long x_stride, float *y, long long y_stride, const int32_t *pos,
                                      const float *error, int items, int n, int mem)
 {
-    int rc = check(device, items, n, x, y, pos, error);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ex, ey, ep, ee;
+    int rc;
+    if ((rc = call.args_ok(items, n, {x, y, pos, error})) < 0  ||  (rc = call.arg(kCvecLmsX, x_stride, items, n, &ex)) < 0
+        ||  (rc = call.arg(kCvecLmsY, y_stride, items, n, &ey)) < 0  ||  (rc = call.arg(kCvecLmsPos, 0, items, n, &ep)) < 0
+        ||  (rc = call.arg(kCvecLmsErr, 0, items, n, &ee)) < 0  ||  (rc = call.pos_ok(pos, items, n)) < 0  ||  (rc = call.ready(device)) < 0)
         return rc;
-    if ((rc = check_pos(pos, items, n, mem)) != SPANGPU_OK)
-        return rc;
-    if (y_stride < n)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "the rows of y are written: they cannot overlap");
-    Staged st;
-    float *dx, *dy, *de;
+    float2 *dx, *dy, *de;
     int32_t *dp;
-    bool o;
-    if ((rc = stage_in(x, 2*(size_t) (x_stride  ?  (size_t) x_stride*items  :  (size_t) n), mem, &dx, &o)) < 0) return rc;
-    st.keep(dx, o);
-    if ((rc = stage_in((const float *) y, 2*(size_t) y_stride*items, mem, &dy, &o)) < 0) return rc;
-    st.keep(dy, o);
-    if ((rc = stage_in(pos, (size_t) items, mem, &dp, &o)) < 0) return rc;
-    st.keep(dp, o);
-    if ((rc = stage_in(error, 2*(size_t) items, mem, &de, &o)) < 0) return rc;
-    st.keep(de, o);
-    hipLaunchKernelGGL(cvec_circ_lms_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const float2 *) dx, x_stride, (float2 *) dy, y_stride, dp,
-                       (const float2 *) de, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(y, dy, 2*(size_t) y_stride*items*sizeof(float), hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
+    if ((rc = call.stage(kCvecLmsX, (const float2 *) x, ex, &dx)) < 0  ||  (rc = call.stage(kCvecLmsY, (const float2 *) y, ey, &dy)) < 0
+        ||  (rc = call.stage(kCvecLmsPos, pos, ep, &dp)) < 0  ||  (rc = call.stage(kCvecLmsErr, (const float2 *) error, ee, &de)) < 0)
+        return rc;
+    hipLaunchKernelGGL(cvec_circ_lms_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dx, x_stride, dy, y_stride, dp, de, items, n);
+    return call.finish();
 }
 
 // reading[i] after power_meter_update() over amp[i*stride .. + n) with shift[i], starting from reading[i]
 int spangpu_power_meter_update_batch(int device, const int16_t *amp, long long stride, int32_t *reading, const int32_t *shift, int items, int n, int mem)
 {
-    int rc = check(device, items, n, amp, reading, shift, shift);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t ea, er, es;
+    int rc;
+    if ((rc = call.args_ok(items, n, {amp, reading, shift})) < 0  ||  (rc = call.arg(kPowerAmp, stride, items, n, &ea)) < 0
+        ||  (rc = call.arg(kPowerReading, 0, items, n, &er)) < 0  ||  (rc = call.arg(kPowerShift, 0, items, n, &es)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
-    Staged st;
     int16_t *da;
     int32_t *dr, *ds;
-    bool o;
-    if ((rc = stage_in(amp, (size_t) stride*items, mem, &da, &o)) < 0) return rc;
-    st.keep(da, o);
-    if ((rc = stage_in((const int32_t *) reading, (size_t) items, mem, &dr, &o)) < 0) return rc;
-    st.keep(dr, o);
-    if ((rc = stage_in(shift, (size_t) items, mem, &ds, &o)) < 0) return rc;
-    st.keep(ds, o);
-    hipLaunchKernelGGL(power_meter_kernel, dim3((items + 63)/64), dim3(64), 0, 0, (const int16_t *) da, stride, dr, (const int32_t *) ds, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(reading, dr, (size_t) items*sizeof(int32_t), hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
+    if ((rc = call.stage(kPowerAmp, amp, ea, &da)) < 0  ||  (rc = call.stage(kPowerReading, (const int32_t *) reading, er, &dr)) < 0
+        ||  (rc = call.stage(kPowerShift, shift, es, &ds)) < 0)
+        return rc;
+    hipLaunchKernelGGL(power_meter_kernel, dim3((items + 63)/64), dim3(64), 0, 0, da, stride, dr, ds, items, n);
+    return call.finish();
 }
 
 // items Godard timing error detectors, each over its row of n samples (godard_ted_rx() n times)
 int spangpu_godard_ted_rx_batch(int device, uint32_t *state, const uint32_t *desc, long long desc_stride, const float *samples, long long stride,
                                 int items, int n, int mem)
 {
-    int rc = check(device, items, n, state, desc, samples, samples);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t est, ed, ex;
+    int rc;
+    if ((rc = call.args_ok(items, n, {state, desc, samples})) < 0  ||  (rc = call.arg(kGodardRxState, 0, items, n, &est)) < 0
+        ||  (rc = call.arg(kGodardRxDesc, desc_stride, items, n, &ed)) < 0  ||  (rc = call.arg(kGodardRxSamples, stride, items, n, &ex)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
-    if ((desc_stride != 0  &&  desc_stride < 12)  ||  stride < 0  ||  (items > 1  &&  stride != 0  &&  stride < n))
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a descriptor stride is 0 or at least 12 words, a sample stride 0 or at least a row");
-    Staged st;
     uint32_t *dst, *dd;
     float *dx;
-    bool o;
-    if ((rc = stage_in((const uint32_t *) state, (size_t) items*8, mem, &dst, &o)) < 0) return rc;
-    st.keep(dst, o);
-    if ((rc = stage_in(desc, (desc_stride  ?  (size_t) desc_stride*items  :  (size_t) 12), mem, &dd, &o)) < 0) return rc;
-    st.keep(dd, o);
-    if ((rc = stage_in(samples, (size_t) stride*(items - 1) + n, mem, &dx, &o)) < 0) return rc;
-    st.keep(dx, o);
-    hipLaunchKernelGGL(godard_rx_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dst, (const uint32_t *) dd, desc_stride, (const float *) dx, stride, items, n);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-        SPG_TRY(hipMemcpy(state, dst, (size_t) items*8*sizeof(uint32_t), hipMemcpyDeviceToHost));
-    else
-        SPG_TRY(hipDeviceSynchronize());
-    return SPANGPU_OK;
+    if ((rc = call.stage(kGodardRxState, (const uint32_t *) state, est, &dst)) < 0  ||  (rc = call.stage(kGodardRxDesc, desc, ed, &dd)) < 0
+        ||  (rc = call.stage(kGodardRxSamples, samples, ex, &dx)) < 0)
+        return rc;
+    hipLaunchKernelGGL(godard_rx_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dst, dd, desc_stride, dx, stride, items, n);
+    return call.finish();
 }
 
 // godard_ted_per_baud() of every item: correction[i] = what the call returns (the step to add to eq_put_step)
 int spangpu_godard_ted_per_baud_batch(int device, uint32_t *state, const uint32_t *desc, long long desc_stride, int32_t *correction, int items, int mem)
 {
-    int rc = check(device, items, 1, state, desc, correction, correction);
-    if (rc != SPANGPU_OK)
+    PrimCall call(mem);
+    size_t est, ed, ec;
+    int rc;
+    if ((rc = call.args_ok(items, 1, {state, desc, correction})) < 0  ||  (rc = call.arg(kGodardBaudState, 0, items, 1, &est)) < 0
+        ||  (rc = call.arg(kGodardBaudDesc, desc_stride, items, 1, &ed)) < 0  ||  (rc = call.arg(kGodardBaudCorr, 0, items, 1, &ec)) < 0
+        ||  (rc = call.ready(device)) < 0)
         return rc;
-    if (desc_stride != 0  &&  desc_stride < 12)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a descriptor stride is 0 (one for all items) or at least 12 words");
-    Staged st;
     uint32_t *dst, *dd;
     int32_t *dc;
-    bool o;
-    if ((rc = stage_in((const uint32_t *) state, (size_t) items*8, mem, &dst, &o)) < 0) return rc;
-    st.keep(dst, o);
-    if ((rc = stage_in(desc, (desc_stride  ?  (size_t) desc_stride*items  :  (size_t) 12), mem, &dd, &o)) < 0) return rc;
-    st.keep(dd, o);
-    if ((rc = stage_in((const int32_t *) correction, (size_t) items, mem, &dc, &o)) < 0) return rc;
-    st.keep(dc, o);
-    hipLaunchKernelGGL(godard_baud_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dst, (const uint32_t *) dd, desc_stride, dc, items);
-    SPG_TRY(hipGetLastError());
-    if (mem != SPANGPU_MEM_DEVICE)
-    {
-        SPG_TRY(hipMemcpy(state, dst, (size_t) items*8*sizeof(uint32_t), hipMemcpyDeviceToHost));
-        SPG_TRY(hipMemcpy(correction, dc, (size_t) items*sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    else
-    {
-        SPG_TRY(hipDeviceSynchronize());
-    }
-    return SPANGPU_OK;
+    if ((rc = call.stage(kGodardBaudState, (const uint32_t *) state, est, &dst)) < 0  ||  (rc = call.stage(kGodardBaudDesc, desc, ed, &dd)) < 0
+        ||  (rc = call.stage(kGodardBaudCorr, (const int32_t *) correction, ec, &dc)) < 0)
+        return rc;
+    hipLaunchKernelGGL(godard_baud_kernel, dim3((items + 63)/64), dim3(64), 0, 0, dst, dd, desc_stride, dc, items);
+    return call.finish();
 }
 
 }   // extern "C"

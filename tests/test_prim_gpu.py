@@ -52,6 +52,50 @@ def ref_dot(x, y, pos):
     return f32(a + b)
 
 
+def ref_lms(x, y, pos, err):
+    """y after vec_circular_lmsf(x, y, n, pos, err)"""
+    n = len(x)
+    out = y.copy()
+    for k in range(n):
+        xv = x[pos + k] if k < n - pos else x[k - (n - pos)]
+        out[k] = f32(f32(y[k]*f32(0.9999)) + f32(xv*err))
+    return out
+
+
+def ref_cdot(x, y, pos):
+    """cvec_circular_dot_prodf() of two complex64 rows"""
+    n = len(x)
+    acc = [[f32(0), f32(0)], [f32(0), f32(0)]]
+    for part, (xo, yo, cnt) in enumerate(((pos, 0, n - pos), (0, n - pos, pos))):
+        for k in range(cnt):
+            a, b = x[xo + k], y[yo + k]
+            acc[part][0] = f32(acc[part][0] + f32(f32(a.real*b.real) - f32(a.imag*b.imag)))
+            acc[part][1] = f32(acc[part][1] + f32(f32(a.real*b.imag) + f32(a.imag*b.real)))
+    return complex(f32(acc[0][0] + acc[1][0]), f32(acc[0][1] + acc[1][1]))
+
+
+def ref_clms(x, y, pos, e):
+    """y after cvec_circular_lmsf(x, y, n, pos, &e), complex64 rows"""
+    n = len(x)
+    out = y.copy()
+    for k in range(n):
+        xv = x[pos + k] if k < n - pos else x[k - (n - pos)]
+        re = f32(f32(y[k].real*f32(0.9999)) + f32(f32(xv.imag*e.imag) + f32(xv.real*e.real)))
+        im = f32(f32(y[k].imag*f32(0.9999)) + f32(f32(xv.real*e.imag) - f32(xv.imag*e.real)))
+        out[k] = complex(re, im)
+    return out
+
+
+def ref_power(amp, reading, shift):
+    """the reading after power_meter_update() over a row of samples"""
+    r = int(reading)
+    for a in amp:
+        a = int(a)
+        r = r + ((a*a - r) >> int(shift))
+        r = (r + 2**31) % 2**32 - 2**31
+    return r
+
+
 @pytest.mark.parametrize("n", [27, 33, 8])
 def test_vec_circular_dot_prodf_and_lmsf(built, n):
     from spandsp_amd import engine
@@ -76,12 +120,7 @@ def test_vec_circular_dot_prodf_and_lmsf(built, n):
         err = nasty(rng, items)
         err[:200] = rng.normal(0, 0.01, 200).astype(np.float32)
         got2 = engine.vec_circular_lmsf(x, y, pos, err)
-        want2 = y.copy()
-        for i in range(items):
-            p = int(pos[i])
-            for k in range(n):
-                xv = x[i, p + k] if k < n - p else x[i, k - (n - p)]
-                want2[i, k] = f32(f32(y[i, k]*f32(0.9999)) + f32(xv*err[i]))
+        want2 = np.stack([ref_lms(x[i], y[i], int(pos[i]), err[i]) for i in range(items)])
         assert same(got2, want2)
     if oracle.have_ref():
         L = ref.lib()
@@ -108,29 +147,12 @@ def test_cvec_circular_dot_prodf_and_lmsf(built, n):
         pos = rng.integers(0, n, items).astype(np.int32)
         pos[:2] = [0, n - 1]
         got = engine.cvec_circular_dot_prodf(x, y, pos)
-        want = np.zeros(items, np.complex64)
-        for i in range(items):
-            p = int(pos[i])
-            acc = [[f32(0), f32(0)], [f32(0), f32(0)]]
-            for part, (xo, yo, cnt) in enumerate(((p, 0, n - p), (0, n - p, p))):
-                for k in range(cnt):
-                    a, b = x[i, xo + k], y[i, yo + k]
-                    acc[part][0] = f32(acc[part][0] + f32(f32(a.real*b.real) - f32(a.imag*b.imag)))
-                    acc[part][1] = f32(acc[part][1] + f32(f32(a.real*b.imag) + f32(a.imag*b.real)))
-            want[i] = complex(f32(acc[0][0] + acc[1][0]), f32(acc[0][1] + acc[1][1]))
+        want = np.array([ref_cdot(x[i], y[i], int(pos[i])) for i in range(items)], np.complex64)
         assert same(got.view(np.float32), want.view(np.float32))
         err = (nasty(rng, items) + 1j*nasty(rng, items)).astype(np.complex64)
         err[:150] = (rng.normal(0, 0.01, 150) + 1j*rng.normal(0, 0.01, 150)).astype(np.complex64)
         got2 = engine.cvec_circular_lmsf(x, y, pos, err)
-        want2 = y.copy()
-        for i in range(items):
-            p = int(pos[i])
-            e = err[i]
-            for k in range(n):
-                xv = x[i, p + k] if k < n - p else x[i, k - (n - p)]
-                re = f32(f32(y[i, k].real*f32(0.9999)) + f32(f32(xv.imag*e.imag) + f32(xv.real*e.real)))
-                im = f32(f32(y[i, k].imag*f32(0.9999)) + f32(f32(xv.real*e.imag) - f32(xv.imag*e.real)))
-                want2[i, k] = complex(re, im)
+        want2 = np.stack([ref_clms(x[i], y[i], int(pos[i]), err[i]) for i in range(items)])
         assert same(got2.view(np.float32), want2.view(np.float32))
     if oracle.have_ref():
         L = ref.lib()
@@ -156,14 +178,7 @@ def test_power_meter_update(built):
     reading = rng.integers(0, 1 << 30, items).astype(np.int32)
     shift = rng.integers(1, 12, items).astype(np.int32)
     got = engine.power_meter_update(amp, reading, shift)
-    want = reading.copy()
-    for i in range(items):
-        r = int(want[i])
-        for k in range(n):
-            a = int(amp[i, k])
-            r = r + ((a*a - r) >> int(shift[i]))
-            r = (r + 2**31) % 2**32 - 2**31
-        want[i] = r
+    want = np.array([ref_power(amp[i], reading[i], shift[i]) for i in range(items)], np.int32)
     assert np.array_equal(got, want)
     if oracle.have_ref():
         L = ref.lib()
