@@ -188,7 +188,8 @@ struct Bank
 #else
     // -DSPG_TONE_FMA: the experiment of round 6 (a BUILD variant, tools/build_variant.sh fma worktree
     // EXTRA=-DSPG_TONE_FMA): fac*v2 - v1 as one v_pk_fma_f32 -- one rounding where the reference has two, so the energies are
-    // no longer the reference's to the bit (decisions and digits stay: tools/fma_check.py, profiles/r6_tone_fma.log)
+    // no longer the reference's to the bit, and the build is NOT decision-exact either: block energies differ by up to 1.2e-5 of
+    // the largest and the reference's own Bell MF test program loses a run of digits (profiles/r6_tone_levers.log)
 #define SPG_C_FMA(t, f, s, a)   "v_pk_fma_f32 %" #t ", %" #f ", %" #s ", %" #a " neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"
 #define SPG_CHAIN_G1 SPG_C_FMA(2, 3, 1, 0) SPG_C_GAP SPG_C_ADDL(0, 2, 4) SPG_C_GAP SPG_C_FMA(2, 3, 0, 1) SPG_C_GAP SPG_C_ADDH(1, 2, 4)
 #define SPG_CHAIN_G2 SPG_C_FMA(4, 6, 2, 0) SPG_C_FMA(5, 7, 3, 1) SPG_C_ADDL(0, 4, 8) SPG_C_ADDL(1, 5, 8) \

@@ -119,6 +119,25 @@ __device__ __forceinline__ void seg_barrier()
 #include "tone_pairs_asm.inc"
 #endif
 
+// The operands of the asm bodies of tone_pairs_asm.inc, per number of packed bin pairs: the running state and the energy as
+// "+v", the coefficients in SGPR pairs.  SPG_PA_RUN(BODY, NPX, IN, CLOB) is one asm statement of body BODY for NPX bin pairs.
+#define SPG_PA_STATE2 [a0] "+v"(a[0]), [a1] "+v"(a[1]), [b0] "+v"(b[0]), [b1] "+v"(b[1]), [en] "+v"(energy)
+#define SPG_PA_STATE3 [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [en] "+v"(energy)
+#define SPG_PA_STATE4 [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), \
+                      [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [b3] "+v"(b[3]), [en] "+v"(energy)
+#define SPG_PA_FAC2 [f0] "s"(fac[0]), [f1] "s"(fac[1])
+#define SPG_PA_FAC3 [f0] "s"(fac[0]), [f1] "s"(fac[1]), [f2] "s"(fac[2])
+#define SPG_PA_FAC4 [f0] "s"(fac[0]), [f1] "s"(fac[1]), [f2] "s"(fac[2]), [f3] "s"(fac[3])
+#define SPG_PA_ADDR [ad0] "v"(ad), [ad1] "v"(ad1), [ad2] "v"(ad2), [ad3] "v"(ad3)
+#define SPG_PA_RUN(BODY, NPX, IN, CLOB) \
+    do \
+    { \
+        if constexpr (ENERGY) \
+            asm volatile(BODY##_NP##NPX##_E1 : SPG_PA_STATE##NPX : SPG_PA_FAC##NPX, IN : CLOB); \
+        else \
+            asm volatile(BODY##_NP##NPX##_E0 : SPG_PA_STATE##NPX : SPG_PA_FAC##NPX, IN : CLOB); \
+    } while (0)
+
 // Sample pairs [k0, k1) of the sixteen of one row piece through the recurrence, as one asm body that is entered at pair k0
 // and left after pair k1 - 1 (tone_pairs_asm.inc, written by tools/gen_pairs_asm.py): the piece that holds a block end is
 // taken as [0, p), the block end, [p, 16) -- the same straight-line pair blocks either side, two scalar instructions per pair
@@ -127,45 +146,49 @@ __device__ __forceinline__ void seg_barrier()
 template <int NP, bool ENERGY>
 __device__ __forceinline__ void pairs_asm(f32x2 (&a)[NP], f32x2 (&b)[NP], float &energy, const f32x2 (&fac)[NP], uint32_t ad, int k0, int k1)
 {
+    static_assert(NP == 2  ||  NP == 3  ||  NP == 4, "pairs_asm: banks of 4, 6 or 8 bins per lane");
     const uint32_t ad1 = ad ^ 16u;
     const uint32_t ad2 = ad ^ 32u;
     const uint32_t ad3 = ad ^ 48u;
-#define SPG_PA_ADDR [ad0] "v"(ad), [ad1] "v"(ad1), [ad2] "v"(ad2), [ad3] "v"(ad3), [k0] "s"(k0), [k1] "s"(k1)
+#define SPG_PA_IN SPG_PA_ADDR, [k0] "s"(k0), [k1] "s"(k1)
     if constexpr (NP == 2)
-    {
-        if constexpr (ENERGY)
-            asm volatile(SPG_PAIRS_ASM_NP2_E1 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [b0] "+v"(b[0]), [b1] "+v"(b[1]), [en] "+v"(energy)
-                         : [f0] "s"(fac[0]), [f1] "s"(fac[1]), SPG_PA_ADDR : SPG_PAIRS_ASM_CLOBBERS);
-        else
-            asm volatile(SPG_PAIRS_ASM_NP2_E0 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [b0] "+v"(b[0]), [b1] "+v"(b[1]), [en] "+v"(energy)
-                         : [f0] "s"(fac[0]), [f1] "s"(fac[1]), SPG_PA_ADDR : SPG_PAIRS_ASM_CLOBBERS);
-    }
+        SPG_PA_RUN(SPG_PAIRS_ASM, 2, SPG_PA_IN, SPG_PAIRS_ASM_CLOBBERS);
     else if constexpr (NP == 3)
-    {
-        if constexpr (ENERGY)
-            asm volatile(SPG_PAIRS_ASM_NP3_E1 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [en] "+v"(energy)
-                         : [f0] "s"(fac[0]), [f1] "s"(fac[1]), [f2] "s"(fac[2]), SPG_PA_ADDR : SPG_PAIRS_ASM_CLOBBERS);
-        else
-            asm volatile(SPG_PAIRS_ASM_NP3_E0 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [en] "+v"(energy)
-                         : [f0] "s"(fac[0]), [f1] "s"(fac[1]), [f2] "s"(fac[2]), SPG_PA_ADDR : SPG_PAIRS_ASM_CLOBBERS);
-    }
-    else if constexpr (NP == 4)
-    {
-        if constexpr (ENERGY)
-            asm volatile(SPG_PAIRS_ASM_NP4_E1 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]),
-                           [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [b3] "+v"(b[3]), [en] "+v"(energy)
-                         : [f0] "s"(fac[0]), [f1] "s"(fac[1]), [f2] "s"(fac[2]), [f3] "s"(fac[3]), SPG_PA_ADDR : SPG_PAIRS_ASM_CLOBBERS);
-        else
-            asm volatile(SPG_PAIRS_ASM_NP4_E0 : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]),
-                           [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [b3] "+v"(b[3]), [en] "+v"(energy)
-                         : [f0] "s"(fac[0]), [f1] "s"(fac[1]), [f2] "s"(fac[2]), [f3] "s"(fac[3]), SPG_PA_ADDR : SPG_PAIRS_ASM_CLOBBERS);
-    }
+        SPG_PA_RUN(SPG_PAIRS_ASM, 3, SPG_PA_IN, SPG_PAIRS_ASM_CLOBBERS);
     else
-    {
-        static_assert(NP == 2  ||  NP == 3  ||  NP == 4, "pairs_asm: banks of 4, 6 or 8 bins per lane");
-    }
-#undef SPG_PA_ADDR
+        SPG_PA_RUN(SPG_PAIRS_ASM, 4, SPG_PA_IN, SPG_PAIRS_ASM_CLOBBERS);
+#undef SPG_PA_IN
 }
+
+// All sixteen sample pairs of a row piece, the common segment: the same operations with no way in or out between the pairs,
+// the piece read as four whole chunks up front.  An asm body and not C++ because of the block energy: its squares and adds are
+// pure operations, which instruction selection moved behind the last (non-volatile) asm statement of the recurrence whatever
+// the source order and the sched_barriers between them said -- thirty-two dependent v_add_f32 at the end of every segment,
+// overlapping nothing (profiles/tone_energy_in_gaps.md).  Here the converts, the squares and the adds stand one at a time at
+// the joints between the recurrence's groups, converts and squares a pair ahead, the adds in sample order (gen_pairs_asm.py).
+template <int NP, bool ENERGY>
+__device__ __forceinline__ void pairs_common_asm(f32x2 (&a)[NP], f32x2 (&b)[NP], float &energy, const f32x2 (&fac)[NP], uint32_t ad)
+{
+    static_assert(NP == 2  ||  NP == 3  ||  NP == 4, "pairs_common_asm: banks of 4, 6 or 8 bins per lane");
+    const uint32_t ad1 = ad ^ 16u;
+    const uint32_t ad2 = ad ^ 32u;
+    const uint32_t ad3 = ad ^ 48u;
+    if constexpr (NP == 2)
+        SPG_PA_RUN(SPG_PAIRS_COMMON_ASM, 2, SPG_PA_ADDR, SPG_PAIRS_COMMON_ASM_CLOBBERS);
+    else if constexpr (NP == 3)
+        SPG_PA_RUN(SPG_PAIRS_COMMON_ASM, 3, SPG_PA_ADDR, SPG_PAIRS_COMMON_ASM_CLOBBERS);
+    else
+        SPG_PA_RUN(SPG_PAIRS_COMMON_ASM, 4, SPG_PA_ADDR, SPG_PAIRS_COMMON_ASM_CLOBBERS);
+}
+
+#undef SPG_PA_RUN
+#undef SPG_PA_ADDR
+#undef SPG_PA_FAC4
+#undef SPG_PA_FAC3
+#undef SPG_PA_FAC2
+#undef SPG_PA_STATE4
+#undef SPG_PA_STATE3
+#undef SPG_PA_STATE2
 
 // The loader wave of a workgroup (LDR kernels): it issues every LDS-DMA of the workgroup's WPB consumer waves and tells
 // them, one barrier per segment, that a segment has landed.  Why a wave of its own: while the chip streams a frame the
@@ -479,6 +502,7 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
             // ... and this wave's copy of the tables: lane l asks for first[l] and elements l and l + 64 (the host only builds this
             // variant into a launch when the tables fit: kCadLdsTones, kCadLdsElems)
             static_assert(kCadLdsTones + 1 <= kWave  &&  kCadLdsElems <= 2*kWave, "a wave's lanes cover the cadence tables");
+            static_assert(kCadLdsElems >= kWave, "cad_elem[lane] below is stored without a bound test");
             if ((int) lane <= L.cad.n_tones)
                 cad_tf = L.cad.first[lane];
             if ((int) lane < L.cad.n_elems)
@@ -516,6 +540,8 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
             cad_elem[lane] = cad_te0;
             if ((int) lane + kWave < kCadLdsElems)
                 cad_elem[lane + kWave] = cad_te1;
+            // (... and the look-ups of the walk read what OTHER lanes of the wave stored: the compiler is told so)
+            __builtin_amdgcn_wave_barrier();
         }
     }
     stamp(1);
@@ -536,10 +562,12 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
             energy += x;
     };
     // NPAIR consecutive sample pairs; get(k) yields pair k as floats (k is a compile-time constant after unrolling).
-    // The few instructions of a pair that are not the recurrence are dealt around the recurrence block so that no
-    // dependent two of them are neighbours: before block k the converts of pair k + 1 and the first energy add of
-    // pair k, after it the second add and the squares of pair k + 1 (energy += x*x per sample, dtmf.c:199,
-    // super_tone_rx.c:467: the adds stay in sample order).
+    // The few instructions of a pair that are not the recurrence are written around the recurrence block: before block k
+    // the converts of pair k + 1 and the first energy add of pair k, after it the second add and the squares of pair k + 1
+    // (energy += x*x per sample, dtmf.c:199, super_tone_rx.c:467: the adds stay in sample order).  For 12 and 16 bins and
+    // for G.711 input the compiled code has them there.  For a whole segment of a bank of up to 8 bins it had every square and
+    // add behind the last recurrence block, whatever the sched_barriers (profiles/tone_energy_in_gaps.md): those segments
+    // are asm bodies (kPairsAsm) and do not come here.
     auto run_pairs = [&](auto npair_tag, auto get)
     {
         constexpr int NPAIR = decltype(npair_tag)::value;
@@ -714,17 +742,27 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
                 issue_dma(seg + R - 1, (slot == 0)  ?  (R - 1)  :  (slot - 1));    // into the slot consumed last
         }
     };
-    // The common segment: whole, and no block ends inside it -- straight-line code, all four chunk reads up front
+    // The common segment: whole, and no block ends inside it -- straight-line code, all four chunk reads up front.  Where the
+    // asm bodies serve it is one of them (pairs_common_asm above: the energy in the recurrence's gaps, not behind it).
     auto common_segment = [&](uint32_t rd)
     {
-        const int4 c0 = chunk_at(rd);
-        const int4 c1 = chunk_at(rd ^ 16u);
-        const int4 c2 = chunk_at(rd ^ 32u);
-        const int4 c3 = chunk_at(rd ^ 48u);
-        run_pairs(std::integral_constant<int, 4*PPC>(), [&](int k)
+        if constexpr (kPairsAsm  &&  !(ABL & 8))        // (probe bit 3, no recurrence, is a knock-out of the C++ form)
         {
-            return pair_from((k < PPC)  ?  c0  :  (k < 2*PPC)  ?  c1  :  (k < 3*PPC)  ?  c2  :  c3, k%PPC);
-        });
+            float no_energy = 0.0f;
+            pairs_common_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac,
+                                                  (uint32_t) (uintptr_t) (__attribute__((address_space(3))) char *) lds_raw + rd);
+        }
+        else
+        {
+            const int4 c0 = chunk_at(rd);
+            const int4 c1 = chunk_at(rd ^ 16u);
+            const int4 c2 = chunk_at(rd ^ 32u);
+            const int4 c3 = chunk_at(rd ^ 48u);
+            run_pairs(std::integral_constant<int, 4*PPC>(), [&](int k)
+            {
+                return pair_from((k < PPC)  ?  c0  :  (k < 2*PPC)  ?  c1  :  (k < 3*PPC)  ?  c2  :  c3, k%PPC);
+            });
+        }
     };
     int pos = 0;                                    // samples of the frame consumed so far (wave-uniform)
     int cs_s = cs_first;
