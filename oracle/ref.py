@@ -116,6 +116,7 @@ def lib():
             "echo_can_hpf_tx": (C.c_int16, [vp, C.c_int16]),
             "v29_rx": (ci, [vp, vp, ci]), "v29_rx_free": (ci, [vp]), "v29_rx_restart": (ci, [vp, ci, ci]),
             "v29_rx_set_signal_cutoff": (None, [vp, cf]), "v27ter_rx_set_signal_cutoff": (None, [vp, cf]), "v17_rx_set_signal_cutoff": (None, [vp, cf]),
+            "v29_rx_fillin": (ci, [vp, ci]), "v27ter_rx_fillin": (ci, [vp, ci]), "v17_rx_fillin": (ci, [vp, ci]),
             "v29_rx_carrier_frequency": (cf, [vp]), "v29_rx_symbol_timing_correction": (cf, [vp]),
             "v29_tx": (ci, [vp, vp, ci]), "v29_tx_free": (ci, [vp]), "v29_tx_power": (None, [vp, cf]),
             "v27ter_rx": (ci, [vp, vp, ci]), "v27ter_rx_free": (ci, [vp]),

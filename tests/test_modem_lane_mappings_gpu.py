@@ -195,7 +195,7 @@ def test_one_lane_var_ticks_and_restarts_match_oracle(built, name, bit_rate, n_s
     of a few channels mid-stream, spangpu_modem_restart_ex() of others -- V.29 to another rate, V.27ter and V.17 with their
     train flag (V.17's short train; a V.17 or V.27ter bank runs one rate, the library refuses another).  Every channel is held
     against an oracle receiver fed its own calls only.  spangpu_modem_fillin() is not here: the oracle has no fill-in of the
-    modem receivers to follow it with."""
+    modem receivers to follow it with (tests/test_loud_modems_gpu.py holds it to the reference's recorded results)."""
     from spandsp_amd import engine
     use_v17_tx_tables(built)
     sig, lines, cutoffs = offset_lines(name, bit_rate, N_CH, n_signal, seed=bit_rate + 3*len(name) + 1)

@@ -176,6 +176,32 @@ def test_v29_old_train_restart_and_fillin(L):
     L.v29_rx_free(s)
 
 
+@pytest.mark.parametrize("pfx,name,rate", [("v27ter_rx", "v27ter", 4800), ("v17_rx", "v17", 14400)])
+def test_v27ter_and_v17_fillin_by_name(L, pfx, name, rate):
+    """v27ter_rx_fillin() / v17_rx_fillin() for a lost packet in training and in the data: the stream a caller sees is the one
+    the reference's own fill-in leaves (tests/golden/loud_modems.npz, written by tests/golden/make_golden_loud_modems.py)."""
+    import loud_lines as ll
+    import loud_modem_lines as lm
+    golden = ll.unpack(lm.load())
+    x = np.ascontiguousarray(lm.clean_input(name, rate), np.int16)
+    for point in ("training_97", "data"):
+        want = golden["fillin/%s_%d/%s" % (name, rate, point)]
+        at, lost = (int(v) for v in want["at"])
+        t = Tap()
+        s = getattr(L, pfx + "_init")(None, rate, t.put_bit, None)
+        assert s
+        for i, k in enumerate(range(0, len(x), 160)):
+            blk = x[k:k + 160]
+            if i == at:
+                assert getattr(L, pfx + "_fillin")(s, lost) == 0
+                blk = blk[lost:]
+            if len(blk):
+                blk = np.ascontiguousarray(blk)
+                assert getattr(L, pfx)(s, blk.ctypes.data, len(blk)) == 0
+        assert np.array_equal(np.array(t.ev, np.int32), want["events"].astype(np.int32)), point
+        getattr(L, pfx + "_free")(s)
+
+
 def test_logging_descriptors(L):
     for pfx, rate, proto in (("v29_rx", 9600, b"V.29 RX"), ("v27ter_rx", 4800, b"V.27ter RX"), ("v17_rx", 14400, b"V.17 RX")):
         tap = Tap()
