@@ -1666,6 +1666,60 @@ SPANGPU_API int spangpu_g726_state_words(const spangpu_g726_t *bank);
 SPANGPU_API int spangpu_g726_get_state(spangpu_g726_t *bank, int channel, int32_t *words);
 SPANGPU_API int spangpu_g726_set_state(spangpu_g726_t *bank, int channel, const int32_t *words);
 
+/* ---- G.722 codec banks (csrc/g722_api.hip, csrc/g722_dev.hpp) ---------------------------------
+ * N G.722 wideband codecs, one lane per channel, each with a bit rate (48000, 56000 or 64000) and options of its own
+ * (SPANGPU_G722_SAMPLE_RATE_8000: the low band alone, 8 kHz samples; SPANGPU_G722_PACKED: the 6- or 7-bit codes back to back,
+ * LSB first, which means nothing at 64000, as in g722_*_init()); rates[] and options[] (n entries each) are cycled over the
+ * channels.  A bank encodes or decodes, as the reference has two state types: the other direction's call is
+ * SPANGPU_ERR_BAD_ARG.  A rate outside the three or option bits outside 0x3 are SPANGPU_ERR_BAD_ARG (the reference takes
+ * every unknown rate for 64000; the by-name g722_*_init() of spangpu_spandsp.h keep that rule).
+ *
+ *   spangpu_g722_create()              g722_encode_init(NULL, rate, options) x N                 src/g722.c:621-648
+ *                                      or g722_decode_init(NULL, rate, options) x N              src/g722.c:413-441
+ *   spangpu_g722_encode()              g722_encode(s, g722_data, amp, len) x N                   src/g722.c:457-618
+ *   spangpu_g722_decode()              g722_decode(s, amp, g722_data, len) x N                   src/g722.c:261-410
+ *   spangpu_g722_restart()             g722_encode_init(s, rate, options) / g722_decode_init(s, rate, options) on one channel
+ *
+ * Rows, Alignment and Counts are those of the G.726 banks above, with these particulars.  A PCM row is int16_t samples, at
+ * 16 kHz or at 8 kHz according to the channel; a code row is one code per byte, or packed bytes.  lens[c] is the reference's
+ * len: samples of the row to encode, bytes to decode.  A 16 kHz encoder takes pairs, and the reference reads amp[len] at an
+ * odd len: a call that brings a 16 kHz encoder an odd length is SPANGPU_ERR_BAD_ARG before anything is queued.  A PCM row
+ * to encode holds 2*max_samples bytes, a code row spangpu_g722_encode_capacity(bank, max_samples) bytes; for decoding the PCM
+ * row holds spangpu_g722_decode_capacity(bank, max_bytes) samples.  A decoder's call ends when its last byte has been read: a
+ * packed one may keep a whole code for the next call, which delivers it before it reads anything, so a packed 6-bit 16 kHz
+ * decoder can deliver up to 2*((7 + 8*bytes)/6) samples of `bytes` bytes.
+ * State words, in the order of the reference's fields (src/spandsp/private/g722.h): packed, eight_k, bits_per_sample, x[12],
+ * y[12], ptr, band[0] then band[1] each as nb, det, s, sz, r, p[2], a[2], b[6], d[7], in_buffer / out_buffer, in_bits /
+ * out_bits (74; itu_test_mode, which no public call sets, is left out).  x[], y[] and ptr are where the reference's rings have
+ * them.  set_state moves a stream, its configuration, histories and waiting bits included, to another channel; words no codec
+ * could have left (a ptr outside 0..11, more than 7 waiting bits, a configuration g722_*_init() cannot make) are refused. */
+#define SPANGPU_G722_ENCODER                0
+#define SPANGPU_G722_DECODER                1
+#define SPANGPU_G722_SAMPLE_RATE_8000       1
+#define SPANGPU_G722_PACKED                 2
+
+typedef struct spangpu_g722_s spangpu_g722_t;
+
+SPANGPU_API int spangpu_g722_create(spangpu_g722_t **bank, int device, int n_channels, int direction, const int32_t *rates,
+                                    const int32_t *options, int n);
+SPANGPU_API void spangpu_g722_destroy(spangpu_g722_t *bank);
+SPANGPU_API int spangpu_g722_channels(const spangpu_g722_t *bank);
+SPANGPU_API int spangpu_g722_set_stream(spangpu_g722_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_g722_sync(spangpu_g722_t *bank);
+SPANGPU_API int spangpu_g722_encode(spangpu_g722_t *bank, const void *amp, int amp_mem_kind, long long amp_stride_bytes, const int32_t *lens,
+                                    int max_samples, uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes, int32_t *bytes_out);
+SPANGPU_API int spangpu_g722_decode(spangpu_g722_t *bank, const uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes,
+                                    const int32_t *lens, int max_bytes, void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                    int32_t *samples_out);
+/* bytes (samples) a row must hold for the worst channel of the bank, waiting bits included */
+SPANGPU_API long long spangpu_g722_encode_capacity(const spangpu_g722_t *bank, int samples);
+SPANGPU_API long long spangpu_g722_decode_capacity(const spangpu_g722_t *bank, int bytes);
+SPANGPU_API const int32_t *spangpu_g722_counts_dev(const spangpu_g722_t *bank);
+SPANGPU_API int spangpu_g722_restart(spangpu_g722_t *bank, int channel, int rate, int options);
+SPANGPU_API int spangpu_g722_state_words(const spangpu_g722_t *bank);
+SPANGPU_API int spangpu_g722_get_state(spangpu_g722_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_g722_set_state(spangpu_g722_t *bank, int channel, const int32_t *words);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -1001,6 +1001,62 @@ SPANGPU_G726_API int g726_free(g726_state_t *s);
 SPANGPU_G726_API int g726_decode(g726_state_t *s, int16_t amp[], const uint8_t g726_data[], int g726_bytes);
 SPANGPU_G726_API int g726_encode(g726_state_t *s, uint8_t g726_data[], const int16_t amp[], int len);
 
+/* ---- G.722 wideband codec (csrc/shim_g722.c) ------------------------------------------------------------------------
+ * Reference declarations being replaced:
+ *   g722_encode_init, g722_encode_release, g722_encode_free, g722_encode    src/spandsp/g722.h:71-89    src/g722.c:457-661
+ *   g722_decode_init, g722_decode_release, g722_decode_free, g722_decode    src/spandsp/g722.h:97-115   src/g722.c:261-454
+ * An object is a one-channel codec bank (spangpu.h, "G.722 codec banks"): plumbing for a caller that moves over one call at
+ * a time; the path for scale is the bank.  The init calls take every rate other than 48000 and 56000 for 64000, as the
+ * reference does, and return NULL without a GPU.  `s` may be the caller's own storage (this header has the whole structs, as
+ * the reference's private header has): the release call then gives up what the object holds on the device and the free
+ * call leaves the storage alone.  One deviation: g722_encode() with an odd len on a 16 kHz encoder encodes len - 1 samples
+ * and never reads amp[len], which the reference does.  A codec call hands its output back in the same call, so these objects
+ * are not members of channel groups.
+ * These names are declared with a macro of their own, as the G.726 ones are: tests/test_g722.py holds them against
+ * src/spandsp/g722.h.
+ */
+#define SPANGPU_G722_API SPANGPU_API
+
+enum
+{
+    G722_SAMPLE_RATE_8000 = 0x0001,
+    G722_PACKED = 0x0002
+};
+
+typedef struct g722_encode_state_s g722_encode_state_t;
+typedef struct g722_decode_state_s g722_decode_state_t;
+
+struct g722_encode_state_s
+{
+    int bits_per_sample;
+    int eight_k;
+    int packed;
+    spangpu_g722_t *bank;
+    uint8_t *row;               /* what a call's piece comes back in, before the caller's buffer gets its count of it */
+    size_t row_cap;
+    int caller_storage;
+};
+
+struct g722_decode_state_s
+{
+    int bits_per_sample;
+    int eight_k;
+    int packed;
+    spangpu_g722_t *bank;
+    uint8_t *row;
+    size_t row_cap;
+    int caller_storage;
+};
+
+SPANGPU_G722_API g722_encode_state_t *g722_encode_init(g722_encode_state_t *s, int rate, int options);
+SPANGPU_G722_API int g722_encode_release(g722_encode_state_t *s);
+SPANGPU_G722_API int g722_encode_free(g722_encode_state_t *s);
+SPANGPU_G722_API int g722_encode(g722_encode_state_t *s, uint8_t g722_data[], const int16_t amp[], int len);
+SPANGPU_G722_API g722_decode_state_t *g722_decode_init(g722_decode_state_t *s, int rate, int options);
+SPANGPU_G722_API int g722_decode_release(g722_decode_state_t *s);
+SPANGPU_G722_API int g722_decode_free(g722_decode_state_t *s);
+SPANGPU_G722_API int g722_decode(g722_decode_state_t *s, int16_t amp[], const uint8_t g722_data[], int len);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -504,6 +504,20 @@ def lib():
             "spangpu_g726_state_words": (ci, [vp]),
             "spangpu_g726_get_state": (ci, [vp, ci, vp]),
             "spangpu_g726_set_state": (ci, [vp, ci, vp]),
+            "spangpu_g722_create": (ci, [C.POINTER(vp), ci, ci, ci, vp, vp, ci]),
+            "spangpu_g722_destroy": (None, [vp]),
+            "spangpu_g722_channels": (ci, [vp]),
+            "spangpu_g722_set_stream": (ci, [vp, vp]),
+            "spangpu_g722_sync": (ci, [vp]),
+            "spangpu_g722_encode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_g722_decode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_g722_encode_capacity": (ll, [vp, ci]),
+            "spangpu_g722_decode_capacity": (ll, [vp, ci]),
+            "spangpu_g722_counts_dev": (vp, [vp]),
+            "spangpu_g722_restart": (ci, [vp, ci, ci, ci]),
+            "spangpu_g722_state_words": (ci, [vp]),
+            "spangpu_g722_get_state": (ci, [vp, ci, vp]),
+            "spangpu_g722_set_state": (ci, [vp, ci, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -2296,6 +2310,89 @@ class G726Bank(_Bank):
         assert len(w) == self.words
         _check(lib().spangpu_g726_set_state(self.h, channel, w.ctypes.data))
         self.codings[channel] = w[27]
+
+
+# ---- G.722 codec banks (include/spangpu.h "G.722 codec banks") -----------------------------
+G722_ENCODER, G722_DECODER = 0, 1
+G722_SAMPLE_RATE_8000, G722_PACKED = 1, 2
+
+
+class G722Bank(_Bank):
+    """N G.722 encoders or decoders (g722_encode / g722_decode), each channel with its own rate and options (the two lists
+    are cycled over the channels), state in HBM.  A PCM row is int16 samples, at 16 kHz or 8 kHz according to the channel."""
+    _prefix = "g722"
+
+    def __init__(self, n_channels, direction, rates=64000, options=0, device=0):
+        r, o = (np.atleast_1d(np.asarray(v, np.int32)).copy() for v in (rates, options))
+        n = max(len(r), len(o))
+        r, o = (np.resize(v, n).astype(np.int32) for v in (r, o))
+        self.n = n_channels
+        self.direction = direction
+        self.h = C.c_void_p()
+        _check(lib().spangpu_g722_create(C.byref(self.h), device, n_channels, direction, r.ctypes.data, o.ctypes.data, n))
+        self.words = lib().spangpu_g722_state_words(self.h)
+
+    def encode_capacity(self, samples):
+        return _check(lib().spangpu_g722_encode_capacity(self.h, samples))
+
+    def decode_capacity(self, nbytes):
+        return _check(lib().spangpu_g722_decode_capacity(self.h, nbytes))
+
+    _lens = staticmethod(G726Bank._lens)
+
+    def encode_host(self, pcm, samples, lens=None):
+        """pcm: [n][>= samples] int16 rows.  Returns (codes [n][encode_capacity(samples)] uint8, bytes [n])."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        assert pcm.shape[0] == self.n
+        lens, lp = self._lens(lens, self.n)
+        codes = np.zeros((self.n, max(1, self.encode_capacity(samples))), np.uint8)
+        counts = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_g722_encode(self.h, pcm.ctypes.data, MEM_HOST, 2*pcm.shape[1], lp, samples, codes.ctypes.data, MEM_HOST,
+                                         codes.shape[1], counts.ctypes.data))
+        return codes, counts
+
+    def decode_host(self, codes, nbytes, lens=None):
+        """codes: [n][>= nbytes] uint8 rows.  Returns (pcm [n][decode_capacity(nbytes)] int16, samples [n])."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        assert codes.shape[0] == self.n
+        lens, lp = self._lens(lens, self.n)
+        pcm = np.zeros((self.n, max(1, self.decode_capacity(nbytes))), np.int16)
+        counts = np.zeros(self.n, np.int32)
+        _check(lib().spangpu_g722_decode(self.h, codes.ctypes.data, MEM_HOST, codes.shape[1], lp, nbytes, pcm.ctypes.data, MEM_HOST,
+                                         2*pcm.shape[1], counts.ctypes.data))
+        return pcm, counts
+
+    def encode_device(self, pcm_ptr, pcm_stride, samples, codes_ptr, codes_stride, lens=None, counts=False):
+        """Rows in device memory (16-byte aligned, strides in bytes, multiples of 16).  counts: read the byte counts back."""
+        lens, lp = self._lens(lens, self.n)
+        out = np.zeros(self.n, np.int32) if counts else None
+        _check(lib().spangpu_g722_encode(self.h, pcm_ptr, MEM_DEVICE, pcm_stride, lp, samples, codes_ptr, MEM_DEVICE, codes_stride,
+                                         out.ctypes.data if counts else None))
+        return out
+
+    def decode_device(self, codes_ptr, codes_stride, nbytes, pcm_ptr, pcm_stride, lens=None, counts=False):
+        lens, lp = self._lens(lens, self.n)
+        out = np.zeros(self.n, np.int32) if counts else None
+        _check(lib().spangpu_g722_decode(self.h, codes_ptr, MEM_DEVICE, codes_stride, lp, nbytes, pcm_ptr, MEM_DEVICE, pcm_stride,
+                                         out.ctypes.data if counts else None))
+        return out
+
+    def counts_dev(self):
+        """device pointer to the last call's per-channel counts (int32 [n])"""
+        return lib().spangpu_g722_counts_dev(self.h)
+
+    def restart(self, channel, rate, options):
+        _check(lib().spangpu_g722_restart(self.h, channel, rate, options))
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_g722_get_state(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_g722_set_state(self.h, channel, w.ctypes.data))
 
 
 # ---- HDLC framing banks (include/spangpu.h "HDLC framing banks") ---------------------------

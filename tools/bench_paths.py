@@ -1800,7 +1800,8 @@ def bench_g726(args, dev, stream):
                 "decode": {"avg_launch_us": sum(d_ms)/len(d_ms)*1e3, "min_launch_us": min(d_ms)*1e3},
                 "code_bytes_per_tick": int(lens.sum()), "pcm_bytes_per_tick": int(n_ch*FRAME*2)}
 
-    uni = run([(args.rate, GL.LINEAR, GL.PACK_RIGHT)], "%d bit/s, linear, right-packed" % args.rate)
+    rate = args.rate if args.rate in GL.RATES else 32000
+    uni = run([(rate, GL.LINEAR, GL.PACK_RIGHT)], "%d bit/s, linear, right-packed" % rate)
     mix = run(GL.CONFIGS, "36 configurations mixed within every wave")
     h2d_ms = copy_alone_ms(n_ch*FRAME*2, "h2d", dev)
     sig = bench_sigtone(types.SimpleNamespace(channels=n_ch, warmup=2, steps=20, no_cpu_baseline=True, cpu_channels=0), dev, stream)
@@ -1822,6 +1823,162 @@ def bench_g726(args, dev, stream):
         "roofline": None,
         "cpu_baseline": None,
         "cpu_baseline_reason": "g726.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
+
+
+def bench_g722(args, dev, stream):
+    """G.722 codec banks: g722_encode() of every line into HBM and g722_decode() from there, each launch between its own pair
+    of events, 65 536 lines x one 20 ms tick (320 samples of a 16 kHz line, 160 of an 8 kHz one).  Once with every channel at
+    --rate (64000 by default), 16 kHz, unpacked, once with the 12 configurations (3 rates x 2 sample rates x 2 packings) mixed
+    within every wave; every timed window holds enough ticks to last half a second.  In the same command, alternating with
+    them, --repeats times: the host-to-device copy of the 65 536 x 320 int16 rows the codec keeps off the link, and the G.726
+    banks' launches (32 kbit/s, linear, right-packed, 160 samples) at the same line count.  A 72-channel bank pair is held
+    against the committed fixture first."""
+    import g722_lines as GL
+    import g726_lines as G6
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    rate = args.rate if args.rate in GL.RATES else 64000
+    repeats = 3
+    the_lines = GL.lines()
+    # ---- the spot check: 72 channels, the 12 configurations, five ticks of the ten-segment line ----
+    cases = {(c.kind, c.rate, c.eight_k, c.packed, c.line): c for c in GL.cases(GL.load())}
+    cfg72 = [GL.CONFIGS[c % 12] for c in range(72)]
+    r12, o12 = [r for r, _, _ in GL.CONFIGS], [GL.options_of(e, p) for _, e, p in GL.CONFIGS]
+    enc, dec = engine.G722Bank(72, engine.G722_ENCODER, r12, o12), engine.G722Bank(72, engine.G722_DECODER, r12, o12)
+    take = np.array([FRAME if e else 2*FRAME for _, e, _ in cfg72], np.int32)
+    made_b, made_s = [0]*72, [0]*72
+    checked = 0
+    for k in range(5):
+        pcm = np.zeros((72, 2*FRAME), np.int16)
+        for c in range(72):
+            pcm[c, :take[c]] = the_lines[0][k*take[c]:(k + 1)*take[c]]
+        codes, counts = enc.encode_host(pcm, 2*FRAME, take)
+        out, samples = dec.decode_host(codes, int(counts.max()), counts)
+        for c in range(72):
+            want = cases[(GL.ENCODE,) + cfg72[c] + (0,)].want[made_b[c]:made_b[c] + counts[c]]
+            assert np.array_equal(codes[c, :counts[c]], want), ("encode", c, k)
+            want = cases[(GL.DECODE,) + cfg72[c] + (0,)].want[made_s[c]:made_s[c] + samples[c]]
+            assert samples[c] >= take[c] - 2 and np.array_equal(out[c, :samples[c]], want), ("decode", c, k)
+            made_b[c] += int(counts[c])
+            made_s[c] += int(samples[c])
+            checked += 1
+    enc.close()
+    dec.close()
+
+    def launches(enc, dec, frames, in_stride, n_in, codes, cap, lens, out, out_stride):
+        """encode and decode launches of one bank pair, each between its own events: warm-up, then ticks for half a second"""
+        def tick(i, keep):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            e[0].record(stream)
+            enc.encode_device(ctypes.c_void_p(frames[i % len(frames)].data_ptr()), in_stride, n_in, ctypes.c_void_p(codes.data_ptr()), cap)
+            e[1].record(stream)
+            dec.decode_device(ctypes.c_void_p(codes.data_ptr()), cap, int(lens.max()), ctypes.c_void_p(out.data_ptr()), out_stride, lens=lens)
+            e[2].record(stream)
+            if keep is not None:
+                keep.append(e)
+        warm = max(args.warmup, 10)
+        for i in range(warm):
+            tick(i, None)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(20):
+            tick(i, None)
+        torch.cuda.synchronize()
+        ticks = max(args.steps, int(0.6*20/(time.perf_counter() - t0)) + 1)
+        kept = []
+        t0 = time.perf_counter()
+        for i in range(ticks):
+            tick(warm + i, kept)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        e_us = [a.elapsed_time(b)*1e3 for a, b, _ in kept]
+        d_us = [b.elapsed_time(c)*1e3 for _, b, c in kept]
+        return {"steps": ticks, "ms_per_step": dt*1e3/ticks, "window_s": dt,
+                "encode": {"avg_launch_us": sum(e_us)/len(e_us), "min_launch_us": min(e_us)},
+                "decode": {"avg_launch_us": sum(d_us)/len(d_us), "min_launch_us": min(d_us)}}
+
+    def run_g722(configs):
+        n_cfg = len(configs)
+        r, o = [x[0] for x in configs], [GL.options_of(x[1], x[2]) for x in configs]
+        enc, dec = engine.G722Bank(n_ch, engine.G722_ENCODER, r, o), engine.G722Bank(n_ch, engine.G722_DECODER, r, o)
+        for b in (enc, dec):
+            b.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        idx = np.arange(n_ch)
+        eight = np.array([x[1] for x in configs])[idx % n_cfg].astype(bool)
+        bps = np.array([GL.bits_of(x[0]) for x in configs])[idx % n_cfg]
+        packed = np.array([bool(x[2]) and x[0] != 64000 for x in configs])[idx % n_cfg]
+        # frames[f][c]: a row of 320 int16; an 8 kHz line brings the first 160 of it
+        nf = GL.N//(2*FRAME)
+        src = np.stack([ln[:nf*2*FRAME].reshape(nf, 2*FRAME) for ln in the_lines])         # [3][nf][320]
+        frames = torch.tensor(src[(idx//n_cfg) % 3], device=dev).permute(1, 0, 2).contiguous()      # [nf][n_ch][320]
+        take = np.where(eight, FRAME, 2*FRAME).astype(np.int32)
+        cap = (enc.encode_capacity(2*FRAME) + 15) & ~15
+        codes = torch.zeros(n_ch, cap, dtype=torch.uint8, device=dev)
+        out_stride = (2*dec.decode_capacity(FRAME) + 15) & ~15
+        out = torch.zeros(n_ch, out_stride, dtype=torch.uint8, device=dev)
+        # 160 codes a tick and line: a whole number of bytes at every rate
+        lens = np.where(packed, FRAME*bps//8, FRAME).astype(np.int32)
+        enc_lens = None if n_cfg == 1 else take
+
+        class Enc:
+            def encode_device(self, p, stride, n_in, c, cap):
+                enc.encode_device(p, stride, n_in, c, cap, lens=enc_lens)
+        res = launches(Enc(), dec, frames, 4*FRAME, 2*FRAME, codes, cap, lens, out, out_stride)
+        counts = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+        ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(dec.counts_dev()), ctypes.c_size_t(4*n_ch), 3)
+        assert (counts.cpu().numpy() == take).all(), "a decoder did not make a tick of its bytes"
+        enc.close()
+        dec.close()
+        res.update({"configurations": n_cfg, "code_bytes_per_tick": int(lens.sum()), "pcm_bytes_per_tick": int(take.sum())*2})
+        return res
+
+    def run_g726():
+        cfg = ([32000], [G6.LINEAR], [G6.PACK_RIGHT])
+        enc, dec = engine.G726Bank(n_ch, *cfg), engine.G726Bank(n_ch, *cfg)
+        for b in (enc, dec):
+            b.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        nf = GL.N//FRAME
+        src = np.stack([ln[:nf*FRAME].reshape(nf, FRAME) for ln in the_lines])
+        frames = torch.tensor(src[np.arange(n_ch) % 3], device=dev).permute(1, 0, 2).contiguous()       # [nf][n_ch][160]
+        cap = (enc.encode_capacity(FRAME) + 15) & ~15
+        codes = torch.zeros(n_ch, cap, dtype=torch.uint8, device=dev)
+        out_stride = (enc.pcm_row_bytes(dec.decode_capacity(FRAME//2)) + 15) & ~15
+        out = torch.zeros(n_ch, out_stride, dtype=torch.uint8, device=dev)
+        lens = np.full(n_ch, FRAME//2, np.int32)
+        res = launches(enc, dec, frames, 2*FRAME, FRAME, codes, cap, lens, out, out_stride)
+        enc.close()
+        dec.close()
+        return res
+
+    runs = {"uniform": [], "mixed": [], "g726": [], "h2d_ms": []}
+    for _ in range(repeats):
+        runs["uniform"].append(run_g722([(rate, 0, 0)]))
+        runs["h2d_ms"].append(copy_alone_ms(n_ch*2*FRAME*2, "h2d", dev))
+        runs["mixed"].append(run_g722(GL.CONFIGS))
+        runs["g726"].append(run_g726())
+
+    def spread(name, side):
+        v = [r[side]["avg_launch_us"] for r in runs[name]]
+        return {"avg_launch_us_per_run": v, "min": min(v), "max": max(v), "min_launch_us": min(r[side]["min_launch_us"] for r in runs[name])}
+
+    uni = runs["uniform"][0]
+    h2d_us = [x*1e3 for x in runs["h2d_ms"]]
+    worst = {"%s_%s" % (n, s): spread(n, s)["max"]/min(h2d_us) for n in ("uniform", "mixed") for s in ("encode", "decode")}
+    value = n_ch*2*FRAME*2/(uni["ms_per_step"]*1e-3)/1e6
+    return {
+        "metric": "Msamples/s of a G.722 codec bank pair (g722_encode into HBM, g722_decode from HBM; both directions counted)",
+        "value": value, "unit": "Msamples/s", "realtime_channels": value*1e6/16000.0/2, "n_gpus": 1, "steps": uni["steps"], "warmup": max(args.warmup, 10),
+        "ms_per_step": uni["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+        "config": {"workload": "G.722 codec banks, %d channels x one 20 ms tick" % n_ch, "channels_per_gpu": n_ch, "uniform_rate": rate,
+                   "repeats": repeats, "spot_checked_against_fixture": checked},
+        "kernels": {"uniform": {"encode": spread("uniform", "encode"), "decode": spread("uniform", "decode"), "runs": runs["uniform"]},
+                    "mixed": {"encode": spread("mixed", "encode"), "decode": spread("mixed", "decode"), "runs": runs["mixed"]},
+                    "g726_32000_linear_right_packed": {"encode": spread("g726", "encode"), "decode": spread("g726", "decode")}},
+        "yardsticks": {"h2d_copy_of_int16_rows_us_per_run": h2d_us,
+                       "slowest_launch_vs_fastest_copy": worst, "every_launch_below_the_copy": all(v < 1.0 for v in worst.values())},
+        "roofline": None,
+        "cpu_baseline": None,
+        "cpu_baseline_reason": "g722.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
 
 
 def bench_hdlc(args, dev, stream):
@@ -2159,9 +2316,10 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
-    ap.add_argument("--rate", type=int, choices=[16000, 24000, 32000, 40000], default=32000, help="g726: the bit rate of the uniform run")
+    ap.add_argument("--rate", type=int, choices=[16000, 24000, 32000, 40000, 48000, 56000, 64000], default=None,
+                    help="g726: the bit rate of the uniform run (32000); g722: the same (64000)")
     ap.add_argument("--bit-source", choices=["lfsr", "queue"], default="lfsr", help="v29_tx: the data bits come from the per-channel LFSR or from per-channel bit rings in HBM, refilled outside the timed region")
     ap.add_argument("--steps", type=int, default=0, help="default: 150 (190 for v27ter, whose training alone is 0.7 s)")
     ap.add_argument("--warmup", type=int, default=0)
@@ -2241,6 +2399,10 @@ def main():
     if args.workload == "g726":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         emit(bench_g726(args, dev, stream), "g726", args.channels or None)
+        return
+    if args.workload == "g722":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        emit(bench_g722(args, dev, stream), "g722", args.channels or None)
         return
     if args.workload == "fax_fe":
         emit(bench_fax_fe(args, dev, stream), "fax_fe", args.channels or None)
