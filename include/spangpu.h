@@ -229,7 +229,8 @@ SPANGPU_API int spangpu_bank_blocks(spangpu_bank_t *bank, spangpu_block_t *out, 
 SPANGPU_API int spangpu_bank_set_records_buffer(spangpu_bank_t *bank, void *device_buffer, size_t bytes);
 SPANGPU_API long long spangpu_bank_copy_records(spangpu_bank_t *bank, void *dst_device, size_t dst_bytes);
 /* The digits of the last spangpu_bank_rx() as a compact device-resident list, written on the bank's stream: dst[0] = how
-   many blocks accepted a digit (SPANGPU_BLK_CHANGE with a non-zero code), dst[1 + i] = channel | code << 20 | block << 28
+   many blocks accepted a digit (a non-zero code with SPANGPU_BLK_CHANGE in a DTMF bank, with SPANGPU_BLK_REPORT in a Bell MF
+   or R2 MF bank, whose detectors never set SPANGPU_BLK_CHANGE), dst[1 + i] = channel | code << 20 | block << 28
    for the first cap_entries of them, in no particular order (dst holds 1 + cap_entries words; a count above cap_entries
    says the list was cut).  A separate small kernel over the records of the last launch (two stream operations). */
 SPANGPU_API int spangpu_bank_digit_events(spangpu_bank_t *bank, uint32_t *dst_device, int cap_entries);

@@ -295,10 +295,13 @@ static void dtmf_levels(const spangpu_tone_params_t &tp, float &threshold, float
 }
 
 // The digits of the last launch as a compact list, for reports that leave the GPU (an RCCL gather to another rank, a
-// small D2H copy): out[0] = number of blocks in which the debouncer accepted a digit (SPANGPU_BLK_CHANGE with a non-zero
-// code: dtmf.c:318-340, Bell MF :629-655), out[1 + i] = channel | code << 20 | block << 28, in no particular order.
+// small D2H copy): out[0] = number of blocks in which the detector accepted a digit, out[1 + i] = channel | code << 20 |
+// block << 28, in no particular order.  `accept` = the flag that marks such a block when its code is not zero:
+// SPANGPU_BLK_CHANGE for DTMF (dtmf.c:318-340), SPANGPU_BLK_REPORT for Bell MF (bell_r2_mf.c:629-655) and R2 MF (:869-875;
+// the end of a tone is reported with code 0 and is no digit) -- those two never set SPANGPU_BLK_CHANGE, and their lists were
+// empty while this kernel asked for it.
 // A 65536-channel DTMF tick has 131072 record words and, on live lines, a few thousand such blocks.
-__global__ __launch_bounds__(256) void digit_events_kernel(const uint32_t *rec, int n_ch, int maxb, uint32_t *out, int cap)
+__global__ __launch_bounds__(256) void digit_events_kernel(const uint32_t *rec, int n_ch, int maxb, uint32_t *out, int cap, uint32_t accept)
 {
     const int ch = (int) (blockIdx.x*256 + threadIdx.x);
     if (ch >= n_ch)
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(256) void digit_events_kernel(const uint32_t *rec, 
         const uint32_t w = rec[(size_t) b*n_ch + ch];
         const uint32_t flags = (w >> 16) & 0xFF;
         const uint32_t code = (w >> 8) & 0xFF;
-        if ((flags & kBlkValid)  &&  (flags & kBlkChange)  &&  code)
+        if ((flags & kBlkValid)  &&  (flags & accept)  &&  code)
         {
             const uint32_t at = atomicAdd(out, 1u);
             if (at < (uint32_t) cap)
@@ -1607,7 +1610,8 @@ int spangpu_bank_digit_events(spangpu_bank_t *b, uint32_t *dst_device, int cap_e
     if (b->last_maxb > 0)
     {
         hipLaunchKernelGGL(digit_events_kernel, dim3((b->n_ch + 255)/256), dim3(256), 0, joined(b),
-                           (const uint32_t *) (b->cur_rec  ?  b->cur_rec  :  b->rec), b->n_ch, b->last_maxb, dst_device, cap_entries);
+                           (const uint32_t *) (b->cur_rec  ?  b->cur_rec  :  b->rec), b->n_ch, b->last_maxb, dst_device, cap_entries,
+                           (uint32_t) ((b->kind == SPANGPU_BELL_MF  ||  b->kind == SPANGPU_R2_MF)  ?  kBlkReport  :  kBlkChange));
         SPG_TRY(hipGetLastError());
     }
     return SPANGPU_OK;
