@@ -11,6 +11,8 @@
 // The six banks with an _rx_var entry point (fsk, mct, sigtone, modem, v18, adsi _api.hip) keep that call's per-channel lengths
 // in a VarLens; those six and the HDLC receiver and FAX front-end banks (hdlc_api.hip, faxfe_api.hip) hand a call's result
 // rows to the host through CountRows, count_row_scan() and rows_fetch().
+// The codec banks (g726_api.hip, g722_api.hip) embed codec_host.hpp's CodecBank, and through it BankCore, a VarLens and a
+// CountRows; its one encode / decode call uses grow(), lens_check(), lens_upload() and counts_fetch().
 //
 // The behaviours this sharing makes uniform:
 //  - every sender's tx refuses more than kMaxSamples samples a call (tx_args_ok); before, the tone and modem senders did not;

@@ -4,41 +4,27 @@
 // the host, as the reference's own g722_*_init() edits one object.
 
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "../../include/spangpu.h"
 #include "g722_dev.hpp"
-#include "bank_host.hpp"
+#include "codec_host.hpp"
 
 using namespace spg;
 
 struct spangpu_g722_s
 {
-    BankCore c;
+    CodecBank k;                // cfg: bits per sample, eight_k, packed
     int direction;              // SPANGPU_G722_ENCODER or SPANGPU_G722_DECODER
-    uint8_t *d_in;              // a host caller's rows: [n_ch][in_cap] bytes
-    size_t in_cap;
-    uint8_t *d_out;
-    size_t out_cap;
-    VarLens lens;               // per-channel lengths of a call
-    bool lens_kept;             // lens.dev holds what lens.pinned holds: a caller that brings the same lengths tick after tick
-    CountRows count;            // counts of the last call: bytes (encode) or samples (decode)
-    uint8_t *cfg;               // [n_ch][3]: bits per sample, eight_k, packed, as the state words have them
     int present[3][2][2];       // channels per configuration: what the capacity functions and the row checks need of cfg
 };
-
-static size_t round16(size_t v)
-{
-    return (v + 15) & ~(size_t) 15;
-}
 
 static void summarise(spangpu_g722_s *b)
 {
     memset(b->present, 0, sizeof(b->present));
-    for (int c = 0;  c < b->c.n_ch;  c++)
-        b->present[b->cfg[3*c] - 6][b->cfg[3*c + 1]][b->cfg[3*c + 2]]++;
+    for (int c = 0;  c < b->k.c.n_ch;  c++)
+        b->present[b->k.cfg[3*c] - 6][b->k.cfg[3*c + 1]][b->k.cfg[3*c + 2]]++;
 }
 
 // the worst channel's output for `items` samples (encode: bytes) or bytes (decode: samples)
@@ -61,113 +47,49 @@ static long long capacity(const spangpu_g722_s *b, bool encode, long long items)
     return worst;
 }
 
-// A row in device memory is read and written in aligned 16-byte chunks, its last one whole: the base and the stride are
-// multiples of 16 and the stride holds the row rounded up to 16.  A host caller's rows are copied, so any stride that
-// holds the row will do.
-static int row_ok(const void *p, int mem_kind, long long stride, long long need)
+template <bool ENCODE>
+static void launch(const CodecLaunch &L, dim3 grid, hipStream_t stream)
 {
-    if (p == NULL)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null rows");
-    if (mem_kind_ok(mem_kind) != SPANGPU_OK)
-        return SPANGPU_ERR_BAD_ARG;
-    if (mem_kind == SPANGPU_MEM_HOST)
-        return (stride >= need)  ?  SPANGPU_OK  :  spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a row stride is shorter than the row");
-    if ((stride & 15) != 0  ||  (reinterpret_cast<uintptr_t>(p) & 15) != 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "rows in device memory: base and stride are multiples of 16 bytes");
-    if (stride < (long long) round16((size_t) need))
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "a row stride is shorter than the row rounded up to 16 bytes");
-    return SPANGPU_OK;
+    hipLaunchKernelGGL((codec_kernel<G722Codec, ENCODE>), grid, dim3(64), 0, stream, L);
 }
 
 static int run(spangpu_g722_s *b, bool encode, const void *in, int in_kind, long long in_stride, const int32_t *lens, int max_len,
                void *out, int out_kind, long long out_stride, int32_t *counts_out)
 {
-    if (b == NULL  ||  max_len < 0  ||  max_len > kMaxSamples)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
+    int rc;
+    if ((rc = codec_args_ok(b, max_len)) != SPANGPU_OK)
+        return rc;
     if (b->direction != (encode  ?  SPANGPU_G722_ENCODER  :  SPANGPU_G722_DECODER))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "an encoder bank does not decode, and a decoder bank does not encode");
     const long long in_need = encode  ?  2*(long long) max_len  :  (long long) max_len;
     const long long out_need = encode  ?  capacity(b, true, max_len)  :  2*capacity(b, false, max_len);
-    int rc;
-    if ((rc = row_ok(in, in_kind, in_stride, in_need)) != SPANGPU_OK  ||  (rc = row_ok(out, out_kind, out_stride, out_need)) != SPANGPU_OK)
-        return rc;
-    bool all = true;
-    int longest = max_len;
-    if (lens  &&  (rc = lens_check(lens, b->c.n_ch, max_len, &longest, &all)) != SPANGPU_OK)
+    CodecCall call = {in, in_kind, in_stride, in_need, out, out_kind, out_stride, out_need, lens, max_len, counts_out, 0, false};
+    if ((rc = codec_check(&b->k, &call)) != SPANGPU_OK)
         return rc;
     // a 16 kHz encoder takes pairs: the reference reads amp[len] at an odd len
     if (encode)
     {
-        for (int c = 0;  c < b->c.n_ch;  c++)
+        for (int c = 0;  c < b->k.c.n_ch;  c++)
         {
-            if (!b->cfg[3*c + 1]  &&  ((lens  ?  lens[c]  :  max_len) & 1))
+            if (!b->k.cfg[3*c + 1]  &&  ((lens  ?  lens[c]  :  max_len) & 1))
                 return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "an odd number of samples for a 16 kHz encoder");
         }
     }
-    SPG_TRY(hipSetDevice(b->c.device));
-    if (longest == 0)
-    {
-        // nobody brings anything: no launch, and the counts of this call are zeros
-        SPG_TRY(hipMemsetAsync(b->count.dev, 0, (size_t) b->c.n_ch*sizeof(int32_t), b->c.stream));
-    }
-    else
-    {
-        // (the same lengths as the last upload, the steady state of a gateway's ticks: no copy and no wait)
-        if (!all  &&  !(b->lens_kept  &&  memcmp(b->lens.pinned, lens, (size_t) b->c.n_ch*sizeof(int32_t)) == 0))
-        {
-            b->lens_kept = false;
-            if ((rc = lens_upload(&b->c, &b->lens, lens)) != SPANGPU_OK)
-                return rc;
-            b->lens_kept = true;
-        }
-        G722Launch L;
-        memset(&L, 0, sizeof(L));
-        L.st = b->c.st;
-        L.lens = all  ?  NULL  :  b->lens.dev;
-        L.counts = b->count.dev;
-        L.n_ch = b->c.n_ch;
-        L.len = longest;
-        L.in = (const uint8_t *) in;
-        L.in_stride = in_stride;
-        if (in_kind == SPANGPU_MEM_HOST)
-        {
-            const size_t pitch = round16((size_t) in_need);
-            if ((rc = grow(&b->d_in, &b->in_cap, pitch, (size_t) b->c.n_ch, b->c.stream)) != SPANGPU_OK)
-                return rc;
-            SPG_TRY(hipMemcpy2DAsync(b->d_in, b->in_cap, in, (size_t) in_stride, (size_t) in_need, (size_t) b->c.n_ch, hipMemcpyHostToDevice, b->c.stream));
-            L.in = b->d_in;
-            L.in_stride = (long long) b->in_cap;
-        }
-        L.out = (uint8_t *) out;
-        L.out_stride = out_stride;
-        if (out_kind == SPANGPU_MEM_HOST)
-        {
-            const size_t pitch = round16((size_t) out_need);
-            if ((rc = grow(&b->d_out, &b->out_cap, pitch, (size_t) b->c.n_ch, b->c.stream)) != SPANGPU_OK)
-                return rc;
-            L.out = b->d_out;
-            L.out_stride = (long long) b->out_cap;
-        }
-        const dim3 grid((b->c.n_ch + 63)/64);
-        if (encode)
-            hipLaunchKernelGGL(g722_kernel<true>, grid, dim3(64), 0, b->c.stream, L);
-        else
-            hipLaunchKernelGGL(g722_kernel<false>, grid, dim3(64), 0, b->c.stream, L);
-        SPG_TRY(hipGetLastError());
-        if (out_kind == SPANGPU_MEM_HOST  &&  out_need > 0)
-            SPG_TRY(hipMemcpy2DAsync(out, (size_t) out_stride, b->d_out, b->out_cap, (size_t) out_need, (size_t) b->c.n_ch, hipMemcpyDeviceToHost, b->c.stream));
-    }
-    b->lens.next = NULL;
-    if (counts_out)
-    {
-        // the one wait of the call, behind the rows
-        if ((rc = counts_fetch(&b->c, &b->count, 1)) != SPANGPU_OK)
-            return rc;
-        memcpy(counts_out, b->count.pinned, (size_t) b->c.n_ch*sizeof(int32_t));
-    }
-    else if (in_kind == SPANGPU_MEM_HOST  ||  out_kind == SPANGPU_MEM_HOST)
-        SPG_TRY(hipStreamSynchronize(b->c.stream));         // a host buffer is only borrowed for the call
-    return SPANGPU_OK;
+    return codec_run(&b->k, &call, encode  ?  launch<true>  :  launch<false>);
+}
+
+// create's arguments, for init_channel()
+struct InitArgs
+{
+    const int32_t *rates;
+    const int32_t *options;
+    int n;
+};
+
+static void init_channel(const void *arg, int channel, int32_t *words)
+{
+    const InitArgs *a = (const InitArgs *) arg;
+    (void) g722_init_words(words, a->rates[channel % a->n], a->options[channel % a->n]);
 }
 
 // words g722_*_init() and a codec's calls could have left: the configuration, a ring position inside the histories (a lane
@@ -195,12 +117,7 @@ void spangpu_g722_destroy(spangpu_g722_t *b)
 {
     if (b == NULL)
         return;
-    core_destroy(&b->c);
-    (void) hipFree(b->d_in);
-    (void) hipFree(b->d_out);
-    lens_free(&b->lens);
-    counts_free(&b->count);
-    free(b->cfg);
+    codec_destroy(&b->k);
     free(b);
 }
 
@@ -222,60 +139,22 @@ int spangpu_g722_create(spangpu_g722_t **out, int device, int n_channels, int di
     spangpu_g722_s *b = (spangpu_g722_s *) calloc(1, sizeof(*b));
     if (b == NULL)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "calloc");
-    if ((rc = core_create(&b->c, device, n_channels, kG722Words)) != SPANGPU_OK  ||  (rc = counts_create(&b->c, &b->count, 1, 1)) != SPANGPU_OK)
+    const InitArgs args = {rates, options, n};
+    if ((rc = codec_create(&b->k, device, n_channels, kG722Words, G2_BPS, G2_EIGHT_K, G2_PACKED, init_channel, &args)) != SPANGPU_OK)
     {
         spangpu_g722_destroy(b);
         return rc;
     }
     b->direction = direction;
-    const size_t nn = (size_t) n_channels;
-    int32_t *host = (int32_t *) calloc((size_t) kG722Words*nn, sizeof(int32_t));
-    b->cfg = (uint8_t *) malloc(3*nn);
-    if (host == NULL  ||  b->cfg == NULL)
-    {
-        free(host);
-        spangpu_g722_destroy(b);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "allocation of the codec bank failed");
-    }
-    for (int c = 0;  c < n_channels;  c++)
-    {
-        (void) g722_init_words(one, rates[c % n], options[c % n]);
-        for (int w = 0;  w < kG722Words;  w++)
-            host[(size_t) w*nn + c] = one[w];
-        b->cfg[3*c] = (uint8_t) one[G2_BPS];
-        b->cfg[3*c + 1] = (uint8_t) one[G2_EIGHT_K];
-        b->cfg[3*c + 2] = (uint8_t) one[G2_PACKED];
-    }
     summarise(b);
-    rc = core_upload(&b->c, host);
-    free(host);
-    if (rc == SPANGPU_OK  &&  hipMemset(b->count.dev, 0, nn*sizeof(int32_t)) != hipSuccess)
-        rc = spangpu_set_error(SPANGPU_ERR_HIP, "state upload failed");
-    if (rc != SPANGPU_OK)
-    {
-        spangpu_g722_destroy(b);
-        return rc;
-    }
     *out = b;
     return SPANGPU_OK;
 }
 
-int spangpu_g722_channels(const spangpu_g722_t *b) { return b  ?  b->c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
+int spangpu_g722_channels(const spangpu_g722_t *b) { return b  ?  b->k.c.n_ch  :  SPANGPU_ERR_BAD_ARG; }
 int spangpu_g722_state_words(const spangpu_g722_t *b) { return b  ?  kG722Words  :  SPANGPU_ERR_BAD_ARG; }
-
-int spangpu_g722_set_stream(spangpu_g722_t *b, void *stream)
-{
-    if (b == NULL)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    return core_set_stream(&b->c, stream);
-}
-
-int spangpu_g722_sync(spangpu_g722_t *b)
-{
-    if (b == NULL)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "null bank");
-    return core_sync(&b->c);
-}
+int spangpu_g722_set_stream(spangpu_g722_t *b, void *stream) { return codec_set_stream(b  ?  &b->k  :  NULL, stream); }
+int spangpu_g722_sync(spangpu_g722_t *b) { return codec_sync(b  ?  &b->k  :  NULL); }
 
 int spangpu_g722_encode(spangpu_g722_t *b, const void *amp, int amp_mem_kind, long long amp_stride_bytes, const int32_t *lens, int max_samples,
                         uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes, int32_t *bytes_out)
@@ -305,41 +184,35 @@ long long spangpu_g722_decode_capacity(const spangpu_g722_t *b, int bytes)
 
 const int32_t *spangpu_g722_counts_dev(const spangpu_g722_t *b)
 {
-    return b  ?  b->count.dev  :  NULL;
+    return b  ?  b->k.count.dev  :  NULL;
 }
 
 static int put_words(spangpu_g722_s *b, int channel, int32_t *w)
 {
-    const int rc = core_rw_words(&b->c, channel, 0, kG722Words, w, true);
-    if (rc != SPANGPU_OK)
-        return rc;
-    b->cfg[3*channel] = (uint8_t) w[G2_BPS];
-    b->cfg[3*channel + 1] = (uint8_t) w[G2_EIGHT_K];
-    b->cfg[3*channel + 2] = (uint8_t) w[G2_PACKED];
-    summarise(b);
-    return SPANGPU_OK;
+    const int rc = codec_put_words(&b->k, channel, w);
+    if (rc == SPANGPU_OK)
+        summarise(b);
+    return rc;
 }
 
 int spangpu_g722_restart(spangpu_g722_t *b, int channel, int rate, int options)
 {
     int32_t w[kG722Words];
-    if (b == NULL  ||  !channel_ok(&b->c, channel)  ||  !g722_init_words(w, rate, options))
+    if (b == NULL  ||  !channel_ok(&b->k.c, channel)  ||  !g722_init_words(w, rate, options))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     return put_words(b, channel, w);
 }
 
 int spangpu_g722_get_state(spangpu_g722_t *b, int channel, int32_t *words)
 {
-    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->c, channel))
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    return core_rw_words(&b->c, channel, 0, kG722Words, words, false);
+    return codec_get_state(b  ?  &b->k  :  NULL, channel, words);
 }
 
 // The channel takes the configuration words too (a stream moves with its rate, sample rate and packing, its histories and
 // the bits that wait); words no codec could have left are refused.
 int spangpu_g722_set_state(spangpu_g722_t *b, int channel, const int32_t *words)
 {
-    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->c, channel)  ||  !words_ok(words))
+    if (b == NULL  ||  words == NULL  ||  !channel_ok(&b->k.c, channel)  ||  !words_ok(words))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     return put_words(b, channel, const_cast<int32_t *>(words));
 }

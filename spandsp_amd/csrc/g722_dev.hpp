@@ -3,7 +3,8 @@
 // (one code per byte, or the codes back to back, LSB first) of its own.
 //
 // The per-code functions are __host__ __device__ and the file compiles for the host (tests/c_callers/g722_host.cpp runs
-// them one lane at a time under ASan and UBSan); the two kernels at the end are HIP only.
+// them one lane at a time under ASan and UBSan); G722Codec at the end, what codec_kernel<> (codec_rows.hpp) runs
+// these functions through, is HIP only.
 //
 // int16_t arithmetic.  The reference leans on the truncation of its int16_t locals; here every value is an int32_t and each
 // truncation is an explicit g722_s16().  A right shift of a negative value is arithmetic, as everywhere the reference is
@@ -29,6 +30,8 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "codec_rows.hpp"
 
 #ifdef __HIPCC__
 #define G722_HD __host__ __device__ __forceinline__
@@ -501,182 +504,63 @@ G722_UNROLL
     st[G2_BITS*n] = s.bits;
 }
 
-// ---- a lane's row in 16-byte chunks -----------------------------------------------------------------------------------
-// In: a window of two chunks; an element is picked out of it by selects (the position differs from lane to lane), and once
-// four codes are through (16 bytes at the most: a 16 kHz encoder's four pairs), a lane whose position has left the first
-// chunk moves on to the chunk requested before those four.  Out: bytes gather in three 8-byte words; sixteen of them leave
-// as one chunk (a 16 kHz decoder makes 16 bytes of four codes).
-
-struct G722In
-{
-    uint32_t w[8];
-    int32_t pos;            // the next byte, 0 .. 31
-    int32_t chunk;          // the row's chunk in w[0 .. 3]
-};
-
-// (the eight words by value: picked through a reference to the struct, the compiler keeps the window in LDS)
-G722_HD uint32_t g722_pick(int i, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6, uint32_t w7)
-{
-    const uint32_t a = (i & 1)  ?  w1  :  w0;
-    const uint32_t b = (i & 1)  ?  w3  :  w2;
-    const uint32_t c = (i & 1)  ?  w5  :  w4;
-    const uint32_t d = (i & 1)  ?  w7  :  w6;
-    const uint32_t e = (i & 2)  ?  b  :  a;
-    const uint32_t f = (i & 2)  ?  d  :  c;
-    return (i & 4)  ?  f  :  e;
-}
-
-// the word that holds the next byte, shifted down to it: a 16 kHz encoder's position is a multiple of 4 (the whole word, both
-// samples), an 8 kHz one's a multiple of 2
-G722_HD uint32_t g722_in_peek(const G722In &in)
-{
-    return g722_pick(in.pos >> 2, in.w[0], in.w[1], in.w[2], in.w[3], in.w[4], in.w[5], in.w[6], in.w[7]) >> (8*(in.pos & 3));
-}
-
-struct G722Out
-{
-    uint64_t w[3];
-    int32_t fill;           // bytes held, 0 .. 23
-    int32_t chunk;          // the next chunk of the row to write
-};
-
-// `bytes` (0, 1, 2 or 4; at a fill that is a multiple of it) of v
-G722_HD void g722_out_push(G722Out &o, uint32_t v, int32_t bytes)
-{
-    const uint32_t mask = (bytes == 4)  ?  0xFFFFFFFFu  :  ((bytes == 2)  ?  0xFFFFu  :  ((bytes == 1)  ?  0xFFu  :  0u));
-    const uint64_t x = (uint64_t) (v & mask) << (8*(o.fill & 7));
-    const int k = o.fill >> 3;
-    o.w[0] |= (k == 0)  ?  x  :  0;
-    o.w[1] |= (k == 1)  ?  x  :  0;
-    o.w[2] |= (k == 2)  ?  x  :  0;
-    o.fill += bytes;
-}
+// ---- the kernels: codec_kernel<G722Codec, ENCODE> (codec_rows.hpp) ------------------------------------------------------
 
 #if defined(__HIPCC__)  &&  !defined(SPG_G722_STEP_FUNCTIONS_ONLY)
 
-struct G722Launch
+// Four codes between two advances of the window: a 16 kHz encoder's four pairs are 16 bytes in, and a 16 kHz decoder makes
+// 16 bytes of four codes.  A 16 kHz encoder's position in its row is a multiple of 4 (the whole word, both samples), an
+// 8 kHz one's a multiple of 2.
+struct G722Codec
 {
-    int32_t *st;                // [kG722Words][n_ch]
-    const uint8_t *in;          // rows of in_stride bytes, 16-byte aligned
-    uint8_t *out;               // rows of out_stride bytes, 16-byte aligned
-    const int32_t *lens;        // [n_ch] samples (encode) or bytes (decode), or NULL: `len` for all
-    int32_t *counts;            // [n_ch] bytes written (encode) or samples (decode)
-    long long in_stride;
-    long long out_stride;
-    int n_ch;
-    int len;
-};
+    typedef G722 State;
+    static constexpr int kTabWords = kG722TabWords;
+    static constexpr int kGroup = 4;
+    static constexpr int kWidest = 4;
 
-__device__ __forceinline__ uint4 g722_chunk(const uint8_t *row, int chunk, int last)
-{
-    return *(const uint4 *) (row + 16*(size_t) ((chunk <= last)  ?  chunk  :  0));
-}
+    static __device__ __forceinline__ const int32_t *table() { return kG722TabDev; }
+    static __device__ __forceinline__ void load(G722 &s, const int32_t *st, size_t n) { g722_load(s, st, n); }
+    static __device__ __forceinline__ void store(const G722 &s, int32_t *st, size_t n) { g722_store(s, st, n); }
+    static __device__ __forceinline__ int pcm_bytes(int) { return 2; }
 
-__device__ __forceinline__ void g722_flush(uint8_t *dst, const G722Out &o)
-{
-    *(uint4 *) (dst + 16*(size_t) o.chunk) = make_uint4((uint32_t) o.w[0], (uint32_t) (o.w[0] >> 32), (uint32_t) o.w[1], (uint32_t) (o.w[1] >> 32));
-}
-
-// ENCODE: lens are samples and counts bytes; else lens are bytes and counts samples
-template <bool ENCODE>
-__global__ __launch_bounds__(64) void g722_kernel(const G722Launch L)
-{
-    __shared__ __attribute__((aligned(16))) int32_t table[kG722TabWords];
-    const int lane = threadIdx.x;
-G722_UNROLL
-    for (int i = 0;  i < kG722TabWords/64;  i++)
-        table[i*64 + lane] = kG722TabDev[i*64 + lane];
-    __syncthreads();
-    const int ch = blockIdx.x*64 + lane;
-    if (ch >= L.n_ch)
-        return;
-    const size_t n = (size_t) L.n_ch;
-    int32_t *st = L.st + ch;
-    const int mylen = L.lens  ?  min(max(L.lens[ch], 0), L.len)  :  L.len;
-    if (mylen == 0)
+    // samples of a code
+    static __device__ __forceinline__ int unit(const G722 &s)
     {
-        L.counts[ch] = 0;
-        return;
+        return s.eight_k  ?  1  :  2;
     }
-    G722 s;
-    g722_load(s, st, n);
-    const int per = s.eight_k  ?  1  :  2;          // samples of a code
+
     // (a decoder's count follows from the bits waiting in its state: never past the row, whatever a caller has set there)
-    const int todo = ENCODE  ?  (mylen/per)  :  (int) min((long long) g722_decode_codes(s, mylen), L.out_stride/(2*per));
-    const int in_bytes = ENCODE  ?  2*mylen  :  mylen;
-    const int last = (in_bytes - 1) >> 4;
-    const uint8_t *src = L.in + (size_t) ch*L.in_stride;
-    uint8_t *dst = L.out + (size_t) ch*L.out_stride;
-
-    G722In in;
-    G722Out out;
+    template <bool ENCODE>
+    static __device__ __forceinline__ int todo(const G722 &s, int per, int mylen, long long out_stride)
     {
-        const uint4 q0 = g722_chunk(src, 0, last);
-        const uint4 q1 = g722_chunk(src, 1, last);
-        in.w[0] = q0.x;  in.w[1] = q0.y;  in.w[2] = q0.z;  in.w[3] = q0.w;
-        in.w[4] = q1.x;  in.w[5] = q1.y;  in.w[6] = q1.z;  in.w[7] = q1.w;
+        return ENCODE  ?  (mylen/per)  :  (int) min((long long) g722_decode_codes(s, mylen), out_stride/(2*per));
     }
-    in.pos = 0;
-    in.chunk = 0;
-    out.w[0] = out.w[1] = out.w[2] = 0;
-    out.fill = 0;
-    out.chunk = 0;
-    uint4 ahead = {0, 0, 0, 0};
-    for (int i = 0;  i < todo;  i++)
+
+    template <bool ENCODE>
+    static __device__ __forceinline__ int32_t take(const G722 &s, int per)
     {
-        // (i is the same in every lane still in the loop, so the two branches on it are the wave's)
-        if ((i & 3) == 0)
-            ahead = g722_chunk(src, in.chunk + 2, last);
-        const uint32_t raw = g722_in_peek(in);
+        return ENCODE  ?  (2*per)  :  (g722_unpack_needs(s)  ?  1  :  0);
+    }
+
+    template <bool ENCODE>
+    static __device__ __forceinline__ RowPush step(G722 &s, const int32_t *table, int per, uint32_t raw)
+    {
         if (ENCODE)
         {
-            in.pos += 2*per;
             const int32_t code = g722_encode_code(s, table, (int32_t) (raw & 0xFFFF), (int32_t) (raw >> 16));
             int32_t byte;
             const bool full = g722_pack(s, code, &byte);
-            g722_out_push(out, (uint32_t) byte, full  ?  1  :  0);
+            return {(uint32_t) byte, full  ?  1  :  0};
         }
         else
         {
-            in.pos += g722_unpack_needs(s)  ?  1  :  0;
             const int32_t code = g722_unpack(s, (int32_t) raw);
             int32_t amp[2];
             g722_decode_code(s, table, code, amp);
-            g722_out_push(out, ((uint32_t) amp[0] & 0xFFFF) | ((uint32_t) amp[1] << 16), 2*per);
-        }
-        if ((i & 3) == 3)
-        {
-            const bool on = (in.pos >= 16);
-            in.w[0] = on  ?  in.w[4]  :  in.w[0];
-            in.w[1] = on  ?  in.w[5]  :  in.w[1];
-            in.w[2] = on  ?  in.w[6]  :  in.w[2];
-            in.w[3] = on  ?  in.w[7]  :  in.w[3];
-            in.w[4] = on  ?  ahead.x  :  in.w[4];
-            in.w[5] = on  ?  ahead.y  :  in.w[5];
-            in.w[6] = on  ?  ahead.z  :  in.w[6];
-            in.w[7] = on  ?  ahead.w  :  in.w[7];
-            in.pos -= on  ?  16  :  0;
-            in.chunk += on  ?  1  :  0;
-            if (out.fill >= 16)
-            {
-                g722_flush(dst, out);
-                out.w[0] = out.w[2];
-                out.w[1] = 0;
-                out.w[2] = 0;
-                out.fill -= 16;
-                out.chunk++;
-            }
+            return {((uint32_t) amp[0] & 0xFFFF) | ((uint32_t) amp[1] << 16), 2*per};
         }
     }
-    // what is left leaves as chunks too: the row is written up to the next 16-byte boundary past its count
-    const int32_t total = 16*out.chunk + out.fill;
-    if (out.fill > 0)
-        g722_flush(dst, out);
-    if (out.fill > 16)
-        *(uint4 *) (dst + 16*(size_t) (out.chunk + 1)) = make_uint4((uint32_t) out.w[2], (uint32_t) (out.w[2] >> 32), 0u, 0u);
-    L.counts[ch] = ENCODE  ?  total  :  (total/2);
-    g722_store(s, st, n);
-}
+};
 
 #endif  // __HIPCC__
 

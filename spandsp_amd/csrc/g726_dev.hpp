@@ -2,7 +2,8 @@
 // with a rate (16 / 24 / 32 / 40 kbit/s), an external coding (linear, u-law, A-law) and a packing (none, left, right) of its own.
 //
 // The per-sample functions are __host__ __device__ and the file compiles for the host (tests/c_callers/g726_host.cpp runs
-// them one lane at a time under ASan and UBSan); the two kernels at the end are HIP only.
+// them one lane at a time under ASan and UBSan); G726Codec at the end, what codec_kernel<> (codec_rows.hpp) runs
+// these functions through, is HIP only.
 //
 // How the reference's four encoders and four decoders become one body.  They differ in the tables, in the mask applied
 // to dq when sr is rebuilt (0x7FFF at 40 kbit/s, 0x3FFF otherwise), in the leak of the zero predictor (>> 9 at 40 kbit/s) and in
@@ -20,6 +21,8 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "codec_rows.hpp"
 
 #ifdef __HIPCC__
 #define G726_HD __host__ __device__ __forceinline__
@@ -552,171 +555,59 @@ G726_UNROLL
     st[G7_RESIDUE*n] = s.residue;
 }
 
-// ---- a lane's row in 16-byte chunks -----------------------------------------------------------------------------------
-// In: a window of two chunks; an element is picked out of it by selects (the position differs from lane to lane), and once
-// eight samples are through, a lane whose position has left the first chunk moves on to the chunk requested before those
-// eight.  Out: bytes gather in three 8-byte words; sixteen of them leave as one chunk.
-
-struct G726In
-{
-    uint32_t w[8];
-    int32_t pos;            // the next byte, 0 .. 31
-    int32_t chunk;          // the row's chunk in w[0 .. 3]
-};
-
-G726_HD uint32_t g726_pick(int i, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint32_t w5, uint32_t w6, uint32_t w7)
-{
-    const uint32_t a = (i & 1)  ?  w1  :  w0;
-    const uint32_t b = (i & 1)  ?  w3  :  w2;
-    const uint32_t c = (i & 1)  ?  w5  :  w4;
-    const uint32_t d = (i & 1)  ?  w7  :  w6;
-    const uint32_t e = (i & 2)  ?  b  :  a;
-    const uint32_t f = (i & 2)  ?  d  :  c;
-    return (i & 4)  ?  f  :  e;
-}
-
-G726_HD uint32_t g726_in_peek(const G726In &in)
-{
-    return g726_pick(in.pos >> 2, in.w[0], in.w[1], in.w[2], in.w[3], in.w[4], in.w[5], in.w[6], in.w[7]) >> (8*(in.pos & 3));
-}
-
-struct G726Out
-{
-    uint64_t w[3];
-    int32_t fill;           // bytes held, 0 .. 23
-    int32_t chunk;          // the next chunk of the row to write
-};
-
-// `bytes` (0, 1 or 2; two only at an even fill) of v
-G726_HD void g726_out_push(G726Out &o, uint32_t v, int32_t bytes)
-{
-    const uint64_t x = (uint64_t) (bytes  ?  (v & ((bytes == 2)  ?  0xFFFFu  :  0xFFu))  :  0) << (8*(o.fill & 7));
-    const int k = o.fill >> 3;
-    o.w[0] |= (k == 0)  ?  x  :  0;
-    o.w[1] |= (k == 1)  ?  x  :  0;
-    o.w[2] |= (k == 2)  ?  x  :  0;
-    o.fill += bytes;
-}
+// ---- the kernels: codec_kernel<G726Codec, ENCODE> (codec_rows.hpp) ------------------------------------------------------
 
 #if defined(__HIPCC__)  &&  !defined(SPG_G726_STEP_FUNCTIONS_ONLY)
 
-struct G726Launch
+// Eight samples between two advances of the window: 16 bytes of linear PCM in, or 16 out.
+struct G726Codec
 {
-    int32_t *st;                // [kG726Words][n_ch]
-    const uint8_t *in;          // rows of in_stride bytes, 16-byte aligned
-    uint8_t *out;               // rows of out_stride bytes, 16-byte aligned
-    const int32_t *lens;        // [n_ch] samples (encode) or bytes (decode), or NULL: `len` for all
-    int32_t *counts;            // [n_ch] bytes written (encode) or samples (decode)
-    long long in_stride;
-    long long out_stride;
-    int n_ch;
-    int len;
-};
+    typedef G726 State;
+    static constexpr int kTabWords = kG726TabWords;
+    static constexpr int kGroup = 8;
+    static constexpr int kWidest = 2;
 
-__device__ __forceinline__ uint4 g726_chunk(const uint8_t *row, int chunk, int last)
-{
-    return *(const uint4 *) (row + 16*(size_t) ((chunk <= last)  ?  chunk  :  0));
-}
+    static __device__ __forceinline__ const int32_t *table() { return kG726TabDev; }
+    static __device__ __forceinline__ void load(G726 &s, const int32_t *st, size_t n) { g726_load(s, st, n); }
+    static __device__ __forceinline__ void store(const G726 &s, int32_t *st, size_t n) { g726_store(s, st, n); }
+    static __device__ __forceinline__ int pcm_bytes(int el) { return el; }
 
-// ENCODE: lens are samples and counts bytes; else lens are bytes and counts samples
-template <bool ENCODE>
-__global__ __launch_bounds__(64) void g726_kernel(const G726Launch L)
-{
-    __shared__ __attribute__((aligned(16))) int32_t table[kG726TabWords];
-    const int lane = threadIdx.x;
-G726_UNROLL
-    for (int i = 0;  i < kG726TabWords/64;  i++)
-        table[i*64 + lane] = kG726TabDev[i*64 + lane];
-    __syncthreads();
-    const int ch = blockIdx.x*64 + lane;
-    if (ch >= L.n_ch)
-        return;
-    const size_t n = (size_t) L.n_ch;
-    int32_t *st = L.st + ch;
-    const int mylen = L.lens  ?  min(max(L.lens[ch], 0), L.len)  :  L.len;
-    if (mylen == 0)
+    // bytes of an element of the PCM row
+    static __device__ __forceinline__ int unit(const G726 &s)
     {
-        L.counts[ch] = 0;
-        return;
+        return (s.coding == kG726Linear)  ?  2  :  1;
     }
-    G726 s;
-    g726_load(s, st, n);
-    const bool linear = (s.coding == kG726Linear);
-    const int el = linear  ?  2  :  1;              // bytes of an element of the PCM row
+
     // (a decoder's count follows from the residue in its state: never past the row, whatever a caller has set there)
-    const int todo = ENCODE  ?  mylen  :  (int) min((long long) g726_decode_count(s, mylen), L.out_stride/el);
-    const int in_bytes = ENCODE  ?  mylen*el  :  mylen;
-    const int last = (in_bytes - 1) >> 4;
-    const uint8_t *src = L.in + (size_t) ch*L.in_stride;
-    uint8_t *dst = L.out + (size_t) ch*L.out_stride;
-
-    G726In in;
-    G726Out out;
+    template <bool ENCODE>
+    static __device__ __forceinline__ int todo(const G726 &s, int el, int mylen, long long out_stride)
     {
-        const uint4 q0 = g726_chunk(src, 0, last);
-        const uint4 q1 = g726_chunk(src, 1, last);
-        in.w[0] = q0.x;  in.w[1] = q0.y;  in.w[2] = q0.z;  in.w[3] = q0.w;
-        in.w[4] = q1.x;  in.w[5] = q1.y;  in.w[6] = q1.z;  in.w[7] = q1.w;
+        return ENCODE  ?  mylen  :  (int) min((long long) g726_decode_count(s, mylen), out_stride/el);
     }
-    in.pos = 0;
-    in.chunk = 0;
-    out.w[0] = out.w[1] = out.w[2] = 0;
-    out.fill = 0;
-    out.chunk = 0;
-    uint4 ahead = {0, 0, 0, 0};
-    for (int i = 0;  i < todo;  i++)
+
+    template <bool ENCODE>
+    static __device__ __forceinline__ int32_t take(const G726 &s, int el)
     {
-        // (i is the same in every lane still in the loop, so the two branches on it are the wave's)
-        if ((i & 7) == 0)
-            ahead = g726_chunk(src, in.chunk + 2, last);
-        const uint32_t raw = g726_in_peek(in);
+        return ENCODE  ?  el  :  (g726_unpack_needs(s)  ?  1  :  0);
+    }
+
+    template <bool ENCODE>
+    static __device__ __forceinline__ RowPush step(G726 &s, const int32_t *table, int el, uint32_t raw)
+    {
         if (ENCODE)
         {
-            in.pos += el;
             const int32_t code = g726_encode_sample(s, table, g726_linearize(s.coding, (int32_t) raw));
             int32_t byte;
             const bool full = g726_pack(s, code, &byte);
-            g726_out_push(out, (uint32_t) byte, full  ?  1  :  0);
+            return {(uint32_t) byte, full  ?  1  :  0};
         }
         else
         {
-            in.pos += g726_unpack_needs(s)  ?  1  :  0;
             const int32_t code = g726_unpack(s, (int32_t) raw);
-            g726_out_push(out, (uint32_t) g726_decode_code(s, table, code), el);
-        }
-        if ((i & 7) == 7)
-        {
-            const bool on = (in.pos >= 16);
-            in.w[0] = on  ?  in.w[4]  :  in.w[0];
-            in.w[1] = on  ?  in.w[5]  :  in.w[1];
-            in.w[2] = on  ?  in.w[6]  :  in.w[2];
-            in.w[3] = on  ?  in.w[7]  :  in.w[3];
-            in.w[4] = on  ?  ahead.x  :  in.w[4];
-            in.w[5] = on  ?  ahead.y  :  in.w[5];
-            in.w[6] = on  ?  ahead.z  :  in.w[6];
-            in.w[7] = on  ?  ahead.w  :  in.w[7];
-            in.pos -= on  ?  16  :  0;
-            in.chunk += on  ?  1  :  0;
-            if (out.fill >= 16)
-            {
-                *(uint4 *) (dst + 16*(size_t) out.chunk) = make_uint4((uint32_t) out.w[0], (uint32_t) (out.w[0] >> 32), (uint32_t) out.w[1], (uint32_t) (out.w[1] >> 32));
-                out.w[0] = out.w[2];
-                out.w[1] = 0;
-                out.w[2] = 0;
-                out.fill -= 16;
-                out.chunk++;
-            }
+            return {(uint32_t) g726_decode_code(s, table, code), el};
         }
     }
-    // what is left leaves as chunks too: the row is written up to the next 16-byte boundary past its count
-    const int32_t total = 16*out.chunk + out.fill;
-    if (out.fill > 0)
-        *(uint4 *) (dst + 16*(size_t) out.chunk) = make_uint4((uint32_t) out.w[0], (uint32_t) (out.w[0] >> 32), (uint32_t) out.w[1], (uint32_t) (out.w[1] >> 32));
-    if (out.fill > 16)
-        *(uint4 *) (dst + 16*(size_t) (out.chunk + 1)) = make_uint4((uint32_t) out.w[2], (uint32_t) (out.w[2] >> 32), 0u, 0u);
-    L.counts[ch] = ENCODE  ?  total  :  (total/el);
-    g726_store(s, st, n);
-}
+};
 
 #endif  // __HIPCC__
 

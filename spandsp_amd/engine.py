@@ -2221,7 +2221,63 @@ G726_LINEAR, G726_ULAW, G726_ALAW = 0, 1, 2
 G726_PACKING_NONE, G726_PACKING_LEFT, G726_PACKING_RIGHT = 0, 1, 2
 
 
-class G726Bank(_Bank):
+class _CodecBank(_Bank):
+    """What the codec banks share: capacities, one encode or decode call of every channel over host or device rows, whole or
+    with per-channel lengths, the counts and the state words."""
+
+    def encode_capacity(self, samples):
+        return _check(self._f("encode_capacity")(self.h, samples))
+
+    def decode_capacity(self, nbytes):
+        return _check(self._f("decode_capacity")(self.h, nbytes))
+
+    @staticmethod
+    def _lens(lens, n):
+        if lens is None:
+            return None, None
+        lens = np.ascontiguousarray(lens, np.int32)
+        assert lens.shape == (n,)
+        return lens, lens.ctypes.data
+
+    def _host(self, call, rows, length, lens, out_shape, out_dtype):
+        """rows (their own dtype) through `call` into zeroed rows of out_shape; returns (those, counts [n])"""
+        assert rows.shape[0] == self.n
+        lens, lp = self._lens(lens, self.n)
+        out = np.zeros(out_shape, out_dtype)
+        counts = np.zeros(self.n, np.int32)
+        _check(self._f(call)(self.h, rows.ctypes.data, MEM_HOST, rows.strides[0], lp, length, out.ctypes.data, MEM_HOST, out.strides[0],
+                             counts.ctypes.data))
+        return out, counts
+
+    def _device(self, call, in_ptr, in_stride, length, out_ptr, out_stride, lens, counts):
+        lens, lp = self._lens(lens, self.n)
+        out = np.zeros(self.n, np.int32) if counts else None
+        _check(self._f(call)(self.h, in_ptr, MEM_DEVICE, in_stride, lp, length, out_ptr, MEM_DEVICE, out_stride, out.ctypes.data if counts else None))
+        return out
+
+    def encode_device(self, pcm_ptr, pcm_stride, samples, codes_ptr, codes_stride, lens=None, counts=False):
+        """Rows in device memory (16-byte aligned, strides in bytes, multiples of 16).  counts: read the byte counts back."""
+        return self._device("encode", pcm_ptr, pcm_stride, samples, codes_ptr, codes_stride, lens, counts)
+
+    def decode_device(self, codes_ptr, codes_stride, nbytes, pcm_ptr, pcm_stride, lens=None, counts=False):
+        return self._device("decode", codes_ptr, codes_stride, nbytes, pcm_ptr, pcm_stride, lens, counts)
+
+    def counts_dev(self):
+        """device pointer to the last call's per-channel counts (int32 [n])"""
+        return self._f("counts_dev")(self.h)
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(self._f("get_state")(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(self._f("set_state")(self.h, channel, w.ctypes.data))
+
+
+class G726Bank(_CodecBank):
     """N G.726 codecs (g726_encode / g726_decode), each channel with its own rate, external coding and packing (the three
     lists are cycled over the channels), state in HBM.  A PCM row is bytes: int16 samples where the channel's coding is
     linear, G.711 bytes where it is not."""
@@ -2237,78 +2293,26 @@ class G726Bank(_Bank):
         self.words = lib().spangpu_g726_state_words(self.h)
         self.codings = c[np.arange(n_channels) % n].copy()      # per channel: what a PCM row holds
 
-    def encode_capacity(self, samples):
-        return _check(lib().spangpu_g726_encode_capacity(self.h, samples))
-
-    def decode_capacity(self, nbytes):
-        return _check(lib().spangpu_g726_decode_capacity(self.h, nbytes))
-
     def pcm_row_bytes(self, samples):
         """bytes a PCM row of `samples` elements takes in this bank's widest coding"""
         return 2*samples if (self.codings == G726_LINEAR).any() else samples
 
-    @staticmethod
-    def _lens(lens, n):
-        if lens is None:
-            return None, None
-        lens = np.ascontiguousarray(lens, np.int32)
-        assert lens.shape == (n,)
-        return lens, lens.ctypes.data
-
     def encode_host(self, pcm, samples, lens=None):
         """pcm: [n][>= pcm_row_bytes(samples)] uint8 rows.  Returns (codes [n][encode_capacity(samples)] uint8, bytes [n])."""
         pcm = np.ascontiguousarray(pcm).view(np.uint8)
-        assert pcm.shape[0] == self.n
-        lens, lp = self._lens(lens, self.n)
-        codes = np.zeros((self.n, max(1, self.encode_capacity(samples))), np.uint8)
-        counts = np.zeros(self.n, np.int32)
-        _check(lib().spangpu_g726_encode(self.h, pcm.ctypes.data, MEM_HOST, pcm.shape[1], lp, samples, codes.ctypes.data, MEM_HOST,
-                                         codes.shape[1], counts.ctypes.data))
-        return codes, counts
+        return self._host("encode", pcm, samples, lens, (self.n, max(1, self.encode_capacity(samples))), np.uint8)
 
     def decode_host(self, codes, nbytes, lens=None):
         """codes: [n][>= nbytes] uint8 rows.  Returns (pcm [n][pcm_row_bytes(decode_capacity(nbytes))] uint8, samples [n])."""
         codes = np.ascontiguousarray(codes, np.uint8)
-        assert codes.shape[0] == self.n
-        lens, lp = self._lens(lens, self.n)
-        pcm = np.zeros((self.n, max(1, self.pcm_row_bytes(self.decode_capacity(nbytes)))), np.uint8)
-        counts = np.zeros(self.n, np.int32)
-        _check(lib().spangpu_g726_decode(self.h, codes.ctypes.data, MEM_HOST, codes.shape[1], lp, nbytes, pcm.ctypes.data, MEM_HOST,
-                                         pcm.shape[1], counts.ctypes.data))
-        return pcm, counts
-
-    def encode_device(self, pcm_ptr, pcm_stride, samples, codes_ptr, codes_stride, lens=None, counts=False):
-        """Rows in device memory (16-byte aligned, strides in bytes, multiples of 16).  counts: read the byte counts back."""
-        lens, lp = self._lens(lens, self.n)
-        out = np.zeros(self.n, np.int32) if counts else None
-        _check(lib().spangpu_g726_encode(self.h, pcm_ptr, MEM_DEVICE, pcm_stride, lp, samples, codes_ptr, MEM_DEVICE, codes_stride,
-                                         out.ctypes.data if counts else None))
-        return out
-
-    def decode_device(self, codes_ptr, codes_stride, nbytes, pcm_ptr, pcm_stride, lens=None, counts=False):
-        lens, lp = self._lens(lens, self.n)
-        out = np.zeros(self.n, np.int32) if counts else None
-        _check(lib().spangpu_g726_decode(self.h, codes_ptr, MEM_DEVICE, codes_stride, lp, nbytes, pcm_ptr, MEM_DEVICE, pcm_stride,
-                                         out.ctypes.data if counts else None))
-        return out
-
-    def counts_dev(self):
-        """device pointer to the last call's per-channel counts (int32 [n])"""
-        return lib().spangpu_g726_counts_dev(self.h)
+        return self._host("decode", codes, nbytes, lens, (self.n, max(1, self.pcm_row_bytes(self.decode_capacity(nbytes)))), np.uint8)
 
     def restart(self, channel, rate, coding, packing):
         _check(lib().spangpu_g726_restart(self.h, channel, rate, coding, packing))
         self.codings[channel] = coding
 
-    def get_state(self, channel):
-        w = np.zeros(self.words, np.int32)
-        _check(lib().spangpu_g726_get_state(self.h, channel, w.ctypes.data))
-        return w
-
     def set_state(self, channel, w):
-        w = np.ascontiguousarray(w, np.int32)
-        assert len(w) == self.words
-        _check(lib().spangpu_g726_set_state(self.h, channel, w.ctypes.data))
+        super().set_state(channel, w)
         self.codings[channel] = w[27]
 
 
@@ -2317,7 +2321,7 @@ G722_ENCODER, G722_DECODER = 0, 1
 G722_SAMPLE_RATE_8000, G722_PACKED = 1, 2
 
 
-class G722Bank(_Bank):
+class G722Bank(_CodecBank):
     """N G.722 encoders or decoders (g722_encode / g722_decode), each channel with its own rate and options (the two lists
     are cycled over the channels), state in HBM.  A PCM row is int16 samples, at 16 kHz or 8 kHz according to the channel."""
     _prefix = "g722"
@@ -2332,67 +2336,18 @@ class G722Bank(_Bank):
         _check(lib().spangpu_g722_create(C.byref(self.h), device, n_channels, direction, r.ctypes.data, o.ctypes.data, n))
         self.words = lib().spangpu_g722_state_words(self.h)
 
-    def encode_capacity(self, samples):
-        return _check(lib().spangpu_g722_encode_capacity(self.h, samples))
-
-    def decode_capacity(self, nbytes):
-        return _check(lib().spangpu_g722_decode_capacity(self.h, nbytes))
-
-    _lens = staticmethod(G726Bank._lens)
-
     def encode_host(self, pcm, samples, lens=None):
         """pcm: [n][>= samples] int16 rows.  Returns (codes [n][encode_capacity(samples)] uint8, bytes [n])."""
         pcm = np.ascontiguousarray(pcm, np.int16)
-        assert pcm.shape[0] == self.n
-        lens, lp = self._lens(lens, self.n)
-        codes = np.zeros((self.n, max(1, self.encode_capacity(samples))), np.uint8)
-        counts = np.zeros(self.n, np.int32)
-        _check(lib().spangpu_g722_encode(self.h, pcm.ctypes.data, MEM_HOST, 2*pcm.shape[1], lp, samples, codes.ctypes.data, MEM_HOST,
-                                         codes.shape[1], counts.ctypes.data))
-        return codes, counts
+        return self._host("encode", pcm, samples, lens, (self.n, max(1, self.encode_capacity(samples))), np.uint8)
 
     def decode_host(self, codes, nbytes, lens=None):
         """codes: [n][>= nbytes] uint8 rows.  Returns (pcm [n][decode_capacity(nbytes)] int16, samples [n])."""
         codes = np.ascontiguousarray(codes, np.uint8)
-        assert codes.shape[0] == self.n
-        lens, lp = self._lens(lens, self.n)
-        pcm = np.zeros((self.n, max(1, self.decode_capacity(nbytes))), np.int16)
-        counts = np.zeros(self.n, np.int32)
-        _check(lib().spangpu_g722_decode(self.h, codes.ctypes.data, MEM_HOST, codes.shape[1], lp, nbytes, pcm.ctypes.data, MEM_HOST,
-                                         2*pcm.shape[1], counts.ctypes.data))
-        return pcm, counts
-
-    def encode_device(self, pcm_ptr, pcm_stride, samples, codes_ptr, codes_stride, lens=None, counts=False):
-        """Rows in device memory (16-byte aligned, strides in bytes, multiples of 16).  counts: read the byte counts back."""
-        lens, lp = self._lens(lens, self.n)
-        out = np.zeros(self.n, np.int32) if counts else None
-        _check(lib().spangpu_g722_encode(self.h, pcm_ptr, MEM_DEVICE, pcm_stride, lp, samples, codes_ptr, MEM_DEVICE, codes_stride,
-                                         out.ctypes.data if counts else None))
-        return out
-
-    def decode_device(self, codes_ptr, codes_stride, nbytes, pcm_ptr, pcm_stride, lens=None, counts=False):
-        lens, lp = self._lens(lens, self.n)
-        out = np.zeros(self.n, np.int32) if counts else None
-        _check(lib().spangpu_g722_decode(self.h, codes_ptr, MEM_DEVICE, codes_stride, lp, nbytes, pcm_ptr, MEM_DEVICE, pcm_stride,
-                                         out.ctypes.data if counts else None))
-        return out
-
-    def counts_dev(self):
-        """device pointer to the last call's per-channel counts (int32 [n])"""
-        return lib().spangpu_g722_counts_dev(self.h)
+        return self._host("decode", codes, nbytes, lens, (self.n, max(1, self.decode_capacity(nbytes))), np.int16)
 
     def restart(self, channel, rate, options):
         _check(lib().spangpu_g722_restart(self.h, channel, rate, options))
-
-    def get_state(self, channel):
-        w = np.zeros(self.words, np.int32)
-        _check(lib().spangpu_g722_get_state(self.h, channel, w.ctypes.data))
-        return w
-
-    def set_state(self, channel, w):
-        w = np.ascontiguousarray(w, np.int32)
-        assert len(w) == self.words
-        _check(lib().spangpu_g722_set_state(self.h, channel, w.ctypes.data))
 
 
 # ---- HDLC framing banks (include/spangpu.h "HDLC framing banks") ---------------------------
