@@ -1721,6 +1721,61 @@ SPANGPU_API int spangpu_g722_state_words(const spangpu_g722_t *bank);
 SPANGPU_API int spangpu_g722_get_state(spangpu_g722_t *bank, int channel, int32_t *words);
 SPANGPU_API int spangpu_g722_set_state(spangpu_g722_t *bank, int channel, const int32_t *words);
 
+/* ---- GSM 06.10 codec banks (csrc/gsm0610_api.hip, csrc/gsm0610_dev.hpp) ------------------------
+ * N GSM 06.10 full-rate codecs, one lane per channel, each with a packing of its own (SPANGPU_GSM0610_PACKING_NONE: 76 bytes
+ * a frame, a byte a parameter; _VOIP: 33 bytes a frame behind the nibble 0xD; _WAV49: two frames in 65 bytes); packings[]
+ * (n entries) is cycled over the channels.  A bank encodes or decodes: the other direction's call is SPANGPU_ERR_BAD_ARG.  A
+ * packing outside the three is SPANGPU_ERR_BAD_ARG at create, restart and set_packing (the reference stores any value and
+ * treats an unknown one as NONE).
+ *
+ *   spangpu_gsm0610_create()           gsm0610_init(NULL, packing) x N                           src/gsm0610_encode.c:313-326
+ *   spangpu_gsm0610_encode()           gsm0610_encode(s, code, amp, len) x N                     src/gsm0610_encode.c:282-310
+ *   spangpu_gsm0610_decode()           gsm0610_decode(s, amp, code, len) x N                     src/gsm0610_decode.c:312-353
+ *   spangpu_gsm0610_set_packing()      gsm0610_set_packing(s, packing) on one channel            src/gsm0610_encode.c:108-112
+ *   spangpu_gsm0610_restart()          gsm0610_init(s, packing) on one channel
+ *
+ * Rows, Alignment and Counts are those of the G.726 banks above, with these particulars.  A PCM row is int16_t samples at
+ * 8 kHz.  lens[c] is the reference's len: samples of the row to encode, bytes to decode.  The codec works in frames of 160
+ * samples and the reference reads past the end of a partial one, so a length that is not a whole number of the channel's
+ * units is SPANGPU_ERR_BAD_ARG before anything is queued: the units are 160 samples (320 under WAV49) to encode and 76, 33 or
+ * 65 bytes to decode.  A length of 0 sits the call out.  A PCM row to encode holds 2*max_samples bytes, a code row
+ * spangpu_gsm0610_encode_capacity(bank, max_samples) bytes; for decoding the PCM row holds
+ * spangpu_gsm0610_decode_capacity(bank, max_bytes) samples.
+ * Code bytes.  A decoder masks every parameter to its width (LARc 6,6,5,5,4,4,3,3; per subframe Nc 7, bc 2, Mc 2, xmaxc 6,
+ * xMc 13 x 3).  Only unpacked bytes can be wider, and those are undefined in the reference: bc, Mc and xMc index 4- and 8-entry
+ * tables there and trip its asserts.  The nibble in front of a VoIP frame is not looked at, as in the reference.
+ * State words, in the order of the reference's fields (src/spandsp/private/gsm0610.h): packing, dp0[0..119] (the history;
+ * dp0[120..279] and e[] are workspace and are left out), z1, L_z2, mp, u[8], LARpp[2][8], j, nrp, v[9], msr (160).  set_state
+ * moves a stream to another channel, its packing included; words no codec could have left (a packing outside the three, a j
+ * outside 0..1, an nrp outside 40..120) are refused. */
+#define SPANGPU_GSM0610_ENCODER             0
+#define SPANGPU_GSM0610_DECODER             1
+#define SPANGPU_GSM0610_PACKING_NONE        0
+#define SPANGPU_GSM0610_PACKING_WAV49       1
+#define SPANGPU_GSM0610_PACKING_VOIP        2
+
+typedef struct spangpu_gsm0610_s spangpu_gsm0610_t;
+
+SPANGPU_API int spangpu_gsm0610_create(spangpu_gsm0610_t **bank, int device, int n_channels, int direction, const int32_t *packings, int n);
+SPANGPU_API void spangpu_gsm0610_destroy(spangpu_gsm0610_t *bank);
+SPANGPU_API int spangpu_gsm0610_channels(const spangpu_gsm0610_t *bank);
+SPANGPU_API int spangpu_gsm0610_set_stream(spangpu_gsm0610_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_gsm0610_sync(spangpu_gsm0610_t *bank);
+SPANGPU_API int spangpu_gsm0610_encode(spangpu_gsm0610_t *bank, const void *amp, int amp_mem_kind, long long amp_stride_bytes, const int32_t *lens,
+                                       int max_samples, uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes, int32_t *bytes_out);
+SPANGPU_API int spangpu_gsm0610_decode(spangpu_gsm0610_t *bank, const uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes,
+                                       const int32_t *lens, int max_bytes, void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                       int32_t *samples_out);
+/* bytes (samples) a row must hold for the worst channel of the bank */
+SPANGPU_API long long spangpu_gsm0610_encode_capacity(const spangpu_gsm0610_t *bank, int samples);
+SPANGPU_API long long spangpu_gsm0610_decode_capacity(const spangpu_gsm0610_t *bank, int bytes);
+SPANGPU_API const int32_t *spangpu_gsm0610_counts_dev(const spangpu_gsm0610_t *bank);
+SPANGPU_API int spangpu_gsm0610_set_packing(spangpu_gsm0610_t *bank, int channel, int packing);
+SPANGPU_API int spangpu_gsm0610_restart(spangpu_gsm0610_t *bank, int channel, int packing);
+SPANGPU_API int spangpu_gsm0610_state_words(const spangpu_gsm0610_t *bank);
+SPANGPU_API int spangpu_gsm0610_get_state(spangpu_gsm0610_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_gsm0610_set_state(spangpu_gsm0610_t *bank, int channel, const int32_t *words);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -1057,6 +1057,67 @@ SPANGPU_G722_API int g722_decode_release(g722_decode_state_t *s);
 SPANGPU_G722_API int g722_decode_free(g722_decode_state_t *s);
 SPANGPU_G722_API int g722_decode(g722_decode_state_t *s, int16_t amp[], const uint8_t g722_data[], int len);
 
+/* ---- GSM 06.10 full-rate codec (csrc/shim_gsm0610.c, csrc/gsm0610_host.c) -------------------------------------------
+ * Reference declarations being replaced:
+ *   gsm0610_init, gsm0610_release, gsm0610_free, gsm0610_set_packing        src/spandsp/gsm0610.h:84-100  src/gsm0610_encode.c:108-341
+ *   gsm0610_encode, gsm0610_decode                                          src/spandsp/gsm0610.h:108-116
+ *   gsm0610_pack_none, _wav49, _voip, gsm0610_unpack_none, _wav49, _voip    src/spandsp/gsm0610.h:118-144
+ * The reference has one state type for both directions; an object here is a pair of one-channel codec banks (spangpu.h,
+ * "GSM 06.10 codec banks"), an encoder and a decoder with a history each: plumbing for a caller that
+ * moves over one call at a time; the path for scale is the bank.  gsm0610_init() returns NULL without a GPU, and takes a
+ * packing outside the three for GSM0610_PACKING_NONE, as the reference's switch statements do.  `s` may be the caller's own
+ * storage (this header has the whole struct): the release call then gives up what the object holds on the device and the free
+ * call leaves the storage alone.  One deviation: gsm0610_encode() and gsm0610_decode() work on the whole frames of `len`
+ * (160 samples, 320 under WAV49; 76, 33 or 65 bytes) and never read past it, which the reference does at a partial frame.
+ * The six pack and unpack calls are host code and need no GPU.  gsm0610_unpack_none() hands the bytes over as they are, as the
+ * reference does; the decoders mask them.  These objects are not members of channel groups.
+ * These names are declared with a macro of their own, as the G.722 ones are: tests/test_gsm0610.py holds them against
+ * src/spandsp/gsm0610.h.
+ */
+#define SPANGPU_GSM0610_API SPANGPU_API
+
+enum
+{
+    GSM0610_PACKING_NONE = 0,
+    GSM0610_PACKING_WAV49 = 1,
+    GSM0610_PACKING_VOIP = 2
+};
+
+typedef struct
+{
+    int16_t LARc[8];
+    int16_t Nc[4];
+    int16_t bc[4];
+    int16_t Mc[4];
+    int16_t xmaxc[4];
+    int16_t xMc[4][13];
+} gsm0610_frame_t;
+
+typedef struct gsm0610_state_s gsm0610_state_t;
+
+struct gsm0610_state_s
+{
+    int packing;
+    spangpu_gsm0610_t *encoder;
+    spangpu_gsm0610_t *decoder;
+    uint8_t *row;               /* what a call's piece comes back in, before the caller's buffer gets its count of it */
+    size_t row_cap;
+    int caller_storage;
+};
+
+SPANGPU_GSM0610_API gsm0610_state_t *gsm0610_init(gsm0610_state_t *s, int packing);
+SPANGPU_GSM0610_API int gsm0610_release(gsm0610_state_t *s);
+SPANGPU_GSM0610_API int gsm0610_free(gsm0610_state_t *s);
+SPANGPU_GSM0610_API int gsm0610_set_packing(gsm0610_state_t *s, int packing);
+SPANGPU_GSM0610_API int gsm0610_encode(gsm0610_state_t *s, uint8_t code[], const int16_t amp[], int len);
+SPANGPU_GSM0610_API int gsm0610_decode(gsm0610_state_t *s, int16_t amp[], const uint8_t code[], int len);
+SPANGPU_GSM0610_API int gsm0610_pack_none(uint8_t c[76], const gsm0610_frame_t *s);
+SPANGPU_GSM0610_API int gsm0610_pack_wav49(uint8_t c[65], const gsm0610_frame_t *s);
+SPANGPU_GSM0610_API int gsm0610_pack_voip(uint8_t c[33], const gsm0610_frame_t *s);
+SPANGPU_GSM0610_API int gsm0610_unpack_none(gsm0610_frame_t *s, const uint8_t c[76]);
+SPANGPU_GSM0610_API int gsm0610_unpack_wav49(gsm0610_frame_t *s, const uint8_t c[65]);
+SPANGPU_GSM0610_API int gsm0610_unpack_voip(gsm0610_frame_t *s, const uint8_t c[33]);
+
 #if defined(__cplusplus)
 }
 #endif

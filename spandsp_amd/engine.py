@@ -518,6 +518,21 @@ def lib():
             "spangpu_g722_state_words": (ci, [vp]),
             "spangpu_g722_get_state": (ci, [vp, ci, vp]),
             "spangpu_g722_set_state": (ci, [vp, ci, vp]),
+            "spangpu_gsm0610_create": (ci, [C.POINTER(vp), ci, ci, ci, vp, ci]),
+            "spangpu_gsm0610_destroy": (None, [vp]),
+            "spangpu_gsm0610_channels": (ci, [vp]),
+            "spangpu_gsm0610_set_stream": (ci, [vp, vp]),
+            "spangpu_gsm0610_sync": (ci, [vp]),
+            "spangpu_gsm0610_encode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_gsm0610_decode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_gsm0610_encode_capacity": (ll, [vp, ci]),
+            "spangpu_gsm0610_decode_capacity": (ll, [vp, ci]),
+            "spangpu_gsm0610_counts_dev": (vp, [vp]),
+            "spangpu_gsm0610_set_packing": (ci, [vp, ci, ci]),
+            "spangpu_gsm0610_restart": (ci, [vp, ci, ci]),
+            "spangpu_gsm0610_state_words": (ci, [vp]),
+            "spangpu_gsm0610_get_state": (ci, [vp, ci, vp]),
+            "spangpu_gsm0610_set_state": (ci, [vp, ci, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -2348,6 +2363,42 @@ class G722Bank(_CodecBank):
 
     def restart(self, channel, rate, options):
         _check(lib().spangpu_g722_restart(self.h, channel, rate, options))
+
+
+# ---- GSM 06.10 codec banks (include/spangpu.h "GSM 06.10 codec banks") ---------------------
+GSM0610_ENCODER, GSM0610_DECODER = 0, 1
+GSM0610_PACKING_NONE, GSM0610_PACKING_WAV49, GSM0610_PACKING_VOIP = 0, 1, 2
+
+
+class Gsm0610Bank(_CodecBank):
+    """N GSM 06.10 encoders or decoders (gsm0610_encode / gsm0610_decode), each channel with its own packing (the list is
+    cycled over the channels), state in HBM.  A PCM row is int16 samples; lengths are whole frames (160 samples, 320 under
+    WAV49; 76, 33 or 65 bytes)."""
+    _prefix = "gsm0610"
+
+    def __init__(self, n_channels, direction, packings=GSM0610_PACKING_NONE, device=0):
+        p = np.atleast_1d(np.asarray(packings, np.int32)).copy()
+        self.n = n_channels
+        self.direction = direction
+        self.h = C.c_void_p()
+        _check(lib().spangpu_gsm0610_create(C.byref(self.h), device, n_channels, direction, p.ctypes.data, len(p)))
+        self.words = lib().spangpu_gsm0610_state_words(self.h)
+
+    def encode_host(self, pcm, samples, lens=None):
+        """pcm: [n][>= samples] int16 rows.  Returns (codes [n][encode_capacity(samples)] uint8, bytes [n])."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        return self._host("encode", pcm, samples, lens, (self.n, max(1, self.encode_capacity(samples))), np.uint8)
+
+    def decode_host(self, codes, nbytes, lens=None):
+        """codes: [n][>= nbytes] uint8 rows.  Returns (pcm [n][decode_capacity(nbytes)] int16, samples [n])."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        return self._host("decode", codes, nbytes, lens, (self.n, max(1, self.decode_capacity(nbytes))), np.int16)
+
+    def set_packing(self, channel, packing):
+        _check(lib().spangpu_gsm0610_set_packing(self.h, channel, packing))
+
+    def restart(self, channel, packing):
+        _check(lib().spangpu_gsm0610_restart(self.h, channel, packing))
 
 
 # ---- HDLC framing banks (include/spangpu.h "HDLC framing banks") ---------------------------

@@ -1825,6 +1825,39 @@ def bench_g726(args, dev, stream):
         "cpu_baseline_reason": "g726.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
 
 
+def codec_launches(args, stream, enc, dec, frames, in_stride, n_in, codes, cap, lens, out, out_stride):
+    """encode and decode launches of one bank pair, each between its own events: warm-up, then ticks for half a second"""
+    def tick(i, keep):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record(stream)
+        enc.encode_device(ctypes.c_void_p(frames[i % len(frames)].data_ptr()), in_stride, n_in, ctypes.c_void_p(codes.data_ptr()), cap)
+        e[1].record(stream)
+        dec.decode_device(ctypes.c_void_p(codes.data_ptr()), cap, int(lens.max()), ctypes.c_void_p(out.data_ptr()), out_stride, lens=lens)
+        e[2].record(stream)
+        if keep is not None:
+            keep.append(e)
+    warm = max(args.warmup, 10)
+    for i in range(warm):
+        tick(i, None)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(20):
+        tick(i, None)
+    torch.cuda.synchronize()
+    ticks = max(args.steps, int(0.6*20/(time.perf_counter() - t0)) + 1)
+    kept = []
+    t0 = time.perf_counter()
+    for i in range(ticks):
+        tick(warm + i, kept)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    e_us = [a.elapsed_time(b)*1e3 for a, b, _ in kept]
+    d_us = [b.elapsed_time(c)*1e3 for _, b, c in kept]
+    return {"steps": ticks, "ms_per_step": dt*1e3/ticks, "window_s": dt,
+            "encode": {"avg_launch_us": sum(e_us)/len(e_us), "min_launch_us": min(e_us)},
+            "decode": {"avg_launch_us": sum(d_us)/len(d_us), "min_launch_us": min(d_us)}}
+
+
 def bench_g722(args, dev, stream):
     """G.722 codec banks: g722_encode() of every line into HBM and g722_decode() from there, each launch between its own pair
     of events, 65 536 lines x one 20 ms tick (320 samples of a 16 kHz line, 160 of an 8 kHz one).  Once with every channel at
@@ -1865,38 +1898,6 @@ def bench_g722(args, dev, stream):
     enc.close()
     dec.close()
 
-    def launches(enc, dec, frames, in_stride, n_in, codes, cap, lens, out, out_stride):
-        """encode and decode launches of one bank pair, each between its own events: warm-up, then ticks for half a second"""
-        def tick(i, keep):
-            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-            e[0].record(stream)
-            enc.encode_device(ctypes.c_void_p(frames[i % len(frames)].data_ptr()), in_stride, n_in, ctypes.c_void_p(codes.data_ptr()), cap)
-            e[1].record(stream)
-            dec.decode_device(ctypes.c_void_p(codes.data_ptr()), cap, int(lens.max()), ctypes.c_void_p(out.data_ptr()), out_stride, lens=lens)
-            e[2].record(stream)
-            if keep is not None:
-                keep.append(e)
-        warm = max(args.warmup, 10)
-        for i in range(warm):
-            tick(i, None)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(20):
-            tick(i, None)
-        torch.cuda.synchronize()
-        ticks = max(args.steps, int(0.6*20/(time.perf_counter() - t0)) + 1)
-        kept = []
-        t0 = time.perf_counter()
-        for i in range(ticks):
-            tick(warm + i, kept)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        e_us = [a.elapsed_time(b)*1e3 for a, b, _ in kept]
-        d_us = [b.elapsed_time(c)*1e3 for _, b, c in kept]
-        return {"steps": ticks, "ms_per_step": dt*1e3/ticks, "window_s": dt,
-                "encode": {"avg_launch_us": sum(e_us)/len(e_us), "min_launch_us": min(e_us)},
-                "decode": {"avg_launch_us": sum(d_us)/len(d_us), "min_launch_us": min(d_us)}}
-
     def run_g722(configs):
         n_cfg = len(configs)
         r, o = [x[0] for x in configs], [GL.options_of(x[1], x[2]) for x in configs]
@@ -1923,7 +1924,7 @@ def bench_g722(args, dev, stream):
         class Enc:
             def encode_device(self, p, stride, n_in, c, cap):
                 enc.encode_device(p, stride, n_in, c, cap, lens=enc_lens)
-        res = launches(Enc(), dec, frames, 4*FRAME, 2*FRAME, codes, cap, lens, out, out_stride)
+        res = codec_launches(args, stream, Enc(), dec, frames, 4*FRAME, 2*FRAME, codes, cap, lens, out, out_stride)
         counts = torch.zeros(n_ch, dtype=torch.int32, device=dev)
         ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(dec.counts_dev()), ctypes.c_size_t(4*n_ch), 3)
         assert (counts.cpu().numpy() == take).all(), "a decoder did not make a tick of its bytes"
@@ -1945,7 +1946,7 @@ def bench_g722(args, dev, stream):
         out_stride = (enc.pcm_row_bytes(dec.decode_capacity(FRAME//2)) + 15) & ~15
         out = torch.zeros(n_ch, out_stride, dtype=torch.uint8, device=dev)
         lens = np.full(n_ch, FRAME//2, np.int32)
-        res = launches(enc, dec, frames, 2*FRAME, FRAME, codes, cap, lens, out, out_stride)
+        res = codec_launches(args, stream, enc, dec, frames, 2*FRAME, FRAME, codes, cap, lens, out, out_stride)
         enc.close()
         dec.close()
         return res
@@ -1979,6 +1980,96 @@ def bench_g722(args, dev, stream):
         "roofline": None,
         "cpu_baseline": None,
         "cpu_baseline_reason": "g722.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
+
+
+def bench_gsm0610(args, dev, stream):
+    """GSM 06.10 codec banks: gsm0610_encode() of every line into HBM and gsm0610_decode() from there, each launch between its
+    own pair of events, 65 536 lines x one 160-sample frame (a WAV49 channel brings its unit, a pair of frames).  Once per
+    packing with every channel alike, once with the three mixed within every wave; every timed window holds enough ticks to
+    last half a second.  In the same command, alternating with them, --repeats times: the host-to-device copy of the
+    65 536 x 160 int16 rows.  A 72-channel bank pair is held against the committed fixture first."""
+    import gsm0610_lines as GL
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    repeats = 3
+    the_lines = GL.lines()
+    # ---- the spot check: 72 channels, the three packings, six calls of two frames of the pulse train ----
+    cases = {(c.kind, c.packing, c.line): c for c in GL.cases(GL.load())}
+    p72 = [GL.PACKINGS[c % 3] for c in range(72)]
+    enc, dec = engine.Gsm0610Bank(72, engine.GSM0610_ENCODER, GL.PACKINGS), engine.Gsm0610Bank(72, engine.GSM0610_DECODER, GL.PACKINGS)
+    checked = 0
+    for k in range(6):
+        pcm = np.tile(the_lines[1][k*320:(k + 1)*320], (72, 1))
+        codes, counts = enc.encode_host(pcm, 320)
+        out, samples = dec.decode_host(codes, int(counts.max()), counts)
+        for c in range(72):
+            want = cases[(GL.ENCODE, p72[c], 1)].want[k*counts[c]:(k + 1)*counts[c]]
+            assert counts[c] == GL.unit_bytes(p72[c])*(1 if p72[c] == GL.WAV49 else 2) and np.array_equal(codes[c, :counts[c]], want), ("encode", c, k)
+            assert samples[c] == 320 and np.array_equal(out[c, :320], cases[(GL.DECODE, p72[c], 1)].want[k*320:(k + 1)*320]), ("decode", c, k)
+            checked += 1
+    enc.close()
+    dec.close()
+
+    def run(packings):
+        enc, dec = engine.Gsm0610Bank(n_ch, engine.GSM0610_ENCODER, packings), engine.Gsm0610Bank(n_ch, engine.GSM0610_DECODER, packings)
+        for b in (enc, dec):
+            b.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        idx = np.arange(n_ch)
+        pk = np.array(packings)[idx % len(packings)]
+        # frames[f][c]: a row of 320 int16; a channel that is not WAV49 brings the first 160 of it
+        nf = GL.N//320
+        src = np.stack([ln.reshape(nf, 320) for ln in the_lines])                                              # [5][nf][320]
+        frames = torch.tensor(src[(idx//len(packings)) % 5], device=dev).permute(1, 0, 2).contiguous()          # [nf][n_ch][320]
+        take = np.where(pk == GL.WAV49, 320, 160).astype(np.int32)
+        n_in = int(take.max())
+        cap = (enc.encode_capacity(n_in) + 15) & ~15
+        codes = torch.zeros(n_ch, cap, dtype=torch.uint8, device=dev)
+        lens = np.array([GL.unit_bytes(p) for p in packings], np.int32)[idx % len(packings)]
+        out_stride = (2*dec.decode_capacity(int(lens.max())) + 15) & ~15
+        out = torch.zeros(n_ch, out_stride, dtype=torch.uint8, device=dev)
+        enc_lens = None if len(packings) == 1 else take
+
+        class Enc:
+            def encode_device(self, p, stride, n, c, cap):
+                enc.encode_device(p, stride, n, c, cap, lens=enc_lens)
+        res = codec_launches(args, stream, Enc(), dec, frames, 640, n_in, codes, cap, lens, out, out_stride)
+        counts = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+        ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(dec.counts_dev()), ctypes.c_size_t(4*n_ch), 3)
+        assert (counts.cpu().numpy() == take).all(), "a decoder did not make its frames"
+        enc.close()
+        dec.close()
+        res.update({"packings": list(packings), "frames_per_tick": int(take.sum())//160, "code_bytes_per_tick": int(lens.sum()),
+                    "pcm_bytes_per_tick": int(take.sum())*2})
+        return res
+
+    names = {"none": [GL.NONE], "voip": [GL.VOIP], "wav49": [GL.WAV49], "mixed": list(GL.PACKINGS)}
+    runs = {k: [] for k in names}
+    runs["h2d_ms"] = []
+    for _ in range(repeats):
+        for k, p in names.items():
+            runs[k].append(run(p))
+            if k == "voip":
+                runs["h2d_ms"].append(copy_alone_ms(n_ch*FRAME*2, "h2d", dev))
+
+    def spread(name, side):
+        v = [r[side]["avg_launch_us"] for r in runs[name]]
+        return {"avg_launch_us_per_run": v, "min": min(v), "max": max(v), "min_launch_us": min(r[side]["min_launch_us"] for r in runs[name])}
+
+    uni = runs["voip"][0]
+    h2d_us = [x*1e3 for x in runs["h2d_ms"]]
+    value = n_ch*FRAME*2/(uni["ms_per_step"]*1e-3)/1e6
+    return {
+        "metric": "Msamples/s of a GSM 06.10 codec bank pair, VoIP packing (gsm0610_encode into HBM, gsm0610_decode from HBM; both directions counted)",
+        "value": value, "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0/2, "n_gpus": 1, "steps": uni["steps"], "warmup": max(args.warmup, 10),
+        "ms_per_step": uni["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+        "config": {"workload": "GSM 06.10 codec banks, %d channels x one frame (WAV49: a pair)" % n_ch, "channels_per_gpu": n_ch,
+                   "repeats": repeats, "spot_checked_against_fixture": checked},
+        "kernels": {k: {"encode": spread(k, "encode"), "decode": spread(k, "decode"), "frames_per_tick": runs[k][0]["frames_per_tick"],
+                        "code_bytes_per_tick": runs[k][0]["code_bytes_per_tick"], "runs": runs[k]} for k in names},
+        "yardsticks": {"h2d_copy_of_int16_rows_us_per_run": h2d_us},
+        "roofline": None,
+        "cpu_baseline": None,
+        "cpu_baseline_reason": "gsm0610_*.c are not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
 
 
 def bench_hdlc(args, dev, stream):
@@ -2316,7 +2407,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722", "gsm0610"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--rate", type=int, choices=[16000, 24000, 32000, 40000, 48000, 56000, 64000], default=None,
                     help="g726: the bit rate of the uniform run (32000); g722: the same (64000)")
@@ -2403,6 +2494,10 @@ def main():
     if args.workload == "g722":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         emit(bench_g722(args, dev, stream), "g722", args.channels or None)
+        return
+    if args.workload == "gsm0610":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        emit(bench_gsm0610(args, dev, stream), "gsm0610", args.channels or None)
         return
     if args.workload == "fax_fe":
         emit(bench_fax_fe(args, dev, stream), "fax_fe", args.channels or None)
