@@ -70,6 +70,15 @@ typedef struct logging_state_s
     void *user_data;
 } logging_state_t;
 
+/* What every lone object -- one that owns a private one-channel bank -- keeps beside its bank (csrc/shim_object.h): the row a
+   launch's piece comes back in before the caller's buffer gets its count of it, and who owns the object's storage. */
+typedef struct
+{
+    void *row;
+    size_t row_cap;             /* bytes */
+    int caller_storage;
+} spangpu_object_t;
+
 typedef void (*digits_rx_callback_t)(void *user_data, const char *digits, int len);
 typedef void (*span_tone_report_func_t)(void *user_data, int code, int level, int delay);
 typedef void (*tone_segment_func_t)(void *data, int f1, int f2, int duration);
@@ -457,7 +466,7 @@ struct dtmf_tx_state_s
     digits_tx_callback_t callback;
     void *callback_data;
     int puts;                   /* dtmf_tx_put() calls that queued digits (the callback's way of answering) */
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 SPANGPU_API extern const fsk_spec_t preset_fsk_specs[];
@@ -527,17 +536,13 @@ struct fsk_tx_state_s
     int baud_rate;
     int baud_frac;
     int shutdown;
-    int16_t *row;
-    int row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 struct modem_connect_tones_tx_state_s
 {
     spangpu_mcttx_t *bank;
     int tone_type;
-    int16_t *row;
-    int row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 struct async_tx_state_s
 {
@@ -550,7 +555,7 @@ struct async_tx_state_s
     uint16_t frame_in_progress;
     int bitpos;
     int presend_bits;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 SPANGPU_API fsk_tx_state_t *fsk_tx_init(fsk_tx_state_t *s, const fsk_spec_t *spec, span_get_bit_func_t get_bit, void *user_data);
@@ -596,9 +601,7 @@ typedef struct
     span_modem_status_func_t status_handler;
     void *status_user_data;
     logging_state_t logging;
-    int16_t *row;
-    int row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 } spangpu_modemtx_object_t;
 
 typedef struct v29_tx_state_s v29_tx_state_t;
@@ -687,12 +690,12 @@ typedef struct r2_mf_tx_state_s r2_mf_tx_state_t;
 struct bell_mf_tx_state_s
 {
     spangpu_txbank_t *bank;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 struct r2_mf_tx_state_s
 {
     spangpu_txbank_t *bank;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 SPANGPU_API bell_mf_tx_state_t *bell_mf_tx_init(bell_mf_tx_state_t *s);
 SPANGPU_API int bell_mf_tx_release(bell_mf_tx_state_t *s);
@@ -732,9 +735,7 @@ struct v18_state_s
     int current_mode;
     char stored_message[81];
     logging_state_t logging;
-    int16_t *row;
-    int row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 enum
@@ -918,9 +919,7 @@ struct adsi_tx_state_s
     int baudot_shift;
     spangpu_adsi_tx_t *bank;
     logging_state_t logging;
-    int16_t *row;
-    int row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 typedef struct adsi_rx_state_s adsi_rx_state_t;
@@ -931,7 +930,7 @@ struct adsi_rx_state_s
     span_put_msg_func_t put_msg;
     void *user_data;
     logging_state_t logging;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 SPANGPU_ADSI_API logging_state_t *adsi_rx_get_logging_state(adsi_rx_state_t *s);
@@ -990,9 +989,7 @@ struct g726_state_s
     int bits_per_sample;
     int packing;
     spangpu_g726_t *bank;
-    uint8_t *row;               /* what a call's piece comes back in, before the caller's buffer gets its count of it */
-    size_t row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 SPANGPU_G726_API g726_state_t *g726_init(g726_state_t *s, int bit_rate, int ext_coding, int packing);
@@ -1032,9 +1029,7 @@ struct g722_encode_state_s
     int eight_k;
     int packed;
     spangpu_g722_t *bank;
-    uint8_t *row;               /* what a call's piece comes back in, before the caller's buffer gets its count of it */
-    size_t row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 struct g722_decode_state_s
@@ -1043,9 +1038,7 @@ struct g722_decode_state_s
     int eight_k;
     int packed;
     spangpu_g722_t *bank;
-    uint8_t *row;
-    size_t row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 SPANGPU_G722_API g722_encode_state_t *g722_encode_init(g722_encode_state_t *s, int rate, int options);
@@ -1100,9 +1093,7 @@ struct gsm0610_state_s
     int packing;
     spangpu_gsm0610_t *encoder;
     spangpu_gsm0610_t *decoder;
-    uint8_t *row;               /* what a call's piece comes back in, before the caller's buffer gets its count of it */
-    size_t row_cap;
-    int caller_storage;
+    spangpu_object_t obj;
 };
 
 SPANGPU_GSM0610_API gsm0610_state_t *gsm0610_init(gsm0610_state_t *s, int packing);

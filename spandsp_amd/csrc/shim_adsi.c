@@ -3,12 +3,11 @@
  * include/spangpu_spandsp.h: adsi_*.  An object is a one-channel caller-ID bank of include/spangpu.h ("Caller-ID banks").
  * Without a GPU the two inits return NULL: there is no CPU implementation.  The field helpers are host code (adsi_host.c).
  */
-#include <stdlib.h>
-#include <string.h>
-
-#include "spangpu_spandsp.h"
+#include "shim_object.h"
 
 #define PIECE       4096        /* samples per launch of one object */
+
+OBJ_SENDER_LOOP(tx_pieces, spangpu_adsi_tx_t, spangpu_adsi_tx)
 
 static int fsk_standard(int standard)
 {
@@ -17,22 +16,16 @@ static int fsk_standard(int standard)
 
 adsi_tx_state_t *adsi_tx_init(adsi_tx_state_t *s, int standard)
 {
-    const int mine = (s != NULL);
     int32_t std = standard;
     spangpu_adsi_tx_t *bank;
 
     if (!fsk_standard(standard)  ||  spangpu_adsi_tx_create(&bank, 0, 1, &std, 1) != SPANGPU_OK)
         return NULL;
-    if (mine)
-    {
-        memset(s, 0, sizeof(*s));
-    }
-    else if ((s = (adsi_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if ((s = OBJ_TAKE(s, adsi_tx_state_t)) == NULL)
     {
         spangpu_adsi_tx_destroy(bank);
         return NULL;
     }
-    s->caller_storage = mine;
     s->bank = bank;
     s->standard = standard;
     /* what memset() leaves of a logging_state_t, with the rate span_log would be given */
@@ -47,9 +40,7 @@ int adsi_tx_release(adsi_tx_state_t *s)
         if (s->bank)
             spangpu_adsi_tx_destroy(s->bank);
         s->bank = NULL;
-        free(s->row);
-        s->row = NULL;
-        s->row_cap = 0;
+        obj_drop(&s->obj, NULL);
     }
     return 0;
 }
@@ -59,41 +50,16 @@ int adsi_tx_free(adsi_tx_state_t *s)
     if (s)
     {
         adsi_tx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
 
 int adsi_tx(adsi_tx_state_t *s, int16_t amp[], int max_len)
 {
-    int done = 0;
-
     if (s == NULL  ||  s->bank == NULL  ||  max_len <= 0)
         return 0;
-    while (done < max_len)
-    {
-        const int piece = (max_len - done > PIECE)  ?  PIECE  :  (max_len - done);
-        int32_t got = 0;
-
-        if (s->row_cap < piece)
-        {
-            int16_t *r = (int16_t *) realloc(s->row, (size_t) piece*sizeof(int16_t));
-
-            if (r == NULL)
-                break;
-            s->row = r;
-            s->row_cap = piece;
-        }
-        /* the bank fills a row with zeros behind what it made; the reference leaves the caller's samples there alone */
-        if (spangpu_adsi_tx(s->bank, SPANGPU_MEM_HOST, s->row, piece, piece, &got) != SPANGPU_OK)
-            break;
-        memcpy(amp + done, s->row, (size_t) got*sizeof(int16_t));
-        done += got;
-        if (got < piece)
-            break;
-    }
-    return done;
+    return tx_pieces(&s->obj, s->bank, amp, max_len, PIECE);
 }
 
 int adsi_tx_put_message(adsi_tx_state_t *s, const uint8_t *msg, int len)
@@ -127,22 +93,16 @@ logging_state_t *adsi_tx_get_logging_state(adsi_tx_state_t *s)
 
 adsi_rx_state_t *adsi_rx_init(adsi_rx_state_t *s, int standard, span_put_msg_func_t put_msg, void *user_data)
 {
-    const int mine = (s != NULL);
     int32_t std = standard;
     spangpu_adsi_rx_t *bank;
 
     if (!fsk_standard(standard)  ||  spangpu_adsi_rx_create(&bank, 0, 1, &std, 1) != SPANGPU_OK)
         return NULL;
-    if (mine)
-    {
-        memset(s, 0, sizeof(*s));
-    }
-    else if ((s = (adsi_rx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if ((s = OBJ_TAKE(s, adsi_rx_state_t)) == NULL)
     {
         spangpu_adsi_rx_destroy(bank);
         return NULL;
     }
-    s->caller_storage = mine;
     s->bank = bank;
     s->standard = standard;
     s->put_msg = put_msg;
@@ -167,8 +127,7 @@ int adsi_rx_free(adsi_rx_state_t *s)
     if (s)
     {
         adsi_rx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }

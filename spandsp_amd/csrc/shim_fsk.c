@@ -10,6 +10,7 @@
 
 #include "spangpu_spandsp.h"
 #include "shim_group.h"
+#include "shim_object.h"
 
 /* preset_fsk_specs[], src/fsk.c:60-155 */
 const fsk_spec_t preset_fsk_specs[] =
@@ -510,21 +511,18 @@ const char *modem_connect_tone_to_str(int tone)
 /* ---- dtmf_tx: one private sender per object ---------------------------------------------------------- */
 dtmf_tx_state_t *dtmf_tx_init(dtmf_tx_state_t *s, digits_tx_callback_t callback, void *user_data)
 {
-    const int mine = (s != NULL);
+    spangpu_txbank_t *bank;
 
-    if (mine)
-        memset(s, 0, sizeof(*s));
-    else if ((s = (dtmf_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if (spangpu_txbank_create(&bank, 0, SPANGPU_TX_DTMF, 1) != SPANGPU_OK)
         return NULL;
-    s->caller_storage = mine;
-    s->callback = callback;
-    s->callback_data = user_data;
-    if (spangpu_txbank_create(&s->bank, 0, SPANGPU_TX_DTMF, 1) != SPANGPU_OK)
+    if ((s = OBJ_TAKE(s, dtmf_tx_state_t)) == NULL)
     {
-        if (!mine)
-            free(s);
+        spangpu_txbank_destroy(bank);
         return NULL;
     }
+    s->bank = bank;
+    s->callback = callback;
+    s->callback_data = user_data;
     return s;
 }
 
@@ -543,8 +541,7 @@ int dtmf_tx_free(dtmf_tx_state_t *s)
     if (s)
     {
         dtmf_tx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
@@ -597,19 +594,16 @@ int dtmf_tx(dtmf_tx_state_t *s, int16_t amp[], int max_samples)
 /* ---- bell_mf_tx / r2_mf_tx: one private sender per object (src/bell_r2_mf.c:281-372, 386-462) ----------------- */
 bell_mf_tx_state_t *bell_mf_tx_init(bell_mf_tx_state_t *s)
 {
-    const int mine = (s != NULL);
+    spangpu_txbank_t *bank;
 
-    if (mine)
-        memset(s, 0, sizeof(*s));
-    else if ((s = (bell_mf_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if (spangpu_txbank_create(&bank, 0, SPANGPU_TX_BELL_MF, 1) != SPANGPU_OK)
         return NULL;
-    s->caller_storage = mine;
-    if (spangpu_txbank_create(&s->bank, 0, SPANGPU_TX_BELL_MF, 1) != SPANGPU_OK)
+    if ((s = OBJ_TAKE(s, bell_mf_tx_state_t)) == NULL)
     {
-        if (!mine)
-            free(s);
+        spangpu_txbank_destroy(bank);
         return NULL;
     }
+    s->bank = bank;
     return s;
 }
 
@@ -628,8 +622,7 @@ int bell_mf_tx_free(bell_mf_tx_state_t *s)
     if (s)
     {
         bell_mf_tx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
@@ -652,19 +645,16 @@ int bell_mf_tx(bell_mf_tx_state_t *s, int16_t amp[], int max_samples)
 
 r2_mf_tx_state_t *r2_mf_tx_init(r2_mf_tx_state_t *s, bool fwd)
 {
-    const int mine = (s != NULL);
+    spangpu_txbank_t *bank;
 
-    if (mine)
-        memset(s, 0, sizeof(*s));
-    else if ((s = (r2_mf_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if (spangpu_txbank_create(&bank, 0, fwd  ?  SPANGPU_TX_R2_MF_FWD  :  SPANGPU_TX_R2_MF_BACK, 1) != SPANGPU_OK)
         return NULL;
-    s->caller_storage = mine;
-    if (spangpu_txbank_create(&s->bank, 0, fwd  ?  SPANGPU_TX_R2_MF_FWD  :  SPANGPU_TX_R2_MF_BACK, 1) != SPANGPU_OK)
+    if ((s = OBJ_TAKE(s, r2_mf_tx_state_t)) == NULL)
     {
-        if (!mine)
-            free(s);
+        spangpu_txbank_destroy(bank);
         return NULL;
     }
+    s->bank = bank;
     return s;
 }
 
@@ -683,8 +673,7 @@ int r2_mf_tx_free(r2_mf_tx_state_t *s)
     if (s)
     {
         r2_mf_tx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }

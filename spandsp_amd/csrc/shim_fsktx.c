@@ -6,26 +6,9 @@
  * async_tx* is host code as it is in the reference (src/async.c:277-393).
  * Without a GPU fsk_tx_init() and modem_connect_tones_tx_init() return NULL: there is no CPU implementation.
  */
-#include <stdlib.h>
-#include <string.h>
-
-#include "spangpu_spandsp.h"
+#include "shim_object.h"
 
 #define PIECE       8192        /* samples per launch of one object: at most as many bits, which is what its ring takes */
-
-static int16_t *row_for(int16_t **row, int *cap, int len)
-{
-    if (len > *cap)
-    {
-        int16_t *r = (int16_t *) realloc(*row, (size_t) len*sizeof(int16_t));
-
-        if (r == NULL)
-            return NULL;
-        *row = r;
-        *cap = len;
-    }
-    return *row;
-}
 
 /* ---- fsk_tx ---------------------------------------------------------------------------------------------- */
 static void spec_of(spangpu_fsk_spec_t *sp, const fsk_spec_t *spec)
@@ -39,26 +22,23 @@ static void spec_of(spangpu_fsk_spec_t *sp, const fsk_spec_t *spec)
 
 fsk_tx_state_t *fsk_tx_init(fsk_tx_state_t *s, const fsk_spec_t *spec, span_get_bit_func_t get_bit, void *user_data)
 {
-    const int mine = (s != NULL);
     spangpu_fsk_spec_t sp;
+    spangpu_fsktx_t *bank;
 
     if (spec == NULL)
         return NULL;
-    if (mine)
-        memset(s, 0, sizeof(*s));
-    else if ((s = (fsk_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    spec_of(&sp, spec);
+    if (spangpu_fsktx_create(&bank, 0, 1, &sp, SPANGPU_FSKTX_QUEUE, NULL, PIECE) != SPANGPU_OK)
         return NULL;
-    s->caller_storage = mine;
+    if ((s = OBJ_TAKE(s, fsk_tx_state_t)) == NULL)
+    {
+        spangpu_fsktx_destroy(bank);
+        return NULL;
+    }
+    s->bank = bank;
     s->get_bit = get_bit;
     s->get_bit_user_data = user_data;
     s->baud_rate = spec->baud_rate;
-    spec_of(&sp, spec);
-    if (spangpu_fsktx_create(&s->bank, 0, 1, &sp, SPANGPU_FSKTX_QUEUE, NULL, PIECE) != SPANGPU_OK)
-    {
-        if (!mine)
-            free(s);
-        return NULL;
-    }
     return s;
 }
 
@@ -84,9 +64,7 @@ int fsk_tx_release(fsk_tx_state_t *s)
         if (s->bank)
             spangpu_fsktx_destroy(s->bank);
         s->bank = NULL;
-        free(s->row);
-        s->row = NULL;
-        s->row_cap = 0;
+        obj_drop(&s->obj, NULL);
     }
     return 0;
 }
@@ -96,8 +74,7 @@ int fsk_tx_free(fsk_tx_state_t *s)
     if (s)
     {
         fsk_tx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
@@ -130,26 +107,14 @@ int fsk_tx(fsk_tx_state_t *s, int16_t amp[], int len)
     {
         const int piece = (len - done > PIECE)  ?  PIECE  :  (len - done);
         const int due = (int) spangpu_fsktx_bits_due(s->baud_rate, s->baud_frac, piece);
-        int32_t n_bits = 0;
+        int32_t n_bits;
         int32_t got = 0;
-        int ended = 0;
+        int ended;
         int16_t *row;
 
         /* exactly the calls fsk_tx() makes, in order, up to SIG_STATUS_END_OF_DATA (fsk.c:176-189) */
-        memset(bits, 0, sizeof(bits));
-        while (n_bits < due)
-        {
-            const int bit = s->get_bit(s->get_bit_user_data);
-
-            if (bit == SIG_STATUS_END_OF_DATA)
-            {
-                ended = 1;
-                break;
-            }
-            bits[n_bits >> 3] |= (uint8_t) ((bit & 1) << (n_bits & 7));
-            n_bits++;
-        }
-        if ((row = row_for(&s->row, &s->row_cap, piece)) == NULL)
+        n_bits = obj_pull_bits(s->get_bit, s->get_bit_user_data, due, bits, sizeof(bits), &ended);
+        if ((row = (int16_t *) obj_room(&s->obj, (size_t) piece*sizeof(int16_t))) == NULL)
             return done;
         if ((n_bits > 0  &&  spangpu_fsktx_put_bits(s->bank, 0, 1, bits, PIECE/8, &n_bits, NULL) != SPANGPU_OK)
             ||  (ended  &&  spangpu_fsktx_end_of_data(s->bank, 0, 1) != SPANGPU_OK)
@@ -175,20 +140,17 @@ int fsk_tx(fsk_tx_state_t *s, int16_t amp[], int len)
 /* ---- modem_connect_tones_tx -------------------------------------------------------------------------------- */
 modem_connect_tones_tx_state_t *modem_connect_tones_tx_init(modem_connect_tones_tx_state_t *s, int tone_type)
 {
-    const int mine = (s != NULL);
+    spangpu_mcttx_t *bank;
 
-    if (mine)
-        memset(s, 0, sizeof(*s));
-    else if ((s = (modem_connect_tones_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if (spangpu_mcttx_create(&bank, 0, tone_type, 1) != SPANGPU_OK)
         return NULL;
-    s->caller_storage = mine;
-    s->tone_type = tone_type;
-    if (spangpu_mcttx_create(&s->bank, 0, tone_type, 1) != SPANGPU_OK)
+    if ((s = OBJ_TAKE(s, modem_connect_tones_tx_state_t)) == NULL)
     {
-        if (!mine)
-            free(s);
+        spangpu_mcttx_destroy(bank);
         return NULL;
     }
+    s->bank = bank;
+    s->tone_type = tone_type;
     return s;
 }
 
@@ -199,9 +161,7 @@ int modem_connect_tones_tx_release(modem_connect_tones_tx_state_t *s)
         if (s->bank)
             spangpu_mcttx_destroy(s->bank);
         s->bank = NULL;
-        free(s->row);
-        s->row = NULL;
-        s->row_cap = 0;
+        obj_drop(&s->obj, NULL);
     }
     return 0;
 }
@@ -211,8 +171,7 @@ int modem_connect_tones_tx_free(modem_connect_tones_tx_state_t *s)
     if (s)
     {
         modem_connect_tones_tx_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
@@ -224,7 +183,7 @@ int modem_connect_tones_tx(modem_connect_tones_tx_state_t *s, int16_t amp[], int
 
     if (s == NULL  ||  s->bank == NULL  ||  len <= 0)
         return 0;
-    if ((row = row_for(&s->row, &s->row_cap, len)) == NULL
+    if ((row = (int16_t *) obj_room(&s->obj, (size_t) len*sizeof(int16_t))) == NULL
         ||  spangpu_mcttx_tx(s->bank, SPANGPU_MEM_HOST, row, len, len, &got) != SPANGPU_OK)
         return 0;
     memcpy(amp, row, (size_t) got*sizeof(int16_t));
@@ -275,14 +234,9 @@ void async_tx_presend_bits(async_tx_state_t *s, int bits)
 async_tx_state_t *async_tx_init(async_tx_state_t *s, int data_bits, int parity, int stop_bits, bool use_v14,
                                 span_get_byte_func_t get_byte, void *user_data)
 {
-    const int mine = (s != NULL);
-
     (void) use_v14;
-    if (mine)
-        memset(s, 0, sizeof(*s));
-    else if ((s = (async_tx_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if ((s = OBJ_TAKE(s, async_tx_state_t)) == NULL)
         return NULL;
-    s->caller_storage = mine;
     s->data_bits = data_bits;
     s->parity = parity;
     s->stop_bits = stop_bits;
@@ -299,7 +253,7 @@ int async_tx_release(async_tx_state_t *s)
 
 int async_tx_free(async_tx_state_t *s)
 {
-    if (s  &&  !s->caller_storage)
-        free(s);
+    if (s)
+        obj_drop(&s->obj, s);
     return 0;
 }

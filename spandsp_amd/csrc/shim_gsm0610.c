@@ -5,12 +5,12 @@
  * reference's one state type serves both directions.  Without a GPU gsm0610_init() returns NULL: there is no CPU
  * implementation.
  */
-#include <stdlib.h>
-#include <string.h>
-
-#include "spangpu_spandsp.h"
+#include "shim_object.h"
 
 #define PIECE_FRAMES    32          /* units (a frame, or a WAV49 pair) per launch of one object */
+
+OBJ_CODEC_LOOP(encode_pieces, spangpu_gsm0610_t, spangpu_gsm0610_encode_capacity, spangpu_gsm0610_encode)
+OBJ_CODEC_LOOP(decode_pieces, spangpu_gsm0610_t, spangpu_gsm0610_decode_capacity, spangpu_gsm0610_decode)
 
 /* a packing the reference's switch statements do not name is GSM0610_PACKING_NONE to them */
 static int known(int packing)
@@ -28,23 +28,8 @@ static int unit_bytes(int packing)
     return (packing == GSM0610_PACKING_WAV49)  ?  65  :  ((packing == GSM0610_PACKING_VOIP)  ?  33  :  76);
 }
 
-static int room(uint8_t **row, size_t *cap, size_t bytes)
-{
-    if (*cap < bytes)
-    {
-        uint8_t *r = (uint8_t *) realloc(*row, bytes);
-
-        if (r == NULL)
-            return 0;
-        *row = r;
-        *cap = bytes;
-    }
-    return 1;
-}
-
 gsm0610_state_t *gsm0610_init(gsm0610_state_t *s, int packing)
 {
-    const int mine = (s != NULL);
     const int32_t p = known(packing);
     spangpu_gsm0610_t *enc;
     spangpu_gsm0610_t *dec;
@@ -56,17 +41,12 @@ gsm0610_state_t *gsm0610_init(gsm0610_state_t *s, int packing)
         spangpu_gsm0610_destroy(enc);
         return NULL;
     }
-    if (mine)
-    {
-        memset(s, 0, sizeof(*s));
-    }
-    else if ((s = (gsm0610_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if ((s = OBJ_TAKE(s, gsm0610_state_t)) == NULL)
     {
         spangpu_gsm0610_destroy(enc);
         spangpu_gsm0610_destroy(dec);
         return NULL;
     }
-    s->caller_storage = mine;
     s->encoder = enc;
     s->decoder = dec;
     s->packing = p;
@@ -83,9 +63,7 @@ int gsm0610_release(gsm0610_state_t *s)
             spangpu_gsm0610_destroy(s->decoder);
         s->encoder = NULL;
         s->decoder = NULL;
-        free(s->row);
-        s->row = NULL;
-        s->row_cap = 0;
+        obj_drop(&s->obj, NULL);
     }
     return 0;
 }
@@ -95,8 +73,7 @@ int gsm0610_free(gsm0610_state_t *s)
     if (s)
     {
         gsm0610_release(s);
-        if (!s->caller_storage)
-            free(s);
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
@@ -115,55 +92,17 @@ int gsm0610_set_packing(gsm0610_state_t *s, int packing)
 
 int gsm0610_encode(gsm0610_state_t *s, uint8_t code[], const int16_t amp[], int len)
 {
-    int done = 0;
-    int bytes = 0;
-
     if (s == NULL  ||  s->encoder == NULL  ||  code == NULL  ||  amp == NULL)
         return 0;
     /* whole frames: the reference reads past amp[len] at a partial one */
     len -= len%unit_samples(s->packing);
-    while (done < len)
-    {
-        const int most = PIECE_FRAMES*unit_samples(s->packing);
-        const int piece = (len - done > most)  ?  most  :  (len - done);
-        const long long cap = spangpu_gsm0610_encode_capacity(s->encoder, piece);
-        int32_t got = 0;
-
-        if (cap <= 0  ||  !room(&s->row, &s->row_cap, (size_t) cap))
-            break;
-        if (spangpu_gsm0610_encode(s->encoder, amp + done, SPANGPU_MEM_HOST, (long long) piece*2, NULL, piece, s->row, SPANGPU_MEM_HOST,
-                                   cap, &got) != SPANGPU_OK)
-            break;
-        memcpy(code + bytes, s->row, (size_t) got);
-        bytes += got;
-        done += piece;
-    }
-    return bytes;
+    return encode_pieces(&s->obj, s->encoder, amp, 2, code, 1, len, PIECE_FRAMES*unit_samples(s->packing));
 }
 
 int gsm0610_decode(gsm0610_state_t *s, int16_t amp[], const uint8_t code[], int len)
 {
-    int done = 0;
-    int samples = 0;
-
     if (s == NULL  ||  s->decoder == NULL  ||  code == NULL  ||  amp == NULL)
         return 0;
     len -= len%unit_bytes(s->packing);
-    while (done < len)
-    {
-        const int most = PIECE_FRAMES*unit_bytes(s->packing);
-        const int piece = (len - done > most)  ?  most  :  (len - done);
-        const long long cap = spangpu_gsm0610_decode_capacity(s->decoder, piece);
-        int32_t got = 0;
-
-        if (cap <= 0  ||  !room(&s->row, &s->row_cap, (size_t) cap*2))
-            break;
-        if (spangpu_gsm0610_decode(s->decoder, code + done, SPANGPU_MEM_HOST, piece, NULL, piece, s->row, SPANGPU_MEM_HOST,
-                                   (long long) (cap*2), &got) != SPANGPU_OK)
-            break;
-        memcpy(amp + samples, s->row, (size_t) got*2);
-        samples += got;
-        done += piece;
-    }
-    return samples;
+    return decode_pieces(&s->obj, s->decoder, code, 1, amp, 2, len, PIECE_FRAMES*unit_bytes(s->packing));
 }

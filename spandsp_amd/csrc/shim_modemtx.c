@@ -5,10 +5,7 @@
  * call needs, in order, queues them and launches.  Without a GPU the _init() functions return NULL: there is no CPU
  * implementation.
  */
-#include <stdlib.h>
-#include <string.h>
-
-#include "spangpu_spandsp.h"
+#include "shim_object.h"
 
 #define PIECE       4096        /* samples per launch of one object */
 #define RING        8192        /* bits its ring takes: 14400 bps makes 1.8 bits a sample */
@@ -18,29 +15,25 @@ typedef spangpu_modemtx_object_t obj_t;
 static obj_t *obj_init(obj_t *o, size_t size, int modem, const char *protocol, int bit_rate, int tep, span_get_bit_func_t get_bit,
                        void *user_data)
 {
-    const int mine = (o != NULL);
     spangpu_modemtx_cursor_t cursor;
+    spangpu_modemtx_t *bank;
 
-    /* as the reference: a bad bit rate returns NULL and leaves the caller's storage alone */
-    if (spangpu_modemtx_cursor_init(&cursor, modem, bit_rate, tep, 0) != SPANGPU_OK)
+    /* as the reference: a bad bit rate returns NULL and leaves the caller's storage alone; so does a bank that cannot be made */
+    if (spangpu_modemtx_cursor_init(&cursor, modem, bit_rate, tep, 0) != SPANGPU_OK
+        ||  spangpu_modemtx_create_ex(&bank, 0, modem, 1, bit_rate, tep, SPANGPU_MODEMTX_QUEUE, NULL, RING) != SPANGPU_OK)
         return NULL;
-    if (mine)
-        memset(o, 0, size);
-    else if ((o = (obj_t *) calloc(1, size)) == NULL)
+    if ((o = (obj_t *) obj_take(o, size, offsetof(obj_t, obj))) == NULL)
+    {
+        spangpu_modemtx_destroy(bank);
         return NULL;
-    o->caller_storage = mine;
+    }
+    o->bank = bank;
     o->cursor = cursor;
     o->get_bit = get_bit;
     o->get_bit_user_data = user_data;
     /* what span_log_init(.., SPAN_LOG_NONE, NULL) + span_log_set_protocol() leave behind (v29tx.c:423-424 and twins) */
     o->logging.samples_per_second = 8000;
     o->logging.protocol = protocol;
-    if (spangpu_modemtx_create_ex(&o->bank, 0, modem, 1, bit_rate, tep, SPANGPU_MODEMTX_QUEUE, NULL, RING) != SPANGPU_OK)
-    {
-        if (!mine)
-            free(o);
-        return NULL;
-    }
     return o;
 }
 
@@ -62,9 +55,7 @@ static int obj_release(obj_t *o)
         if (o->bank)
             spangpu_modemtx_destroy(o->bank);
         o->bank = NULL;
-        free(o->row);
-        o->row = NULL;
-        o->row_cap = 0;
+        obj_drop(&o->obj, NULL);
     }
     return 0;
 }
@@ -74,8 +65,7 @@ static int obj_free(obj_t *o)
     if (o)
     {
         obj_release(o);
-        if (!o->caller_storage)
-            free(o);
+        obj_drop(&o->obj, o);
     }
     return 0;
 }
@@ -94,47 +84,29 @@ static int obj_tx(obj_t *o, int16_t amp[], int len)
         const long long due = spangpu_modemtx_cursor_advance(&ahead, piece, -1);
         const int32_t *channels;
         const int32_t *kinds;
-        int32_t n_bits = 0;
+        int32_t n_bits;
         int32_t got = 0;
-        int ended = 0;
+        int16_t *row;
+        int ended;
         int events;
         int i;
 
         /* exactly the calls xxx_tx() makes, in order, up to SIG_STATUS_END_OF_DATA (v29tx.c:108-118) */
         if (due < 0  ||  due > RING)
             return done;
-        memset(bits, 0, sizeof(bits));
-        while (n_bits < due)
-        {
-            const int bit = o->get_bit(o->get_bit_user_data);
-
-            if (bit == SIG_STATUS_END_OF_DATA)
-            {
-                if (o->status_handler)
-                    o->status_handler(o->status_user_data, SIG_STATUS_END_OF_DATA);
-                ended = 1;
-                break;
-            }
-            bits[n_bits >> 3] |= (uint8_t) ((bit & 1) << (n_bits & 7));
-            n_bits++;
-        }
-        if (o->row_cap < piece)
-        {
-            int16_t *r = (int16_t *) realloc(o->row, (size_t) piece*sizeof(int16_t));
-
-            if (r == NULL)
-                return done;
-            o->row = r;
-            o->row_cap = piece;
-        }
+        n_bits = obj_pull_bits(o->get_bit, o->get_bit_user_data, due, bits, sizeof(bits), &ended);
+        if (ended  &&  o->status_handler)
+            o->status_handler(o->status_user_data, SIG_STATUS_END_OF_DATA);
+        if ((row = (int16_t *) obj_room(&o->obj, (size_t) piece*sizeof(int16_t))) == NULL)
+            return done;
         if ((n_bits > 0  &&  spangpu_modemtx_put_bits(o->bank, 0, 1, bits, RING/8, &n_bits, NULL) != SPANGPU_OK)
             ||  (ended  &&  spangpu_modemtx_end_of_data(o->bank, 0, 1) != SPANGPU_OK)
-            ||  ((done == 0)  ?  spangpu_modemtx_tx_lens(o->bank, SPANGPU_MEM_HOST, o->row, piece, piece, &got)
-                              :  spangpu_modemtx_tx_continue(o->bank, SPANGPU_MEM_HOST, o->row, piece, piece, &got)) < 0)
+            ||  ((done == 0)  ?  spangpu_modemtx_tx_lens(o->bank, SPANGPU_MEM_HOST, row, piece, piece, &got)
+                              :  spangpu_modemtx_tx_continue(o->bank, SPANGPU_MEM_HOST, row, piece, piece, &got)) < 0)
             return done;
         if (done > 0  ||  got > 0)
             spangpu_modemtx_cursor_advance(&o->cursor, piece, ended  ?  n_bits  :  -1);
-        memcpy(amp + done, o->row, (size_t) got*sizeof(int16_t));
+        memcpy(amp + done, row, (size_t) got*sizeof(int16_t));
         done += got;
         events = spangpu_modemtx_events(o->bank, &channels, &kinds);
         for (i = 0;  i < events;  i++)

@@ -3,17 +3,15 @@
  * modes, declared in include/spangpu_spandsp.h: v18_*.  An object is a one-channel V.18 text bank of include/spangpu.h
  * ("V.18 text banks").  Without a GPU v18_init() returns NULL: there is no CPU implementation.
  */
-#include <stdlib.h>
-#include <string.h>
-
-#include "spangpu_spandsp.h"
+#include "shim_object.h"
 
 #define PIECE       4096        /* samples per launch of one object */
+
+OBJ_SENDER_LOOP(tx_pieces, spangpu_v18_t, spangpu_v18_tx)
 
 v18_state_t *v18_init(v18_state_t *s, bool calling_party, int mode, int nation, span_put_msg_func_t put_msg, void *put_msg_user_data,
                       span_modem_status_func_t status_handler, void *status_handler_user_data)
 {
-    const int mine = (s != NULL);
     int32_t bank_mode;
     spangpu_v18_t *bank;
 
@@ -25,16 +23,11 @@ v18_state_t *v18_init(v18_state_t *s, bool calling_party, int mode, int nation, 
     bank_mode = mode;
     if (spangpu_v18_create(&bank, 0, 1, &bank_mode, 1, calling_party) != SPANGPU_OK)
         return NULL;
-    if (mine)
-    {
-        memset(s, 0, sizeof(*s));
-    }
-    else if ((s = (v18_state_t *) calloc(1, sizeof(*s))) == NULL)
+    if ((s = OBJ_TAKE(s, v18_state_t)) == NULL)
     {
         spangpu_v18_destroy(bank);
         return NULL;
     }
-    s->caller_storage = mine;
     s->bank = bank;
     s->current_mode = mode;
     s->put_msg = put_msg;
@@ -54,9 +47,7 @@ int v18_release(v18_state_t *s)
         if (s->bank)
             spangpu_v18_destroy(s->bank);
         s->bank = NULL;
-        free(s->row);
-        s->row = NULL;
-        s->row_cap = 0;
+        obj_drop(&s->obj, NULL);
     }
     return 0;
 }
@@ -66,46 +57,16 @@ int v18_free(v18_state_t *s)
     if (s)
     {
         v18_release(s);
-        if (!s->caller_storage)
-            free(s);
-    }
-    return 0;
-}
-
-static int row_for(v18_state_t *s, int n)
-{
-    if (s->row_cap < n)
-    {
-        int16_t *r = (int16_t *) realloc(s->row, (size_t) n*sizeof(int16_t));
-
-        if (r == NULL)
-            return -1;
-        s->row = r;
-        s->row_cap = n;
+        obj_drop(&s->obj, s);
     }
     return 0;
 }
 
 int v18_tx(v18_state_t *s, int16_t amp[], int max_len)
 {
-    int done = 0;
-
     if (s == NULL  ||  s->bank == NULL  ||  max_len <= 0)
         return 0;
-    while (done < max_len)
-    {
-        const int piece = (max_len - done > PIECE)  ?  PIECE  :  (max_len - done);
-        int32_t got = 0;
-
-        /* the bank fills a row with zeros behind what it made; the reference leaves the caller's samples there alone */
-        if (row_for(s, piece) < 0  ||  spangpu_v18_tx(s->bank, SPANGPU_MEM_HOST, s->row, piece, piece, &got) != SPANGPU_OK)
-            break;
-        memcpy(amp + done, s->row, (size_t) got*sizeof(int16_t));
-        done += got;
-        if (got < piece)
-            break;
-    }
-    return done;
+    return tx_pieces(&s->obj, s->bank, amp, max_len, PIECE);
 }
 
 int v18_rx(v18_state_t *s, const int16_t amp[], int len)
