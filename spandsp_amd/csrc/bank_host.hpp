@@ -6,10 +6,12 @@
 // Who uses what.  The sender and side-receiver banks (txgen, modemtx, fsktx, v18, fsk, mct, sigtone, awgn _api.hip) and the
 // modem receiver bank (modem_api.hip) embed BankCore and PcmStage; the echo canceller bank (echo_api.hip) embeds BankCore for
 // its device, channel count and stream alone (its four-row staging is its own).  The sets of banks over several devices
-// (shard_api.hip) sit on shard_core.hpp, which holds banks of these kinds.  The tone bank (spangpu_api.hip), the feeds and the
-// primitives take SPG_TRY only: two joined streams and slot rings are another shape.
-// The six banks with an _rx_var entry point (fsk, mct, sigtone, modem, v18, adsi _api.hip) keep that call's per-channel lengths
-// in a VarLens; those six and the HDLC receiver and FAX front-end banks (hdlc_api.hip, faxfe_api.hip) hand a call's result
+// (shard_api.hip) sit on shard_core.hpp, which holds banks of these kinds.  The tone bank (tone_bank.hpp; tone_api, tone_rx,
+// tone_state, tone_cadence .hip) embeds BankCore for its device, channel count and stream, a VarLens, and stages host frames
+// with grow(); its two float / int state arrays, its three frame formats and its two joined streams stay its own (every core
+// call that uses c.stream comes behind its joined()).  The feeds and the primitives take SPG_TRY only: slot rings are another shape.
+// The seven banks with an _rx_var entry point (tone, fsk, mct, sigtone, modem, v18, adsi) keep that call's per-channel lengths
+// in a VarLens; the last six and the HDLC receiver and FAX front-end banks (hdlc_api.hip, faxfe_api.hip) hand a call's result
 // rows to the host through CountRows, count_row_scan() and rows_fetch().
 // The codec banks (g726_api.hip, g722_api.hip) embed codec_host.hpp's CodecBank, and through it BankCore, a VarLens and a
 // CountRows; its one encode / decode call uses grow(), lens_check(), lens_upload() and counts_fetch().
@@ -24,6 +26,13 @@
 //  - every read-back brings the counts first and then only the columns some channel filled (before, only hdlc and faxfe
 //    did; adsi's "only if any count is non-zero" is the case of no column): two waits where small banks had one;
 //  - so host entries past a channel's count may hold an earlier call's data.  spangpu.h promises entries below the count only.
+//  - the tone bank: spangpu_bank_set_stream() and _sync() make the bank's device current first; a bad length in
+//    spangpu_bank_rx_var() is refused with lens_check()'s text (same code, still before anything is queued);
+//    spangpu_dtmf_import_state() writes its parameter row through the bank's stream, not with blocking copies;
+//    spangpu_banks_own_queues() returns SPANGPU_ERR_BAD_ARG for a bank listed twice, makes at most 12 streams in all and
+//    gives up with SPANGPU_ERR_HIP at the first stream that cannot be made; a records buffer too small for a call is refused
+//    before a host frame is staged (behind a bad mem kind, as ever), in spangpu_banks_rx() with the other paths' text (no
+//    bank index); a bank whose stream cannot be made reports core_create()'s text.
 // Everything else a family does differently is a parameter or stays at its call site.
 
 #pragma once
@@ -53,6 +62,9 @@ namespace spg __attribute__((visibility("hidden")))
 {
 
 constexpr int kMaxSamples = 1 << 24;        // per call: the chunk index of a wave's 16 rows stays inside 32 bits
+
+// spangpu_set_error() with a formatted message (spangpu_api.hip); returns code
+int failf(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // hipGetDeviceCount, the range check, hipSetDevice: SPANGPU_ERR_NO_DEVICE where there is no GPU, never a CPU path
 int device_ok(int device);
