@@ -235,7 +235,7 @@ SPANGPU_API long long spangpu_bank_copy_records(spangpu_bank_t *bank, void *dst_
    says the list was cut).  A separate small kernel over the records of the last launch (two stream operations). */
 SPANGPU_API int spangpu_bank_digit_events(spangpu_bank_t *bank, uint32_t *dst_device, int cap_entries);
 
-/* ---- The pipelined host-buffer path (csrc/feed_api.hip) -----------------------------------------------------------------
+/* ---- The pipelined host-buffer path (csrc/feed_api.hip, csrc/feed_ring.hpp) ---------------------------------------------
    For a caller whose frames live in host memory (what N spandsp callers hold between dtmf_rx() calls): a ring of `depth`
    slots, each a pinned host buffer the caller's receive path writes a frame into, so that tick t + 1's copy to the device
    overlaps tick t's kernel and the way back of its digits.  Per tick:

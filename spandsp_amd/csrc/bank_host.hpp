@@ -9,7 +9,9 @@
 // (shard_api.hip) sit on shard_core.hpp, which holds banks of these kinds.  The tone bank (tone_bank.hpp; tone_api, tone_rx,
 // tone_state, tone_cadence .hip) embeds BankCore for its device, channel count and stream, a VarLens, and stages host frames
 // with grow(); its two float / int state arrays, its three frame formats and its two joined streams stay its own (every core
-// call that uses c.stream comes behind its joined()).  The feeds and the primitives take SPG_TRY only: slot rings are another shape.
+// call that uses c.stream comes behind its joined()).  The primitives take SPG_TRY only.  So do the three pipelined feeds
+// (feed_api.hip) of this header: a ring of slots is another shape, and its core is theirs -- feed_ring.hpp (the ring and the tick
+// loop of the _run calls, no HIP) and FeedCore in feed_api.hip (streams, per-slot blocks and events, create, destroy, the way down).
 // The seven banks with an _rx_var entry point (tone, fsk, mct, sigtone, modem, v18, adsi) keep that call's per-channel lengths
 // in a VarLens; the last six and the HDLC receiver and FAX front-end banks (hdlc_api.hip, faxfe_api.hip) hand a call's result
 // rows to the host through CountRows, count_row_scan() and rows_fetch().

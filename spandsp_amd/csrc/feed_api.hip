@@ -1,4 +1,5 @@
-// feed_api.hip -- the pipelined host-buffer path of a tone bank (include/spangpu.h: spangpu_feed_*).
+// feed_api.hip -- the pipelined host-buffer paths: of a tone bank (include/spangpu.h: spangpu_feed_*), and further down of the
+// echo canceller and modem receiver banks (spangpu_echo_feed_*, spangpu_modem_feed_*).
 //
 // spangpu_bank_rx(.., SPANGPU_MEM_HOST, ..) is a synchronous convenience: copy the frame in, launch, and the caller then
 // asks for records.  A caller that holds its frames in host memory tick after tick -- every caller that is not itself
@@ -10,38 +11,164 @@
 // entries of spangpu_bank_digit_events().  What crosses PCIe per tick is the frame down and four bytes per digit up,
 // not the 32-bit record of every block of every channel.
 #include <hip/hip_runtime.h>
-#include <time.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "../../include/spangpu.h"
 #include "bank_host.hpp"
+#include "feed_ring.hpp"
 
-enum { kFeedMaxDepth = 8 };
+using namespace spg;
 
+// =====================================================================================================================
+// The feed core: what the three families' feeds are made of.  The ring (feed_ring.hpp), the stream the input travels down
+// on, and per slot the pinned and device input blocks with the event behind the copy down and the event that says the tick
+// is done; where the family asks for it an output pair per slot, and with an out-stream the event behind the bank's kernels
+// that the way up waits for.  A family's struct embeds FeedCore and keeps what is its own; a commit is
+//     slot = ring_next();  feed_send();  the family's launches, its way up and the record of ev_done;  ring_committed()
+// so that a commit refused or failed anywhere leaves the ring as it was, and a collect is feed_wait_oldest() and the
+// family's look at the slot.
+// =====================================================================================================================
+namespace {
+
+struct FeedSlot
+{
+    void *h_in;                 // pinned: the caller writes the tick's input here
+    void *d_in;
+    void *h_out;                // pinned: the caller reads the tick's output here
+    void *d_out;
+    hipEvent_t ev_in;           // the copy down is done
+    hipEvent_t ev_k;            // the bank's stream is done with the tick (out-stream only)
+    hipEvent_t ev_done;         // the tick is done
+};
+
+struct FeedCore
+{
+    int device;
+    FeedRing ring;
+    size_t in_bytes;            // what travels down per tick
+    size_t out_bytes;           // the output pair's size, whole 16 bytes
+    hipStream_t in_stream;
+    hipStream_t out_stream;
+    FeedSlot slot[kFeedMaxDepth];
+};
+
+// what the three create calls refuse first (rest_ok: whatever else the family checks in the same breath), and the law
+int feed_args_ok(const void *out, const void *bank, int max_samples, int depth, bool rest_ok = true)
+{
+    if (out == nullptr  ||  bank == nullptr  ||  max_samples <= 0  ||  !rest_ok  ||  !ring_depth_ok(depth))
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (1 .. 8 slots)");
+    return SPANGPU_OK;
+}
+
+int feed_law_ok(int law)
+{
+    if (law != 0  &&  law != SPANGPU_G711_ALAW  &&  law != SPANGPU_G711_ULAW)
+        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "law must be 0 (16 bit linear), SPANGPU_G711_ALAW or SPANGPU_G711_ULAW");
+    return SPANGPU_OK;
+}
+
+hipError_t feed_stream(hipStream_t *s, bool prio, int hi)
+{
+    return prio  ?  hipStreamCreateWithPriority(s, hipStreamNonBlocking, hi)  :  hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+}
+
+// *c is zeroed.  in_bytes down and out_bytes up per slot (0: no output pair), device blocks with 64 bytes to spare, pinned
+// blocks zeroed; an out-stream (and ev_k) for a family that sends its output up on a stream of its own; prio: the copy
+// streams at the device's high priority.  After a failure the family still calls feed_destroy().
+int feed_create(FeedCore *c, int device, int depth, size_t in_bytes, size_t out_bytes, bool out_stream, bool prio)
+{
+    c->device = device;
+    c->ring.depth = depth;
+    c->in_bytes = in_bytes;
+    c->out_bytes = (out_bytes + 15)/16*16;
+    int lo = 0;
+    int hi = 0;
+    bool ok = hipSetDevice(device) == hipSuccess;
+    if (ok  &&  prio)
+        (void) hipDeviceGetStreamPriorityRange(&lo, &hi);
+    ok = ok  &&  feed_stream(&c->in_stream, prio, hi) == hipSuccess  &&  (!out_stream  ||  feed_stream(&c->out_stream, prio, hi) == hipSuccess);
+    for (int k = 0;  ok  &&  k < depth;  k++)
+    {
+        FeedSlot *s = &c->slot[k];
+        ok = hipHostMalloc(&s->h_in, c->in_bytes) == hipSuccess
+             &&  hipMalloc(&s->d_in, c->in_bytes + 64) == hipSuccess
+             &&  (c->out_bytes == 0  ||  (hipHostMalloc(&s->h_out, c->out_bytes) == hipSuccess  &&  hipMalloc(&s->d_out, c->out_bytes + 64) == hipSuccess))
+             &&  hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming) == hipSuccess
+             &&  (!out_stream  ||  hipEventCreateWithFlags(&s->ev_k, hipEventDisableTiming) == hipSuccess)
+             &&  hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming) == hipSuccess;
+        if (ok)
+        {
+            memset(s->h_in, 0, c->in_bytes);
+            if (c->out_bytes)
+                memset(s->h_out, 0, c->out_bytes);
+        }
+    }
+    return ok  ?  SPANGPU_OK  :  spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of (pinned) memory for the feed");
+}
+
+// Nothing is freed under a tick: the way down, then the bank (sync_bank(), the family's), then the way up are waited for.
+template <typename SyncBank>
+void feed_destroy(FeedCore *c, SyncBank sync_bank)
+{
+    (void) hipSetDevice(c->device);
+    if (c->in_stream) (void) hipStreamSynchronize(c->in_stream);
+    sync_bank();
+    if (c->out_stream) (void) hipStreamSynchronize(c->out_stream);
+    if (c->in_stream) (void) hipStreamDestroy(c->in_stream);
+    if (c->out_stream) (void) hipStreamDestroy(c->out_stream);
+    for (int k = 0;  k < c->ring.depth;  k++)
+    {
+        FeedSlot *s = &c->slot[k];
+        if (s->h_in) (void) hipHostFree(s->h_in);
+        if (s->d_in) (void) hipFree(s->d_in);
+        if (s->h_out) (void) hipHostFree(s->h_out);
+        if (s->d_out) (void) hipFree(s->d_out);
+        if (s->ev_in) (void) hipEventDestroy(s->ev_in);
+        if (s->ev_k) (void) hipEventDestroy(s->ev_k);
+        if (s->ev_done) (void) hipEventDestroy(s->ev_done);
+    }
+}
+
+// Send the slot's input down and make the bank's stream wait for it.  *bs = bank_stream(), asked for with the feed's device
+// current.  (The slot's device blocks are free: its last tick was collected, i.e. its kernels and copies are done.)
+template <typename BankStream>
+inline int feed_send(FeedCore *c, int slot, BankStream bank_stream, hipStream_t *bs)
+{
+    FeedSlot *s = &c->slot[slot];
+    SPG_TRY(hipSetDevice(c->device));
+    *bs = bank_stream();
+    SPG_TRY(hipMemcpyAsync(s->d_in, s->h_in, c->in_bytes, hipMemcpyHostToDevice, c->in_stream));
+    SPG_TRY(hipEventRecord(s->ev_in, c->in_stream));
+    SPG_TRY(hipStreamWaitEvent(*bs, s->ev_in, 0));
+    return SPANGPU_OK;
+}
+
+// Wait for the oldest tick: *slot is its slot, now free to be committed again, or -1 when no tick is outstanding.
+inline int feed_wait_oldest(FeedCore *c, int *slot)
+{
+    if ((*slot = ring_oldest(&c->ring)) < 0)
+        return SPANGPU_OK;
+    SPG_TRY(hipSetDevice(c->device));
+    SPG_TRY(hipEventSynchronize(c->slot[*slot].ev_done));
+    ring_collected(&c->ring, *slot);
+    return SPANGPU_OK;
+}
+
+}   // namespace
+
+// ---- tone: input = the frame (slot.h_in / d_in), output pair = the digit list, which travels up on the bank's stream --------
 struct spangpu_feed_s
 {
+    FeedCore core;
     spangpu_bank_t *bank;
-    int device;
     int n_ch;
     int max_samples;
     int law;                    // 0 = 16 bit linear, SPANGPU_G711_ALAW / _ULAW = one byte per sample
-    int depth;
     int cap;                    // digit list entries per tick (no tick can make more: blocks per frame x channels)
     int quick;                  // entries that travel back with every tick; a livelier tick has the rest fetched when it is collected
     long long stride;           // samples per row of the staging buffers (rows 16-byte aligned)
-    size_t frame_bytes;
-    void *h_stage[kFeedMaxDepth];
-    void *d_frame[kFeedMaxDepth];
-    uint32_t *d_list[kFeedMaxDepth];
-    uint32_t *h_list[kFeedMaxDepth];
-    hipEvent_t ev_h2d[kFeedMaxDepth];
-    hipEvent_t ev_done[kFeedMaxDepth];
-    bool busy[kFeedMaxDepth];
-    hipStream_t copy_stream;
-    long long n_commit;
-    long long n_collect;
 };
 
 extern "C" {
@@ -50,32 +177,15 @@ int spangpu_feed_destroy(spangpu_feed_t *f)
 {
     if (f == nullptr)
         return SPANGPU_OK;
-    (void) hipSetDevice(f->device);
-    if (f->copy_stream)
-    {
-        (void) hipStreamSynchronize(f->copy_stream);
-        (void) spangpu_bank_sync(f->bank);
-        (void) hipStreamDestroy(f->copy_stream);
-    }
-    for (int k = 0;  k < f->depth;  k++)
-    {
-        if (f->h_stage[k]) (void) hipHostFree(f->h_stage[k]);
-        if (f->d_frame[k]) (void) hipFree(f->d_frame[k]);
-        if (f->d_list[k]) (void) hipFree(f->d_list[k]);
-        if (f->h_list[k]) (void) hipHostFree(f->h_list[k]);
-        if (f->ev_h2d[k]) (void) hipEventDestroy(f->ev_h2d[k]);
-        if (f->ev_done[k]) (void) hipEventDestroy(f->ev_done[k]);
-    }
+    feed_destroy(&f->core, [f] { (void) spangpu_bank_sync(f->bank); });
     free(f);
     return SPANGPU_OK;
 }
 
 int spangpu_feed_create(spangpu_feed_t **out, spangpu_bank_t *bank, int device, int max_samples, int law, int depth)
 {
-    if (out == nullptr  ||  bank == nullptr  ||  max_samples <= 0  ||  depth < 1  ||  depth > kFeedMaxDepth)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (1 .. 8 slots)");
-    if (law != 0  &&  law != SPANGPU_G711_ALAW  &&  law != SPANGPU_G711_ULAW)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "law must be 0 (16 bit linear), SPANGPU_G711_ALAW or SPANGPU_G711_ULAW");
+    if (feed_args_ok(out, bank, max_samples, depth) != SPANGPU_OK  ||  feed_law_ok(law) != SPANGPU_OK)
+        return SPANGPU_ERR_BAD_ARG;
     *out = nullptr;
     const int n_ch = spangpu_bank_channels(bank);
     if (n_ch <= 0)
@@ -91,35 +201,22 @@ int spangpu_feed_create(spangpu_feed_t **out, spangpu_bank_t *bank, int device, 
     if (f == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory");
     f->bank = bank;
-    f->device = device;
     f->n_ch = n_ch;
     f->max_samples = max_samples;
     f->law = law;
-    f->depth = depth;
     const int bps = law  ?  1  :  2;
     f->stride = ((long long) max_samples*bps + 15)/16*16/bps;
-    f->frame_bytes = (size_t) f->stride*bps*n_ch;
     // a block is at least 64 samples long on every detector kind: blocks per frame (+1 for one in progress)
     f->cap = n_ch*(max_samples/64 + 2);
     f->quick = (n_ch/8 > 4096)  ?  n_ch/8  :  4096;
     if (f->quick > f->cap)
         f->quick = f->cap;
-    bool ok = (hipSetDevice(device) == hipSuccess)  &&  (hipStreamCreateWithFlags(&f->copy_stream, hipStreamNonBlocking) == hipSuccess);
-    for (int k = 0;  ok  &&  k < depth;  k++)
-    {
-        ok = hipHostMalloc(&f->h_stage[k], f->frame_bytes) == hipSuccess
-             &&  hipMalloc(&f->d_frame[k], f->frame_bytes + 64) == hipSuccess
-             &&  hipMalloc((void **) &f->d_list[k], (size_t) (1 + f->cap)*sizeof(uint32_t)) == hipSuccess
-             &&  hipHostMalloc((void **) &f->h_list[k], (size_t) (1 + f->cap)*sizeof(uint32_t)) == hipSuccess
-             &&  hipEventCreateWithFlags(&f->ev_h2d[k], hipEventDisableTiming) == hipSuccess
-             &&  hipEventCreateWithFlags(&f->ev_done[k], hipEventDisableTiming) == hipSuccess;
-        if (ok)
-            memset(f->h_stage[k], 0, f->frame_bytes);
-    }
-    if (!ok)
+    // a plain copy stream, and no out-stream: the list's quick part follows the kernel on the bank's stream
+    const int rc = feed_create(&f->core, device, depth, (size_t) f->stride*bps*n_ch, (size_t) (1 + f->cap)*sizeof(uint32_t), false, false);
+    if (rc != SPANGPU_OK)
     {
         spangpu_feed_destroy(f);
-        return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of (pinned) memory for the feed");
+        return rc;
     }
     *out = f;
     return SPANGPU_OK;
@@ -137,13 +234,8 @@ void *spangpu_feed_acquire(spangpu_feed_t *f)
 {
     if (f == nullptr)
         return nullptr;
-    const int slot = (int) (f->n_commit % f->depth);
-    if (f->busy[slot])
-    {
-        spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-        return nullptr;
-    }
-    return f->h_stage[slot];
+    const int slot = ring_next(&f->core.ring);
+    return (slot < 0)  ?  nullptr  :  f->core.slot[slot].h_in;
 }
 
 // Queue the tick whose frame the caller has written into the acquired buffer.  Returns at once.
@@ -151,28 +243,25 @@ int spangpu_feed_commit(spangpu_feed_t *f, int samples)
 {
     if (f == nullptr  ||  samples <= 0  ||  samples > f->max_samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int slot = (int) (f->n_commit % f->depth);
-    if (f->busy[slot])
-        return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    SPG_TRY(hipSetDevice(f->device));
-    hipStream_t bs = (hipStream_t) spangpu_bank_get_stream(f->bank);
-    // (the slot's device buffers are free: its last tick was collected, i.e. its kernel and copies are done)
-    SPG_TRY(hipMemcpyAsync(f->d_frame[slot], f->h_stage[slot], f->frame_bytes, hipMemcpyHostToDevice, f->copy_stream));
-    SPG_TRY(hipEventRecord(f->ev_h2d[slot], f->copy_stream));
-    SPG_TRY(hipStreamWaitEvent(bs, f->ev_h2d[slot], 0));
-    int rc;
-    if (f->law)
-        rc = spangpu_bank_rx_g711(f->bank, (const uint8_t *) f->d_frame[slot], SPANGPU_MEM_DEVICE, f->law, samples, f->stride);
-    else
-        rc = spangpu_bank_rx(f->bank, (const int16_t *) f->d_frame[slot], SPANGPU_MEM_DEVICE, SPANGPU_LAYOUT_CHANNEL_MAJOR, samples, f->stride);
+    const int slot = ring_next(&f->core.ring);
+    if (slot < 0)
+        return slot;
+    FeedSlot *s = &f->core.slot[slot];
+    hipStream_t bs;
+    int rc = feed_send(&f->core, slot, [f] { return (hipStream_t) spangpu_bank_get_stream(f->bank); }, &bs);
     if (rc < 0)
         return rc;
-    if ((rc = spangpu_bank_digit_events(f->bank, f->d_list[slot], f->cap)) < 0)
+    if (f->law)
+        rc = spangpu_bank_rx_g711(f->bank, (const uint8_t *) s->d_in, SPANGPU_MEM_DEVICE, f->law, samples, f->stride);
+    else
+        rc = spangpu_bank_rx(f->bank, (const int16_t *) s->d_in, SPANGPU_MEM_DEVICE, SPANGPU_LAYOUT_CHANNEL_MAJOR, samples, f->stride);
+    if (rc < 0)
         return rc;
-    SPG_TRY(hipMemcpyAsync(f->h_list[slot], f->d_list[slot], (size_t) (1 + f->quick)*sizeof(uint32_t), hipMemcpyDeviceToHost, bs));
-    SPG_TRY(hipEventRecord(f->ev_done[slot], bs));
-    f->busy[slot] = true;
-    f->n_commit++;
+    if ((rc = spangpu_bank_digit_events(f->bank, (uint32_t *) s->d_out, f->cap)) < 0)
+        return rc;
+    SPG_TRY(hipMemcpyAsync(s->h_out, s->d_out, (size_t) (1 + f->quick)*sizeof(uint32_t), hipMemcpyDeviceToHost, bs));
+    SPG_TRY(hipEventRecord(s->ev_done, bs));
+    ring_committed(&f->core.ring, slot);
     return SPANGPU_OK;
 }
 
@@ -184,69 +273,47 @@ int spangpu_feed_collect(spangpu_feed_t *f, const uint32_t **entries)
     if (f == nullptr  ||  entries == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     *entries = nullptr;
-    if (f->n_collect >= f->n_commit)
-        return 0;
-    const int slot = (int) (f->n_collect % f->depth);
-    SPG_TRY(hipSetDevice(f->device));
-    SPG_TRY(hipEventSynchronize(f->ev_done[slot]));
-    f->busy[slot] = false;
-    f->n_collect++;
-    const uint32_t n = f->h_list[slot][0];
+    int slot;
+    const int rc = feed_wait_oldest(&f->core, &slot);
+    if (rc < 0  ||  slot < 0)
+        return rc;
+    uint32_t *h_list = (uint32_t *) f->core.slot[slot].h_out;
+    const uint32_t n = h_list[0];
     if (n > (uint32_t) f->cap)
         return spangpu_set_error(SPANGPU_ERR_STATE, "digit list overflow");
     if (n > (uint32_t) f->quick)
     {
         // more digits than travel with every tick (an eighth of the channels delivering one in the same 20 ms): the rest now
-        SPG_TRY(hipMemcpy(f->h_list[slot] + 1 + f->quick, f->d_list[slot] + 1 + f->quick, (size_t) (n - (uint32_t) f->quick)*sizeof(uint32_t),
-                           hipMemcpyDeviceToHost));
+        SPG_TRY(hipMemcpy(h_list + 1 + f->quick, (const uint32_t *) f->core.slot[slot].d_out + 1 + f->quick,
+                          (size_t) (n - (uint32_t) f->quick)*sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
-    *entries = f->h_list[slot] + 1;
+    *entries = h_list + 1;
     return (int) n;
 }
 
 int spangpu_feed_outstanding(const spangpu_feed_t *f)
 {
-    return f  ?  (int) (f->n_commit - f->n_collect)  :  SPANGPU_ERR_BAD_ARG;
+    return f  ?  ring_outstanding(&f->core.ring)  :  SPANGPU_ERR_BAD_ARG;
 }
 
-// A caller's tick loop in C, for measurements (bench.py's `e2e`): `ticks` times acquire (the slots keep the frames they
-// hold: the caller's receive path is not part of this path) / commit / collect with `lag` ticks between a commit and the
-// collect of its digits (1 .. depth - 1), then the rest collected.  *elapsed_ms = wall time of the whole loop.
+// A caller's tick loop in C, for measurements (bench.py's `e2e`): ring_run() over the frames the slots hold (the caller's
+// receive path is not part of this path), with `lag` ticks between a commit and the collect of its digits (1 .. depth - 1).
+// *elapsed_ms = wall time of the whole loop, *digits = the entries collected.
 int spangpu_feed_run(spangpu_feed_t *f, int samples, int ticks, int lag, double *elapsed_ms, long long *digits)
 {
-    if (f == nullptr  ||  ticks <= 0  ||  lag < 1  ||  lag >= f->depth  ||  spangpu_feed_outstanding(f) != 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (lag in 1 .. depth - 1, nothing outstanding)");
-    struct timespec t0, t1;
     long long seen = 0;
     const uint32_t *entries;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (int i = 0;  i < ticks;  i++)
-    {
-        if (spangpu_feed_acquire(f) == nullptr)
-            return SPANGPU_ERR_STATE;
-        int rc = spangpu_feed_commit(f, samples);
-        if (rc < 0)
-            return rc;
-        if (spangpu_feed_outstanding(f) > lag)
-        {
-            if ((rc = spangpu_feed_collect(f, &entries)) < 0)
-                return rc;
-            seen += rc;
-        }
-    }
-    while (spangpu_feed_outstanding(f) > 0)
-    {
-        const int rc = spangpu_feed_collect(f, &entries);
-        if (rc < 0)
-            return rc;
-        seen += rc;
-    }
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (elapsed_ms)
-        *elapsed_ms = (t1.tv_sec - t0.tv_sec)*1e3 + (t1.tv_nsec - t0.tv_nsec)*1e-6;
-    if (digits)
+    const int rc = ring_run(f  ?  &f->core.ring  :  nullptr, ticks, lag, elapsed_ms,
+                            [=] { return spangpu_feed_commit(f, samples); },
+                            [&]
+                            {
+                                const int n = spangpu_feed_collect(f, &entries);
+                                seen += (n > 0)  ?  n  :  0;
+                                return n;
+                            });
+    if (rc == SPANGPU_OK  &&  digits)
         *digits = seen;
-    return SPANGPU_OK;
+    return rc;
 }
 
 }   // extern "C"
@@ -389,125 +456,100 @@ __global__ void copy_out_kernel(feed_u32x4 *dst, const feed_u32x4 *src, size_t n
         __builtin_nontemporal_store(src[i], &dst[i]);
 }
 
+// Both families' handles are this struct (include/spangpu.h), so a feed carries its family, and every entry point refuses
+// the other family's feed like a null one.
+enum { kEchoFeed = 1, kModemFeed = 2 };
+
 struct spangpu_xfeed_s
 {
-    int what;                   // 1 echo, 2 modem
+    FeedCore core;
+    int what;                   // kEchoFeed / kModemFeed: which of the two below
+    union
+    {
+        spangpu_echo_t *echo;
+        spangpu_modem_t *modem;
+    };
     int d2h_kernel;             // the way up by copy_out_kernel instead of hipMemcpyAsync
     void *h_out_dev[kFeedMaxDepth];
-    spangpu_echo_t *echo;
-    spangpu_modem_t *modem;
-    int device;
     int n_ch;
     int max_samples;
     int law;
-    int depth;
     long long stride;           // samples per row (rows 16-byte aligned in either format)
-    size_t in_bytes;            // what travels down per tick
-    size_t out_bytes;           // what travels up per tick
     int wpc;                    // modem: packed words per channel
     int status_cap;             // modem: status list entries
     int use_hpf_tx;
-    void *h_in[kFeedMaxDepth];
-    void *d_in[kFeedMaxDepth];
-    void *h_out[kFeedMaxDepth];
-    void *d_out[kFeedMaxDepth];
     int16_t *d_pcm_in;          // echo, G.711: the decoded tx and rx rows (one buffer: a tick's kernel has read it before the next decode, both on the bank's stream)
     int16_t *d_pcm_out;         // echo, G.711: the clean rows before encoding
-    hipEvent_t ev_in[kFeedMaxDepth];
-    hipEvent_t ev_k[kFeedMaxDepth];
-    hipEvent_t ev_done[kFeedMaxDepth];
-    bool busy[kFeedMaxDepth];
     int samples_of[kFeedMaxDepth];
-    hipStream_t in_stream;
-    hipStream_t out_stream;
-    long long n_commit;
-    long long n_collect;
 };
 
 typedef struct spangpu_xfeed_s spangpu_xfeed_t;
+
+static inline bool is_feed_of(const spangpu_xfeed_t *f, int what)
+{
+    return f != nullptr  &&  f->what == what;
+}
 
 static int xfeed_destroy(spangpu_xfeed_t *f)
 {
     if (f == nullptr)
         return SPANGPU_OK;
-    (void) hipSetDevice(f->device);
-    if (f->in_stream) (void) hipStreamSynchronize(f->in_stream);
-    if (f->what == 1  &&  f->echo) (void) spangpu_echo_sync(f->echo);
-    if (f->what == 2  &&  f->modem) (void) spangpu_modem_sync(f->modem);
-    if (f->out_stream) (void) hipStreamSynchronize(f->out_stream);
-    if (f->in_stream) (void) hipStreamDestroy(f->in_stream);
-    if (f->out_stream) (void) hipStreamDestroy(f->out_stream);
-    for (int k = 0;  k < f->depth;  k++)
-    {
-        if (f->h_in[k]) (void) hipHostFree(f->h_in[k]);
-        if (f->d_in[k]) (void) hipFree(f->d_in[k]);
-        if (f->h_out[k]) (void) hipHostFree(f->h_out[k]);
-        if (f->d_out[k]) (void) hipFree(f->d_out[k]);
-        if (f->ev_in[k]) (void) hipEventDestroy(f->ev_in[k]);
-        if (f->ev_k[k]) (void) hipEventDestroy(f->ev_k[k]);
-        if (f->ev_done[k]) (void) hipEventDestroy(f->ev_done[k]);
-    }
+    feed_destroy(&f->core, [f] { (void) ((f->what == kEchoFeed)  ?  spangpu_echo_sync(f->echo)  :  spangpu_modem_sync(f->modem)); });
     if (f->d_pcm_in) (void) hipFree(f->d_pcm_in);
     if (f->d_pcm_out) (void) hipFree(f->d_pcm_out);
     free(f);
     return SPANGPU_OK;
 }
 
-static int xfeed_copy_out(spangpu_xfeed_t *f, int slot)
-{
-    if (f->d2h_kernel)
-    {
-        const size_t n16 = (f->out_bytes + 15)/16;
-        hipLaunchKernelGGL(copy_out_kernel, dim3(256), dim3(256), 0, f->out_stream, (feed_u32x4 *) f->h_out_dev[slot], (const feed_u32x4 *) f->d_out[slot], n16);
-        SPG_TRY(hipGetLastError());
-        return SPANGPU_OK;
-    }
-    SPG_TRY(hipMemcpyAsync(f->h_out[slot], f->d_out[slot], f->out_bytes, hipMemcpyDeviceToHost, f->out_stream));
-    return SPANGPU_OK;
-}
-
-static int xfeed_alloc(spangpu_xfeed_t *f)
+static int xfeed_alloc(spangpu_xfeed_t *f, int device, int depth, size_t in_bytes, size_t out_bytes)
 {
     // Measured (profiles/r4_feed_ab.log, 131 072 echo lines / 16 384 V.29 receivers per tick): the echo feed's 21 - 42 MB way
     // up is fastest as a DMA copy on a stream of its own priority (u-law 0.82 ms a tick against 1.08; int16 1.66 against 1.73),
     // the modem feed's 0.6 MB as a kernel's stores on a plain stream (0.20 ms against 0.35 - 0.49).
     const char *how = getenv("SPANGPU_FEED_D2H");           // "dma" / "kernel" for A-B runs
-    f->d2h_kernel = (how == nullptr)  ?  (f->what == 2)  :  (strcmp(how, "kernel") == 0);
-    f->out_bytes = (f->out_bytes + 15)/16*16;
+    f->d2h_kernel = (how == nullptr)  ?  (f->what == kModemFeed)  :  (strcmp(how, "kernel") == 0);
     // The copy streams get a priority of their own: the runtime deals streams of one priority round over a handful of
     // hardware queues (GPU_MAX_HW_QUEUES, 4 by default), and a copy stream that lands on the bank stream's queue runs in
     // turn with its kernels instead of beside them (measured: the way up of tick t then sits between the kernels of t and t + 1).
-    int lo = 0;
-    int hi = 0;
-    (void) hipDeviceGetStreamPriorityRange(&lo, &hi);
     const char *pr = getenv("SPANGPU_FEED_PRIORITY");       // "0": plain streams (A-B runs)
-    const bool prio = (pr == nullptr)  ?  (f->what == 1)  :  (strcmp(pr, "0") != 0);
-    bool ok = (hipSetDevice(f->device) == hipSuccess)
-              &&  ((prio  ?  hipStreamCreateWithPriority(&f->in_stream, hipStreamNonBlocking, hi)  :  hipStreamCreateWithFlags(&f->in_stream, hipStreamNonBlocking)) == hipSuccess)
-              &&  ((prio  ?  hipStreamCreateWithPriority(&f->out_stream, hipStreamNonBlocking, hi)  :  hipStreamCreateWithFlags(&f->out_stream, hipStreamNonBlocking)) == hipSuccess);
-    for (int k = 0;  ok  &&  k < f->depth;  k++)
+    const bool prio = (pr == nullptr)  ?  (f->what == kEchoFeed)  :  (strcmp(pr, "0") != 0);
+    const int rc = feed_create(&f->core, device, depth, in_bytes, out_bytes, true, prio);
+    if (rc != SPANGPU_OK)
+        return rc;
+    for (int k = 0;  f->d2h_kernel  &&  k < depth;  k++)
     {
-        ok = hipHostMalloc(&f->h_in[k], f->in_bytes) == hipSuccess
-             &&  hipMalloc(&f->d_in[k], f->in_bytes + 64) == hipSuccess
-             &&  hipHostMalloc(&f->h_out[k], f->out_bytes) == hipSuccess
-             &&  hipMalloc(&f->d_out[k], f->out_bytes + 64) == hipSuccess
-             &&  hipEventCreateWithFlags(&f->ev_in[k], hipEventDisableTiming) == hipSuccess
-             &&  hipEventCreateWithFlags(&f->ev_k[k], hipEventDisableTiming) == hipSuccess
-             &&  hipEventCreateWithFlags(&f->ev_done[k], hipEventDisableTiming) == hipSuccess;
-        if (ok)
-        {
-            memset(f->h_in[k], 0, f->in_bytes);
-            memset(f->h_out[k], 0, f->out_bytes);
-            if (f->d2h_kernel  &&  hipHostGetDevicePointer(&f->h_out_dev[k], f->h_out[k], 0) != hipSuccess)
-                f->d2h_kernel = 0;
-        }
+        if (hipHostGetDevicePointer(&f->h_out_dev[k], f->core.slot[k].h_out, 0) != hipSuccess)
+            f->d2h_kernel = 0;
     }
-    if (ok  &&  f->what == 1  &&  f->law)
+    if (f->what == kEchoFeed  &&  f->law)
     {
         const size_t rows = (size_t) f->stride*f->n_ch*sizeof(int16_t);
-        ok = hipMalloc((void **) &f->d_pcm_in, 2*rows + 64) == hipSuccess  &&  hipMalloc((void **) &f->d_pcm_out, rows + 64) == hipSuccess;
+        if (hipMalloc((void **) &f->d_pcm_in, 2*rows + 64) != hipSuccess  ||  hipMalloc((void **) &f->d_pcm_out, rows + 64) != hipSuccess)
+            return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of (pinned) memory for the feed");
     }
-    return ok  ?  SPANGPU_OK  :  spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of (pinned) memory for the feed");
+    return SPANGPU_OK;
+}
+
+// The way up, behind what the family has put on the bank's stream: the out-stream waits for it, takes the slot's output to
+// its pinned block -- by DMA or by copy_out_kernel -- and says when the tick is done.  Then the tick counts as queued.
+static int xfeed_send_up(spangpu_xfeed_t *f, int slot, hipStream_t bs, int samples)
+{
+    FeedCore *c = &f->core;
+    FeedSlot *s = &c->slot[slot];
+    SPG_TRY(hipEventRecord(s->ev_k, bs));
+    SPG_TRY(hipStreamWaitEvent(c->out_stream, s->ev_k, 0));
+    if (f->d2h_kernel)
+    {
+        const size_t n16 = (c->out_bytes + 15)/16;
+        hipLaunchKernelGGL(copy_out_kernel, dim3(256), dim3(256), 0, c->out_stream, (feed_u32x4 *) f->h_out_dev[slot], (const feed_u32x4 *) s->d_out, n16);
+        SPG_TRY(hipGetLastError());
+    }
+    else
+        SPG_TRY(hipMemcpyAsync(s->h_out, s->d_out, c->out_bytes, hipMemcpyDeviceToHost, c->out_stream));
+    SPG_TRY(hipEventRecord(s->ev_done, c->out_stream));
+    f->samples_of[slot] = samples;
+    ring_committed(&c->ring, slot);
+    return SPANGPU_OK;
 }
 
 extern "C" {
@@ -515,177 +557,130 @@ extern "C" {
 // ---- echo ------------------------------------------------------------------------------------------------------------------
 int spangpu_echo_feed_create(spangpu_echo_feed_t **out, spangpu_echo_t *ec, int max_samples, int law, int depth, int use_hpf_tx)
 {
-    if (out == nullptr  ||  ec == nullptr  ||  max_samples <= 0  ||  depth < 1  ||  depth > kFeedMaxDepth)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (1 .. 8 slots)");
-    if (law != 0  &&  law != SPANGPU_G711_ALAW  &&  law != SPANGPU_G711_ULAW)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "law must be 0 (16 bit linear), SPANGPU_G711_ALAW or SPANGPU_G711_ULAW");
+    if (feed_args_ok(out, ec, max_samples, depth) != SPANGPU_OK  ||  feed_law_ok(law) != SPANGPU_OK)
+        return SPANGPU_ERR_BAD_ARG;
     *out = nullptr;
     spangpu_xfeed_t *f = (spangpu_xfeed_t *) calloc(1, sizeof(*f));
     if (f == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory");
-    f->what = 1;
+    f->what = kEchoFeed;
     f->echo = ec;
-    f->device = spangpu_echo_device(ec);
     f->n_ch = spangpu_echo_channels(ec);
     f->max_samples = max_samples;
     f->law = law;
-    f->depth = depth;
     f->use_hpf_tx = use_hpf_tx;
     const int bps = law  ?  1  :  2;
     f->stride = ((long long) max_samples + 15)/16*16;            // rows of whole 16-sample groups in either format
-    f->in_bytes = (size_t) 2*f->stride*bps*f->n_ch;
-    f->out_bytes = (size_t) f->stride*bps*f->n_ch;
-    const int rc = xfeed_alloc(f);
+    const size_t rows_bytes = (size_t) f->stride*bps*f->n_ch;
+    const int rc = xfeed_alloc(f, spangpu_echo_device(ec), depth, 2*rows_bytes, rows_bytes);
     if (rc != SPANGPU_OK)
     {
         xfeed_destroy(f);
         return rc;
     }
-    *out = (spangpu_echo_feed_t *) f;
+    *out = f;
     return SPANGPU_OK;
 }
 
-int spangpu_echo_feed_destroy(spangpu_echo_feed_t *feed) { return xfeed_destroy((spangpu_xfeed_t *) feed); }
+int spangpu_echo_feed_destroy(spangpu_echo_feed_t *f) { return xfeed_destroy(f); }
 
-long long spangpu_echo_feed_stride(const spangpu_echo_feed_t *feed)
+long long spangpu_echo_feed_stride(const spangpu_echo_feed_t *f)
 {
-    return feed  ?  ((const spangpu_xfeed_t *) feed)->stride  :  (long long) SPANGPU_ERR_BAD_ARG;
+    return f  ?  f->stride  :  (long long) SPANGPU_ERR_BAD_ARG;
 }
 
 // The pinned buffers of the next tick: *tx and *rx for the caller to write (channel c's samples at c*stride samples -- int16,
 // or bytes with a G.711 law); NULL / SPANGPU_ERR_STATE while every slot holds a tick that has not been collected.
-int spangpu_echo_feed_acquire(spangpu_echo_feed_t *feed, void **tx, void **rx)
+int spangpu_echo_feed_acquire(spangpu_echo_feed_t *f, void **tx, void **rx)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  f->what != 1  ||  tx == nullptr  ||  rx == nullptr)
+    if (!is_feed_of(f, kEchoFeed)  ||  tx == nullptr  ||  rx == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int slot = (int) (f->n_commit % f->depth);
-    if (f->busy[slot])
-        return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    *tx = f->h_in[slot];
-    *rx = (char *) f->h_in[slot] + f->in_bytes/2;
+    const int slot = ring_next(&f->core.ring);
+    if (slot < 0)
+        return slot;
+    *tx = f->core.slot[slot].h_in;
+    *rx = (char *) f->core.slot[slot].h_in + f->core.in_bytes/2;
     return SPANGPU_OK;
 }
 
-int spangpu_echo_feed_commit(spangpu_echo_feed_t *feed, int samples)
+int spangpu_echo_feed_commit(spangpu_echo_feed_t *f, int samples)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  f->what != 1  ||  samples <= 0  ||  samples > f->max_samples)
+    if (!is_feed_of(f, kEchoFeed)  ||  samples <= 0  ||  samples > f->max_samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int slot = (int) (f->n_commit % f->depth);
-    if (f->busy[slot])
-        return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    SPG_TRY(hipSetDevice(f->device));
-    hipStream_t bs = (hipStream_t) spangpu_echo_get_stream(f->echo);
-    SPG_TRY(hipMemcpyAsync(f->d_in[slot], f->h_in[slot], f->in_bytes, hipMemcpyHostToDevice, f->in_stream));
-    SPG_TRY(hipEventRecord(f->ev_in[slot], f->in_stream));
-    SPG_TRY(hipStreamWaitEvent(bs, f->ev_in[slot], 0));
+    const int slot = ring_next(&f->core.ring);
+    if (slot < 0)
+        return slot;
+    FeedSlot *s = &f->core.slot[slot];
+    hipStream_t bs;
+    int rc = feed_send(&f->core, slot, [f] { return (hipStream_t) spangpu_echo_get_stream(f->echo); }, &bs);
+    if (rc < 0)
+        return rc;
     const size_t rows = (size_t) f->stride*f->n_ch;
-    int rc;
     if (f->law)
     {
         const long long n16 = (long long) (2*rows/16);
-        hipLaunchKernelGGL(g711_to_linear_kernel, dim3((unsigned) ((n16 + 255)/256)), dim3(256), 0, bs, (const uint8_t *) f->d_in[slot], f->d_pcm_in, n16, f->law);
+        hipLaunchKernelGGL(g711_to_linear_kernel, dim3((unsigned) ((n16 + 255)/256)), dim3(256), 0, bs, (const uint8_t *) s->d_in, f->d_pcm_in, n16, f->law);
         SPG_TRY(hipGetLastError());
         rc = spangpu_echo_update(f->echo, f->d_pcm_in, f->d_pcm_in + rows, f->d_pcm_out, SPANGPU_MEM_DEVICE, samples, f->stride, f->use_hpf_tx);
         if (rc < 0)
             return rc;
         const long long m16 = (long long) (rows/16);
-        hipLaunchKernelGGL(linear_to_g711_kernel, dim3((unsigned) ((m16 + 255)/256)), dim3(256), 0, bs, (const int16_t *) f->d_pcm_out, (uint8_t *) f->d_out[slot], m16, f->law);
+        hipLaunchKernelGGL(linear_to_g711_kernel, dim3((unsigned) ((m16 + 255)/256)), dim3(256), 0, bs, (const int16_t *) f->d_pcm_out, (uint8_t *) s->d_out, m16, f->law);
         SPG_TRY(hipGetLastError());
     }
     else
     {
-        rc = spangpu_echo_update(f->echo, (const int16_t *) f->d_in[slot], (const int16_t *) f->d_in[slot] + rows, (int16_t *) f->d_out[slot],
+        rc = spangpu_echo_update(f->echo, (const int16_t *) s->d_in, (const int16_t *) s->d_in + rows, (int16_t *) s->d_out,
                                  SPANGPU_MEM_DEVICE, samples, f->stride, f->use_hpf_tx);
         if (rc < 0)
             return rc;
     }
-    SPG_TRY(hipEventRecord(f->ev_k[slot], bs));
-    SPG_TRY(hipStreamWaitEvent(f->out_stream, f->ev_k[slot], 0));
-    if ((rc = xfeed_copy_out(f, slot)) < 0)
-        return rc;
-    SPG_TRY(hipEventRecord(f->ev_done[slot], f->out_stream));
-    f->busy[slot] = true;
-    f->samples_of[slot] = samples;
-    f->n_commit++;
-    return SPANGPU_OK;
+    return xfeed_send_up(f, slot, bs, samples);
 }
 
 // The clean rows of the oldest tick not yet collected (waits for it): *clean is good until the slot is committed again.
 // Returns the tick's samples per channel, 0 with *clean = NULL when no tick is outstanding.
-int spangpu_echo_feed_collect(spangpu_echo_feed_t *feed, const void **clean)
+int spangpu_echo_feed_collect(spangpu_echo_feed_t *f, const void **clean)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  f->what != 1  ||  clean == nullptr)
+    if (!is_feed_of(f, kEchoFeed)  ||  clean == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     *clean = nullptr;
-    if (f->n_collect >= f->n_commit)
-        return 0;
-    const int slot = (int) (f->n_collect % f->depth);
-    SPG_TRY(hipSetDevice(f->device));
-    SPG_TRY(hipEventSynchronize(f->ev_done[slot]));
-    f->busy[slot] = false;
-    f->n_collect++;
-    *clean = f->h_out[slot];
+    int slot;
+    const int rc = feed_wait_oldest(&f->core, &slot);
+    if (rc < 0  ||  slot < 0)
+        return rc;
+    *clean = f->core.slot[slot].h_out;
     return f->samples_of[slot];
 }
 
-int spangpu_echo_feed_outstanding(const spangpu_echo_feed_t *feed)
+int spangpu_echo_feed_outstanding(const spangpu_echo_feed_t *f)
 {
-    const spangpu_xfeed_t *f = (const spangpu_xfeed_t *) feed;
-    return f  ?  (int) (f->n_commit - f->n_collect)  :  SPANGPU_ERR_BAD_ARG;
+    return f  ?  ring_outstanding(&f->core.ring)  :  SPANGPU_ERR_BAD_ARG;
 }
 
-// A caller's tick loop in C, for measurements: `ticks` x { acquire (the slots keep what they hold), commit, collect with
-// `lag` ticks between a commit and the collect of its clean rows }, then the rest collected.
-int spangpu_echo_feed_run(spangpu_echo_feed_t *feed, int samples, int ticks, int lag, double *elapsed_ms)
+// A caller's tick loop in C, for measurements: ring_run() over what the slots hold, with `lag` ticks between a commit and the
+// collect of its clean rows.
+int spangpu_echo_feed_run(spangpu_echo_feed_t *f, int samples, int ticks, int lag, double *elapsed_ms)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  ticks <= 0  ||  lag < 1  ||  lag >= f->depth  ||  spangpu_echo_feed_outstanding(feed) != 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (lag in 1 .. depth - 1, nothing outstanding)");
-    struct timespec t0, t1;
     const void *clean;
-    void *tx;
-    void *rx;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (int i = 0;  i < ticks;  i++)
-    {
-        int rc = spangpu_echo_feed_acquire(feed, &tx, &rx);
-        if (rc < 0)
-            return rc;
-        if ((rc = spangpu_echo_feed_commit(feed, samples)) < 0)
-            return rc;
-        if (spangpu_echo_feed_outstanding(feed) > lag  &&  (rc = spangpu_echo_feed_collect(feed, &clean)) < 0)
-            return rc;
-    }
-    while (spangpu_echo_feed_outstanding(feed) > 0)
-    {
-        const int rc = spangpu_echo_feed_collect(feed, &clean);
-        if (rc < 0)
-            return rc;
-    }
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (elapsed_ms)
-        *elapsed_ms = (t1.tv_sec - t0.tv_sec)*1e3 + (t1.tv_nsec - t0.tv_nsec)*1e-6;
-    return SPANGPU_OK;
+    return ring_run(f  ?  &f->core.ring  :  nullptr, ticks, lag, elapsed_ms,
+                    [=] { return spangpu_echo_feed_commit(f, samples); },
+                    [&] { return spangpu_echo_feed_collect(f, &clean); });
 }
 
 // ---- modem receivers ---------------------------------------------------------------------------------------------------------
 int spangpu_modem_feed_create(spangpu_modem_feed_t **out, spangpu_modem_t *modem, int max_samples, int max_bit_rate, int depth)
 {
-    if (out == nullptr  ||  modem == nullptr  ||  max_samples <= 0  ||  max_bit_rate <= 0  ||  depth < 1  ||  depth > kFeedMaxDepth)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (1 .. 8 slots)");
+    if (feed_args_ok(out, modem, max_samples, depth, max_bit_rate > 0) != SPANGPU_OK)
+        return SPANGPU_ERR_BAD_ARG;
     *out = nullptr;
     spangpu_xfeed_t *f = (spangpu_xfeed_t *) calloc(1, sizeof(*f));
     if (f == nullptr)
         return spangpu_set_error(SPANGPU_ERR_NO_MEMORY, "out of memory");
-    f->what = 2;
+    f->what = kModemFeed;
     f->modem = modem;
-    f->device = spangpu_modem_device(modem);
     f->n_ch = spangpu_modem_channels(modem);
     f->max_samples = max_samples;
-    f->depth = depth;
     f->stride = ((long long) max_samples + 7)/8*8;
     f->wpc = spangpu_modem_packed_words(max_bit_rate, max_samples);
     // What a tick can produce: a receiver reports at most a carrier drop and a new carrier with its training in progress in
@@ -696,142 +691,104 @@ int spangpu_modem_feed_create(spangpu_modem_feed_t **out, spangpu_modem_t *modem
     const long long per_channel = 2 + (max_samples + 159)/160;
     const long long cap = (long long) f->n_ch*per_channel;
     f->status_cap = (int) ((cap > 4096)  ?  ((cap < 0x3FFFFFFF)  ?  cap  :  0x3FFFFFFF)  :  4096);
-    f->in_bytes = (size_t) f->stride*sizeof(int16_t)*f->n_ch;
-    f->out_bytes = ((size_t) f->n_ch*f->wpc + 1 + 2*(size_t) f->status_cap)*sizeof(uint32_t);
-    const int rc = xfeed_alloc(f);
+    const int rc = xfeed_alloc(f, spangpu_modem_device(modem), depth, (size_t) f->stride*sizeof(int16_t)*f->n_ch,
+                               ((size_t) f->n_ch*f->wpc + 1 + 2*(size_t) f->status_cap)*sizeof(uint32_t));
     if (rc != SPANGPU_OK)
     {
         xfeed_destroy(f);
         return rc;
     }
-    *out = (spangpu_modem_feed_t *) f;
+    *out = f;
     return SPANGPU_OK;
 }
 
-int spangpu_modem_feed_destroy(spangpu_modem_feed_t *feed) { return xfeed_destroy((spangpu_xfeed_t *) feed); }
+int spangpu_modem_feed_destroy(spangpu_modem_feed_t *f) { return xfeed_destroy(f); }
 
-long long spangpu_modem_feed_stride(const spangpu_modem_feed_t *feed)
+long long spangpu_modem_feed_stride(const spangpu_modem_feed_t *f)
 {
-    return feed  ?  ((const spangpu_xfeed_t *) feed)->stride  :  (long long) SPANGPU_ERR_BAD_ARG;
+    return f  ?  f->stride  :  (long long) SPANGPU_ERR_BAD_ARG;
 }
 
-int spangpu_modem_feed_words_per_channel(const spangpu_modem_feed_t *feed)
+int spangpu_modem_feed_words_per_channel(const spangpu_modem_feed_t *f)
 {
-    return feed  ?  ((const spangpu_xfeed_t *) feed)->wpc  :  SPANGPU_ERR_BAD_ARG;
+    return f  ?  f->wpc  :  SPANGPU_ERR_BAD_ARG;
 }
 
-int spangpu_modem_feed_status_cap(const spangpu_modem_feed_t *feed)
+int spangpu_modem_feed_status_cap(const spangpu_modem_feed_t *f)
 {
-    return feed  ?  ((const spangpu_xfeed_t *) feed)->status_cap  :  SPANGPU_ERR_BAD_ARG;
+    return f  ?  f->status_cap  :  SPANGPU_ERR_BAD_ARG;
 }
 
-void *spangpu_modem_feed_acquire(spangpu_modem_feed_t *feed)
+void *spangpu_modem_feed_acquire(spangpu_modem_feed_t *f)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  f->what != 2)
+    if (!is_feed_of(f, kModemFeed))
         return nullptr;
-    const int slot = (int) (f->n_commit % f->depth);
-    if (f->busy[slot])
-    {
-        spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-        return nullptr;
-    }
-    return f->h_in[slot];
+    const int slot = ring_next(&f->core.ring);
+    return (slot < 0)  ?  nullptr  :  f->core.slot[slot].h_in;
 }
 
-int spangpu_modem_feed_commit(spangpu_modem_feed_t *feed, int samples)
+int spangpu_modem_feed_commit(spangpu_modem_feed_t *f, int samples)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  f->what != 2  ||  samples <= 0  ||  samples > f->max_samples)
+    if (!is_feed_of(f, kModemFeed)  ||  samples <= 0  ||  samples > f->max_samples)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
-    const int slot = (int) (f->n_commit % f->depth);
-    if (f->busy[slot])
-        return spangpu_set_error(SPANGPU_ERR_STATE, "every slot of the feed holds a tick: collect one first");
-    SPG_TRY(hipSetDevice(f->device));
-    hipStream_t bs = (hipStream_t) spangpu_modem_get_stream(f->modem);
-    SPG_TRY(hipMemcpyAsync(f->d_in[slot], f->h_in[slot], f->in_bytes, hipMemcpyHostToDevice, f->in_stream));
-    SPG_TRY(hipEventRecord(f->ev_in[slot], f->in_stream));
-    SPG_TRY(hipStreamWaitEvent(bs, f->ev_in[slot], 0));
-    int rc = spangpu_modem_rx(f->modem, (const int16_t *) f->d_in[slot], SPANGPU_MEM_DEVICE, samples, f->stride);
+    const int slot = ring_next(&f->core.ring);
+    if (slot < 0)
+        return slot;
+    FeedSlot *s = &f->core.slot[slot];
+    hipStream_t bs;
+    int rc = feed_send(&f->core, slot, [f] { return (hipStream_t) spangpu_modem_get_stream(f->modem); }, &bs);
     if (rc < 0)
         return rc;
-    uint32_t *packed = (uint32_t *) f->d_out[slot];
+    if ((rc = spangpu_modem_rx(f->modem, (const int16_t *) s->d_in, SPANGPU_MEM_DEVICE, samples, f->stride)) < 0)
+        return rc;
+    uint32_t *packed = (uint32_t *) s->d_out;
     uint32_t *status = packed + (size_t) f->n_ch*f->wpc;
     if ((rc = spangpu_modem_pack_events(f->modem, packed, f->wpc, status, f->status_cap)) < 0)
         return rc;
-    SPG_TRY(hipEventRecord(f->ev_k[slot], bs));
-    SPG_TRY(hipStreamWaitEvent(f->out_stream, f->ev_k[slot], 0));
-    if ((rc = xfeed_copy_out(f, slot)) < 0)
-        return rc;
-    SPG_TRY(hipEventRecord(f->ev_done[slot], f->out_stream));
-    f->busy[slot] = true;
-    f->samples_of[slot] = samples;
-    f->n_commit++;
-    return SPANGPU_OK;
+    return xfeed_send_up(f, slot, bs, samples);
 }
 
 // The oldest tick's put_bit stream in packed form (waits for it): *packed = [n_ch][words_per_channel] rows, *status = the
 // bank's status list (word 0 = entries), both good until the slot is committed again; spangpu_modem_unpack_events() turns
 // them into the calls.  Returns the tick's samples per channel, 0 when no tick is outstanding.
-int spangpu_modem_feed_collect(spangpu_modem_feed_t *feed, const uint32_t **packed, const uint32_t **status)
+int spangpu_modem_feed_collect(spangpu_modem_feed_t *f, const uint32_t **packed, const uint32_t **status)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  f->what != 2  ||  packed == nullptr  ||  status == nullptr)
+    if (!is_feed_of(f, kModemFeed)  ||  packed == nullptr  ||  status == nullptr)
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments");
     *packed = nullptr;
     *status = nullptr;
-    if (f->n_collect >= f->n_commit)
-        return 0;
-    const int slot = (int) (f->n_collect % f->depth);
-    SPG_TRY(hipSetDevice(f->device));
-    SPG_TRY(hipEventSynchronize(f->ev_done[slot]));
-    f->busy[slot] = false;
-    f->n_collect++;
-    *packed = (const uint32_t *) f->h_out[slot];
+    int slot;
+    const int rc = feed_wait_oldest(&f->core, &slot);
+    if (rc < 0  ||  slot < 0)
+        return rc;
+    *packed = (const uint32_t *) f->core.slot[slot].h_out;
     *status = *packed + (size_t) f->n_ch*f->wpc;
     return f->samples_of[slot];
 }
 
-int spangpu_modem_feed_outstanding(const spangpu_modem_feed_t *feed)
+int spangpu_modem_feed_outstanding(const spangpu_modem_feed_t *f)
 {
-    const spangpu_xfeed_t *f = (const spangpu_xfeed_t *) feed;
-    return f  ?  (int) (f->n_commit - f->n_collect)  :  SPANGPU_ERR_BAD_ARG;
+    return f  ?  ring_outstanding(&f->core.ring)  :  SPANGPU_ERR_BAD_ARG;
 }
 
-int spangpu_modem_feed_run(spangpu_modem_feed_t *feed, int samples, int ticks, int lag, double *elapsed_ms, long long *bits)
+// The same loop; *bits = the sum of what the header words of every 64th row say (a look at the rows: the data is there).
+int spangpu_modem_feed_run(spangpu_modem_feed_t *f, int samples, int ticks, int lag, double *elapsed_ms, long long *bits)
 {
-    spangpu_xfeed_t *f = (spangpu_xfeed_t *) feed;
-    if (f == nullptr  ||  ticks <= 0  ||  lag < 1  ||  lag >= f->depth  ||  spangpu_modem_feed_outstanding(feed) != 0)
-        return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (lag in 1 .. depth - 1, nothing outstanding)");
-    struct timespec t0, t1;
     const uint32_t *packed;
     const uint32_t *status;
     long long seen = 0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (int i = 0;  i <= ticks;  i++)
-    {
-        int rc;
-        if (i < ticks)
-        {
-            if (spangpu_modem_feed_acquire(feed) == nullptr)
-                return SPANGPU_ERR_STATE;
-            if ((rc = spangpu_modem_feed_commit(feed, samples)) < 0)
-                return rc;
-        }
-        while (spangpu_modem_feed_outstanding(feed) > ((i < ticks)  ?  lag  :  0))
-        {
-            if ((rc = spangpu_modem_feed_collect(feed, &packed, &status)) < 0)
-                return rc;
-            for (int c = 0;  c < f->n_ch;  c += 64)             // (a look at the headers of some rows: the data is there)
-                seen += packed[(size_t) c*f->wpc] & 0x7FFFu;
-        }
-    }
-    clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (elapsed_ms)
-        *elapsed_ms = (t1.tv_sec - t0.tv_sec)*1e3 + (t1.tv_nsec - t0.tv_nsec)*1e-6;
-    if (bits)
+    const int rc = ring_run(f  ?  &f->core.ring  :  nullptr, ticks, lag, elapsed_ms,
+                            [=] { return spangpu_modem_feed_commit(f, samples); },
+                            [&]
+                            {
+                                const int n = spangpu_modem_feed_collect(f, &packed, &status);
+                                for (int c = 0;  n > 0  &&  c < f->n_ch;  c += 64)
+                                    seen += packed[(size_t) c*f->wpc] & 0x7FFFu;
+                                return n;
+                            });
+    if (rc == SPANGPU_OK  &&  bits)
         *bits = seen;
-    return SPANGPU_OK;
+    return rc;
 }
 
 }   // extern "C"

@@ -850,23 +850,26 @@ class BanksPlan:
 ECHO_STATS_DTYPE = np.dtype([("sum_rx2", "<u8"), ("sum_clean2", "<u8"), ("crc", "<u4"), ("samples", "<u4")])
 
 
-class Feed:
-    """The pipelined host-buffer path of a tone bank (spangpu_feed_*): `depth` pinned slots; slot() hands out the numpy view
-    of the next tick's staging buffer ([n_ch, stride] int16, or uint8 for G.711) for the caller to fill, commit() queues the
-    tick, collect() returns the digits of the oldest tick as (channel, digit, block) arrays."""
+class _Feed:
+    """What the three pipelined feeds named spangpu_<_prefix>_* share: the handle's life, commit(), outstanding(), the tick loop
+    in C, and the numpy view of a slot's rows ([n_ch, stride] int16, or uint8 with a G.711 law)."""
+    _prefix = None
+    law = 0
 
-    def __init__(self, bank, max_samples, law=0, depth=2, device=0):
+    def _f(self, name):
+        return getattr(lib(), "spangpu_%s_%s" % (self._prefix, name))
+
+    def _create(self, bank, depth, *args):
         self.bank = bank
-        self.law = law
         self.h = C.c_void_p()
-        _check(lib().spangpu_feed_create(C.byref(self.h), bank.h, device, max_samples, law, depth))
-        self.stride = int(lib().spangpu_feed_stride(self.h))
+        _check(self._f("create")(C.byref(self.h), bank.h, *args))
+        self.stride = int(self._f("stride")(self.h))
         self.n_ch = bank.n
         self.depth = depth
 
     def close(self):
         if self.h:
-            lib().spangpu_feed_destroy(self.h)
+            self._f("destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -875,25 +878,45 @@ class Feed:
         except Exception:
             pass
 
-    def slot(self):
-        p = lib().spangpu_feed_acquire(self.h)
+    def _view(self, p):
+        ctype, dtype = (C.c_uint8, np.uint8) if self.law else (C.c_int16, np.int16)
+        return np.frombuffer((ctype*(self.n_ch*self.stride)).from_address(p), dtype).reshape(self.n_ch, self.stride)
+
+    def _slot(self):
+        p = self._f("acquire")(self.h)
         if not p:
             raise SpanGpuError(-6, lib().spangpu_last_error().decode())
-        if self.law:
-            buf = (C.c_uint8*(self.n_ch*self.stride)).from_address(p)
-            return np.frombuffer(buf, np.uint8).reshape(self.n_ch, self.stride)
-        buf = (C.c_int16*(self.n_ch*self.stride)).from_address(p)
-        return np.frombuffer(buf, np.int16).reshape(self.n_ch, self.stride)
+        return self._view(p)
 
     def commit(self, samples):
-        _check(lib().spangpu_feed_commit(self.h, samples))
+        _check(self._f("commit")(self.h, samples))
+
+    def outstanding(self):
+        return _check(self._f("outstanding")(self.h))
+
+    def _run(self, samples, ticks, lag, *outs):
+        ms = C.c_double()
+        _check(self._f("run")(self.h, samples, ticks, lag, C.byref(ms), *[C.byref(o) for o in outs]))
+        return ms.value
+
+
+class Feed(_Feed):
+    """The pipelined host-buffer path of a tone bank (spangpu_feed_*): `depth` pinned slots; slot() hands out the numpy view
+    of the next tick's staging buffer ([n_ch, stride] int16, or uint8 for G.711) for the caller to fill, commit() queues the
+    tick, collect() returns the digits of the oldest tick as (channel, digit, block) arrays."""
+    _prefix = "feed"
+
+    def __init__(self, bank, max_samples, law=0, depth=2, device=0):
+        self.law = law
+        self._create(bank, depth, device, max_samples, law, depth)
+
+    def slot(self):
+        return self._slot()
 
     def run(self, samples, ticks, lag=1):
         """The tick loop in C over the frames the slots hold -> (milliseconds, digits collected)."""
-        ms = C.c_double()
         digits = C.c_longlong()
-        _check(lib().spangpu_feed_run(self.h, samples, ticks, lag, C.byref(ms), C.byref(digits)))
-        return ms.value, digits.value
+        return self._run(samples, ticks, lag, digits), digits.value
 
     def collect(self):
         """-> (channel, digit, block) uint32 arrays of the oldest outstanding tick, or None if there is none."""
@@ -1180,47 +1203,21 @@ class ShardedModemBank(_Sharded):
         return counts, ev
 
 
-class EchoFeed:
+class EchoFeed(_Feed):
     """The pipelined host path of an echo canceller bank (spangpu_echo_feed_*): slots() hands out the numpy views of the next
     tick's tx and rx staging rows ([n_ch, stride] int16, or uint8 with a G.711 law), commit() queues the tick (H2D, kernel and
     D2H on three streams), collect() returns the clean rows of the oldest tick ([n_ch, stride], good until that slot is
     committed again)."""
+    _prefix = "echo_feed"
 
     def __init__(self, bank, max_samples, law=0, depth=3, use_hpf_tx=False):
-        self.bank = bank
         self.law = law
-        self.h = C.c_void_p()
-        _check(lib().spangpu_echo_feed_create(C.byref(self.h), bank.h, max_samples, law, depth, int(use_hpf_tx)))
-        self.stride = int(lib().spangpu_echo_feed_stride(self.h))
-        self.n_ch = bank.n
-        self.depth = depth
-
-    def close(self):
-        if self.h:
-            lib().spangpu_echo_feed_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _view(self, p):
-        if self.law:
-            return np.frombuffer((C.c_uint8*(self.n_ch*self.stride)).from_address(p), np.uint8).reshape(self.n_ch, self.stride)
-        return np.frombuffer((C.c_int16*(self.n_ch*self.stride)).from_address(p), np.int16).reshape(self.n_ch, self.stride)
+        self._create(bank, depth, max_samples, law, depth, int(use_hpf_tx))
 
     def slots(self):
         tx, rx = C.c_void_p(), C.c_void_p()
         _check(lib().spangpu_echo_feed_acquire(self.h, C.byref(tx), C.byref(rx)))
         return self._view(tx.value), self._view(rx.value)
-
-    def commit(self, samples):
-        _check(lib().spangpu_echo_feed_commit(self.h, samples))
-
-    def outstanding(self):
-        return _check(lib().spangpu_echo_feed_outstanding(self.h))
 
     def collect(self):
         """-> (clean rows view, samples) of the oldest outstanding tick, or None."""
@@ -1231,49 +1228,23 @@ class EchoFeed:
         return self._view(p.value), n
 
     def run(self, samples, ticks, lag=1):
-        ms = C.c_double()
-        _check(lib().spangpu_echo_feed_run(self.h, samples, ticks, lag, C.byref(ms)))
-        return ms.value
+        return self._run(samples, ticks, lag)
 
 
-class ModemFeed:
+class ModemFeed(_Feed):
     """The pipelined host path of a modem receiver bank (spangpu_modem_feed_*): slot() = the next tick's PCM staging rows
     ([n_ch, stride] int16), commit() queues the tick, collect() returns the oldest tick's put_bit stream -- as the packed rows
     and status list (raw=True) or unpacked into per-channel int8 arrays like ModemBank.events()."""
+    _prefix = "modem_feed"
 
     def __init__(self, bank, max_samples, max_bit_rate, depth=3):
-        self.bank = bank
-        self.h = C.c_void_p()
-        _check(lib().spangpu_modem_feed_create(C.byref(self.h), bank.h, max_samples, max_bit_rate, depth))
-        self.stride = int(lib().spangpu_modem_feed_stride(self.h))
+        self._create(bank, depth, max_samples, max_bit_rate, depth)
         self.wpc = _check(lib().spangpu_modem_feed_words_per_channel(self.h))
         self.status_cap = _check(lib().spangpu_modem_feed_status_cap(self.h))
-        self.n_ch = bank.n
-        self.depth = depth
         self.max_samples = max_samples
 
-    def close(self):
-        if self.h:
-            lib().spangpu_modem_feed_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def slot(self):
-        p = lib().spangpu_modem_feed_acquire(self.h)
-        if not p:
-            raise SpanGpuError(-6, lib().spangpu_last_error().decode())
-        return np.frombuffer((C.c_int16*(self.n_ch*self.stride)).from_address(p), np.int16).reshape(self.n_ch, self.stride)
-
-    def commit(self, samples):
-        _check(lib().spangpu_modem_feed_commit(self.h, samples))
-
-    def outstanding(self):
-        return _check(lib().spangpu_modem_feed_outstanding(self.h))
+        return self._slot()
 
     def collect(self, raw=False):
         if self.outstanding() <= 0:
@@ -1287,10 +1258,8 @@ class ModemFeed:
         return unpack_modem_events(packed, status, self.status_cap, self.max_samples*4 + 64)
 
     def run(self, samples, ticks, lag=1):
-        ms = C.c_double()
         bits = C.c_longlong()
-        _check(lib().spangpu_modem_feed_run(self.h, samples, ticks, lag, C.byref(ms), C.byref(bits)))
-        return ms.value, bits.value
+        return self._run(samples, ticks, lag, bits), bits.value
 
 
 def unpack_modem_events(packed, status, status_cap, cap):

@@ -324,7 +324,7 @@ class ToneOps:
         self.feed.commit(n)
 
     def outstanding(self):
-        return self.engine.lib().spangpu_feed_outstanding(self.feed.h)
+        return self.feed.outstanding()
 
     def collect(self):
         r = self.feed.collect()

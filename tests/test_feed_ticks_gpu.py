@@ -344,3 +344,144 @@ def test_feeds_refused_at_create(built):
         # the largest and the smallest feeds there are: nothing to collect, and gone again
         for feed in (own(engine.Feed(tone, 1024, depth=8)), own(engine.EchoFeed(echo, 1, depth=1)), own(engine.ModemFeed(modem, 1, 9600, depth=8))):
             assert feed.collect() is None
+
+
+def test_tone_feed_run_refusals(built):
+    """spangpu_feed_run() with lag = depth, lag 0 and a tick outstanding: refused, and that tick is there to collect, once."""
+    from spandsp_amd import engine
+    case = ft.tone_case("dtmf", 0)
+    with ft.closing_in_order(tone_bank(engine, "dtmf")) as own:
+        feed = own(engine.Feed(own.objs[0], ft.TONE_MAX, depth=3))
+        refused_runs(engine, ft.ToneOps(engine, feed, case.wire), feed, 160, 3)
+        ms, digits = feed.run(160, 4, 2)
+        assert ms > 0.0 and digits >= 0 and feed.outstanding() == 0
+
+
+def other_family_refused(engine, echo_feed, modem_feed):
+    """every echo call on the modem feed and every modem call on the echo feed: SPANGPU_ERR_BAD_ARG or NULL, nothing written,
+    and neither feed's count of outstanding ticks moves"""
+    import ctypes as C
+    L = engine.lib()
+    bad_arg = -2
+    before = echo_feed.outstanding(), modem_feed.outstanding()
+    a, b = C.c_void_p(), C.c_void_p()
+    ms, bits = C.c_double(-1.0), C.c_longlong(-1)
+    assert L.spangpu_echo_feed_acquire(modem_feed.h, C.byref(a), C.byref(b)) == bad_arg
+    assert L.spangpu_echo_feed_commit(modem_feed.h, 160) == bad_arg
+    assert L.spangpu_echo_feed_collect(modem_feed.h, C.byref(a)) == bad_arg
+    assert L.spangpu_echo_feed_run(modem_feed.h, 160, 2, 1, C.byref(ms)) == bad_arg
+    assert not L.spangpu_modem_feed_acquire(echo_feed.h)
+    assert L.spangpu_modem_feed_commit(echo_feed.h, 160) == bad_arg
+    assert L.spangpu_modem_feed_collect(echo_feed.h, C.byref(a), C.byref(b)) == bad_arg
+    assert L.spangpu_modem_feed_run(echo_feed.h, 160, 2, 1, C.byref(ms), C.byref(bits)) == bad_arg
+    assert not a.value and not b.value and ms.value == -1.0 and bits.value == -1
+    assert (echo_feed.outstanding(), modem_feed.outstanding()) == before
+
+
+def test_feeds_refuse_the_other_family(built):
+    """An echo feed and a modem feed are one struct behind two names (include/spangpu.h).  The other family's calls are refused
+    with nothing outstanding (where a run gets as far as its first commit) and around ticks in flight, and the ticks are the
+    oracle's."""
+    from spandsp_amd import engine
+    taps, mode, ticks = 128, 0x01, 3
+    ec, mc = ft.echo_case(taps, mode, False, 0), ft.modem_case("v29", 9600)
+    with ft.closing_in_order(engine.EchoBank(ft.N_CH, taps, mode), ft.modem_bank(engine, "v29", 9600)) as own:
+        echo_feed = own(engine.EchoFeed(own.objs[0], ft.XFEED_MAX, depth=3))
+        modem_feed = own(engine.ModemFeed(own.objs[1], ft.XFEED_MAX, 9600, depth=3))
+        sides = [(ft.EchoOps(engine, echo_feed, ec.wire_tx, ec.wire_rx), ec), (ft.ModemOps(engine, modem_feed, mc.sig), mc)]
+        other_family_refused(engine, echo_feed, modem_feed)
+        for t in range(ticks):
+            for ops, case in sides:
+                bufs = ops.acquire()
+                for buf in bufs:
+                    ft.poison(buf, 0)
+                ops.write(bufs, int(case.starts[t]), case.cuts[t])
+                ops.commit(case.cuts[t])
+            other_family_refused(engine, echo_feed, modem_feed)
+            assert echo_feed.outstanding() == t + 1 and modem_feed.outstanding() == t + 1
+        for t in range(ticks):
+            clean, n, _ = sides[0][0].collect()
+            assert n == ec.cuts[t] and np.array_equal(clean, ec.clean[t]), ("clean rows", t)
+            events, n, _ = sides[1][0].collect()
+            assert n == mc.cuts[t]
+            for c in range(ft.N_CH):
+                assert np.array_equal(events[c], mc.events[t][c]), ("events", t, c)
+        other_family_refused(engine, echo_feed, modem_feed)
+
+
+# ---- a feed destroyed under its ticks ------------------------------------------------------------------------------------------
+DESTROY_DEPTH = 3
+
+
+def fill_and_destroy(engine, feed, ops, case):
+    """A tick into every slot, none collected, and the feed destroyed: destroy waits for the way down, the bank and the way up
+    before it frees, so it returns with the bank's state that of `depth` ticks."""
+    for t in range(DESTROY_DEPTH):
+        bufs = ops.acquire()
+        for buf in bufs:
+            ft.poison(buf, ops.law)
+        ops.write(bufs, int(case.starts[t]), case.cuts[t])
+        ops.commit(case.cuts[t])
+    assert ops.outstanding() == DESTROY_DEPTH
+    feed.close()
+    assert not feed.h
+    return int(case.starts[DESTROY_DEPTH]), case.cuts[DESTROY_DEPTH]
+
+
+def test_tone_feed_destroyed_with_every_slot_taken(built):
+    """... and the next tick through the serial path makes the records it makes behind `depth` serial ticks."""
+    from spandsp_amd import engine
+    case = ft.tone_case("dtmf", 0)
+    want = serial_entries("dtmf", 0)[DESTROY_DEPTH]
+    assert want
+    with ft.closing_in_order(tone_bank(engine, "dtmf")) as own:
+        bank = own.objs[0]
+        feed = own(engine.Feed(bank, ft.TONE_MAX, depth=DESTROY_DEPTH))
+        a, n = fill_and_destroy(engine, feed, ft.ToneOps(engine, feed, case.wire), case)
+        bank.rx_host(case.wire[:, a:a + n])
+        got = sorted((int(r["channel"]), int(r["code"]), int(r["block"])) for r in bank.blocks() if (r["flags"] & engine.BLK_CHANGE) and r["code"])
+        assert got == want
+
+
+def test_echo_feed_destroyed_with_every_slot_taken(built):
+    from oracle import restated as orc
+    from spandsp_amd import engine
+    taps, mode = 128, 0x01
+    case = ft.echo_case(taps, mode, False, 0)
+    dets = [orc.EchoCan(taps, mode) for _ in range(ft.N_CH)]
+    for t in range(DESTROY_DEPTH):
+        a, n = int(case.starts[t]), case.cuts[t]
+        for c, d in enumerate(dets):
+            d.run(case.tx[c, a:a + n], case.rx[c, a:a + n], False)
+    with ft.closing_in_order(engine.EchoBank(ft.N_CH, taps, mode)) as own:
+        bank = own.objs[0]
+        feed = own(engine.EchoFeed(bank, ft.XFEED_MAX, depth=DESTROY_DEPTH))
+        a, n = fill_and_destroy(engine, feed, ft.EchoOps(engine, feed, case.wire_tx, case.wire_rx), case)
+        echo_lines.compare_state(bank, dets, "behind a destroyed feed")
+        clean = bank.update_host(case.tx[:, a:a + n], case.rx[:, a:a + n])
+        assert np.array_equal(clean, case.clean_pcm[DESTROY_DEPTH])
+
+
+def test_modem_feed_destroyed_with_every_slot_taken(built):
+    from oracle import restated as orc
+    from spandsp_amd import engine
+    from test_oracle_pin import bits
+    name, rate = "v29", 9600
+    case = ft.modem_case(name, rate)
+    state = []
+    for c in range(ft.N_CH):
+        o = orc.V29(rate)
+        for t in range(DESTROY_DEPTH):
+            a = int(case.starts[t])
+            o.rx(case.sig[c, a:a + case.cuts[t]])
+        f, w = o.snapshot()
+        state.append((bits(f).copy(), w))
+    with ft.closing_in_order(ft.modem_bank(engine, name, rate)) as own:
+        bank = own.objs[0]
+        feed = own(engine.ModemFeed(bank, ft.XFEED_MAX, rate, depth=DESTROY_DEPTH))
+        a, n = fill_and_destroy(engine, feed, ft.ModemOps(engine, feed, case.sig), case)
+        modem_state_check(bank, state, "behind a destroyed feed")
+        bank.rx_host(case.sig[:, a:a + n])
+        events = bank.events()
+        for c in range(ft.N_CH):
+            assert np.array_equal(events[c], case.events[DESTROY_DEPTH][c]), ("the next serial tick", c)
