@@ -1,7 +1,7 @@
 // v17_dev.hpp -- device side of the batched V.17 (and V.32bis 4800) receiver (reference: src/v17rx.c:214-1358;
-// primitives as in v29_dev.hpp).  Same mapping and baud-aligned execution as the V.29 bank -- one channel per lane,
-// RRC delay line / PCM tile / equaliser taps index-major in LDS, equaliser delay line in VGPRs in age order, reference
-// summation order -- plus what V.17 adds:
+// primitives as in v29_dev.hpp).  Same mapping and baud-aligned execution as the V.29 bank (its header has the reasoning)
+// -- one channel per lane, RRC delay line / PCM tile / equaliser taps index-major in LDS, equaliser delay line in VGPRs in
+// age order, reference summation order: the lane frame of modem_lane.hpp, included part by part -- plus what V.17 adds:
 //   * the 8-state trellis decoder (v17rx.c:396-589): accumulated path metrics in VGPRs, the 16-deep survivor memory
 //     packed in LDS per lane (3 bits per predecessor state, 1 byte per surviving point), traceback as 15 dependent
 //     LDS reads per baud;
@@ -20,6 +20,16 @@
 
 namespace spg {
 
+// the lane frame's constants (modem_lane.hpp); the float words up to eq_buf are V.29's
+#define LF_FLOATS   kV17Floats
+#define LF_F(x)     VF_##x
+#define LF_I(x)     XI_##x
+#define LF_TILE     kTile
+#define LF_EQLEN    kEqLen
+#define LF_PARKED   V17_PARKED
+#define LF_DELTA    use_delta
+#define LF_DELTA_MOVES
+
 // WPB, TILE, PK16: several waves per workgroup sharing the tables, a short PCM tile and the RRC delay line as packed
 // int16 pairs, for banks of full waves -- see v29_bank_kernel.  With the survivor memory a V.17 wave needs 45 KB of its
 // own: three of them and the 20 KB of tables fill a CU (155 KB), where the one-wave workgroups of 81 KB put two on it.
@@ -33,13 +43,11 @@ void v17_bank_kernel(const V17Launch L)
     __shared__ uint32_t t_map[36*36*2];
     __shared__ uint16_t t_sqrt[194];
     // per-lane RRC delay line (doubled) + survivor memory, PCM tile, equaliser taps: all index-major [word][CPW]
-    // (the RRC delay line as zero padded pairs, see v29_dev.hpp)
     __shared__ float2 lanes[PK16  ?  1  :  WPB*CPW*2*kRrcLen];
     __shared__ uint32_t lanes16[PK16  ?  WPB*CPW*2*kRrcLen  :  1];
     __shared__ uint32_t surv[WPB*CPW*(16 + 32)];
     // (a full wave's LDS must stay under half a CU's 160 KB so that two waves share a CU: shorter PCM tile there)
     constexpr int kTile = (TILE > 0)  ?  TILE  :  (CPW == 64)  ?  32  :  kPcmTile;
-    static_assert(kTile%8 == 0, "the PCM tile is staged in 16-byte pieces");
     __shared__ uint32_t pcm[WPB*CPW*(kTile/2)];
     __shared__ float2 taps[WPB*kEqLen*CPW];
 
@@ -83,37 +91,8 @@ void v17_bank_kernel(const V17Launch L)
 
     const size_t N = (size_t) L.n_ch;
     const int mylen = L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
-    auto ldf = [&](int w) { return __uint_as_float(L.state[(size_t) w*N + ch]); };
-    auto ldi = [&](int w) { return (int32_t) L.state[(size_t) (kV17Floats + w)*N + ch]; };
-    // A float word goes back as its bits -- except a NaN (a receiver whose equaliser has run away is full of them), which
-    // goes back as x86's: there an invalid operation makes the negative quiet NaN and arithmetic hands an operand's NaN on
-    // sign and all, while here the negated operand of a subtraction flips it.  Nothing ever depends on a NaN's sign.
-    auto stf = [&](int w, float v) { L.state[(size_t) w*N + ch] = (v != v)  ?  0xFFC00000u  :  __float_as_uint(v); };
-    auto sti = [&](int w, int32_t v) { L.state[(size_t) (kV17Floats + w)*N + ch] = (uint32_t) v; };
-
-    float2 *rrc2 = &lanes[PK16  ?  0  :  (wv*CPW*2*kRrcLen + lane)];           // [2*27] pairs, stride CPW
-    uint32_t *rrc16 = &lanes16[PK16  ?  (wv*CPW*2*kRrcLen + lane)  :  0];
-    uint32_t *pcmw = &pcm[wv*CPW*(kTile/2)];
-    auto rrc_put = [&](int k, float v)
-    {
-        if (PK16)
-        {
-            const uint32_t h = (uint32_t) (int) v & 0xFFFFu;
-            rrc16[k*CPW] = h;
-            rrc16[(kRrcLen + k)*CPW] = h << 16;
-        }
-        else
-        {
-            rrc2[k*CPW].x = v;
-            rrc2[(kRrcLen + k)*CPW].y = v;
-        }
-    };
-    auto rrc_at = [&](int k) -> float
-    {
-        if (PK16)
-            return (float) (int) (short) (rrc16[k*CPW] & 0xFFFFu);
-        return rrc2[k*CPW].x;
-    };
+#define LANE_PART LANE_STATE
+#include "modem_lane.inc"
     uint32_t *past = &surv[wv*CPW*(16 + 32) + lane];    // [16]: 8 x 3 bit predecessor states per time step
     uint32_t *full = past + 16*CPW;                     // [16][2]: 8 x 1 byte surviving points per time step
     float2 *ctap = &taps[wv*kEqLen*CPW + lane];
@@ -134,34 +113,10 @@ void v17_bank_kernel(const V17Launch L)
     float gdc0 = ldf(VF_GDC);
     float gdc1 = ldf(VF_GDC + 1);
     float baud_phase = ldf(VF_BAUD_PHASE);
-    for (int i = 0;  i < kRrcLen;  i++)
-    {
-        const float v = ldf(VF_RRC + i);
-        if (!PK16)
-        {
-            rrc2[i*CPW] = make_float2(v, 0.0f);
-            rrc2[(kRrcLen + i)*CPW] = make_float2(0.0f, v);
-        }
-        rrc_put(i, v);
-    }
-    for (int i = 0;  i < kEqLen;  i++)
-        TAP(i) = make_float2(ldf(VF_EQ_COEFF + 2*i), ldf(VF_EQ_COEFF + 2*i + 1));
-    // equaliser delay line in age order: xre[i] = eq_buf[(eq_step + i) mod 33] (i = 0 oldest)
-    float xre[kEqLen];
-    float xim[kEqLen];
-    bool eq_clear_pending = false;
-    bool restart_pending = false;
-    {
-        const int es = ldi(XI_EQ_STEP);
-#pragma unroll
-        for (int i = 0;  i < kEqLen;  i++)
-        {
-            int k = es + i;
-            k = (k >= kEqLen)  ?  (k - kEqLen)  :  k;
-            xre[i] = ldf(VF_EQ_BUF + 2*k);
-            xim[i] = ldf(VF_EQ_BUF + 2*k + 1);
-        }
-    }
+#define LANE_PART LANE_RRC_LOAD
+#include "modem_lane.inc"
+#define LANE_PART LANE_EQ_LOAD
+#include "modem_lane.inc"
     float sd[8];
 #pragma unroll
     for (int i = 0;  i < 8;  i++)
@@ -212,47 +167,14 @@ void v17_bank_kernel(const V17Launch L)
     auto diff_ld = [&](int k) { return ldi(XI_DIFF_ANGLES + (k & 0xF)); };
     auto diff_st = [&](int k, int32_t v) { sti(XI_DIFF_ANGLES + (k & 0xF), v); };
 
-    int8_t *evp = L.events + (size_t) ch*L.ev_cap;
-    int n_ev = 0;
-    auto emit = [&](int v)
-    {
-        if (n_ev < L.ev_cap)
-            evp[n_ev] = (int8_t) v;
-        n_ev++;
-    };
-
-    // qam_report(user, constel, target, symbol) calls, for the kernel variant a caller's tap asks for: one record per
-    // call = {events emitted before it in this launch, 1 if the pointers were NULL, symbol, constel re / im, target re / im}
-    int n_q = 0;
-    auto qam_report = [&](uint32_t null_ptrs, int symbol, float cre, float cim, float tre, float tim)
-    {
-        if constexpr (QAM)
-        {
-            if (n_q < L.qam_cap)
-            {
-                uint32_t *r = L.qam + ((size_t) ch*L.qam_cap + n_q)*7;
-                r[0] = (uint32_t) n_ev;
-                r[1] = null_ptrs;
-                r[2] = (uint32_t) symbol;
-                r[3] = __float_as_uint(cre);
-                r[4] = __float_as_uint(cim);
-                r[5] = __float_as_uint(tre);
-                r[6] = __float_as_uint(tim);
-            }
-            n_q++;
-        }
-    };
+#define LANE_PART LANE_RECORDS
+#include "modem_lane.inc"
 
     // v17_rx_restart(s, s->bit_rate, s->short_train), v17rx.c:1399-1500
     auto restart = [&]()
     {
-        for (int i = 0;  i < 2*kRrcLen;  i++)
-        {
-            if (PK16)
-                rrc16[i*CPW] = 0;
-            else
-                rrc2[i*CPW] = make_float2(0.0f, 0.0f);
-        }
+#define LANE_PART LANE_RRC_CLEAR
+#include "modem_lane.inc"
         training_error = 0.0f;
         rrc_step = 0;
         diff = 1;
@@ -280,8 +202,7 @@ void v17_bank_kernel(const V17Launch L)
         trellis_ptr = 14;
         carrier_phase = 0;
         power_reading = 0;
-        // (the equaliser delay line is register state: it is cleared where it is next looked at, see v29_dev.hpp)
-        eq_clear_pending = true;
+        eq_clear_pending = true;                            // (LANE_EQ_CLEAR)
         eq_put_step = kV17Sets*10/(3*2) - 1;
         eq_step = 0;
         eq_skip = 0;
@@ -313,60 +234,13 @@ void v17_bank_kernel(const V17Launch L)
         baud_half = 0;
     };
 
-    // vec_circular_dot_prodf() with its two partial sums kept in the halves of a packed pair (see v29_dev.hpp)
+    // the pulse shaper's coefficients come from HBM/L2: all 27 reads of a filter go out at once
     auto rrc_dot = [&](const float *table, int row)
     {
-        const float *y = table + row;
-        const float2 *x = rrc2 + rrc_step*CPW;
-        const uint32_t *xq = rrc16 + rrc_step*CPW;
-        f32x2v xs[kRrcLen];
-        float ys[kRrcLen];
-#pragma unroll
-        for (int i = 0;  i < kRrcLen;  i++)
-        {
-            if (PK16)
-            {
-                const uint32_t q = xq[i*CPW];
-                xs[i] = (f32x2v) {(float) (int) (short) (q & 0xFFFFu), (float) ((int) q >> 16)};
-            }
-            else
-            {
-                const float2 w = x[i*CPW];
-                xs[i] = (f32x2v) {w.x, w.y};
-            }
-            ys[i] = y[i*kV17Sets];
-        }
-        f32x2v a = {0.0f, 0.0f};
-#pragma unroll
-        for (int i = 0;  i < kRrcLen;  i++)
-            a += xs[i]*(f32x2v) {ys[i], ys[i]};
-        return a.x + a.y;
+        return spg::rrc_dot<kV17Sets, kRrcLen, CPW, PK16>(rrc2, rrc16, rrc_step, table, row);
     };
-    // track_carrier() and tune_equalizer() are requested by the stage logic and carried out once, after it, with the
-    // loop gains and step size as they were when the reference would have called them (see v29_dev.hpp).
-    bool do_track = false;
-    bool do_tune = false;
-    bool do_save = false;
-    float tgt_re = 0.0f;
-    float tgt_im = 0.0f;
-    float use_track_i = 0.0f;
-    float use_track_p = 0.0f;
-    float use_delta = 0.0f;
-    auto track_carrier = [&](float tre, float tim)
-    {
-        do_track = true;
-        tgt_re = tre;
-        tgt_im = tim;
-        use_track_i = carrier_track_i;
-        use_track_p = carrier_track_p;
-    };
-    auto tune_equalizer = [&](float tre, float tim)
-    {
-        do_tune = true;
-        tgt_re = tre;
-        tgt_im = tim;
-        use_delta = eq_delta;
-    };
+#define LANE_PART LANE_REQUESTS
+#include "modem_lane.inc"
     // v17rx.c:336-349 (scrambler_tap is 18 - 1: v17_rx_init never changes it)
     auto descramble = [&](int in_bit)
     {
@@ -534,32 +408,8 @@ void v17_bank_kernel(const V17Launch L)
     for (int tile = 0;  tile < L.samples;  tile += kTile)
     {
     const int tn = max(0, min(kTile, mylen - tile));         // per lane when the call carries per-channel lengths
-    // ---- stage this lane's stretch of PCM: pcm[k][lane] = samples 2k, 2k+1 of the tile ----------------------
-    {
-        const int16_t *row = src + tile;
-        const bool wide = ((((uintptr_t) row) & 15) == 0)  &&  (tn == kTile);
-        if (wide)
-        {
-#pragma unroll
-            for (int k = 0;  k < kTile/8;  k++)
-            {
-                const int4 v = ((const int4 *) row)[k];
-                pcmw[(4*k + 0)*CPW + lane] = (uint32_t) v.x;
-                pcmw[(4*k + 1)*CPW + lane] = (uint32_t) v.y;
-                pcmw[(4*k + 2)*CPW + lane] = (uint32_t) v.z;
-                pcmw[(4*k + 3)*CPW + lane] = (uint32_t) v.w;
-            }
-        }
-        else
-        {
-            for (int k = 0;  k < (tn + 1)/2;  k++)
-            {
-                const uint32_t lo = (uint16_t) row[2*k];
-                const uint32_t hi = (2*k + 1 < tn)  ?  (uint16_t) row[2*k + 1]  :  0u;
-                pcmw[k*CPW + lane] = lo | (hi << 16);
-            }
-        }
-    }
+#define LANE_PART LANE_STAGE_PCM
+#include "modem_lane.inc"
     int pos = 0;
     for (;;)
     {
@@ -581,72 +431,11 @@ void v17_bank_kernel(const V17Launch L)
     {
     if (take  &&  !ready  &&  !restart_pending  &&  pos < tn)
     {
-        const uint32_t pw = pcmw[(pos >> 1)*CPW + lane];
-        const int amp = (int) (short) ((pos & 1)  ?  (pw >> 16)  :  (pw & 0xFFFF));
-        pos++;
         do
         {
-        rrc_put(rrc_step, (float) amp);
-        if (++rrc_step >= kRrcLen)
-            rrc_step = 0;
-
-        // signal_detect(), v17rx.c:1133-1210 (IAXMODEM_STUFF is #defined at v17rx.c:1)
-        {
-            const int x = amp >> 1;
-            int d = (int) (short) (x - last_sample);
-            last_sample = x;
-            power_reading += ((d*d - power_reading) >> 4);
-            power = power_reading;
-            d = (int) (short) abs(d);
-            if (10*d < high_sample)
-            {
-                if (++low_samples > 120)
-                {
-                    power_reading = 0;
-                    high_sample = 0;
-                    low_samples = 0;
-                }
-            }
-            else
-            {
-                low_samples = 0;
-                if (d > high_sample)
-                    high_sample = d;
-            }
-            if (signal_present > 0)
-            {
-                if (drop_pending  ||  power < carrier_off_power)
-                {
-                    if (--signal_present <= 0)
-                    {
-                        // v17_rx_restart(): carried out right after this loop (see v29_dev.hpp)
-                        restart_pending = true;
-                        emit(-1);                           // SIG_STATUS_CARRIER_DOWN
-                        power = 0;
-                        break;
-                    }
-                    else
-                    {
-                        drop_pending = 1;
-                    }
-                }
-            }
-            else
-            {
-                if (power < carrier_on_power)
-                {
-                    power = 0;
-                }
-                else
-                {
-                    signal_present = 1;
-                    drop_pending = 0;
-                    emit(-2);                               // SIG_STATUS_CARRIER_UP
-                }
-            }
-        }
-        if (power == 0  ||  stage == V17_PARKED)
-            break;
+        // ---- v17_rx(), v17rx.c:1214-1295 ----
+#define LANE_PART LANE_SAMPLE
+#include "modem_lane.inc"
 
         eq_put_step -= kV17Sets;
         step = -eq_put_step;
@@ -682,35 +471,16 @@ void v17_bank_kernel(const V17Launch L)
         }
     }
     // (and the restart leaves the clearing of the equaliser delay line to here)
-    if (__any(eq_clear_pending))
-    {
-        if (eq_clear_pending)
-        {
-#pragma unroll
-            for (int i = 0;  i < kEqLen;  i++)
-            {
-                xre[i] = 0.0f;
-                xim[i] = 0.0f;
-            }
-            eq_clear_pending = false;
-        }
-    }
+#define LANE_PART LANE_EQ_CLEAR
+#include "modem_lane.inc"
     if (ready)
     {
         any_ready = true;
         float v;
             if (agc_scaling_save == 0.0f)
             {
-                int root_power;
-                {
-                    uint32_t xx = (uint32_t) power;
-                    const int top = 31 - __builtin_clz(xx);
-                    const int shift = 30 - (top & ~1);
-                    xx <<= shift;
-                    root_power = t_sqrt[((xx >> 24) & 0xFF) - 64] >> (shift >> 1);
-                }
-                if (root_power == 0)
-                    root_power = 1;
+#define LANE_PART LANE_ROOT_POWER
+#include "modem_lane.inc"
                 agc_scaling = (2.17f/1.000000f)/(float) root_power;
             }
             v = rrc_dot(g_rrc_im, step);
@@ -722,16 +492,8 @@ void v17_bank_kernel(const V17Launch L)
             eq_put_step += kV17Sets*10/(3*2);
 
             // ---- process_half_baud(), v17rx.c:592-1130 ----
-#pragma unroll
-            for (int i = 0;  i < kEqLen - 1;  i++)
-            {
-                xre[i] = xre[i + 1];
-                xim[i] = xim[i + 1];
-            }
-            xre[kEqLen - 1] = hre;
-            xim[kEqLen - 1] = him;
-            if (++eq_step >= kEqLen)
-                eq_step = 0;
+#define LANE_PART LANE_EQ_PUSH
+#include "modem_lane.inc"
             baud_half ^= 1;
             if (baud_half == 0)
                 baud_done = true;
@@ -760,29 +522,8 @@ void v17_bank_kernel(const V17Launch L)
                         eq_put_step += i;
                     }
                 }
-                {
-                    const int split = kEqLen - eq_step;
-                    float2 cs_[kEqLen];
-#pragma unroll
-                    for (int i = 0;  i < kEqLen;  i++)
-                        cs_[i] = TAP(i);
-                    f32x2v acc = f32x2v{0.0f, 0.0f};
-                    f32x2v fst = f32x2v{0.0f, 0.0f};
-#pragma unroll
-                    for (int i = 0;  i < kEqLen;  i++)
-                    {
-                        if (i == split)
-                        {
-                            fst = acc;
-                            acc = f32x2v{0.0f, 0.0f};
-                        }
-                        const f32x2v t1 = f32x2v{xre[i], xre[i]}*f32x2v{cs_[i].x, cs_[i].y};
-                        const f32x2v t2 = f32x2v{xim[i], xim[i]}*f32x2v{cs_[i].y, cs_[i].x};
-                        acc += t1 + f32x2v{-t2.x, t2.y};
-                    }
-                    zre = fst.x + acc.x;
-                    zim = fst.y + acc.y;
-                }
+#define LANE_PART LANE_EQ_DOT
+#include "modem_lane.inc"
 
                 float tre;
                 float tim;
@@ -1082,36 +823,8 @@ void v17_bank_kernel(const V17Launch L)
                     break;
                 }
                 qam_report(0, cs, zre, zim, rep_re, rep_im);                        // v17rx.c:1117-1131
-                if (do_track)
-                {
-                    const float error = zim*tgt_re - zre*tgt_im;
-                    carrier_phase_rate += v29_f2i(use_track_i*error);
-                    carrier_phase += (uint32_t) v29_f2i(use_track_p*error);
-                }
-                if (do_tune)
-                {
-                    const float ere = (tgt_re - zre)*use_delta;
-                    const float eim = (tgt_im - zim)*use_delta;
-#pragma unroll
-                    for (int i = 0;  i < kEqLen;  i++)
-                    {
-                        const float2 c0 = TAP(i);
-                        const f32x2v u = f32x2v{xim[i], xre[i]}*f32x2v{eim, eim};
-                        const f32x2v w = f32x2v{xre[i], xim[i]}*f32x2v{ere, ere};
-                        const f32x2v c = f32x2v{c0.x, c0.y}*f32x2v{0.9999f, 0.9999f} + (u + f32x2v{w.x, -w.y});
-                        TAP(i) = make_float2(c.x, c.y);
-                    }
-                }
-                if (do_save)
-                {
-                    carrier_phase_rate_save = carrier_phase_rate;
-                    for (int k = 0;  k < kEqLen;  k++)
-                    {
-                        const float2 c = TAP(k);
-                        stf(VF_EQ_SAVE + 2*k, c.x);
-                        stf(VF_EQ_SAVE + 2*k + 1, c.y);
-                    }
-                }
+#define LANE_PART LANE_CARRY_OUT
+#include "modem_lane.inc"
         carrier_phase += (uint32_t) carrier_phase_rate;     // dds_advancef() with the rate the baud left behind
     }
     }
@@ -1130,35 +843,12 @@ void v17_bank_kernel(const V17Launch L)
     stf(VF_GDC, gdc0);
     stf(VF_GDC + 1, gdc1);
     stf(VF_BAUD_PHASE, baud_phase);
-    for (int i = 0;  i < kRrcLen;  i++)
-        stf(VF_RRC + i, rrc_at(i));
-    for (int i = 0;  i < kEqLen;  i++)
-    {
-        const float2 c = TAP(i);
-        stf(VF_EQ_COEFF + 2*i, c.x);
-        stf(VF_EQ_COEFF + 2*i + 1, c.y);
-    }
-    if (__any(eq_clear_pending))
-    {
-        if (eq_clear_pending)
-        {
-#pragma unroll
-            for (int i = 0;  i < kEqLen;  i++)
-            {
-                xre[i] = 0.0f;
-                xim[i] = 0.0f;
-            }
-            eq_clear_pending = false;
-        }
-    }
-#pragma unroll
-    for (int i = 0;  i < kEqLen;  i++)
-    {
-        int k = eq_step + i;
-        k = (k >= kEqLen)  ?  (k - kEqLen)  :  k;
-        stf(VF_EQ_BUF + 2*k, xre[i]);
-        stf(VF_EQ_BUF + 2*k + 1, xim[i]);
-    }
+#define LANE_PART LANE_LINES_STORE
+#include "modem_lane.inc"
+#define LANE_PART LANE_EQ_CLEAR
+#include "modem_lane.inc"
+#define LANE_PART LANE_EQ_STORE
+#include "modem_lane.inc"
 #pragma unroll
     for (int i = 0;  i < 8;  i++)
         stf(XF_DIST + i, sd[i]);
@@ -1199,10 +889,12 @@ void v17_bank_kernel(const V17Launch L)
     L.ev_count[ch] = n_ev;
     if constexpr (QAM)
         L.qam_count[ch] = n_q;
-#undef RRC2
 #undef TAP
 #undef PAST
 #undef FULL
 }
+
+#define LANE_PART LANE_END
+#include "modem_lane.inc"
 
 }   // namespace spg

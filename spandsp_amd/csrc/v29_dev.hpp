@@ -13,8 +13,7 @@
 //     summation and as the order in which state is stored.  The 33 complex taps sit in LDS,
 //     [tap][lane], also always indexed by a compile-time tap number;
 //   * the RRC delay line lives in a per-lane LDS column, stored twice back to back so
-//     x[(pos + i) mod n] is the contiguous x2[pos + i], as zero padded pairs ({x, 0} then {0, x}) so that
-//     one packed multiply-add per tap forms both partial sums of the circular inner product; the frame's
+//     x[(pos + i) mod n] is the contiguous x2[pos + i], as zero padded pairs (modem_lane.inc, LANE_STATE); the frame's
 //     PCM is staged in LDS too;
 //   * the polyphase RRC table (48 x 27 x {re, im}) and the sine table live once per
 //     workgroup in LDS and are gathered by per-lane row;
@@ -34,15 +33,29 @@
 // Numerics: fp32, every op rounded separately (-ffp-contract=off), float->int conversions
 // with the x86 out-of-range result the reference build has; the single libm dependency of
 // the reference path (cosf/sinf of the training phase spin, v29rx.c:618-623) is computed
-// with the C library's own algorithm (spg_sincosf below), so it has the same bits too.
+// with the C library's own algorithm (spg_sincosf, v29_common.hpp), so it has the same bits too.
+//
+// What a lane does the same way in the V.27ter and V.17 banks (v27ter_dev.hpp, v17_dev.hpp) -- state words, the RRC delay
+// line, records, the PCM tile, a sample's way through carrier detection, the AGC's square root, the loop updates, the
+// equaliser delay line -- is the lane frame of modem_lane.hpp, included part by part.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "v29_common.hpp"
+#include "modem_lane.hpp"
 
 namespace spg {
+
+// the lane frame's constants (modem_lane.hpp)
+#define LF_FLOATS   kV29Floats
+#define LF_F(x)     VF_##x
+#define LF_I(x)     VI_##x
+#define LF_TILE     TILE
+#define LF_EQLEN    kEqLen
+#define LF_PARKED   V29_PARKED
+#define LF_DELTA    eq_delta
 
 // CPW = channels per workgroup (one wavefront): 64 when the bank is big enough to fill every SIMD of the chip with
 // full waves, fewer (idle upper lanes) for small banks so that the channels still spread over all 1024 SIMDs.
@@ -56,7 +69,6 @@ __global__ __launch_bounds__(64*WPB)
 void v29_bank_kernel(const V29Launch L)
 {
     static_assert(WPB == 1  ||  CPW == 64, "several waves per workgroup: full waves only");
-    static_assert(TILE%8 == 0  &&  TILE >= 8, "the PCM tile is staged in 16-byte pieces");
     // coefficient tables transposed to [tap][set]: lanes on different polyphase sets hit different banks
     __shared__ float t_rrc_re[kRrcSets*kRrcLen];
     __shared__ float t_rrc_im[kRrcSets*kRrcLen];
@@ -64,12 +76,9 @@ void v29_bank_kernel(const V29Launch L)
     __shared__ float t_const[32];
     __shared__ uint16_t t_sqrt[194];
     __shared__ uint8_t t_map[400];
-    // per-lane RRC delay line and PCM tile, index-major [word][CPW]: lane l always uses the banks of (l mod 32)
-    // whatever its position.  The delay line is stored as 2*27 pairs: pair k < 27 is {x[k], 0}, pair 27 + k is
-    // {0, x[k]} -- the window of 27 pairs starting at the circular position then holds, in .x, the head part of
-    // vec_circular_dot_prodf()'s sum padded with zeros and, in .y, zeros followed by its wrapped part.
+    // per-lane RRC delay line (one of the two a stub) and PCM tile, index-major [word][CPW]
     __shared__ float2 lanes[PK16  ?  1  :  WPB*CPW*2*kRrcLen];
-    __shared__ uint32_t lanes16[PK16  ?  WPB*CPW*2*kRrcLen  :  1];     // PK16: pair k = x[k] | 0 << 16, pair 27 + k = 0 | x[k] << 16
+    __shared__ uint32_t lanes16[PK16  ?  WPB*CPW*2*kRrcLen  :  1];
     __shared__ uint32_t pcm[WPB*CPW*(TILE/2)];
     // equaliser taps {re, im}, [tap][lane]: always indexed by a compile-time tap number
     __shared__ float2 taps[WPB*kEqLen*CPW];
@@ -121,38 +130,8 @@ void v29_bank_kernel(const V29Launch L)
     // ---- state -> registers / LDS ---------------------------------------------------------------
     const size_t N = (size_t) L.n_ch;
     const int mylen = L.lens  ?  min(max(L.lens[ch], 0), L.samples)  :  L.samples;
-    auto ldf = [&](int w) { return __uint_as_float(L.state[(size_t) w*N + ch]); };
-    auto ldi = [&](int w) { return (int32_t) L.state[(size_t) (kV29Floats + w)*N + ch]; };
-    // A float word goes back as its bits -- except a NaN (a receiver whose equaliser has run away is full of them), which
-    // goes back as x86's: there an invalid operation makes the negative quiet NaN and arithmetic hands an operand's NaN on
-    // sign and all, while here the negated operand of a subtraction flips it.  Nothing ever depends on a NaN's sign.
-    auto stf = [&](int w, float v) { L.state[(size_t) w*N + ch] = (v != v)  ?  0xFFC00000u  :  __float_as_uint(v); };
-    auto sti = [&](int w, int32_t v) { L.state[(size_t) (kV29Floats + w)*N + ch] = (uint32_t) v; };
-
-    float2 *rrc2 = &lanes[PK16  ?  0  :  (wv*CPW*2*kRrcLen + lane)];           // [2*27] pairs, stride CPW
-    uint32_t *rrc16 = &lanes16[PK16  ?  (wv*CPW*2*kRrcLen + lane)  :  0];
-    uint32_t *pcmw = &pcm[wv*CPW*(TILE/2)];
-    // delay line element k <- v (both of its pairs); the element back as a float
-    auto rrc_put = [&](int k, float v)
-    {
-        if (PK16)
-        {
-            const uint32_t h = (uint32_t) (int) v & 0xFFFFu;
-            rrc16[k*CPW] = h;
-            rrc16[(kRrcLen + k)*CPW] = h << 16;
-        }
-        else
-        {
-            rrc2[k*CPW].x = v;
-            rrc2[(kRrcLen + k)*CPW].y = v;
-        }
-    };
-    auto rrc_at = [&](int k) -> float
-    {
-        if (PK16)
-            return (float) (int) (short) (rrc16[k*CPW] & 0xFFFFu);
-        return rrc2[k*CPW].x;
-    };
+#define LANE_PART LANE_STATE
+#include "modem_lane.inc"
 
     float agc_scaling = ldf(VF_AGC);
     float agc_scaling_save = ldf(VF_AGC_SAVE);
@@ -167,36 +146,12 @@ void v29_bank_kernel(const V29Launch L)
     float gdc0 = ldf(VF_GDC);
     float gdc1 = ldf(VF_GDC + 1);
     float baud_phase = ldf(VF_BAUD_PHASE);
-    for (int i = 0;  i < kRrcLen;  i++)
-    {
-        const float v = ldf(VF_RRC + i);
-        if (!PK16)
-        {
-            rrc2[i*CPW] = make_float2(v, 0.0f);
-            rrc2[(kRrcLen + i)*CPW] = make_float2(0.0f, v);
-        }
-        rrc_put(i, v);
-    }
+#define LANE_PART LANE_RRC_LOAD
+#include "modem_lane.inc"
     float2 *ctap = &taps[wv*kEqLen*CPW + lane];
 #define TAP(i)      ctap[(i)*CPW]
-    for (int i = 0;  i < kEqLen;  i++)
-        TAP(i) = make_float2(ldf(VF_EQ_COEFF + 2*i), ldf(VF_EQ_COEFF + 2*i + 1));
-    // equaliser delay line in age order: xre[i] = eq_buf[(eq_step + i) mod 33] (i = 0 oldest)
-    float xre[kEqLen];
-    float xim[kEqLen];
-    bool eq_clear_pending = false;
-    bool restart_pending = false;
-    {
-        const int es = ldi(VI_EQ_STEP);
-#pragma unroll
-        for (int i = 0;  i < kEqLen;  i++)
-        {
-            int k = es + i;
-            k = (k >= kEqLen)  ?  (k - kEqLen)  :  k;
-            xre[i] = ldf(VF_EQ_BUF + 2*k);
-            xim[i] = ldf(VF_EQ_BUF + 2*k + 1);
-        }
-    }
+#define LANE_PART LANE_EQ_LOAD
+#include "modem_lane.inc"
     const int bit_rate = ldi(VI_BIT_RATE);
     int rrc_step = ldi(VI_RRC_STEP);
     uint32_t scramble_reg = (uint32_t) ldi(VI_SCRAMBLE);
@@ -228,47 +183,14 @@ void v29_bank_kernel(const V29Launch L)
     auto diff_ld = [&](int k) { return ldi(VI_DIFF_ANGLES + (k & 0xF)); };
     auto diff_st = [&](int k, int32_t v) { sti(VI_DIFF_ANGLES + (k & 0xF), v); };
 
-    int8_t *evp = L.events + (size_t) ch*L.ev_cap;
-    int n_ev = 0;
-    auto emit = [&](int v)
-    {
-        if (n_ev < L.ev_cap)
-            evp[n_ev] = (int8_t) v;
-        n_ev++;
-    };
-
-    // qam_report(user, constel, target, symbol) calls, for the kernel variant a caller's tap asks for: one record per
-    // call = {events emitted before it in this launch, 1 if the pointers were NULL, symbol, constel re / im, target re / im}
-    int n_q = 0;
-    auto qam_report = [&](uint32_t null_ptrs, int symbol, float cre, float cim, float tre, float tim)
-    {
-        if constexpr (QAM)
-        {
-            if (n_q < L.qam_cap)
-            {
-                uint32_t *r = L.qam + ((size_t) ch*L.qam_cap + n_q)*7;
-                r[0] = (uint32_t) n_ev;
-                r[1] = null_ptrs;
-                r[2] = (uint32_t) symbol;
-                r[3] = __float_as_uint(cre);
-                r[4] = __float_as_uint(cim);
-                r[5] = __float_as_uint(tre);
-                r[6] = __float_as_uint(tim);
-            }
-            n_q++;
-        }
-    };
+#define LANE_PART LANE_RECORDS
+#include "modem_lane.inc"
 
     // v29rx.c:1019-1098 (old_train == false, the only way the receive path calls it)
     auto restart = [&]()
     {
-        for (int i = 0;  i < 2*kRrcLen;  i++)
-        {
-            if (PK16)
-                rrc16[i*CPW] = 0;
-            else
-                rrc2[i*CPW] = make_float2(0.0f, 0.0f);
-        }
+#define LANE_PART LANE_RRC_CLEAR
+#include "modem_lane.inc"
         rrc_step = 0;
         scramble_reg = 0;
         training_scramble_reg = 0x2A;
@@ -287,10 +209,7 @@ void v29_bank_kernel(const V29Launch L)
         carrier_phase_rate = v29_f2i(1700.0f*65536.0f*65536.0f/8000);
         for (int i = 0;  i < kEqLen;  i++)
             TAP(i) = make_float2((i == 16)  ?  3.0f  :  0.0f, 0.0f);       // V29_EQUALIZER_PRE_LEN
-        // The equaliser delay line is register state, and this path is rare: clearing it here, inside the sample loop,
-        // made every iteration of that loop pay ~450 register moves at the merge points.  It is cleared where it is
-        // next looked at instead (start of the T/2 phase, write-back).
-        eq_clear_pending = true;
+        eq_clear_pending = true;                            // (LANE_EQ_CLEAR)
         eq_put_step = kRrcSets*10/(3*2) - 1;
         eq_step = 0;
         agc_scaling_save = 0.0f;
@@ -305,67 +224,14 @@ void v29_bank_kernel(const V29Launch L)
         baud_half = 0;
     };
 
-    // vec_circular_dot_prodf(rrc_filter, coeffs[row], 27, rrc_step)   (vector_float.c:890-939)
+    // the pulse shaper runs on every sample here: its LDS reads go out nine taps at a time
     auto rrc_dot = [&](const float *table, int row)
     {
-        const float *y = table + row;
-        const float2 *x = rrc2 + rrc_step*CPW;
-        const uint32_t *xq = rrc16 + rrc_step*CPW;
-        // the LDS reads go out nine taps at a time, ahead of that group's part of the summation chain: all 54 at once
-        // kept 81 registers live across a kernel that already overflows into AGPRs
-        f32x2v a = {0.0f, 0.0f};
-#pragma unroll
-        for (int i0 = 0;  i0 < kRrcLen;  i0 += 9)
-        {
-            f32x2v xs[9];
-            float ys[9];
-#pragma unroll
-            for (int i = 0;  i < 9;  i++)
-            {
-                if (PK16)
-                {
-                    const uint32_t q = xq[(i0 + i)*CPW];
-                    xs[i] = (f32x2v) {(float) (int) (short) (q & 0xFFFFu), (float) ((int) q >> 16)};
-                }
-                else
-                {
-                    const float2 w = x[(i0 + i)*CPW];
-                    xs[i] = (f32x2v) {w.x, w.y};
-                }
-                ys[i] = y[(i0 + i)*kRrcSets];
-            }
-            // .x: x[pos..n) . y[0..n-pos) then + 0*y (exact: a running sum that starts at +0 is never -0);
-            // .y: 0*y then x[0..pos) . y[n-pos..n) -- the reference's two partial sums, each in its own order
-#pragma unroll
-            for (int i = 0;  i < 9;  i++)
-                a += xs[i]*(f32x2v) {ys[i], ys[i]};
-        }
-        return a.x + a.y;
+        return spg::rrc_dot<kRrcSets, 9, CPW, PK16>(rrc2, rrc16, rrc_step, table, row);
     };
 
-    // track_carrier() and tune_equalizer() (v29rx.c:281-331) are requested by the stage logic and carried out once,
-    // after it, with the loop gains as they were when the reference would have called them.
-    bool do_track = false;
-    bool do_tune = false;
-    bool do_save = false;
-    float tgt_re = 0.0f;
-    float tgt_im = 0.0f;
-    float use_track_i = 0.0f;
-    float use_track_p = 0.0f;
-    auto track_carrier = [&](float tre, float tim)
-    {
-        do_track = true;
-        tgt_re = tre;
-        tgt_im = tim;
-        use_track_i = carrier_track_i;
-        use_track_p = carrier_track_p;
-    };
-    auto tune_equalizer = [&](float tre, float tim)
-    {
-        do_tune = true;
-        tgt_re = tre;
-        tgt_im = tim;
-    };
+#define LANE_PART LANE_REQUESTS
+#include "modem_lane.inc"
     auto put_bit = [&](int bit)
     {
         // v29rx.c:365-397
@@ -437,32 +303,8 @@ void v29_bank_kernel(const V29Launch L)
     for (int tile = 0;  tile < L.samples;  tile += TILE)
     {
     const int tn = max(0, min(TILE, mylen - tile));         // per lane when the call carries per-channel lengths
-    // ---- stage this lane's stretch of PCM: pcm[k][lane] = samples 2k, 2k+1 of the tile ----------------------
-    {
-        const int16_t *row = src + tile;
-        const bool wide = ((((uintptr_t) row) & 15) == 0)  &&  (tn == TILE);
-        if (wide)
-        {
-#pragma unroll
-            for (int k = 0;  k < TILE/8;  k++)
-            {
-                const int4 v = ((const int4 *) row)[k];
-                pcmw[(4*k + 0)*CPW + lane] = (uint32_t) v.x;
-                pcmw[(4*k + 1)*CPW + lane] = (uint32_t) v.y;
-                pcmw[(4*k + 2)*CPW + lane] = (uint32_t) v.z;
-                pcmw[(4*k + 3)*CPW + lane] = (uint32_t) v.w;
-            }
-        }
-        else
-        {
-            for (int k = 0;  k < (tn + 1)/2;  k++)
-            {
-                const uint32_t lo = (uint16_t) row[2*k];
-                const uint32_t hi = (2*k + 1 < tn)  ?  (uint16_t) row[2*k + 1]  :  0u;
-                pcmw[k*CPW + lane] = lo | (hi << 16);
-            }
-        }
-    }
+#define LANE_PART LANE_STAGE_PCM
+#include "modem_lane.inc"
     int pos = 0;
     for (;;)
     {
@@ -485,75 +327,11 @@ void v29_bank_kernel(const V29Launch L)
     {
     if (take  &&  !ready  &&  !restart_pending  &&  pos < tn)
     {
-        const uint32_t pw = pcmw[(pos >> 1)*CPW + lane];
-        const int amp = (int) (short) ((pos & 1)  ?  (pw >> 16)  :  (pw & 0xFFFF));
-        pos++;
         do
         {
         // ---- v29_rx(), v29rx.c:885-961 --------------------------------------------------------
-        rrc_put(rrc_step, (float) amp);
-        if (++rrc_step >= kRrcLen)
-            rrc_step = 0;
-
-        // signal_detect(), v29rx.c:788-865 (with the IAXMODEM_STUFF this snapshot #defines)
-        {
-            const int x = amp >> 1;
-            int diff = (int) (short) (x - last_sample);
-            last_sample = x;
-            power_reading += ((diff*diff - power_reading) >> 4);
-            power = power_reading;
-            diff = (int) (short) abs(diff);
-            if (10*diff < high_sample)
-            {
-                if (++low_samples > 120)
-                {
-                    power_reading = 0;
-                    high_sample = 0;
-                    low_samples = 0;
-                }
-            }
-            else
-            {
-                low_samples = 0;
-                if (diff > high_sample)
-                    high_sample = diff;
-            }
-            if (signal_present > 0)
-            {
-                if (drop_pending  ||  power < carrier_off_power)
-                {
-                    if (--signal_present <= 0)
-                    {
-                        // v29_rx_restart() rewrites some forty state variables: done right after this loop (the lane
-                        // takes no further sample until then), because with it inline every iteration of the loop
-                        // paid for the register copies at its merge points
-                        restart_pending = true;
-                        emit(-1);                           // SIG_STATUS_CARRIER_DOWN
-                        power = 0;
-                        break;
-                    }
-                    else
-                    {
-                        drop_pending = 1;
-                    }
-                }
-            }
-            else
-            {
-                if (power < carrier_on_power)
-                {
-                    power = 0;
-                }
-                else
-                {
-                    signal_present = 1;
-                    drop_pending = 0;
-                    emit(-2);                               // SIG_STATUS_CARRIER_UP
-                }
-            }
-        }
-        if (power == 0  ||  stage == V29_PARKED)
-            break;
+#define LANE_PART LANE_SAMPLE
+#include "modem_lane.inc"
 
         eq_put_step -= kRrcSets;
         step = -eq_put_step;
@@ -590,36 +368,16 @@ void v29_bank_kernel(const V29Launch L)
         }
     }
     // (and the restart leaves the clearing of the equaliser delay line to here)
-    if (__any(eq_clear_pending))
-    {
-        if (eq_clear_pending)
-        {
-#pragma unroll
-            for (int i = 0;  i < kEqLen;  i++)
-            {
-                xre[i] = 0.0f;
-                xim[i] = 0.0f;
-            }
-            eq_clear_pending = false;
-        }
-    }
+#define LANE_PART LANE_EQ_CLEAR
+#include "modem_lane.inc"
     if (ready)
     {
         any_ready = true;
         float v;
             if (agc_scaling_save == 0.0f)
             {
-                // fixed_sqrt32(), math_fixed.c:158-169
-                int root_power;
-                {
-                    uint32_t xx = (uint32_t) power;
-                    const int top = 31 - __builtin_clz(xx);
-                    const int shift = 30 - (top & ~1);
-                    xx <<= shift;
-                    root_power = t_sqrt[((xx >> 24) & 0xFF) - 64] >> (shift >> 1);
-                }
-                if (root_power == 0)
-                    root_power = 1;
+#define LANE_PART LANE_ROOT_POWER
+#include "modem_lane.inc"
                 agc_scaling = (1.25f/1.0f)/(float) root_power;
             }
             v = rrc_dot(t_rrc_im, step);
@@ -632,16 +390,8 @@ void v29_bank_kernel(const V29Launch L)
             eq_put_step += kRrcSets*10/(3*2);
 
             // ---- process_half_baud(), v29rx.c:484-786 ----------------------------------------
-#pragma unroll
-            for (int i = 0;  i < kEqLen - 1;  i++)
-            {
-                xre[i] = xre[i + 1];
-                xim[i] = xim[i + 1];
-            }
-            xre[kEqLen - 1] = hre;
-            xim[kEqLen - 1] = him;
-            if (++eq_step >= kEqLen)
-                eq_step = 0;
+#define LANE_PART LANE_EQ_PUSH
+#include "modem_lane.inc"
             baud_half ^= 1;
             if (baud_half == 0)
                 baud_done = true;
@@ -673,31 +423,8 @@ void v29_bank_kernel(const V29Launch L)
                         eq_put_step += i;
                     }
                 }
-                // equalizer_get(): cvec_circular_dot_prodf (complex_vector_float.c:137-196)
-                {
-                    const int split = kEqLen - eq_step;
-                    float2 cs[kEqLen];
-#pragma unroll
-                    for (int i = 0;  i < kEqLen;  i++)
-                        cs[i] = TAP(i);
-                    f32x2v acc = f32x2v{0.0f, 0.0f};
-                    f32x2v fst = f32x2v{0.0f, 0.0f};
-#pragma unroll
-                    for (int i = 0;  i < kEqLen;  i++)
-                    {
-                        if (i == split)
-                        {
-                            fst = acc;
-                            acc = f32x2v{0.0f, 0.0f};
-                        }
-                        // {xr*c.x - xi*c.y, xr*c.y + xi*c.x}: two packed products, a packed add with one negated half
-                        const f32x2v t1 = f32x2v{xre[i], xre[i]}*f32x2v{cs[i].x, cs[i].y};
-                        const f32x2v t2 = f32x2v{xim[i], xim[i]}*f32x2v{cs[i].y, cs[i].x};
-                        acc += t1 + f32x2v{-t2.x, t2.y};
-                    }
-                    zre = fst.x + acc.x;
-                    zim = fst.y + acc.y;
-                }
+#define LANE_PART LANE_EQ_DOT
+#include "modem_lane.inc"
 
                 do_track = false;
                 do_tune = false;
@@ -864,38 +591,8 @@ void v29_bank_kernel(const V29Launch L)
                     break;
                 }
                 qam_report(0, constellation_state, zre, zim, rep_re, rep_im);      // v29rx.c:769-783
-                if (do_track)
-                {
-                    const float error = zim*tgt_re - zre*tgt_im;
-                    carrier_phase_rate += v29_f2i(use_track_i*error);
-                    carrier_phase += (uint32_t) v29_f2i(use_track_p*error);
-                }
-                if (do_tune)
-                {
-                    // cvec_circular_lmsf (complex_vector_float.c:201-219)
-                    const float ere = (tgt_re - zre)*eq_delta;
-                    const float eim = (tgt_im - zim)*eq_delta;
-#pragma unroll
-                    for (int i = 0;  i < kEqLen;  i++)
-                    {
-                        const float2 c0 = TAP(i);
-                        // {xi*eim + xr*ere, xr*eim - xi*ere}
-                        const f32x2v u = f32x2v{xim[i], xre[i]}*f32x2v{eim, eim};
-                        const f32x2v w = f32x2v{xre[i], xim[i]}*f32x2v{ere, ere};
-                        const f32x2v c = f32x2v{c0.x, c0.y}*f32x2v{0.9999f, 0.9999f} + (u + f32x2v{w.x, -w.y});
-                        TAP(i) = make_float2(c.x, c.y);
-                    }
-                }
-                if (do_save)
-                {
-                    carrier_phase_rate_save = carrier_phase_rate;
-                    for (int k = 0;  k < kEqLen;  k++)
-                    {
-                        const float2 c = TAP(k);
-                        stf(VF_EQ_SAVE + 2*k, c.x);
-                        stf(VF_EQ_SAVE + 2*k + 1, c.y);
-                    }
-                }
+#define LANE_PART LANE_CARRY_OUT
+#include "modem_lane.inc"
         carrier_phase += (uint32_t) carrier_phase_rate;     // dds_advancef() with the rate the baud left behind
     }
     }
@@ -915,35 +612,12 @@ void v29_bank_kernel(const V29Launch L)
         stf(VF_GDC, gdc0);
         stf(VF_GDC + 1, gdc1);
         stf(VF_BAUD_PHASE, baud_phase);
-        for (int i = 0;  i < kRrcLen;  i++)
-            stf(VF_RRC + i, rrc_at(i));
-        for (int i = 0;  i < kEqLen;  i++)
-        {
-            const float2 c = TAP(i);
-            stf(VF_EQ_COEFF + 2*i, c.x);
-            stf(VF_EQ_COEFF + 2*i + 1, c.y);
-        }
-        if (__any(eq_clear_pending))
-        {
-            if (eq_clear_pending)
-            {
-#pragma unroll
-                for (int i = 0;  i < kEqLen;  i++)
-                {
-                    xre[i] = 0.0f;
-                    xim[i] = 0.0f;
-                }
-                eq_clear_pending = false;
-            }
-        }
-#pragma unroll
-        for (int i = 0;  i < kEqLen;  i++)
-        {
-            int k = eq_step + i;
-            k = (k >= kEqLen)  ?  (k - kEqLen)  :  k;
-            stf(VF_EQ_BUF + 2*k, xre[i]);
-            stf(VF_EQ_BUF + 2*k + 1, xim[i]);
-        }
+#define LANE_PART LANE_LINES_STORE
+#include "modem_lane.inc"
+#define LANE_PART LANE_EQ_CLEAR
+#include "modem_lane.inc"
+#define LANE_PART LANE_EQ_STORE
+#include "modem_lane.inc"
         sti(VI_RRC_STEP, rrc_step);
         sti(VI_SCRAMBLE, (int32_t) scramble_reg);
         sti(VI_TRAIN_SCRAMBLE, training_scramble_reg);
@@ -973,7 +647,8 @@ void v29_bank_kernel(const V29Launch L)
     }
 }
 
-#undef RRC2
 #undef TAP
+#define LANE_PART LANE_END
+#include "modem_lane.inc"
 
 }   // namespace spg
