@@ -34,6 +34,13 @@
 
 namespace spg {
 
+// The block-end piece's rework (profiles/tone_block_end.md) sits behind a build switch so that a library can be built without it
+// and measured against one with it (make EXTRA=-DSPG_BLOCK_END_PARTS=0): bit 1, the two halves of the piece in the common
+// segment's layout (tone_fast.hpp: pairs_head_asm / pairs_tail_asm).  Two more parts were built, measured and taken out again.
+#ifndef SPG_BLOCK_END_PARTS
+#define SPG_BLOCK_END_PARTS 1
+#endif
+
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
 constexpr int kMaxBins = 64;            // banks of more than 16 bins run two lanes per channel, of more than 32 four (16 bins per lane)
@@ -76,7 +83,7 @@ struct ToneLaunch
     CadenceArgs cad;            // super-tone: cad.state != nullptr has the streaming kernel built with kToneCadence match
                                 // the cadences in its epilogue (cadence_dev.hpp)
     int wg0;                    // streaming kernels: the launch covers workgroups wg0 .. wg0 + wgn - 1 of the bank (wgn = 0: all of
-    int wgn;                    // them) -- a bank in queue mode is advanced by two launches on two streams (spangpu_api.hip)
+    int wgn;                    // them) -- a bank in queue mode is advanced by two launches on two streams (tone_rx.hip)
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -45,6 +45,14 @@ static inline int tone_fast_flags(const ToneLaunch &L)
     return kFastAligned | (L.lens  ?  kFastLens  :  0) | ((L.maxb > 2)  ?  kFastManyBlocks  :  0) | (L.cad.state  ?  kFastCadence  :  0);
 }
 
+// (the parts of the block-end piece's rework: SPG_BLOCK_END_PARTS, tone_dev.hpp)
+#if defined(SPG_TONE_FMA)
+constexpr bool kBeSplitLayout = false;                 // (the experiment keeps the split bodies it was measured with: tone_pairs_asm_fma.inc has no others)
+#else
+constexpr bool kBeSplitLayout = (SPG_BLOCK_END_PARTS & 1) != 0;
+#endif
+constexpr int kProbeBlockEnd = 1048576;             // ABL bit 20 (tools/probe2 be): stamps around the parts of a block end in the hot loop
+
 template <int LPC, int R, bool G711, int WPB>
 struct FastLds
 {
@@ -159,6 +167,46 @@ __device__ __forceinline__ void pairs_asm(f32x2 (&a)[NP], f32x2 (&b)[NP], float 
         SPG_PA_RUN(SPG_PAIRS_ASM, 4, SPG_PA_IN, SPG_PAIRS_ASM_CLOBBERS);
 #undef SPG_PA_IN
 }
+
+#if !defined(SPG_TONE_FMA)
+// The same two halves in the common segment's layout (kBeSplitLayout): [0, k1) with an exit test behind every pair, [k0, 16)
+// entered through a tree and run to the end with no test at all; either reads the piece as four whole chunks up front and has
+// the converts, the squares and the energy where the common body has them.  Against pairs_asm: one LDS read and one wait per
+// chunk and not per pair, no exit tests in the second half -- some sixty issue slots of a block end's piece.
+template <int NP, bool ENERGY>
+__device__ __forceinline__ void pairs_head_asm(f32x2 (&a)[NP], f32x2 (&b)[NP], float &energy, const f32x2 (&fac)[NP], uint32_t ad, int k1)
+{
+    static_assert(NP == 2  ||  NP == 3  ||  NP == 4, "pairs_head_asm: banks of 4, 6 or 8 bins per lane");
+    const uint32_t ad1 = ad ^ 16u;
+    const uint32_t ad2 = ad ^ 32u;
+    const uint32_t ad3 = ad ^ 48u;
+#define SPG_PA_IN SPG_PA_ADDR, [k1] "s"(k1)
+    if constexpr (NP == 2)
+        SPG_PA_RUN(SPG_PAIRS_HEAD_ASM, 2, SPG_PA_IN, SPG_PAIRS_SPLIT_ASM_CLOBBERS);
+    else if constexpr (NP == 3)
+        SPG_PA_RUN(SPG_PAIRS_HEAD_ASM, 3, SPG_PA_IN, SPG_PAIRS_SPLIT_ASM_CLOBBERS);
+    else
+        SPG_PA_RUN(SPG_PAIRS_HEAD_ASM, 4, SPG_PA_IN, SPG_PAIRS_SPLIT_ASM_CLOBBERS);
+#undef SPG_PA_IN
+}
+
+template <int NP, bool ENERGY>
+__device__ __forceinline__ void pairs_tail_asm(f32x2 (&a)[NP], f32x2 (&b)[NP], float &energy, const f32x2 (&fac)[NP], uint32_t ad, int k0)
+{
+    static_assert(NP == 2  ||  NP == 3  ||  NP == 4, "pairs_tail_asm: banks of 4, 6 or 8 bins per lane");
+    const uint32_t ad1 = ad ^ 16u;
+    const uint32_t ad2 = ad ^ 32u;
+    const uint32_t ad3 = ad ^ 48u;
+#define SPG_PA_IN SPG_PA_ADDR, [k0] "s"(k0)
+    if constexpr (NP == 2)
+        SPG_PA_RUN(SPG_PAIRS_TAIL_ASM, 2, SPG_PA_IN, SPG_PAIRS_SPLIT_ASM_CLOBBERS);
+    else if constexpr (NP == 3)
+        SPG_PA_RUN(SPG_PAIRS_TAIL_ASM, 3, SPG_PA_IN, SPG_PAIRS_SPLIT_ASM_CLOBBERS);
+    else
+        SPG_PA_RUN(SPG_PAIRS_TAIL_ASM, 4, SPG_PA_IN, SPG_PAIRS_SPLIT_ASM_CLOBBERS);
+#undef SPG_PA_IN
+}
+#endif
 
 // All sixteen sample pairs of a row piece, the common segment: the same operations with no way in or out between the pairs,
 // the piece read as four whole chunks up front.  An asm body and not C++ because of the block energy: its squares and adds are
@@ -284,7 +332,8 @@ __device__ __forceinline__ void tone_loader(const ToneLaunch &L, const int wg, c
 
 // The body of the streaming kernel for workgroup `wg` of the bank described by L.  Preconditions (the host checks
 // them and otherwise launches tone_bank_kernel): L.layout == 0, L.aligned16, L.samples > 0, and linear PCM unless
-// G711.  ABL is the tuning-probe knob of tools/probe.hip (bit 3: no recurrence, bit 4: no DMA, bit 5: timestamps, bit 10: no state traffic, bit 11: the general block-end decision only); the
+// G711.  ABL is the tuning-probe knob of tools/probe.hip (bit 3: no recurrence, bit 4: no DMA, bit 5: timestamps, bit 10: no state
+// traffic, bit 11: the general block-end decision only, bit 20 with bit 5: ticks per part of the hot loop's block-end piece); the
 // library instantiates ABL = 0 only.
 template <class Det, int LPC, int R, bool G711, bool NT, int WPB, int ABL = 0, bool LDR = false>
 __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg, char *lds_raw)
@@ -403,6 +452,37 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
             ts[k] = (long long) __builtin_readcyclecounter();
     };
     stamp(0);
+    // probe-only (kProbeBlockEnd): the parts of the hot loop's block-end piece, as sums of ticks over the block ends of the launch.
+    // Slots of the wave: 1 .. 5 = first body [0, p), finish(), decision and debounce, record hand-over, second body [p, 16);
+    // 6 = block ends counted; 7 = common segments (behind their barrier), 8 = how many.  The per-segment stamps are off then.
+    long long be_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long be_sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    auto be_stamp = [&](int k)
+    {
+        if constexpr ((ABL & kProbeBlockEnd) != 0)
+        {
+            __builtin_amdgcn_sched_barrier(0);
+            be_t[k] = (long long) __builtin_readcyclecounter();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    auto be_done = [&]()
+    {
+        if constexpr ((ABL & kProbeBlockEnd) != 0)
+        {
+            for (int k = 1;  k <= 5;  k++)
+                be_sum[k] += be_t[k] - be_t[k - 1];
+            be_sum[6]++;
+        }
+    };
+    auto be_common = [&]()
+    {
+        if constexpr ((ABL & kProbeBlockEnd) != 0)
+        {
+            be_sum[7] += be_t[7] - be_t[6];
+            be_sum[8]++;
+        }
+    };
 
     // ---- frame geometry (wave-uniform) -------------------------------------------------------------
     const unsigned rowbytes = (unsigned) L.samples*BPS;
@@ -648,6 +728,8 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
         float el[NBL];
         f32x2 esum;
         bk.finish(fac, el, &esum);
+        if constexpr (UNI)
+            be_stamp(2);
         float e[NB];
         if (LPC == 1)
         {
@@ -683,6 +765,8 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
         // The record words of the first two blocks of a call (all there are in a 160-sample frame) wait in registers
         // for the write-back: a store here would stand in the memory pipeline's queue with the sample loop behind it.
         if constexpr (UNI)
+            be_stamp(3);
+        if constexpr (UNI)
         {
             const int nbu = __builtin_amdgcn_readfirstlane(nb);
             if (nbu == 0)
@@ -701,6 +785,8 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
             else if (store)
                 *(uint32_t *) ((char *) (L.rec + (size_t) nb*nch) + ch4) = recw;
         }
+        if constexpr (UNI)
+            be_stamp(4);
         if ((ABL & kToneDigits)  &&  L.digits  &&  store)
             L.digits[(size_t) nb*nch + ch] = tone_digit_byte<Det::kDuration>(recw);
         nb++;
@@ -784,7 +870,8 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
                 {
                     pos += 4*SPC;
                     slot = (slot == R - 1)  ?  0  :  (slot + 1);
-                    stamp(3 + seg);
+                    if constexpr ((ABL & kProbeBlockEnd) == 0)
+                        stamp(3 + seg);
                     seg++;
                 };
                 for (  ;  ;  )
@@ -799,7 +886,10 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
                     for (bool more = common_next();  more;  more = common_next())
                     {
                         make_resident(seg, slot);
+                        be_stamp(6);
                         common_segment(rd0 + (uint32_t) slot*kSlot);
+                        be_stamp(7);
+                        be_common();
                         cs_s += 4*SPC;
                         take_acc += 4*SPC;
                         if constexpr (!kPairsAsm)
@@ -817,16 +907,33 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
                         break;
                     if constexpr (kPairsAsm)
                     {
-                        // pairs [0, p), the block end, pairs [p, 16) -- through two copies of the one asm body (pairs_asm above)
+                        // pairs [0, p), the block end, pairs [p, 16) -- the head and the tail of the common segment's body
+                        // (pairs_head_asm, pairs_tail_asm above; without kBeSplitLayout two copies of the one body of pairs_asm)
                         make_resident(seg, slot);
                         const uint32_t ad = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) char *) lds_raw + rd0 + (uint32_t) slot*kSlot;
                         float no_energy = 0.0f;
                         const int p = __builtin_amdgcn_readfirstlane(m >> 1);
-                        pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, 0, p);
+                        be_stamp(0);
+#if !defined(SPG_TONE_FMA)
+                        if constexpr (kBeSplitLayout)
+                            pairs_head_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, p);
+                        else
+#endif
+                            pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, 0, p);
+                        be_stamp(1);
                         take_acc += m;
-                        end_block(std::true_type());
+                        end_block(std::true_type());        // (stamps 2, 3, 4: after finish(), the decision, the record's hand-over)
                         if (p < 4*PPC)
-                            pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, p, 4*PPC);
+                        {
+#if !defined(SPG_TONE_FMA)
+                            if constexpr (kBeSplitLayout)
+                                pairs_tail_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, p);
+                            else
+#endif
+                                pairs_asm<NBL/2, Det::kEnergy>(bk.a, bk.b, Det::kEnergy  ?  energy  :  no_energy, fac, ad, p, 4*PPC);
+                        }
+                        be_stamp(5);
+                        be_done();
                         cs_s = 4*SPC - m;
                         take_acc += 4*SPC - m;
                         next_segment();
@@ -973,7 +1080,16 @@ __device__ __forceinline__ void tone_fast_body(const ToneLaunch &L, const int wg
         }
         pos += seglen;
         slot = (slot == R - 1)  ?  0  :  (slot + 1);
-        stamp(3 + seg);
+        if constexpr ((ABL & kProbeBlockEnd) == 0)
+            stamp(3 + seg);
+    }
+    if constexpr ((ABL & kProbeBlockEnd) != 0)
+    {
+        if ((ABL & 32)  &&  lane == 0)
+        {
+            for (int k = 1;  k <= 8;  k++)
+                ts[k] = be_sum[k];
+        }
     }
     if (L.force_end)
     {

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Writes spandsp_amd/csrc/tone_pairs_asm.inc: the sixteen sample pairs of one 64-byte row piece as ONE inline-asm body,
-in two forms (tone_fast.hpp): SPG_PAIRS_ASM_* can be entered at any pair and left after any pair (the segment that holds a
-block end); SPG_PAIRS_COMMON_ASM_* is the sixteen pair blocks straight through, with no entry tree and no exit tests, its
-samples fetched by four ds_read_b128 up front and waited for chunk by chunk (the common segment).  Written in C++ the
+in these forms (tone_fast.hpp): SPG_PAIRS_ASM_* can be entered at any pair and left after any pair (the segment that holds a
+block end, as it was first built: a read and an exit test per pair); SPG_PAIRS_COMMON_ASM_* is the sixteen pair blocks straight
+through, with no entry tree and no exit tests, its samples fetched by four ds_read_b128 up front and waited for chunk by chunk
+(the common segment); SPG_PAIRS_HEAD_ASM_* and SPG_PAIRS_TAIL_ASM_* are that common body left after a pair and entered at a
+pair (the two halves of the segment that holds a block end, as the library builds it; not in the v_pk_fma_f32 file).  Written in C++ the
 energy's squares and adds are pure operations that instruction selection sinks behind the last asm statement of the
 recurrence, one serial chain of thirty-two adds at the end of the segment (profiles/tone_energy_in_gaps.md); here they sit
 in the issue slots the recurrence leaves.
@@ -144,8 +146,10 @@ def body(np_, energy, fma=False):
     return L
 
 
-def common_body(np_, energy, fma=False):
-    """The common segment: all sixteen pairs, chunk j (pairs 4j .. 4j+3) read whole from %[adj] into v[112+4j:115+4j].
+def common_parts(np_, energy, fma=False):
+    """The common segment in the parts it is put together from: all sixteen pairs, chunk j (pairs 4j .. 4j+3) read whole from
+    %[adj] into v[112+4j:115+4j].  Returns (reads, lead_in, pairs): the four reads; lead_in[k], what the body has done for pair k
+    by the time it reaches it (its chunk waited for, its samples converted and squared); pairs[k], the pair itself.
 
     With no way in or out between the pairs, the work of a pair that is not the recurrence is spread one instruction at a time
     over the joints between the recurrence's groups (each group's first instruction waits for the first of the group before:
@@ -171,14 +175,18 @@ def common_body(np_, energy, fma=False):
         # before pair k's first convert, if it opens a chunk (LDS reads return in order)
         return ["s_waitcnt lgkmcnt(%d)" % (3 - k//4)] if k % 4 == 0 else []
 
-    L = []
-    L.append("s_waitcnt lgkmcnt(0)")                  # as above: from here on the counter counts the four reads alone
+    def lead_in(k):
+        out = ["s_waitcnt lgkmcnt(%d)" % (3 - k//4), cvt(k, 0), cvt(k, 1)]
+        if energy:
+            out.append("v_pk_mul_f32 %s, %s, %s" % (SQ, xp(k), xp(k)))
+        return out
+
+    reads = ["s_waitcnt lgkmcnt(0)"]                  # as above: from here on the counter counts the four reads alone
     for j in range(4):
-        L.append("ds_read_b128 v[%d:%d], %%[ad%d]" % (112 + 4*j, 115 + 4*j, j))
-    L += wait(0) + [cvt(0, 0), cvt(0, 1)]
-    if energy:
-        L.append("v_pk_mul_f32 %s, %s, %s" % (SQ, xp(0), xp(0)))
+        reads.append("ds_read_b128 v[%d:%d], %%[ad%d]" % (112 + 4*j, 115 + 4*j, j))
+    pairs = []
     for k in range(16):
+        L = []
         x = xp(k)
         nxt = k + 1 < 16
         add_lo = ["v_add_f32 %%[en], %%[en], %s" % SQL] if energy else []
@@ -195,38 +203,102 @@ def common_body(np_, energy, fma=False):
             L += add_hi
             L += ["v_pk_add_f32 %s, %s, %s op_sel:[0,1] op_sel_hi:[1,1]" % (b(i), T(i), x) for i in range(np_)]
             L += square
-            continue
-        L += ["v_pk_mul_f32 %s, %s, %s" % (T(i), f(i), b(i)) for i in range(np_)]
-        L += add_lo
-        L += ["v_pk_add_f32 %s, %s, %s neg_lo:[0,1] neg_hi:[0,1]" % (T(i), T(i), a(i)) for i in range(np_)]
-        L += cvt_lo
-        L += ["v_pk_add_f32 %s, %s, %s op_sel_hi:[1,0]" % (a(i), T(i), x) for i in range(np_)]
-        L += add_hi
-        L += ["v_pk_mul_f32 %s, %s, %s" % (T(i), f(i), a(i)) for i in range(np_)]
-        L += cvt_hi
-        L += ["v_pk_add_f32 %s, %s, %s neg_lo:[0,1] neg_hi:[0,1]" % (T(i), T(i), b(i)) for i in range(np_)]
-        L += square
-        L += ["v_pk_add_f32 %s, %s, %s op_sel:[0,1] op_sel_hi:[1,1]" % (b(i), T(i), x) for i in range(np_)]
+        else:
+            L += ["v_pk_mul_f32 %s, %s, %s" % (T(i), f(i), b(i)) for i in range(np_)]
+            L += add_lo
+            L += ["v_pk_add_f32 %s, %s, %s neg_lo:[0,1] neg_hi:[0,1]" % (T(i), T(i), a(i)) for i in range(np_)]
+            L += cvt_lo
+            L += ["v_pk_add_f32 %s, %s, %s op_sel_hi:[1,0]" % (a(i), T(i), x) for i in range(np_)]
+            L += add_hi
+            L += ["v_pk_mul_f32 %s, %s, %s" % (T(i), f(i), a(i)) for i in range(np_)]
+            L += cvt_hi
+            L += ["v_pk_add_f32 %s, %s, %s neg_lo:[0,1] neg_hi:[0,1]" % (T(i), T(i), b(i)) for i in range(np_)]
+            L += square
+            L += ["v_pk_add_f32 %s, %s, %s op_sel:[0,1] op_sel_hi:[1,1]" % (b(i), T(i), x) for i in range(np_)]
+        pairs.append(L)
+    return reads, [lead_in(k) for k in range(16)], pairs
+
+
+def common_body(np_, energy, fma=False):
+    reads, lead_in, pairs = common_parts(np_, energy, fma)
+    return reads + lead_in[0] + [l for p in pairs for l in p]
+
+
+def entry_tree():
+    """k0 in 0 .. 15 to the leaf of its pair (tail bodies)."""
+    L = []
+
+    def tree(lo, hi):
+        if lo == hi:
+            L.append("s_branch Le%%=_%d" % lo)
+            return
+        mid = (lo + hi + 1)//2
+        L.append("s_cmp_lt_u32 %%[k0], %d" % mid)
+        L.append("s_cbranch_scc1 Lt%%=_%d_%d" % (lo, mid - 1))
+        tree(mid, hi)
+        L.append("Lt%%=_%d_%d:" % (lo, mid - 1))
+        tree(lo, mid - 1)
+    tree(0, 15)
     return L
+
+
+def define(out, name, lines):
+    out.append("#define %s \\" % name)
+    for i, l in enumerate(lines):
+        out.append('    "%s\\n\\t"%s' % (l, " \\" if i + 1 < len(lines) else ""))
+
+
+def write_split(out):
+    """The common segment once more, pair by pair (SPG_PC_*), and put together three ways: whole (what SPG_PAIRS_COMMON_ASM_* is),
+    and as the two halves of the piece that holds a block end.  SPG_PAIRS_HEAD_ASM_* is pairs [0, k1): an exit test behind every
+    pair -- what is converted and squared a pair ahead by then lies in clobbered registers and is dropped.  SPG_PAIRS_TAIL_ASM_*
+    is pairs [k0, 16): the four reads, on their way while the entry tree is walked, a leaf per pair that does the pair's lead-in
+    and joins the body at it, and no exit test anywhere."""
+    define(out, "SPG_PC_READS", common_parts(2, 1)[0])
+    define(out, "SPG_PC_TREE", entry_tree())
+    for energy in (0, 1):
+        lead = common_parts(2, energy)[1]
+        for k in range(16):
+            define(out, "SPG_PC_E%d_IN%d" % (energy, k), lead[k])
+    for np_ in (2, 3, 4):
+        for energy in (0, 1):
+            pairs = common_parts(np_, energy)[2]
+            for k in range(16):
+                define(out, "SPG_PC_NP%d_E%d_P%d" % (np_, energy, k), pairs[k])
+    out.append("#define SPG_PC_P(n, e, k) SPG_PC_NP##n##_E##e##_P##k")
+    out.append('#define SPG_PC_OUT(k) "s_cmp_eq_u32 %[k1], " #k "\\n\\ts_cbranch_scc1 Lx%=\\n\\t"')
+    out.append('#define SPG_PC_LEAF(e, k) "Le%=_" #k ":\\n\\t" SPG_PC_E##e##_IN##k "s_branch Lp%=_" #k "\\n\\t"')
+    out.append('#define SPG_PC_AT(n, e, k) "Lp%=_" #k ":\\n\\t" SPG_PC_P(n, e, k)')
+    out.append("#define SPG_PC_HEAD(n, e) SPG_PC_READS SPG_PC_E##e##_IN0 \\")
+    out.append("    " + " ".join("SPG_PC_P(n, e, %d) SPG_PC_OUT(%d)" % (k, k + 1) for k in range(15)) + " \\")
+    out.append('    SPG_PC_P(n, e, 15) "Lx%=:\\n\\ts_waitcnt lgkmcnt(0)\\n\\t"')
+    out.append("#define SPG_PC_TAIL(n, e) SPG_PC_READS SPG_PC_TREE \\")
+    out.append("    " + " ".join("SPG_PC_LEAF(e, %d)" % k for k in range(15, 0, -1)) + ' "Le%=_0:\\n\\t" SPG_PC_E##e##_IN0 \\')
+    out.append("    " + " ".join("SPG_PC_AT(n, e, %d)" % k for k in range(16)))
+    out.append("#define SPG_PC_WHOLE(n, e) SPG_PC_READS SPG_PC_E##e##_IN0 " + " ".join("SPG_PC_P(n, e, %d)" % k for k in range(16)))
+    for np_ in (2, 3, 4):
+        for energy in (0, 1):
+            out.append("#define SPG_PAIRS_COMMON_ASM_NP%d_E%d SPG_PC_WHOLE(%d, %d)" % (np_, energy, np_, energy))
+            out.append("#define SPG_PAIRS_HEAD_ASM_NP%d_E%d SPG_PC_HEAD(%d, %d)" % (np_, energy, np_, energy))
+            out.append("#define SPG_PAIRS_TAIL_ASM_NP%d_E%d SPG_PC_TAIL(%d, %d)" % (np_, energy, np_, energy))
+    out.append('#define SPG_PAIRS_SPLIT_ASM_CLOBBERS "memory", "scc", ' + ", ".join('"v%d"' % r for r in range(100, 128)))
 
 
 def write(path, fma):
     out = []
-    out.append("// %s -- GENERATED by tools/gen_pairs_asm.py; do not edit.  See that file and tone_fast.hpp (pairs_asm)." % os.path.basename(path))
+    out.append("// %s -- GENERATED by tools/gen_pairs_asm.py; do not edit.  See that file and tone_fast.hpp (pairs_asm, pairs_common_asm, pairs_head_asm, pairs_tail_asm)." % os.path.basename(path))
     if fma:
         out.append("// The v_pk_fma_f32 form of the recurrence (fac*v2 - v1 fused: NOT the reference's roundings): only built with -DSPG_TONE_FMA.")
     for np_ in (2, 3, 4):
         for energy in (0, 1):
-            out.append("#define SPG_PAIRS_ASM_NP%d_E%d \\" % (np_, energy))
-            lines = body(np_, energy, fma)
-            for i, l in enumerate(lines):
-                out.append('    "%s\\n\\t"%s' % (l, " \\" if i + 1 < len(lines) else ""))
-    for np_ in (2, 3, 4):
-        for energy in (0, 1):
-            out.append("#define SPG_PAIRS_COMMON_ASM_NP%d_E%d \\" % (np_, energy))
-            lines = common_body(np_, energy, fma)
-            for i, l in enumerate(lines):
-                out.append('    "%s\\n\\t"%s' % (l, " \\" if i + 1 < len(lines) else ""))
+            define(out, "SPG_PAIRS_ASM_NP%d_E%d" % (np_, energy), body(np_, energy, fma))
+    if fma:
+        # (the experiment keeps the split bodies it was measured with: tone_fast.hpp builds no head and tail under SPG_TONE_FMA)
+        for np_ in (2, 3, 4):
+            for energy in (0, 1):
+                define(out, "SPG_PAIRS_COMMON_ASM_NP%d_E%d" % (np_, energy), common_body(np_, energy, fma))
+    else:
+        write_split(out)
     out.append('#define SPG_PAIRS_ASM_CLOBBERS "memory", "scc", ' + ", ".join('"v%d"' % r for r in range(100, 116)))
     out.append('#define SPG_PAIRS_COMMON_ASM_CLOBBERS "memory", ' + ", ".join('"v%d"' % r for r in range(100, 128)))
     with open(path, "w") as fh:

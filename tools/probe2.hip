@@ -451,6 +451,68 @@ static void sweep_r4_long(int n_ch)
     free_rig(r);
 }
 
+// The parts of the hot loop's block-end piece (kernels built with ABL 32 + kProbeBlockEnd keep, per wave, the ticks each part
+// took summed over the launch's block ends: tone_fast.hpp, be_stamp): per part the minimum, mean and maximum over the waves of
+// the last launch, per block end; beside them a common segment between the same kind of stamps.  Stamps cost a wave about a
+// tenth of its cycles: the parts are to be compared with each other, not with a launch without stamps.
+static void sweep_block_end(int n_ch, int samples, int reps)
+{
+    typedef DtmfDet<false> D;
+    constexpr int ABL = 32 + kProbeBlockEnd;
+    Rig r = make_rig<D>(n_ch, samples, 32, 102, false);
+    printf("---- block end: DTMF, %d channels x %d samples, loader wave (SPG_BLOCK_END_PARTS = %d) ----\n", n_ch, samples, (int) SPG_BLOCK_END_PARTS);
+    const int waves = (n_ch + kWave - 1)/kWave;
+    const int blocks = (waves + 3)/4;
+    const unsigned long long want = run_new<D, 1, 2, false, 4, 0, true>("product", r, 102, false, reps);
+    reset_rig(r, false, 102);
+    int f = 0;
+    auto go = [&] {
+        r.L.amp = r.amp + (size_t) (f % r.n_frames)*r.frame_elems;
+        f++;
+        launch_tone_fast<D, 1, 2, false, false, 4, ABL, true>(r.L, blocks, g_stream);
+    };
+    go(); go(); go();
+    CK(hipDeviceSynchronize());
+    if (digest(r) != want)
+        printf("   !!! the stamped kernel differs from the product\n");
+    const float ms = time_ms(go, reps);
+    CK(hipDeviceSynchronize());
+    printf("stamped: %8.2f us a launch\n", ms*1e3);
+    std::vector<long long> t((size_t) waves*16);
+    CK(hipMemcpy(t.data(), r.d_ts, t.size()*sizeof(long long), hipMemcpyDeviceToHost));
+    const char *names[8] = {"", "first body [0, p)", "finish()", "decision and debounce", "record hand-over", "second body [p, 16)",
+                            "the five together", "a common segment"};
+    for (int k = 1;  k <= 7;  k++)
+    {
+        double acc = 0;
+        double mx = 0, mn = 1e30;
+        int cnt = 0;
+        for (int w = 0;  w < waves;  w++)
+        {
+            const long long *tw = &t[(size_t) w*16];
+            const long long n = (k == 7)  ?  tw[8]  :  tw[6];
+            if (n <= 0)
+                continue;
+            long long sum = (k == 7)  ?  tw[7]  :  (k == 6)  ?  (tw[1] + tw[2] + tw[3] + tw[4] + tw[5])  :  tw[k];
+            const double v = (double) sum/(double) n;
+            acc += v;
+            mx = std::max(mx, v);
+            mn = std::min(mn, v);
+            cnt++;
+        }
+        if (cnt)
+            printf("   %-24s min %7.0f  mean %7.0f  max %7.0f ticks   (%d waves)\n", names[k], mn, acc/cnt, mx, cnt);
+    }
+    double be = 0, cs = 0;
+    for (int w = 0;  w < waves;  w++)
+    {
+        be += (double) t[(size_t) w*16 + 6];
+        cs += (double) t[(size_t) w*16 + 8];
+    }
+    printf("   block ends per wave in the last launch %.2f, common segments %.2f\n", be/waves, cs/waves);
+    free_rig(r);
+}
+
 // Round 5: what do the two record rows' stores cost the end of a launch?  (ABL bit 18: not stored.)  Variants taken in turn.
 static void ab_rec(int n_ch, int n_frames, int reps, int rounds)
 {
@@ -509,6 +571,13 @@ int main(int argc, char **argv)
         sweep_r4(65536, 64, 300);
         sweep_r4(131072, 32, 200);
         sweep_r4(1048576, 6, 30);
+        return 0;
+    }
+    if (argc > 1  &&  strcmp(argv[1], "be") == 0)
+    {
+        CK(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
+        sweep_block_end(65536, 160, 200);
+        sweep_block_end(65536, 320, 100);
         return 0;
     }
     if (argc > 1  &&  strcmp(argv[1], "rec") == 0)
