@@ -1776,6 +1776,56 @@ SPANGPU_API int spangpu_gsm0610_state_words(const spangpu_gsm0610_t *bank);
 SPANGPU_API int spangpu_gsm0610_get_state(spangpu_gsm0610_t *bank, int channel, int32_t *words);
 SPANGPU_API int spangpu_gsm0610_set_state(spangpu_gsm0610_t *bank, int channel, const int32_t *words);
 
+/* ---- Packet loss concealment banks (csrc/plc_api.hip, csrc/plc_dev.hpp) ------------------------
+ * N packet loss concealers, one lane per line: plc_rx() on the rows that were heard, plc_fillin() on the rows that were not,
+ * in place, mixed in any way within a call.  Behind a decoder bank the rows never leave the device.
+ *
+ *   spangpu_plc_create()           plc_init(NULL) x N                                              src/plc.c:261-272
+ *   spangpu_plc_run()              plc_rx(s, amp, len) or plc_fillin(s, amp, len), per line        src/plc.c:125-258
+ *   spangpu_plc_conceal()          the same, chosen by a decoder bank's counts on the device
+ *   spangpu_plc_restart()          plc_init(s) on one line
+ *
+ * Rows are int16_t samples at 8 kHz, one row a line, amp_stride_bytes apart.  SPANGPU_MEM_DEVICE: the base and the stride are
+ * multiples of 16 bytes and the stride holds max_samples rounded up to 8 samples.  SPANGPU_MEM_HOST: any stride that holds
+ * max_samples; the rows are copied in and back out and the call returns when they are back.  max_samples is 0 .. 2^24.
+ *
+ * spangpu_plc_run(): lens[c] (host, 0 .. max_samples; NULL: max_samples for all) is the line's len; lost[c] (host; NULL: nobody)
+ * other than 0 makes the call plc_fillin(), 0 plc_rx().  spangpu_plc_conceal(): counts_dev[c] (device memory: a decoder
+ * bank's spangpu_*_counts_dev(), samples per line of its last call) above 0 is a line heard for that many samples, max_samples
+ * at the most; at 0 the line is filled in for fill_lens[c] samples (host, 0 .. max_samples; NULL: fill_samples for all).  The
+ * call reads no count on the host, and waits for nothing unless fill_lens differ from one another and from the last call's.
+ * With the bank on the decoder's stream (set_stream), a decode without counts_out followed by conceal is one queue.
+ * Bad arguments are SPANGPU_ERR_BAD_ARG before anything is queued.
+ *
+ * A length of 0 sits the line out: nothing of its state or row changes.  One deviation follows: the reference's
+ * plc_rx(s, amp, 0) clears missing_samples (and with it ends the gap without an overlap); here a line that brings nothing has
+ * not been heard, and its gap goes on.
+ * Writes.  A heard line's row changes nowhere but in its first min(pitch >> 2, len) samples, and only where samples were
+ * missing before it.  A filled-in line's row is written in 16-byte chunks, zeros from its length to the next 16-byte boundary;
+ * nothing beyond that.
+ *
+ * State words, in the order of the reference's fields (src/spandsp/private/plc.h): missing_samples, pitch_offset, pitch,
+ * pitchbuf[0..119] as float bit patterns, history[0..279] sign-extended and as the reference's ring has them, buf_ptr (404).
+ * set_state moves a stream to another line; words no plc_state_t could hold are refused: a buf_ptr outside 0..280 (280 is
+ * what an append that exactly fills the ring leaves in the reference, and get_state reports it), a history word outside
+ * int16_t, negative missing_samples, missing_samples above 0 with a pitch outside 40..120, a pitch_offset outside
+ * 0 .. max(pitch, 1) - 1. */
+typedef struct spangpu_plc_s spangpu_plc_t;
+
+SPANGPU_API int spangpu_plc_create(spangpu_plc_t **bank, int device, int n_channels);
+SPANGPU_API void spangpu_plc_destroy(spangpu_plc_t *bank);
+SPANGPU_API int spangpu_plc_channels(const spangpu_plc_t *bank);
+SPANGPU_API int spangpu_plc_set_stream(spangpu_plc_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_plc_sync(spangpu_plc_t *bank);
+SPANGPU_API int spangpu_plc_run(spangpu_plc_t *bank, void *amp, int amp_mem_kind, long long amp_stride_bytes, const int32_t *lens,
+                                const int32_t *lost, int max_samples);
+SPANGPU_API int spangpu_plc_conceal(spangpu_plc_t *bank, void *amp_dev, long long amp_stride_bytes, const int32_t *counts_dev,
+                                    const int32_t *fill_lens, int fill_samples, int max_samples);
+SPANGPU_API int spangpu_plc_restart(spangpu_plc_t *bank, int channel);
+SPANGPU_API int spangpu_plc_state_words(const spangpu_plc_t *bank);
+SPANGPU_API int spangpu_plc_get_state(spangpu_plc_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_plc_set_state(spangpu_plc_t *bank, int channel, const int32_t *words);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -1109,6 +1109,32 @@ SPANGPU_GSM0610_API int gsm0610_unpack_none(gsm0610_frame_t *s, const uint8_t c[
 SPANGPU_GSM0610_API int gsm0610_unpack_wav49(gsm0610_frame_t *s, const uint8_t c[65]);
 SPANGPU_GSM0610_API int gsm0610_unpack_voip(gsm0610_frame_t *s, const uint8_t c[33]);
 
+/* ---- Packet loss concealment (csrc/shim_plc.c) -----------------------------------------------------------------------
+ * Reference declarations being replaced:
+ *   plc_rx, plc_fillin, plc_init, plc_release, plc_free                     src/spandsp/plc.h:125-149  src/plc.c:125-288
+ * An object is a one-line concealment bank (spangpu.h, "Packet loss concealment banks"): plumbing for a caller that moves
+ * over one call at a time; the path for scale is the bank.  plc_init() returns NULL without a GPU.  `s` may be the caller's
+ * own storage (this header has the whole struct).  plc_rx() and plc_fillin() return len, and 0 on a NULL object; a len of 0
+ * changes nothing (the reference's plc_rx() clears missing_samples there).  These objects are not members of channel groups.
+ * These names are declared with a macro of their own, as the GSM 06.10 ones are: tests/test_plc.py holds them against
+ * src/spandsp/plc.h.
+ */
+#define SPANGPU_PLC_API SPANGPU_API
+
+typedef struct plc_state_s plc_state_t;
+
+struct plc_state_s
+{
+    spangpu_plc_t *bank;
+    spangpu_object_t obj;
+};
+
+SPANGPU_PLC_API int plc_rx(plc_state_t *s, int16_t amp[], int len);
+SPANGPU_PLC_API int plc_fillin(plc_state_t *s, int16_t amp[], int len);
+SPANGPU_PLC_API plc_state_t *plc_init(plc_state_t *s);
+SPANGPU_PLC_API int plc_release(plc_state_t *s);
+SPANGPU_PLC_API int plc_free(plc_state_t *s);
+
 #if defined(__cplusplus)
 }
 #endif

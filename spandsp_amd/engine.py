@@ -533,6 +533,17 @@ def lib():
             "spangpu_gsm0610_state_words": (ci, [vp]),
             "spangpu_gsm0610_get_state": (ci, [vp, ci, vp]),
             "spangpu_gsm0610_set_state": (ci, [vp, ci, vp]),
+            "spangpu_plc_create": (ci, [C.POINTER(vp), ci, ci]),
+            "spangpu_plc_destroy": (None, [vp]),
+            "spangpu_plc_channels": (ci, [vp]),
+            "spangpu_plc_set_stream": (ci, [vp, vp]),
+            "spangpu_plc_sync": (ci, [vp]),
+            "spangpu_plc_run": (ci, [vp, vp, ci, ll, vp, vp, ci]),
+            "spangpu_plc_conceal": (ci, [vp, vp, ll, vp, vp, ci, ci]),
+            "spangpu_plc_restart": (ci, [vp, ci]),
+            "spangpu_plc_state_words": (ci, [vp]),
+            "spangpu_plc_get_state": (ci, [vp, ci, vp]),
+            "spangpu_plc_set_state": (ci, [vp, ci, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -2368,6 +2379,60 @@ class Gsm0610Bank(_CodecBank):
 
     def restart(self, channel, packing):
         _check(lib().spangpu_gsm0610_restart(self.h, channel, packing))
+
+
+# ---- packet loss concealment banks (include/spangpu.h "Packet loss concealment banks") -----
+class PlcBank(_Bank):
+    """N packet loss concealers (plc_rx / plc_fillin), one per line, state in HBM.  Rows are int16 samples, worked on in
+    place: a heard line's row is smoothed into the end of a gap, a lost line's row is filled in."""
+    _prefix = "plc"
+
+    def __init__(self, n_channels, device=0):
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_plc_create(C.byref(self.h), device, n_channels))
+        self.words = lib().spangpu_plc_state_words(self.h)
+
+    def _per_line(self, v):
+        if v is None:
+            return None, None
+        v = np.ascontiguousarray(v, np.int32)
+        assert v.shape == (self.n,)
+        return v, v.ctypes.data
+
+    def run_host(self, amp, samples, lens=None, lost=None):
+        """amp: [n][>= samples] int16 rows, changed in place (a copy is made of anything else).  Returns the rows."""
+        buf = amp if (isinstance(amp, np.ndarray) and amp.dtype == np.int16 and amp.flags.c_contiguous and amp.flags.writeable) \
+            else np.array(amp, np.int16, order="C", copy=True)
+        assert buf.ndim == 2 and buf.shape[0] == self.n
+        lens, lp = self._per_line(lens)
+        lost, sp = self._per_line(lost)
+        _check(lib().spangpu_plc_run(self.h, buf.ctypes.data, MEM_HOST, buf.strides[0], lp, sp, samples))
+        return buf
+
+    def run_device(self, amp_ptr, amp_stride, samples, lens=None, lost=None):
+        """Rows in device memory (16-byte aligned, the stride in bytes and a multiple of 16)."""
+        lens, lp = self._per_line(lens)
+        lost, sp = self._per_line(lost)
+        _check(lib().spangpu_plc_run(self.h, amp_ptr, MEM_DEVICE, amp_stride, lp, sp, samples))
+
+    def conceal(self, amp_ptr, amp_stride, counts_ptr, max_samples, fill_samples=0, fill_lens=None):
+        """Behind a decoder bank: counts_ptr is its counts_dev(); a line it gave nothing is filled in."""
+        fill_lens, fp = self._per_line(fill_lens)
+        _check(lib().spangpu_plc_conceal(self.h, amp_ptr, amp_stride, counts_ptr, fp, fill_samples, max_samples))
+
+    def restart(self, channel):
+        _check(lib().spangpu_plc_restart(self.h, channel))
+
+    def get_state(self, channel):
+        w = np.zeros(self.words, np.int32)
+        _check(lib().spangpu_plc_get_state(self.h, channel, w.ctypes.data))
+        return w
+
+    def set_state(self, channel, w):
+        w = np.ascontiguousarray(w, np.int32)
+        assert len(w) == self.words
+        _check(lib().spangpu_plc_set_state(self.h, channel, w.ctypes.data))
 
 
 # ---- HDLC framing banks (include/spangpu.h "HDLC framing banks") ---------------------------

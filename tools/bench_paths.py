@@ -2072,6 +2072,139 @@ def bench_gsm0610(args, dev, stream):
         "cpu_baseline_reason": "gsm0610_*.c are not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
 
 
+def bench_plc(args, dev, stream):
+    """Packet loss concealment banks: spangpu_plc_conceal() on 65 536 lines x 160 samples in HBM, the lost lines chosen by a row
+    of counts in device memory as a decoder bank leaves one, each launch between its own pair of events.  Three ticks, timed
+    separately: (a) nobody lost; (b) 2 % of the lines starting a gap, at uniformly random lanes, and another 2 % in the second
+    tick of theirs; (c) every line starting a gap.  Between two timed ticks of (b) and (c) the untimed ticks that put the
+    lines back: everybody heard (which ends the gaps), and for (b) the tick that starts the gaps of the 2 % that go on.  In
+    the same command, alternating with them, --repeats times: the GSM 06.10 VoIP decode launch such a tick follows, and the
+    copies of the 65 536 x 160 int16 rows down and up that a host-side plc_fillin() would need.  A 72-line bank is held against
+    the committed fixture first."""
+    import gsm0610_lines as GL
+    import plc_lines as PL
+    from spandsp_amd import engine
+    n_ch = args.channels or 65536
+    repeats = 3
+    vp = ctypes.c_void_p
+    # ---- the spot check: 72 lines, the nine fixture lines, the whole schedule ----
+    cases = PL.sched_cases(PL.load())
+    bank = engine.PlcBank(72)
+    checked = 0
+    for k, (lost, n) in enumerate(PL.SCHEDULE):
+        rows = np.stack([np.pad(cases[c % 9].calls[k][2], (0, 320 - n)) for c in range(72)]).astype(np.int16)
+        bank.run_host(rows, n, lost=np.full(72, lost, np.int32))
+        for c in range(72):
+            assert np.array_equal(rows[c, :n], cases[c % 9].calls[k][3]), ("plc", c, k)
+            checked += 1
+    assert all(np.array_equal(bank.get_state(c), cases[c % 9].calls[-1][4]) for c in range(72))
+    bank.close()
+
+    the_lines = PL.lines()
+    idx = np.arange(n_ch)
+    nf = 8
+    src = np.stack([ln[:nf*FRAME].reshape(nf, FRAME) for ln in the_lines])                              # [9][nf][160]
+    frames = torch.tensor(src[idx % 9], device=dev).permute(1, 0, 2).contiguous()                       # [nf][n_ch][160]
+    rng = np.random.RandomState(20)
+    pick = rng.permutation(n_ch)
+    k = max(1, n_ch//50)
+    first, second = pick[:k], pick[k:2*k]
+
+    def counts_of(lost_lines):
+        c = np.full(n_ch, FRAME, np.int32)
+        c[lost_lines] = 0
+        return torch.tensor(c, device=dev)
+    heard_all, lost_all = counts_of([]), counts_of(idx)
+    lost_second, lost_both = counts_of(second), counts_of(np.concatenate([first, second]))
+
+    def run_plc():
+        bank = engine.PlcBank(n_ch)
+        bank.set_stream(vp(stream.cuda_stream))
+        rows = torch.zeros(n_ch, FRAME, dtype=torch.int16, device=dev)
+        state = {"f": 0}
+
+        def tick(counts, keep=None):
+            rows.copy_(frames[state["f"] % nf])
+            state["f"] += 1
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record(stream)
+            bank.conceal(vp(rows.data_ptr()), 2*FRAME, vp(counts.data_ptr()), FRAME, fill_samples=FRAME)
+            e[1].record(stream)
+            if keep is not None:
+                keep.append(e)
+        cycles = {"a_nobody_lost": [(heard_all, True)],
+                  "b_2pc_starting_2pc_continuing": [(lost_second, False), (lost_both, True), (heard_all, False)],
+                  "c_everyone_starting": [(lost_all, True), (heard_all, False)]}
+        out = {}
+        for name, cycle in cycles.items():
+            for _ in range(3):
+                tick(heard_all)
+            for _ in range(max(args.warmup, 5)):
+                for counts, _ in cycle:
+                    tick(counts)
+            kept = []
+            for _ in range(max(args.steps, 100)//(1 if name.startswith("a") else 2)):
+                for counts, timed in cycle:
+                    tick(counts, kept if timed else None)
+            torch.cuda.synchronize()
+            us = [a.elapsed_time(b)*1e3 for a, b in kept]
+            out[name] = {"launches": len(us), "avg_launch_us": sum(us)/len(us), "min_launch_us": min(us)}
+        # what (b) left: the gaps are over and every line has heard its last tick
+        w = bank.get_state(int(first[0]))
+        assert w[PL.W_MISSING] == 0 and 40 <= w[PL.W_PITCH] <= 120
+        bank.close()
+        return out
+
+    def run_decode():
+        enc, dec = engine.Gsm0610Bank(n_ch, engine.GSM0610_ENCODER, [GL.VOIP]), engine.Gsm0610Bank(n_ch, engine.GSM0610_DECODER, [GL.VOIP])
+        for b in (enc, dec):
+            b.set_stream(vp(stream.cuda_stream))
+        codes = torch.zeros(nf, n_ch, 48, dtype=torch.uint8, device=dev)
+        out = torch.zeros(n_ch, FRAME, dtype=torch.int16, device=dev)
+        for f in range(nf):
+            enc.encode_device(vp(frames[f].data_ptr()), 2*FRAME, FRAME, vp(codes[f].data_ptr()), 48)
+        kept = []
+        for i in range(max(args.warmup, 5) + max(args.steps, 100)):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record(stream)
+            dec.decode_device(vp(codes[i % nf].data_ptr()), 48, 33, vp(out.data_ptr()), 2*FRAME)
+            e[1].record(stream)
+            if i >= max(args.warmup, 5):
+                kept.append(e)
+        torch.cuda.synchronize()
+        us = [a.elapsed_time(b)*1e3 for a, b in kept]
+        enc.close()
+        dec.close()
+        return {"launches": len(us), "avg_launch_us": sum(us)/len(us), "min_launch_us": min(us)}
+
+    runs = {"plc": [], "gsm0610_voip_decode": [], "h2d_ms": [], "d2h_ms": []}
+    for _ in range(repeats):
+        runs["plc"].append(run_plc())
+        runs["gsm0610_voip_decode"].append(run_decode())
+        runs["d2h_ms"].append(copy_alone_ms(n_ch*FRAME*2, "d2h", dev))
+        runs["h2d_ms"].append(copy_alone_ms(n_ch*FRAME*2, "h2d", dev))
+
+    def spread(v):
+        return {"avg_launch_us_per_run": v, "min": min(v), "max": max(v)}
+    ticks = {name: spread([r[name]["avg_launch_us"] for r in runs["plc"]]) for name in runs["plc"][0]}
+    a = ticks["a_nobody_lost"]["min"]
+    return {
+        "metric": "Msamples/s of a packet loss concealment bank on a tick with nobody lost (spangpu_plc_conceal on rows in HBM)",
+        "value": n_ch*FRAME/a, "unit": "Msamples/s", "realtime_channels": n_ch*FRAME/(a*1e-6)/8000.0, "n_gpus": 1,
+        "steps": runs["plc"][0]["a_nobody_lost"]["launches"], "warmup": max(args.warmup, 5), "ms_per_step": a*1e-3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int16 / float32", "data": "synthetic",
+        "config": {"workload": "packet loss concealment bank, %d lines x 160 samples" % n_ch, "channels_per_gpu": n_ch, "repeats": repeats,
+                   "lines_starting_in_b": int(len(first)), "lines_continuing_in_b": int(len(second)), "spot_checked_against_fixture": checked},
+        "kernels": {"plc": ticks, "plc_runs": runs["plc"],
+                    "search_under_divergence_us_b_minus_a": ticks["b_2pc_starting_2pc_continuing"]["min"] - a,
+                    "gsm0610_voip_decode": spread([r["avg_launch_us"] for r in runs["gsm0610_voip_decode"]])},
+        "yardsticks": {"d2h_copy_of_int16_rows_us_per_run": [x*1e3 for x in runs["d2h_ms"]],
+                       "h2d_copy_of_int16_rows_us_per_run": [x*1e3 for x in runs["h2d_ms"]]},
+        "roofline": None,
+        "cpu_baseline": None,
+        "cpu_baseline_reason": "plc.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
+
+
 def bench_hdlc(args, dev, stream):
     """An HDLC sender bank producing 192 bits per line and tick (what V.29 9600 takes) into HBM, and an HDLC receiver bank
     framing 192 events per line and tick from HBM: hdlc_tx_get_bit() and hdlc_rx_put_bit() of every line, timed separately.
@@ -2407,7 +2540,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722", "gsm0610"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722", "gsm0610", "plc"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--rate", type=int, choices=[16000, 24000, 32000, 40000, 48000, 56000, 64000], default=None,
                     help="g726: the bit rate of the uniform run (32000); g722: the same (64000)")
@@ -2498,6 +2631,10 @@ def main():
     if args.workload == "gsm0610":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         emit(bench_gsm0610(args, dev, stream), "gsm0610", args.channels or None)
+        return
+    if args.workload == "plc":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        emit(bench_plc(args, dev, stream), "plc", args.channels or None)
         return
     if args.workload == "fax_fe":
         emit(bench_fax_fe(args, dev, stream), "fax_fe", args.channels or None)
