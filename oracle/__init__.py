@@ -9,6 +9,9 @@ package; only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 * ``oracle.ref``       -- ctypes binding of ``oracle/_ref/libspandsp_ref.so`` (the
   real reference compiled from /root/reference by ``oracle/Makefile``), when
   that file exists.
+* ``oracle.ref_codecs`` -- ctypes binding of ``oracle/_ref/libspandsp_codecs_ref.so`` (the
+  reference's G.726, G.722, GSM 06.10 and packet loss concealment modules behind batch
+  drivers, for the codec sweep), when that file exists.
 """
 import os
 import subprocess
