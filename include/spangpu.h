@@ -1826,6 +1826,97 @@ SPANGPU_API int spangpu_plc_state_words(const spangpu_plc_t *bank);
 SPANGPU_API int spangpu_plc_get_state(spangpu_plc_t *bank, int channel, int32_t *words);
 SPANGPU_API int spangpu_plc_set_state(spangpu_plc_t *bank, int channel, const int32_t *words);
 
+/* ---- IMA ADPCM codec banks (csrc/adpcm_api.hip, csrc/adpcm_dev.hpp) ---------------------------
+ * N IMA ADPCM codecs, one lane per channel, each with a variant (SPANGPU_IMA_ADPCM_IMA4, _DVI4 or _VDVI) and a chunk size
+ * of its own; variants[] and chunk_sizes[] (n entries each) are cycled over the channels.  A variant outside the three is
+ * SPANGPU_ERR_BAD_ARG.  Only whether chunk_size is 0 matters, as in the reference: at 0 every encode call begins with a
+ * 4-byte header and every decode call reads one; otherwise no header is ever written or read.
+ *
+ *   spangpu_ima_adpcm_create()         ima_adpcm_init(NULL, variant, chunk_size) x N             src/ima_adpcm.c:280-295
+ *   spangpu_ima_adpcm_encode()         ima_adpcm_encode(s, ima_data, amp, len) x N               src/ima_adpcm.c:426-508
+ *   spangpu_ima_adpcm_decode()         ima_adpcm_decode(s, amp, ima_data, ima_bytes) x N         src/ima_adpcm.c:310-424
+ *   spangpu_ima_adpcm_restart()        ima_adpcm_init(s, variant, chunk_size) on one channel
+ *
+ * Rows, lengths, alignment and counts are the G.726 banks' (above), with int16_t PCM rows: a code row must hold
+ * spangpu_ima_adpcm_encode_capacity(bank, max_samples) bytes, a decoder's PCM row spangpu_ima_adpcm_decode_capacity(bank,
+ * max_bytes) samples (a VDVI channel makes up to 4 samples of a byte).  Rows in device memory are read and written in
+ * aligned 8-byte words inside the 16-byte chunks the alignment rule describes.
+ * Where the reference reads outside its arguments the bank does not:
+ *   - a length of 0 changes nothing and counts 0 (the reference's IMA4 encoder reads amp[0], its DVI4 and VDVI encoders
+ *     write a bare header);
+ *   - a decode call of fewer than 4 bytes on a channel with chunk_size == 0 produces nothing and leaves the state alone
+ *     (the reference reads the header beyond the data);
+ *   - a header's step_index above 88 is taken as 88 (the reference reads past its table).
+ * State words, in the order of the reference's fields: variant, chunk_size, last, step_index, ima_byte, bits (6).
+ * set_state moves a stream, its configuration included, to another channel; words no call could have left (a variant
+ * outside the three, last outside int16_t, step_index outside 0..88, ima_byte outside 16 bits, negative bits) are refused. */
+#define SPANGPU_IMA_ADPCM_IMA4              0
+#define SPANGPU_IMA_ADPCM_DVI4              1
+#define SPANGPU_IMA_ADPCM_VDVI              2
+
+typedef struct spangpu_ima_adpcm_s spangpu_ima_adpcm_t;
+
+SPANGPU_API int spangpu_ima_adpcm_create(spangpu_ima_adpcm_t **bank, int device, int n_channels, const int32_t *variants,
+                                         const int32_t *chunk_sizes, int n);
+SPANGPU_API void spangpu_ima_adpcm_destroy(spangpu_ima_adpcm_t *bank);
+SPANGPU_API int spangpu_ima_adpcm_channels(const spangpu_ima_adpcm_t *bank);
+SPANGPU_API int spangpu_ima_adpcm_set_stream(spangpu_ima_adpcm_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_ima_adpcm_sync(spangpu_ima_adpcm_t *bank);
+SPANGPU_API int spangpu_ima_adpcm_encode(spangpu_ima_adpcm_t *bank, const void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                         const int32_t *lens, int max_samples, uint8_t *codes, int codes_mem_kind,
+                                         long long codes_stride_bytes, int32_t *bytes_out);
+SPANGPU_API int spangpu_ima_adpcm_decode(spangpu_ima_adpcm_t *bank, const uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes,
+                                         const int32_t *lens, int max_bytes, void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                         int32_t *samples_out);
+/* bytes (samples) a row must hold for the worst channel of the bank: header, carried nibble and pad octet included */
+SPANGPU_API long long spangpu_ima_adpcm_encode_capacity(const spangpu_ima_adpcm_t *bank, int samples);
+SPANGPU_API long long spangpu_ima_adpcm_decode_capacity(const spangpu_ima_adpcm_t *bank, int bytes);
+SPANGPU_API const int32_t *spangpu_ima_adpcm_counts_dev(const spangpu_ima_adpcm_t *bank);
+SPANGPU_API int spangpu_ima_adpcm_restart(spangpu_ima_adpcm_t *bank, int channel, int variant, int chunk_size);
+SPANGPU_API int spangpu_ima_adpcm_state_words(const spangpu_ima_adpcm_t *bank);
+SPANGPU_API int spangpu_ima_adpcm_get_state(spangpu_ima_adpcm_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_ima_adpcm_set_state(spangpu_ima_adpcm_t *bank, int channel, const int32_t *words);
+
+/* ---- OKI ADPCM codec banks (csrc/adpcm_api.hip, csrc/adpcm_dev.hpp) ---------------------------
+ * N OKI (Dialogic "VOX") ADPCM codecs, one lane per channel, each with a bit rate of its own: 32000, or 24000 with the
+ * reference's 6 kHz <-> 8 kHz rate converter in front of the coder and behind the decoder.  bit_rates[] (n entries) is cycled
+ * over the channels; any other rate is SPANGPU_ERR_BAD_ARG, as oki_adpcm_init() returns NULL for it.
+ *
+ *   spangpu_oki_adpcm_create()         oki_adpcm_init(NULL, bit_rate) x N                        src/oki_adpcm.c:244-257
+ *   spangpu_oki_adpcm_encode()         oki_adpcm_encode(s, oki_data, amp, len) x N               src/oki_adpcm.c:326-384
+ *   spangpu_oki_adpcm_decode()         oki_adpcm_decode(s, amp, oki_data, oki_bytes) x N         src/oki_adpcm.c:273-323
+ *   spangpu_oki_adpcm_restart()        oki_adpcm_init(s, bit_rate) on one channel
+ *
+ * Rows, lengths, alignment and counts are the IMA banks' (above).  A length of 0 changes nothing and counts 0 (the
+ * reference's 24 kbit/s encoder reads amp[0]).
+ * Narrowing.  The 24 kbit/s paths convert a binary32 sum to int16_t, and the sum does leave the int16_t range (on random
+ * codes the decoder's output reaches both rails).  C leaves that conversion undefined; the bank does what the reference's
+ * x86-64 build does: to int32_t truncating toward zero, then the low 16 bits.
+ * State words: bit_rate, last, step_index, oki_byte, history[32], ptr, mark, phase (39).  set_state moves a stream, its
+ * rate included, to another channel; words no call could have left (last outside -2048..2047, step_index outside 0..48,
+ * oki_byte outside a byte, a history word outside int16_t, ptr outside 0..31, negative mark, phase outside 0..3) are refused. */
+typedef struct spangpu_oki_adpcm_s spangpu_oki_adpcm_t;
+
+SPANGPU_API int spangpu_oki_adpcm_create(spangpu_oki_adpcm_t **bank, int device, int n_channels, const int32_t *bit_rates, int n);
+SPANGPU_API void spangpu_oki_adpcm_destroy(spangpu_oki_adpcm_t *bank);
+SPANGPU_API int spangpu_oki_adpcm_channels(const spangpu_oki_adpcm_t *bank);
+SPANGPU_API int spangpu_oki_adpcm_set_stream(spangpu_oki_adpcm_t *bank, void *hip_stream);
+SPANGPU_API int spangpu_oki_adpcm_sync(spangpu_oki_adpcm_t *bank);
+SPANGPU_API int spangpu_oki_adpcm_encode(spangpu_oki_adpcm_t *bank, const void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                         const int32_t *lens, int max_samples, uint8_t *codes, int codes_mem_kind,
+                                         long long codes_stride_bytes, int32_t *bytes_out);
+SPANGPU_API int spangpu_oki_adpcm_decode(spangpu_oki_adpcm_t *bank, const uint8_t *codes, int codes_mem_kind, long long codes_stride_bytes,
+                                         const int32_t *lens, int max_bytes, void *amp, int amp_mem_kind, long long amp_stride_bytes,
+                                         int32_t *samples_out);
+/* bytes (samples) a row must hold for the worst channel of the bank: carried nibble and converter phase included */
+SPANGPU_API long long spangpu_oki_adpcm_encode_capacity(const spangpu_oki_adpcm_t *bank, int samples);
+SPANGPU_API long long spangpu_oki_adpcm_decode_capacity(const spangpu_oki_adpcm_t *bank, int bytes);
+SPANGPU_API const int32_t *spangpu_oki_adpcm_counts_dev(const spangpu_oki_adpcm_t *bank);
+SPANGPU_API int spangpu_oki_adpcm_restart(spangpu_oki_adpcm_t *bank, int channel, int bit_rate);
+SPANGPU_API int spangpu_oki_adpcm_state_words(const spangpu_oki_adpcm_t *bank);
+SPANGPU_API int spangpu_oki_adpcm_get_state(spangpu_oki_adpcm_t *bank, int channel, int32_t *words);
+SPANGPU_API int spangpu_oki_adpcm_set_state(spangpu_oki_adpcm_t *bank, int channel, const int32_t *words);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -1135,6 +1135,62 @@ SPANGPU_PLC_API plc_state_t *plc_init(plc_state_t *s);
 SPANGPU_PLC_API int plc_release(plc_state_t *s);
 SPANGPU_PLC_API int plc_free(plc_state_t *s);
 
+/* ---- IMA and OKI ADPCM (csrc/shim_adpcm.c) --------------------------------------------------------------------------
+ * Reference declarations being replaced:
+ *   ima_adpcm_init, ima_adpcm_release, ima_adpcm_free, ima_adpcm_encode, ima_adpcm_decode   src/spandsp/ima_adpcm.h:74-108
+ *   oki_adpcm_init, oki_adpcm_release, oki_adpcm_free, oki_adpcm_encode, oki_adpcm_decode   src/spandsp/oki_adpcm.h
+ * An object is a one-channel codec bank (spangpu.h, "IMA ADPCM codec banks", "OKI ADPCM codec banks"): plumbing for a caller
+ * that moves over one call at a time; the path for scale is the bank.  oki_adpcm_init() returns NULL for a bit rate other
+ * than 24000 and 32000, as the reference does; ima_adpcm_init() returns NULL for a variant outside the enum (the reference
+ * takes it and then codes nothing); both return NULL without a GPU.  `s` may be the caller's own storage (this header has
+ * the whole structs): the release call then gives up what the object holds on the device and the free call leaves the
+ * storage alone.  A call is one launch up to 2^24 samples or bytes and is cut into launches beyond; a call that cannot be
+ * cut without changing what it makes (IMA with chunk_size == 0: a header per call; VDVI: bits reset and padded per call)
+ * returns 0 beyond that length.  The deviations of the banks hold here too: a length of 0 does nothing and returns 0, an IMA
+ * decode call with chunk_size == 0 and fewer than 4 bytes returns 0, a header's step_index above 88 is taken as 88; and the
+ * 24 kbit/s OKI paths narrow to int16_t as the reference's x86-64 build does (spangpu.h).  A codec call hands its output
+ * back in the same call, so these objects are not members of channel groups.
+ * These names are declared with a macro of their own, as the G.726 ones are: tests/test_adpcm.py holds them against
+ * src/spandsp/ima_adpcm.h and src/spandsp/oki_adpcm.h.
+ */
+#define SPANGPU_ADPCM_API SPANGPU_API
+
+enum
+{
+    IMA_ADPCM_IMA4 = 0,
+    IMA_ADPCM_DVI4 = 1,
+    IMA_ADPCM_VDVI = 2
+};
+
+typedef struct ima_adpcm_state_s ima_adpcm_state_t;
+typedef struct oki_adpcm_state_s oki_adpcm_state_t;
+
+struct ima_adpcm_state_s
+{
+    int variant;
+    int chunk_size;
+    spangpu_ima_adpcm_t *bank;
+    spangpu_object_t obj;
+};
+
+struct oki_adpcm_state_s
+{
+    int bit_rate;
+    spangpu_oki_adpcm_t *bank;
+    spangpu_object_t obj;
+};
+
+SPANGPU_ADPCM_API ima_adpcm_state_t *ima_adpcm_init(ima_adpcm_state_t *s, int variant, int chunk_size);
+SPANGPU_ADPCM_API int ima_adpcm_release(ima_adpcm_state_t *s);
+SPANGPU_ADPCM_API int ima_adpcm_free(ima_adpcm_state_t *s);
+SPANGPU_ADPCM_API int ima_adpcm_encode(ima_adpcm_state_t *s, uint8_t ima_data[], const int16_t amp[], int len);
+SPANGPU_ADPCM_API int ima_adpcm_decode(ima_adpcm_state_t *s, int16_t amp[], const uint8_t ima_data[], int ima_bytes);
+SPANGPU_ADPCM_API oki_adpcm_state_t *oki_adpcm_init(oki_adpcm_state_t *s, int bit_rate);
+SPANGPU_ADPCM_API int oki_adpcm_release(oki_adpcm_state_t *s);
+SPANGPU_ADPCM_API int oki_adpcm_free(oki_adpcm_state_t *s);
+SPANGPU_ADPCM_API int oki_adpcm_encode(oki_adpcm_state_t *s, uint8_t oki_data[], const int16_t amp[], int len);
+SPANGPU_ADPCM_API int oki_adpcm_decode(oki_adpcm_state_t *s, int16_t amp[], const uint8_t oki_data[], int oki_bytes);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -504,6 +504,34 @@ def lib():
             "spangpu_g726_state_words": (ci, [vp]),
             "spangpu_g726_get_state": (ci, [vp, ci, vp]),
             "spangpu_g726_set_state": (ci, [vp, ci, vp]),
+            "spangpu_ima_adpcm_create": (ci, [C.POINTER(vp), ci, ci, vp, vp, ci]),
+            "spangpu_ima_adpcm_destroy": (None, [vp]),
+            "spangpu_ima_adpcm_channels": (ci, [vp]),
+            "spangpu_ima_adpcm_set_stream": (ci, [vp, vp]),
+            "spangpu_ima_adpcm_sync": (ci, [vp]),
+            "spangpu_ima_adpcm_encode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_ima_adpcm_decode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_ima_adpcm_encode_capacity": (ll, [vp, ci]),
+            "spangpu_ima_adpcm_decode_capacity": (ll, [vp, ci]),
+            "spangpu_ima_adpcm_counts_dev": (vp, [vp]),
+            "spangpu_ima_adpcm_restart": (ci, [vp, ci, ci, ci]),
+            "spangpu_ima_adpcm_state_words": (ci, [vp]),
+            "spangpu_ima_adpcm_get_state": (ci, [vp, ci, vp]),
+            "spangpu_ima_adpcm_set_state": (ci, [vp, ci, vp]),
+            "spangpu_oki_adpcm_create": (ci, [C.POINTER(vp), ci, ci, vp, ci]),
+            "spangpu_oki_adpcm_destroy": (None, [vp]),
+            "spangpu_oki_adpcm_channels": (ci, [vp]),
+            "spangpu_oki_adpcm_set_stream": (ci, [vp, vp]),
+            "spangpu_oki_adpcm_sync": (ci, [vp]),
+            "spangpu_oki_adpcm_encode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_oki_adpcm_decode": (ci, [vp, vp, ci, ll, vp, ci, vp, ci, ll, vp]),
+            "spangpu_oki_adpcm_encode_capacity": (ll, [vp, ci]),
+            "spangpu_oki_adpcm_decode_capacity": (ll, [vp, ci]),
+            "spangpu_oki_adpcm_counts_dev": (vp, [vp]),
+            "spangpu_oki_adpcm_restart": (ci, [vp, ci, ci]),
+            "spangpu_oki_adpcm_state_words": (ci, [vp]),
+            "spangpu_oki_adpcm_get_state": (ci, [vp, ci, vp]),
+            "spangpu_oki_adpcm_set_state": (ci, [vp, ci, vp]),
             "spangpu_g722_create": (ci, [C.POINTER(vp), ci, ci, ci, vp, vp, ci]),
             "spangpu_g722_destroy": (None, [vp]),
             "spangpu_g722_channels": (ci, [vp]),
@@ -2379,6 +2407,58 @@ class Gsm0610Bank(_CodecBank):
 
     def restart(self, channel, packing):
         _check(lib().spangpu_gsm0610_restart(self.h, channel, packing))
+
+
+# ---- IMA and OKI ADPCM codec banks (include/spangpu.h "IMA ADPCM codec banks", "OKI ADPCM codec banks") ----
+IMA_ADPCM_IMA4, IMA_ADPCM_DVI4, IMA_ADPCM_VDVI = 0, 1, 2
+
+
+class _AdpcmBank(_CodecBank):
+    """The two small ADPCM families: int16 PCM rows, byte rows of codes."""
+
+    def encode_host(self, pcm, samples, lens=None):
+        """pcm: [n][>= samples] int16 rows.  Returns (codes [n][encode_capacity(samples)] uint8, bytes [n])."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        return self._host("encode", pcm, samples, lens, (self.n, max(1, self.encode_capacity(samples))), np.uint8)
+
+    def decode_host(self, codes, nbytes, lens=None):
+        """codes: [n][>= nbytes] uint8 rows.  Returns (pcm [n][decode_capacity(nbytes)] int16, samples [n])."""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        return self._host("decode", codes, nbytes, lens, (self.n, max(1, self.decode_capacity(nbytes))), np.int16)
+
+
+class ImaAdpcmBank(_AdpcmBank):
+    """N IMA ADPCM codecs (ima_adpcm_encode / ima_adpcm_decode), each channel with its own variant (IMA4, DVI4, VDVI) and
+    chunk size (the two lists are cycled over the channels), state in HBM."""
+    _prefix = "ima_adpcm"
+
+    def __init__(self, n_channels, variants=IMA_ADPCM_DVI4, chunk_sizes=0, device=0):
+        v, k = (np.atleast_1d(np.asarray(x, np.int32)).copy() for x in (variants, chunk_sizes))
+        n = max(len(v), len(k))
+        v, k = (np.resize(x, n).astype(np.int32) for x in (v, k))
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_ima_adpcm_create(C.byref(self.h), device, n_channels, v.ctypes.data, k.ctypes.data, n))
+        self.words = lib().spangpu_ima_adpcm_state_words(self.h)
+
+    def restart(self, channel, variant, chunk_size):
+        _check(lib().spangpu_ima_adpcm_restart(self.h, channel, variant, chunk_size))
+
+
+class OkiAdpcmBank(_AdpcmBank):
+    """N OKI (Dialogic VOX) ADPCM codecs (oki_adpcm_encode / oki_adpcm_decode), each channel at 32000 or 24000 bit/s (the
+    list is cycled over the channels), state in HBM."""
+    _prefix = "oki_adpcm"
+
+    def __init__(self, n_channels, bit_rates=32000, device=0):
+        r = np.atleast_1d(np.asarray(bit_rates, np.int32)).copy()
+        self.n = n_channels
+        self.h = C.c_void_p()
+        _check(lib().spangpu_oki_adpcm_create(C.byref(self.h), device, n_channels, r.ctypes.data, len(r)))
+        self.words = lib().spangpu_oki_adpcm_state_words(self.h)
+
+    def restart(self, channel, bit_rate):
+        _check(lib().spangpu_oki_adpcm_restart(self.h, channel, bit_rate))
 
 
 # ---- packet loss concealment banks (include/spangpu.h "Packet loss concealment banks") -----

@@ -1825,14 +1825,16 @@ def bench_g726(args, dev, stream):
         "cpu_baseline_reason": "g726.c is not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
 
 
-def codec_launches(args, stream, enc, dec, frames, in_stride, n_in, codes, cap, lens, out, out_stride):
-    """encode and decode launches of one bank pair, each between its own events: warm-up, then ticks for half a second"""
+def codec_launches(args, stream, enc, dec, frames, in_stride, n_in, codes, cap, lens, out, out_stride, dec_codes=None):
+    """encode and decode launches of one bank pair, each between its own events: warm-up, then ticks for half a second.
+    dec_codes: rows the decoder reads instead of what the encoder just wrote (packets whose lengths change from tick to tick)"""
     def tick(i, keep):
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e[0].record(stream)
         enc.encode_device(ctypes.c_void_p(frames[i % len(frames)].data_ptr()), in_stride, n_in, ctypes.c_void_p(codes.data_ptr()), cap)
         e[1].record(stream)
-        dec.decode_device(ctypes.c_void_p(codes.data_ptr()), cap, int(lens.max()), ctypes.c_void_p(out.data_ptr()), out_stride, lens=lens)
+        dec.decode_device(ctypes.c_void_p((codes if dec_codes is None else dec_codes).data_ptr()), cap, int(lens.max()),
+                          ctypes.c_void_p(out.data_ptr()), out_stride, lens=lens)
         e[2].record(stream)
         if keep is not None:
             keep.append(e)
@@ -1856,6 +1858,110 @@ def codec_launches(args, stream, enc, dec, frames, in_stride, n_in, codes, cap, 
     return {"steps": ticks, "ms_per_step": dt*1e3/ticks, "window_s": dt,
             "encode": {"avg_launch_us": sum(e_us)/len(e_us), "min_launch_us": min(e_us)},
             "decode": {"avg_launch_us": sum(d_us)/len(d_us), "min_launch_us": min(d_us)}}
+
+
+def bench_adpcm(args, dev, stream, family):
+    """IMA or OKI ADPCM codec banks: encode of every line into HBM and decode from there, each launch between its own pair of
+    events, 65 536 lines x 160 samples.  Once uniform (IMA: DVI4 with a header per tick, as RTP carries it; OKI: 32 kbit/s),
+    once with all configurations mixed within every wave (IMA: 3 variants x 2 chunk_size kinds; OKI: both rates).  In the same
+    session: the G.726 banks' launches (32 kbit/s, linear, right-packed) at the same line count, and the host-to-device copy
+    of the int16 rows a codec path saves most of.  A 64-channel bank pair is held against the committed fixture first, on the
+    configurations whose streams may be cut anywhere.  In the mixed IMA run the decoder takes the packets of the first tick
+    again every tick: a VDVI packet's length changes from tick to tick, and reading the counts back would put a wait
+    between the two launches."""
+    import adpcm_lines as AL
+    import g726_lines as G6
+    from spandsp_amd import engine
+    ima = family == "ima_adpcm"
+    fam = AL.IMA if ima else AL.OKI
+    n_ch = args.channels or 65536
+    line = AL.line()
+    nf = len(line)//FRAME
+
+    def bank(n, configs):
+        a, b = zip(*configs)
+        return engine.ImaAdpcmBank(n, a, b) if ima else engine.OkiAdpcmBank(n, a)
+
+    # ---- the spot check: 64 channels, five frames of the line, against the head of the fixture's streams ----
+    fixture = {(c.kind, c.a, c.b, c.tag): c for c in AL.cases(AL.load(fam))}
+    spot = [(AL.IMA4, AL.CHUNK), (AL.DVI4, AL.CHUNK)] if ima else list(AL.OKI_CONFIGS)
+    enc, dec = bank(64, spot), bank(64, spot)
+    e_at, d_at, checked = [0]*64, [0]*64, 0
+    for k in range(5):
+        pcm = np.tile(line[k*FRAME:(k + 1)*FRAME], (64, 1))
+        codes, counts = enc.encode_host(pcm, FRAME)
+        out, samples = dec.decode_host(codes, int(counts.max()), counts)
+        for c in range(64):
+            cfg = spot[c % len(spot)]
+            want = fixture[(AL.ENCODE,) + cfg + ("line",)].want
+            assert np.array_equal(codes[c, :counts[c]], want[e_at[c]:e_at[c] + counts[c]]), ("encode", c, k)
+            back = fixture[(AL.DECODE,) + cfg + ("line",)].want
+            assert np.array_equal(out[c, :samples[c]], back[d_at[c]:d_at[c] + samples[c]]), ("decode", c, k)
+            e_at[c] += int(counts[c])
+            d_at[c] += int(samples[c])
+            checked += 1
+    enc.close()
+    dec.close()
+
+    idx = np.arange(n_ch)
+    rolled = np.stack([np.roll(line, 40*k)[:nf*FRAME].reshape(nf, FRAME) for k in range(11)])           # [11][nf][160]
+    frames = torch.tensor(rolled[idx % 11], device=dev).permute(1, 0, 2).contiguous()                   # [nf][n_ch][160] int16
+
+    def run(configs, name):
+        enc, dec = bank(n_ch, configs), bank(n_ch, configs)
+        for b in (enc, dec):
+            b.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        cap = (enc.encode_capacity(FRAME) + 15) & ~15
+        codes = torch.zeros(n_ch, cap, dtype=torch.uint8, device=dev)
+        out_stride = (2*dec.decode_capacity(cap) + 15) & ~15
+        out = torch.zeros(n_ch, out_stride, dtype=torch.uint8, device=dev)
+        # the packets of the first tick, and what every channel brings to the decoder
+        first = bank(n_ch, configs)
+        lens = first.encode_device(ctypes.c_void_p(frames[0].data_ptr()), 2*FRAME, FRAME, ctypes.c_void_p(codes.data_ptr()), cap, counts=True)
+        first.close()
+        fixed = codes.clone() if (ima and len(configs) > 1) else None
+        r = codec_launches(args, stream, enc, dec, frames, 2*FRAME, FRAME, codes, cap, lens.astype(np.int32), out, out_stride, dec_codes=fixed)
+        made = torch.zeros(n_ch, dtype=torch.int32, device=dev)
+        ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(made.data_ptr()), ctypes.c_void_p(dec.counts_dev()), ctypes.c_size_t(4*n_ch), 3)
+        got = made.cpu().numpy()
+        assert got.min() >= FRAME - 1 and got.max() <= FRAME + 1, "a decoder did not make a frame of its bytes"
+        enc.close()
+        dec.close()
+        r.update({"name": name, "configurations": len(configs), "code_bytes_per_tick": int(lens.sum()), "pcm_bytes_per_tick": int(n_ch*FRAME*2)})
+        return r
+
+    def run_g726():
+        enc, dec = (engine.G726Bank(n_ch, 32000, G6.LINEAR, G6.PACK_RIGHT) for _ in range(2))
+        for b in (enc, dec):
+            b.set_stream(ctypes.c_void_p(stream.cuda_stream))
+        codes = torch.zeros(n_ch, 80, dtype=torch.uint8, device=dev)
+        out = torch.zeros(n_ch, 2*FRAME, dtype=torch.uint8, device=dev)
+        r = codec_launches(args, stream, enc, dec, frames, 2*FRAME, FRAME, codes, 80, np.full(n_ch, 80, np.int32), out, 2*FRAME)
+        enc.close()
+        dec.close()
+        return r
+
+    uni = run([(AL.DVI4, 0)] if ima else [(32000, 0)], "DVI4, a header per tick" if ima else "32 kbit/s")
+    g726 = run_g726()
+    mix = run(list(AL.CONFIGS[fam]), "%d configurations mixed within every wave" % len(AL.CONFIGS[fam]))
+    h2d_ms = copy_alone_ms(n_ch*FRAME*2, "h2d", dev)
+    value = n_ch*FRAME*2/(uni["ms_per_step"]*1e-3)/1e6
+    return {
+        "metric": "Msamples/s of an %s ADPCM codec bank pair (encode into HBM, decode from HBM; both directions counted)" % ("IMA" if ima else "OKI"),
+        "value": value, "unit": "Msamples/s", "realtime_channels": value*1e6/8000.0/2, "n_gpus": 1, "steps": uni["steps"], "warmup": args.warmup,
+        "ms_per_step": uni["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+        "config": {"workload": "%s codec banks, %d channels x %d-sample frames" % (family, n_ch, FRAME), "channels_per_gpu": n_ch,
+                   "spot_checked_against_fixture": checked},
+        "kernels": {"uniform": uni, "mixed": mix},
+        "yardsticks": {"h2d_copy_of_int16_rows_ms": h2d_ms, "g726_32000_linear_right_packed": g726,
+                       "encode_vs_g726": uni["encode"]["avg_launch_us"]/g726["encode"]["avg_launch_us"],
+                       "decode_vs_g726": uni["decode"]["avg_launch_us"]/g726["decode"]["avg_launch_us"],
+                       "mixed_encode_vs_g726": mix["encode"]["avg_launch_us"]/g726["encode"]["avg_launch_us"],
+                       "mixed_decode_vs_g726": mix["decode"]["avg_launch_us"]/g726["decode"]["avg_launch_us"],
+                       "encode_vs_copy": uni["encode"]["avg_launch_us"]/(h2d_ms*1e3), "decode_vs_copy": uni["decode"]["avg_launch_us"]/(h2d_ms*1e3)},
+        "roofline": None,
+        "cpu_baseline": None,
+        "cpu_baseline_reason": "ima_adpcm.c and oki_adpcm.c are not among the modules oracle/Makefile builds into oracle/_ref, and oracle/ does not change"}
 
 
 def bench_g722(args, dev, stream):
@@ -2540,7 +2646,7 @@ def emit(line, key, channels=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722", "gsm0610", "plc"], default="v29")
+    ap.add_argument("--workload", choices=["v29", "v17", "v27ter", "echo", "echo_group", "mixed", "dtmf_tx", "fsk", "mct", "sigtone", "supertone", "fax_rx", "fax_fe", "fax_tx", "v29_tx", "awgn", "fsk_tx", "mct_tx", "v18", "adsi", "hdlc", "g726", "g722", "gsm0610", "plc", "ima_adpcm", "oki_adpcm"], default="v29")
     ap.add_argument("--channels", type=int, default=0)
     ap.add_argument("--rate", type=int, choices=[16000, 24000, 32000, 40000, 48000, 56000, 64000], default=None,
                     help="g726: the bit rate of the uniform run (32000); g722: the same (64000)")
@@ -2623,6 +2729,10 @@ def main():
     if args.workload == "g726":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         emit(bench_g726(args, dev, stream), "g726", args.channels or None)
+        return
+    if args.workload in ("ima_adpcm", "oki_adpcm"):
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        emit(bench_adpcm(args, dev, stream, args.workload), args.workload, args.channels or None)
         return
     if args.workload == "g722":
         sys.path.insert(0, os.path.join(ROOT, "tests"))
