@@ -872,9 +872,10 @@ SPANGPU_API int spangpu_adsi_rx(spangpu_adsi_rx_t *bank, const int16_t *amp, int
 /* lens[] is host memory; a channel with lens[c] == 0 sits the call out */
 SPANGPU_API int spangpu_adsi_rx_var(spangpu_adsi_rx_t *bank, const int16_t *amp, int mem_kind, const int32_t *lens, int max_samples,
                                     long long stride);
-/* Valid until the next call on this bank.  At 1200 baud a message takes at least 30 bit times, so a call completes at most
-   samples*1200/(8000*30) + 1 of them (spangpu_adsi_rx_msg_capacity()); a count above that is an error (SPANGPU_ERR_STATE),
-   never a record cut short. */
+/* Valid until the next call on this bank.  A message takes at least 30 bits, and the receiver's asynchronous bit clock, put
+   to 50 % by every transition, reports no two bits closer than 4 samples at 1200 baud (a sender's bits are 6.67 apart; a
+   line's need not be), so a call completes at most samples/120 + 1 of them (spangpu_adsi_rx_msg_capacity()); a count above
+   that is an error (SPANGPU_ERR_STATE), never a record cut short, and no line can reach it. */
 SPANGPU_API int spangpu_adsi_rx_messages(spangpu_adsi_rx_t *bank, const uint8_t **bytes, const int32_t **lens, const int32_t **counts);
 SPANGPU_API int spangpu_adsi_rx_msg_capacity(const spangpu_adsi_rx_t *bank, int samples);
 SPANGPU_API int spangpu_adsi_rx_restart(spangpu_adsi_rx_t *bank, int channel, int standard);

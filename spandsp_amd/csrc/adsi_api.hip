@@ -321,7 +321,14 @@ int spangpu_adsi_tx_restart(spangpu_adsi_tx_t *b, int channel, int standard)
 {
     if (b == NULL  ||  !channel_ok(&b->c, channel)  ||  !standard_ok(standard))
         return spangpu_set_error(SPANGPU_ERR_BAD_ARG, "bad arguments (CLASS, CLIP, A-CLIP or J-CLIP)");
-    return tx_edit(b, channel, 0, &standard);
+    // adsi_tx_init() clears the whole object, msg[] with it: a sender that is restarted and then runs without a put sends
+    // msg[0] behind its preamble (adsi.c:129 with msg_len 0), and that byte is 0, not the first of the message before
+    const int rc = tx_edit(b, channel, 0, &standard);
+    if (rc != SPANGPU_OK)
+        return rc;
+    SPG_TRY(hipMemsetAsync(b->msgs + (size_t) channel*kAdsiMsg, 0, kAdsiMsg, b->c.stream));
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
+    return SPANGPU_OK;
 }
 
 int spangpu_adsi_tx(spangpu_adsi_tx_t *b, int mem_kind, int16_t *pcm, long long stride, int samples, int32_t *lens)
@@ -490,9 +497,13 @@ int spangpu_adsi_rx_msg_capacity(const spangpu_adsi_rx_t *b, int samples)
 {
     if (b == NULL  ||  samples < 0)
         return SPANGPU_ERR_BAD_ARG;
-    // the shortest message is 3 bytes of 10 bit times at 1200 baud: samples*1200/(8000*30), and one for the message under
-    // way when the call starts
-    return (int) ((long long) samples*1200/(8000LL*30)) + 1;
+    // The asynchronous bit clock (fsk.c:514-537, fsk_dev.hpp) is put to 50 % by every transition of the demodulator's output
+    // and reports a bit when it reaches 100 %: after a report it stands below one sample's step, so no two bits are closer
+    // than the samples from 50 % to 100 %, ceil(8000*50/1200) = 4 at 1200 baud, not the 6.67 of a sender.  The shortest
+    // message is 3 bytes of 10 bits, so deliveries are at least 30*4 samples apart; and one for the message under way when
+    // the call starts.
+    const int bit_gap = (kFskRateX100/2 + 1200*100 - 1)/(1200*100);
+    return samples/(30*bit_gap) + 1;
 }
 
 static int rx_launch(spangpu_adsi_rx_s *b, const int16_t *amp, int mem_kind, int samples, long long stride)
@@ -596,7 +607,12 @@ int spangpu_adsi_rx_restart(spangpu_adsi_rx_t *b, int channel, int standard)
     rx_words(w, b->c.words, standard);
     const int rc = core_rw_words(&b->c, channel, 0, b->c.words, w, true);
     free(w);
-    return rc;
+    if (rc != SPANGPU_OK)
+        return rc;
+    // (adsi_rx_init() clears msg[] too; the framer never reads what it has not written, spangpu_adsi_rx_get_message() does)
+    SPG_TRY(hipMemsetAsync(b->msgs + (size_t) channel*kAdsiMsg, 0, kAdsiMsg, b->c.stream));
+    SPG_TRY(hipStreamSynchronize(b->c.stream));
+    return SPANGPU_OK;
 }
 
 int spangpu_adsi_rx_get_state(spangpu_adsi_rx_t *b, int channel, int32_t *words)

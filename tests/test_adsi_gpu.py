@@ -194,7 +194,8 @@ def test_receiver_parity_on_the_hand_framed_lines(built, golden, lines):
     # two deliveries in one record, and the bound on a record
     (name, s, x, tick), = lines["wide"]
     wide = engine.AdsiRxBank([s], 3)
-    assert wide.msg_capacity(tick) == tick*1200//(8000*30) + 1 == 6 and wide.msg_capacity(160) == 1
+    # (30 bits a message, and the receiver's bit clock reports no two bits closer than 4 samples: include/spangpu.h)
+    assert wide.msg_capacity(tick) == tick//(30*4) + 1 == 9 and wide.msg_capacity(160) == 160//(30*4) + 1 == 2
     got = run_lines(wide, [AL.calls_of(x, tick).reshape(-1)]*3, -(-len(x)//tick), tick)
     want = fixture_messages(g, name)
     assert len(want) == 2 and want[0][0] == want[1][0] == 1
